@@ -13,6 +13,8 @@ Inputs and targets are resident in HBM before the timed region.  Arithmetic: --m
 bf16 tensors, fp32 accumulation / statistics / master weights; the parity-holding fp32 and bf16x3 figures ride along in the same
 line as `fp32_products` / `bf16x3_products`); no step of the loop is skipped.  Rank 0 prints ONE JSON line, which also carries
 `host_enqueue_ms_per_step` (host time to queue one step, GPU idle at its start) and `gpu_idle_frac` (1 - GPU kernel time / step time).
+The timed steps start from the seeded initial weights whatever the time-bound pre-warm ran; --dump-outputs DIR writes what the
+last timed step computed (dump_outputs) so that two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -83,6 +85,35 @@ def synth_batch(B, seed, dev):
     tseg = torch.stack([(lab == c) for c in range(7)], 1).float()
     theat = torch.rand(B, 14, 184, 184, generator=g) * 0.02
     return x.to(dev), tseg.to(dev), theat.to(dev)
+
+
+DUMP_SEED = 20240611
+# --dump-outputs: most float32 values written per array (a fixed, seeded sample above it); 62e6 bytes in all, under 64 MB
+DUMP_CAP = {'seg': 4_500_000, 'heat': 9_000_000, 'loss': 1, 'params_sample': 1_000_000, 'grads_sample': 1_000_000}
+
+
+def _dump_sample(t, cap, seed):
+    """t as it is, or -- above `cap` values -- its values at `cap` sorted flat indices drawn with a fixed seed (same shape, same
+    indices: two runs or two builds compare element for element)."""
+    t = t.detach()
+    if t.numel() > cap:
+        g = torch.Generator().manual_seed(seed)
+        idx = torch.randperm(t.numel(), generator=g)[:cap].sort().values
+        t = t.reshape(-1)[idx.to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def dump_outputs(path, last, net):
+    """What the last timed step computed, as a caller of the step receives it: the forward's seg and heat maps, the loss, the
+    updated parameters and the gradients of that step (the two concatenated in parameters() order, then sampled).  float32 .npy."""
+    import numpy as np
+    ps = list(net.parameters())
+    arrays = {'seg': last['seg'], 'heat': last['heat'], 'loss': last['loss'],
+              'params_sample': torch.cat([p.detach().reshape(-1) for p in ps]),
+              'grads_sample': torch.cat([p.grad.detach().reshape(-1) for p in ps if p.grad is not None])}
+    os.makedirs(path, exist_ok=True)
+    for i, (name, t) in enumerate(arrays.items()):
+        np.save(os.path.join(path, name + '.npy'), _dump_sample(t, DUMP_CAP[name], DUMP_SEED + i))
 
 
 def op_profile(plan, lib, nat, stream, detail=None):
@@ -422,7 +453,12 @@ def main():
     ap.add_argument('--grad-compress', default=None, choices=['bf16'], help='all-reduce the gradient buckets as bf16 (default: fp32)')
     ap.add_argument('--force-dp', action='store_true',
                     help='keep the collective path on in a one-rank group (self-test of the RCCL path on a 1-GPU box)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy (float32, rank 0): seg, heat, '
+                         'loss, and fixed seeded samples of the updated parameters and of the gradients (62 MB at most)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ and 'RANK' not in os.environ:
         # `python bench.py --gpus N` as typed: become the launcher the contract names (one rank per GPU, rendezvous on
@@ -466,19 +502,37 @@ def main():
     from dfl_amd.util import LateScalars
     late = LateScalars(depth=0 if args.sync_loss else 1)   # as train.py's loop: every loss is read, one step late
 
+    last_out = {} if args.dump_outputs else None
+
     def step():
         opt.zero_grad()
         seg, heat = net(x)
         loss = crit((dfl_amd.center_crop(seg, tseg.shape), dfl_amd.center_crop(heat, theat.shape)), (tseg, theat))
         loss.backward()
         opt.step()
+        if last_out is not None:
+            last_out.update(seg=seg.detach(), heat=heat.detach(), loss=loss.detach())
         return late.push(loss)      # train.py:430 reads the loss of every step; so do we (all of them, see the flush below)
 
+    state = list(net.parameters()) + list(net.buffers())
+    state0 = [t.detach().clone() for t in state]
     prewarm_steps = 0
     t_pre = time.perf_counter()
     while time.perf_counter() - t_pre < args.prewarm_seconds:
         step()
         prewarm_steps += 1
+    if prewarm_steps:
+        # the pre-warm runs for a time, not for a number of steps: put weights, BatchNorm statistics and momentum back to the
+        # seeded start (in place: every recorded address stays valid), so that the timed steps compute the same at every run
+        late.flush()
+        with torch.no_grad():
+            for t, t0_ in zip(state, state0):
+                t.copy_(t0_)
+            for st in opt.state.values():
+                if st.get('momentum_buffer') is not None:
+                    st['momentum_buffer'].zero_()       # a zero buffer is a fresh one: the first update sets it to the gradient
+        net.mark_weights_dirty()
+    del state, state0
     for _ in range(args.warmup):
         step()
     late.flush()
@@ -501,6 +555,8 @@ def main():
         dt = float(tt.item())
     ms_per_step = dt / args.steps * 1e3
     value = B * world * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_out, net)
 
     roofline = None
     extra = {'rccl_ranks': world if (multi and args.backend == 'nccl') else 0, 'prewarm_steps': prewarm_steps,
