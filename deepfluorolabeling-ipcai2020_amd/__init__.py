@@ -12,6 +12,7 @@ from .warm_restarts_lr import WarmRestartLR
 from .sgd import SGD
 from . import parallel
 from .parallel import DataParallel
+from .dataset import DeviceAugment
 
 __all__ = ['UNet', 'DiceLoss2D', 'DiceAndHeatMapLoss2D', 'ncc_2d', 'center_crop', 'get_device', 'WarmRestartLR', 'SGD',
-           'DataParallel', 'parallel']
+           'DataParallel', 'parallel', 'DeviceAugment']

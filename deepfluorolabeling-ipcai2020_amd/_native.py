@@ -174,6 +174,23 @@ class PrepArgs(C.Structure):
                 ('standardize', i32)]
 
 
+AUG_INVERT, AUG_NOISE, AUG_GAMMA, AUG_ERASE = 1, 2, 4, 8          # include/dfl_hip.h: DFL_AUG_*
+AUG_LANDS_NONE, AUG_LANDS_REFERENCE, AUG_LANDS_IN_VIEW = 0, 1, 2
+
+
+class AugmentItem(C.Structure):
+    _fields_ = [('img_map', C.c_double * 6), ('seg_map', C.c_double * 6), ('land_map', C.c_double * 6),
+                ('noise_key', C.c_uint64), ('box_key', C.c_uint64 * 5), ('box', (i32 * 4) * 5), ('noise_sigma', f32),
+                ('gamma', f32), ('row', i32), ('flags', i32), ('n_box', i32), ('reserved', i32)]
+
+
+class AugmentArgs(C.Structure):
+    _fields_ = [('proj', fp), ('labels', fp), ('lands', fp), ('x', fp), ('masks', fp), ('heats', fp), ('lands_out', fp),
+                ('items', fp), ('scratch', fp), ('levels', fp), ('noise', fp),
+                ('n_items', i32), ('B', i32), ('H', i32), ('W', i32), ('pad', i32), ('C', i32), ('L', i32), ('sigma', f32),
+                ('standardize', i32), ('land_rule', i32)]
+
+
 class EstLandsArgs(C.Structure):
     _fields_ = [('heats', fp), ('segs', fp), ('label_for_land', fp), ('rowcol', fp), ('ncc', fp),
                 ('B', i32), ('L', i32), ('H', i32), ('W', i32), ('sigma', f32), ('min_ncc', f32)]
@@ -213,7 +230,7 @@ _KIND_OF = {ConvArgs: OP_CONV, WgradArgs: OP_WGRAD, SumPartialsArgs: OP_SUM_PART
 
 _SIZEOF_ORDER = [ConvArgs, WgradArgs, PackJob, BnFinalizeArgs, ColstatsArgs, BnBwdFinalizeArgs, BnReluBwdArgs,
                  AffineCopyArgs, PoolArgs, HeadFwdArgs, HeadBwdArgs, LossArgs, EnsembleArgs, Op, ReduceJob, PrepArgs, EstLandsArgs,
-                 UpsampleArgs]
+                 UpsampleArgs, AugmentArgs, AugmentItem]
 
 EXPORTS = ['dfl_version', 'dfl_last_error', 'dfl_sizeof', 'dfl_conv2d', 'dfl_conv_grid_m', 'dfl_conv2d_wgrad',
            'dfl_wgrad_suggest_splits', 'dfl_sum_partials', 'dfl_pack_weights', 'dfl_bn_finalize',
@@ -227,7 +244,8 @@ EXPORTS = ['dfl_version', 'dfl_last_error', 'dfl_sizeof', 'dfl_conv2d', 'dfl_con
            'dfl_set_conv_rows_min_tiles', 'dfl_conv_candidates', 'dfl_conv_force_geometry', 'dfl_conv_tune_add',
            'dfl_head_wgrad_blocks', 'dfl_head_scratch_ld_for', 'dfl_head_scratch_off_for', 'dfl_upsample2x_fwd',
            'dfl_upsample2x_bwd', 'dfl_bn_finalize_live', 'dfl_bn_bwd_finalize_live', 'dfl_pack_weights_tiled',
-           'dfl_sgd_pack_tiled', 'dfl_conv2d_pair', 'dfl_conv_pair_ok']
+           'dfl_sgd_pack_tiled', 'dfl_conv2d_pair', 'dfl_conv_pair_ok', 'dfl_augment_batch',
+           'dfl_augment_scratch_bytes']
 
 
 class DflError(RuntimeError):
@@ -267,6 +285,9 @@ def lib():
     L.dfl_prep_scratch_doubles.argtypes = [i32]
     L.dfl_prep_batch.argtypes = [fp, fp]
     L.dfl_est_lands.argtypes = [fp, fp]
+    L.dfl_augment_scratch_bytes.restype = i64
+    L.dfl_augment_scratch_bytes.argtypes = [i32, i32, i32, i32]
+    L.dfl_augment_batch.argtypes = [fp, fp]
     L.dfl_set_math_mode.argtypes = [i32]
     L.dfl_hard_dice.argtypes = [fp, fp, i64, i32, i32, fp, fp, fp]
     L.dfl_sgd_step.argtypes = [fp, fp, fp, i64, f32, f32, f32, f32, i32, i32, fp]

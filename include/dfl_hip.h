@@ -45,7 +45,8 @@ typedef enum {
 int dfl_version(void);
 const char* dfl_last_error(void);
 /* sizeof() of the argument structs, in declaration order (conv, wgrad, pack_job, bn_finalize, colstats,
- * bn_bwd_finalize, bn_relu_bwd, affine_copy, pool, head_fwd, head_bwd, loss, ensemble, op): lets a binding written
+ * bn_bwd_finalize, bn_relu_bwd, affine_copy, pool, head_fwd, head_bwd, loss, ensemble, op, reduce_job, prep,
+ * est_lands, upsample, augment_args, augment_item): lets a binding written
  * in another language verify its struct mirrors at load time.  Returns -1 past the end. */
 int dfl_sizeof(int which);
 
@@ -592,6 +593,61 @@ typedef struct {
 } dfl_prep_args;
 int64_t dfl_prep_scratch_doubles(int32_t B);
 int dfl_prep_batch(const dfl_prep_args* a, dfl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Random augmentation of training items (the reference's RandomDataAugDataSet, train_test_code/dataset.py:107-283):
+ * run dfl_prep_batch on the batch first, then this call overwrites the rows items[k].row of x / masks / heats /
+ * lands_out with the augmented item.  Per item, in order: invert (p = max - p); noise (min/max normalised, + sigma *
+ * N(0,1) with the normals from Philox4x32-10 keyed by noise_key and counted by the pixel index, Box-Muller in fp32,
+ * mapped back); gamma (normalised, ^gamma, mapped back); the affine warp -- normalise, reflect-pad by ceil(H/2)+pad /
+ * ceil(W/2)+pad, quantise to 8 bits by truncation, PIL's 8-bit bilinear Image.transform(AFFINE) with img_map (source =
+ * img_map (x+0.5, y+0.5, 1) in the padded frame), / 255, centre crop to (H+2pad) x (W+2pad), map back; the labels
+ * reflect-padded by ceil(H/2), ceil(W/2) and warped with seg_map by nearest (outside the frame: no label, all masks 0);
+ * the landmarks mapped by land_map (pixel coordinates), inf kept, and dropped (inf) by land_rule; erase: n_box boxes
+ * (row, col, rows, cols) in order, each + 0.2 (max - min of the box) * N(0,1) (key box_key[b], counter the pixel
+ * index of the padded image); then x standardised with the mean and unbiased std of the padded image, one-hot masks,
+ * and heat maps for every finite landmark.  Steps whose flag is clear are skipped (the affine warp always runs).
+ * levels / noise (optional, NULL = skipped) receive the warped 8-bit levels [n_items][H+2pad][W+2pad] and the noise
+ * normals [n_items][H][W] (rows of items without the noise flag are left as they are).
+ * ------------------------------------------------------------------------------------------------------------ */
+#define DFL_AUG_INVERT 1
+#define DFL_AUG_NOISE 2
+#define DFL_AUG_GAMMA 4
+#define DFL_AUG_ERASE 8
+#define DFL_AUG_LANDS_NONE 0        /* no landmark is dropped (the reference without segmentations) */
+#define DFL_AUG_LANDS_REFERENCE 1   /* dataset.py:245-247 as written: x < 0 or x > H-1 or y < 0 or y < C-1 */
+#define DFL_AUG_LANDS_IN_VIEW 2     /* the intended test: outside [0, W-1] x [0, H-1] */
+typedef struct {
+  double img_map[6];            /* projection: padded-frame source of an output pixel centre (PIL's inverse map) */
+  double seg_map[6];            /* labels: the same in the labels' padded frame */
+  double land_map[6];           /* landmarks: forward map in unpadded pixel coordinates */
+  uint64_t noise_key;
+  uint64_t box_key[5];
+  int32_t box[5][4];            /* row, col, rows, cols in the (H+2pad) x (W+2pad) image */
+  float noise_sigma, gamma;
+  int32_t row;                  /* batch row this item overwrites */
+  int32_t flags;                /* DFL_AUG_* */
+  int32_t n_box;                /* 0..5 */
+  int32_t reserved;
+} dfl_augment_item;
+typedef struct {
+  const float* proj;            /* [B][H][W] raw intensities (what dfl_prep_batch read) */
+  const unsigned char* labels;  /* [B][H][W] or NULL */
+  const float* lands;           /* [B][2][L] raw landmarks or NULL */
+  float* x;                     /* [B][1][H+2*pad][W+2*pad] */
+  float* masks;                 /* [B][C][H][W] or NULL */
+  float* heats;                 /* [B][L][H][W] or NULL */
+  float* lands_out;             /* [B][2][L] (a buffer other than lands) */
+  const dfl_augment_item* items;  /* [n_items], device memory */
+  void* scratch;                /* dfl_augment_scratch_bytes(n_items, H, W, pad) bytes, 256-byte aligned */
+  unsigned char* levels;        /* optional, see above */
+  float* noise;                 /* optional, see above */
+  int32_t n_items, B, H, W, pad, C, L;
+  float sigma;                  /* heat-map sigma */
+  int32_t standardize, land_rule;
+} dfl_augment_args;
+int64_t dfl_augment_scratch_bytes(int32_t B, int32_t H, int32_t W, int32_t pad);
+int dfl_augment_batch(const dfl_augment_args* a, dfl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Landmark extraction from predicted heat maps (est_lands_csv.py:96-124, the step after the network in the paper's

@@ -19,8 +19,9 @@ replica, i.e. what the reference computes at that batch size); the global batch 
         --nesterov --wgt-decay 1e-4
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 train.py data.h5 ...
 
-Extensions (not in the reference): --math, --seed, --dist-backend.  Refused loudly: --no-gpu (there is no CPU path) and
---data-aug (PIL-based random augmentation is outside the HIP path).  The data file is the
+Extensions (not in the reference): --math, --seed, --dist-backend.  Refused loudly: --no-gpu (there is no CPU path).
+--data-aug runs the reference's augmentation recipe on the device (dfl_amd.DeviceAugment), its
+draws seeded from --seed (or a fresh system seed, broadcast to every rank).  The data file is the
 reference's HDF5 layout (read by the dependency-free dfl_amd.h5lite) or an .npz with the same dataset names.
 """
 import argparse
@@ -91,7 +92,8 @@ def build_parser():
     a('--unet-padding', action='store_true', help='zero-pad the 3x3 convolutions (output size = input size)')
     a('--unet-no-max-pool', action='store_true', help='down-sample with learned 2x2 stride-2 convolutions')
     a('--unet-block-depth', type=int, default=2, help='3x3 convolutions per block')
-    a('--data-aug', action='store_true', help='(refused: random augmentation is outside the HIP path)')
+    a('--data-aug', action='store_true', help='random augmentation of the training items (the reference\'s recipe, on the '
+                                               'device: dfl_amd.DeviceAugment seeded from --seed)')
     a('--use-lands', action='store_true', help='also learn the landmark heat maps (count read from the data file)')
     a('--heat-coeff', type=float, default=0.5, help='weight of the heat-map loss; Dice gets one minus this')
     a('--dice-valid', action='store_true', help='validate on Dice alone even when training with the heat-map loss')
@@ -206,7 +208,7 @@ class Trainer:
         # (the library default is fp32 products, the 1e-4 parity mode; BASELINE configs[1] is --math bf16s, 2.4x the speed)
         self.say('arithmetic: {}{}'.format(names.get(mode, mode), '' if args.math is not None or mode != 0 else
                                             ' (library default; --math bf16s = bf16 tensors in HBM, see DESIGN.md section 4b)'))
-        self._seed(args.seed)
+        self.seed = self._seed(args.seed)
 
         self.cfg = Settings.from_args(args)
         if args.use_lands:
@@ -231,8 +233,17 @@ class Trainer:
                 if self.train_idx is None or self.valid_idx is None:
                     raise ValueError('--train-valid-split: the checkpoint holds no train/validation split')
         c = self.cfg
+        self.augment = None
         if c['data-aug']:
-            raise NotImplementedError('--data-aug: random data augmentation is outside the HIP path (DESIGN.md section 7)')
+            seed, how = self.seed, 'from --seed'
+            if seed is None:                            # (world > 1 without --seed: _seed drew and broadcast one)
+                seed, how = random.SystemRandom().randrange(1 << 31), 'fresh system seed'
+            elif args.seed is None:
+                how = 'fresh system seed, broadcast to every rank'
+            if self.resumed and args.seed is None:
+                how += '; resumed without --seed: the draws differ from the interrupted run\'s'
+            self.augment = dataset.DeviceAugment(seed, rank=self.rank)
+            self.say('augmentation: {} on the device, seed {} ({})'.format(self.augment, seed, how))
         self._load_data()
         self._build_model(resume)
         self._build_optimizer(resume)
@@ -256,6 +267,7 @@ class Trainer:
         if seed is not None:
             random.seed(seed)
             torch.manual_seed(seed)
+        return seed
 
     def _load_data(self):
         a, c = self.args, self.cfg
@@ -269,7 +281,7 @@ class Trainer:
         got = dataset.get_dataset(a.input_data_file_path, train_pats, num_classes=c['num-classes'],
                                   pad_img_dim=c['pad-img-size'], data_aug=False, train_valid_split=split,
                                   train_valid_idx=(self.train_idx, self.valid_idx), dup_data_w_left_right_flip=False,
-                                  device=self.dev)
+                                  device=self.dev, augment=self.augment)
         if split is not None:
             self.train_ds, self.valid_ds, self.train_idx, self.valid_idx = got
         else:
@@ -473,6 +485,8 @@ class Trainer:
         while True:
             t0 = time.time()
             self.say('Epoch: {:03d}'.format(self.epoch))
+            if self.augment is not None:
+                self.augment.set_epoch(self.epoch)      # the draws of an epoch depend on (seed, epoch, rank) alone
             train_loss = self.train_epoch()
             self.say('  Running validation')
             valid_loss, valid_std = self.validate()
