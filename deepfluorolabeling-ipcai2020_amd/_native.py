@@ -196,6 +196,19 @@ class EstLandsArgs(C.Structure):
                 ('B', i32), ('L', i32), ('H', i32), ('W', i32), ('sigma', f32), ('min_ncc', f32)]
 
 
+OVERLAY_ROUND, OVERLAY_TRUNC = 0, 1                 # include/dfl_hip.h: DFL_OVERLAY_*
+OVERLAY_MAX_COLORS, OVERLAY_MAX_MARKERS, OVERLAY_STAMP_DIM, OVERLAY_SCRATCH_FLOATS = 8, 256, 64, 256
+
+
+class OverlayArgs(C.Structure):
+    _fields_ = [('image', fp), ('labels', fp), ('heat', fp), ('gt_lands', fp), ('est_lands', fp), ('stamp_index', fp),
+                ('stamp_spans', fp), ('scratch', fp), ('out', fp),
+                ('B', i32), ('H', i32), ('W', i32), ('ld_image', i32), ('ld_labels', i32), ('ld_heat', i32),
+                ('n_tint', i32), ('tint_scale', f32), ('tint_add', (f32 * 3) * OVERLAY_MAX_COLORS), ('heat_color', f32 * 3),
+                ('radius', C.c_double), ('n_gt', i32), ('gt_f64', i32), ('n_est', i32), ('cross', i32),
+                ('quant', i32), ('grid', i32)]
+
+
 class UpsampleArgs(C.Structure):
     _fields_ = [('x', fp), ('y', fp), ('N', i32), ('H', i32), ('W', i32), ('C', i32), ('ldx', i32), ('ldy', i32),
                 ('bf16', i32), ('accumulate', i32)]
@@ -230,7 +243,7 @@ _KIND_OF = {ConvArgs: OP_CONV, WgradArgs: OP_WGRAD, SumPartialsArgs: OP_SUM_PART
 
 _SIZEOF_ORDER = [ConvArgs, WgradArgs, PackJob, BnFinalizeArgs, ColstatsArgs, BnBwdFinalizeArgs, BnReluBwdArgs,
                  AffineCopyArgs, PoolArgs, HeadFwdArgs, HeadBwdArgs, LossArgs, EnsembleArgs, Op, ReduceJob, PrepArgs, EstLandsArgs,
-                 UpsampleArgs, AugmentArgs, AugmentItem]
+                 UpsampleArgs, AugmentArgs, AugmentItem, OverlayArgs]
 
 EXPORTS = ['dfl_version', 'dfl_last_error', 'dfl_sizeof', 'dfl_conv2d', 'dfl_conv_grid_m', 'dfl_conv2d_wgrad',
            'dfl_wgrad_suggest_splits', 'dfl_sum_partials', 'dfl_pack_weights', 'dfl_bn_finalize',
@@ -245,7 +258,7 @@ EXPORTS = ['dfl_version', 'dfl_last_error', 'dfl_sizeof', 'dfl_conv2d', 'dfl_con
            'dfl_head_wgrad_blocks', 'dfl_head_scratch_ld_for', 'dfl_head_scratch_off_for', 'dfl_upsample2x_fwd',
            'dfl_upsample2x_bwd', 'dfl_bn_finalize_live', 'dfl_bn_bwd_finalize_live', 'dfl_pack_weights_tiled',
            'dfl_sgd_pack_tiled', 'dfl_conv2d_pair', 'dfl_conv_pair_ok', 'dfl_augment_batch',
-           'dfl_augment_scratch_bytes']
+           'dfl_augment_scratch_bytes', 'dfl_overlay_batch']
 
 
 class DflError(RuntimeError):
@@ -288,6 +301,7 @@ def lib():
     L.dfl_augment_scratch_bytes.restype = i64
     L.dfl_augment_scratch_bytes.argtypes = [i32, i32, i32, i32]
     L.dfl_augment_batch.argtypes = [fp, fp]
+    L.dfl_overlay_batch.argtypes = [fp, fp]
     L.dfl_set_math_mode.argtypes = [i32]
     L.dfl_hard_dice.argtypes = [fp, fp, i64, i32, i32, fp, fp, fp]
     L.dfl_sgd_step.argtypes = [fp, fp, fp, i64, f32, f32, f32, f32, i32, i32, fp]

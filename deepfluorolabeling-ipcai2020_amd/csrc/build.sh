@@ -4,9 +4,12 @@ set -euo pipefail
 here="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 out="$here/../lib"
 mkdir -p "$out"
-srcs=(api.hip conv_gemm.hip conv_rows.hip convp_bf16.hip convq_bf16.hip convn_bf16.hip convs_bf16.hip convs_f32.hip wgradp_bf16.hip wgrad_gemm.hip direct_small.hip bn_elem.hip head.hip loss.hip prep.hip augment.hip upsample.hip)
+srcs=(api.hip conv_gemm.hip conv_rows.hip convp_bf16.hip convq_bf16.hip convn_bf16.hip convs_bf16.hip convs_f32.hip wgradp_bf16.hip wgrad_gemm.hip direct_small.hip bn_elem.hip head.hip loss.hip prep.hip augment.hip upsample.hip overlay.hip)
 objs=()
 pids=()
+# one hipcc per source, at most $MAX_JOBS (default 16) at a time
+jobs_max="${MAX_JOBS:-16}"
+[[ "$jobs_max" =~ ^[1-9][0-9]*$ ]] || jobs_max=16
 for s in "${srcs[@]}"; do
   o="$out/${s%.hip}.o"
   objs+=("$o")
@@ -16,8 +19,13 @@ for s in "${srcs[@]}"; do
     # bn_elem.hip (the batched sums issue their loads earlier: 0.23 -> 0.21 ms per step)
     extra=""
     case "$s" in convp_bf16.hip|convq_bf16.hip|convn_bf16.hip|convs_bf16.hip|convs_f32.hip|wgradp_bf16.hip|bn_elem.hip) extra="-mllvm -amdgpu-sched-strategy=max-ilp";; esac
-    # the augmentation rounds every product and sum separately, as its numpy restatement (tests/aug_ref.py) does
-    case "$s" in augment.hip) extra="-ffp-contract=off";; esac
+    # the augmentation rounds every product and sum separately, as its numpy restatement (tests/aug_ref.py) does, and the
+    # overlays as torch's CPU ops do (an FMA moves results across the 8-bit truncation boundaries)
+    case "$s" in augment.hip|overlay.hip) extra="-ffp-contract=off";; esac
+    if [ "${#pids[@]}" -ge "$jobs_max" ]; then
+      wait "${pids[0]}"
+      pids=("${pids[@]:1}")
+    fi
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $extra "$@" -c "$here/$s" -o "$o" &
     pids+=($!)
   fi

@@ -46,7 +46,7 @@ int dfl_version(void);
 const char* dfl_last_error(void);
 /* sizeof() of the argument structs, in declaration order (conv, wgrad, pack_job, bn_finalize, colstats,
  * bn_bwd_finalize, bn_relu_bwd, affine_copy, pool, head_fwd, head_bwd, loss, ensemble, op, reduce_job, prep,
- * est_lands, upsample, augment_args, augment_item): lets a binding written
+ * est_lands, upsample, augment_args, augment_item, overlay): lets a binding written
  * in another language verify its struct mirrors at load time.  Returns -1 past the end. */
 int dfl_sizeof(int which);
 
@@ -672,6 +672,50 @@ int dfl_est_lands(const dfl_est_lands_args* a, dfl_stream_t stream);
  * occurs in neither.  counts[b][l][3] = (|est==l|, |gt==l|, |both|) for l = 0..C-1 (exact integers). */
 int dfl_hard_dice(const unsigned char* est, const unsigned char* gt, int64_t pixels_per_image, int32_t B, int32_t C,
                   int64_t* counts, double* dice, dfl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Result overlays (overlay_est_ann.py, overlay_est_heat.py, examples_dataset/make_preproc_overlays.py of the reference):
+ * uint8 RGB for a batch of B fp32 images, two launches.  Phase 1: per-image min / max of the image (and of the heat map).
+ * Phase 2, per pixel, every fp32 operation rounded on its own (built with -ffp-contract=off):
+ *   g = (uint8) trunc(((x - min) / (max - min)) * 255)          0 when max == min (the reference divides 0 by 0)
+ *   v = g / 255 in three channels
+ *   1 <= label <= n_tint:  v[c] = tint_scale * v[c] + tint_add[label-1][c]
+ *   heat:  h = heat - hmin, / (hmax - hmin) only if that is > 1e-3;  v[c] = (1 - h) * v[c] + h * heat_color[c]
+ *   out[c] = quant ROUND: (uint8) clamp(v * 255 + 0.5, 0, 255),  TRUNC: (uint8) clamp(v * 255, 0, 255)
+ *   markers overwrite with yellow (255, 255, 0): filled ellipses of Pillow's ImageDraw.ellipse on the box
+ *   (trunc(x - radius), trunc(y - radius), trunc(x + radius), trunc(y + radius)) -- the subtraction / addition in the
+ *   centres' type -- drawn from a stamp table (per box (w, h), per row, the filled column span); crosses of +-cross
+ *   pixels, both ends included.  Both clipped to the image.
+ * grid != 0 writes image k as tile k of torchvision's make_grid(nrow=8, padding=2, pad_value=0) into one canvas
+ * [(H+2)*rows+2][(W+2)*min(8,B)+2][3] (rows = ceil(B/8)), padding and empty tiles zeroed; with B == 1 the canvas is the
+ * image.  Without grid, out is [B][H][W][3].
+ * ------------------------------------------------------------------------------------------------------------ */
+#define DFL_OVERLAY_ROUND 0
+#define DFL_OVERLAY_TRUNC 1
+#define DFL_OVERLAY_MAX_COLORS 8
+#define DFL_OVERLAY_MAX_MARKERS 256       /* per image and kind */
+#define DFL_OVERLAY_STAMP_DIM 64          /* stamp_index is [DIM][DIM]: box (w, h) at w * DIM + h */
+#define DFL_OVERLAY_SCRATCH_FLOATS 256    /* scratch floats per image */
+typedef struct {
+  const float* image;             /* [B][H][ld_image] */
+  const unsigned char* labels;    /* [B][H][ld_labels] or NULL */
+  const float* heat;              /* [B][H][ld_heat] or NULL */
+  const void* gt_lands;           /* [B][n_gt][2] (x = column, y = row), fp32 or fp64 (gt_f64); non-finite = none */
+  const int32_t* est_lands;       /* [B][n_est][2] (column, row); negative = none */
+  const int32_t* stamp_index;     /* [DIM * DIM]: first row of box (w, h) in stamp_spans, -1 = not in the table */
+  const int32_t* stamp_spans;     /* per stamp row: lo | hi << 16 (lo > hi: empty row) */
+  float* scratch;                 /* B * DFL_OVERLAY_SCRATCH_FLOATS floats */
+  unsigned char* out;             /* see above */
+  int32_t B, H, W, ld_image, ld_labels, ld_heat;
+  int32_t n_tint;                 /* labels 1..n_tint are tinted (<= DFL_OVERLAY_MAX_COLORS) */
+  float tint_scale;
+  float tint_add[DFL_OVERLAY_MAX_COLORS][3];
+  float heat_color[3];
+  double radius;                  /* ellipse radius (rounded to fp32 for fp32 centres) */
+  int32_t n_gt, gt_f64, n_est, cross;
+  int32_t quant, grid;
+} dfl_overlay_args;
+int dfl_overlay_batch(const dfl_overlay_args* a, dfl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Product arithmetic of the convolution / weight-gradient GEMMs (fast paths; odd channel counts always use fp32):
