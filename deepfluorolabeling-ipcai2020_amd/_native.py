@@ -209,6 +209,27 @@ class OverlayArgs(C.Structure):
                 ('quant', i32), ('grid', i32)]
 
 
+RESAMPLE_TILE_ROWS, RESAMPLE_TILE_COLS, RESAMPLE_MAX_LDS = 8, 64, 49152     # include/dfl_hip.h: DFL_RESAMPLE_*
+FULLRES_MAX_BOXES, FULLRES_MAX_TEXTS = 64, 2                               # DFL_FULLRES_*
+
+
+class ResamplePlan(C.Structure):
+    _fields_ = [('h_bounds', fp), ('h_coefs', fp), ('v_bounds', fp), ('v_coefs', fp), ('h_in', i32), ('w_in', i32),
+                ('h_out', i32), ('w_out', i32), ('kh', i32), ('kv', i32), ('span_rows', i32), ('span_cols', i32)]
+
+
+class ResampleArgs(C.Structure):
+    _fields_ = [('inp', fp), ('out', fp), ('plan', ResamplePlan), ('B', i32), ('reserved', i32)]
+
+
+class FullresArgs(C.Structure):
+    _fields_ = [('image', fp), ('labels', fp), ('rot180', fp), ('boxes', fp), ('n_boxes', fp), ('texts', fp),
+                ('stamp_spans', fp), ('text_stamps', fp), ('text_masks', fp), ('scratch', fp), ('out', fp),
+                ('plan', ResamplePlan), ('B', i32), ('H', i32), ('W', i32), ('n_tint', i32), ('tint_scale', f32),
+                ('tint_add', (f32 * 3) * OVERLAY_MAX_COLORS), ('n_text_stamps', i32), ('n_stamp_spans', i32),
+                ('tile0', i32), ('n_tiles', i32)]
+
+
 class UpsampleArgs(C.Structure):
     _fields_ = [('x', fp), ('y', fp), ('N', i32), ('H', i32), ('W', i32), ('C', i32), ('ldx', i32), ('ldy', i32),
                 ('bf16', i32), ('accumulate', i32)]
@@ -243,7 +264,7 @@ _KIND_OF = {ConvArgs: OP_CONV, WgradArgs: OP_WGRAD, SumPartialsArgs: OP_SUM_PART
 
 _SIZEOF_ORDER = [ConvArgs, WgradArgs, PackJob, BnFinalizeArgs, ColstatsArgs, BnBwdFinalizeArgs, BnReluBwdArgs,
                  AffineCopyArgs, PoolArgs, HeadFwdArgs, HeadBwdArgs, LossArgs, EnsembleArgs, Op, ReduceJob, PrepArgs, EstLandsArgs,
-                 UpsampleArgs, AugmentArgs, AugmentItem, OverlayArgs]
+                 UpsampleArgs, AugmentArgs, AugmentItem, OverlayArgs, ResamplePlan, ResampleArgs, FullresArgs]
 
 EXPORTS = ['dfl_version', 'dfl_last_error', 'dfl_sizeof', 'dfl_conv2d', 'dfl_conv_grid_m', 'dfl_conv2d_wgrad',
            'dfl_wgrad_suggest_splits', 'dfl_sum_partials', 'dfl_pack_weights', 'dfl_bn_finalize',
@@ -258,7 +279,7 @@ EXPORTS = ['dfl_version', 'dfl_last_error', 'dfl_sizeof', 'dfl_conv2d', 'dfl_con
            'dfl_head_wgrad_blocks', 'dfl_head_scratch_ld_for', 'dfl_head_scratch_off_for', 'dfl_upsample2x_fwd',
            'dfl_upsample2x_bwd', 'dfl_bn_finalize_live', 'dfl_bn_bwd_finalize_live', 'dfl_pack_weights_tiled',
            'dfl_sgd_pack_tiled', 'dfl_conv2d_pair', 'dfl_conv_pair_ok', 'dfl_augment_batch',
-           'dfl_augment_scratch_bytes', 'dfl_overlay_batch']
+           'dfl_augment_scratch_bytes', 'dfl_overlay_batch', 'dfl_resample_bilinear_u8', 'dfl_fullres_overlay']
 
 
 class DflError(RuntimeError):
@@ -302,6 +323,8 @@ def lib():
     L.dfl_augment_scratch_bytes.argtypes = [i32, i32, i32, i32]
     L.dfl_augment_batch.argtypes = [fp, fp]
     L.dfl_overlay_batch.argtypes = [fp, fp]
+    L.dfl_resample_bilinear_u8.argtypes = [fp, fp]
+    L.dfl_fullres_overlay.argtypes = [fp, fp]
     L.dfl_set_math_mode.argtypes = [i32]
     L.dfl_hard_dice.argtypes = [fp, fp, i64, i32, i32, fp, fp, fp]
     L.dfl_sgd_step.argtypes = [fp, fp, fp, i64, f32, f32, f32, f32, i32, i32, fp]

@@ -238,6 +238,12 @@ __global__ void __launch_bounds__(256) ovl_render_kernel(const dfl_overlay_args 
   }
 }
 
+// phase 1 alone, for the full-resolution overlays (overlay_fullres.hip): per-image min / max partials of a.image into
+// a.scratch (OVL_NB slices of 4 floats per image)
+void ovl_launch_minmax(const dfl_overlay_args& a, hipStream_t s) {
+  hipLaunchKernelGGL(ovl_minmax_kernel, dim3(OVL_NB, a.B), dim3(256), 0, s, a);
+}
+
 }  // namespace dfl
 
 extern "C" int dfl_overlay_batch(const dfl_overlay_args* a, dfl_stream_t stream) {

@@ -46,7 +46,7 @@ int dfl_version(void);
 const char* dfl_last_error(void);
 /* sizeof() of the argument structs, in declaration order (conv, wgrad, pack_job, bn_finalize, colstats,
  * bn_bwd_finalize, bn_relu_bwd, affine_copy, pool, head_fwd, head_bwd, loss, ensemble, op, reduce_job, prep,
- * est_lands, upsample, augment_args, augment_item, overlay): lets a binding written
+ * est_lands, upsample, augment_args, augment_item, overlay, resample_plan, resample_args, fullres): lets a binding written
  * in another language verify its struct mirrors at load time.  Returns -1 past the end. */
 int dfl_sizeof(int which);
 
@@ -716,6 +716,72 @@ typedef struct {
   int32_t quant, grid;
 } dfl_overlay_args;
 int dfl_overlay_batch(const dfl_overlay_args* a, dfl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Full-resolution dataset overlays (examples_dataset/make_full_res_overlays.py of the reference) and Pillow's 8-bit
+ * BILINEAR resample (Image.resize(size, Image.BILINEAR) of an RGB image, libImaging/Resample.c).
+ *
+ * Resample plan: per output column (row) the first input column (row) and the tap count, and kh (kv) coefficients in
+ * 22-bit fixed point, computed as Pillow does (support 1 scaled by max(in / out, 1), weights normalised, then
+ * rounded).  Every output pixel, per channel:  t = clip8(2^21 + sum_k in[row][x0 + k] * h_coefs[k])  for each input row
+ * it needs, then  out = clip8(2^21 + sum_k t[y0 + k] * v_coefs[k]),  clip8(s) = clamp(s >> 22, 0, 255).  The kernels
+ * work on output tiles of DFL_RESAMPLE_TILE_ROWS x DFL_RESAMPLE_TILE_COLS; span_rows / span_cols bound the input
+ * rows / columns one tile reads (a tile whose tables ask for more writes nothing).
+ * ------------------------------------------------------------------------------------------------------------ */
+#define DFL_RESAMPLE_TILE_ROWS 8
+#define DFL_RESAMPLE_TILE_COLS 64
+#define DFL_RESAMPLE_MAX_LDS 49152        /* bytes: 4 * (4 * span_cols + DFL_RESAMPLE_TILE_COLS * span_rows) */
+typedef struct {
+  const int32_t* h_bounds;        /* [w_out][2]: first input column, taps */
+  const int32_t* h_coefs;         /* [w_out][kh] */
+  const int32_t* v_bounds;        /* [h_out][2]: first input row, taps */
+  const int32_t* v_coefs;         /* [h_out][kv] */
+  int32_t h_in, w_in, h_out, w_out, kh, kv;
+  int32_t span_rows, span_cols;
+} dfl_resample_plan;
+
+/* uint8 RGB [B][h_in][w_in][3] -> [B][h_out][w_out][3], one launch. */
+typedef struct {
+  const unsigned char* in;
+  unsigned char* out;
+  dfl_resample_plan plan;
+  int32_t B, reserved;
+} dfl_resample_args;
+int dfl_resample_bilinear_u8(const dfl_resample_args* a, dfl_stream_t stream);
+
+/* Full-resolution overlays, reduced and tiled.  Image b (full resolution H x W) is drawn as the reference draws it:
+ * rotated by 180 degrees when rot180[b] (source pixel (H-1-y, W-1-x)), grey level, tint of labels 1..n_tint and the
+ * second 8-bit truncation exactly as dfl_overlay_batch's TRUNC path; then filled yellow ellipses from the ellipse stamp
+ * table of dfl_overlay_args on the boxes[b][k] = (x0, y0, w, h, first stamp row) of image coordinates, k < n_boxes[b];
+ * then up to DFL_FULLRES_MAX_TEXTS text masks texts[b][t] = (x, y, mask) (top-left in image coordinates, index into
+ * text_stamps, -1 = none), in order, each blended with white ink as Pillow blends an L mask m onto RGB:
+ * c = (t + (t >> 8)) >> 8 with t = c * (255 - m) + 255 * m + 128.  text_stamps[i] = (w, h, first byte in text_masks).
+ * The full-resolution RGB image never leaves the chip: the resample of `plan` reduces it to h_out x w_out, written as
+ * tile (tile0 + b) of torchvision's make_grid(nrow=8, padding=2) over n_tiles images into `out`, a canvas of
+ * grid_shape(n_tiles, h_out, w_out) (n_tiles == 1: the image itself).  Padding pixels are not written.
+ * Two launches: dfl_overlay_batch's per-image min / max partials into scratch, then the fused render + resample. */
+#define DFL_FULLRES_MAX_BOXES 64          /* visible landmarks per image */
+#define DFL_FULLRES_MAX_TEXTS 2
+typedef struct {
+  const float* image;             /* [B][H][W] */
+  const unsigned char* labels;    /* [B][H][W] */
+  const int32_t* rot180;          /* [B] */
+  const int32_t* boxes;           /* [B][DFL_FULLRES_MAX_BOXES][5] */
+  const int32_t* n_boxes;         /* [B] */
+  const int32_t* texts;           /* [B][DFL_FULLRES_MAX_TEXTS][3] */
+  const int32_t* stamp_spans;     /* ellipse stamp rows, as dfl_overlay_args */
+  const int32_t* text_stamps;     /* [n_text_stamps][3] */
+  const unsigned char* text_masks;
+  float* scratch;                 /* B * DFL_OVERLAY_SCRATCH_FLOATS floats */
+  unsigned char* out;
+  dfl_resample_plan plan;         /* h_in == H, w_in == W */
+  int32_t B, H, W, n_tint;
+  float tint_scale;
+  float tint_add[DFL_OVERLAY_MAX_COLORS][3];
+  int32_t n_text_stamps, n_stamp_spans;
+  int32_t tile0, n_tiles;
+} dfl_fullres_args;
+int dfl_fullres_overlay(const dfl_fullres_args* a, dfl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Product arithmetic of the convolution / weight-gradient GEMMs (fast paths; odd channel counts always use fp32):
