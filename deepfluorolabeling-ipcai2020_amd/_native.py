@@ -230,6 +230,41 @@ class FullresArgs(C.Structure):
                 ('tile0', i32), ('n_tiles', i32)]
 
 
+MESH_MAX_LABELS, MESH_MC_CELLS, MESH_MAX_ITERS = 4, 4096, 64                # include/dfl_hip.h: DFL_MESH_*
+
+
+class MeshMcArgs(C.Structure):
+    _fields_ = [('volume', fp), ('tri_off', fp), ('tri_edges', fp), ('block_counts', fp), ('block_offsets', fp),
+                ('totals', fp), ('keys', fp), ('nx', i32), ('ny', i32), ('nz', i32), ('n_labels', i32),
+                ('labels', i32 * MESH_MAX_LABELS)]
+
+
+class MeshDecodeArgs(C.Structure):
+    _fields_ = [('keys', fp), ('pos', fp), ('V', i64), ('nx', i32), ('ny', i32)]
+
+
+class MeshTopoArgs(C.Structure):
+    _fields_ = [('tris', fp), ('edge_keys', fp), ('vt_keys', fp), ('T', i64), ('V', i64)]
+
+
+class MeshCsrArgs(C.Structure):
+    _fields_ = [('keys', fp), ('counts', fp), ('col', fp), ('row_ptr', fp), ('fixed', fp), ('nnz', i64), ('div', i64),
+                ('col_div', i64), ('n_rows', i64)]
+
+
+class MeshSmoothArgs(C.Structure):
+    _fields_ = [('x', fp), ('row_ptr', fp), ('col', fp), ('fixed', fp), ('t_a', fp), ('t_b', fp), ('acc', fp), ('out', fp),
+                ('V', i64), ('iterations', i32), ('reserved', i32), ('coef', f32 * (MESH_MAX_ITERS + 1))]
+
+
+class MeshXformArgs(C.Structure):
+    _fields_ = [('x', fp), ('out', fp), ('V', i64), ('M', C.c_double * 16)]
+
+
+class MeshNormalsArgs(C.Structure):
+    _fields_ = [('pos', fp), ('tris', fp), ('vt_ptr', fp), ('vt_tri', fp), ('normals', fp), ('V', i64)]
+
+
 class UpsampleArgs(C.Structure):
     _fields_ = [('x', fp), ('y', fp), ('N', i32), ('H', i32), ('W', i32), ('C', i32), ('ldx', i32), ('ldy', i32),
                 ('bf16', i32), ('accumulate', i32)]
@@ -264,7 +299,8 @@ _KIND_OF = {ConvArgs: OP_CONV, WgradArgs: OP_WGRAD, SumPartialsArgs: OP_SUM_PART
 
 _SIZEOF_ORDER = [ConvArgs, WgradArgs, PackJob, BnFinalizeArgs, ColstatsArgs, BnBwdFinalizeArgs, BnReluBwdArgs,
                  AffineCopyArgs, PoolArgs, HeadFwdArgs, HeadBwdArgs, LossArgs, EnsembleArgs, Op, ReduceJob, PrepArgs, EstLandsArgs,
-                 UpsampleArgs, AugmentArgs, AugmentItem, OverlayArgs, ResamplePlan, ResampleArgs, FullresArgs]
+                 UpsampleArgs, AugmentArgs, AugmentItem, OverlayArgs, ResamplePlan, ResampleArgs, FullresArgs, MeshMcArgs, MeshDecodeArgs,
+                 MeshTopoArgs, MeshCsrArgs, MeshSmoothArgs, MeshXformArgs, MeshNormalsArgs]
 
 EXPORTS = ['dfl_version', 'dfl_last_error', 'dfl_sizeof', 'dfl_conv2d', 'dfl_conv_grid_m', 'dfl_conv2d_wgrad',
            'dfl_wgrad_suggest_splits', 'dfl_sum_partials', 'dfl_pack_weights', 'dfl_bn_finalize',
@@ -279,7 +315,9 @@ EXPORTS = ['dfl_version', 'dfl_last_error', 'dfl_sizeof', 'dfl_conv2d', 'dfl_con
            'dfl_head_wgrad_blocks', 'dfl_head_scratch_ld_for', 'dfl_head_scratch_off_for', 'dfl_upsample2x_fwd',
            'dfl_upsample2x_bwd', 'dfl_bn_finalize_live', 'dfl_bn_bwd_finalize_live', 'dfl_pack_weights_tiled',
            'dfl_sgd_pack_tiled', 'dfl_conv2d_pair', 'dfl_conv_pair_ok', 'dfl_augment_batch',
-           'dfl_augment_scratch_bytes', 'dfl_overlay_batch', 'dfl_resample_bilinear_u8', 'dfl_fullres_overlay']
+           'dfl_augment_scratch_bytes', 'dfl_overlay_batch', 'dfl_resample_bilinear_u8', 'dfl_fullres_overlay',
+           'dfl_mesh_mc_count', 'dfl_mesh_mc_emit', 'dfl_mesh_decode', 'dfl_mesh_topology', 'dfl_mesh_csr', 'dfl_mesh_smooth',
+           'dfl_mesh_transform', 'dfl_mesh_normals']
 
 
 class DflError(RuntimeError):
@@ -325,6 +363,9 @@ def lib():
     L.dfl_overlay_batch.argtypes = [fp, fp]
     L.dfl_resample_bilinear_u8.argtypes = [fp, fp]
     L.dfl_fullres_overlay.argtypes = [fp, fp]
+    for fn in ('dfl_mesh_mc_count', 'dfl_mesh_mc_emit', 'dfl_mesh_decode', 'dfl_mesh_topology', 'dfl_mesh_csr',
+               'dfl_mesh_smooth', 'dfl_mesh_transform', 'dfl_mesh_normals'):
+        getattr(L, fn).argtypes = [fp, fp]
     L.dfl_set_math_mode.argtypes = [i32]
     L.dfl_hard_dice.argtypes = [fp, fp, i64, i32, i32, fp, fp, fp]
     L.dfl_sgd_step.argtypes = [fp, fp, fp, i64, f32, f32, f32, f32, i32, i32, fp]

@@ -1,0 +1,234 @@
+#!/usr/bin/env python3
+"""3D ground truth of one projection of the full-resolution file, as a glTF 2.0 binary scene: the reference's
+examples_dataset/full_res_3d_viz.py, with the bone surfaces built on the GPU (dfl_amd.mesh) and a .glb file in place of
+its interactive VTK window (any glTF viewer can rotate it).
+
+    python examples/full_res_3d_viz.py ipcai_2020_full_res_data.h5 17-1882 0      # writes 17-1882_000.glb
+    python examples/full_res_3d_viz.py full_res.h5 17-1882 0 --out scene.glb
+
+Scene, in the camera projective frame, in mm: the left / right hemipelvis (labels 1 / 2, green / red) and the left /
+right femur (5 / 6, cyan / orange) placed by the ground-truth poses, the 3D landmarks (purple spheres, radius 5), the
+X-ray source (green, radius 10), the detector plane textured with the projection, and for each visible 2D landmark a
+green sphere (radius 2.5) on the detector and a ray from the source to where its 3D landmark projects.  The surfaces
+keep the reference's quirk of sitting 2 voxels off along the volume's y axis.
+Files: the reference's HDF5 (dfl_amd.h5lite) or .npz with the same names as keys.
+"""
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import dfl_amd  # noqa: E402,F401
+from dfl_amd import _native as nat, gltf, mesh  # noqa: E402
+from make_full_res_overlays import Source  # noqa: E402
+
+USAGE = 'Usage: {} <HDF5 full-res data file> <specimen ID> <projection index>'
+# (node name, progress name, label, colour, pose)
+SURFACES = (('left-hemipelvis', 'left hemipelvis', 1, (0.0, 1.0, 0.0), 'cam-to-pelvis-vol'),
+            ('right-hemipelvis', 'right hemipelvis', 2, (1.0, 0.0, 0.0), 'cam-to-pelvis-vol'),
+            ('left-femur', 'left femur', 5, (0.0, 1.0, 1.0), 'cam-to-left-femur-vol'),
+            ('right-femur', 'right femur', 6, (1.0, 0.5, 0.0), 'cam-to-right-femur-vol'))
+LAND3D_COLOR, LAND3D_RADIUS = (0.5, 0.0, 0.5), 5.0
+SOURCE_COLOR, SOURCE_RADIUS = (0.0, 1.0, 0.0), 10.0
+LAND2D_COLOR, LAND2D_RADIUS = (0.0, 1.0, 0.0), 2.5
+RAY_COLOR = (0.0, 1.0, 0.0)
+BACKGROUND = (0.7, 0.8, 1.0)
+SPHERE_RES = 20                     # vtkSphereSource theta / phi resolution
+
+
+def invert_rigid(H):
+    out = np.eye(4)
+    R_inv = H[0:3, 0:3].T
+    out[0:3, 0:3] = R_inv
+    out[0:3, 3] = R_inv @ -H[0:3, 3]
+    return out
+
+
+def flip_y(ny):
+    """vtkImageFlip(FilteredAxis 1, FlipAboutOriginOff) on index coordinates: y -> ny - 1 - y."""
+    F = np.eye(4)
+    F[1, 1], F[1, 3] = -1.0, ny - 1
+    return F
+
+
+def vertex_xform(ny):
+    """create_mesh's vertex_xform: y -> ny + 1 - y (together with flip_y: y -> y + 2)."""
+    X = np.eye(4)
+    X[1, 1], X[1, 3] = -1.0, ny + 1
+    return X
+
+
+def get(src, path):
+    return np.asarray(src.get(path))
+
+
+def host_geometry(src, spec, idx, log=print):
+    """Everything of the scene but the surfaces, in fp64 as the script computes it, plus the volume and the 4x4 that
+    takes each label's marching-cubes index coordinates into the camera projective frame."""
+    g = {}
+    log('reading projection parameters...')
+    extrinsic = get(src, 'proj-params/extrinsic').astype(np.float64)
+    intrinsic = get(src, 'proj-params/intrinsic').astype(np.float64)
+    intrinsic_inv = np.linalg.inv(intrinsic)
+    cols = int(get(src, 'proj-params/num-cols').reshape(-1)[0])
+    rows = int(get(src, 'proj-params/num-rows').reshape(-1)[0])
+    col_sp = float(get(src, 'proj-params/pixel-col-spacing').reshape(-1)[0])
+    row_sp = float(get(src, 'proj-params/pixel-row-spacing').reshape(-1)[0])
+    focal_len = abs((intrinsic[0, 0] * col_sp) + (intrinsic[1, 1] * row_sp)) / 2.0
+
+    def det(x):
+        return (intrinsic_inv * -focal_len) @ np.asarray(x, np.float64).reshape(3)
+
+    g['detector'] = np.stack([det([0, 0, 1]), det([0, rows - 1, 1]), det([cols - 1, rows - 1, 1]), det([cols - 1, 0, 1])])
+    pfx = '{}/projections/{:03d}/'.format(spec, idx)
+    log('reading projection...')
+    pix = get(src, pfx + 'image/pixels')
+    if pix.dtype.kind != 'f':
+        raise nat.DflError('%simage/pixels has dtype %s: a float type expected' % (pfx, pix.dtype))
+    lo, hi = pix.min(), pix.max()
+    with np.errstate(invalid='ignore', divide='ignore'):
+        scaled = 255 * ((pix - lo) / (hi - lo))
+    g['texture'] = np.where(np.isnan(scaled), 0, scaled).astype(np.uint8)       # constant image: 0
+    if g['texture'].shape != (rows, cols):
+        raise nat.DflError('%simage/pixels has shape %s, proj-params say %s' % (pfx, pix.shape, (rows, cols)))
+    log('reading GT poses...')
+    poses = {k: extrinsic @ invert_rigid(get(src, pfx + 'gt-poses/' + k).astype(np.float64))
+             for k in ('cam-to-pelvis-vol', 'cam-to-left-femur-vol', 'cam-to-right-femur-vol')}
+    log('reading GT 2D landmarks...')
+    lands_2d = {}
+    for name in src.children(pfx + 'gt-landmarks'):
+        l2 = get(src, pfx + 'gt-landmarks/' + name).astype(np.float64).reshape(-1)
+        if l2[0] >= 0 and l2[1] >= 0 and l2[0] < cols - 1 and l2[1] < rows - 1:
+            lands_2d[name] = det(np.append(l2, 1))
+    log('reading 3D landmarks...')
+    lands_3d = {}
+    for name in src.children(spec + '/vol-landmarks'):
+        l3 = get(src, spec + '/vol-landmarks/' + name).astype(np.float64).reshape(-1)
+        lands_3d[name] = poses['cam-to-pelvis-vol'] @ np.append(l3, 1)
+    g['lands_3d'] = {k: v[:3] for k, v in lands_3d.items()}
+    g['lands_2d'] = lands_2d
+    g['rays'] = {}
+    for name in lands_2d:
+        p = intrinsic @ lands_3d[name][0:3]
+        g['rays'][name] = det(p / p[2])
+    log('reading 3D segmentation...')
+    img = spec + '/vol-seg/image/'
+    vol = get(src, img + 'pixels')
+    if vol.dtype != np.uint8:
+        raise nat.DflError('%spixels has dtype %s: uint8 expected (the reference reads it as unsigned char)' % (img, vol.dtype))
+    if vol.ndim != 3:
+        raise nat.DflError('%spixels has shape %s: [z, y, x] expected' % (img, vol.shape))
+    spacing = get(src, img + 'spacing').astype(np.float64).reshape(-1)
+    dir_mat = get(src, img + 'dir-mat').astype(np.float64).reshape(3, 3)
+    origin = get(src, img + 'origin').astype(np.float64).reshape(-1)
+    inds_to_phys = np.eye(4)
+    inds_to_phys[:3, :3] = dir_mat * spacing[None, :]
+    inds_to_phys[:3, 3] = origin
+    ny = vol.shape[1]
+    g['volume'] = vol
+    g['surface_xforms'] = [poses[pose] @ inds_to_phys @ vertex_xform(ny) @ flip_y(ny) for _, _, _, _, pose in SURFACES]
+    return g
+
+
+def unit_sphere(res=SPHERE_RES):
+    """(positions [V, 3], triangles [T, 3]) of a unit UV sphere: two poles and res - 1 rings of res points."""
+    phi = np.pi * np.arange(1, res) / res
+    th = 2 * np.pi * np.arange(res) / res
+    ring = np.stack([np.outer(np.sin(phi), np.cos(th)), np.outer(np.sin(phi), np.sin(th)),
+                     np.repeat(np.cos(phi)[:, None], res, 1)], -1).reshape(-1, 3)
+    pos = np.concatenate([[[0, 0, 1]], ring, [[0, 0, -1]]])
+    tris = []
+    ring_at = lambda k, j: 1 + k * res + j % res        # noqa: E731
+    for j in range(res):
+        tris.append((0, ring_at(0, j), ring_at(0, j + 1)))
+        for k in range(res - 2):
+            a, b, c, d = ring_at(k, j), ring_at(k + 1, j), ring_at(k + 1, j + 1), ring_at(k, j + 1)
+            tris += [(a, b, c), (a, c, d)]
+        tris.append((len(pos) - 1, ring_at(res - 2, j + 1), ring_at(res - 2, j)))
+    return pos.astype(np.float32), np.array(tris, np.uint32)
+
+
+def surfaces_on_gpu(g, dev, log=print):
+    """[(positions, normals, triangles) or None] per entry of SURFACES: one marching-cubes pass for all labels, then
+    per label the smoother, the transform into the camera projective frame and the normals."""
+    vol = torch.from_numpy(np.ascontiguousarray(g['volume'])).to(dev)
+    meshes = mesh.label_surfaces(vol, [s[2] for s in SURFACES])
+    out = []
+    for (_, what, _, _, _), (verts, tris), M in zip(SURFACES, meshes, g['surface_xforms']):
+        log('creating {} mesh...'.format(what))
+        if tris.shape[0] == 0:
+            out.append(None)
+            continue
+        xs, undo = mesh.smooth(verts, tris)
+        pos = mesh.transform(xs, M @ undo)
+        nrm = mesh.vertex_normals(pos, tris)
+        out.append((pos.cpu().numpy(), nrm.cpu().numpy(), tris.cpu().numpy()))
+    return out
+
+
+def build_scene(g, surfaces):
+    sc = gltf.Scene()
+    sc.doc['scenes'][0]['extras'] = {'background': list(BACKGROUND)}
+    for (name, _, label, rgb, _), s in zip(SURFACES, surfaces):
+        if s is None:
+            sc.node(name)
+            continue
+        pos, nrm, tris = s
+        sc.node(name, sc.mesh(name, pos, tris.astype(np.uint32), sc.material(name, rgb), normals=nrm))
+    sp, st = unit_sphere()
+    land3d = sc.mesh('sphere-landmark', sp, st, sc.material('landmark', LAND3D_COLOR), normals=sp)
+    green = sc.mesh('sphere-green', sp, st, sc.material('green', SOURCE_COLOR), normals=sp)
+    for name, p in g['lands_3d'].items():
+        sc.node('vol-landmark/' + name, land3d, translation=p, scale=[LAND3D_RADIUS] * 3)
+    sc.node('source', green, translation=[0, 0, 0], scale=[SOURCE_RADIUS] * 3)
+    ray_mat = sc.material('ray', RAY_COLOR)
+    for name, p in g['lands_2d'].items():
+        sc.node('proj-landmark/' + name, green, translation=p, scale=[LAND2D_RADIUS] * 3)
+        line = np.stack([np.zeros(3), g['rays'][name]])
+        sc.node('ray/' + name, sc.mesh('ray/' + name, line, None, ray_mat, mode=gltf.LINES))
+    H, W = g['texture'].shape
+    corners = g['detector']                                   # r0c0, rMc0, rMcN, r0cN as the reference inserts them
+    # texel (r, c) lands on the detector point of index (c, r): corners at texel centres, sampled NEAREST
+    uv = np.array([[0.5 / W, 0.5 / H], [0.5 / W, (H - 0.5) / H], [(W - 0.5) / W, (H - 0.5) / H], [(W - 0.5) / W, 0.5 / H]])
+    n = np.cross(corners[1] - corners[0], corners[2] - corners[0])
+    n = np.tile(n / max(np.linalg.norm(n), 1e-300), (4, 1))
+    tex = np.repeat(g['texture'][:, :, None], 3, 2)
+    det_mat = sc.material('detector', (1.0, 1.0, 1.0), texture_rgb=tex)
+    sc.node('detector', sc.mesh('detector', corners, np.array([[0, 1, 2], [0, 2, 3]], np.uint32), det_mat, normals=n,
+                                texcoords=uv))
+    return sc
+
+
+def main(argv=None):
+    argv = sys.argv[1:] if argv is None else list(argv)
+    out = None
+    if '--out' in argv:
+        k = argv.index('--out')
+        if k + 1 >= len(argv):
+            print('--out needs a path')
+            return 1
+        out = argv[k + 1]
+        del argv[k:k + 2]
+    if len(argv) < 3:
+        print(USAGE.format(os.path.basename(sys.argv[0])))
+        return 1
+    spec, idx = argv[1], int(argv[2])
+    if not torch.cuda.is_available():
+        raise nat.DflError('no GPU visible: the bone surfaces are built by HIP kernels (no CPU path)')
+    src = Source(argv[0])
+    try:
+        g = host_geometry(src, spec, idx)
+    finally:
+        src.close()
+    surfaces = surfaces_on_gpu(g, dfl_amd.get_device())
+    out = out or '{}_{:03d}.glb'.format(spec, idx)
+    build_scene(g, surfaces).write(out)
+    print('wrote {}'.format(out))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -46,7 +46,8 @@ int dfl_version(void);
 const char* dfl_last_error(void);
 /* sizeof() of the argument structs, in declaration order (conv, wgrad, pack_job, bn_finalize, colstats,
  * bn_bwd_finalize, bn_relu_bwd, affine_copy, pool, head_fwd, head_bwd, loss, ensemble, op, reduce_job, prep,
- * est_lands, upsample, augment_args, augment_item, overlay, resample_plan, resample_args, fullres): lets a binding written
+ * est_lands, upsample, augment_args, augment_item, overlay, resample_plan, resample_args, fullres, mesh_mc,
+ * mesh_decode, mesh_topo, mesh_csr, mesh_smooth, mesh_xform, mesh_normals): lets a binding written
  * in another language verify its struct mirrors at load time.  Returns -1 past the end. */
 int dfl_sizeof(int which);
 
@@ -782,6 +783,112 @@ typedef struct {
   int32_t tile0, n_tiles;
 } dfl_fullres_args;
 int dfl_fullres_overlay(const dfl_fullres_args* a, dfl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Bone surfaces of a label volume (examples_dataset/full_res_3d_viz.py of the reference: vtkDiscreteMarchingCubes,
+ * vtkWindowedSincPolyDataFilter, vtkTransformPolyDataFilter), restated in DESIGN.md section 12.
+ *
+ * Discrete marching cubes: volume [nz][ny][nx] uint8, x fastest.  Cell c is the cube between grid points p and
+ * p + (1,1,1), numbered c = x + (nx-1) * (y + (ny-1) * z); the case of a label sets bit i when corner
+ * p + (i & 1, (i >> 1) & 1, (i >> 2) & 1) equals the label.  The case table (data/mc_cases.txt, tools/gen_mc_table.py)
+ * lists triangles as edge triples: tri_off[case] .. tri_off[case + 1] - 1.  Edge e lies along axis a = e >> 2 with
+ * the lower end offset by (e & 1, (e >> 1) & 1) along the two other axes in ascending order; its key is
+ * 3 * (x + nx * (y + ny * z)) + a of that lower end.  Every triangle of label l (labels[l], l < n_labels) becomes
+ * three int64 keys in `keys`, triangles of label 0 first, each label's in ascending cell order and table order within a
+ * cell.  dfl_mesh_mc_count: per block of DFL_MESH_MC_CELLS cells the triangle counts, then one scan kernel writing
+ * block_offsets (first triangle of each block and label) and totals[l] (first triangle of label l; totals[n_labels] =
+ * the sum).  dfl_mesh_mc_emit (after the caller has sized `keys` from totals): the keys.  Cells < 2^31.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define DFL_MESH_MAX_LABELS 4
+#define DFL_MESH_MC_CELLS 4096            /* cells per workgroup of the two passes */
+#define DFL_MESH_MAX_ITERS 64
+typedef struct {
+  const unsigned char* volume;
+  const int32_t* tri_off;         /* [257] */
+  const unsigned char* tri_edges; /* [tri_off[256]][3] */
+  int32_t* block_counts;          /* [n_blocks][DFL_MESH_MAX_LABELS], n_blocks = ceil(cells / DFL_MESH_MC_CELLS) */
+  int64_t* block_offsets;         /* [n_blocks][DFL_MESH_MAX_LABELS] */
+  int64_t* totals;                /* [DFL_MESH_MAX_LABELS + 1] */
+  int64_t* keys;                  /* [totals[n_labels]][3] (emit only) */
+  int32_t nx, ny, nz, n_labels;
+  int32_t labels[DFL_MESH_MAX_LABELS];
+} dfl_mesh_mc_args;
+int dfl_mesh_mc_count(const dfl_mesh_mc_args* a, dfl_stream_t stream);
+int dfl_mesh_mc_emit(const dfl_mesh_mc_args* a, dfl_stream_t stream);
+
+/* Vertex position of each edge key: the midpoint of the grid edge, (x, y, z) + 0.5 along its axis, fp32 [V][3]. */
+typedef struct {
+  const int64_t* keys;
+  float* pos;
+  int64_t V;
+  int32_t nx, ny;
+} dfl_mesh_decode_args;
+int dfl_mesh_decode(const dfl_mesh_decode_args* a, dfl_stream_t stream);
+
+/* Topology keys of a triangle list tris [T][3] (vertex ids < V): edge_keys[6t + ...] = i * V + j for the directed
+ * pairs (a,b) (b,a) (b,c) (c,b) (c,a) (a,c) of triangle t = (a,b,c), and vt_keys[3t + k] = tris[t][k] * 3T + 3t + k.
+ * Either output may be NULL.  Sorted (and, for edge_keys, made unique with counts), they give the CSR lists below. */
+typedef struct {
+  const int32_t* tris;
+  int64_t* edge_keys;
+  int64_t* vt_keys;
+  int64_t T, V;
+} dfl_mesh_topo_args;
+int dfl_mesh_topology(const dfl_mesh_topo_args* a, dfl_stream_t stream);
+
+/* CSR of sorted, distinct keys: row = key / div, col[k] = (key % div) / col_div, row_ptr [n_rows + 1].  With counts
+ * (the number of times each key occurred), fixed[row] = 1 when some count is 1 (an edge of exactly one triangle), else
+ * 0; fixed may be NULL without counts.  nnz >= 1. */
+typedef struct {
+  const int64_t* keys;
+  const int64_t* counts;
+  int32_t* col;
+  int32_t* row_ptr;
+  unsigned char* fixed;
+  int64_t nnz, div, col_div;
+  int64_t n_rows;
+} dfl_mesh_csr_args;
+int dfl_mesh_csr(const dfl_mesh_csr_args* a, dfl_stream_t stream);
+
+/* Windowed-sinc smoothing: out = sum_{n <= iterations} coef[n] T_n with T_0 = x, T_1 = W x, T_{n+1} = 2 W T_n - T_{n-1};
+ * (W y)_i = the mean of y over the neighbours col[row_ptr[i] .. row_ptr[i+1]-1] in that order, or y_i when fixed[i].
+ * Fixed vertices are copied from x bit for bit.  One gather launch per n, fp32; t_a, t_b, acc are [V][4] scratch.
+ * x, out [V][3]. */
+typedef struct {
+  const float* x;
+  const int32_t* row_ptr;
+  const int32_t* col;
+  const unsigned char* fixed;
+  float* t_a;
+  float* t_b;
+  float* acc;
+  float* out;
+  int64_t V;
+  int32_t iterations, reserved;
+  float coef[DFL_MESH_MAX_ITERS + 1];
+} dfl_mesh_smooth_args;
+int dfl_mesh_smooth(const dfl_mesh_smooth_args* a, dfl_stream_t stream);
+
+/* out[v] = fp32(M[0:3, 0:3] x[v] + M[0:3, 3]), evaluated in fp64 (M row-major, affine).  In place is allowed. */
+typedef struct {
+  const float* x;
+  float* out;
+  int64_t V;
+  double M[16];
+} dfl_mesh_xform_args;
+int dfl_mesh_transform(const dfl_mesh_xform_args* a, dfl_stream_t stream);
+
+/* Area-weighted vertex normals: n[v] = unit(sum over the triangles t of v, in vt_tri order, of (b - a) x (c - a)),
+ * fp64 inside, 0 when the sum is 0.  vt_ptr [V + 1], vt_tri [3T] from dfl_mesh_csr over vt_keys. */
+typedef struct {
+  const float* pos;
+  const int32_t* tris;
+  const int32_t* vt_ptr;
+  const int32_t* vt_tri;
+  float* normals;
+  int64_t V;
+} dfl_mesh_normals_args;
+int dfl_mesh_normals(const dfl_mesh_normals_args* a, dfl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Product arithmetic of the convolution / weight-gradient GEMMs (fast paths; odd channel counts always use fp32):
