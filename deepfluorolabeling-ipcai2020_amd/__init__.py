@@ -10,9 +10,10 @@ from .ncc import ncc_2d
 from .util import center_crop, get_device
 from .warm_restarts_lr import WarmRestartLR
 from .sgd import SGD
+from .optim import Adam, RMSprop
 from . import parallel
 from .parallel import DataParallel
 from .dataset import DeviceAugment
 
 __all__ = ['UNet', 'DiceLoss2D', 'DiceAndHeatMapLoss2D', 'ncc_2d', 'center_crop', 'get_device', 'WarmRestartLR', 'SGD',
-           'DataParallel', 'parallel', 'DeviceAugment']
+           'Adam', 'RMSprop', 'DataParallel', 'parallel', 'DeviceAugment']

@@ -50,6 +50,15 @@ class SgdPackArgs(C.Structure):
                 ('momentum', f32), ('weight_decay', f32), ('grad_scale', f32), ('nesterov', i32), ('reserved', i32)]
 
 
+OPTIM_ADAM, OPTIM_RMSPROP = 1, 2             # include/dfl_hip.h: DFL_OPTIM_ADAM, DFL_OPTIM_RMSPROP
+
+
+class OptimPackArgs(C.Structure):
+    _fields_ = [('jobs_dev', fp), ('grad_delta', i64), ('state1_delta', i64), ('state2_delta', i64), ('beta1', C.c_double),
+                ('beta2', C.c_double), ('alpha', C.c_double), ('njobs', i32), ('total_tiles', i32), ('kind', i32), ('lr', f32),
+                ('eps', f32), ('weight_decay', f32), ('grad_scale', f32), ('step_size', f32), ('bc2_sqrt', f32), ('momentum', f32)]
+
+
 class BnLiveJob(C.Structure):
     _fields_ = [('totals', fp), ('gamma', fp), ('beta', fp), ('running_mean', fp), ('running_var', fp), ('num_batches_tracked', fp),
                 ('scale', fp), ('shift', fp), ('save_mean', fp), ('save_invstd', fp), ('count', i64), ('C', i32), ('eps', f32),
@@ -300,7 +309,7 @@ _KIND_OF = {ConvArgs: OP_CONV, WgradArgs: OP_WGRAD, SumPartialsArgs: OP_SUM_PART
 _SIZEOF_ORDER = [ConvArgs, WgradArgs, PackJob, BnFinalizeArgs, ColstatsArgs, BnBwdFinalizeArgs, BnReluBwdArgs,
                  AffineCopyArgs, PoolArgs, HeadFwdArgs, HeadBwdArgs, LossArgs, EnsembleArgs, Op, ReduceJob, PrepArgs, EstLandsArgs,
                  UpsampleArgs, AugmentArgs, AugmentItem, OverlayArgs, ResamplePlan, ResampleArgs, FullresArgs, MeshMcArgs, MeshDecodeArgs,
-                 MeshTopoArgs, MeshCsrArgs, MeshSmoothArgs, MeshXformArgs, MeshNormalsArgs]
+                 MeshTopoArgs, MeshCsrArgs, MeshSmoothArgs, MeshXformArgs, MeshNormalsArgs, OptimPackArgs]
 
 EXPORTS = ['dfl_version', 'dfl_last_error', 'dfl_sizeof', 'dfl_conv2d', 'dfl_conv_grid_m', 'dfl_conv2d_wgrad',
            'dfl_wgrad_suggest_splits', 'dfl_sum_partials', 'dfl_pack_weights', 'dfl_bn_finalize',
@@ -317,7 +326,7 @@ EXPORTS = ['dfl_version', 'dfl_last_error', 'dfl_sizeof', 'dfl_conv2d', 'dfl_con
            'dfl_sgd_pack_tiled', 'dfl_conv2d_pair', 'dfl_conv_pair_ok', 'dfl_augment_batch',
            'dfl_augment_scratch_bytes', 'dfl_overlay_batch', 'dfl_resample_bilinear_u8', 'dfl_fullres_overlay',
            'dfl_mesh_mc_count', 'dfl_mesh_mc_emit', 'dfl_mesh_decode', 'dfl_mesh_topology', 'dfl_mesh_csr', 'dfl_mesh_smooth',
-           'dfl_mesh_transform', 'dfl_mesh_normals']
+           'dfl_mesh_transform', 'dfl_mesh_normals', 'dfl_adam_step', 'dfl_rmsprop_step', 'dfl_optim_pack_tiled']
 
 
 class DflError(RuntimeError):
@@ -369,6 +378,9 @@ def lib():
     L.dfl_set_math_mode.argtypes = [i32]
     L.dfl_hard_dice.argtypes = [fp, fp, i64, i32, i32, fp, fp, fp]
     L.dfl_sgd_step.argtypes = [fp, fp, fp, i64, f32, f32, f32, f32, i32, i32, fp]
+    L.dfl_adam_step.argtypes = [fp, fp, fp, fp, i64, f32, C.c_double, C.c_double, f32, f32, f32, f32, f32, fp]
+    L.dfl_rmsprop_step.argtypes = [fp, fp, fp, fp, i64, f32, C.c_double, f32, f32, f32, f32, fp]
+    L.dfl_optim_pack_tiled.argtypes = [fp, fp]
     L.dfl_exec.argtypes = [fp, i32, fp]
     L.dfl_exec_timed.argtypes = [fp, i32, fp, fp]
     L.dfl_set_conv_rows_min_tiles.argtypes = [i32]

@@ -2,7 +2,7 @@
 // affine copy, 2x2 max-pool, weight re-layout, SGD.  All operate on NHWC rows [M][C] with float4 (= 4 channels)
 // accesses when C, ld and the pointers allow it, 4-byte accesses otherwise.
 // Reference behaviour: nn.BatchNorm2d (train_test_code/unet.py:215,222), nn.ReLU (:213,220), F.max_pool2d (:169),
-// torch.optim.SGD (train.py:333-334).  Contracts: include/dfl_hip.h.
+// torch.optim.SGD (train.py:333-334), torch.optim.Adam / RMSprop (train.py:331-352).  Contracts: include/dfl_hip.h.
 #include "common.h"
 
 namespace dfl {
@@ -1051,6 +1051,117 @@ __global__ void __launch_bounds__(256) sgd_pack_tiles_kernel(dfl_sgd_pack_args a
   if (j.dst2 != nullptr) pack_emit(tile, j.dst2, j.kind2, j.flip2, j.split2, A, B, Cc, a0, b0);
 }
 
+// ------------------------------------------------------------------------------------------------ Adam, RMSprop
+// torch's _multi_tensor_adam / _multi_tensor_rmsprop (the reference's --optim adam|rmsprop, train.py:331-352) one foreach op at
+// a time, in torch's order, each result rounded to fp32.  No contraction into FMAs: the flat kernel and the tiled one then give
+// the same bits whatever the compiler schedules around the inlined rule.  The (1 - beta) factors are formed in double on the host.
+struct AdamRule {
+  float eps, wd, gscale, beta2, step_size, bc2_sqrt, w1, omb2;   // w1 = 1 - beta1 (the lerp weight), omb2 = 1 - beta2
+  static constexpr bool always2 = true;
+  __device__ __forceinline__ float operator()(float w, float gr, float* m, float* v, bool) const {
+#pragma clang fp contract(off)
+    const float g = gr * gscale + wd * w;                      // _foreach_add(grads, params, alpha=wd)
+    const float d = g - *m;                                    // _foreach_lerp_(exp_avgs, grads, 1 - beta1): at::lerp
+    *m = (fabsf(w1) < 0.5f) ? *m + w1 * d : g - d * (1.f - w1);
+    *v = *v * beta2 + (omb2 * g) * g;                          // _foreach_mul_(beta2); _foreach_addcmul_(g, g, 1 - beta2)
+    const float den = sqrtf(*v) / bc2_sqrt + eps;              // sqrt; _foreach_div_(bc2_sqrt); _foreach_add_(eps)
+    return w - step_size * (*m / den);                         // _foreach_addcdiv_(params, exp_avgs, den, -step_size)
+  }
+};
+
+struct RmspropRule {
+  float eps, wd, gscale, alpha, oma, lr, mom;                  // oma = 1 - alpha
+  static constexpr bool always2 = false;
+  __device__ __forceinline__ float operator()(float w, float gr, float* sq, float* buf, bool hasb) const {
+#pragma clang fp contract(off)
+    const float g = gr * gscale + wd * w;                      // _foreach_add(grads, params, alpha=wd)
+    *sq = *sq * alpha + (oma * g) * g;                         // _foreach_mul_(alpha); _foreach_addcmul_(g, g, 1 - alpha)
+    const float avg = sqrtf(*sq) + eps;
+    if (hasb) {
+      *buf = *buf * mom + g / avg;                             // _foreach_mul_(momentum); _foreach_addcdiv_(buf, g, avg)
+      return w + -lr * *buf;                                   // _foreach_add_(params, buf, alpha=-lr)
+    }
+    return w + -lr * (g / avg);                                // _foreach_addcdiv_(params, g, avg, -lr)
+  }
+};
+
+template <class Rule>
+__global__ void __launch_bounds__(256) optim_kernel(float* __restrict__ p, const float* __restrict__ grad, float* __restrict__ s1,
+                                                   float* __restrict__ s2, int64_t n, Rule r) {
+  const bool has2 = Rule::always2 || s2 != nullptr;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    float a = s1[i], b = has2 ? s2[i] : 0.f;
+    p[i] = r(p[i], grad[i], &a, &b, has2);
+    s1[i] = a;
+    if (has2) s2[i] = b;
+  }
+}
+
+// dfl_optim_pack_tiled: sgd_pack_tiles_kernel with an Adam / RMSprop update -- the same jobs, tiles and layouts; the tile is
+// updated with 16-byte accesses to the master and both state arenas, then emitted from LDS.
+template <class Rule>
+__global__ void __launch_bounds__(256) optim_pack_tiles_kernel(dfl_optim_pack_args a, Rule r) {
+  __shared__ float tile[PK_T][PK_T * PK_CMAX + 1];
+  const dfl_pack_job* __restrict__ jobs = a.jobs_dev;
+  int lo = 0, hi = a.njobs - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (jobs[mid].first_tile <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
+  }
+  const dfl_pack_job j = jobs[lo];
+  const int tidx = (int)blockIdx.x - j.first_tile;
+  float* __restrict__ P = const_cast<float*>(j.src);
+  const float* __restrict__ G = j.src + a.grad_delta;
+  float* __restrict__ S1 = const_cast<float*>(j.src) + a.state1_delta;
+  float* __restrict__ S2 = const_cast<float*>(j.src) + a.state2_delta;
+  const bool has2 = Rule::always2 || a.momentum != 0.f;
+  if (j.kind == DFL_PACK_PLAIN) {
+    const int64_t i0 = (int64_t)tidx * DFL_SGD_PLAIN_TILE;
+    const int64_t i1 = min((int64_t)j.A, i0 + DFL_SGD_PLAIN_TILE);
+    for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
+      float s = S1[i], b = has2 ? S2[i] : 0.f;
+      P[i] = r(P[i], G[i], &s, &b, has2);
+      S1[i] = s;
+      if (has2) S2[i] = b;
+    }
+    return;
+  }
+  const int A = j.A, B = j.B, Cc = j.C;
+  const int tb = B / PK_T;
+  const int a0 = (tidx / tb) * PK_T, b0 = (tidx % tb) * PK_T;
+  const int run4 = 8 * Cc;
+  for (int e = threadIdx.x; e < PK_T * run4; e += 256) {
+    const int ar = e / run4, q4 = e - ar * run4;
+    const int64_t o = ((int64_t)(a0 + ar) * B + b0) * Cc + 4 * q4;
+    const float4 w = *reinterpret_cast<const float4*>(P + o);
+    const float4 g = *reinterpret_cast<const float4*>(G + o);
+    float4 s = *reinterpret_cast<const float4*>(S1 + o);
+    float4 b = has2 ? *reinterpret_cast<const float4*>(S2 + o) : make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 v;
+    v.x = r(w.x, g.x, &s.x, &b.x, has2);
+    v.y = r(w.y, g.y, &s.y, &b.y, has2);
+    v.z = r(w.z, g.z, &s.z, &b.z, has2);
+    v.w = r(w.w, g.w, &s.w, &b.w, has2);
+    *reinterpret_cast<float4*>(P + o) = v;
+    *reinterpret_cast<float4*>(S1 + o) = s;
+    if (has2) *reinterpret_cast<float4*>(S2 + o) = b;
+    float* t = &tile[ar][4 * q4];
+    t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
+  }
+  __syncthreads();
+  pack_emit(tile, j.dst, j.kind, j.flip, j.split, A, B, Cc, a0, b0);
+  if (j.dst2 != nullptr) pack_emit(tile, j.dst2, j.kind2, j.flip2, j.split2, A, B, Cc, a0, b0);
+}
+
+static AdamRule adam_rule(double beta1, double beta2, float eps, float wd, float step_size, float bc2_sqrt, float gscale) {
+  return AdamRule{eps, wd, gscale, (float)beta2, step_size, bc2_sqrt, (float)(1.0 - beta1), (float)(1.0 - beta2)};
+}
+
+static RmspropRule rmsprop_rule(float lr, double alpha, float eps, float wd, float mom, float gscale) {
+  return RmspropRule{eps, wd, gscale, (float)alpha, (float)(1.0 - alpha), lr, mom};
+}
+
 static unsigned stream_grid(int64_t units) {
   int64_t b = ceil_div(units, 256);
   if (b > 8192) b = 8192;
@@ -1284,4 +1395,68 @@ extern "C" int dfl_sgd_step(float* p, const float* grad, float* momentum_buf, in
   hipLaunchKernelGGL(sgd_kernel, dim3(stream_grid(n)), dim3(256), 0, static_cast<hipStream_t>(stream), p, grad,
                      momentum_buf, n, lr, momentum, weight_decay, grad_scale, (int)nesterov, (int)first_step);
   return check_launch("dfl_sgd_step");
+}
+
+// ---- Adam / RMSprop entry points: every coefficient is checked before anything is launched
+static bool adam_coefs_ok(float lr, double beta1, double beta2, float eps, float wd, float step_size, float bc2_sqrt) {
+  // step_size = lr / (1 - beta1^t) >= lr and bc2_sqrt = sqrt(1 - beta2^t) in (0, 1] for every step count t >= 1
+  return lr >= 0.f && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.f && wd >= 0.f &&
+         step_size >= lr && step_size < INFINITY && bc2_sqrt > 0.f && bc2_sqrt <= 1.f;
+}
+
+static bool rmsprop_coefs_ok(float lr, double alpha, float eps, float wd, float mom) {
+  return lr >= 0.f && lr < INFINITY && alpha >= 0.0 && alpha < INFINITY && eps >= 0.f && wd >= 0.f && wd < INFINITY &&
+         mom >= 0.f && mom < INFINITY;
+}
+
+extern "C" int dfl_adam_step(float* p, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, double beta1,
+                             double beta2, float eps, float weight_decay, float step_size, float bc2_sqrt, float grad_scale,
+                             dfl_stream_t stream) {
+  DFL_REQUIRE(p && grad && exp_avg && exp_avg_sq && n > 0, "dfl_adam_step: bad args (NULL tensor or n <= 0)");
+  DFL_REQUIRE(exp_avg != exp_avg_sq && exp_avg != p && exp_avg_sq != p, "dfl_adam_step: state tensors alias each other or p");
+  DFL_REQUIRE(adam_coefs_ok(lr, beta1, beta2, eps, weight_decay, step_size, bc2_sqrt),
+              "dfl_adam_step: bad coefficients (need 0 <= beta < 1, lr, eps, weight_decay >= 0, step_size = lr/(1-beta1^t) "
+              ">= lr, bc2_sqrt = sqrt(1-beta2^t) in (0, 1])");
+  hipLaunchKernelGGL(optim_kernel<AdamRule>, dim3(stream_grid(n)), dim3(256), 0, static_cast<hipStream_t>(stream), p, grad, exp_avg,
+                     exp_avg_sq, n, adam_rule(beta1, beta2, eps, weight_decay, step_size, bc2_sqrt, grad_scale));
+  return check_launch("dfl_adam_step");
+}
+
+extern "C" int dfl_rmsprop_step(float* p, const float* grad, float* square_avg, float* momentum_buf, int64_t n, float lr,
+                                double alpha, float eps, float weight_decay, float momentum, float grad_scale,
+                                dfl_stream_t stream) {
+  DFL_REQUIRE(p && grad && square_avg && n > 0, "dfl_rmsprop_step: bad args (NULL tensor or n <= 0)");
+  DFL_REQUIRE(rmsprop_coefs_ok(lr, alpha, eps, weight_decay, momentum),
+              "dfl_rmsprop_step: bad coefficients (lr, alpha, eps, weight_decay, momentum must be finite and >= 0)");
+  DFL_REQUIRE((momentum == 0.f) == (momentum_buf == nullptr), "dfl_rmsprop_step: momentum buffer required when (and only when) momentum > 0");
+  DFL_REQUIRE(square_avg != p && (momentum_buf == nullptr || (momentum_buf != p && momentum_buf != square_avg)),
+              "dfl_rmsprop_step: state tensors alias each other or p");
+  hipLaunchKernelGGL(optim_kernel<RmspropRule>, dim3(stream_grid(n)), dim3(256), 0, static_cast<hipStream_t>(stream), p, grad,
+                     square_avg, momentum_buf, n, rmsprop_rule(lr, alpha, eps, weight_decay, momentum, grad_scale));
+  return check_launch("dfl_rmsprop_step");
+}
+
+extern "C" int dfl_optim_pack_tiled(const dfl_optim_pack_args* a, dfl_stream_t stream) {
+  DFL_REQUIRE(a != nullptr && a->jobs_dev != nullptr && a->njobs > 0 && a->total_tiles > 0, "dfl_optim_pack_tiled: empty job list");
+  DFL_REQUIRE(a->kind == DFL_OPTIM_ADAM || a->kind == DFL_OPTIM_RMSPROP, "dfl_optim_pack_tiled: kind must be DFL_OPTIM_ADAM or DFL_OPTIM_RMSPROP");
+  const bool has2 = a->kind == DFL_OPTIM_ADAM || a->momentum != 0.f;
+  DFL_REQUIRE(a->grad_delta % 4 == 0 && a->state1_delta % 4 == 0 && (!has2 || a->state2_delta % 4 == 0),
+              "dfl_optim_pack_tiled: gradient / state arenas not 16-byte congruent with the parameters");
+  DFL_REQUIRE(a->grad_delta != 0 && a->state1_delta != 0 && a->state1_delta != a->grad_delta &&
+              (!has2 || (a->state2_delta != 0 && a->state2_delta != a->grad_delta && a->state2_delta != a->state1_delta)),
+              "dfl_optim_pack_tiled: parameter, gradient and state arenas overlap (equal deltas)");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (a->kind == DFL_OPTIM_ADAM) {
+    DFL_REQUIRE(adam_coefs_ok(a->lr, a->beta1, a->beta2, a->eps, a->weight_decay, a->step_size, a->bc2_sqrt),
+                "dfl_optim_pack_tiled: bad Adam coefficients (need 0 <= beta < 1, lr, eps, weight_decay >= 0, step_size >= lr, "
+                "bc2_sqrt in (0, 1])");
+    hipLaunchKernelGGL(optim_pack_tiles_kernel<AdamRule>, dim3((unsigned)a->total_tiles), dim3(256), 0, s, *a,
+                       adam_rule(a->beta1, a->beta2, a->eps, a->weight_decay, a->step_size, a->bc2_sqrt, a->grad_scale));
+  } else {
+    DFL_REQUIRE(rmsprop_coefs_ok(a->lr, a->alpha, a->eps, a->weight_decay, a->momentum),
+                "dfl_optim_pack_tiled: bad RMSprop coefficients (lr, alpha, eps, weight_decay, momentum must be finite and >= 0)");
+    hipLaunchKernelGGL(optim_pack_tiles_kernel<RmspropRule>, dim3((unsigned)a->total_tiles), dim3(256), 0, s, *a,
+                       rmsprop_rule(a->lr, a->alpha, a->eps, a->weight_decay, a->momentum, a->grad_scale));
+  }
+  return check_launch("dfl_optim_pack_tiled");
 }

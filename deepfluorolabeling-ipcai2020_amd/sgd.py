@@ -96,41 +96,10 @@ class SGD(Optimizer):
         if gdelta % 16 or bdelta % 16:
             return None
         key = (id(plan), gdelta, bdelta, tuple(p.data_ptr() for p in live))
-        hit = self._fused_cache.get(key)
-        if hit is not None and hit[0]() is plan:
-            return (plan,) + hit[1:]
-        raw, ntiled, tiles, tiled_src = plan._tiled_host
-        ptrs = {p.data_ptr(): p.numel() for p in live}
-        if any(ptrs.get(s) != n for s, n in tiled_src.items()):
-            return None                      # a tiled parameter without a gradient (or a view of one): not this path
-        plain, cur = [], None                # what has no tiled layout, adjacent slices merged (alignment padding absorbed)
-        flat = getattr(net, '_param_flat', None)
-        lo = flat.data_ptr() if flat is not None else 0
-        hi = lo + 4 * flat.numel() if flat is not None else 0
-
-        def in_arena(ptr):                   # only slices of the network's own flat arena are merged across a gap
-            return lo <= ptr < hi
-        for p in live:
-            pp, n = p.data_ptr(), p.numel()
-            if pp in tiled_src:
-                cur = None
-                continue
-            if cur is not None and 0 <= pp - cur[0] - 4 * cur[1] <= 12 and in_arena(cur[0]) and in_arena(pp):
-                cur[1] = (pp - cur[0]) // 4 + n          # (the gap is the arena's alignment padding: nobody else's memory)
-            else:
-                cur = [pp, n]
-                plain.append(cur)
-        arr = (nat.PackJob * (ntiled + len(plain)))()
-        C.memmove(arr, raw, len(raw))
-        for i, (pp, n) in enumerate(plain):
-            a = arr[ntiled + i]
-            a.src, a.A, a.B, a.C, a.kind, a.first_tile = pp, n, 1, 1, nat.PACK_PLAIN, tiles
-            tiles += -(-n // nat.SGD_PLAIN_TILE)
-        jobs_dev = torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(live[0].device)
-        if len(self._fused_cache) >= 4:
-            self._fused_cache.clear()
-        self._fused_cache[key] = (weakref.ref(plan), jobs_dev, len(arr), tiles, gdelta // 4, bdelta // 4)
-        return (plan,) + self._fused_cache[key][1:]
+        jl = tiled_job_list(self._fused_cache, net, plan, live, key)
+        if jl is None:
+            return None
+        return (plan,) + jl + (gdelta // 4, bdelta // 4)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -184,3 +153,44 @@ class SGD(Optimizer):
             if net is not None:
                 net.prepack()            # next step's weight re-layout starts now, behind the update kernels
         return loss
+
+
+def tiled_job_list(cache, net, plan, live, key):
+    """(device job list, jobs, tiles) of an update inside the tiled weight re-layout of `plan` (dfl_sgd_pack_tiled,
+    dfl_optim_pack_tiled), or None: every tiled parameter must be among `live`.  The tiled jobs of the plan, then one
+    DFL_PACK_PLAIN job per stretch of the other live parameters.  Cached in `cache` under `key` while `plan` lives."""
+    hit = cache.get(key)
+    if hit is not None and hit[0]() is plan:
+        return hit[1:]
+    raw, ntiled, tiles, tiled_src = plan._tiled_host
+    ptrs = {p.data_ptr(): p.numel() for p in live}
+    if any(ptrs.get(s) != n for s, n in tiled_src.items()):
+        return None                      # a tiled parameter without a gradient (or a view of one): not this path
+    plain, cur = [], None                # what has no tiled layout, adjacent slices merged (alignment padding absorbed)
+    flat = getattr(net, '_param_flat', None)
+    lo = flat.data_ptr() if flat is not None else 0
+    hi = lo + 4 * flat.numel() if flat is not None else 0
+
+    def in_arena(ptr):                   # only slices of the network's own flat arena are merged across a gap (ADVICE r04)
+        return lo <= ptr < hi
+    for p in live:
+        pp, n = p.data_ptr(), p.numel()
+        if pp in tiled_src:
+            cur = None
+            continue
+        if cur is not None and 0 <= pp - cur[0] - 4 * cur[1] <= 12 and in_arena(cur[0]) and in_arena(pp):
+            cur[1] = (pp - cur[0]) // 4 + n          # (the gap is the arena's alignment padding: nobody else's memory)
+        else:
+            cur = [pp, n]
+            plain.append(cur)
+    arr = (nat.PackJob * (ntiled + len(plain)))()
+    C.memmove(arr, raw, len(raw))
+    for i, (pp, n) in enumerate(plain):
+        a = arr[ntiled + i]
+        a.src, a.A, a.B, a.C, a.kind, a.first_tile = pp, n, 1, 1, nat.PACK_PLAIN, tiles
+        tiles += -(-n // nat.SGD_PLAIN_TILE)
+    jobs_dev = torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(live[0].device)
+    if len(cache) >= 4:
+        cache.clear()
+    cache[key] = (weakref.ref(plan), jobs_dev, len(arr), tiles)
+    return cache[key][1:]

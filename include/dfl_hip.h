@@ -47,7 +47,7 @@ const char* dfl_last_error(void);
 /* sizeof() of the argument structs, in declaration order (conv, wgrad, pack_job, bn_finalize, colstats,
  * bn_bwd_finalize, bn_relu_bwd, affine_copy, pool, head_fwd, head_bwd, loss, ensemble, op, reduce_job, prep,
  * est_lands, upsample, augment_args, augment_item, overlay, resample_plan, resample_args, fullres, mesh_mc,
- * mesh_decode, mesh_topo, mesh_csr, mesh_smooth, mesh_xform, mesh_normals): lets a binding written
+ * mesh_decode, mesh_topo, mesh_csr, mesh_smooth, mesh_xform, mesh_normals, optim_pack): lets a binding written
  * in another language verify its struct mirrors at load time.  Returns -1 past the end. */
 int dfl_sizeof(int which);
 
@@ -570,6 +570,46 @@ typedef struct {
   int32_t nesterov, reserved;
 } dfl_sgd_pack_args;
 int dfl_sgd_pack_tiled(const dfl_sgd_pack_args* a, dfl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Fused multi-tensor Adam and RMSprop steps (torch.optim.Adam / torch.optim.RMSprop as configured by the reference's
+ * train.py:331-352 --optim adam|rmsprop), over a flat arena like dfl_sgd_step; the arithmetic of torch's
+ * _multi_tensor_adam (amsgrad, maximize off; coupled L2 weight decay) and _multi_tensor_rmsprop (centered off):
+ *   Adam:    g = grad*grad_scale + wd*p ; m = lerp(m, g, 1-beta1) ; v = beta2*v + (1-beta2)*g*g ;
+ *            p -= step_size * m / (sqrt(v)/bc2_sqrt + eps)
+ *            with, for step count t (after its increment), step_size = lr/(1-beta1^t) and bc2_sqrt = sqrt(1-beta2^t),
+ *            both computed by the caller in double and passed as floats (lr is then not read by the update).
+ *   RMSprop: g = grad*grad_scale + wd*p ; v = alpha*v + (1-alpha)*g*g ; avg = sqrt(v) + eps ;
+ *            momentum > 0:  buf = momentum*buf + g/avg ; p -= lr*buf        (momentum_buf required)
+ *            momentum == 0: p -= lr*g/avg                                    (momentum_buf NULL)
+ * beta1, beta2 and alpha are doubles: the factors 1 - beta and 1 - alpha are formed from them in double and then rounded to
+ * fp32, as torch does with its Python-float hyper-parameters (1 - 0.999f is 1.3e-5 away from 1 - 0.999 in relative terms).
+ * ------------------------------------------------------------------------------------------------------------ */
+int dfl_adam_step(float* p, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, double beta1,
+                  double beta2, float eps, float weight_decay, float step_size, float bc2_sqrt, float grad_scale,
+                  dfl_stream_t stream);
+int dfl_rmsprop_step(float* p, const float* grad, float* square_avg, float* momentum_buf, int64_t n, float lr, double alpha,
+                     float eps, float weight_decay, float momentum, float grad_scale, dfl_stream_t stream);
+
+/* Either update inside the tiled weight re-layout, as dfl_sgd_pack_tiled does for SGD: the same job list (tiled jobs of
+ * dfl_pack_weights_tiled, then DFL_PACK_PLAIN jobs of DFL_SGD_PLAIN_TILE elements per workgroup).  The gradient and the two
+ * state tensors of an element live at src + grad_delta, src + state1_delta, src + state2_delta (ELEMENTS, multiples of 4):
+ * Adam: state1 = exp_avg, state2 = exp_avg_sq; RMSprop: state1 = square_avg, state2 = momentum buffer (not touched, and
+ * state2_delta not read, when momentum == 0).  All parameters of the launch share one step count. */
+#define DFL_OPTIM_ADAM 1
+#define DFL_OPTIM_RMSPROP 2
+typedef struct {
+  const dfl_pack_job* jobs_dev;
+  int64_t grad_delta, state1_delta, state2_delta;
+  double beta1, beta2;          /* Adam */
+  double alpha;                 /* RMSprop */
+  int32_t njobs, total_tiles;
+  int32_t kind;                 /* DFL_OPTIM_ADAM | DFL_OPTIM_RMSPROP */
+  float lr, eps, weight_decay, grad_scale;
+  float step_size, bc2_sqrt;    /* Adam */
+  float momentum;               /* RMSprop */
+} dfl_optim_pack_args;
+int dfl_optim_pack_tiled(const dfl_optim_pack_args* a, dfl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * GPU-side input pipeline: the deterministic part of the reference loader (train_test_code/dataset.py) from raw

@@ -9,10 +9,11 @@ and pre-warm-restart copies and the three stop rules (:556-577).
 
 What is this build's own: the structure below (Settings / Snapshots / Trainer instead of one long script), the
 GPU-resident loader (dfl_amd.dataset: batches are built on the device by dfl_prep_batch, no DataLoader), the one-launch
-optimizer (dfl_amd.SGD) and DATA-PARALLEL training: started under torchrun (one process per GPU, RCCL) every rank takes
-a contiguous slice of each global minibatch, gradients are averaged by dfl_amd.DataParallel while backward is still
-running, rank 0 alone writes logs and checkpoints.  --batch-size is the batch PER GPU (BatchNorm statistics stay per
-replica, i.e. what the reference computes at that batch size); the global batch is --batch-size x world size.
+optimizers (dfl_amd.SGD, dfl_amd.Adam, dfl_amd.RMSprop) and DATA-PARALLEL training: started under torchrun (one process
+per GPU, RCCL) every rank takes a contiguous slice of each global minibatch, gradients are averaged by
+dfl_amd.DataParallel while backward is still running, rank 0 alone writes logs and checkpoints.  --batch-size is the
+batch PER GPU (BatchNorm statistics stay per replica, i.e. what the reference computes at that batch size); the global
+batch is --batch-size x world size.
 
     python train.py data.h5 --train-pats 1,2,3 --valid-pats 4 --num-classes 7 --unet-img-dim 192 --batch-size 16 \
         --unet-num-lvls 6 --unet-init-feats-exp 5 --unet-batch-norm --unet-padding --unet-no-max-pool --use-lands \
@@ -327,10 +328,10 @@ class Trainer:
             if meth != 'none':
                 raise ValueError("--optim {} takes --lr-sched none".format(kind))
             if kind == 'adam':
-                self.optimizer = optim.Adam(self.net.parameters(), lr=a.init_lr, weight_decay=c['opt-wgt-decay'])
+                self.optimizer = dfl_amd.Adam(self.net.parameters(), lr=a.init_lr, weight_decay=c['opt-wgt-decay'])
             else:
-                self.optimizer = optim.RMSprop(self.net.parameters(), lr=a.init_lr, weight_decay=c['opt-wgt-decay'],
-                                               momentum=c['opt-momentum'])
+                self.optimizer = dfl_amd.RMSprop(self.net.parameters(), lr=a.init_lr, weight_decay=c['opt-wgt-decay'],
+                                                 momentum=c['opt-momentum'])
         else:
             raise ValueError('unknown --optim {!r}'.format(kind))
         self.say('optimizer: {}, LR schedule: {}'.format(kind, meth))
