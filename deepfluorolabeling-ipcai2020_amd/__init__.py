@@ -9,8 +9,7 @@ from .dice import DiceLoss2D, DiceAndHeatMapLoss2D
 from .ncc import ncc_2d
 from .util import center_crop, get_device
 from .warm_restarts_lr import WarmRestartLR
-from .sgd import SGD
-from .optim import Adam, RMSprop
+from .optim import SGD, Adam, RMSprop
 from . import parallel
 from .parallel import DataParallel
 from .dataset import DeviceAugment

@@ -948,117 +948,40 @@ __device__ __forceinline__ void pack_emit(const float (*tile)[PK_T * PK_CMAX + 1
   else pack_emit_quads(tile, dst, kind, flip, split, A, B, Cc, a0, b0);
 }
 
-__global__ void __launch_bounds__(256) pack_tiles_kernel(const dfl_pack_job* __restrict__ jobs, int njobs) {
-  __shared__ float tile[PK_T][PK_T * PK_CMAX + 1];
-  // which job: the last one whose first_tile <= blockIdx.x (binary search; the few records stay in the scalar cache)
-  int lo = 0, hi = njobs - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (jobs[mid].first_tile <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-  }
-  const dfl_pack_job j = jobs[lo];
-  const int A = j.A, B = j.B, Cc = j.C;
-  const int tb = B / PK_T;
-  const int tidx = (int)blockIdx.x - j.first_tile;
-  const int a0 = (tidx / tb) * PK_T, b0 = (tidx % tb) * PK_T;
-  const int run4 = 8 * Cc;                                     // float4 per tile row (32 * C floats)
-  for (int e = threadIdx.x; e < PK_T * run4; e += 256) {
-    const int ar = e / run4, q4 = e - ar * run4;
-    const float4 v = *reinterpret_cast<const float4*>(j.src + ((int64_t)(a0 + ar) * B + b0) * Cc + 4 * q4);
-    float* t = &tile[ar][4 * q4];
-    t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
-  }
-  __syncthreads();
-  pack_emit(tile, j.dst, j.kind, j.flip, j.split, A, B, Cc, a0, b0);
-  if (j.dst2 != nullptr) pack_emit(tile, j.dst2, j.kind2, j.flip2, j.split2, A, B, Cc, a0, b0);
-}
+// ------------------------------------------------------------------------------------------------ optimizer update rules
+// One element's update: p = r(w, g, &s1, &s2), the rule's state streams read before and written back after; has1() / has2()
+// say which of them exist (the others are neither loaded nor stored).  PackOnly: the re-layout alone, nothing read but the master.
+struct PackOnly {
+  __device__ bool has1() const { return false; }
+  __device__ bool has2() const { return false; }
+  __device__ float operator()(float w, float, float*, float*) const { return w; }
+};
 
-// ------------------------------------------------------------------------------------------------ SGD
-__global__ void __launch_bounds__(256) sgd_kernel(float* __restrict__ p, const float* __restrict__ grad,
-                                                 float* __restrict__ buf, int64_t n, float lr, float mom, float wd,
-                                                 float gscale, int nesterov, int first) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float w = p[i];
-    float g = fmaf(wd, w, grad[i] * gscale);
+// torch.optim.SGD: state 1 = momentum buffer (only when momentum != 0); first: buf = g, torch's first step (dfl_sgd_step only)
+struct SgdRule {
+  float lr, mom, wd, gscale;
+  int nesterov, first;
+  __device__ bool has1() const { return mom != 0.f; }
+  __device__ bool has2() const { return false; }
+  __device__ __forceinline__ float operator()(float w, float gr, float* b, float*) const {
+    float g = fmaf(wd, w, gr * gscale);
     if (mom != 0.f) {
-      const float b = first ? g : fmaf(mom, buf[i], g);
-      buf[i] = b;
-      g = nesterov ? fmaf(mom, b, g) : b;
+      const float nb = first ? g : fmaf(mom, *b, g);
+      *b = nb;
+      g = nesterov ? fmaf(mom, nb, g) : nb;
     }
-    p[i] = fmaf(-lr, g, w);
+    return fmaf(-lr, g, w);
   }
-}
+};
 
-__device__ __forceinline__ float sgd_update(float w, float gr, float* b, float lr, float mom, float wd, float gscale, int nesterov) {
-  float g = fmaf(wd, w, gr * gscale);                          // (the arithmetic of sgd_kernel, word for word)
-  if (mom != 0.f) {
-    const float nb = fmaf(mom, *b, g);
-    *b = nb;
-    g = nesterov ? fmaf(mom, nb, g) : nb;
-  }
-  return fmaf(-lr, g, w);
-}
-
-// dfl_sgd_pack_tiled: pack_tiles_kernel whose workgroups update their tile of the master before they emit its layouts -- the
-// weights are read once per step (sgd_kernel + pack_tiles_kernel: twice) and one launch goes.
-__global__ void __launch_bounds__(256) sgd_pack_tiles_kernel(dfl_sgd_pack_args a) {
-  __shared__ float tile[PK_T][PK_T * PK_CMAX + 1];
-  const dfl_pack_job* __restrict__ jobs = a.jobs_dev;
-  int lo = 0, hi = a.njobs - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (jobs[mid].first_tile <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-  }
-  const dfl_pack_job j = jobs[lo];
-  const int tidx = (int)blockIdx.x - j.first_tile;
-  float* __restrict__ P = const_cast<float*>(j.src);
-  const float* __restrict__ G = j.src + a.grad_delta;
-  float* __restrict__ Bf = const_cast<float*>(j.src) + a.buf_delta;
-  const bool hasb = a.momentum != 0.f;
-  if (j.kind == DFL_PACK_PLAIN) {
-    const int64_t i0 = (int64_t)tidx * DFL_SGD_PLAIN_TILE;
-    const int64_t i1 = min((int64_t)j.A, i0 + DFL_SGD_PLAIN_TILE);
-    for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
-      float b = hasb ? Bf[i] : 0.f;
-      P[i] = sgd_update(P[i], G[i], &b, a.lr, a.momentum, a.weight_decay, a.grad_scale, a.nesterov);
-      if (hasb) Bf[i] = b;
-    }
-    return;
-  }
-  const int A = j.A, B = j.B, Cc = j.C;
-  const int tb = B / PK_T;
-  const int a0 = (tidx / tb) * PK_T, b0 = (tidx % tb) * PK_T;
-  const int run4 = 8 * Cc;
-  for (int e = threadIdx.x; e < PK_T * run4; e += 256) {
-    const int ar = e / run4, q4 = e - ar * run4;
-    const int64_t o = ((int64_t)(a0 + ar) * B + b0) * Cc + 4 * q4;
-    const float4 w = *reinterpret_cast<const float4*>(P + o);
-    const float4 g = *reinterpret_cast<const float4*>(G + o);
-    float4 b = hasb ? *reinterpret_cast<const float4*>(Bf + o) : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 v;
-    v.x = sgd_update(w.x, g.x, &b.x, a.lr, a.momentum, a.weight_decay, a.grad_scale, a.nesterov);
-    v.y = sgd_update(w.y, g.y, &b.y, a.lr, a.momentum, a.weight_decay, a.grad_scale, a.nesterov);
-    v.z = sgd_update(w.z, g.z, &b.z, a.lr, a.momentum, a.weight_decay, a.grad_scale, a.nesterov);
-    v.w = sgd_update(w.w, g.w, &b.w, a.lr, a.momentum, a.weight_decay, a.grad_scale, a.nesterov);
-    *reinterpret_cast<float4*>(P + o) = v;
-    if (hasb) *reinterpret_cast<float4*>(Bf + o) = b;
-    float* t = &tile[ar][4 * q4];
-    t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
-  }
-  __syncthreads();
-  pack_emit(tile, j.dst, j.kind, j.flip, j.split, A, B, Cc, a0, b0);
-  if (j.dst2 != nullptr) pack_emit(tile, j.dst2, j.kind2, j.flip2, j.split2, A, B, Cc, a0, b0);
-}
-
-// ------------------------------------------------------------------------------------------------ Adam, RMSprop
 // torch's _multi_tensor_adam / _multi_tensor_rmsprop (the reference's --optim adam|rmsprop, train.py:331-352) one foreach op at
 // a time, in torch's order, each result rounded to fp32.  No contraction into FMAs: the flat kernel and the tiled one then give
 // the same bits whatever the compiler schedules around the inlined rule.  The (1 - beta) factors are formed in double on the host.
 struct AdamRule {
   float eps, wd, gscale, beta2, step_size, bc2_sqrt, w1, omb2;   // w1 = 1 - beta1 (the lerp weight), omb2 = 1 - beta2
-  static constexpr bool always2 = true;
-  __device__ __forceinline__ float operator()(float w, float gr, float* m, float* v, bool) const {
+  __device__ bool has1() const { return true; }
+  __device__ bool has2() const { return true; }
+  __device__ __forceinline__ float operator()(float w, float gr, float* m, float* v) const {
 #pragma clang fp contract(off)
     const float g = gr * gscale + wd * w;                      // _foreach_add(grads, params, alpha=wd)
     const float d = g - *m;                                    // _foreach_lerp_(exp_avgs, grads, 1 - beta1): at::lerp
@@ -1069,11 +992,14 @@ struct AdamRule {
   }
 };
 
+// state 1 = square_avg, state 2 = momentum buffer (only when momentum != 0)
 struct RmspropRule {
   float eps, wd, gscale, alpha, oma, lr, mom;                  // oma = 1 - alpha
-  static constexpr bool always2 = false;
-  __device__ __forceinline__ float operator()(float w, float gr, float* sq, float* buf, bool hasb) const {
+  __device__ bool has1() const { return true; }
+  __device__ bool has2() const { return mom != 0.f; }
+  __device__ __forceinline__ float operator()(float w, float gr, float* sq, float* buf) const {
 #pragma clang fp contract(off)
+    const bool hasb = has2();
     const float g = gr * gscale + wd * w;                      // _foreach_add(grads, params, alpha=wd)
     *sq = *sq * alpha + (oma * g) * g;                         // _foreach_mul_(alpha); _foreach_addcmul_(g, g, 1 - alpha)
     const float avg = sqrtf(*sq) + eps;
@@ -1085,26 +1011,31 @@ struct RmspropRule {
   }
 };
 
+// dfl_sgd_step, dfl_adam_step, dfl_rmsprop_step: a flat arena, 4-byte accesses
 template <class Rule>
 __global__ void __launch_bounds__(256) optim_kernel(float* __restrict__ p, const float* __restrict__ grad, float* __restrict__ s1,
                                                    float* __restrict__ s2, int64_t n, Rule r) {
-  const bool has2 = Rule::always2 || s2 != nullptr;
+  const bool has1 = r.has1(), has2 = r.has2();
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    float a = s1[i], b = has2 ? s2[i] : 0.f;
-    p[i] = r(p[i], grad[i], &a, &b, has2);
-    s1[i] = a;
+    float a = has1 ? s1[i] : 0.f, b = has2 ? s2[i] : 0.f;
+    p[i] = r(p[i], grad[i], &a, &b);
+    if (has1) s1[i] = a;
     if (has2) s2[i] = b;
   }
 }
 
-// dfl_optim_pack_tiled: sgd_pack_tiles_kernel with an Adam / RMSprop update -- the same jobs, tiles and layouts; the tile is
-// updated with 16-byte accesses to the master and both state arenas, then emitted from LDS.
+// One workgroup of the tiled re-layout: finds its job, updates its 32 x 32 x C tile of the fp32 master with 16-byte accesses to
+// the master, the gradient and the rule's state arenas (all at the master's offsets plus a delta, in elements), and emits the
+// tile's layouts from LDS -- the weights are read once per step, and the update costs no launch of its own.  A DFL_PACK_PLAIN job
+// (something without a tiled layout) updates DFL_SGD_PLAIN_TILE elements as optim_kernel does, and emits nothing.
 template <class Rule>
-__global__ void __launch_bounds__(256) optim_pack_tiles_kernel(dfl_optim_pack_args a, Rule r) {
+__device__ __forceinline__ void pack_tile(const dfl_pack_job* __restrict__ jobs, int njobs, int64_t grad_delta, int64_t s1_delta,
+                                          int64_t s2_delta, Rule r) {
+  constexpr bool updates = !std::is_same<Rule, PackOnly>::value;
   __shared__ float tile[PK_T][PK_T * PK_CMAX + 1];
-  const dfl_pack_job* __restrict__ jobs = a.jobs_dev;
-  int lo = 0, hi = a.njobs - 1;
+  // which job: the last one whose first_tile <= blockIdx.x (binary search; the few records stay in the scalar cache)
+  int lo = 0, hi = njobs - 1;
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
     if (jobs[mid].first_tile <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
@@ -1112,17 +1043,17 @@ __global__ void __launch_bounds__(256) optim_pack_tiles_kernel(dfl_optim_pack_ar
   const dfl_pack_job j = jobs[lo];
   const int tidx = (int)blockIdx.x - j.first_tile;
   float* __restrict__ P = const_cast<float*>(j.src);
-  const float* __restrict__ G = j.src + a.grad_delta;
-  float* __restrict__ S1 = const_cast<float*>(j.src) + a.state1_delta;
-  float* __restrict__ S2 = const_cast<float*>(j.src) + a.state2_delta;
-  const bool has2 = Rule::always2 || a.momentum != 0.f;
-  if (j.kind == DFL_PACK_PLAIN) {
+  const float* __restrict__ G = j.src + grad_delta;
+  float* __restrict__ S1 = P + s1_delta;
+  float* __restrict__ S2 = P + s2_delta;
+  const bool has1 = r.has1(), has2 = r.has2();
+  if (updates && j.kind == DFL_PACK_PLAIN) {
     const int64_t i0 = (int64_t)tidx * DFL_SGD_PLAIN_TILE;
     const int64_t i1 = min((int64_t)j.A, i0 + DFL_SGD_PLAIN_TILE);
     for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
-      float s = S1[i], b = has2 ? S2[i] : 0.f;
-      P[i] = r(P[i], G[i], &s, &b, has2);
-      S1[i] = s;
+      float s = has1 ? S1[i] : 0.f, b = has2 ? S2[i] : 0.f;
+      P[i] = r(P[i], G[i], &s, &b);
+      if (has1) S1[i] = s;
       if (has2) S2[i] = b;
     }
     return;
@@ -1130,28 +1061,45 @@ __global__ void __launch_bounds__(256) optim_pack_tiles_kernel(dfl_optim_pack_ar
   const int A = j.A, B = j.B, Cc = j.C;
   const int tb = B / PK_T;
   const int a0 = (tidx / tb) * PK_T, b0 = (tidx % tb) * PK_T;
-  const int run4 = 8 * Cc;
+  const int run4 = 8 * Cc;                                     // float4 per tile row (32 * C floats)
   for (int e = threadIdx.x; e < PK_T * run4; e += 256) {
     const int ar = e / run4, q4 = e - ar * run4;
     const int64_t o = ((int64_t)(a0 + ar) * B + b0) * Cc + 4 * q4;
-    const float4 w = *reinterpret_cast<const float4*>(P + o);
-    const float4 g = *reinterpret_cast<const float4*>(G + o);
-    float4 s = *reinterpret_cast<const float4*>(S1 + o);
-    float4 b = has2 ? *reinterpret_cast<const float4*>(S2 + o) : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 v;
-    v.x = r(w.x, g.x, &s.x, &b.x, has2);
-    v.y = r(w.y, g.y, &s.y, &b.y, has2);
-    v.z = r(w.z, g.z, &s.z, &b.z, has2);
-    v.w = r(w.w, g.w, &s.w, &b.w, has2);
-    *reinterpret_cast<float4*>(P + o) = v;
-    *reinterpret_cast<float4*>(S1 + o) = s;
-    if (has2) *reinterpret_cast<float4*>(S2 + o) = b;
+    float4 v = *reinterpret_cast<const float4*>(P + o);
+    if constexpr (updates) {
+      const float4 w = v, g = *reinterpret_cast<const float4*>(G + o);
+      float4 s = has1 ? *reinterpret_cast<const float4*>(S1 + o) : make_float4(0.f, 0.f, 0.f, 0.f);
+      float4 b = has2 ? *reinterpret_cast<const float4*>(S2 + o) : make_float4(0.f, 0.f, 0.f, 0.f);
+      v.x = r(w.x, g.x, &s.x, &b.x);
+      v.y = r(w.y, g.y, &s.y, &b.y);
+      v.z = r(w.z, g.z, &s.z, &b.z);
+      v.w = r(w.w, g.w, &s.w, &b.w);
+      *reinterpret_cast<float4*>(P + o) = v;
+      if (has1) *reinterpret_cast<float4*>(S1 + o) = s;
+      if (has2) *reinterpret_cast<float4*>(S2 + o) = b;
+    }
     float* t = &tile[ar][4 * q4];
     t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
   }
   __syncthreads();
   pack_emit(tile, j.dst, j.kind, j.flip, j.split, A, B, Cc, a0, b0);
   if (j.dst2 != nullptr) pack_emit(tile, j.dst2, j.kind2, j.flip2, j.split2, A, B, Cc, a0, b0);
+}
+
+// dfl_pack_weights_tiled
+__global__ void __launch_bounds__(256) pack_tiles_kernel(const dfl_pack_job* __restrict__ jobs, int njobs) {
+  pack_tile(jobs, njobs, 0, 0, 0, PackOnly{});
+}
+
+// dfl_sgd_pack_tiled
+__global__ void __launch_bounds__(256) sgd_pack_tiles_kernel(dfl_sgd_pack_args a) {
+  pack_tile(a.jobs_dev, a.njobs, a.grad_delta, a.buf_delta, 0, SgdRule{a.lr, a.momentum, a.weight_decay, a.grad_scale, a.nesterov, 0});
+}
+
+// dfl_optim_pack_tiled
+template <class Rule>
+__global__ void __launch_bounds__(256) optim_pack_tiles_kernel(dfl_optim_pack_args a, Rule r) {
+  pack_tile(a.jobs_dev, a.njobs, a.grad_delta, a.state1_delta, a.state2_delta, r);
 }
 
 static AdamRule adam_rule(double beta1, double beta2, float eps, float wd, float step_size, float bc2_sqrt, float gscale) {
@@ -1392,8 +1340,8 @@ extern "C" int dfl_sgd_step(float* p, const float* grad, float* momentum_buf, in
                             dfl_stream_t stream) {
   DFL_REQUIRE(p && grad && n > 0, "dfl_sgd_step: bad args");
   DFL_REQUIRE(momentum == 0.f || momentum_buf != nullptr, "dfl_sgd_step: momentum buffer required");
-  hipLaunchKernelGGL(sgd_kernel, dim3(stream_grid(n)), dim3(256), 0, static_cast<hipStream_t>(stream), p, grad,
-                     momentum_buf, n, lr, momentum, weight_decay, grad_scale, (int)nesterov, (int)first_step);
+  hipLaunchKernelGGL(optim_kernel<SgdRule>, dim3(stream_grid(n)), dim3(256), 0, static_cast<hipStream_t>(stream), p, grad,
+                     momentum_buf, nullptr, n, SgdRule{lr, momentum, weight_decay, grad_scale, (int)nesterov, (int)first_step});
   return check_launch("dfl_sgd_step");
 }
 

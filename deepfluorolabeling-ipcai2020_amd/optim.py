@@ -1,45 +1,61 @@
-"""Adam and RMSprop, torch.optim.Adam / torch.optim.RMSprop semantics, on the flat parameter arena.
+"""SGD, Adam and RMSprop, torch.optim.SGD / Adam / RMSprop semantics, on the flat parameter arena.
 
-Reference: train.py:331-352 builds ``optim.Adam(net.parameters(), lr, weight_decay)`` or ``optim.RMSprop(net.parameters(), lr,
-weight_decay, momentum)`` for --optim adam|rmsprop (with --lr-sched none) and loads ``optimizer-state-dict`` into it on resume
-(:354-355).  The design is sgd.SGD's: parameters (UNet._flatten_parameters), gradients (plan.grad_flat) and each state tensor
-(one arena per state key) share one layout, so a step is one dfl_adam_step / dfl_rmsprop_step launch per contiguous run of live
-parameters whose step counts are equal (two runs for the paper network), or -- when the network has a training plan with tiled
-weight layouts -- one dfl_optim_pack_tiled launch that updates every parameter inside the next step's weight re-layout.
-State is torch's, key for key: a CPU float32 ``step`` per parameter and fp32 tensors, only for parameters that received a
-gradient, so checkpoints move between this class and torch.optim in both directions.  Results differ from torch's
-multi-tensor kernels by fp32 rounding only.  CPU tensors are refused: there is no fallback path.
+Reference: train.py:287-290 builds ``optim.SGD(net.parameters(), lr, momentum, weight_decay, nesterov)``, train.py:331-352
+``optim.Adam(net.parameters(), lr, weight_decay)`` or ``optim.RMSprop(net.parameters(), lr, weight_decay, momentum)`` for
+--optim adam|rmsprop (with --lr-sched none); ``optimizer.step()`` runs once per batch (train.py:423) and a resumed run loads
+``optimizer-state-dict`` (:354-355).  torch runs a step as several multi-tensor kernels over ~140 tensors; here parameters
+(UNet._flatten_parameters), gradients (plan.grad_flat) and each state tensor (one arena per state key) share one layout, so a
+step is one dfl_sgd_step / dfl_adam_step / dfl_rmsprop_step launch per contiguous run of live parameters whose step counts are
+equal (two runs for the paper network: the never-used ``downsample_convs[depth-1]`` has no gradient and, exactly as in torch, is
+skipped -- no weight decay either), or -- when the network has a training plan with tiled weight layouts -- one
+dfl_sgd_pack_tiled / dfl_optim_pack_tiled launch that updates every parameter inside the next step's weight re-layout.
+Parameters whose tensors do not line up (foreign modules, accumulated gradients) are updated tensor by tensor with the same
+kernel.  State is torch's, key for key (Adam and RMSprop: with a CPU float32 ``step`` per parameter), only for parameters that
+received a gradient, so checkpoints move between these classes and torch.optim in both directions.  Adam and RMSprop differ from
+torch's multi-tensor kernels by fp32 rounding only.  CPU tensors are refused: there is no fallback path.
 """
 import ctypes as C
 import math
+import os
+import weakref
 
+import numpy as np
 import torch
-from torch.optim.optimizer import Optimizer, _get_scalar_dtype
+from torch.optim.optimizer import Optimizer, _get_scalar_dtype, required
 
 from . import _native as nat
-from .sgd import SGD, tiled_job_list
 
 
 class _ArenaOptimizer(Optimizer):
-    """What Adam and RMSprop share: state arenas, contiguous runs, the update inside the tiled re-layout."""
-    FUSE_PACK = SGD.FUSE_PACK          # DFL_SGD_PACK=0 switches the update inside the re-layout off for every optimizer
+    """What SGD, Adam and RMSprop share: state arenas, contiguous runs, the update inside the tiled re-layout."""
+    FUSE_PACK = os.environ.get('DFL_SGD_PACK', '1') != '0'   # 0: no update inside the re-layout, for every optimizer
     NAME = ''
     REFUSED = ()                       # group flags no reference command line selects: (key, value that is refused)
+    KEEPS_STEP = True                  # keeps torch's per-parameter 'step' tensor
 
     def __init__(self, params, defaults):
+        for k, bad in self.REFUSED:
+            if defaults[k] == bad:
+                raise NotImplementedError('%s: %s=%r is not implemented in the HIP path (no reference command line selects it)'
+                                          % (self.NAME, k, bad))
         super().__init__(params, defaults)
-        self.grad_scale = 1.0          # parallel.DataParallel leaves SUMMED gradients when asked to; see sgd.SGD
         self._lib = nat.lib()
-        self._fused_cache = {}         # tiled job lists, see sgd.tiled_job_list
+        self._fused_cache = {}         # tiled job lists, see tiled_job_list
 
     # ---- per optimizer
     def _state_keys(self, group):
         raise NotImplementedError
 
+    def _pads_ok(self, group):
+        """Whether an update may run across the alignment padding between slices (merged runs, the plain jobs of the tiled
+        update).  Adam and RMSprop: only when eps > 0, otherwise they would write 0/0 there."""
+        return group['eps'] > 0
+
     def _launch_run(self, lib, group, t, pp, gp, sp, n, stream):
         raise NotImplementedError
 
-    def _pack_args(self, group, t):
+    def _launch_tiled(self, lib, group, t, jobs, deltas, stream):
+        """`jobs`: the job fields of the pack-args struct; `deltas`: element deltas of the state arenas to the parameters."""
         raise NotImplementedError
 
     # ---- state
@@ -51,7 +67,7 @@ class _ArenaOptimizer(Optimizer):
                     group.setdefault(k, v)
             for p in group['params']:       # (old checkpoints keep the step count as a number, as torch.optim does)
                 st = self.state.get(p, {})
-                if len(st) != 0 and not torch.is_tensor(st.get('step')):
+                if self.KEEPS_STEP and len(st) != 0 and not torch.is_tensor(st.get('step')):
                     st['step'] = torch.tensor(float(st.get('step', 0)), dtype=_get_scalar_dtype())
 
     @staticmethod
@@ -69,16 +85,17 @@ class _ArenaOptimizer(Optimizer):
     def _init_state(self, group):
         """torch's state for parameters that have a gradient and no state yet (zero tensors, step 0).  When the whole group is
         new and its parameters share one arena, each state key gets one arena with the same layout."""
-        ps = [p for p in group['params'] if p.grad is not None and len(self.state.get(p, {})) == 0]
-        if not ps:
-            return
         keys = self._state_keys(group)
+        ps = [p for p in group['params'] if p.grad is not None and len(self.state.get(p, {})) == 0]
+        if not ps or not (keys or self.KEEPS_STEP):
+            return
         fresh = all(len(self.state.get(p, {})) == 0 for p in group['params'])
         lay = self._arena_layout(group['params']) if fresh else None
         flats = {k: torch.zeros(lay[1], dtype=torch.float32, device=ps[0].device) for k in keys} if lay else None
         for p in ps:                          # like torch: only parameters that received a gradient get state
             st = self.state[p]
-            st['step'] = torch.tensor(0.0, dtype=_get_scalar_dtype())
+            if self.KEEPS_STEP:
+                st['step'] = torch.tensor(0.0, dtype=_get_scalar_dtype())
             for k in keys:
                 if flats is not None:
                     o = (p.data_ptr() - lay[0]) // 4
@@ -107,27 +124,30 @@ class _ArenaOptimizer(Optimizer):
                         self.state[p][k] = view
 
     # ---- step
-    def _fused(self, group, net, live, runs, keys):
-        """(plan, device job list, jobs, tiles, deltas) for dfl_optim_pack_tiled, or None: every live parameter at one step
+    def _fused(self, group, net, live, runs):
+        """(plan, job fields, state deltas) of an update inside the tiled re-layout, or None: every live parameter at one step
         count, every tiled parameter live, gradients and state tensors laid out like the parameters (one delta each)."""
-        if net is None or not self.FUSE_PACK or len(self.param_groups) != 1 or len({r[3] for r in runs}) != 1 or group['eps'] <= 0:
-            return None                       # (eps = 0: the plain jobs would write 0/0 into the arena's alignment padding)
+        if net is None or not self.FUSE_PACK or len(self.param_groups) != 1 or len({r[3] for r in runs}) != 1 \
+                or not self._pads_ok(group):
+            return None
         plan = net.plan_for_fused_update()
         if plan is None:
             return None
         deltas = []
-        for j in range(1 + len(keys)):
+        for j in range(len(runs[0][1])):
             d = {r[1][j] - r[0] for r in runs}
             if len(d) != 1:
                 return None
             deltas.append(d.pop())
         if any(d % 16 for d in deltas):
             return None
-        key = (id(plan), type(self).__name__) + tuple(deltas) + tuple(p.data_ptr() for p in live)
+        key = (id(plan),) + tuple(deltas) + tuple(p.data_ptr() for p in live)
         jl = tiled_job_list(self._fused_cache, net, plan, live, key)
         if jl is None:
             return None
-        return (plan,) + jl + tuple(d // 4 for d in deltas)
+        jobs_dev, njobs, tiles = jl
+        jobs = dict(jobs_dev=jobs_dev.data_ptr(), njobs=njobs, total_tiles=tiles, grad_delta=deltas[0] // 4)
+        return plan, jobs, [d // 4 for d in deltas[1:]]
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -151,12 +171,14 @@ class _ArenaOptimizer(Optimizer):
                     raise nat.DflError('%s needs contiguous float32 parameters and gradients' % self.NAME)
             self._init_state(group)
             keys = self._state_keys(group)
-            steps = [self.state[p]['step'] for p in live]
-            torch._foreach_add_(steps, 1.0)   # torch's per-parameter step counts (CPU float32 scalars)
-            counts = torch.stack([s.detach().to('cpu', torch.float64) for s in steps]).tolist()
+            counts = [None] * len(live)
+            if self.KEEPS_STEP:
+                steps = [self.state[p]['step'] for p in live]
+                torch._foreach_add_(steps, 1.0)   # torch's per-parameter step counts (CPU float32 scalars)
+                counts = torch.stack([s.detach().to('cpu', torch.float64) for s in steps]).tolist()
             stream = torch.cuda.current_stream(live[0].device).cuda_stream
             # contiguous runs: parameter, gradient and state addresses all advance by the same number of bytes, one step count
-            gap = 12 if group['eps'] > 0 else 0
+            gap = 12 if self._pads_ok(group) else 0
             runs, cur = [], None
             for p, t in zip(live, counts):
                 pp, n = p.data_ptr(), p.numel()
@@ -169,31 +191,104 @@ class _ArenaOptimizer(Optimizer):
                     runs.append(cur)
             from .unet import owner_of
             net = owner_of(live[0])
-            fused = self._fused(group, net, live, runs, keys)
+            fused = self._fused(group, net, live, runs)
             if fused is not None:
                 # one pass over the weights: the workgroups of the tiled re-layout update their tile first
-                plan, jobs_dev, njobs, tiles = fused[:4]
-                a = self._pack_args(group, runs[0][3])
-                a.jobs_dev, a.njobs, a.total_tiles, a.grad_delta, a.state1_delta = jobs_dev.data_ptr(), njobs, tiles, fused[4], fused[5]
-                a.state2_delta = fused[6] if len(fused) > 6 else 0
-                a.grad_scale = self.grad_scale
-                nat.check(lib.dfl_optim_pack_tiled(C.addressof(a), stream), 'dfl_optim_pack_tiled')
-                torch.autograd.graph.increment_version(live)
-                net.after_fused_update(plan, stream)
-                continue
-            for pp, other, n, t in runs:
-                self._launch_run(lib, group, t, pp, other[0], other[1:], n, stream)
-            # the kernel wrote behind autograd's back: bump the version counters like an in-place torch op would
+                plan, jobs, deltas = fused
+                self._launch_tiled(lib, group, runs[0][3], jobs, deltas, stream)
+            else:
+                for pp, other, n, t in runs:
+                    self._launch_run(lib, group, t, pp, other[0], other[1:], n, stream)
+            # the kernel wrote behind autograd's back: bump the version counters like an in-place torch op would (the
+            # network re-packs its weights when they move, and autograd must see saved tensors as modified)
             torch.autograd.graph.increment_version(live)
-            if net is not None:
+            if fused is not None:
+                net.after_fused_update(plan, stream)
+            elif net is not None:
                 net.prepack()            # next step's weight re-layout starts now, behind the update kernels
         return loss
+
+
+def tiled_job_list(cache, net, plan, live, key):
+    """(device job list, jobs, tiles) of an update inside the tiled weight re-layout of `plan` (dfl_sgd_pack_tiled,
+    dfl_optim_pack_tiled), or None: every tiled parameter must be among `live`.  The tiled jobs of the plan, then one
+    DFL_PACK_PLAIN job per stretch of the other live parameters.  Cached in `cache` under `key` while `plan` lives."""
+    hit = cache.get(key)
+    if hit is not None and hit[0]() is plan:
+        return hit[1:]
+    raw, ntiled, tiles, tiled_src = plan._tiled_host
+    ptrs = {p.data_ptr(): p.numel() for p in live}
+    if any(ptrs.get(s) != n for s, n in tiled_src.items()):
+        return None                      # a tiled parameter without a gradient (or a view of one): not this path
+    plain, cur = [], None                # what has no tiled layout, adjacent slices merged (alignment padding absorbed)
+    flat = getattr(net, '_param_flat', None)
+    lo = flat.data_ptr() if flat is not None else 0
+    hi = lo + 4 * flat.numel() if flat is not None else 0
+
+    def in_arena(ptr):                   # only slices of the network's own flat arena are merged across a gap (ADVICE r04)
+        return lo <= ptr < hi
+    for p in live:
+        pp, n = p.data_ptr(), p.numel()
+        if pp in tiled_src:
+            cur = None
+            continue
+        if cur is not None and 0 <= pp - cur[0] - 4 * cur[1] <= 12 and in_arena(cur[0]) and in_arena(pp):
+            cur[1] = (pp - cur[0]) // 4 + n          # (the gap is the arena's alignment padding: nobody else's memory)
+        else:
+            cur = [pp, n]
+            plain.append(cur)
+    arr = (nat.PackJob * (ntiled + len(plain)))()
+    C.memmove(arr, raw, len(raw))
+    for i, (pp, n) in enumerate(plain):
+        a = arr[ntiled + i]
+        a.src, a.A, a.B, a.C, a.kind, a.first_tile = pp, n, 1, 1, nat.PACK_PLAIN, tiles
+        tiles += -(-n // nat.SGD_PLAIN_TILE)
+    jobs_dev = torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(live[0].device)
+    if len(cache) >= 4:
+        cache.clear()
+    cache[key] = (weakref.ref(plan), jobs_dev, len(arr), tiles)
+    return cache[key][1:]
 
 
 def _number(x, what):
     if torch.is_tensor(x):
         raise NotImplementedError('%s as a Tensor is not implemented in the HIP path (capturable use only)' % what)
     return x
+
+
+class SGD(_ArenaOptimizer):
+    """torch.optim.SGD with momentum / Nesterov / weight decay (dampening refused)."""
+    NAME = 'optim.SGD'
+    KEEPS_STEP = False                 # (torch's SGD keeps no step count)
+
+    def __init__(self, params, lr=required, momentum=0, dampening=0, weight_decay=0, nesterov=False):
+        if lr is not required and lr < 0.0:
+            raise ValueError('Invalid learning rate: {}'.format(lr))
+        if momentum < 0.0:
+            raise ValueError('Invalid momentum value: {}'.format(momentum))
+        if weight_decay < 0.0:
+            raise ValueError('Invalid weight_decay value: {}'.format(weight_decay))
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError('Nesterov momentum requires a momentum and zero dampening')
+        if dampening != 0:
+            raise NotImplementedError('dampening != 0 is not implemented in the HIP path (no reference CLI selects it)')
+        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov)
+        super().__init__(params, defaults)
+
+    def _state_keys(self, group):
+        return ('momentum_buffer',) if group['momentum'] != 0 else ()
+
+    def _pads_ok(self, group):
+        return True
+
+    def _launch_run(self, lib, group, t, pp, gp, sp, n, stream):
+        nat.check(lib.dfl_sgd_step(pp, gp, sp[0] if sp else None, n, group['lr'], group['momentum'], group['weight_decay'], 1.0,
+                                   int(group['nesterov']), 0, stream), 'dfl_sgd_step')
+
+    def _launch_tiled(self, lib, group, t, jobs, deltas, stream):
+        a = nat.SgdPackArgs(buf_delta=deltas[0] if deltas else 0, lr=group['lr'], momentum=group['momentum'],
+                            weight_decay=group['weight_decay'], grad_scale=1.0, nesterov=int(group['nesterov']), **jobs)
+        nat.check(lib.dfl_sgd_pack_tiled(C.addressof(a), stream), 'dfl_sgd_pack_tiled')
 
 
 class Adam(_ArenaOptimizer):
@@ -219,10 +314,6 @@ class Adam(_ArenaOptimizer):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize, foreach=foreach,
                         capturable=capturable, differentiable=differentiable, fused=fused,
                         decoupled_weight_decay=decoupled_weight_decay)
-        for k, bad in self.REFUSED:
-            if defaults[k] == bad:
-                raise NotImplementedError('%s: %s=%r is not implemented in the HIP path (no reference command line selects it)'
-                                          % (self.NAME, k, bad))
         super().__init__(params, defaults)
 
     def _state_keys(self, group):
@@ -238,13 +329,15 @@ class Adam(_ArenaOptimizer):
         b1, b2 = group['betas']
         step_size, bc2_sqrt = self._coefs(group, t)
         nat.check(lib.dfl_adam_step(pp, gp, sp[0], sp[1], n, group['lr'], b1, b2, group['eps'], group['weight_decay'], step_size,
-                                    bc2_sqrt, self.grad_scale, stream), 'dfl_adam_step')
+                                    bc2_sqrt, 1.0, stream), 'dfl_adam_step')
 
-    def _pack_args(self, group, t):
+    def _launch_tiled(self, lib, group, t, jobs, deltas, stream):
         b1, b2 = group['betas']
         step_size, bc2_sqrt = self._coefs(group, t)
-        return nat.OptimPackArgs(kind=nat.OPTIM_ADAM, lr=group['lr'], eps=group['eps'], weight_decay=group['weight_decay'],
-                                 beta1=b1, beta2=b2, step_size=step_size, bc2_sqrt=bc2_sqrt)
+        a = nat.OptimPackArgs(kind=nat.OPTIM_ADAM, state1_delta=deltas[0], state2_delta=deltas[1], lr=group['lr'], eps=group['eps'],
+                              weight_decay=group['weight_decay'], grad_scale=1.0, beta1=b1, beta2=b2, step_size=step_size,
+                              bc2_sqrt=bc2_sqrt, **jobs)
+        nat.check(lib.dfl_optim_pack_tiled(C.addressof(a), stream), 'dfl_optim_pack_tiled')
 
 
 class RMSprop(_ArenaOptimizer):
@@ -267,10 +360,6 @@ class RMSprop(_ArenaOptimizer):
             raise ValueError('Invalid alpha value: {}'.format(alpha))
         defaults = dict(lr=lr, momentum=momentum, alpha=alpha, eps=eps, centered=centered, weight_decay=weight_decay,
                         capturable=capturable, foreach=foreach, maximize=maximize, differentiable=differentiable)
-        for k, bad in self.REFUSED:
-            if defaults[k] == bad:
-                raise NotImplementedError('%s: %s=%r is not implemented in the HIP path (no reference command line selects it)'
-                                          % (self.NAME, k, bad))
         super().__init__(params, defaults)
 
     def _state_keys(self, group):
@@ -278,8 +367,10 @@ class RMSprop(_ArenaOptimizer):
 
     def _launch_run(self, lib, group, t, pp, gp, sp, n, stream):
         nat.check(lib.dfl_rmsprop_step(pp, gp, sp[0], sp[1] if len(sp) > 1 else None, n, group['lr'], group['alpha'], group['eps'],
-                                       group['weight_decay'], group['momentum'], self.grad_scale, stream), 'dfl_rmsprop_step')
+                                       group['weight_decay'], group['momentum'], 1.0, stream), 'dfl_rmsprop_step')
 
-    def _pack_args(self, group, t):
-        return nat.OptimPackArgs(kind=nat.OPTIM_RMSPROP, lr=group['lr'], eps=group['eps'], weight_decay=group['weight_decay'],
-                                 alpha=group['alpha'], momentum=group['momentum'])
+    def _launch_tiled(self, lib, group, t, jobs, deltas, stream):
+        a = nat.OptimPackArgs(kind=nat.OPTIM_RMSPROP, state1_delta=deltas[0], state2_delta=deltas[1] if len(deltas) > 1 else 0,
+                              lr=group['lr'], eps=group['eps'], weight_decay=group['weight_decay'], grad_scale=1.0,
+                              alpha=group['alpha'], momentum=group['momentum'], **jobs)
+        nat.check(lib.dfl_optim_pack_tiled(C.addressof(a), stream), 'dfl_optim_pack_tiled')

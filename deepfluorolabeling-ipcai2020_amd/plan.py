@@ -228,7 +228,7 @@ class UNetPlan:
             t = torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(self.dev)
             self._keep.append(t)
             return t
-        self._tiled_host, self._tiled_index = None, None      # what sgd.SGD needs to update the weights inside this launch
+        self._tiled_host, self._tiled_index = None, None      # what optim.py needs to update the weights inside this launch
         if tiled:
             arr = (PackJob * len(tiled))()
             tiles = 0
@@ -1404,8 +1404,8 @@ class UNetPlan:
         self.pack.run(stream)
 
     def run_pack_rest(self, stream):
-        """The pack program without its tiled launch: what is left to do after dfl_sgd_pack_tiled (sgd.SGD.step) has written the
-        tiled layouts together with the update."""
+        """The pack program without its tiled launch: what is left to do after dfl_sgd_pack_tiled / dfl_optim_pack_tiled (optim.py)
+        has written the tiled layouts together with the update."""
         i, n = self._tiled_index, len(self.pack)
         if i > 0:
             self.pack.run(stream, 0, i)

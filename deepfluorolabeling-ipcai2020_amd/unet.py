@@ -206,7 +206,7 @@ class UNet(nn.Module):
 
     def _flatten_parameters(self):
         """Keep every parameter as a view of ONE arena, in parameters() order, each slice padded to 4 floats -- the
-        layout of the gradient arena the backward program fills (plan.grad_flat).  sgd.SGD then updates the whole
+        layout of the gradient arena the backward program fills (plan.grad_flat).  optim.SGD then updates the whole
         network with one dfl_sgd_step per contiguous run instead of one launch per tensor."""
         ps = list(self.parameters())
         if not ps or any(p.dtype != torch.float32 for p in ps) or len({p.device for p in ps}) != 1:
@@ -227,7 +227,7 @@ class UNet(nn.Module):
         self.invalidate_plans() if hasattr(self, '_plans') else None
         _NETS[id(self)] = self
         for p in ps:
-            p._dfl_net_id = id(self)   # lets sgd.SGD start the next step's weight re-layout right behind its update
+            p._dfl_net_id = id(self)   # lets the optim.py optimizers start the next step's weight re-layout right behind its update
 
     def __getstate__(self):
         """Recorded programs hold raw device addresses and ctypes structures: they are rebuilt on demand, not pickled."""
@@ -293,7 +293,7 @@ class UNet(nn.Module):
 
     def prepack(self):
         """Enqueue the weight re-layout of the plan the last training forward used (no-op when nothing changed).  Called
-        by sgd.SGD.step(): the GPU then packs while the host is still in loss.item() / zero_grad() / forward()'s
+        by optim.SGD / Adam / RMSprop .step(): the GPU then packs while the host is still in loss.item() / zero_grad() / forward()'s
         bookkeeping instead of idling until the next forward's first launch (~0.14 ms per step)."""
         plan = self._last_train_plan() if self._last_train_plan is not None else None
         if plan is None or self._param_list is None or not any(plan is q for ps in self._plans.values() for q in ps):
@@ -303,7 +303,7 @@ class UNet(nn.Module):
         self._ensure_packed(plan, torch.cuda.current_stream(plan.dev).cuda_stream)
 
     def plan_for_fused_update(self):
-        """The training plan whose tiled weight re-layout sgd.SGD.step() may run inside its update kernel (dfl_sgd_pack_tiled), or
+        """The training plan whose tiled weight re-layout an optim.py step may run inside its update kernel (dfl_sgd_pack_tiled), or
         None: the same conditions as prepack() + a tiled pack list without aliases."""
         plan = self._last_train_plan() if self._last_train_plan is not None else None
         if plan is None or self._param_list is None or not any(plan is q for ps in self._plans.values() for q in ps):
