@@ -10,11 +10,17 @@ strided-conv down-sampling, residual blocks) with the seg + 14-landmark heat-map
 1x192x192 images (184x184 reflect-padded size), Dice + NCC loss, SGD(nesterov 0.9, wd 1e-4): one step =
 zero_grad -> forward -> crop -> loss -> backward -> optimizer step -> loss.item(), exactly train.py:405-430.
 Inputs and targets are resident in HBM before the timed region.  Arithmetic: --math (default bf16s = BASELINE configs[1] as named:
-bf16 tensors, fp32 accumulation / statistics / master weights; the parity-holding fp32 and bf16x3 figures ride along in the same
-line as `fp32_products` / `bf16x3_products`); no step of the loop is skipped.  Rank 0 prints ONE JSON line, which also carries
-`host_enqueue_ms_per_step` (host time to queue one step, GPU idle at its start) and `gpu_idle_frac` (1 - GPU kernel time / step time).
+bf16 tensors, fp32 accumulation / statistics / master weights); no step of the loop is skipped.  Rank 0 prints ONE JSON line.
 The timed steps start from the seeded initial weights whatever the time-bound pre-warm ran; --dump-outputs DIR writes what the
 last timed step computed (dump_outputs) so that two builds can be compared output for output.
+
+A plain run does only that: set up, pre-warm, warm up, time the steps, dump, print.  --full adds, after the timed steps and in
+the same line, everything else the benchmark measures: `host_enqueue_ms_per_step` (host time to queue one step, GPU idle at its
+start), the per-op profile with `roofline` and `gpu_idle_frac` (1 - GPU kernel time / step time), the same step in the other
+arithmetic modes (`fp32_products`, `bf16x3_products`, ...), the eval-forward timings (`fwd_ms_per_img`), BASELINE configs[3]
+(`configs3`) and the CPU oracle (`cpu_baseline`); the --no-* options leave parts of it out.
+
+    python bench.py --full
 """
 import argparse
 import ctypes as C
@@ -432,11 +438,16 @@ def main():
                     help='untimed steps run for this long BEFORE the --warmup steps: a fresh box (cold GPU clocks, cold host caches) '
                          'runs its first few hundred milliseconds of steps up to 50 %% slower than steady state (measured: first process on a box '
                          '7.9 ms per step, every later one 5.1; training runs for hours).  0 = off')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-profile', action='store_true')
-    ap.add_argument('--no-fwd', action='store_true', help='skip the eval-forward timings (fwd_ms_per_img)')
-    ap.add_argument('--no-configs3', action='store_true', help='skip the 768x768 batch-8 training timing (configs3)')
-    ap.add_argument('--detail', action='store_true', help='per-op table on stderr')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure everything beyond the headline: host enqueue time, per-op profile and '
+                         'roofline, the other arithmetic modes, eval-forward timings, configs[3] and the CPU baseline (off: the '
+                         'headline alone)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline (cpu_baseline)')
+    ap.add_argument('--no-profile', action='store_true',
+                    help='with --full: skip the per-op profile, the other arithmetic modes, fwd_ms_per_img and configs3')
+    ap.add_argument('--no-fwd', action='store_true', help='with --full: skip the eval-forward timings (fwd_ms_per_img)')
+    ap.add_argument('--no-configs3', action='store_true', help='with --full: skip the 768x768 batch-8 training timing (configs3)')
+    ap.add_argument('--detail', action='store_true', help='with --full: per-op table on stderr')
     ap.add_argument('--backend', default='nccl', help="torch.distributed backend ('nccl' = RCCL; 'gloo' for a self-test)")
     ap.add_argument('--optimizer', default='dfl', choices=['dfl', 'torch'],
                     help="dfl = dfl_amd.SGD (one dfl_sgd_step launch per contiguous run); torch = torch.optim.SGD")
@@ -445,8 +456,9 @@ def main():
                          'activations, activation gradients and GEMM weight copies in HBM, bf16 MFMA, fp32 accumulation / BatchNorm '
                          'statistics / losses / weight gradients / master weights.  bf16x3 = fp32 tensors, values split into hi+lo '
                          'bf16, 3 bf16 MFMA products (2^-16 per product: forward within the 1e-4 parity bar); fp32 = fp32 MFMA '
-                         '(the parity gate); bf16 = fp32 tensors, one bf16 product.  The other modes are timed beside the chosen one.')
-    ap.add_argument('--no-fp32-reference', action='store_true', help='skip the extra fp32-product timing (profiling runs)')
+                         '(the parity gate); bf16 = fp32 tensors, one bf16 product.  --full times the other modes beside the chosen one.')
+    ap.add_argument('--no-fp32-reference', action='store_true',
+                    help='with --full: skip the timings of the other arithmetic modes (profiling runs)')
     ap.add_argument('--sync-loss', action='store_true', help='loss.item() right after every optimizer step (the reference loop verbatim) '
                     'instead of reading each loss one step late')
     ap.add_argument('--no-overlap', action='store_true', help='all-reduce after backward instead of overlapped buckets')
@@ -459,6 +471,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error('--steps must be at least 1')
+    if args.detail and not args.full:
+        ap.error('--detail prints the per-op profile of --full: give both')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ and 'RANK' not in os.environ:
         # `python bench.py --gpus N` as typed: become the launcher the contract names (one rank per GPU, rendezvous on
@@ -561,20 +575,22 @@ def main():
     roofline = None
     extra = {'rccl_ranks': world if (multi and args.backend == 'nccl') else 0, 'prewarm_steps': prewarm_steps,
              'prewarm_seconds': args.prewarm_seconds}
-    # host time to queue one step when the GPU is idle at its start (nothing to wait for): what a slow host adds to a step once
-    # it exceeds the GPU time (8.4 ms per step observed by the driver where the kernels take 5.3)
-    nh = 10
-    host = 0.0
-    late.flush()
-    for _ in range(nh):
+    # everything below the headline runs under --full only: a plain run has measured what it prints
+    if args.full:
+        # host time to queue one step when the GPU is idle at its start (nothing to wait for): what a slow host adds to a step
+        # once it exceeds the GPU time (8.4 ms per step seen end to end where the kernels take 5.3)
+        nh = 10
+        host = 0.0
+        late.flush()
+        for _ in range(nh):
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            step()
+            host += time.perf_counter() - t1
+        late.flush()
         torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        step()
-        host += time.perf_counter() - t1
-    late.flush()
-    torch.cuda.synchronize()
-    extra['host_enqueue_ms_per_step'] = round(host / nh * 1e3, 3)
-    if rank == 0 and not args.no_profile:
+        extra['host_enqueue_ms_per_step'] = round(host / nh * 1e3, 3)
+    if args.full and rank == 0 and not args.no_profile:
         # one more forward/backward, replayed op by op with hipEvents on the launch stream
         detail = [] if args.detail else None
         plan, groups = profile_plan(net, x, lib, nat, detail)
@@ -632,7 +648,7 @@ def main():
         extra['kernels'] = {k: {'ms': round(v[0], 3), 'tflops': round(v[1] / (v[0] * 1e-3) / 1e12, 1) if v[0] > 0 and v[1] > 0 else None,
                                 'launches': v[2]} for k, v in sorted(groups.items(), key=lambda kv: -kv[1][0])}
 
-    if rank == 0 and world == 1 and not args.no_profile and not args.no_fp32_reference:
+    if args.full and rank == 0 and world == 1 and not args.no_profile and not args.no_fp32_reference:
         # the same step in the other arithmetic modes, for reference: fp32 MFMA products (the mode the 1e-4 forward bar is
         # written for), fp32 tensors with 3 bf16 products per product (bf16x3, inside that bar), fp32 tensors with plain bf16
         # products, bf16 storage (BASELINE configs[1] as named)
@@ -660,16 +676,16 @@ def main():
                 extra['roofline_fp32']['kernel_time_ms_per_step'] = round(sum(v[0] for v in g32.values()), 3)
         nat.check(lib.dfl_set_math_mode(MATH[args.math][0]), 'dfl_set_math_mode')
 
-    if rank == 0 and world == 1 and not args.no_profile and not args.no_fwd:
+    if args.full and rank == 0 and world == 1 and not args.no_profile and not args.no_fwd:
         extra['fwd_ms_per_img'] = fwd_ms_per_img(lib, nat, dev, args.math)
-    if rank == 0 and world == 1 and not args.no_profile and not args.no_configs3:
+    if args.full and rank == 0 and world == 1 and not args.no_profile and not args.no_configs3:
         del net, opt, x, tseg, theat
         torch.cuda.empty_cache()
         extra['configs3'] = dict(configs3(), math=args.math)
     nat.check(lib.dfl_set_math_mode(mode_before), 'dfl_set_math_mode')
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(B)
 
     if rank == 0:

@@ -73,7 +73,7 @@ def main():
     for k, rec in traffic.items():
         rec['src_sha16'] = _bench.csrc_sha16(k)
     json.dump({'note': 'bytes = (2*FETCH_SIZE + WRITE_SIZE) * 1024, averaged over the launches of each kernel in '
-                       'bench.py --steps 6 --warmup 2; see tools/summarize_profile.py', 'round': tag.split('_')[0],
+                       'bench.py --full --steps 6 --warmup 2; see tools/summarize_profile.py', 'round': tag.split('_')[0],
                'csrc_sha16': _bench.csrc_sha16(), 'kernels': traffic},
               open(os.path.join(d, tag + '_traffic.json'), 'w'), indent=1)
 
