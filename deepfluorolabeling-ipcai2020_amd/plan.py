@@ -6,6 +6,11 @@ Reference being restated: UNet.forward / UNetConvBlock.forward / UNetUpBlock.for
 is NHWC fp32; torch.cat([up, bridge], 1) (unet.py:257) is free because both producers write straight into the two
 channel halves of one buffer (pixel stride 2C); BatchNorm is never applied as a separate pass -- its scale/shift
 ride on the next consumer's loads (see include/dfl_hip.h).
+
+UNetPlan._build records in the order of the network: _levels (sizes, PlanError checks), _alloc_buffers, _down_forward and
+_up_forward (one _block_forward per UNetConvBlock), _heads_forward; with gradients then _grad_arena, _heads_backward (the
+landmark block included), _up_backward and _down_backward (one _block_backward per block, last block first; per layer the
+BatchNorm-backward coefficients, then the gradient launches); last the pack program (_finish_pack) and _grad_ready_ops.
 """
 import ctypes as C
 import os
@@ -15,8 +20,8 @@ import torch
 
 from . import _native as nat
 from ._native import (ConvArgs, WgradArgs, PackJob, BnFinalizeArgs, ColstatsArgs, BnBwdFinalizeArgs, BnReluBwdArgs,
-                      AffineCopyArgs, PoolArgs, HeadFwdArgs, HeadBwdArgs, SumPartialsArgs, PackArgs, BnEvalArgs, UpsampleArgs, BnLiveJob, BnLiveArgs, BnBwdLiveJob, BnBwdLiveArgs,
-                      ReducePartialsArgs, MemsetArgs, ReduceJob, ReduceBatchArgs, Program)
+                      AffineCopyArgs, PoolArgs, HeadFwdArgs, HeadBwdArgs, PackArgs, BnEvalArgs, UpsampleArgs, BnLiveJob, BnLiveArgs,
+                      BnBwdLiveJob, BnBwdLiveArgs, MemsetArgs, ReduceJob, ReduceBatchArgs, Program)
 
 BN_EPS = 1.0e-5
 BN_MOMENTUM = 0.1
@@ -51,7 +56,42 @@ class PlanError(RuntimeError):
 KEEP_GRADS = False
 
 
+class _Layer:
+    """One 3x3 convolution of a block as its backward sees it (UNetPlan._block_forward)."""
+    __slots__ = ('w', 'wname', 'relu', 'inp', 'gin', 'inp_aff', 'r', 'bn', 'live_bwd')
+
+    def __init__(self, w, wname, relu, inp, gin, inp_aff, r, bn, live_bwd):
+        # w / wname: the weight and its parameter prefix; relu: module name of the nn.ReLU behind it; inp: the input Act,
+        # gin: what the convolution gathers from (inp, or its wrapped copy); inp_aff: BatchNorm (scale, shift) applied on
+        # load; r: the saved ReLU output; bn: (gamma, mean, invstd, name) of the BatchNorm behind it, or None; live_bwd:
+        # its backward takes live (sum dy, sum dy*r) totals
+        self.w, self.wname, self.relu, self.inp, self.gin, self.inp_aff = w, wname, relu, inp, gin, inp_aff
+        self.r, self.bn, self.live_bwd = r, bn, live_bwd
+
+
+class _Block:
+    """What the backward of one UNetConvBlock needs from its forward."""
+    __slots__ = ('prefix', 'xin', 'out', 'convs', 'rw', 'last_r', 'last_live')
+
+    def __init__(self, prefix, xin, out):
+        self.prefix, self.xin, self.out = prefix, xin, out
+        self.convs = []           # _Layer per 3x3 convolution, in forward order
+        self.rw = None            # residual 1x1 weight (do_res)
+        self.last_r = None        # saved ReLU output of the last layer if a BatchNorm follows it: the producer of dout leaves sums for it
+        self.last_live = False    # ... and may leave them as live totals
+
+
 class UNetPlan:
+    # Switches: the DFL_* environment knobs are read once, at import; tests flip LIVE_BN, LIVE_HEAD and DPRE_OUT_BYTES.
+    PACK_TILED = os.environ.get('DFL_PACK_TILED', '1') != '0'     # weight layouts that tile into 32 x 32 x C blocks: dfl_pack_weights_tiled
+    FUSE_BRB = os.environ.get('DFL_FUSE_BRB', '1') != '0'         # BatchNorm + ReLU backward inside the weight-/data-gradient staging (bf16 storage)
+    FUSE_DOWN_STATS = os.environ.get('DFL_FUSE_DOWN_STATS', '1') != '0'   # ... and BN-backward sums from the strided-conv data gradient's scatter
+    FLUSH_BYTES = int(float(os.environ.get('DFL_FLUSH_MB', '16')) * (1 << 20))   # queued sums flushed from here (4 / 16 / 64 MB: 0.414 / 0.373 / 0.367 ms per step)
+    DPRE_OUT_BYTES = int(float(os.environ.get('DFL_DPRE_OUT_MB', '12')) * (1 << 20))   # data gradient also writes the operand it forms up to this size
+    LIVE_BN = os.environ.get('DFL_LIVE_BN', '1') != '0'           # BatchNorm statistics completed by their consumers (live totals)
+    LIVE_HEAD = os.environ.get('DFL_LIVE_HEAD', '1') != '0'       # ... and the head's backward kernel adds the sums of its dx itself (no colstats pass)
+    BN_R = 8                                                      # include/dfl_hip.h: DFL_BN_R
+
     def __init__(self, cfg, params, buffers, N, H, W, training, need_grad, device, input_grad=False):
         """cfg: dict of the UNet constructor flags; params / buffers: name -> tensor (module state)."""
         self.cfg = cfg
@@ -69,7 +109,6 @@ class UNetPlan:
         self.bwd = Program() if need_grad else None
         self._prep = Program()          # eval-mode BatchNorm scale / shift of an inference plan: part of its pack program
         self._pack_jobs = []
-        self._pack_dsts = []
         self.busy = False
         self.graph = None               # hipGraph of the forward program (inference plans, captured on first use)
         self.generation = 0
@@ -78,7 +117,7 @@ class UNetPlan:
         self._red_bytes = 0
         self._red_flushes = []          # (index of the batch op in bwd, [dst pointers])
         self.partial_sum_bytes = 0      # bytes of fp32 partial sums the batched reductions of one backward pass read
-        self._side = []                 # weight gradients running on the side stream: dict(done=event, op=index, waited=index|None)
+        self._tiled_host = self._tiled_index = None     # the tiled pack launch, for optim.py (see _finish_pack_tiled)
         self.math = self.lib.dfl_get_math_mode()   # product arithmetic the plan is recorded for (split operand formats)
         # math mode 4, "bf16 storage": internal activations, their gradients and the GEMM copies of the weights are bf16
         # tensors (BASELINE configs[1] as named); statistics, losses, master weights and weight gradients stay fp32
@@ -91,6 +130,9 @@ class UNetPlan:
         self.dbg = {}                   # name -> Act / tensors of intermediate results (introspection for tests, see KEEP_GRADS)
         self.keep_grads = bool(KEEP_GRADS)
         self.pool_in = {}               # level -> Act the max-pool of that level reads
+        # inference plans ask for the latency form of the bf16 convolution (include/dfl_hip.h: a hint the library honours for the
+        # small problems of a batch-1 forward -- the per-image loops of util.py -- and ignores for everything else)
+        self._latency_form = int(not training and not need_grad and os.environ.get('DFL_PLAN_LATENCY_FORM', '1') != '0')
         self._build()
 
     # ------------------------------------------------------------------------------------------ memory
@@ -141,7 +183,7 @@ class UNetPlan:
         dst = self._new((K + 3) // 4 * N * 4)
         # split quads (hi4 | lo4 bf16) when the consuming conv will take the split-bf16 fast path: its input channels
         # (B for a forward operand, A for the transposed ones) must be a multiple of 16 and K large enough for the GEMM
-        split = int(self.math in (1, 3) and cin % 16 == 0 and self.WSPLIT)
+        split = int(self.math in (1, 3) and cin % 16 == 0)
         self._packed_split[dst.data_ptr()] = split
         self._pack_jobs.append((w, dst, A, B, Cc, kind, flip, split))
         return dst
@@ -161,52 +203,36 @@ class UNetPlan:
     def _pack_convT_dgrad(self, w):   # ConvTranspose2d data gradient = conv 2x2 s2 over dy: k = (ab, co), n = ci
         return self._pack(w, 1)
 
+    @staticmethod
+    def _set_pack_job(a, job):
+        """Fill PackJob a from a job of _pack: (src, dst, A, B, C, kind, flip, split)."""
+        src, dst, A, B, Cc, kind, flip, split = job
+        a.src, a.dst, a.A, a.B, a.C, a.kind, a.flip, a.split = src.data_ptr(), dst.data_ptr(), A, B, Cc, kind, flip, split
+
+    def _upload(self, arr):
+        """Address of a device copy of the ctypes array arr, kept alive by the plan."""
+        t = torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(self.dev)
+        self._keep.append(t)
+        return t.data_ptr()
+
     def _finish_pack(self):
-        n = len(self._pack_jobs)
+        """The pack program: the eval-mode BatchNorm prep of an inference plan, then the weight re-layouts."""
         self.pack = Program()
         self.pack.extend(self._prep)
-        if n == 0:
+        if not self._pack_jobs:
             return
-        if not self.PACK_OVERLAP and self.PACK_TILED:
+        if self.PACK_TILED:
             self._finish_pack_tiled()
-            return
-        arr = (PackJob * n)()
-        mx = 0
-        for i, (src, dst, A, B, Cc, kind, flip, split) in enumerate(self._pack_jobs):
-            arr[i].src, arr[i].dst = src.data_ptr(), dst.data_ptr()
-            arr[i].A, arr[i].B, arr[i].C, arr[i].kind, arr[i].flip, arr[i].split = A, B, Cc, kind, flip, split
-            mx = max(mx, A * B * Cc)
-        raw = np.frombuffer(bytes(arr), dtype=np.uint8).copy()
-        self._jobs_dev = torch.from_numpy(raw).to(self.dev)
-        self._keep.append(self._jobs_dev)
-        nf = getattr(self, '_n_fwd_pack', n)
-        if not self.PACK_OVERLAP or self.bwd is None or nf in (0, n):
-            self.pack.add(PackArgs(jobs_dev=self._jobs_dev.data_ptr(), max_elems=mx, njobs=n))
-            return
-        # Only what the FIRST forward layers read is packed on the main stream.  The side stream -- forked behind the
-        # optimizer step -- packs the large forward layouts of the deep levels (9/10 of the bytes: the forward program waits
-        # for them in front of its first deep layer, about a millisecond of shallow-level kernels later) and then the layouts
-        # only the backward pass reads (flipped / transposed data-gradient operands; the backward program starts by waiting
-        # for those): an HBM-bound kernel next to latency-bound convolutions.
-        def mx_of(jobs):
-            return max(A * B * Cc for (_, _, A, B, Cc, _, _, _) in jobs)
-        jobs = self._pack_jobs
-        nd = self._n_deep_pack
-        ns = nf - nd                         # (_order_pack_jobs: shallow forward jobs, deep forward jobs, backward jobs)
-        sz = C.sizeof(PackJob)
-        base = self._jobs_dev.data_ptr()
-        self.pack.record(self.EV_PACK_FORK, stream=0)
-        self.pack.wait(self.EV_PACK_FORK, stream=1)
-        if ns > 0:
-            self.pack.add(PackArgs(jobs_dev=base, max_elems=mx_of(jobs[:ns]), njobs=ns))
-        if nd > 0:
-            self.pack.add(PackArgs(jobs_dev=base + ns * sz, max_elems=mx_of(jobs[ns:nf]), njobs=nd), stream=1)
-            self.pack.record(self.EV_PACK_DEEP, stream=1)
-        self.pack.add(PackArgs(jobs_dev=base + nf * sz, max_elems=mx_of(jobs[nf:]), njobs=n - nf), stream=1)
-        self.pack.record(self.EV_PACK_DONE, stream=1)
-        self._bwd_needs_pack_wait = True
+        else:
+            self._add_pack_launch(self._pack_jobs)
 
-    PACK_TILED = os.environ.get('DFL_PACK_TILED', '1') != '0'
+    def _add_pack_launch(self, jobs):
+        """One dfl_pack_weights launch over a flat PackJob array."""
+        arr = (PackJob * len(jobs))()
+        for a, job in zip(arr, jobs):
+            self._set_pack_job(a, job)
+        mx = max(A * B * Cc for (_, _, A, B, Cc, _, _, _) in jobs)
+        self.pack.add(PackArgs(jobs_dev=self._upload(arr), max_elems=mx, njobs=len(jobs)))
 
     def _finish_pack_tiled(self):
         """One-stream pack (round 4; round 5: every arithmetic, not only bf16 storage): the layouts of parameters that tile into 32 x 32 x C blocks go through
@@ -224,64 +250,22 @@ class UNetPlan:
                     tiled.append(by_src[k])
             else:
                 rest.append(job)
-        def to_dev(arr):
-            t = torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(self.dev)
-            self._keep.append(t)
-            return t
-        self._tiled_host, self._tiled_index = None, None      # what optim.py needs to update the weights inside this launch
         if tiled:
             arr = (PackJob * len(tiled))()
             tiles = 0
-            for i, group in enumerate(tiled):
-                src, dst, A, B, Cc, kind, flip, split = group[0]
-                a = arr[i]
-                a.src, a.dst, a.A, a.B, a.C, a.kind, a.flip, a.split = src.data_ptr(), dst.data_ptr(), A, B, Cc, kind, flip, split
+            for a, group in zip(arr, tiled):
+                self._set_pack_job(a, group[0])
                 if len(group) > 1:
                     a.dst2, a.kind2, a.flip2, a.split2 = group[1][1].data_ptr(), group[1][5], group[1][6], group[1][7]
                 a.first_tile = tiles
-                tiles += (A // 32) * (B // 32)
-            self._tiled_index = len(self.pack)
-            self.pack.add(PackArgs(jobs_dev=to_dev(arr).data_ptr(), max_elems=tiles, njobs=len(tiled), tiled=1))
+                tiles += (a.A // 32) * (a.B // 32)
+            self._tiled_index = len(self.pack)       # what optim.py needs to update the weights inside this launch
+            self.pack.add(PackArgs(jobs_dev=self._upload(arr), max_elems=tiles, njobs=len(tiled), tiled=1))
             srcs = [g[0][0].data_ptr() for g in tiled]
             if len(set(srcs)) == len(srcs):                   # (a parameter with a third layout: its second record would read
                 self._tiled_host = (bytes(arr), len(tiled), tiles, {g[0][0].data_ptr(): g[0][0].numel() for g in tiled})   # what the first one writes)
         if rest:
-            arr = (PackJob * len(rest))()
-            mx = 0
-            for i, (src, dst, A, B, Cc, kind, flip, split) in enumerate(rest):
-                arr[i].src, arr[i].dst = src.data_ptr(), dst.data_ptr()
-                arr[i].A, arr[i].B, arr[i].C, arr[i].kind, arr[i].flip, arr[i].split = A, B, Cc, kind, flip, split
-                mx = max(mx, A * B * Cc)
-            self.pack.add(PackArgs(jobs_dev=to_dev(arr).data_ptr(), max_elems=mx, njobs=len(rest)))
-
-    DEEP_PACK_ELEMS = 256 * 1024   # forward layouts from this size on are packed on the side stream (0: none)
-
-    def _order_pack_jobs(self):
-        """Forward jobs: small ones first, then -- from the first large one in forward order on -- the rest ("deep": packed on
-        the side stream); a wait for them goes in front of the first forward op that reads one."""
-        nf = self._n_fwd_pack
-        self._n_deep_pack = 0
-        if not self.PACK_OVERLAP or self.bwd is None or self.DEEP_PACK_ELEMS <= 0 or nf == 0:
-            return
-        fwd_jobs = self._pack_jobs[:nf]
-        first = next((i for i, j in enumerate(fwd_jobs) if j[2] * j[3] * j[4] >= self.DEEP_PACK_ELEMS), None)
-        if first is None or first == 0:
-            return
-        deep = {fwd_jobs[i][1].data_ptr() for i in range(first, nf) if fwd_jobs[i][2] * fwd_jobs[i][3] * fwd_jobs[i][4] >= self.DEEP_PACK_ELEMS}
-        # small weights that come later in forward order (decoder levels, heads) stay on the main stream
-        shallow = [j for j in fwd_jobs if j[1].data_ptr() not in deep]
-        deepj = [j for j in fwd_jobs if j[1].data_ptr() in deep]
-        self._pack_jobs[:nf] = shallow + deepj
-        self._n_deep_pack = len(deepj)
-        for idx, st in enumerate(self.fwd.structs):
-            if isinstance(st, ConvArgs) and st.w in deep:
-                self.fwd.insert(idx, nat.SyncArgs(event=self.EV_PACK_DEEP), nat.OP_WAIT, 0)
-                break
-
-    PACK_OVERLAP = False     # (round 4: off -- with the BatchNorm launches gone the one-stream form is 1.2 % faster)
-    WSPLIT = True      # split-bf16 modes: weights split once by the pack kernel
-    DSPLIT = True      # ... and the BatchNorm/ReLU backward output split once by its producer
-    EV_PACK_FORK, EV_PACK_DONE, EV_PACK_DEEP = 60000, 60001, 60002
+            self._add_pack_launch(rest)
 
     # ------------------------------------------------------------------------------------------ op helpers
     def _conv(self, prog, x, w, y, KH, KW, stride, pad, Ntot, bias=None, in_aff=None, relu=0, add=None,
@@ -325,9 +309,7 @@ class UNetPlan:
         a.Hout, a.Wout = (y.H, y.W) if Hout is None else (Hout, Wout)
         a.Ntot, a.ldy = Ntot, y.ld
         a.relu, a.accumulate, a.scatter2x2 = relu, accumulate, scatter
-        # inference plans ask for the latency form of the bf16 convolution (include/dfl_hip.h: a hint the library honours for the
-        # small problems of a batch-1 forward -- the per-image loops of util.py -- and ignores for everything else)
-        a.latency_form = 1 if (not self.training and not self.need_grad and os.environ.get('DFL_PLAN_LATENCY_FORM', '1') != '0') else 0
+        a.latency_form = self._latency_form
         self._out_aff_taken = False
         if out_aff is not None:
             # the consumer's eval-mode BatchNorm applied by this (producing) kernel: only the latency form does that
@@ -357,24 +339,7 @@ class UNetPlan:
         prog.add(a)
         return partials
 
-    # A layer's weight gradient and data gradient both read dpre and are independent: for all but the largest layers
-    # neither fills the 256 CUs on its own at batch 16, so the weight gradient goes to the library's side stream
-    # (fork after dpre is written; joined before dpre's buffer is rewritten two layers later, before a batched sum
-    # reads its slices, and at the end of backward).  Measured: +10 % on an isolated pair for 24x24..96x96 layers, -8 % at
-    # 192x192 -- but nothing inside the real backward pass (both kernels just run slower side by side), so it is off by default.
-    OUT_AFF = True          # inference: a block's inner BatchNorm applied by the producing kernel (measured: affine on load +3 us per 3x3 layer)
-    PAIRS = True            # inference: a block's last 3x3 convolution and its 1x1 as one launch (measured: -4.5 us per block end)
-    SIDE_STREAM = False     # off: inside the whole backward pass the pair runs no faster (r01)
-    SIDE_MAX_PIXELS = 16 * 96 * 96
-
-    def _side_join(self, prog, buf=None):
-        """Main stream waits for the side-stream weight gradients emitted so far (all, or those reading buffer `buf`)."""
-        todo = [e for e in self._side if e['waited'] is None and (buf is None or e['buf'] == buf)]
-        for e in todo:
-            e['waited'] = len(prog.structs)
-            prog.wait(e['done'], stream=0)
-
-    def _wgrad(self, prog, g, d, dw, KH, KW, stride, pad, Hout, Wout, in_aff=None, side=False, side_buf=None, d_split=0, brb=None,
+    def _wgrad(self, prog, g, d, dw, KH, KW, stride, pad, Hout, Wout, in_aff=None, d_split=0, brb=None,
                bias_out=None, bias_plain=False):
         """bias_plain: d is the operand itself (materialised through dfl_conv_args.x_out) and the kernel still leaves its column
         sums -- the bias gradient -- per pixel slice."""
@@ -408,39 +373,17 @@ class UNetPlan:
         n = d.C * g.C * KH * KW
         if s > 1:
             big = 4 * n >= self.FLUSH_BYTES
-            part = self._wg_partial(s * n) if big else self._new(s * n)   # deferred sums keep their own slices
+            part = self._shared_scratch('wg_partial', s * n) if big else self._new(s * n)   # deferred sums keep their own slices
             a.partial = part.data_ptr()
-        if side:
-            k = len(self._side)
-            prog.record(2 * k, stream=0)            # dpre is complete on the main stream
-            prog.wait(2 * k, stream=1)
-            self._side.append(dict(done=2 * k + 1, op=len(prog.structs), waited=None, buf=side_buf))
-            prog.add(a, stream=1)
-            prog.record(2 * k + 1, stream=1)
-        else:
-            prog.add(a)
+        prog.add(a)
         if bias_job is not None:
             self._red_pending.append(bias_job)
             self._red_bytes += 4 * d.C
         if s > 1:
-            # the caller flushes (self._maybe_flush) once the main-stream work that may overlap has been emitted
-            self._red_pending.append((part.data_ptr(), dw.data_ptr(), n, n, s, KH * KW))
-            self._red_bytes += 4 * n
-            if not side:
-                self._maybe_flush(prog)
+            self._defer_sum(prog, part.data_ptr(), dw.data_ptr(), n, n, s, KH * KW)
 
     # Small sums (bias gradients, pixel-slice partials of narrow layers) are not launched one by one: they queue up
     # and one dfl_reduce_batch finishes the queue once FLUSH_BYTES of gradient are waiting (and at the end of backward).
-    FLUSH_BYTES = int(float(os.environ.get('DFL_FLUSH_MB', '16')) * (1 << 20))   # (4 / 16 / 64 MB measured: 0.414 / 0.373 / 0.367 ms of sums per step)
-    FUSE_BWD_STATS = True
-    FUSE_DOWN_STATS = os.environ.get('DFL_FUSE_DOWN_STATS', '1') != '0'   # ... and the strided-conv data gradient's scatter (bf16)
-    FUSE_BRB = os.environ.get('DFL_FUSE_BRB', '1') != '0'      # BatchNorm + ReLU backward inside the weight-/data-gradient staging (bf16 storage)
-    # the data-gradient kernel also WRITES the operand it forms (dfl_conv_args.x_out) for layers whose tensor is at most this large:
-    # the weight gradient then reads one plain tensor instead of forming the operand again in each of its (cm, cg) tiles
-    DPRE_OUT_BYTES = int(float(os.environ.get('DFL_DPRE_OUT_MB', '12')) * (1 << 20))
-    RES_DGRAD_LAST = True   # residual 1x1 data gradient accumulates onto the 3x3 one (not the reverse)
-    FUSE_COLSUMS = True   # sums across block boundaries (see the backward program)
-
     def _defer_sum(self, prog, src, dst, n, stride, count, T=1):
         self._red_pending.append((src, dst, n, stride, count, T))
         self._red_bytes += 4 * n
@@ -455,34 +398,22 @@ class UNetPlan:
         jobs = self._red_pending
         if not jobs:
             return
-        self._side_join(prog)       # the slices of side-stream weight gradients must be complete
         arr = (ReduceJob * len(jobs))()
         blocks = 0
-        for i, (src, dst, n, stride, count, T) in enumerate(jobs):
-            arr[i].src, arr[i].dst, arr[i].n, arr[i].stride, arr[i].count, arr[i].first_block = src, dst, n, stride, count, blocks
-            arr[i].T = T
+        for a, (src, dst, n, stride, count, T) in zip(arr, jobs):
+            a.src, a.dst, a.n, a.stride, a.count, a.first_block, a.T = src, dst, n, stride, count, blocks, T
             blocks += nat.check(self.lib.dfl_reduce_job_blocks(n, count), 'dfl_reduce_job_blocks')
-        dev = torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(self.dev)
-        self._keep.append(dev)
         self._red_flushes.append((len(prog.structs), [j[1] for j in jobs]))
         self.partial_sum_bytes += sum(4 * n * count for (_, _, n, _, count, _) in jobs)
-        prog.add(ReduceBatchArgs(jobs_dev=dev.data_ptr(), njobs=len(jobs), total_blocks=blocks))
+        prog.add(ReduceBatchArgs(jobs_dev=self._upload(arr), njobs=len(jobs), total_blocks=blocks))
         self._red_pending, self._red_bytes = [], 0
 
     def _dz_for(self, g, N, H, W, Cc, fused):
         """Scratch for the data gradient a layer hands to the layer below.  With the BatchNorm + ReLU backward folded into the
         data-gradient kernel that kernel READS the incoming gradient g while it writes: never the same buffer -- 'dz' and 'dpre0'
         (idle in that mode) alternate."""
-        key = 'dz'
-        if fused and g.t is self._scratch.get('dz'):
-            key = 'dpre0'
-        if fused:
-            self._side_join(self.bwd, buf=key)      # side-stream weight gradients that still read this scratch
+        key = 'dpre0' if fused and g.t is self._scratch.get('dz') else 'dz'
         return self._scratch_act(key, N, H, W, Cc)
-
-    LIVE_BN = os.environ.get('DFL_LIVE_BN', '1') != '0'     # BatchNorm statistics completed by their consumers (bf16 patch kernels)
-    LIVE_HEAD = os.environ.get('DFL_LIVE_HEAD', '1') != '0'   # ... and the head's backward kernel adds the sums of its dx itself (no colstats pass)
-    BN_R = 8                                                # include/dfl_hip.h: DFL_BN_R
 
     def _bn_totals(self, Cc, bwd=False):
         """Address of [BN_R][2][C] doubles inside the plan's totals arena of the forward (backward) pass, zeroed by one memset at
@@ -490,9 +421,7 @@ class UNetPlan:
         need = self.BN_R * 2 * Cc
         ar = self._tot_bwd if bwd else self._tot_fwd
         if ar[0] is None:
-            cfg = self.cfg
-            chans = [2 ** (cfg['wf'] + i) for i in range(cfg['depth'])]
-            ar[0] = self._new(sum(chans) * cfg['block_depth'] * 2 * self.BN_R * 2, torch.float64)
+            ar[0] = self._new(sum(self.chans) * self.bd * 2 * self.BN_R * 2, torch.float64)
         assert ar[1] + need <= ar[0].numel()
         ptr = ar[0].data_ptr() + 8 * ar[1]
         ar[1] += need
@@ -504,47 +433,35 @@ class UNetPlan:
         if not jobs:
             return
         arr = (BnBwdLiveJob * len(jobs))()
-        for i, j in enumerate(jobs):
-            a = arr[i]
+        for a, j in zip(arr, jobs):
             a.totals, a.save_mean, a.save_invstd = j['tot'], j['mean'].data_ptr(), j['invstd'].data_ptr()
             a.dgamma, a.dbeta, a.sum_out, a.C = j['dgamma'].data_ptr(), j['dbeta'].data_ptr(), nat.ptr(j['sum_out']), j['C']
-        dev = torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(self.dev)
-        self._keep.append(dev)
         dsts = [j[k].data_ptr() for j in jobs for k in ('dgamma', 'dbeta', 'sum_out') if j[k] is not None]
         self._red_flushes.append((len(prog.structs), dsts))
-        prog.add(BnBwdLiveArgs(jobs_dev=dev.data_ptr(), njobs=len(jobs), max_C=max(j['C'] for j in jobs)))
+        prog.add(BnBwdLiveArgs(jobs_dev=self._upload(arr), njobs=len(jobs), max_C=max(j['C'] for j in jobs)))
         self._live_bwd_pending = []
 
-    def _finish_live_bn(self, fwd, index=None):
+    def _finish_live_bn(self):
         """The zero fill in front of the forward program and the one batched finalize behind its last BatchNorm layer."""
-        if not self._live_jobs:
+        jobs = self._live_jobs
+        if not jobs:
             return
-        arr = (BnLiveJob * len(self._live_jobs))()
-        for i, j in enumerate(self._live_jobs):
-            a = arr[i]
+        arr = (BnLiveJob * len(jobs))()
+        for a, j in zip(arr, jobs):
             a.totals, a.gamma, a.beta = j['totals'], j['gamma'].data_ptr(), j['beta'].data_ptr()
             a.running_mean = self.Bf[j['bname'] + '.running_mean'].data_ptr()
             a.running_var = self.Bf[j['bname'] + '.running_var'].data_ptr()
             a.num_batches_tracked = self.Bf[j['bname'] + '.num_batches_tracked'].data_ptr()
             a.scale, a.shift, a.save_mean, a.save_invstd = (j[k].data_ptr() for k in ('scale', 'shift', 'mean', 'invstd'))
             a.count, a.C, a.eps, a.momentum = j['count'], j['C'], BN_EPS, BN_MOMENTUM
-        dev = torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(self.dev)
-        self._keep.append(dev)
-        fwd.add(BnLiveArgs(jobs_dev=dev.data_ptr(), njobs=len(self._live_jobs), max_C=max(j['C'] for j in self._live_jobs)))
-        fwd.insert(0, MemsetArgs(ptr=self._tot_fwd[0].data_ptr(), bytes=8 * self._tot_fwd[1]))
+        self.fwd.add(BnLiveArgs(jobs_dev=self._upload(arr), njobs=len(jobs), max_C=max(j['C'] for j in jobs)))
+        self.fwd.insert(0, MemsetArgs(ptr=self._tot_fwd[0].data_ptr(), bytes=8 * self._tot_fwd[1]))
 
     def _shared_scratch(self, key, nelem):
         t = self._scratch.get(key)
         if t is None or t.numel() < nelem:
             t = self._new(nelem)
             self._scratch[key] = t
-        return t
-
-    def _wg_partial(self, nelem):
-        t = self._scratch.get('wg_partial')
-        if t is None or t.numel() < nelem:
-            t = self._new(nelem)
-            self._scratch['wg_partial'] = t
         return t
 
     def _colsum(self, prog, a, out):
@@ -596,422 +513,283 @@ class UNetPlan:
 
     # ------------------------------------------------------------------------------------------ build
     def _build(self):
+        self._levels()
+        self._alloc_buffers()
+        self._down_forward()
+        self._up_forward()
+        self._finish_live_bn()
+        self._heads_forward()
+        if self.need_grad:
+            self._grad_arena()
+            dout, sums = self._heads_backward()
+            dout, sums = self._up_backward(dout, sums)
+            self._down_backward(dout, sums)
+            self._finish_backward()
+        self._finish_pack()
+        if self.need_grad:
+            self._grad_ready_ops()
+
+    def _levels(self):
+        """Architecture flags, channel count and spatial size of every level (input / output of its block, down then up)."""
         cfg = self.cfg
-        depth, wf = cfg['depth'], cfg['wf']
-        pad = 1 if cfg['padding'] else 0
-        bd = cfg['block_depth']
-        bn = cfg['batch_norm']
-        do_res = cfg['do_res']
-        circ = bool(pad) and cfg.get('pad_mode', 'zeros') == 'circular'
-        upsample = cfg.get('up_mode', 'upconv') == 'upsample'
-        self.circular = circ
-        N = self.N
-        chans = [2 ** (wf + i) for i in range(depth)]
-        for c in chans:
+        self.depth, self.bd, self.bn, self.do_res = cfg['depth'], cfg['block_depth'], cfg['batch_norm'], cfg['do_res']
+        self.pad = 1 if cfg['padding'] else 0
+        self.circular = bool(self.pad) and cfg.get('pad_mode', 'zeros') == 'circular'
+        self.upsample = cfg.get('up_mode', 'upconv') == 'upsample'
+        self.chans = [2 ** (cfg['wf'] + i) for i in range(self.depth)]
+        for c in self.chans:
             if c % 4 != 0:
                 raise PlanError('channel counts must be multiples of 4 (wf >= 2)')
             if self.bf16 and c % 16 != 0:
                 raise PlanError('math mode 4 (bf16 storage) needs channel counts that are multiples of 16 (wf >= 4); this '
                                 'network has a %d-channel level' % c)
-        shrink = 0 if pad else 2 * bd
-        # spatial size of every level (input / output of the block), down then up
-        hin, win = [self.H], [self.W]
-        hout, wout = [], []
-        for i in range(depth):
-            ho, wo = hin[i] - shrink, win[i] - shrink
+        self.shrink = 0 if self.pad else 2 * self.bd
+        self.hin, self.win, self.hout, self.wout = [self.H], [self.W], [], []
+        for i in range(self.depth):
+            ho, wo = self.hin[i] - self.shrink, self.win[i] - self.shrink
             if ho < 1 or wo < 1:
                 raise PlanError('input %dx%d too small for this architecture' % (self.H, self.W))
-            hout.append(ho)
-            wout.append(wo)
-            if i != depth - 1:
+            self.hout.append(ho)
+            self.wout.append(wo)
+            if i != self.depth - 1:
                 if ho < 2 or wo < 2:
                     raise PlanError('input %dx%d too small for this architecture' % (self.H, self.W))
-                hin.append(ho // 2)
-                win.append(wo // 2)
-        if do_res and shrink != 0:
+                self.hin.append(ho // 2)
+                self.win.append(wo // 2)
+        if self.do_res and self.shrink != 0:
             raise PlanError('do_res=True needs padding=True: the 1x1 residual and the unpadded 3x3 stack differ in '
                             'size (the reference fails at unet.py:231 for the same reason)')
+        self.up_hw = []          # size of the up-sampled tensor of up block j (level i = depth-2-j)
+        uh, uw = self.hout[-1], self.wout[-1]
+        for i in reversed(range(self.depth - 1)):
+            uh, uw = 2 * uh, 2 * uw
+            self.up_hw.append((uh, uw))
+            uh, uw = uh - self.shrink, uw - self.shrink
 
-        # backward scratch: sized for the largest [M][C] any block produces
+    def _alloc_buffers(self):
+        """Backward scratch, the input activation, and the concat buffers of the up path: allocated up front so that the
+        down blocks write their bridge half directly."""
+        N, chans = self.N, self.chans
         if self.need_grad:
-            mx = 0
-            h, w = self.H, self.W
-            sizes = []
-            for i in range(depth):
-                sizes.append((N * hin[i] * win[i], chans[i]))
-            uh, uw = hout[depth - 1], wout[depth - 1]
-            for i in reversed(range(depth - 1)):
-                uh, uw = 2 * uh, 2 * uw
-                sizes.append((N * uh * uw, chans[i]))
-                uh, uw = uh - shrink, uw - shrink
-            mx = max(m * c for m, c in sizes)
+            # backward scratch: sized for the largest [M][C] any block produces
+            sizes = [N * self.hin[i] * self.win[i] * chans[i] for i in range(self.depth)]
+            sizes += [N * uh * uw * chans[self.depth - 2 - j] for j, (uh, uw) in enumerate(self.up_hw)]
+            mx = max(sizes)
             self._scratch['dpre0'] = self._new(mx, self.adt)
             self._scratch['dpre1'] = self._new(mx, self.adt)
             self._dpre_turn = 0
             self._scratch['dz'] = self._new(mx, self.adt)
             if self.bf16 and self.FUSE_BRB and self.DPRE_OUT_BYTES > 0:
                 self._scratch['dmat'] = self._new(mx, self.adt)   # operand materialised by the data-gradient kernel (x_out)
-
-        fwd, bwd = self.fwd, self.bwd
-        Cin0 = cfg['in_channels']
+        Cin0 = self.cfg['in_channels']
         if self.bf16 and Cin0 > 4:
             # multi-channel inputs enter the patch-resident kernels as bf16 (the 1..4-channel case keeps the fp32 image:
             # the direct first-layer kernels read it as is)
             if Cin0 % 16 != 0:
                 raise PlanError('math mode 4 (bf16 storage) takes 1..4 or a multiple of 16 input channels')
             self.x_in = self._new(N * self.H * self.W * Cin0, torch.bfloat16)
-            x0 = Act(self.x_in, self.x_in.data_ptr(), Cin0, N, self.H, self.W, Cin0, 2)
+            self._x0 = Act(self.x_in, self.x_in.data_ptr(), Cin0, N, self.H, self.W, Cin0, 2)
         else:
             self.x_in = self._new(N * self.H * self.W * Cin0)
-            x0 = Act(self.x_in, self.x_in.data_ptr(), Cin0, N, self.H, self.W, Cin0)
-
-        # cat buffers for the up path are allocated up front so that down blocks can write their bridge half directly
-        up_hw = []           # size of the up-sampled tensor at level i (i = depth-2 .. 0)
-        uh, uw = hout[depth - 1], wout[depth - 1]
-        for i in reversed(range(depth - 1)):
-            uh, uw = 2 * uh, 2 * uw
-            up_hw.append((uh, uw))
-            uh, uw = uh - shrink, uw - shrink
-        self.last_hw = (uh, uw)
-        cat = {}
-        dcat = {}
-        direct_bridge = {}
-        for j, i in enumerate(reversed(range(depth - 1))):
-            ch, cw = up_hw[j]
-            cat[i] = self._act(N, ch, cw, 2 * chans[i])
-            direct_bridge[i] = (ch == hout[i] and cw == wout[i])
+            self._x0 = Act(self.x_in, self.x_in.data_ptr(), Cin0, N, self.H, self.W, Cin0)
+        self.cat, self.dcat, self.direct_bridge = {}, {}, {}
+        for j, i in enumerate(reversed(range(self.depth - 1))):
+            ch, cw = self.up_hw[j]
+            self.cat[i] = self._act(N, ch, cw, 2 * chans[i])
+            self.direct_bridge[i] = (ch == self.hout[i] and cw == self.wout[i])
             if self.need_grad:
-                dcat[i] = self._act(N, ch, cw, 2 * chans[i])
+                self.dcat[i] = self._act(N, ch, cw, 2 * chans[i])
 
-        bwd_stages = []      # closures appended in forward order, executed reversed
+    # ------------------------------------------------------------------ one residual conv block, forward
+    def _block_forward(self, prefix, xin, out, first=False):
+        """Forward ops of UNetConvBlock `prefix` reading xin, writing out; returns the _Block its backward needs."""
+        P, fwd, N, Cout = self.P, self.fwd, self.N, out.C
+        blk = _Block(prefix, xin, out)
+        cur, cur_aff, cur_live = xin, None, None
+        step = 3 if self.bn else 2
+        for d in range(self.bd):
+            wname = '%s.block.%d' % (prefix, d * step)
+            w, b = P[wname + '.weight'], P[wname + '.bias']
+            wp = self._pack_conv_fwd(w)
+            Ho, Wo = cur.H - (0 if self.pad else 2), cur.W - (0 if self.pad else 2)
+            r = self._act(N, Ho, Wo, Cout)
+            gin = self._wrap_pad(fwd, cur) if self.circular else cur     # what the convolution (and its weight gradient) gathers from
+            live, live_bwd = self._live_stats(d, xin, cur, gin, Cout, first)
+            tot = self._bn_totals(Cout) if live else None
+            # inference: the BatchNorm between this convolution and the block's next one is applied by THIS kernel where it runs in
+            # latency form (dfl_conv_args.out_scale: the consumer's two roundings, bit for bit) -- the consumer then reads its operand
+            # plain instead of converting 8 channels per lane and k-step on its way into the matrix instruction
+            pre_aff = None
+            if self.bn and not self.training and not self.need_grad and not self.circular and self.pad == 1 and d < self.bd - 1:
+                pre_aff = (self._new(Cout), self._new(Cout))
+            part = self._conv(fwd, gin, wp, r, 3, 3, 1, 0 if self.circular else self.pad, Cout, bias=b,
+                              in_aff=None if cur_live is not None else cur_aff, in_live=cur_live, relu=1,
+                              stats=self.bn and self.training, stat_totals=tot, out_aff=pre_aff)
+            out_aff_taken = pre_aff is not None and self._out_aff_taken
+            relu = '%s.block.%d' % (prefix, d * step + 1)     # module name of the nn.ReLU (tests read its mask)
+            aff, bnrec, cur_live = None, None, None
+            if self.bn:
+                bname = '%s.block.%d' % (prefix, d * step + 2)
+                aff, bnrec = self._bn_forward(bname, part, tot, pre_aff if out_aff_taken else None, N * Ho * Wo, Cout)
+                if live:
+                    cur_live = (tot, P[bname + '.weight'], P[bname + '.bias'], N * Ho * Wo)
+            blk.convs.append(_Layer(w, wname, relu, cur, gin, cur_aff, r, bnrec, live_bwd))
+            self.relu_out[relu] = r
+            cur, cur_aff = r, (None if out_aff_taken else aff)       # (out_aff_taken: r holds BN(ReLU(.)) already)
+        assert cur.H == xin.H - self.shrink and cur.W == xin.W - self.shrink
+        if self.do_res:
+            blk.rw, rb = P[prefix + '.res_conv1x1.weight'], P[prefix + '.res_conv1x1.bias']
+            self._conv(fwd, xin, self._pack_conv_fwd(blk.rw), out, 1, 1, 1, 0, Cout, bias=rb,
+                       add=cur, add_aff=None if cur_live is not None else cur_aff, add_live=cur_live)
+            if not self.training and not self.need_grad:
+                self._pair_last_two()
+        else:
+            a = AffineCopyArgs(x=cur.ptr, y=out.ptr, N=N, H=cur.H, W=cur.W, C=Cout, ldx=cur.ld, xH=cur.H, xW=cur.W,
+                               ldy=out.ld, yH=out.H, yW=out.W, bf16=cur.bf16)
+            if cur_aff is not None:
+                a.scale, a.shift = cur_aff[0].data_ptr(), cur_aff[1].data_ptr()
+            fwd.add(a)
+        self.dbg['out:' + prefix] = out
+        self.dbg['xin:' + prefix] = xin
+        # pre-BatchNorm output of the block's last conv: what a producer of this block's dout needs for fused_in ...
+        last = blk.convs[-1]
+        blk.last_r = last.r if last.bn is not None else None
+        blk.last_live = bool(last.bn is not None and last.live_bwd)      # ... and may leave them as live totals
+        return blk
 
-        # ------------------------------------------------------------------ one residual conv block
-        def block(prefix, xin, out, first=False):
-            """Forward ops of UNetConvBlock `prefix` reading xin, writing out; returns a backward emitter."""
-            P = self.P
-            Cout = out.C
-            Hb, Wb = xin.H - shrink, xin.W - shrink
-            convs = []
-            cur, cur_aff, cur_live = xin, None, None
-            step = 3 if bn else 2
-            patch_in = lambda t: bool(t.bf16) and t.C % 16 == 0            # a convolution reading t runs the bf16 patch kernels
-            for d in range(bd):
-                wname = '%s.block.%d' % (prefix, d * step)
-                w, b = P[wname + '.weight'], P[wname + '.bias']
-                wp = self._pack_conv_fwd(w)
-                Ho, Wo = cur.H - (0 if pad else 2), cur.W - (0 if pad else 2)
-                r = self._act(N, Ho, Wo, Cout)
-                gin = self._wrap_pad(fwd, cur) if circ else cur          # what the convolution (and its weight gradient) gathers from
-                # Live statistics (round 4): this layer's BatchNorm is not finalised by a launch between producer and consumer --
-                # the producing patch kernel adds its sums to the layer's totals, the consuming patch kernel (next 3x3, or the
-                # residual 1x1 whose epilogue adds BN(r)) derives scale / shift itself; ONE batched launch at the end of the forward
-                # pass leaves the vectors the backward pass and the module state need.  Both kernels must be patch kernels.
-                # (the network's first block: its 1-channel layers run the direct kernels, which take part as well -- the 3x3 row
-                # form as a producer, the 1x1 form as the consumer of "+ BN(r)", the 3x3 weight gradient as a consumer of A, B, C)
-                one_ch = lambda t: (not t.bf16) and t.C == 1 and Cout in (8, 16, 32, 64) and pad == 1
-                live = (self.LIVE_BN and bn and self.training and self.bf16 and not circ and (patch_in(gin) or one_ch(gin))
-                        and (d < bd - 1 or (do_res and (patch_in(xin) or one_ch(xin)))))
-                # (round 5) fp32 tensors: the GEMM kernels take part as well -- producer: any of them (statistics tail, K-slice finish
-                # kernel); consumers: the fast gather of the next 3x3 (its scale / shift table in LDS) and the residual 1x1's "+ BN(r)"
-                # (ADVICE r05: the consumer's table form needs the FAST gather, which needs tensors below 2 GiB -- a larger activation keeps
-                # the finalize launch and the generic kernel instead of failing in dfl_conv2d)
-                small = lambda t: t.N * t.H * t.W * t.ld * 4 < (1 << 31) - 4096
-                gemm_in = lambda t: (not t.bf16) and t.C % 16 == 0 and small(t)
-                if (self.LIVE_BN and bn and self.training and not self.bf16 and not circ and gemm_in(gin) and Cout % 16 == 0
-                        and gin.N * gin.H * gin.W * 2 * Cout * 4 < (1 << 31) - 4096 and (d < bd - 1 or do_res)):
-                    live = True
-                tot = self._bn_totals(Cout) if live else None
-                live_bwd = (self.LIVE_BN and bn and self.training and self.bf16 and self.FUSE_BRB and self.FUSE_BWD_STATS and not circ
-                            and self.need_grad and (patch_in(cur) or (one_ch(cur) and d == 0 and first and not self.input_grad)))
-                # (this layer's backward can take live (sum dy, sum dy*r): its consumers derive the coefficients)
-                # inference: the BatchNorm between this convolution and the block's next one is applied by THIS kernel where it runs in
-                # latency form (dfl_conv_args.out_scale: the consumer's two roundings, bit for bit) -- the consumer then reads its operand
-                # plain instead of converting 8 channels per lane and k-step on its way into the matrix instruction
-                pre_aff = None
-                if (bn and self.OUT_AFF and not self.training and not self.need_grad and not circ and pad == 1 and d < bd - 1):
-                    pre_aff = (self._new(Cout), self._new(Cout))
-                part = self._conv(fwd, gin, wp, r, 3, 3, 1, 0 if circ else pad, Cout, bias=b,
-                                   in_aff=None if cur_live is not None else cur_aff, in_live=cur_live, relu=1,
-                                   stats=bn and self.training, stat_totals=tot, out_aff=pre_aff)
-                out_aff_taken = pre_aff is not None and self._out_aff_taken
-                aff = None
-                bnrec = None
-                if bn:
-                    bname = '%s.block.%d' % (prefix, d * step + 2)
-                    gamma, beta = P[bname + '.weight'], P[bname + '.bias']
-                    scale, shift = pre_aff if out_aff_taken else (self._new(Cout), self._new(Cout))
-                    mean, invstd = self._new(Cout), self._new(Cout)
-                    if self.training and live:
-                        self._live_jobs.append(dict(totals=tot, gamma=gamma, beta=beta, bname=bname, scale=scale, shift=shift, mean=mean,
-                                                    invstd=invstd, count=N * Ho * Wo, C=Cout))
-                    elif self.training:
-                        fa = BnFinalizeArgs(partials=part[0].data_ptr(), gamma=gamma.data_ptr(), beta=beta.data_ptr(),
-                                            running_mean=self.Bf[bname + '.running_mean'].data_ptr(),
-                                            running_var=self.Bf[bname + '.running_var'].data_ptr(),
-                                            num_batches_tracked=self.Bf[bname + '.num_batches_tracked'].data_ptr(),
-                                            scale=scale.data_ptr(), shift=shift.data_ptr(),
-                                            save_mean=mean.data_ptr(), save_invstd=invstd.data_ptr(),
-                                            count=N * Ho * Wo, nblocks=part[1], C=Cout, eps=BN_EPS, momentum=BN_MOMENTUM)
-                        fwd.add(fa)
-                    else:
-                        # eval mode: scale / shift depend on parameters and running statistics only -- constants between two
-                        # forwards of an inference loop (util.test_dataset, seg_dataset_ensemble: one image after the other).
-                        # Inference plans compute them in the PACK program (re-run when a parameter, a buffer or a training
-                        # forward has touched them, UNet._ensure_packed) instead of 22 launches in every forward (round 4).
-                        (fwd if self.need_grad else self._prep).add(
-                            BnEvalArgs(gamma=gamma.data_ptr(), beta=beta.data_ptr(),
-                                       running_mean=self.Bf[bname + '.running_mean'].data_ptr(),
-                                       running_var=self.Bf[bname + '.running_var'].data_ptr(),
-                                       scale=scale.data_ptr(), shift=shift.data_ptr(), C=Cout, eps=BN_EPS))
-                        if self.need_grad:
-                            # gradients through eval-mode BatchNorm (nn.Module semantics of unet.py:161-193): the statistics
-                            # are the running ones -- mean is the buffer itself, 1/sqrt(var + eps) is the scale of (gamma = 1)
-                            ones, zeros = self._const(Cout, 1.0), self._const(Cout, 0.0)
-                            mean = self.Bf[bname + '.running_mean']
-                            fwd.add(BnEvalArgs(gamma=ones.data_ptr(), beta=zeros.data_ptr(), running_mean=mean.data_ptr(),
-                                               running_var=self.Bf[bname + '.running_var'].data_ptr(),
-                                               scale=invstd.data_ptr(), shift=self._new(Cout).data_ptr(), C=Cout, eps=BN_EPS))
-                    aff = (scale, shift)
-                    bnrec = (gamma, mean, invstd, bname)
-                    self.dbg['bn:' + bname] = (scale, shift, mean, invstd)
-                convs.append(dict(w=w, wname=wname, inp=cur, gin=gin, inp_aff=cur_aff, r=r, bn=bnrec, live_bwd=live_bwd))
-                self.relu_out['%s.block.%d' % (prefix, d * step + 1)] = r      # (module name of the nn.ReLU: tests read its mask)
-                cur, cur_aff = r, (None if out_aff_taken else aff)       # (out_aff_taken: r holds BN(ReLU(.)) already)
-                cur_live = (tot, gamma, beta, N * Ho * Wo) if (bn and self.training and live) else None
-            assert cur.H == Hb and cur.W == Wb
-            if do_res:
-                rw, rb = P[prefix + '.res_conv1x1.weight'], P[prefix + '.res_conv1x1.bias']
-                rwp = self._pack_conv_fwd(rw)
-                self._conv(fwd, xin, rwp, out, 1, 1, 1, 0, Cout, bias=rb, add=cur, add_aff=None if cur_live is not None else cur_aff,
-                           add_live=cur_live)
-                # inference: the block's last 3x3 convolution and this 1x1 run as ONE launch where the library can (dfl_conv2d_pair:
-                # the latency form of a batch-1 forward -- 11 launches less in its chain of 44)
-                pk = 0
-                if self.PAIRS and not self.training and not self.need_grad and len(fwd) >= 2 and isinstance(fwd.structs[-2], ConvArgs):
-                    pk = self.lib.dfl_conv_pair_ok(C.addressof(fwd.structs[-2]), C.addressof(fwd.structs[-1]))
-                if pk in (1, 2):
-                    b_ = fwd.pop()
-                    a_ = fwd.pop()
-                    if pk == 2:        # K-sliced: the partial sums of BOTH products go through a buffer of twice the size
-                        Mp = a_.N * a_.Hout * a_.Wout
-                        a_.partial = self._shared_scratch('pair_partial', 2 * a_.splits * Mp * a_.Ntot).data_ptr()
-                    fwd.keep += [a_, b_]
-                    fwd.add(nat.ConvPairArgs(a=C.addressof(a_), b=C.addressof(b_)))
+    def _live_stats(self, d, xin, cur, gin, Cout, first):
+        """(live, live_bwd) of layer d of a block reading xin: its forward statistics are live totals, and its backward can take
+        live (sum dy, sum dy*r) -- its consumers derive the coefficients."""
+        # Live statistics (round 4): this layer's BatchNorm is not finalised by a launch between producer and consumer --
+        # the producing patch kernel adds its sums to the layer's totals, the consuming patch kernel (next 3x3, or the
+        # residual 1x1 whose epilogue adds BN(r)) derives scale / shift itself; ONE batched launch at the end of the forward
+        # pass leaves the vectors the backward pass and the module state need.  Both kernels must be patch kernels.
+        # (the network's first block: its 1-channel layers run the direct kernels, which take part as well -- the 3x3 row
+        # form as a producer, the 1x1 form as the consumer of "+ BN(r)", the 3x3 weight gradient as a consumer of A, B, C)
+        patch_in = lambda t: bool(t.bf16) and t.C % 16 == 0            # a convolution reading t runs the bf16 patch kernels
+        one_ch = lambda t: (not t.bf16) and t.C == 1 and Cout in (8, 16, 32, 64) and self.pad == 1
+        # (round 5) fp32 tensors: the GEMM kernels take part as well -- producer: any of them (statistics tail, K-slice finish
+        # kernel); consumers: the fast gather of the next 3x3 (its scale / shift table in LDS) and the residual 1x1's "+ BN(r)"
+        # (ADVICE r05: the consumer's table form needs the FAST gather, which needs tensors below 2 GiB -- a larger activation keeps
+        # the finalize launch and the generic kernel instead of failing in dfl_conv2d)
+        small = lambda t: t.N * t.H * t.W * t.ld * 4 < (1 << 31) - 4096
+        gemm_in = lambda t: (not t.bf16) and t.C % 16 == 0 and small(t)
+        can = self.LIVE_BN and self.bn and self.training and not self.circular
+        inner = d < self.bd - 1
+        if self.bf16:
+            live = can and (patch_in(gin) or one_ch(gin)) and (inner or (self.do_res and (patch_in(xin) or one_ch(xin))))
+        else:
+            live = (can and gemm_in(gin) and Cout % 16 == 0 and gin.N * gin.H * gin.W * 2 * Cout * 4 < (1 << 31) - 4096
+                    and (inner or self.do_res))
+        live_bwd = (can and self.bf16 and self.FUSE_BRB and self.need_grad
+                    and (patch_in(cur) or (one_ch(cur) and d == 0 and first and not self.input_grad)))
+        return live, live_bwd
+
+    def _bn_forward(self, bname, part, tot, out_aff, count, Cout):
+        """Scale / shift of BatchNorm `bname` behind a convolution (applied by the consumer on load) and the statistics its
+        backward reads.  Training: the live batched finalize (tot), or a finalize launch over the producer's partials;
+        eval: the running statistics.  out_aff: the producer already applies scale / shift.  Returns (aff, bn record)."""
+        P, Bf, fwd = self.P, self.Bf, self.fwd
+        gamma, beta = P[bname + '.weight'], P[bname + '.bias']
+        scale, shift = out_aff if out_aff is not None else (self._new(Cout), self._new(Cout))
+        mean, invstd = self._new(Cout), self._new(Cout)
+        if self.training and tot is not None:
+            self._live_jobs.append(dict(totals=tot, gamma=gamma, beta=beta, bname=bname, scale=scale, shift=shift, mean=mean,
+                                        invstd=invstd, count=count, C=Cout))
+        elif self.training:
+            fwd.add(BnFinalizeArgs(partials=part[0].data_ptr(), gamma=gamma.data_ptr(), beta=beta.data_ptr(),
+                                   running_mean=Bf[bname + '.running_mean'].data_ptr(),
+                                   running_var=Bf[bname + '.running_var'].data_ptr(),
+                                   num_batches_tracked=Bf[bname + '.num_batches_tracked'].data_ptr(),
+                                   scale=scale.data_ptr(), shift=shift.data_ptr(),
+                                   save_mean=mean.data_ptr(), save_invstd=invstd.data_ptr(),
+                                   count=count, nblocks=part[1], C=Cout, eps=BN_EPS, momentum=BN_MOMENTUM))
+        else:
+            # eval mode: scale / shift depend on parameters and running statistics only -- constants between two
+            # forwards of an inference loop (util.test_dataset, seg_dataset_ensemble: one image after the other).
+            # Inference plans compute them in the PACK program (re-run when a parameter, a buffer or a training
+            # forward has touched them, UNet._ensure_packed) instead of 22 launches in every forward (round 4).
+            (fwd if self.need_grad else self._prep).add(
+                BnEvalArgs(gamma=gamma.data_ptr(), beta=beta.data_ptr(),
+                           running_mean=Bf[bname + '.running_mean'].data_ptr(),
+                           running_var=Bf[bname + '.running_var'].data_ptr(),
+                           scale=scale.data_ptr(), shift=shift.data_ptr(), C=Cout, eps=BN_EPS))
+            if self.need_grad:
+                # gradients through eval-mode BatchNorm (nn.Module semantics of unet.py:161-193): the statistics
+                # are the running ones -- mean is the buffer itself, 1/sqrt(var + eps) is the scale of (gamma = 1)
+                ones, zeros = self._const(Cout, 1.0), self._const(Cout, 0.0)
+                mean = Bf[bname + '.running_mean']
+                fwd.add(BnEvalArgs(gamma=ones.data_ptr(), beta=zeros.data_ptr(), running_mean=mean.data_ptr(),
+                                   running_var=Bf[bname + '.running_var'].data_ptr(),
+                                   scale=invstd.data_ptr(), shift=self._new(Cout).data_ptr(), C=Cout, eps=BN_EPS))
+        self.dbg['bn:' + bname] = (scale, shift, mean, invstd)
+        return (scale, shift), (gamma, mean, invstd, bname)
+
+    def _pair_last_two(self):
+        """Inference: a block's last 3x3 convolution and its residual 1x1 run as ONE launch where the library can
+        (dfl_conv2d_pair: the latency form of a batch-1 forward -- 11 launches less in its chain of 44)."""
+        fwd = self.fwd
+        if len(fwd) < 2 or not isinstance(fwd.structs[-2], ConvArgs):
+            return
+        pk = self.lib.dfl_conv_pair_ok(C.addressof(fwd.structs[-2]), C.addressof(fwd.structs[-1]))
+        if pk not in (1, 2):
+            return
+        b_ = fwd.pop()
+        a_ = fwd.pop()
+        if pk == 2:        # K-sliced: the partial sums of BOTH products go through a buffer of twice the size
+            Mp = a_.N * a_.Hout * a_.Wout
+            a_.partial = self._shared_scratch('pair_partial', 2 * a_.splits * Mp * a_.Ntot).data_ptr()
+        fwd.keep += [a_, b_]
+        fwd.add(nat.ConvPairArgs(a=C.addressof(a_), b=C.addressof(b_)))
+
+    # ------------------------------------------------------------------ forward: down path, up path, heads
+    def _down_forward(self):
+        """Encoder blocks; a block's output is the bridge half of its level's concat buffer where the sizes agree (a crop
+        copy fills it otherwise), then max-pool or the strided convolution makes the next level's input."""
+        N, fwd = self.N, self.fwd
+        x = self._x0
+        self._down = []         # per level: dict(blk, crop, nxt)
+        for i in range(self.depth):
+            Ci = self.chans[i]
+            last = i == self.depth - 1
+            if not last and self.direct_bridge[i]:
+                out = self.cat[i].chan_slice(Ci, Ci)
             else:
-                a = AffineCopyArgs(x=cur.ptr, y=out.ptr, N=N, H=Hb, W=Wb, C=Cout, ldx=cur.ld, xH=Hb, xW=Wb,
-                                   ldy=out.ld, yH=out.H, yW=out.W, bf16=cur.bf16)
-                if cur_aff is not None:
-                    a.scale, a.shift = cur_aff[0].data_ptr(), cur_aff[1].data_ptr()
-                fwd.add(a)
-
-            self.dbg['out:' + prefix] = out
-            self.dbg['xin:' + prefix] = xin
-
-            def backward(dout, dxin, fused_in=None, dxin_stats=False):
-                """dout: Act with d(loss)/d(block output); dxin: Act to receive d/d(xin) (None for the net input).
-                fused_in: (partials, rows) with sum(dout), sum(dout * r_last) per channel when the kernel that wrote dout
-                already left them (saves this block's first statistics pass).  dxin_stats: let the LAST kernel that
-                writes dxin leave its column sums; returns them as (partials, rows) -- the caller's bias gradient."""
-                G = self.G
-                self.dbg['dout:' + prefix] = dout
-                if dxin is not None:
-                    self.dbg['dxin:' + prefix] = dxin
-                dxin_part = None
-                if do_res:
-                    self._wgrad(bwd, xin, dout, G[prefix + '.res_conv1x1.weight'], 1, 1, 1, 0, xin.H, xin.W)
-                # dxin = (3x3 data gradient of the first conv) + (1x1 data gradient of the residual branch).  The 3x3 one
-                # writes, the cheap 1x1 one accumulates on top: the big kernel keeps its simple epilogue (and, on the wide
-                # levels, the row-tiled form), the column sums of the finished dxin come from the 1x1 kernel.
-                res_dgrad_last = do_res and dxin is not None and self.RES_DGRAD_LAST
-                if do_res and dxin is not None and not res_dgrad_last:
-                    self._conv(bwd, dout, self._pack_conv_dgrad(rw), dxin, 1, 1, 1, 0, xin.C)
-                g = dout
-                fused = fused_in if self.FUSE_COLSUMS else None   # (partials, rows): BN-backward sums of g already left by g's producer
-                for d in reversed(range(bd)):
-                    cv = convs[d]
-                    r = cv['r']
-                    side = self.SIDE_STREAM and r.M <= self.SIDE_MAX_PIXELS
-                    # two dpre buffers alternate, so a side-stream weight gradient may still read one while the next
-                    # layer fills the other; the one about to be rewritten must be free
-                    self._dpre_turn ^= 1
-                    if g.t is self._scratch.get('dpre%d' % self._dpre_turn):
-                        self._dpre_turn ^= 1              # never the buffer the incoming gradient lives in (mixed fused / plain layers)
-                    self._side_join(bwd, buf='dpre%d' % self._dpre_turn)
-                    dpre = self._scratch_act('dpre%d' % self._dpre_turn, N, r.H, r.W, Cout)
-                    nb = self.lib.dfl_rowblock_count(r.M, Cout)
-                    coef = None
-                    self.dbg['g:%s.block.%d' % (prefix, d * step + 1)] = g
-                    if cv['bn'] is not None:
-                        gamma, mean, invstd, bname = cv['bn']
-                        if fused is not None and fused[0] == 'live':
-                            # live statistics: the producer of g added (sum g, sum g*r) to this layer's totals; the two consumers
-                            # below derive A, B, C themselves, the parameter gradients leave with the next batched launch
-                            assert cv['live_bwd']
-                            coef = dict(tot=fused[1], gamma=gamma, mean=mean, invstd=invstd, count=r.M)
-                            self._live_bwd_pending.append(dict(tot=fused[1], mean=mean, invstd=invstd, dgamma=G[bname + '.weight'],
-                                                               dbeta=G[bname + '.bias'], C=Cout,
-                                                               sum_out=G[prefix + '.res_conv1x1.bias'] if (do_res and d == bd - 1) else None))
-                        else:
-                            if fused is not None:
-                                part, prow = fused
-                            else:
-                                part, prow = self._new(nb * 2 * Cout), nb
-                                bwd.add(ColstatsArgs(a=g.ptr, b=r.ptr, partials=part.data_ptr(), M=r.M, C=Cout, lda=g.ld,
-                                                     ldb=r.ld, nblocks=nb, bf16=r.bf16))
-                            coef = self._new(3 * Cout)
-                            self.dbg['coef:%s.block.%d' % (prefix, d * step + 1)] = coef
-                            bwd.add(BnBwdFinalizeArgs(partials=part.data_ptr(), gamma=gamma.data_ptr(),
-                                                      save_mean=mean.data_ptr(), save_invstd=invstd.data_ptr(),
-                                                      dgamma=G[bname + '.weight'].data_ptr(),
-                                                      dbeta=G[bname + '.bias'].data_ptr(), coef=coef.data_ptr(),
-                                                      count=r.M if self.training else 0,      # 0: fixed (running) statistics
-                                                      nblocks=prow, C=Cout))
-                            if do_res and d == bd - 1:
-                                # residual bias gradient = column sums of dout, already in the same partials
-                                self._defer_sum(bwd, part.data_ptr(), G[prefix + '.res_conv1x1.bias'].data_ptr(), Cout,
-                                                2 * Cout, prow)
-                    elif do_res and d == bd - 1:
-                        self._colsum(bwd, g, G[prefix + '.res_conv1x1.bias'])
-                    inp = cv['inp']
-                    # BatchNorm + ReLU backward folded into its two consumers (bf16 patch kernels; round 3): the weight-gradient
-                    # and data-gradient kernels form [r > 0] * (A dy + B r + C) from (dy, r) while they stage their patches --
-                    # dpre is never written (one tensor pass and one launch per layer less), the bias-gradient sums come out
-                    # of the weight-gradient kernel.  The 1-channel first layer (direct kernels) keeps the materialised form.
-                    fuse_brb = self.FUSE_BRB and bool(r.bf16) and bool(inp.bf16) and inp.C % 16 == 0 and g.bf16 == r.bf16
-                    # ... and the network's first layer (1-channel fp32 input, no data gradient): the row form of the direct
-                    # weight-gradient kernel does the same while it reads its d rows
-                    if (self.FUSE_BRB and bool(r.bf16) and g.bf16 == r.bf16 and not inp.bf16 and inp.C == 1
-                            and d == 0 and dxin is None and Cout in (8, 16, 32, 64)):
-                        fuse_brb = True
-                    brb = (r, coef) if fuse_brb else None
-                    dsplit = 0
-                    if fuse_brb:
-                        dpre = g                          # what the consumers are given as their "d" / "x": dy itself
-                    else:
-                        bpart = self._new(nb * Cout)
-                        # dpre feeds exactly two GEMMs (weight gradient: dense operand; data gradient: gathered operand);
-                        # with split-bf16 products it is written split once here instead of being split by every tile of both
-                        dsplit = int(self.math in (1, 3) and Cout % 16 == 0 and inp.C % 4 == 0 and inp.C * 9 > 12 and self.DSPLIT)
-                        bwd.add(BnReluBwdArgs(dy=g.ptr, r=r.ptr, coef=nat.ptr(coef), dpre=dpre.ptr,
-                                              partials=bpart.data_ptr(), M=r.M, C=Cout, lddy=g.ld, ldr=r.ld, ldo=dpre.ld,
-                                              nblocks=nb, split_out=dsplit, bf16=r.bf16))
-                        self._defer_sum(bwd, bpart.data_ptr(), G[cv['wname'] + '.bias'].data_ptr(), Cout, Cout, nb)
-                    side_buf = 'dpre%d' % self._dpre_turn          # (one key space: scratch names, see _side_join / _dz_for)
-                    if fuse_brb:
-                        # (a side-stream weight gradient reads dy itself: the scratch it lives in must not be rewritten --
-                        # by the data gradient one layer further down -- before it is done: _dz_for joins on this key)
-                        side_buf = next((kk for kk in ('dz', 'dpre0') if g.t is self._scratch.get(kk)), None)
-                    # Small tensors (deep levels: many (cm, cg) tiles, each of which would form the operand again): the data-gradient
-                    # kernel, which forms it anyway, writes it once (x_out) and the weight gradient -- emitted BEHIND it -- reads it
-                    dmat = None
-                    if (fuse_brb and bool(inp.bf16) and not circ and pad == 1 and not side and (d > 0 or dxin is not None)
-                            and 'dmat' in self._scratch and r.M * Cout * 2 <= self.DPRE_OUT_BYTES):
-                        dmat = self._scratch_act('dmat', N, r.H, r.W, Cout)
-                        self.dbg['dmat:%s.block.%d' % (prefix, d * step + 1)] = dmat
-
-                    def emit_wgrad():
-                        if dmat is not None:
-                            self._wgrad(bwd, cv['gin'], dmat, G[cv['wname'] + '.weight'], 3, 3, 1, pad, r.H, r.W, in_aff=cv['inp_aff'],
-                                        bias_out=G[cv['wname'] + '.bias'], bias_plain=True)
-                        else:
-                            self._wgrad(bwd, cv['gin'], dpre, G[cv['wname'] + '.weight'], 3, 3, 1, 0 if circ else pad, r.H, r.W,
-                                        in_aff=cv['inp_aff'], side=side, side_buf=side_buf, d_split=dsplit, brb=brb,
-                                        bias_out=G[cv['wname'] + '.bias'])
-                    if dmat is None:
-                        emit_wgrad()
-                    if circ and (d > 0 or dxin is not None):
-                        # data gradient on the framed grid, folded back onto the pixels the frame copies (see _wrap_pad)
-                        wd = self._pack_conv_dgrad(cv['w'])
-                        dzp = self._framed_grad(inp)
-                        self._conv(bwd, dpre, wd, dzp, 3, 3, 1, 2, inp.C, x_split=dsplit, brb=brb)
-                        if d > 0:
-                            dz = self._dz_for(g, N, inp.H, inp.W, Cout, fuse_brb)
-                            self._wrap_fold(bwd, dzp, dz)
-                            fused = None
-                            g = dz
-                        else:
-                            self._wrap_fold(bwd, dzp, dxin, accumulate=1 if (do_res and not res_dgrad_last) else 0)
-                            if res_dgrad_last:
-                                dxin_part = self._conv(bwd, dout, self._pack_conv_dgrad(rw), dxin, 1, 1, 1, 0, xin.C,
-                                                       accumulate=1, stats=dxin_stats and self.FUSE_COLSUMS)
-                    elif d > 0:
-                        wd = self._pack_conv_dgrad(cv['w'])
-                        dz = self._dz_for(g, N, inp.H, inp.W, Cout, fuse_brb)
-                        prev = convs[d - 1]
-                        if prev['bn'] is not None and self.FUSE_BWD_STATS:
-                            # the data-gradient conv leaves sum(dz), sum(dz*r) per channel for the next BN backward
-                            fused = self._conv(bwd, dpre, wd, dz, 3, 3, 1, 2 - pad, Cout, stats=True, stat_other=prev['r'],
-                                               x_split=dsplit, brb=brb, x_out=dmat,
-                                               stat_totals=self._bn_totals(Cout, bwd=True) if prev['live_bwd'] else None)
-                        else:
-                            fused = None
-                            self._conv(bwd, dpre, wd, dz, 3, 3, 1, 2 - pad, Cout, x_split=dsplit, brb=brb, x_out=dmat)
-                        if dmat is not None:
-                            emit_wgrad()
-                        g = dz
-                    elif dxin is not None:
-                        wd = self._pack_conv_dgrad(cv['w'])
-                        want = dxin_stats and self.FUSE_COLSUMS
-                        dxin_part = self._conv(bwd, dpre, wd, dxin, 3, 3, 1, 2 - pad, xin.C,
-                                               accumulate=1 if (do_res and not res_dgrad_last) else 0,
-                                               x_split=dsplit, stats=want and not res_dgrad_last, brb=brb, x_out=dmat)
-                        if res_dgrad_last:
-                            dxin_part = self._conv(bwd, dout, self._pack_conv_dgrad(rw), dxin, 1, 1, 1, 0, xin.C,
-                                                   accumulate=1, stats=want)
-                        if dmat is not None:
-                            emit_wgrad()
-                    self._maybe_flush(bwd)
-                return dxin_part
-            # pre-BatchNorm output of the block's last conv: what a producer of this block's dout needs for fused_in
-            backward.last_r = convs[-1]['r'] if convs[-1]['bn'] is not None else None
-            backward.last_live = bool(convs[-1]['bn'] is not None and convs[-1]['live_bwd'])    # ... and may leave them as live totals
-            return backward
-
-        # ------------------------------------------------------------------ down path
-        x = x0
-        dx_in = None        # gradient Act of the current block input (None for the network input)
-        pending = []        # (kind, data) records consumed when emitting backward
-        down_out = []
-        for i in range(depth):
-            Ci = chans[i]
-            if i != depth - 1 and direct_bridge[i]:
-                out = cat[i].chan_slice(Ci, Ci)
+                out = self._act(N, self.hout[i], self.wout[i], Ci)
+            rec = dict(blk=self._block_forward('down_path.%d' % i, x, out, first=(i == 0)))
+            self._down.append(rec)
+            if last:
+                break
+            if not self.direct_bridge[i]:
+                ch, cw = self.up_hw[self.depth - 2 - i]
+                oy, ox = (self.hout[i] - ch) // 2, (self.wout[i] - cw) // 2
+                dst = self.cat[i].chan_slice(Ci, Ci)
+                fwd.add(AffineCopyArgs(x=out.ptr, y=dst.ptr, N=N, H=ch, W=cw, C=Ci, ldx=out.ld, xH=out.H, xW=out.W,
+                                       xoy=oy, xox=ox, ldy=dst.ld, yH=ch, yW=cw, bf16=out.bf16))
+                rec['crop'] = (oy, ox, ch, cw)
+            nxt = self._act(N, self.hin[i + 1], self.win[i + 1], Ci)
+            if self.cfg['max_pool']:
+                self.pool_in[i] = out
+                fwd.add_pool(PoolArgs(x=out.ptr, y=nxt.ptr, N=N, H=out.H, W=out.W, C=Ci, ldx=out.ld, ldy=nxt.ld,
+                                      bf16=out.bf16), backward=False)
             else:
-                out = self._act(N, hout[i], wout[i], Ci)
-            bw = block('down_path.%d' % i, x, out, first=(i == 0))
-            down_out.append(out)
-            rec = dict(block_bw=bw, out=out, xin=x, level=i)
-            if i != depth - 1:
-                if not direct_bridge[i]:
-                    ch, cw = up_hw[depth - 2 - i]
-                    oy, ox = (hout[i] - ch) // 2, (wout[i] - cw) // 2
-                    dst = cat[i].chan_slice(Ci, Ci)
-                    fwd.add(AffineCopyArgs(x=out.ptr, y=dst.ptr, N=N, H=ch, W=cw, C=Ci, ldx=out.ld, xH=out.H, xW=out.W,
-                                           xoy=oy, xox=ox, ldy=dst.ld, yH=ch, yW=cw, bf16=out.bf16))
-                    rec['crop'] = (oy, ox, ch, cw)
-                nxt = self._act(N, hin[i + 1], win[i + 1], Ci)
-                if cfg['max_pool']:
-                    self.pool_in[i] = out
-                    fwd.add_pool(PoolArgs(x=out.ptr, y=nxt.ptr, N=N, H=out.H, W=out.W, C=Ci, ldx=out.ld, ldy=nxt.ld,
-                                          bf16=out.bf16), backward=False)
-                else:
-                    dw_, db_ = self.P['downsample_convs.%d.weight' % i], self.P['downsample_convs.%d.bias' % i]
-                    wp = self._pack_conv_fwd(dw_)
-                    self._conv(fwd, out, wp, nxt, 2, 2, 2, 0, Ci, bias=db_)
-                rec['nxt'] = nxt
-                self.dbg['nxt:%d' % i] = nxt
-                x = nxt
-            pending.append(rec)
+                dw_, db_ = self.P['downsample_convs.%d.weight' % i], self.P['downsample_convs.%d.bias' % i]
+                self._conv(fwd, out, self._pack_conv_fwd(dw_), nxt, 2, 2, 2, 0, Ci, bias=db_)
+            rec['nxt'] = nxt
+            self.dbg['nxt:%d' % i] = nxt
+            x = nxt
 
-        # ------------------------------------------------------------------ up path
-        up_recs = []
-        u = down_out[depth - 1]
-        for j, i in enumerate(reversed(range(depth - 1))):
-            Ci = chans[i]
+    def _up_forward(self):
+        """Decoder: up-sampling into the up half of each level's concat buffer, then the block; its output is self.feat."""
+        N, fwd = self.N, self.fwd
+        self._up = []           # per up block j: dict(blk, u, level, name, w)
+        u = self._down[-1]['blk'].out
+        for j, i in enumerate(reversed(range(self.depth - 1))):
+            Ci = self.chans[i]
             name = 'up_path.%d' % j
-            ch, cw = up_hw[j]
-            up_half = cat[i].chan_slice(0, Ci)
-            if upsample:
+            ch, cw = self.up_hw[j]
+            up_half = self.cat[i].chan_slice(0, Ci)
+            if self.upsample:
                 # up_mode='upsample' (unet.py:242-244): bilinear x2, then a 1x1 convolution.  Both are linear, the convolution is
                 # pointwise and the interpolation weights sum to one: conv(up(x)) = up(conv(x)) with the bias added once -- the 1x1
                 # runs on the small grid, dfl_upsample2x_fwd spreads its result into the up half of the concat buffer
@@ -1022,17 +800,17 @@ class UNetPlan:
                         nat.OP_UPSAMPLE_FWD)
             else:
                 uw_, ub_ = self.P[name + '.up.weight'], self.P[name + '.up.bias']
-                wp = self._pack_convT_fwd(uw_)
-                self._conv(fwd, u, wp, up_half, 1, 1, 1, 0, 4 * Ci, bias=ub_, scatter=1, Hout=ch, Wout=cw)
-            out = self._act(N, ch - shrink, cw - shrink, Ci)
-            self.dbg['cat:%d' % j] = cat[i]
-            bw = block(name + '.conv_block', cat[i], out)
-            up_recs.append(dict(block_bw=bw, out=out, u=u, level=i, name=name, w=uw_))
+                self._conv(fwd, u, self._pack_convT_fwd(uw_), up_half, 1, 1, 1, 0, 4 * Ci, bias=ub_, scatter=1, Hout=ch, Wout=cw)
+            out = self._act(N, ch - self.shrink, cw - self.shrink, Ci)
+            self.dbg['cat:%d' % j] = self.cat[i]
+            blk = self._block_forward(name + '.conv_block', self.cat[i], out)
+            self._up.append(dict(blk=blk, u=u, level=i, name=name, w=uw_))
             u = out
         self.feat = u
-        self._finish_live_bn(fwd)
 
-        # ------------------------------------------------------------------ heads
+    def _heads_forward(self):
+        """Landmark block (if any) and the head call(s) on the decoder output."""
+        cfg, N, fwd, u = self.cfg, self.N, self.fwd, self.feat
         NC, L = cfg['n_classes'], cfg['num_lands']
         F = u.C
         self.NC, self.L = NC, L
@@ -1074,8 +852,7 @@ class UNetPlan:
             F2 = F // 2
             if F2 % (16 if self.bf16 else 4) != 0:
                 raise PlanError('lands_block_depth > 0 needs F/2 = %d channels to be a multiple of %d in this arithmetic' % (F2, 16 if self.bf16 else 4))
-            lpad = 1 if cfg['padding'] else 0
-            if not lpad:
+            if not self.pad:
                 hl, wl = u.H - 2 * lbd, u.W - 2 * lbd
                 if hl < 1 or wl < 1:
                     raise PlanError('input %dx%d too small for lands_block_depth=%d without padding' % (self.H, self.W, lbd))
@@ -1086,11 +863,11 @@ class UNetPlan:
             src = u
             for j in range(lbd):
                 wname, bname = 'lands_block.%d.weight' % j, 'lands_block.%d.bias' % j
-                ho_, wo_ = src.H - (0 if lpad else 2), src.W - (0 if lpad else 2)
+                ho_, wo_ = src.H - (0 if self.pad else 2), src.W - (0 if self.pad else 2)
                 dst = uw.chan_slice(F, F2) if j == lbd - 1 else self._act(N, ho_, wo_, F2)
-                gin = self._wrap_pad(fwd, src) if circ else src
-                self._conv(fwd, gin, self._pack_conv_fwd(self.P[wname]), dst, 3, 3, 1, 0 if (circ or not lpad) else 1, F2, bias=self.P[bname],
-                           Hout=ho_, Wout=wo_)
+                gin = self._wrap_pad(fwd, src) if self.circular else src
+                self._conv(fwd, gin, self._pack_conv_fwd(self.P[wname]), dst, 3, 3, 1, 0 if self.circular else self.pad, F2,
+                           bias=self.P[bname], Hout=ho_, Wout=wo_)
                 self.lb_layers.append((src, dst, wname, bname, gin, ho_, wo_))
                 src = dst
             self.eff_heads = dict(F=F, F2=F2, w_seg=self._new(NC * Fh).view(NC, Fh, 1, 1).zero_(),
@@ -1109,16 +886,13 @@ class UNetPlan:
         self.head_fwd = HeadFwdArgs(x=head_x.ptr, w_seg=w_seg.data_ptr(), w_l1=nat.ptr(w_l1), w_l2=nat.ptr(w_l2),
                                     N=N, H=hl, W=wl, F=Fh, ldx=head_x.ld, NC=NC, NM=NM, L=L, softmax=sm, x_bf16=u.bf16)
         fwd.add(self.head_fwd, volatile=True)       # writes the caller-owned outputs: addresses change per call
+        self._head_in = (head_x, w_seg, w_l1, w_l2, NM)
         self.out_hw = (u.H, u.W)
         self.heat_hw = (hl, wl)
 
-        self._n_fwd_pack = len(self._pack_jobs)
-        if not self.need_grad:
-            self._finish_pack()
-            return
-
-        # ================================================================== backward program
-        # flat gradient arena in parameters() order
+    # ------------------------------------------------------------------ backward program
+    def _grad_arena(self):
+        """Flat gradient arena in parameters() order."""
         self.grad_names = [k for k in self.P.keys()]
         offs, tot = {}, 0
         for k in self.grad_names:
@@ -1128,230 +902,386 @@ class UNetPlan:
         self.G = {k: self.grad_flat[offs[k]:offs[k] + self.P[k].numel()].view(self.P[k].shape) for k in self.grad_names}
         self.grad_offsets = offs
         self.dead_params = set()
-        if not cfg['max_pool']:
-            self.dead_params.add('downsample_convs.%d.weight' % (depth - 1))    # never used in forward
-            self.dead_params.add('downsample_convs.%d.bias' % (depth - 1))
+        if not self.cfg['max_pool']:
+            self.dead_params.add('downsample_convs.%d.weight' % (self.depth - 1))    # never used in forward
+            self.dead_params.add('downsample_convs.%d.bias' % (self.depth - 1))
 
-        # heads
-        Fdec = F                                  # channels of the decoder output (Fh: what the landmark head call sees)
-        g_seg = self.eff_heads['g_seg'] if self.eff_heads is not None else self.G['seg_conv.weight']
-        g_l1 = (self.eff_heads['g_l1'] if self.eff_heads is not None else self.G['lands_1x1.0.weight']) if L > 0 else None
+    def _heads_backward(self):
+        """Backward of the head call(s) and of the landmark block; returns (gradient of the decoder output, the sums its
+        producer left for the last block's BatchNorm backward, or None)."""
+        G, L, u = self.G, self.L, self.feat
+        head_x, w_seg, w_l1, w_l2, NM = self._head_in
+        g_seg = self.eff_heads['g_seg'] if self.eff_heads is not None else G['seg_conv.weight']
+        g_l1 = (self.eff_heads['g_l1'] if self.eff_heads is not None else G['lands_1x1.0.weight']) if L > 0 else None
         g_l2 = None
         if L > 0 and w_l2 is not None:
-            g_l2 = self.g_l2_eff if self.g_l2_eff is not None else self.G['lands_1x1.1.weight']
-        if self.PACK_OVERLAP:
-            bwd.wait(self.EV_PACK_DONE, stream=0)      # data-gradient weight layouts are packed on the side stream
-
-        def head_backward(x_act, Fx, H_, W_, ws, w1, w2, nm, nl, gs, g1, g2, live_r=None):
-            """HeadBwdArgs + its weight gradients on x_act [N,H_,W_,Fx]; returns (args, dx Act).  live_r: the saved ReLU output behind
-            the BatchNorm dx enters -- the matrix-core kernel then adds (sum dx, sum dx*r) to that layer's live totals itself
-            (self._head_live: ('live', totals) or None)."""
-            sld = self.lib.dfl_head_scratch_ld_for(Fx, NC, nm, nl)
-            M_ = N * H_ * W_
-            dx = self._act(N, H_, W_, Fx)
-            fused_head = bool(x_act.bf16) and Fx == 32 and NC <= 8 and nm <= 24 and nl <= 16 and os.environ.get('DFL_HEAD_FUSED', '1') != '0'
-            hb = HeadBwdArgs(x=x_act.ptr, w_seg=ws.data_ptr(), w_l1=nat.ptr(w1), w_l2=nat.ptr(w2), dx=dx.ptr, N=N, H=H_, W=W_, F=Fx,
-                             ldx=x_act.ld, lddx=dx.ld, NC=NC, NM=nm, L=nl, softmax=1 if cfg['do_soft_max'] else 0, scratch_ld=sld,
-                             x_bf16=x_act.bf16)
-            # bf16 features of the paper's width: the head kernel takes its three weight gradients itself (include/dfl_hip.h);
-            # otherwise it leaves a per-pixel scratch row and three 1x1 weight-gradient launches follow
-            self._head_live = None
-            mfma_head = fused_head and nm <= 24 and (nl == 0 or w2 is not None) and x_act.ld % 8 == 0 and os.environ.get('DFL_HEAD_MFMA', '1') != '0'
-            if mfma_head and live_r is not None and Fx == 32:
-                tot = self._bn_totals(Fx, bwd=True)
-                hb.stat_other, hb.ldso, hb.stat_totals = live_r.ptr, live_r.ld, tot
-                self._head_live = ('live', tot)
-            if fused_head:
-                part = self._new(4096 * nat.check(self.lib.dfl_head_wgrad_blocks(M_), 'dfl_head_wgrad_blocks'))
-                hb.wg_partial = part.data_ptr()
-                hb.dw_seg = gs.data_ptr()
-                if nl > 0:
-                    hb.dw_l1 = g1.data_ptr()
-                    if w2 is not None:
-                        hb.dw_l2 = g2.data_ptr()
-            else:
-                scratch = self._new(M_ * sld)
-                hb.scratch = scratch.data_ptr()
-            bwd.add(hb, volatile=True)                 # reads the caller-owned seg / dseg / dheat
-            if not fused_head:
-                off = [self.lib.dfl_head_scratch_off_for(Fx, NC, nm, nl, k) for k in range(5)]
-
-                def sact(o, c):
-                    return Act(scratch, scratch.data_ptr() + 4 * o, sld, N, H_, W_, c)
-                self._wgrad(bwd, sact(off[0], Fx), sact(off[1], NC), gs, 1, 1, 1, 0, H_, W_)
-                if nl > 0:
-                    self._wgrad(bwd, sact(off[0], Fx + NC), sact(off[2], nm), g1, 1, 1, 1, 0, H_, W_)
-                    if w2 is not None:
-                        self._wgrad(bwd, sact(off[3], nm), sact(off[4], nl), g2, 1, 1, 1, 0, H_, W_)
-            return hb, dx
-
+            g_l2 = self.g_l2_eff if self.g_l2_eff is not None else G['lands_1x1.1.weight']
         hl, wl = self.heat_hw
-        self.head_bwd_seg = None
+        self.head_bwd_seg = dfeat_a = None
         if self.split_heads:
-            self.g_seg_full = self._new(NC * Fdec).view(NC, Fdec, 1, 1)
-            self.head_bwd_seg, dfeat_a = head_backward(u, Fdec, u.H, u.W, self.P['seg_conv.weight'], None, None, 0, 0, self.g_seg_full, None, None)
-            self.dseg_zero = self._new(N * NC * hl * wl).zero_()
-        last_bw = up_recs[-1]['block_bw'] if up_recs else pending[depth - 1]['block_bw']
-        head_live_r = (last_bw.last_r if (self.LIVE_BN and self.LIVE_HEAD and self.FUSE_COLSUMS and not self.lb_layers and not self.split_heads
-                                          and last_bw.last_live) else None)
-        self.head_bwd, dfeat = head_backward(head_x, Fh, hl, wl, w_seg, w_l1, w_l2, NM, L, g_seg, g_l1, g_l2, live_r=head_live_r)
-        head_sums = self._head_live
+            self.g_seg_full = self._new(self.NC * u.C).view(self.NC, u.C, 1, 1)
+            self.head_bwd_seg, dfeat_a, _ = self._head_backward(u, u.H, u.W, self.P['seg_conv.weight'], None, None, 0, 0,
+                                                                self.g_seg_full, None, None)
+            self.dseg_zero = self._new(self.N * self.NC * hl * wl).zero_()
+        last = self._up[-1]['blk'] if self._up else self._down[-1]['blk']
+        live_r = (last.last_r if (self.LIVE_BN and self.LIVE_HEAD and not self.lb_layers and not self.split_heads and last.last_live)
+                  else None)
+        self.head_bwd, dfeat, sums = self._head_backward(head_x, hl, wl, w_seg, w_l1, w_l2, NM, L, g_seg, g_l1, g_l2, live_r=live_r)
         self.dbg['dfeat'] = dfeat
-
-        # up path, last block first
-        # Column sums ride on the kernels that produce the tensors: the conv that completes dcat leaves sum(dy) (the
-        # transposed conv's bias gradient), the conv that produces du leaves the BatchNorm-backward sums of the block
-        # that consumes du, the conv that completes a block-input gradient leaves the down-sampling bias gradient.
-        dout = dfeat
         if self.lb_layers:
-            # backward of the landmark block: the lb columns of dx through the 3x3 convolutions (bias sums, weight gradients,
-            # data gradients), the first one's data gradient added onto the u columns, which then enter the decoder
-            lpad = 1 if cfg['padding'] else 0
-            if self.split_heads:
-                # the u columns of the landmark call's dx belong to the centre window of the full-size feature gradient
-                dout = dfeat_a
-                src_u = dfeat.chan_slice(0, Fdec)
-                bwd.add(AffineCopyArgs(x=src_u.ptr, y=dout.ptr, N=N, H=hl, W=wl, C=Fdec, ldx=src_u.ld, xH=hl, xW=wl, ldy=dout.ld,
-                                       yH=u.H, yW=u.W, yoy=(u.H - hl) // 2, yox=(u.W - wl) // 2, accumulate=1, bf16=dout.bf16))
+            return self._lands_block_backward(dfeat, dfeat_a), None
+        return dfeat, sums
+
+    def _head_backward(self, x_act, H_, W_, ws, w1, w2, nm, nl, gs, g1, g2, live_r=None):
+        """HeadBwdArgs + its weight gradients on x_act [N,H_,W_,Fx]; returns (args, dx Act, live sums).  live_r: the saved ReLU
+        output behind the BatchNorm dx enters -- the matrix-core kernel then adds (sum dx, sum dx*r) to that layer's live
+        totals itself (live sums: ('live', totals), or None)."""
+        N, NC, Fx, bwd = self.N, self.NC, x_act.C, self.bwd
+        sld = self.lib.dfl_head_scratch_ld_for(Fx, NC, nm, nl)
+        M_ = N * H_ * W_
+        dx = self._act(N, H_, W_, Fx)
+        fused_head = bool(x_act.bf16) and Fx == 32 and NC <= 8 and nm <= 24 and nl <= 16 and os.environ.get('DFL_HEAD_FUSED', '1') != '0'
+        hb = HeadBwdArgs(x=x_act.ptr, w_seg=ws.data_ptr(), w_l1=nat.ptr(w1), w_l2=nat.ptr(w2), dx=dx.ptr, N=N, H=H_, W=W_, F=Fx,
+                         ldx=x_act.ld, lddx=dx.ld, NC=NC, NM=nm, L=nl, softmax=1 if self.cfg['do_soft_max'] else 0, scratch_ld=sld,
+                         x_bf16=x_act.bf16)
+        # bf16 features of the paper's width: the head kernel takes its three weight gradients itself (include/dfl_hip.h);
+        # otherwise it leaves a per-pixel scratch row and three 1x1 weight-gradient launches follow
+        live = None
+        mfma_head = fused_head and nm <= 24 and (nl == 0 or w2 is not None) and x_act.ld % 8 == 0 and os.environ.get('DFL_HEAD_MFMA', '1') != '0'
+        if mfma_head and live_r is not None and Fx == 32:
+            tot = self._bn_totals(Fx, bwd=True)
+            hb.stat_other, hb.ldso, hb.stat_totals = live_r.ptr, live_r.ld, tot
+            live = ('live', tot)
+        if fused_head:
+            part = self._new(4096 * nat.check(self.lib.dfl_head_wgrad_blocks(M_), 'dfl_head_wgrad_blocks'))
+            hb.wg_partial = part.data_ptr()
+            hb.dw_seg = gs.data_ptr()
+            if nl > 0:
+                hb.dw_l1 = g1.data_ptr()
+                if w2 is not None:
+                    hb.dw_l2 = g2.data_ptr()
+        else:
+            scratch = self._new(M_ * sld)
+            hb.scratch = scratch.data_ptr()
+        bwd.add(hb, volatile=True)                 # reads the caller-owned seg / dseg / dheat
+        if not fused_head:
+            off = [self.lib.dfl_head_scratch_off_for(Fx, NC, nm, nl, k) for k in range(5)]
+            sact = lambda o, c: Act(scratch, scratch.data_ptr() + 4 * o, sld, N, H_, W_, c)
+            self._wgrad(bwd, sact(off[0], Fx), sact(off[1], NC), gs, 1, 1, 1, 0, H_, W_)
+            if nl > 0:
+                self._wgrad(bwd, sact(off[0], Fx + NC), sact(off[2], nm), g1, 1, 1, 1, 0, H_, W_)
+                if w2 is not None:
+                    self._wgrad(bwd, sact(off[3], nm), sact(off[4], nl), g2, 1, 1, 1, 0, H_, W_)
+        return hb, dx, live
+
+    def _lands_block_backward(self, dfeat, dfeat_a):
+        """Backward of the landmark block: the lb columns of dfeat through its 3x3 convolutions (bias sums, weight gradients,
+        data gradients), the first one's data gradient added onto the u columns, which then enter the decoder.  dfeat_a:
+        the full-size feature gradient of the segmentation call (split heads).  Returns the gradient of the decoder output."""
+        N, G, bwd, u = self.N, self.G, self.bwd, self.feat
+        F, Fh = u.C, dfeat.C
+        hl, wl = self.heat_hw
+        if self.split_heads:
+            # the u columns of the landmark call's dx belong to the centre window of the full-size feature gradient
+            dout = dfeat_a
+            src_u = dfeat.chan_slice(0, F)
+            bwd.add(AffineCopyArgs(x=src_u.ptr, y=dout.ptr, N=N, H=hl, W=wl, C=F, ldx=src_u.ld, xH=hl, xW=wl, ldy=dout.ld,
+                                   yH=u.H, yW=u.W, yoy=(u.H - hl) // 2, yox=(u.W - wl) // 2, accumulate=1, bf16=dout.bf16))
+        else:
+            dout = dfeat.chan_slice(0, F)
+        d = dfeat.chan_slice(F, Fh - F)
+        for j in reversed(range(len(self.lb_layers))):
+            src, dst, wname, bname, gin, ho_, wo_ = self.lb_layers[j]
+            self._colsum(bwd, d, G[bname])
+            self._wgrad(bwd, gin, d, G[wname], 3, 3, 1, 0 if self.circular else self.pad, ho_, wo_)
+            wd = self._pack_conv_dgrad(self.P[wname])
+            tgt = dout if j == 0 else self._act(N, src.H, src.W, Fh - F)
+            if self.circular:
+                dzp = self._framed_grad(src)
+                self._conv(bwd, d, wd, dzp, 3, 3, 1, 2, src.C)
+                self._wrap_fold(bwd, dzp, tgt, accumulate=1 if j == 0 else 0)
             else:
-                dout = dfeat.chan_slice(0, Fdec)
-            d = dfeat.chan_slice(Fdec, Fh - Fdec)
-            for j in reversed(range(len(self.lb_layers))):
-                src, dst, wname, bname, gin, ho_, wo_ = self.lb_layers[j]
-                self._colsum(bwd, d, self.G[bname])
-                self._wgrad(bwd, gin, d, self.G[wname], 3, 3, 1, 0 if (circ or not lpad) else 1, ho_, wo_)
-                wd = self._pack_conv_dgrad(self.P[wname])
-                tgt = dout if j == 0 else self._act(N, src.H, src.W, Fh - Fdec)
-                if circ:
-                    dzp = self._framed_grad(src)
-                    self._conv(bwd, d, wd, dzp, 3, 3, 1, 2, src.C)
-                    self._wrap_fold(bwd, dzp, tgt, accumulate=1 if j == 0 else 0)
-                else:
-                    self._conv(bwd, d, wd, tgt, 3, 3, 1, 1 if lpad else 2, src.C, accumulate=1 if j == 0 else 0)
-                if j > 0:
-                    d = tgt
-        F = Fdec
-        dout_sums = head_sums if not self.lb_layers else None
-        for j in reversed(range(len(up_recs))):
-            rec = up_recs[j]
+                self._conv(bwd, d, wd, tgt, 3, 3, 1, 2 - self.pad, src.C, accumulate=1 if j == 0 else 0)
+            if j > 0:
+                d = tgt
+        return dout
+
+    def _up_backward(self, dout, sums):
+        """Decoder backward, last block first.  Column sums ride on the kernels that produce the tensors: the conv that
+        completes dcat leaves sum(dy) (the transposed conv's bias gradient), the conv that produces du leaves the
+        BatchNorm-backward sums of the block that consumes du.  Returns (du, sums) of the deepest down block."""
+        N, G, bwd = self.N, self.G, self.bwd
+        for j in reversed(range(len(self._up))):
+            rec = self._up[j]
             i = rec['level']
-            Ci = chans[i]
-            st = rec['block_bw'](dout, dcat[i], fused_in=dout_sums, dxin_stats=True)
-            dy = dcat[i].chan_slice(0, Ci)                    # gradient of the transposed-conv output
+            Ci = self.chans[i]
+            st = self._block_backward(rec['blk'], dout, self.dcat[i], fused_in=sums, dxin_stats=True)
+            dy = self.dcat[i].chan_slice(0, Ci)                  # gradient of the transposed-conv output
             uin = rec['u']
-            bias_name = rec['name'] + ('.up.1.bias' if upsample else '.up.bias')
-            if st is not None:                                # rows of (sum v, sum v^2) over all 2*Ci columns of dcat
-                self._defer_sum(bwd, st[0].data_ptr(), self.G[bias_name].data_ptr(), Ci, 4 * Ci, st[1])
+            bias_name = rec['name'] + ('.up.1.bias' if self.upsample else '.up.bias')
+            if st is not None:                                   # rows of (sum v, sum v^2) over all 2*Ci columns of dcat
+                self._defer_sum(bwd, st[0].data_ptr(), G[bias_name].data_ptr(), Ci, 4 * Ci, st[1])
             else:
-                self._colsum(bwd, dy, self.G[bias_name])          # (upsample: the adjoint preserves column sums)
+                self._colsum(bwd, dy, G[bias_name])              # (upsample: the adjoint preserves column sums)
             du = self._act(N, uin.H, uin.W, uin.C)
             self.dbg['du:%d' % j] = du
-            consumer = up_recs[j - 1]['block_bw'] if j > 0 else pending[depth - 1]['block_bw']
-            r_last = consumer.last_r if self.FUSE_COLSUMS else None
-            if upsample:
+            consumer = self._up[j - 1]['blk'] if j > 0 else self._down[-1]['blk']
+            r_last = consumer.last_r
+            if self.upsample:
                 # gradient of the small-grid 1x1 result = adjoint of the interpolation applied to dy; then an ordinary 1x1 layer
                 dylow = self._act(N, uin.H, uin.W, Ci)
                 bwd.add(UpsampleArgs(x=dylow.ptr, y=dy.ptr, N=N, H=uin.H, W=uin.W, C=Ci, ldx=dylow.ld, ldy=dy.ld, bf16=dy.bf16),
                         nat.OP_UPSAMPLE_BWD)
-                self._wgrad(bwd, uin, dylow, self.G[rec['name'] + '.up.1.weight'], 1, 1, 1, 0, uin.H, uin.W)
-                dout_sums = self._conv(bwd, dylow, self._pack_conv_dgrad(rec['w']), du, 1, 1, 1, 0, uin.C,
-                                       stats=r_last is not None, stat_other=r_last,
-                                       stat_totals=self._bn_totals(uin.C, bwd=True) if (r_last is not None and consumer.last_live) else None)
+                self._wgrad(bwd, uin, dylow, G[rec['name'] + '.up.1.weight'], 1, 1, 1, 0, uin.H, uin.W)
+                sums = self._conv(bwd, dylow, self._pack_conv_dgrad(rec['w']), du, 1, 1, 1, 0, uin.C,
+                                  stats=r_last is not None, stat_other=r_last,
+                                  stat_totals=self._bn_totals(uin.C, bwd=True) if (r_last is not None and consumer.last_live) else None)
             else:
                 # dW[ci][co][ab] = sum x[i,j][ci] * dy[2i+a,2j+b][co]
-                self._wgrad(bwd, dy, uin, self.G[rec['name'] + '.up.weight'], 2, 2, 2, 0, uin.H, uin.W)
+                self._wgrad(bwd, dy, uin, G[rec['name'] + '.up.weight'], 2, 2, 2, 0, uin.H, uin.W)
                 wd = self._pack_convT_dgrad(rec['w'])
-                dout_sums = self._conv(bwd, dy, wd, du, 2, 2, 2, 0, uin.C, stats=r_last is not None, stat_other=r_last,
-                                       stat_totals=self._bn_totals(uin.C, bwd=True) if (r_last is not None and consumer.last_live) else None)
+                sums = self._conv(bwd, dy, wd, du, 2, 2, 2, 0, uin.C, stats=r_last is not None, stat_other=r_last,
+                                  stat_totals=self._bn_totals(uin.C, bwd=True) if (r_last is not None and consumer.last_live) else None)
             dout = du
-        # down path, deepest block first
-        for i in reversed(range(depth)):
-            rec = pending[i]
-            out = rec['out']
-            Ci = chans[i]
-            down_sums = None
-            if i != depth - 1:
-                # dout = bridge gradient (+ crop padding) + down-sampling gradient
-                if direct_bridge[i]:
-                    dout = dcat[i].chan_slice(Ci, Ci)
+        return dout, sums
+
+    def _down_backward(self, dout, sums):
+        """Encoder backward, deepest block first: a block's output gradient is its bridge gradient (+ crop padding) plus
+        the down-sampling gradient; the conv that completes a block-input gradient leaves the down-sampling bias gradient."""
+        N, G, bwd = self.N, self.G, self.bwd
+        dnxt = dnxt_sums = None          # gradient of the next level's input, and its column sums (from that block's backward)
+        for i in reversed(range(self.depth)):
+            rec = self._down[i]
+            blk = rec['blk']
+            out = blk.out
+            Ci = self.chans[i]
+            if i != self.depth - 1:
+                sums = None
+                if self.direct_bridge[i]:
+                    dout = self.dcat[i].chan_slice(Ci, Ci)
                 else:
                     dout = self._act(N, out.H, out.W, Ci)
                     oy, ox, ch, cw = rec['crop']
-                    src = dcat[i].chan_slice(Ci, Ci)
+                    src = self.dcat[i].chan_slice(Ci, Ci)
                     bwd.add(MemsetArgs(ptr=dout.ptr, bytes=dout.esz * dout.M * Ci))
                     bwd.add(AffineCopyArgs(x=src.ptr, y=dout.ptr, N=N, H=ch, W=cw, C=Ci, ldx=src.ld, xH=ch, xW=cw,
                                            ldy=dout.ld, yH=out.H, yW=out.W, yoy=oy, yox=ox, bf16=src.bf16))
-                dnxt = rec['dnxt']
                 nxt = rec['nxt']
-                if cfg['max_pool']:
+                if self.cfg['max_pool']:
                     bwd.add_pool(PoolArgs(x=out.ptr, y=dnxt.ptr, dx=dout.ptr, N=N, H=out.H, W=out.W, C=Ci, ldx=out.ld,
                                           ldy=dnxt.ld, lddx=dout.ld, bf16=out.bf16), backward=True)
                 else:
                     wname = 'downsample_convs.%d' % i
-                    st = rec.get('dnxt_sums')
-                    if st is not None:
-                        self._defer_sum(bwd, st[0].data_ptr(), self.G[wname + '.bias'].data_ptr(), Ci, 2 * Ci, st[1])
+                    if dnxt_sums is not None:
+                        self._defer_sum(bwd, dnxt_sums[0].data_ptr(), G[wname + '.bias'].data_ptr(), Ci, 2 * Ci, dnxt_sums[1])
                     else:
-                        self._colsum(bwd, dnxt, self.G[wname + '.bias'])
-                    self._wgrad(bwd, out, dnxt, self.G[wname + '.weight'], 2, 2, 2, 0, nxt.H, nxt.W)
+                        self._colsum(bwd, dnxt, G[wname + '.bias'])
+                    self._wgrad(bwd, out, dnxt, G[wname + '.weight'], 2, 2, 2, 0, nxt.H, nxt.W)
                     wd = self._pack_down_dgrad(self.P[wname + '.weight'])
                     # the last kernel that writes dout leaves sum(dout), sum(dout * r_last) for the block's first BN backward
-                    r_last = rec['block_bw'].last_r
+                    r_last = blk.last_r
                     # (the scatter visits the 2*H' x 2*W' pixels it writes: with an odd out.H / out.W the last row / column of
                     # dout holds bridge gradient only and would be missing from the sums -- then the separate pass takes them)
                     want = (self.FUSE_DOWN_STATS and r_last is not None and bool(dout.bf16) and bool(r_last.bf16)
                             and out.H == 2 * nxt.H and out.W == 2 * nxt.W)
-                    down_sums = self._conv(bwd, dnxt, wd, dout, 1, 1, 1, 0, 4 * Ci, accumulate=1, scatter=1,
-                                           Hout=out.H, Wout=out.W, stats=want, stat_other=r_last if want else None,
-                                           stat_totals=self._bn_totals(Ci, bwd=True) if (want and rec['block_bw'].last_live) else None)
+                    sums = self._conv(bwd, dnxt, wd, dout, 1, 1, 1, 0, 4 * Ci, accumulate=1, scatter=1,
+                                      Hout=out.H, Wout=out.W, stats=want, stat_other=r_last if want else None,
+                                      stat_totals=self._bn_totals(Ci, bwd=True) if (want and blk.last_live) else None)
+            xin = blk.xin
             if i > 0:
-                dxin = self._act(N, rec['xin'].H, rec['xin'].W, rec['xin'].C)
-                pending[i - 1]['dnxt'] = dxin
+                dxin = self._act(N, xin.H, xin.W, xin.C)
             elif self.input_grad:
                 if self.bf16:
                     raise PlanError('gradients with respect to the network input are implemented for the fp32-tensor arithmetic '
                                     'modes only (DFL_MATH=fp32 / bf16x3 / bf16x6 / bf16), not for bf16 storage')
-                dxin = self._act(N, rec['xin'].H, rec['xin'].W, rec['xin'].C)
-                self.dx_in = dxin
+                dxin = self.dx_in = self._act(N, xin.H, xin.W, xin.C)
             else:
                 dxin = None
-            st = rec['block_bw'](dout, dxin, fused_in=dout_sums if i == depth - 1 else down_sums,
-                                 dxin_stats=dxin is not None and i > 0 and not cfg['max_pool'])
-            if i > 0:
-                pending[i - 1]['dnxt_sums'] = st
-        self._flush_sums(bwd)
-        self._side_join(bwd)
+            dnxt_sums = self._block_backward(blk, dout, dxin, fused_in=sums,
+                                             dxin_stats=dxin is not None and i > 0 and not self.cfg['max_pool'])
+            dnxt = dxin
+
+    # ------------------------------------------------------------------ one residual conv block, backward
+    def _block_backward(self, blk, dout, dxin, fused_in=None, dxin_stats=False):
+        """dout: Act with d(loss)/d(block output); dxin: Act to receive d/d(xin) (None for the net input).
+        fused_in: BatchNorm-backward sums of dout -- (partials, rows) of sum(dout), sum(dout * r_last) per channel, or
+        ('live', totals) -- when the kernel that wrote dout already left them (saves this block's first statistics pass).
+        dxin_stats: let the LAST kernel that writes dxin leave its column sums; returns them as (partials, rows) -- the
+        caller's bias gradient."""
+        self.dbg['dout:' + blk.prefix] = dout
+        if dxin is not None:
+            self.dbg['dxin:' + blk.prefix] = dxin
+        if self.do_res:
+            self._wgrad(self.bwd, blk.xin, dout, self.G[blk.prefix + '.res_conv1x1.weight'], 1, 1, 1, 0, blk.xin.H, blk.xin.W)
+        g, sums = dout, fused_in
+        for d in reversed(range(self.bd)):
+            self.dbg['g:' + blk.convs[d].relu] = g
+            coef = self._bn_backward_coef(blk, d, g, sums)
+            g, sums = self._layer_backward(blk, d, g, coef, dout, dxin, dxin_stats)
+            self._maybe_flush(self.bwd)
+        return sums
+
+    def _bn_backward_coef(self, blk, d, g, sums):
+        """Coefficients of the BatchNorm backward of layer d for incoming gradient g (None: no BatchNorm), from the sums
+        g's producer left (live totals or partial rows) or from a statistics pass of its own; queues the BatchNorm parameter
+        gradients and, for the block's last layer, the residual bias gradient (column sums of g)."""
+        cv, G, bwd = blk.convs[d], self.G, self.bwd
+        r, Cout = cv.r, cv.r.C
+        res_bias = G[blk.prefix + '.res_conv1x1.bias'] if (self.do_res and d == self.bd - 1) else None
+        if cv.bn is None:
+            if res_bias is not None:
+                self._colsum(bwd, g, res_bias)
+            return None
+        gamma, mean, invstd, bname = cv.bn
+        if sums is not None and sums[0] == 'live':
+            # live statistics: the producer of g added (sum g, sum g*r) to this layer's totals; the two consumers
+            # of the coefficients derive A, B, C themselves, the parameter gradients leave with the next batched launch
+            assert cv.live_bwd
+            self._live_bwd_pending.append(dict(tot=sums[1], mean=mean, invstd=invstd, dgamma=G[bname + '.weight'],
+                                               dbeta=G[bname + '.bias'], C=Cout, sum_out=res_bias))
+            return dict(tot=sums[1], gamma=gamma, mean=mean, invstd=invstd, count=r.M)
+        if sums is None:
+            nb = self.lib.dfl_rowblock_count(r.M, Cout)
+            part = self._new(nb * 2 * Cout)
+            bwd.add(ColstatsArgs(a=g.ptr, b=r.ptr, partials=part.data_ptr(), M=r.M, C=Cout, lda=g.ld,
+                                 ldb=r.ld, nblocks=nb, bf16=r.bf16))
+            sums = (part, nb)
+        part, prow = sums
+        coef = self._new(3 * Cout)
+        self.dbg['coef:' + cv.relu] = coef
+        bwd.add(BnBwdFinalizeArgs(partials=part.data_ptr(), gamma=gamma.data_ptr(),
+                                  save_mean=mean.data_ptr(), save_invstd=invstd.data_ptr(),
+                                  dgamma=G[bname + '.weight'].data_ptr(),
+                                  dbeta=G[bname + '.bias'].data_ptr(), coef=coef.data_ptr(),
+                                  count=r.M if self.training else 0,      # 0: fixed (running) statistics
+                                  nblocks=prow, C=Cout))
+        if res_bias is not None:
+            # residual bias gradient = column sums of dout, already in the same partials
+            self._defer_sum(bwd, part.data_ptr(), res_bias.data_ptr(), Cout, 2 * Cout, prow)
+        return coef
+
+    def _layer_backward(self, blk, d, g, coef, dout, dxin, dxin_stats):
+        """Gradient emission of layer d for incoming gradient g: the BatchNorm + ReLU backward (written as dpre, or formed
+        by its two consumers), the weight gradient and the data gradient -- into scratch for layer d-1, or for layer 0 into
+        dxin, onto which the residual 1x1 data gradient accumulates.  Returns (the gradient written, the sums its producer
+        left: BatchNorm-backward sums of layer d-1, or the column sums of dxin)."""
+        cv, G, bwd, N = blk.convs[d], self.G, self.bwd, self.N
+        r, inp, Cout, pad, circ = cv.r, cv.inp, cv.r.C, self.pad, self.circular
+        # two dpre buffers alternate: a layer's dpre is never the buffer its incoming gradient lives in (the case when
+        # _dz_for handed out 'dpre0' as the data gradient of a fused layer above)
+        self._dpre_turn ^= 1
+        if g.t is self._scratch.get('dpre%d' % self._dpre_turn):
+            self._dpre_turn ^= 1
+        # BatchNorm + ReLU backward folded into its two consumers (bf16 patch kernels; round 3): the weight-gradient
+        # and data-gradient kernels form [r > 0] * (A dy + B r + C) from (dy, r) while they stage their patches --
+        # dpre is never written (one tensor pass and one launch per layer less), the bias-gradient sums come out
+        # of the weight-gradient kernel.  The 1-channel first layer (direct kernels) keeps the materialised form ...
+        fuse_brb = self.FUSE_BRB and bool(r.bf16) and bool(inp.bf16) and inp.C % 16 == 0 and g.bf16 == r.bf16
+        # ... but the network's first layer (1-channel fp32 input, no data gradient): the row form of the direct
+        # weight-gradient kernel does the same while it reads its d rows
+        if (self.FUSE_BRB and bool(r.bf16) and g.bf16 == r.bf16 and not inp.bf16 and inp.C == 1
+                and d == 0 and dxin is None and Cout in (8, 16, 32, 64)):
+            fuse_brb = True
+        brb = (r, coef) if fuse_brb else None
+        dsplit = 0
+        if fuse_brb:
+            dpre = g                          # what the consumers are given as their "d" / "x": dy itself
+        else:
+            dpre = self._scratch_act('dpre%d' % self._dpre_turn, N, r.H, r.W, Cout)
+            nb = self.lib.dfl_rowblock_count(r.M, Cout)
+            bpart = self._new(nb * Cout)
+            # dpre feeds exactly two GEMMs (weight gradient: dense operand; data gradient: gathered operand);
+            # with split-bf16 products it is written split once here instead of being split by every tile of both
+            dsplit = int(self.math in (1, 3) and Cout % 16 == 0 and inp.C % 4 == 0 and inp.C * 9 > 12)
+            bwd.add(BnReluBwdArgs(dy=g.ptr, r=r.ptr, coef=nat.ptr(coef), dpre=dpre.ptr,
+                                  partials=bpart.data_ptr(), M=r.M, C=Cout, lddy=g.ld, ldr=r.ld, ldo=dpre.ld,
+                                  nblocks=nb, split_out=dsplit, bf16=r.bf16))
+            self._defer_sum(bwd, bpart.data_ptr(), G[cv.wname + '.bias'].data_ptr(), Cout, Cout, nb)
+        # Small tensors (deep levels: many (cm, cg) tiles, each of which would form the operand again): the data-gradient
+        # kernel, which forms it anyway, writes it once (x_out) and the weight gradient -- emitted BEHIND it -- reads it
+        dmat = None
+        if (fuse_brb and bool(inp.bf16) and not circ and pad == 1 and (d > 0 or dxin is not None)
+                and 'dmat' in self._scratch and r.M * Cout * 2 <= self.DPRE_OUT_BYTES):
+            dmat = self._scratch_act('dmat', N, r.H, r.W, Cout)
+            self.dbg['dmat:' + cv.relu] = dmat
+        if dmat is None:
+            self._layer_wgrad(cv, dpre, d_split=dsplit, brb=brb)
+        sums = None
+        if circ and (d > 0 or dxin is not None):
+            # data gradient on the framed grid, folded back onto the pixels the frame copies (see _wrap_pad)
+            wd = self._pack_conv_dgrad(cv.w)
+            dzp = self._framed_grad(inp)
+            self._conv(bwd, dpre, wd, dzp, 3, 3, 1, 2, inp.C, x_split=dsplit, brb=brb)
+            if d > 0:
+                g = self._dz_for(g, N, inp.H, inp.W, Cout, fuse_brb)
+                self._wrap_fold(bwd, dzp, g)
+            else:
+                self._wrap_fold(bwd, dzp, dxin)
+                if self.do_res:
+                    sums = self._conv(bwd, dout, self._pack_conv_dgrad(blk.rw), dxin, 1, 1, 1, 0, blk.xin.C,
+                                      accumulate=1, stats=dxin_stats)
+        elif d > 0:
+            wd = self._pack_conv_dgrad(cv.w)
+            dz = self._dz_for(g, N, inp.H, inp.W, Cout, fuse_brb)
+            prev = blk.convs[d - 1]
+            if prev.bn is not None:
+                # the data-gradient conv leaves sum(dz), sum(dz*r) per channel for the next BN backward
+                sums = self._conv(bwd, dpre, wd, dz, 3, 3, 1, 2 - pad, Cout, stats=True, stat_other=prev.r,
+                                  x_split=dsplit, brb=brb, x_out=dmat,
+                                  stat_totals=self._bn_totals(Cout, bwd=True) if prev.live_bwd else None)
+            else:
+                self._conv(bwd, dpre, wd, dz, 3, 3, 1, 2 - pad, Cout, x_split=dsplit, brb=brb, x_out=dmat)
+            g = dz
+        elif dxin is not None:
+            # dxin = (3x3 data gradient of the first conv) + (1x1 data gradient of the residual branch).  The 3x3 one
+            # writes, the cheap 1x1 one accumulates on top: the big kernel keeps its simple epilogue (and, on the wide
+            # levels, the row-tiled form), the column sums of the finished dxin come from the 1x1 kernel.
+            wd = self._pack_conv_dgrad(cv.w)
+            sums = self._conv(bwd, dpre, wd, dxin, 3, 3, 1, 2 - pad, blk.xin.C,
+                              x_split=dsplit, stats=dxin_stats and not self.do_res, brb=brb, x_out=dmat)
+            if self.do_res:
+                sums = self._conv(bwd, dout, self._pack_conv_dgrad(blk.rw), dxin, 1, 1, 1, 0, blk.xin.C,
+                                  accumulate=1, stats=dxin_stats)
+        if dmat is not None:
+            self._layer_wgrad(cv, dmat, bias_plain=True)
+        return g, sums
+
+    def _layer_wgrad(self, cv, d, **kw):
+        """Weight and bias gradient of a block's 3x3 layer cv from operand d: dpre, dy itself (brb), or the operand the data
+        gradient materialised (bias_plain)."""
+        self._wgrad(self.bwd, cv.gin, d, self.G[cv.wname + '.weight'], 3, 3, 1, 0 if self.circular else self.pad, cv.r.H, cv.r.W,
+                    in_aff=cv.inp_aff, bias_out=self.G[cv.wname + '.bias'], **kw)
+
+    def _finish_backward(self):
+        """The last batched sums, and the zero fill of the backward totals arena in front of the program."""
+        self._flush_sums(self.bwd)
         if self._tot_bwd[0] is not None:
-            bwd.insert(0, MemsetArgs(ptr=self._tot_bwd[0].data_ptr(), bytes=8 * self._tot_bwd[1]))
+            self.bwd.insert(0, MemsetArgs(ptr=self._tot_bwd[0].data_ptr(), bytes=8 * self._tot_bwd[1]))
             # every op index recorded while the program was emitted moved up by one (ADVICE r04: the flushes' indices
             # stayed behind and data-parallel buckets were cut one op early)
             self._red_flushes = [(idx + 1, dsts) for idx, dsts in self._red_flushes]
-            for e in self._side:
-                e['op'] += 1
-                if e['waited'] is not None:
-                    e['waited'] += 1
-        self._order_pack_jobs()
-        self._finish_pack()
-        # index of the last backward op that writes each parameter gradient (data-parallel bucket scheduling)
+
+    def _grad_ready_ops(self):
+        """Index of the last backward op that writes each parameter gradient (data-parallel bucket scheduling)."""
         by_ptr = {self.G[k].data_ptr(): k for k in self.grad_names}
         self.grad_ready_op = {}
-        joined = {e['op']: e['waited'] for e in self._side}     # side-stream op -> main-stream wait that covers it
-        for idx, st in enumerate(bwd.structs):
+        for idx, st in enumerate(self.bwd.structs):
             for field in ('dw', 'dst', 'out', 'dgamma', 'dbeta', 'dw_seg', 'dw_l1', 'dw_l2'):   # (dw_*: head_bwd's own weight gradients)
                 name = by_ptr.get(getattr(st, field, None))
                 if name is not None:
-                    self.grad_ready_op[name] = joined.get(idx, idx)
+                    self.grad_ready_op[name] = idx
         for idx, dsts in self._red_flushes:
             for d in dsts:
                 name = by_ptr.get(d)
                 if name is not None:
                     self.grad_ready_op[name] = max(idx, self.grad_ready_op.get(name, -1))
+        last = len(self.bwd.structs) - 1
         if self.g_l2_eff is not None:            # taken apart after the last op (unfold_tail_grads)
             for name in self.tail_names:
-                self.grad_ready_op[name] = len(bwd.structs) - 1
+                self.grad_ready_op[name] = last
         if self.eff_heads is not None:
             for name in ('seg_conv.weight', 'lands_1x1.0.weight'):
-                self.grad_ready_op[name] = len(bwd.structs) - 1
+                self.grad_ready_op[name] = last
 
     # ------------------------------------------------------------------------------------------ folded 1x1 tail
     def fold_tail(self):
@@ -1400,9 +1330,6 @@ class UNetPlan:
             above = mats[j] if above is None else above @ mats[j]
 
     # ------------------------------------------------------------------------------------------ run
-    def run_pack(self, stream, forward_only=False):
-        self.pack.run(stream)
-
     def run_pack_rest(self, stream):
         """The pack program without its tiled launch: what is left to do after dfl_sgd_pack_tiled / dfl_optim_pack_tiled (optim.py)
         has written the tiled layouts together with the update."""
