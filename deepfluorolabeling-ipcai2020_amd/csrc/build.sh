@@ -4,7 +4,7 @@ set -euo pipefail
 here="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 out="$here/../lib"
 mkdir -p "$out"
-srcs=(api.hip conv_gemm.hip conv_rows.hip convp_bf16.hip convq_bf16.hip convn_bf16.hip convs_bf16.hip convs_f32.hip wgradp_bf16.hip wgrad_gemm.hip direct_small.hip bn_elem.hip head.hip loss.hip prep.hip augment.hip upsample.hip overlay.hip overlay_fullres.hip mesh.hip)
+srcs=(api.hip conv_gemm.hip conv_plan.hip conv_rows.hip convp_bf16.hip convq_bf16.hip convn_bf16.hip convs_bf16.hip convs_f32.hip wgradp_bf16.hip wgrad_gemm.hip direct_small.hip bn_elem.hip head.hip loss.hip prep.hip augment.hip upsample.hip overlay.hip overlay_fullres.hip mesh.hip)
 objs=()
 pids=()
 # one hipcc per source, at most $MAX_JOBS (default 16) at a time
@@ -13,7 +13,7 @@ jobs_max="${MAX_JOBS:-16}"
 for s in "${srcs[@]}"; do
   o="$out/${s%.hip}.o"
   objs+=("$o")
-  if [ ! -f "$o" ] || [ "$here/$s" -nt "$o" ] || [ "$here/common.h" -nt "$o" ] || [ "$here/direct_small.h" -nt "$o" ] || [ "$here/conv_epilogue.h" -nt "$o" ] || [ "$here/conv_rows.h" -nt "$o" ] || [ "$here/convp.h" -nt "$o" ] || [ "$here/head_caps.inc" -nt "$o" ] || [ "$here/head_mfma.inc" -nt "$o" ] || [ "$here/../../include/dfl_hip.h" -nt "$o" ]; then
+  if [ ! -f "$o" ] || [ "$here/$s" -nt "$o" ] || [ "$here/common.h" -nt "$o" ] || [ "$here/direct_small.h" -nt "$o" ] || [ "$here/conv_epilogue.h" -nt "$o" ] || [ "$here/conv_rows.h" -nt "$o" ] || [ "$here/convp.h" -nt "$o" ] || [ "$here/conv_plan.h" -nt "$o" ] || [ "$here/head_caps.inc" -nt "$o" ] || [ "$here/head_mfma.inc" -nt "$o" ] || [ "$here/../../include/dfl_hip.h" -nt "$o" ]; then
     # the two patch-resident kernels live at 1-3 waves per SIMD: schedule them for instruction-level parallelism instead of
     # register pressure (same instructions, same results; measured 4.47 -> 4.45 ms per step), and so are the streaming kernels of
     # bn_elem.hip (the batched sums issue their loads earlier: 0.23 -> 0.21 ms per step)

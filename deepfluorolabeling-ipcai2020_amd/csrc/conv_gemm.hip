@@ -36,8 +36,8 @@
 
 #include "common.h"
 #include "conv_epilogue.h"
+#include "conv_plan.h"
 #include "conv_rows.h"
-#include "convp.h"
 #include "direct_small.h"
 
 namespace dfl {
@@ -732,7 +732,7 @@ static int launch_fast(const ConvK& k, bool aff, bool general, hipStream_t s) {
   return general ? launch<WM, WN, TM, TN, 1, false, 1>(k, s) : launch<WM, WN, TM, TN, 1, false, 0>(k, s);
 }
 
-static int prepare(const dfl_conv_args* a, ConvK* k) {
+int conv_prepare(const dfl_conv_args* a, ConvK* k) {
   DFL_REQUIRE(a != nullptr, "dfl_conv2d: null args");
   DFL_REQUIRE(a->x && a->w && a->y, "dfl_conv2d: x, w and y are required");
   DFL_REQUIRE(a->N > 0 && a->Hin > 0 && a->Win > 0 && a->Cin > 0 && a->Ntot > 0, "dfl_conv2d: bad sizes");
@@ -784,116 +784,80 @@ static int prepare(const dfl_conv_args* a, ConvK* k) {
   return DFL_OK;
 }
 
-static int finish_rows(int M, int Ntot) {   // row blocks of conv_finish_kernel (= rows of stat_partials in split mode)
+int conv_finish_rows(int M, int Ntot) {   // row blocks of conv_finish_kernel (= rows of stat_partials in split mode)
   int64_t nb = ceil_div((int64_t)M * Ntot, 1024);   // 4 elements per thread: the per-element loop over splits is serial
   if (nb > 2048) nb = 2048;
   if (nb > M) nb = M;
   return nb < 1 ? 1 : (int)nb;
 }
 
-}  // namespace dfl
+int conv_gemm_cfg(const ConvK& k) { return (int)pick_cfg(k.Mtot, k.a.Ntot, k.fast); }
 
-extern "C" int dfl_conv_suggest_splits(const dfl_conv_args* a) {
-  if (a != nullptr && a->x_bf16) {          // bf16 tensors: the patch-resident kernels plan their own K slices
-    dfl::ConvP p;
-    int rc = dfl::convp_plan(a, &p, 0);
-    return rc != DFL_OK ? rc : p.splits;
-  }
-  if (const int zs = dfl::convs32_suggest_splits(a)) return zs;          // latency form (fp32 tensors, convs_f32.hip)
-  dfl::ConvK k;
-  int rc = dfl::prepare(a, &k);
-  if (rc != DFL_OK) return rc;
-  if (dfl::direct_conv_ok(a)) return 1;
-  if (const int rs = dfl::conv_rows_splits(k)) return rs;
-  return dfl::pick_splits(k.Mtot, a->Ntot, k.Ktot, dfl::pick_cfg(k.Mtot, a->Ntot, k.fast));
+int conv_gemm_bm(int cfg) {
+  int bm, bn;
+  cfg_tile((ConvCfg)cfg, &bm, &bn);
+  return bm;
 }
+
+int conv_gemm_splits(const ConvK& k) { return pick_splits(k.Mtot, k.a.Ntot, k.Ktot, pick_cfg(k.Mtot, k.a.Ntot, k.fast)); }
+
+static int conv_finish(const ConvK& k, hipStream_t s, const char* what) {
+  int tx = 1;
+  while (tx * 2 <= k.a.Ntot && tx * 2 <= 256) tx *= 2;
+  const int nb = conv_finish_rows(k.Mtot, k.a.Ntot);
+  const int rpb = (int)ceil_div(k.Mtot, nb);
+  hipLaunchKernelGGL(conv_finish_kernel, dim3((unsigned)nb, (unsigned)ceil_div(k.a.Ntot, tx)), dim3(256), 0, s, k, tx, rpb);
+  return check_launch(what);
+}
+
+}  // namespace dfl
 
 extern "C" int dfl_set_conv_rows_min_tiles(int32_t n) {
   DFL_REQUIRE(n >= 1, "dfl_set_conv_rows_min_tiles: n must be positive");
   return dfl::conv_rows_set_min_tiles(n);
 }
 
-extern "C" int dfl_conv_grid_m(const dfl_conv_args* a) {
-  if (a != nullptr && a->x_bf16) {
-    dfl::ConvP p;
-    int rc = dfl::convp_plan(a, &p, a->splits > 1 ? a->splits : 1);
-    if (rc != DFL_OK) return rc;
-    return p.splits > 1 ? dfl::convp_finish_rows(p) : p.npatch;
-  }
-  dfl::ConvK k;
-  int rc = dfl::prepare(a, &k);
-  if (rc != DFL_OK) return rc;
-  if (a->splits > 1) return dfl::finish_rows(k.Mtot, a->Ntot);
-  if (dfl::direct_conv_ok(a)) return dfl::direct_conv_blocks(a);
-  if (const int t = dfl::conv_rows_tile(k)) return k.Mtot / dfl::conv_rows_bm(t);
-  int bm, bn;
-  dfl::cfg_tile(dfl::pick_cfg(k.Mtot, a->Ntot, k.fast), &bm, &bn);
-  return (int)dfl::ceil_div(k.Mtot, bm);
-}
-
-extern "C" int dfl_conv_config(const dfl_conv_args* a) {
-  if (a != nullptr && a->x_bf16) {
-    dfl::ConvP p;
-    int rc = dfl::convp_plan(a, &p, a->splits > 1 ? a->splits : 1);
-    return rc != DFL_OK ? rc : 16 + p.tile;
-  }
-  dfl::ConvK k;
-  int rc = dfl::prepare(a, &k);
-  if (rc != DFL_OK) return rc;
-  if (dfl::convs_first_ok(a) || dfl::convs32_eligible(a)) return 16 + dfl::CONVS_TILE;
-  if (dfl::direct_conv_ok(a)) return dfl::CFG_DIRECT;
-  if (const int t = dfl::conv_rows_tile(k)) return t;
-  return (int)dfl::pick_cfg(k.Mtot, a->Ntot, k.fast);
-}
-
-extern "C" int dfl_conv_pair_ok(const dfl_conv_args* a, const dfl_conv_args* b) {
-  return (a != nullptr && !a->x_bf16) ? dfl::convs32_pair_ok(a, b) : dfl::convs_pair_ok(a, b);
-}
-
 extern "C" int dfl_conv2d_pair(const dfl_conv_args* a, const dfl_conv_args* b, dfl_stream_t stream) {
   DFL_REQUIRE(a != nullptr && b != nullptr, "dfl_conv2d_pair: null arguments");
-  if (!a->x_bf16) {
-    if (dfl::convs32_pair_ok(a, b) > 0) return dfl::convs32_pair_launch(a, b, static_cast<hipStream_t>(stream));
-  } else if (dfl::convs_pair_ok(a, b) > 0) {
-    return dfl::convs_pair_launch(a, b, static_cast<hipStream_t>(stream));
+  dfl::ConvRoute r;
+  if (dfl::conv_pair_route(a, b, &r) > 0) {
+    if (r.form == dfl::FORM_BF16) return dfl::convs_pair_launch(r.plan.p, b, static_cast<hipStream_t>(stream));
+    return dfl::convs32_pair_launch(a, b, static_cast<hipStream_t>(stream));
   }
   const int rc = dfl_conv2d(a, stream);
   return rc != DFL_OK ? rc : dfl_conv2d(b, stream);
 }
 
 extern "C" int dfl_conv2d(const dfl_conv_args* a, dfl_stream_t stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   if (a != nullptr && a->x_bf16) {
     DFL_REQUIRE(a->y_bf16, "dfl_conv2d: bf16 input with fp32 output is not a configuration of the network");
     DFL_REQUIRE(a->splits <= 1 || a->partial != nullptr, "dfl_conv2d: splits > 1 needs the partial buffer");
-    dfl::ConvP p;
-    int rc = dfl::convp_plan(a, &p, a->splits > 1 ? a->splits : 1);
-    if (rc != DFL_OK) return rc;
-    return dfl::convp_launch(p, static_cast<hipStream_t>(stream));
   }
-  if (a != nullptr && a->x != nullptr && a->w != nullptr && a->y != nullptr && dfl::convs_first_ok(a)) return dfl::convs_first_launch(a, static_cast<hipStream_t>(stream));
-  if (a != nullptr && dfl::convs32_eligible(a)) {                      // latency form for fp32 tensors (convs_f32.hip)
-    int sp = 1;
-    int rc = dfl::convs32_launch(a, static_cast<hipStream_t>(stream), &sp);
-    if (rc != DFL_OK || sp <= 1) return rc;
-    dfl::ConvK k;
-    rc = dfl::prepare(a, &k);
-    if (rc != DFL_OK) return rc;
-    k.splits = sp;
-    int tx = 1;
-    while (tx * 2 <= a->Ntot && tx * 2 <= 256) tx *= 2;
-    const int nb = dfl::finish_rows(k.Mtot, a->Ntot);
-    const int rpb = (int)dfl::ceil_div(k.Mtot, nb);
-    hipLaunchKernelGGL(dfl::conv_finish_kernel, dim3((unsigned)nb, (unsigned)dfl::ceil_div(a->Ntot, tx)), dim3(256), 0, static_cast<hipStream_t>(stream), k, tx, rpb);
-    return dfl::check_launch("dfl_conv2d (latency form, split-K finish)");
+  dfl::ConvRoute r;
+  int rc = dfl::conv_route(a, a != nullptr && a->splits > 1 ? a->splits : 1, &r);
+  if (rc != DFL_OK) return rc;
+  dfl::ConvK& k = r.k;
+  switch (r.form) {
+    case dfl::FORM_BF16: return dfl::convp_launch(r.plan, s);
+    case dfl::FORM_FIRST: return dfl::convs_first_launch(a, s);
+    case dfl::FORM_LATENCY32: {
+      int sp = 1;
+      rc = dfl::convs32_launch(a, s, &sp);
+      if (rc != DFL_OK || sp <= 1) return rc;
+      k.splits = sp;
+      return dfl::conv_finish(k, s, "dfl_conv2d (latency form, split-K finish)");
+    }
+    default: break;
   }
-  DFL_REQUIRE(a == nullptr || a->out_scale == nullptr, "dfl_conv2d: out_scale / out_shift are implemented by the latency form only (dfl_conv_config tells)");
-  DFL_REQUIRE(a == nullptr || (a->x_mode == 0 && a->x_out == nullptr), "dfl_conv2d: x_mode (fused BatchNorm + ReLU backward operand) and x_out are implemented by the bf16 patch kernels only");
+  DFL_REQUIRE(a->out_scale == nullptr, "dfl_conv2d: out_scale / out_shift are implemented by the latency form only (dfl_conv_config tells)");
+  DFL_REQUIRE(a->x_mode == 0 && a->x_out == nullptr, "dfl_conv2d: x_mode (fused BatchNorm + ReLU backward operand) and x_out are implemented by the bf16 patch kernels only");
   {
     // live statistics outside the bf16 patch kernels: the 1-channel direct kernels (3x3 row form: stat_totals; 1x1: add_tot) and,
     // round 5, the fp32-tensor GEMM kernels -- producer (stat_totals: plain statistics of the stored values), consumer of an input
     // (in_tot: the fast gather, whose scale / shift table lives in LDS) and of "+ BN(add)" (add_tot)
-    const bool any = a != nullptr && (a->stat_totals != nullptr || a->in_tot != nullptr || a->add_tot != nullptr);
-    const bool direct = any && dfl::direct_conv_ok(a);
+    const bool any = a->stat_totals != nullptr || a->in_tot != nullptr || a->add_tot != nullptr;
+    const bool direct = any && r.form == dfl::FORM_DIRECT;
     const bool direct_ok = direct && a->in_tot == nullptr &&
                            (a->stat_totals == nullptr || (dfl::direct_conv_rows_usable(a) && a->stat_other == nullptr)) &&
                            (a->add_tot == nullptr || (a->add != nullptr && a->add_scale == nullptr && a->add_gamma && a->add_beta && a->add_count > 0 &&
@@ -908,11 +872,7 @@ extern "C" int dfl_conv2d(const dfl_conv_args* a, dfl_stream_t stream) {
                   "dfl_conv2d (fp32 tensors): add_tot replaces add_scale / add_shift and needs add, add_gamma, add_beta, add_count");
     }
   }
-  dfl::ConvK k;
-  int rc = dfl::prepare(a, &k);
-  if (rc != DFL_OK) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dfl::direct_conv_ok(a)) {
+  if (r.form == dfl::FORM_DIRECT) {
     DFL_REQUIRE(!a->w_split && !a->x_split, "dfl_conv2d: split operands are not defined for the direct small-K kernels");
     return dfl::direct_conv_launch(a, s);
   }
@@ -925,19 +885,19 @@ extern "C" int dfl_conv2d(const dfl_conv_args* a, dfl_stream_t stream) {
     k.cps = (int)dfl::ceil_div(nchunks, a->splits);
   }
   if (a->w_split || a->x_split) {
-    DFL_REQUIRE(k.fast && (dfl::math_mode() == 1 || dfl::math_mode() == 3) && !dfl::direct_conv_ok(a),
+    DFL_REQUIRE(k.fast && (dfl::math_mode() == 1 || dfl::math_mode() == 3),
                 "dfl_conv2d: split operands need math mode 1 or 3 (bf16x3 / bf16) and the fast path (Cin %% 16 == 0, aligned, < 2 GiB)");
     DFL_REQUIRE(!a->x_split || a->in_scale == nullptr, "dfl_conv2d: a split input cannot take an affine on load");
   }
   const bool general = a->add != nullptr || a->accumulate || a->scatter2x2 || (a->stat_other != nullptr && !k.so_simple);
   const bool aff = a->in_scale != nullptr || a->in_tot != nullptr;
   DFL_REQUIRE(a->in_tot == nullptr || k.fast, "dfl_conv2d (fp32 tensors): in_tot needs the fast gather (aligned tensors below 2 GiB)");
-  if (dfl::conv_rows_tile(k)) {   // 3x3 layers in whole row segments (it checks the epilogue / slices it can take)
+  if (r.form == dfl::FORM_ROWS) {   // 3x3 layers in whole row segments (it checks the epilogue / slices it can take)
     rc = dfl::conv_rows_launch(k, s);
   } else if (!k.fast) {
     rc = dfl::launch<2, 2, 1, 1, 0, true, 1>(k, s);
   } else {
-    switch (dfl::pick_cfg(k.Mtot, a->Ntot)) {
+    switch (r.cfg) {
       case dfl::CFG_128x128: rc = dfl::launch_fast<2, 2, 2, 2>(k, aff, general, s); break;
       case dfl::CFG_128x64: rc = dfl::launch_fast<2, 2, 2, 1>(k, aff, general, s); break;
       case dfl::CFG_256x32: rc = dfl::launch_fast<4, 1, 2, 1>(k, aff, general, s); break;
@@ -946,11 +906,5 @@ extern "C" int dfl_conv2d(const dfl_conv_args* a, dfl_stream_t stream) {
     }
   }
   if (rc != DFL_OK || k.splits <= 1) return rc;
-  int tx = 1;
-  while (tx * 2 <= a->Ntot && tx * 2 <= 256) tx *= 2;
-  const int nb = dfl::finish_rows(k.Mtot, a->Ntot);
-  const int rpb = (int)dfl::ceil_div(k.Mtot, nb);
-  dim3 grid((unsigned)nb, (unsigned)dfl::ceil_div(a->Ntot, tx));
-  hipLaunchKernelGGL(dfl::conv_finish_kernel, grid, dim3(256), 0, s, k, tx, rpb);
-  return dfl::check_launch("dfl_conv2d (split-K finish)");
+  return dfl::conv_finish(k, s, "dfl_conv2d (split-K finish)");
 }

@@ -38,9 +38,7 @@ __device__ __forceinline__ uint32_t n_pack(float a, float b) {
   return __builtin_bit_cast(uint32_t, h);
 }
 
-struct NCfg { int WX, R; };
-// layouts: waves side by side (32 pixels each) x rows per wave; the patch is 32 WX pixels wide and R (4 / WX) rows high
-constexpr NCfg kN[CONVN_LAYOUTS] = {{2, 4}, {2, 6}, {1, 4}, {1, 6}, {2, 3}, {1, 3}};
+// layouts (convn_layouts): waves side by side (32 pixels each) x rows per wave; the patch is 32 WX pixels wide and R (4 / WX) rows high
 
 #ifndef DFL_CONVN_WL
 #define DFL_CONVN_WL 0       // several channel blocks: a block's weights through LDS and the next block requested ahead (0: the register ring; A/B builds)
@@ -529,25 +527,22 @@ __global__ void __launch_bounds__(256, PERS ? 2 : n_occ(NCT, R, MB)) convn_kerne
 }
 
 // LDS: the image, (several channel blocks) a block's weights, the tables
-size_t n_tab_off(int layout, int cin, int ntot, int pers) {
-  const NCfg c = kN[layout];
+static size_t n_tab_off(int layout, int cin, int ntot, int pers) {
+  const NLayout c = convn_layouts()[layout];
   const size_t img = (size_t)(c.R * (4 / c.WX) + 2) * (32 * c.WX + 2) * (2 * 32 + 16);
   return (img + 15) / 16 * 16 + ((cin > 32 && DFL_CONVN_WL != 0) || pers != 0 ? (size_t)18 * 1024 * (ntot / 32) : 0);
 }
 
 template <int NCT, int WX, int R, bool MB, bool PERS>
-int convn_launch_t(const ConvP& p, int layout, hipStream_t s) {
-  ConvP pl = p;
-  pl.tab_off = (int)n_tab_off(layout, p.a.Cin, p.a.Ntot, PERS ? 1 : 0);
-  const size_t lds = convn_lds_bytes(layout, p.a.Cin, p.a.Ntot, PERS ? 1 : 0);
-  DFL_REQUIRE(lds <= 160 * 1024, "dfl_conv2d (bf16, narrow 3x3): %zu bytes of LDS", lds);
+int convn_launch_t(const ConvPlan& pl, hipStream_t s) {
+  const ConvP& p = pl.p;
   const bool aff = p.a.in_scale != nullptr || p.a.in_tot != nullptr;
   dim3 grid((unsigned)p.grid);
 #define DFL_CN_LAUNCH(AFF_)                                                                                                   \
   {                                                                                                                             \
     auto k = convn_kernel<32, NCT, WX, R, AFF_, MB, PERS>;                                                                      \
-    DFL_LDS_OPT_IN(k, 160 * 1024, "dfl_conv2d (bf16, narrow 3x3)") \
-    hipLaunchKernelGGL(k, grid, dim3(256), lds, s, pl);                                                                         \
+    DFL_LDS_OPT_IN(k, kLdsOptIn, "dfl_conv2d (bf16, narrow 3x3)")                                                              \
+    hipLaunchKernelGGL(k, grid, dim3(256), pl.lds, s, p);                                                                       \
   }
   if (p.a.x_mode != 0) DFL_CN_LAUNCH(2)
   else if (aff) DFL_CN_LAUNCH(1)
@@ -557,27 +552,35 @@ int convn_launch_t(const ConvP& p, int layout, hipStream_t s) {
 }
 
 template <int WX, int R>
-int convn_launch_n(const ConvP& p, int layout, int pers, hipStream_t s) {
-  if (pers != 0) {
+int convn_launch_n(const ConvPlan& pl, hipStream_t s) {
+  const ConvP& p = pl.p;
+  if (pl.pers != 0) {
     if constexpr (R <= 3) {
-      if (p.a.Ntot == 32 && p.nblk == 1) return convn_launch_t<1, WX, R, false, true>(p, layout, s);
+      if (p.a.Ntot == 32 && p.nblk == 1) return convn_launch_t<1, WX, R, false, true>(pl, s);
     }
-    set_error("dfl_conv2d (bf16, narrow 3x3): the persistent form of layout %d takes 32 -> 32 layers", layout);
+    set_error("dfl_conv2d (bf16, narrow 3x3): the persistent form of configuration %d takes 32 -> 32 layers", p.tile);
     return DFL_ERR_INVALID_ARG;
   }
-  if (p.a.Ntot == 32) return p.nblk > 1 ? convn_launch_t<1, WX, R, true, false>(p, layout, s) : convn_launch_t<1, WX, R, false, false>(p, layout, s);
+  if (p.a.Ntot == 32) return p.nblk > 1 ? convn_launch_t<1, WX, R, true, false>(pl, s) : convn_launch_t<1, WX, R, false, false>(pl, s);
   if (p.nblk > 1) {
-    if constexpr (n_inst(2, R, true)) return convn_launch_t<2, WX, R, true, false>(p, layout, s);
+    if constexpr (n_inst(2, R, true)) return convn_launch_t<2, WX, R, true, false>(pl, s);
   } else {
-    if constexpr (n_inst(2, R, false)) return convn_launch_t<2, WX, R, false, false>(p, layout, s);
+    if constexpr (n_inst(2, R, false)) return convn_launch_t<2, WX, R, false, false>(pl, s);
   }
-  set_error("dfl_conv2d (bf16, narrow 3x3): layout %d is not built for 64 columns and %d input channels", layout, p.a.Cin);
+  set_error("dfl_conv2d (bf16, narrow 3x3): configuration %d is not built for 64 columns and %d input channels", p.tile, p.a.Cin);
   return DFL_ERR_INVALID_ARG;
 }
 
 }  // namespace
 
-// The layers this form takes (the caller has validated the argument block as convp_plan_search does)
+// Layouts (the planner's configurations 58 ... 63; 64, 65: the persistent form of the two with three rows per wave)
+const NLayout* convn_layouts() {
+  static const NLayout t[kNumN] = {{2, 4, convn_launch_n<2, 4>}, {2, 6, convn_launch_n<2, 6>}, {1, 4, convn_launch_n<1, 4>},
+                                   {1, 6, convn_launch_n<1, 6>}, {2, 3, convn_launch_n<2, 3>}, {1, 3, convn_launch_n<1, 3>}};
+  return t;
+}
+
+// The layers this form takes (the caller has validated the argument block as convp_validate of conv_plan.hip does)
 bool convn_shape_ok(const dfl_conv_args& a) {
   return a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.scatter2x2 == 0 && a.Cin % 32 == 0 && a.Cin <= 256 &&
          (a.Ntot == 32 || a.Ntot == 64) && a.Hout == a.Hin && a.Wout == a.Win && a.out_scale == nullptr && a.add == nullptr &&
@@ -586,32 +589,16 @@ bool convn_shape_ok(const dfl_conv_args& a) {
   // registers -- measured slower than convp: 29 against 27 us for the 96 x 96 64 -> 64 data gradient)
 }
 
-bool convn_layout_ok(int layout, int ntot, int cin) { return layout >= 0 && layout < CONVN_LAYOUTS && n_inst(ntot / 32, kN[layout].R, cin > 32); }
+bool convn_layout_ok(int layout, int ntot, int cin) { return layout >= 0 && layout < kNumN && n_inst(ntot / 32, convn_layouts()[layout].R, cin > 32); }
 
-void convn_patch(int layout, int* ph, int* pw) {
-  *ph = kN[layout].R * (4 / kN[layout].WX);
-  *pw = 32 * kN[layout].WX;
-}
+bool convn_pers_ok(int layout, const dfl_conv_args& a) { return layout >= 0 && layout < kNumN && convn_layouts()[layout].R <= 3 && a.Cin == 32 && a.Ntot == 32; }
 
-bool convn_pers_ok(int layout, const dfl_conv_args& a) { return layout >= 0 && layout < CONVN_LAYOUTS && kN[layout].R <= 3 && a.Cin == 32 && a.Ntot == 32; }
-
-size_t convn_lds_bytes(int layout, int cin, int ntot, int pers) {
+size_t convn_lds_bytes(int layout, int cin, int ntot, int pers, int* tab_off) {
   size_t img = n_tab_off(layout, cin, ntot, pers);
+  if (tab_off != nullptr) *tab_off = (int)img;
   const size_t red = (size_t)4 * (ntot / 32) * 16 * 64 * sizeof(float);      // the statistics' pass through LDS
   if (img < red) img = red;
   return img + (size_t)(3 * cin + ntot + 2 * ntot * 4) * sizeof(float);
-}
-
-int convn_launch(const ConvP& p, int layout, int pers, hipStream_t s) {
-  DFL_REQUIRE(layout >= 0 && layout < CONVN_LAYOUTS && p.CK == 32 && p.splits == 1, "dfl_conv2d (bf16, narrow 3x3): layout %d, %d resident channels, %d K slices", layout, p.CK, p.splits);
-  switch (layout) {
-    case 0: return convn_launch_n<2, 4>(p, layout, pers, s);
-    case 1: return convn_launch_n<2, 6>(p, layout, pers, s);
-    case 2: return convn_launch_n<1, 4>(p, layout, pers, s);
-    case 3: return convn_launch_n<1, 6>(p, layout, pers, s);
-    case 4: return convn_launch_n<2, 3>(p, layout, pers, s);
-    default: return convn_launch_n<1, 3>(p, layout, pers, s);
-  }
 }
 
 }  // namespace dfl

@@ -25,13 +25,7 @@
 //     normalise).  K slices (blockIdx.z = ranges of channel blocks) leave fp32 partial sums for convp_finish_kernel.
 //
 // Geometry (patch shape, resident channels, K slices, tile configuration) is chosen on the host per layer
-// (convp_plan): candidates are scored by matrix work x rounds over the 256 CUs, including the fill of the last tiles.
-#include <stdlib.h>
-#include <string.h>
-
-#include <mutex>
-#include <vector>
-
+// (convp_plan, conv_plan.hip): candidates are scored by matrix work x rounds over the 256 CUs, including the fill of the last tiles.
 #include "common.h"
 #include "convp.h"
 
@@ -795,41 +789,6 @@ __global__ void __launch_bounds__(256) convp_finish_kernel(const ConvP p, int TX
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 
-struct TileCfg { int WM, WN, TM, TN, GA, KS, Q, P, NL; };   // GA: A fragments straight from global memory (1x1 windows, see the kernel); KS: k-groups (1 or 2);
-                                                       // Q: the unrolled 3x3 form of convq_bf16.hip (8 WM x 12 patch, 32 WN columns); P: its persistent form;
-                                                       // NL: layout + 1 of the narrow 3x3 form of convn_bf16.hip
-// value reported by dfl_conv_config for these kernels = 16 + index
-static const TileCfg kTiles[] = {{4, 1, 2, 1, 0, 1}, {4, 1, 1, 1, 0, 1}, {2, 2, 4, 1, 0, 1}, {2, 2, 3, 1, 0, 1}, {2, 2, 2, 1, 0, 1}, {1, 4, 2, 1, 0, 1},
-                                 {1, 4, 3, 1, 0, 1}, {1, 4, 4, 1, 0, 1}, {1, 4, 6, 1, 0, 1}, {1, 4, 9, 1, 0, 1}, {2, 2, 1, 1, 0, 1}, {1, 4, 1, 1, 0, 1},
-                                 {4, 1, 3, 1, 0, 1}, {4, 1, 4, 1, 0, 1}, {2, 2, 6, 1, 0, 1},
-                                 // two column tiles per wave: half the LDS fragment reads per matrix instruction
-                                 {2, 2, 2, 2, 0, 1}, {2, 2, 3, 2, 0, 1}, {2, 2, 4, 2, 0, 1}, {4, 1, 2, 2, 0, 1}, {4, 1, 3, 2, 0, 1}, {1, 4, 2, 2, 0, 1}, {1, 4, 3, 2, 0, 1},
-                                 // 1x1 windows streamed from global memory (22 ...): only ever chosen through the measured table
-                                 {4, 1, 1, 1, 1, 1}, {4, 1, 2, 1, 1, 1}, {2, 2, 1, 1, 1, 1}, {2, 2, 2, 1, 1, 1}, {1, 4, 1, 1, 1, 1}, {1, 4, 2, 1, 1, 1},
-                                 {4, 1, 1, 2, 1, 1}, {2, 2, 1, 2, 1, 1},
-                                 // two k-groups (512 threads, 30 ...): only ever chosen through the measured table
-                                 {1, 4, 3, 1, 0, 2}, {1, 4, 2, 1, 0, 2}, {1, 4, 4, 1, 0, 2}, {2, 2, 3, 1, 0, 2}, {2, 2, 2, 1, 0, 2}, {1, 4, 2, 2, 0, 2},
-                                 {2, 2, 2, 2, 0, 2}, {4, 1, 3, 1, 0, 2}, {4, 1, 2, 1, 0, 2},
-                                 // (39 = CONVS_TILE: the latency form plans itself, never through this table)
-                                 {0, 0, 0, 0, 0, 0, 0},
-                                 // unrolled 3x3 form (convq_bf16.hip; 40: one k-group, 41: two): chosen through the measured table or, for
-                                 // the layer shapes convq_default() names, by default
-                                 {1, 4, 3, 1, 0, 1, 1}, {1, 4, 3, 1, 0, 2, 1},
-                                 // ... 42: eight waves on a 16 x 12 patch; 43-45: 64 columns; 46-48: 32 columns (WM x 8 patch rows)
-                                 {2, 4, 3, 1, 0, 1, 1}, {2, 2, 3, 1, 0, 1, 1}, {4, 2, 3, 1, 0, 1, 1}, {2, 2, 3, 1, 0, 2, 1},
-                                 {4, 1, 3, 1, 0, 1, 1}, {8, 1, 3, 1, 0, 1, 1}, {4, 1, 3, 1, 0, 2, 1},
-                                 // 49-57: the same nine layouts, persistent (a workgroup walks several patches, the next one staged ahead)
-                                 {1, 4, 3, 1, 0, 1, 1, 1}, {1, 4, 3, 1, 0, 2, 1, 1}, {2, 4, 3, 1, 0, 1, 1, 1}, {2, 2, 3, 1, 0, 1, 1, 1}, {4, 2, 3, 1, 0, 1, 1, 1},
-                                 {2, 2, 3, 1, 0, 2, 1, 1}, {4, 1, 3, 1, 0, 1, 1, 1}, {8, 1, 3, 1, 0, 1, 1, 1}, {4, 1, 3, 1, 0, 2, 1, 1},
-                                 // 58-63: the narrow 3x3 form (convn_bf16.hip: 32 / 64 output columns, its six layouts); table only
-                                 {4, 1, 1, 1, 0, 1, 0, 0, 1}, {4, 1, 1, 1, 0, 1, 0, 0, 2}, {4, 1, 1, 1, 0, 1, 0, 0, 3}, {4, 1, 1, 1, 0, 1, 0, 0, 4},
-                                 {4, 1, 1, 1, 0, 1, 0, 0, 5}, {4, 1, 1, 1, 0, 1, 0, 0, 6},
-                                 // 64, 65: its persistent form (layouts 4 and 5; 32 -> 32 layers)
-                                 {4, 1, 1, 1, 0, 1, 0, 1, 5}, {4, 1, 1, 1, 0, 1, 0, 1, 6}};
-constexpr int kNumTiles = (int)(sizeof(kTiles) / sizeof(kTiles[0]));
-static_assert(kNumTiles == CONVN_PERS_TILE + 2 && CONVN_PERS_TILE == CONVN_TILE + CONVN_LAYOUTS && CONVN_TILE == CONVQ_TILE + 2 * CONVQ_LAYOUTS && CONVQ_TILE == CONVS_TILE + 1, "convp.h: CONVS_TILE is the index behind the patch-kernel configurations, the unrolled 3x3 forms follow it");
-constexpr size_t kLdsSoft = 64 * 1024, kLdsHard = 150 * 1024;
-
 // Row blocks of convp_finish_kernel = rows of stat_partials the following finalize kernel has to read.  Few (<= FIN_ROWS) and
 // the finalize launch reads a few hundred KB instead of up to 4.7 MB (one row per 1-2 GEMM rows on the deep levels: its
 // 10-12 us there against 5-6 us elsewhere); the finish kernel keeps its parallelism through narrow column blocks (FIN_TX).
@@ -845,537 +804,62 @@ static int finish_rows_p(int M, int Ntot) {
 
 int convp_finish_rows(const ConvP& p) { return finish_rows_p(p.Mtot, p.a.Ntot); }
 
-// Fill p's geometry for tile configuration t and a patch of (ipp images, ph x pw pixels); returns false if impossible.
-static bool try_geometry(const dfl_conv_args& a, ConvP* p, const TileCfg& t, int ipp, int ph, int pw, int want_splits,
-                         double* cost) {
-  const int QP = t.WM * t.TM * 32;
-  if (t.WM == 0) return false;
-  if (t.NL) {
-    // narrow 3x3 form: the layout fixes the patch, all input channels pass through one image in blocks of 32, no K slices, one
-    // column tile; workgroups are dealt to the XCDs in runs of q_ngroups patches.  Scored only by measurement.
-    int nph, npw;
-    convn_patch(t.NL - 1, &nph, &npw);
-    if (ipp != 1 || ph != nph || pw != npw || want_splits > 1 || !convn_shape_ok(a) || !convn_layout_ok(t.NL - 1, a.Ntot, a.Cin)) return false;
-    p->IPP = 1;
-    p->PH = ph;
-    p->PW = pw;
-    p->mPP = (uint32_t)(((1ull << 32) + (uint64_t)(ph * pw) - 1) / (uint64_t)(ph * pw));
-    p->mPW = (uint32_t)(((1ull << 32) + (uint64_t)pw - 1) / (uint64_t)pw);
-    p->npy = (int)ceil_div(p->Hg, ph);
-    p->npx = (int)ceil_div(p->Wg, pw);
-    p->npatch = a.N * p->npy * p->npx;
-    if (p->npatch >= 65536) return false;              // (the kernel divides patch numbers by multiply-high)
-    p->IH = ph + 2;
-    p->IW = pw + 2;
-    p->CK = 32;
-    p->nblk = a.Cin / 32;
-    p->splits = 1;
-    p->blk_per_slice = p->nblk;
-    p->ntiles = 1;
-    p->pix_stride = 80;
-    p->upp_shift = 2;
-    p->lds_bytes = p->IH * p->IW * 80;
-    p->xcd_mode = 0;
-    p->q_ngroups = (int)ceil_div(p->npatch, 8);
-    p->q_stride = p->q_ngroups;
-    p->grid = 8 * p->q_ngroups;
-    if (t.P) {                                         // persistent: two workgroups per CU (64 per XCD), each walks several patches of its XCD's run
-      if (!convn_pers_ok(t.NL - 1, a) || p->q_ngroups <= 64) return false;
-      p->q_stride = 64;
-      p->grid = 8 * 64;
-    }
-    auto magic = [](int d) { return (uint32_t)(((1ull << 32) + (uint64_t)d - 1) / (uint64_t)d); };
-    p->qm_npatch = magic(p->npatch);
-    p->qm_ntiles = magic(1);
-    p->qm_perimg = magic(p->npy * p->npx);
-    p->qm_npx = magic(p->npx);
-    if (convn_lds_bytes(t.NL - 1, a.Cin, a.Ntot, t.P) > 160 * 1024) return false;
-    *cost = 1e289;
-    return true;
-  }
-  if (ipp < 1 || ph < 1 || pw < 1 || (int64_t)ipp * ph * pw > QP) return false;
-  if (ipp > 1 && (ph != p->Hg || pw != p->Wg)) return false;
-  if (t.Q && (ipp != 1 || ph != 8 * t.WM || pw != 12 || !convq_shape_ok(a))) return false;
-  p->IPP = ipp;
-  p->PH = ph;
-  p->PW = pw;
-  p->mPP = (uint32_t)(((1ull << 32) + (uint64_t)(ph * pw) - 1) / (uint64_t)(ph * pw));
-  p->mPW = (uint32_t)(((1ull << 32) + (uint64_t)pw - 1) / (uint64_t)pw);
-  p->npy = (int)ceil_div(p->Hg, ph);
-  p->npx = (int)ceil_div(p->Wg, pw);
-  p->npatch = (int)ceil_div(a.N, ipp) * p->npy * p->npx;
-  p->IH = (ph - 1) * a.stride + a.KH;
-  p->IW = (pw - 1) * a.stride + a.KW;
-  const int64_t npix = (int64_t)ipp * p->IH * p->IW;
-  if (t.GA) {
-    // streamed non-overlapping window (1x1 / stride 1, 2x2 / stride 2): no LDS image, no K slices; scored only by
-    // measurement (tools/tune_convp.py)
-    if (a.KH != a.KW || a.stride != a.KH || a.KH > 2 || a.pad != 0 || a.in_scale != nullptr || a.in_tot != nullptr || a.x_mode != 0 || want_splits > 1) return false;
-    p->CK = 16;
-    p->nblk = a.Cin / 16;
-    p->splits = 1;
-    p->blk_per_slice = p->nblk;
-    p->pix_stride = 48;
-    p->upp_shift = 1;
-    p->lds_bytes = 0;
-    p->ntiles = (int)ceil_div(a.Ntot, t.WN * t.TN * 32);
-    p->xcd_mode = 0;
-    p->grid = p->npatch * p->ntiles;
-    *cost = 1e290;
-    return true;
-  }
-  // resident channels: the largest power-of-two multiple of 16 (<= 128, dividing Cin) whose image fits
-  int ck = 128;
-  while (ck > 16 && (a.Cin % ck != 0 || (!t.Q && npix * (ck * 2 + 16) > (int64_t)kLdsSoft))) ck >>= 1;
-  if (a.Cin % ck != 0) return false;
-  const int qmode = ((int)(&t - kTiles) - CONVQ_TILE) % CONVQ_LAYOUTS;    // (the unrolled form: its wave layout)
-  const int ck_min = t.Q ? 32 : 16;
-  if (t.Q) {                                       // the largest resident block the layout is instantiated for and whose image fits
-    while (ck >= 32 && (a.Cin % ck != 0 || !convq_ck_ok(qmode, ck) || convq_lds_bytes(ck, qmode, a.Cin / ck > 1 ? 2 : 1, t.P) > 160 * 1024)) ck >>= 1;
-  }
-  if (ck < ck_min) return false;
-  size_t lds = (size_t)npix * (ck * 2 + 16);
-  if (lds > kLdsHard) return false;
-  const int bn = t.WN * t.TN * 32;
-  const int ntiles = (int)ceil_div(a.Ntot, bn);
-  const int64_t wgs = (int64_t)p->npatch * ntiles;
-  int nblk = a.Cin / ck;
-  // K slices: only whole channel blocks; more blocks (smaller ck) when the layer needs the parallelism
-  int splits = 1;
-  if (want_splits > 1) {
-    splits = want_splits;
-    while (nblk % splits != 0 && ck > ck_min) {
-      ck >>= 1;
-      nblk = a.Cin / ck;
-    }
-    if (t.Q && !convq_ck_ok(qmode, ck)) return false;
-    if (nblk % splits != 0) return false;
-    lds = (size_t)npix * (ck * 2 + 16);
-  }
-  p->CK = ck;
-  p->nblk = nblk;
-  p->splits = splits;
-  p->ntiles = ntiles;
-  {
-    // workgroup -> XCD placement (see the kernel): weight-major when one pass over the weights is the larger stream
-    static const int xcd_env = [] {
-      const char* e = getenv("DFL_CONVP_XCD");       // 0: never weight-major (A/B measurements)
-      return e ? atoi(e) : 1;
-    }();
-    const int64_t wbytes = (int64_t)a.KH * a.KW * a.Cin * a.Ntot * 2;
-    const int64_t abytes = (int64_t)a.N * a.Hin * a.Win * a.Cin * 2;
-    const int pairs = ntiles * splits;
-    p->xcd_mode = 0;
-    p->grid = p->npatch * pairs;
-    if (xcd_env != 0 && wbytes > abytes && wbytes > (1 << 20)) {
-      if (pairs >= 8 && pairs % 8 == 0) {
-        p->xcd_mode = 1;
-      } else if (pairs < 8 && 8 % pairs == 0 && p->npatch >= 8 / pairs) {
-        p->xcd_mode = 2;
-        p->grid = 8 * (int)ceil_div(p->npatch, 8 / pairs);
-      }
-    }
-  }
-  if (t.Q) {
-    if (p->grid >= 65536 || p->npatch >= 65536) return false;      // (the kernel divides workgroup numbers by multiply-high)
-    const size_t qlds = convq_lds_bytes(ck, qmode, nblk / splits, t.P);
-    if (qlds > 160 * 1024) return false;
-    if (t.P) {
-      if (!convq_pers_ok(qmode, ck, a.x_mode)) return false;
-      // persistent: as many workgroups per (column tile, K slice) as the CUs hold at once, patches dealt out evenly; pointless
-      // (and refused) when that leaves one patch per workgroup
-      int occ = convq_threads(qmode) == 512 ? 1 : 2;
-      if ((size_t)occ * qlds > 160 * 1024) occ = 1;
-      int g0 = 256 * occ / (ntiles * splits);
-      if (g0 < 1) g0 = 1;
-      if (g0 >= p->npatch) return false;
-      const int per = (int)ceil_div(p->npatch, g0);
-      p->q_ngroups = (int)ceil_div(p->npatch, per);
-      p->xcd_mode = 0;
-      p->grid = p->q_ngroups * ntiles * splits;
-    }
-    auto magic = [](int d) { return (uint32_t)(((1ull << 32) + (uint64_t)d - 1) / (uint64_t)d); };
-    p->qm_npatch = magic(t.P ? p->q_ngroups : p->npatch);
-    p->qm_ntiles = magic(ntiles);
-    p->qm_perimg = magic(p->npy * p->npx);
-    p->qm_npx = magic(p->npx);
-  }
-  p->blk_per_slice = nblk / splits;
-  p->pix_stride = ck * 2 + 16;
-  int sh = 0;
-  while ((1 << sh) < (ck >> 3)) ++sh;
-  p->upp_shift = sh;
-  p->lds_bytes = (int)lds;
-  // Cost model (cycles), fitted to per-layer timings on MI355X (tools/kbench_bf16.py).  A workgroup's k loop is bound by
-  // the matrix pipe (32 cycles per instruction and wave, one wave per SIMD), by its LDS fragment reads, or by the B
-  // fragments coming from L1/L2 (each wave 1 KiB per k-step and column tile: ~32 B/clk/CU when the four waves read
-  // different columns, more when they share them); around it sit latencies nobody inside the workgroup hides: staging
-  // the patch (one global round trip + the LDS writes) and one pass per accumulator tile row in the epilogue.  `occ`
-  // workgroups share a CU (LDS, registers: 512 / allocation of the tile configuration): while one waits another computes.
-  static const int occ_by_tm[10] = {0, 5, 4, 4, 3, 2, 2, 2, 2, 2};
-  int occ = (int)((160 * 1024) / (lds + 1024));
-  if (occ > occ_by_tm[t.TM]) occ = occ_by_tm[t.TM];
-  if (occ < 1) occ = 1;
-  const int64_t total = wgs * splits;
-  int64_t eff = ceil_div(total, 256);
-  if (eff > occ) eff = occ;                                                      // workgroups actually sharing a CU
-  const int64_t rounds = ceil_div(total, 256 * eff);
-  const int steps = (a.KH * a.KW * (ck / 16) + 3) / 4 * 4 * p->blk_per_slice;
-  const double mfma = (double)t.TM * t.TN * steps * 32.0;
-  const double ldsread = (double)t.TM * steps * 4.0 * 4.0;                       // ds_read_b128 cycles of the 4 waves
-  const double bbw = t.WN == 4 ? 32.0 : (t.WN == 2 ? 48.0 : 64.0);
-  const double bload = (double)steps * t.TN * 4096.0 / bbw;
-  double loop = mfma > ldsread ? mfma : ldsread;
-  if (bload > loop) loop = bload;
-  const double lat = (double)p->blk_per_slice * (4000.0 + (double)lds / 40.0) + 2000.0 + (splits > 1 ? 1500.0 : 2500.0 * t.TM);
-  const double busy = (double)eff * (loop + (double)p->blk_per_slice * (double)lds / 40.0);   // what the CU's pipes must do per round
-  const double per_round = busy > lat + loop ? busy : lat + loop;
-  double c = (double)rounds * per_round;
-  if (splits > 1) c += (double)p->Mtot * a.Ntot * 4.0 * (splits + 1) / 2000.0 + 6000.0;   // partial sums: bytes / (B per cycle of the chip) + the finish launch
-  *cost = (t.KS == 2 || t.Q) ? 1e289 : c;              // (two k-groups, the unrolled form: scored only by measurement, tools/tune_convp.py)
-  return true;
-}
-
-// ---- geometry candidates, forced geometry, tuning table
-struct ConvGeom { int tile, ipp, ph, pw, splits; };
-static thread_local ConvGeom t_force = {-1, 0, 0, 0, 0};
-struct TuneEntry { int key[10]; ConvGeom g; };
-static std::mutex g_tune_mu;
-static std::vector<TuneEntry> g_tune;
-
-static void tune_key(const dfl_conv_args& a, int* k) {
-  k[0] = a.N; k[1] = a.Hin; k[2] = a.Win; k[3] = a.Cin; k[4] = a.Ntot;
-  k[5] = a.KH; k[6] = a.KW; k[7] = a.stride; k[8] = a.pad; k[9] = a.scatter2x2 ? 1 : 0;
-}
-
-static bool tune_lookup(const dfl_conv_args& a, ConvGeom* g) {
-  int k[10];
-  tune_key(a, k);
-  std::lock_guard<std::mutex> lock(g_tune_mu);
-  for (const TuneEntry& e : g_tune)
-    if (memcmp(e.key, k, sizeof(k)) == 0) {
-      *g = e.g;
-      return true;
-    }
-  return false;
-}
-
-// Tile configurations x patch shapes x K slices that are valid for the layer.  The cost model looks at the tiles whose
-// column count matches the layer (`wide` false); tuners also get the narrower column tiles (more workgroups).
-template <typename F>
-static void for_each_candidate(const dfl_conv_args& a, const ConvP& base, int force_splits, bool wide, F&& f) {
-  static const unsigned tile_off = [] {      // DFL_CONVP_TILES_OFF: bit mask of tile configurations to leave out (A/B measurements)
-    const char* e = getenv("DFL_CONVP_TILES_OFF");
-    return e ? (unsigned)strtoul(e, nullptr, 0) : 0u;
-  }();
-  const int n32 = (int)ceil_div(a.Ntot, 32) * 32;
-  for (int ti = 0; ti < kNumTiles; ++ti) {
-    if ((tile_off >> ti) & 1u) continue;
-    const TileCfg& t = kTiles[ti];
-    const int bn = t.WN * t.TN * 32;
-    if (t.NL) {
-      // (takes all the layer's columns itself)
-    } else if (wide) {
-      if (bn > n32 || (bn < 64 && n32 >= 64) || (t.TN > 1 && bn > a.Ntot)) continue;
-    } else {
-      if (t.TN != 1 || t.GA || t.KS != 1) continue;   // the model was fitted on the one-column-tile, one-k-group configurations
-      if (a.Ntot <= 32 && t.WN != 1) continue;
-      if (a.Ntot > 32 && a.Ntot <= 64 && t.WN != 2) continue;
-      if (a.Ntot > 64 && t.WN != 4) continue;
-    }
-    const int QP = t.WM * t.TM * 32;
-    int shapes[24][3];
-    int ns = 0;
-    const int HW = base.Hg * base.Wg;
-    if (t.NL) {                                      // the layout's patch
-      if (!wide || !convn_shape_ok(a)) continue;
-      int nph, npw;
-      convn_patch(t.NL - 1, &nph, &npw);
-      shapes[ns][0] = 1; shapes[ns][1] = nph; shapes[ns][2] = npw; ++ns;
-    } else
-    if (t.Q) {                                       // one patch shape
-      if (!wide) continue;
-      shapes[ns][0] = 1; shapes[ns][1] = 8 * t.WM; shapes[ns][2] = 12; ++ns;
-    } else
-    if (!t.NL && HW <= QP) {                         // whole images
-      shapes[ns][0] = QP / HW; shapes[ns][1] = base.Hg; shapes[ns][2] = base.Wg; ++ns;
-    }
-    if (!t.Q && !t.NL && base.Wg <= QP) {            // whole rows
-      int ph = QP / base.Wg;
-      if (ph > base.Hg) ph = base.Hg;
-      shapes[ns][0] = 1; shapes[ns][1] = ph; shapes[ns][2] = base.Wg; ++ns;
-    }
-    static const int kPh[] = {1, 2, 4, 8, 16, 3, 6, 12};        // row pieces (the model looks at the powers of two)
-    for (int k = 0; k < (wide ? 8 : 5) && ns < 22 && !t.Q && !t.NL; ++k) {
-      const int ph = kPh[k];
-      int pw = QP / ph;
-      if (pw >= base.Wg || ph > base.Hg) continue;
-      shapes[ns][0] = 1; shapes[ns][1] = ph; shapes[ns][2] = pw; ++ns;
-    }
-    for (int si = 0; si < ns; ++si) {
-      for (int sp = 1; sp <= 32; sp *= 2) {
-        if (force_splits > 0 && sp != force_splits) continue;
-        if (!wide && a.scatter2x2 == 0 && a.accumulate == 0 && sp > 1 && base.T * a.Cin < 1024) break;   // short K: never sliced
-        ConvP q = base;
-        double c;
-        if (!try_geometry(a, &q, t, shapes[si][0], shapes[si][1], shapes[si][2], sp, &c)) continue;
-        if (q.splits != sp) continue;
-        f(ti, q, c);
-      }
-    }
-  }
-}
-
-static int convp_plan_search(const dfl_conv_args* a, ConvP* p, int force_splits) {
-  DFL_REQUIRE(a->x && a->w && a->y, "dfl_conv2d (bf16): x, w and y are required");
-  DFL_REQUIRE(a->N > 0 && a->Hin > 0 && a->Win > 0 && a->Cin > 0 && a->Ntot > 0, "dfl_conv2d (bf16): bad sizes");
-  DFL_REQUIRE(a->Ntot % 8 == 0 && a->ldy % 8 == 0 && aligned16(a->y) && (a->add == nullptr || (a->ldadd % 8 == 0 && aligned16(a->add))) &&
-                  (a->stat_other == nullptr || (a->ldso % 8 == 0 && aligned16(a->stat_other))),
-              "dfl_conv2d (bf16): output columns and the pixel strides of y / add / stat_other must be multiples of 8, tensors 16-byte aligned");
-  {
-    const int64_t opx = (int64_t)a->N * a->Hout * a->Wout, lim = 1ll << 32;
-    DFL_REQUIRE(opx * a->ldy < lim && (a->add == nullptr || opx * a->ldadd < lim) && (a->stat_other == nullptr || opx * a->ldso < lim),
-                "dfl_conv2d (bf16): y / add / stat_other must stay below 2^32 elements");
-  }
-  DFL_REQUIRE(a->Cin % 16 == 0 && a->ldx % 8 == 0 && aligned16(a->x) && aligned16(a->w),
-              "dfl_conv2d (bf16): needs Cin %% 16 == 0, ldx %% 8 == 0 and 16-byte aligned x / w (Cin = %d, ldx = %d)", a->Cin, a->ldx);
-  DFL_REQUIRE(a->w_split == 2, "dfl_conv2d (bf16): weights must be packed with dfl_pack_job.split = 2");
-  DFL_REQUIRE(a->x_mode != 0 || (a->in_scale == nullptr) == (a->in_shift == nullptr), "dfl_conv2d: in_scale/in_shift go together");
-  DFL_REQUIRE(a->in_tot == nullptr || (a->in_scale == nullptr && a->in_gamma != nullptr && a->in_count > 0 &&
-                                       (a->x_mode == 0 ? a->in_beta != nullptr : (a->in_mean != nullptr && a->in_invstd != nullptr))),
-              "dfl_conv2d (bf16): in_tot replaces in_scale / in_shift and needs in_gamma, in_count and in_beta (x_mode 0) or in_mean, in_invstd (x_mode 1)");
-  DFL_REQUIRE(a->add_tot == nullptr || (a->add != nullptr && a->add_scale == nullptr && a->add_gamma != nullptr && a->add_beta != nullptr && a->add_count > 0),
-              "dfl_conv2d (bf16): add_tot replaces add_scale / add_shift and needs add, add_gamma, add_beta, add_count");
-
-  DFL_REQUIRE((a->add_scale == nullptr) == (a->add_shift == nullptr), "dfl_conv2d: add_scale/add_shift go together");
-  DFL_REQUIRE(a->KH * a->KW <= 16 && a->KH > 0 && a->KW > 0 && a->stride > 0 && a->pad >= 0, "dfl_conv2d (bf16): bad window");
-  memset(p, 0, sizeof(*p));
-  p->a = *a;
-  if (a->scatter2x2) {
-    DFL_REQUIRE(a->KH == 1 && a->KW == 1 && a->stride == 1 && a->pad == 0, "dfl_conv2d: scatter2x2 needs a 1x1 gather");
-    DFL_REQUIRE(a->Ntot % 4 == 0 && a->Hout >= 2 * a->Hin && a->Wout >= 2 * a->Win, "dfl_conv2d: scatter2x2 geometry");
-    DFL_REQUIRE(a->add == nullptr, "dfl_conv2d: scatter2x2 has no add epilogue");
-    p->Hg = a->Hin;
-    p->Wg = a->Win;
-    p->Cout = a->Ntot / 4;
-  } else {
-    const int ho = (a->Hin + 2 * a->pad - a->KH) / a->stride + 1;
-    const int wo = (a->Win + 2 * a->pad - a->KW) / a->stride + 1;
-    DFL_REQUIRE(ho == a->Hout && wo == a->Wout, "dfl_conv2d: Hout/Wout (%d,%d) do not match the window (%d,%d)", a->Hout,
-                a->Wout, ho, wo);
-    p->Hg = a->Hout;
-    p->Wg = a->Wout;
-    p->Cout = a->Ntot;
-  }
-  DFL_REQUIRE(a->ldy >= p->Cout, "dfl_conv2d: ldy < Cout");
-  const int64_t M = (int64_t)a->N * p->Hg * p->Wg;
-  DFL_REQUIRE(M < (1ll << 31), "dfl_conv2d: too many pixels");
-  p->Mtot = (int)M;
-  p->T = a->KH * a->KW;
-  const int64_t xb = (((int64_t)a->N * a->Hin * a->Win - 1) * a->ldx + a->Cin) * 2;
-  const int64_t wb = (int64_t)p->T * a->Cin * a->Ntot * 2;
-  const int64_t lim = (1ll << 31) - 4096;
-  DFL_REQUIRE(xb < lim && wb < lim, "dfl_conv2d (bf16): tensors must stay below 2 GiB");
-  p->x_bytes = (uint32_t)xb;
-  p->w_bytes = (uint32_t)wb;
-  if (a->x_mode != 0) {
-    DFL_REQUIRE(a->x_mode == 1 && a->x2 != nullptr && a->in_shift == nullptr && a->ldx2 % 8 == 0 && aligned16(a->x2) &&
-                    (a->in_scale == nullptr || aligned16(a->in_scale)),
-                "dfl_conv2d (bf16): x_mode 1 needs x2 (16-byte aligned, ldx2 %% 8 == 0), coefficients in in_scale and no in_shift");
-    const int64_t x2b = (((int64_t)a->N * a->Hin * a->Win - 1) * a->ldx2 + a->Cin) * 2;
-    DFL_REQUIRE(x2b < lim, "dfl_conv2d (bf16): tensors must stay below 2 GiB");
-    p->x2_bytes = (uint32_t)x2b;
-  }
-  p->xo_bytes = 0;
-  if (a->x_out != nullptr) {
-    DFL_REQUIRE(a->x_mode == 1 && a->KH == 3 && a->KW == 3 && a->stride == 1 && a->pad == 1 && a->Hout == a->Hin && a->Wout == a->Win,
-                "dfl_conv2d (bf16): x_out goes with x_mode 1 of a 3x3 stride-1 pad-1 layer");
-    DFL_REQUIRE(a->ldxo % 8 == 0 && a->ldxo >= a->Cin && aligned16(a->x_out) && a->x_out != a->x && a->x_out != a->x2,
-                "dfl_conv2d (bf16): x_out must be 16-byte aligned with ldxo %% 8 == 0, ldxo >= Cin, and a tensor of its own");
-    const int64_t xob = (((int64_t)a->N * a->Hin * a->Win - 1) * a->ldxo + a->Cin) * 2;
-    DFL_REQUIRE(xob < lim, "dfl_conv2d (bf16): tensors must stay below 2 GiB");
-    p->xo_bytes = (uint32_t)xob;
-  }
-
-  // the latency form (dfl_conv_args.latency_form: small problems of a batch-1 inference forward, convs_bf16.hip) plans itself
-  if (t_force.tile < 0 && convs_eligible(*a, *p)) {
-    convs_plan(*a, p, force_splits);
-    return DFL_OK;
-  }
-
-  DFL_REQUIRE(a->out_scale == nullptr, "dfl_conv2d (bf16): out_scale / out_shift are implemented by the latency form only (dfl_conv_config tells)");
-  // a forced geometry (dfl_conv_force_geometry: tuners, tests) or an entry of the tuning table (dfl_conv_tune_add) wins
-  // over the cost model, as long as it is valid for this layer and agrees with the caller's K slices
-  double best = 1e300;
-  ConvP bestp = *p;
-  int best_tile = -1;
-  {
-    ConvGeom g;
-    const bool forced = t_force.tile >= 0;
-    if (forced) g = t_force;
-    if (forced || tune_lookup(*a, &g)) {
-      if (g.tile >= 0 && g.tile < kNumTiles && (force_splits <= 0 || force_splits == g.splits)) {
-        ConvP q = *p;
-        double c;
-        if (try_geometry(*a, &q, kTiles[g.tile], g.ipp, g.ph, g.pw, g.splits, &c) && q.splits == g.splits) {
-          best = c;
-          bestp = q;
-          best_tile = g.tile;
-        }
-      }
-      DFL_REQUIRE(!forced || best_tile >= 0, "dfl_conv2d (bf16): the forced geometry (tile %d, patch %dx%dx%d, %d slices) does not fit this layer",
-                  g.tile, g.ipp, g.ph, g.pw, g.splits);
-    }
-  }
-  if (best_tile < 0) {
-    for_each_candidate(*a, *p, force_splits, false, [&](int ti, const ConvP& q, double c) {
-      if (c < best) {
-        best = c;
-        bestp = q;
-        best_tile = ti;
-      }
-    });
-  }
-  DFL_REQUIRE(best_tile >= 0, "dfl_conv2d (bf16): no patch geometry fits this layer (%dx%d, Cin %d, Ntot %d)", a->Hin, a->Win,
-              a->Cin, a->Ntot);
-  *p = bestp;
-  p->tile = best_tile;
-  static const bool dbg = getenv("DFL_CONVP_DEBUG") != nullptr;
-  if (dbg && force_splits == 0)
-    fprintf(stderr, "convp %dx%d Cin%d->%d k%d s%d: tile %d,%d,%d patch %dx%dx%d CK %d blocks %d splits %d lds %d cost %.0f\n", a->Hin, a->Win,
-            a->Cin, a->Ntot, a->KH, a->stride, kTiles[best_tile].WM, kTiles[best_tile].WN, kTiles[best_tile].TM, p->IPP, p->PH, p->PW, p->CK,
-            p->nblk, p->splits, p->lds_bytes, best);
-  return DFL_OK;
-}
-
-// The geometry of an argument block is resolved ONCE: a recorded program replays the same blocks every step (97 convolutions
-// per training step of the paper network), and the search above -- validation, the tuning-table scan under a mutex, for
-// layers the table does not list up to ~1000 try_geometry calls -- is host time the GPU waits for on a slow host
-// (8.4 ms per step observed where the kernels take 5.3).  Keyed by the whole argument block (addresses
-// included: they select alignment-dependent paths and are copied into ConvP) and the requested K slices; a forced
-// geometry (tuners, tests) bypasses it, a changed tuning table clears it.
-struct PlanMemo { dfl_conv_args a; int force_splits; ConvP p; };
-static std::mutex g_memo_mu;
-static std::vector<PlanMemo> g_memo[64];
-static inline unsigned memo_bucket(const dfl_conv_args* a, int force_splits) {
-  uint64_t h = 1469598103934665603ull;
-  const uint64_t* w = reinterpret_cast<const uint64_t*>(a);
-  for (size_t i = 0; i < sizeof(dfl_conv_args) / 8; ++i) h = (h ^ w[i]) * 1099511628211ull;
-  h ^= (uint64_t)force_splits;
-  return (unsigned)((h ^ (h >> 29)) & 63u);
-}
-static void memo_clear() {
-  std::lock_guard<std::mutex> lock(g_memo_mu);
-  for (auto& b : g_memo) b.clear();
-}
-
-int convp_plan(const dfl_conv_args* a, ConvP* p, int force_splits) {
-  static_assert(sizeof(dfl_conv_args) % 8 == 0, "hashed as 64-bit words");
-  DFL_REQUIRE(a != nullptr && p != nullptr, "dfl_conv2d (bf16): null arguments");
-  if (t_force.tile >= 0) return convp_plan_search(a, p, force_splits);
-  const unsigned b = memo_bucket(a, force_splits);
-  {
-    std::lock_guard<std::mutex> lock(g_memo_mu);
-    for (const PlanMemo& m : g_memo[b])
-      if (m.force_splits == force_splits && memcmp(&m.a, a, sizeof(*a)) == 0) {
-        *p = m.p;
-        return DFL_OK;
-      }
-  }
-  const int rc = convp_plan_search(a, p, force_splits);
-  if (rc != DFL_OK) return rc;
-  std::lock_guard<std::mutex> lock(g_memo_mu);
-  if (g_memo[b].size() >= 256) g_memo[b].clear();          // bounded: 16 K argument blocks, then start over
-  g_memo[b].push_back(PlanMemo{*a, force_splits, *p});
-  return DFL_OK;
-}
-
 template <int WM, int WN, int TM, int TN, bool GA = false, int KS = 1>
-static int convp_launch_t(const ConvP& p, hipStream_t s) {
+static int convp_launch_t(const ConvPlan& pl, hipStream_t s) {
+  const ConvP& p = pl.p;
   const bool aff = p.a.in_scale != nullptr || p.a.in_tot != nullptr;
   dim3 grid((unsigned)p.grid);
-  size_t lds = (size_t)p.lds_bytes;
-  constexpr int BN_ = WN * TN * 32;
   constexpr int NT_ = 256 * KS;
-  constexpr int RPS_ = (NT_ / (BN_ / 8)) < WM * 32 ? (NT_ / (BN_ / 8)) : WM * 32;
-  const size_t epi = (size_t)WM * 32 * (BN_ + 4) * sizeof(float);              // epilogue image (and the k-group exchange)
-  const size_t red = (size_t)RPS_ * 2 * BN_ * sizeof(float);                   // statistics scratch
-  if (lds < epi) lds = epi;
-  if (lds < red) lds = red;
-  ConvP pl = p;                                       // the "live" BatchNorm tables sit behind everything else in LDS
-  pl.tab_off = (int)((lds + 15) / 16 * 16);
-  lds = (size_t)pl.tab_off + (384 + 3 * BN_) * sizeof(float);
-  const ConvP& p_ = pl;
   if constexpr (GA) {
     auto k = convp_kernel<WM, WN, TM, TN, 0, true>;
-    DFL_LDS_OPT_IN(k, (int)kLdsHard, "dfl_conv2d (bf16)")
-    hipLaunchKernelGGL(k, grid, dim3(256), lds, s, p_);
+    DFL_LDS_OPT_IN(k, kLdsOptIn, "dfl_conv2d (bf16)")
+    hipLaunchKernelGGL(k, grid, dim3(256), pl.lds, s, p);
   } else if (p.a.x_mode != 0) {
     auto k = convp_kernel<WM, WN, TM, TN, 2, false, KS>;
-    DFL_LDS_OPT_IN(k, (int)kLdsHard, "dfl_conv2d (bf16)")
-    hipLaunchKernelGGL(k, grid, dim3(NT_), lds, s, p_);
+    DFL_LDS_OPT_IN(k, kLdsOptIn, "dfl_conv2d (bf16)")
+    hipLaunchKernelGGL(k, grid, dim3(NT_), pl.lds, s, p);
   } else if (aff) {
     auto k = convp_kernel<WM, WN, TM, TN, 1, false, KS>;
-    DFL_LDS_OPT_IN(k, (int)kLdsHard, "dfl_conv2d (bf16)")
-    hipLaunchKernelGGL(k, grid, dim3(NT_), lds, s, p_);
+    DFL_LDS_OPT_IN(k, kLdsOptIn, "dfl_conv2d (bf16)")
+    hipLaunchKernelGGL(k, grid, dim3(NT_), pl.lds, s, p);
   } else {
     auto k = convp_kernel<WM, WN, TM, TN, 0, false, KS>;
-    DFL_LDS_OPT_IN(k, (int)kLdsHard, "dfl_conv2d (bf16)")
-    hipLaunchKernelGGL(k, grid, dim3(NT_), lds, s, p_);
+    DFL_LDS_OPT_IN(k, kLdsOptIn, "dfl_conv2d (bf16)")
+    hipLaunchKernelGGL(k, grid, dim3(NT_), pl.lds, s, p);
   }
   return check_launch("dfl_conv2d (bf16)");
 }
 
-int convp_launch(const ConvP& p, hipStream_t s) {
-  int rc;
-  switch (p.tile) {
-    case CONVS_TILE: rc = convs_launch(p, s); break;
-    case 0: rc = convp_launch_t<4, 1, 2, 1>(p, s); break;
-    case 1: rc = convp_launch_t<4, 1, 1, 1>(p, s); break;
-    case 2: rc = convp_launch_t<2, 2, 4, 1>(p, s); break;
-    case 3: rc = convp_launch_t<2, 2, 3, 1>(p, s); break;
-    case 4: rc = convp_launch_t<2, 2, 2, 1>(p, s); break;
-    case 5: rc = convp_launch_t<1, 4, 2, 1>(p, s); break;
-    case 6: rc = convp_launch_t<1, 4, 3, 1>(p, s); break;
-    case 7: rc = convp_launch_t<1, 4, 4, 1>(p, s); break;
-    case 8: rc = convp_launch_t<1, 4, 6, 1>(p, s); break;
-    case 9: rc = convp_launch_t<1, 4, 9, 1>(p, s); break;
-    case 10: rc = convp_launch_t<2, 2, 1, 1>(p, s); break;
-    case 11: rc = convp_launch_t<1, 4, 1, 1>(p, s); break;
-    case 12: rc = convp_launch_t<4, 1, 3, 1>(p, s); break;
-    case 13: rc = convp_launch_t<4, 1, 4, 1>(p, s); break;
-    case 14: rc = convp_launch_t<2, 2, 6, 1>(p, s); break;
-    case 15: rc = convp_launch_t<2, 2, 2, 2>(p, s); break;
-    case 16: rc = convp_launch_t<2, 2, 3, 2>(p, s); break;
-    case 17: rc = convp_launch_t<2, 2, 4, 2>(p, s); break;
-    case 18: rc = convp_launch_t<4, 1, 2, 2>(p, s); break;
-    case 19: rc = convp_launch_t<4, 1, 3, 2>(p, s); break;
-    case 20: rc = convp_launch_t<1, 4, 2, 2>(p, s); break;
-    case 21: rc = convp_launch_t<1, 4, 3, 2>(p, s); break;
-    case 22: rc = convp_launch_t<4, 1, 1, 1, true>(p, s); break;
-    case 23: rc = convp_launch_t<4, 1, 2, 1, true>(p, s); break;
-    case 24: rc = convp_launch_t<2, 2, 1, 1, true>(p, s); break;
-    case 25: rc = convp_launch_t<2, 2, 2, 1, true>(p, s); break;
-    case 26: rc = convp_launch_t<1, 4, 1, 1, true>(p, s); break;
-    case 27: rc = convp_launch_t<1, 4, 2, 1, true>(p, s); break;
-    case 28: rc = convp_launch_t<4, 1, 1, 2, true>(p, s); break;
-    case 29: rc = convp_launch_t<2, 2, 1, 2, true>(p, s); break;
-    case 30: rc = convp_launch_t<1, 4, 3, 1, false, 2>(p, s); break;
-    case 31: rc = convp_launch_t<1, 4, 2, 1, false, 2>(p, s); break;
-    case 32: rc = convp_launch_t<1, 4, 4, 1, false, 2>(p, s); break;
-    case 33: rc = convp_launch_t<2, 2, 3, 1, false, 2>(p, s); break;
-    case 34: rc = convp_launch_t<2, 2, 2, 1, false, 2>(p, s); break;
-    case 35: rc = convp_launch_t<1, 4, 2, 2, false, 2>(p, s); break;
-    case 36: rc = convp_launch_t<2, 2, 2, 2, false, 2>(p, s); break;
-    case 37: rc = convp_launch_t<4, 1, 3, 1, false, 2>(p, s); break;
-    case 38: rc = convp_launch_t<4, 1, 2, 1, false, 2>(p, s); break;
-    default:
-      DFL_REQUIRE(p.tile >= CONVQ_TILE && p.tile < kNumTiles, "dfl_conv2d (bf16): tile configuration %d", p.tile);
-      if (p.tile >= CONVN_PERS_TILE) rc = convn_launch(p, p.tile - CONVN_PERS_TILE + 4, 1, s);
-      else if (p.tile >= CONVN_TILE) rc = convn_launch(p, p.tile - CONVN_TILE, 0, s);
-      else rc = convq_launch(p, (p.tile - CONVQ_TILE) % CONVQ_LAYOUTS, (p.tile - CONVQ_TILE) / CONVQ_LAYOUTS, s);
-      break;
-  }
+// The configurations conv_plan.hip numbers 0 ... 38 (dfl_conv_config reports 16 + the number)
+const PatchTile* convp_tiles() {
+  static const PatchTile t[kNumPatchTiles] = {
+    {4, 1, 2, 1, 0, 1, convp_launch_t<4, 1, 2, 1>}, {4, 1, 1, 1, 0, 1, convp_launch_t<4, 1, 1, 1>}, {2, 2, 4, 1, 0, 1, convp_launch_t<2, 2, 4, 1>},
+    {2, 2, 3, 1, 0, 1, convp_launch_t<2, 2, 3, 1>}, {2, 2, 2, 1, 0, 1, convp_launch_t<2, 2, 2, 1>}, {1, 4, 2, 1, 0, 1, convp_launch_t<1, 4, 2, 1>},
+    {1, 4, 3, 1, 0, 1, convp_launch_t<1, 4, 3, 1>}, {1, 4, 4, 1, 0, 1, convp_launch_t<1, 4, 4, 1>}, {1, 4, 6, 1, 0, 1, convp_launch_t<1, 4, 6, 1>},
+    {1, 4, 9, 1, 0, 1, convp_launch_t<1, 4, 9, 1>}, {2, 2, 1, 1, 0, 1, convp_launch_t<2, 2, 1, 1>}, {1, 4, 1, 1, 0, 1, convp_launch_t<1, 4, 1, 1>},
+    {4, 1, 3, 1, 0, 1, convp_launch_t<4, 1, 3, 1>}, {4, 1, 4, 1, 0, 1, convp_launch_t<4, 1, 4, 1>}, {2, 2, 6, 1, 0, 1, convp_launch_t<2, 2, 6, 1>},
+    // two column tiles per wave (15 ...): half the LDS fragment reads per matrix instruction
+    {2, 2, 2, 2, 0, 1, convp_launch_t<2, 2, 2, 2>}, {2, 2, 3, 2, 0, 1, convp_launch_t<2, 2, 3, 2>}, {2, 2, 4, 2, 0, 1, convp_launch_t<2, 2, 4, 2>},
+    {4, 1, 2, 2, 0, 1, convp_launch_t<4, 1, 2, 2>}, {4, 1, 3, 2, 0, 1, convp_launch_t<4, 1, 3, 2>}, {1, 4, 2, 2, 0, 1, convp_launch_t<1, 4, 2, 2>},
+    {1, 4, 3, 2, 0, 1, convp_launch_t<1, 4, 3, 2>},
+    // 1x1 windows streamed from global memory (22 ...)
+    {4, 1, 1, 1, 1, 1, convp_launch_t<4, 1, 1, 1, true>}, {4, 1, 2, 1, 1, 1, convp_launch_t<4, 1, 2, 1, true>},
+    {2, 2, 1, 1, 1, 1, convp_launch_t<2, 2, 1, 1, true>}, {2, 2, 2, 1, 1, 1, convp_launch_t<2, 2, 2, 1, true>},
+    {1, 4, 1, 1, 1, 1, convp_launch_t<1, 4, 1, 1, true>}, {1, 4, 2, 1, 1, 1, convp_launch_t<1, 4, 2, 1, true>},
+    {4, 1, 1, 2, 1, 1, convp_launch_t<4, 1, 1, 2, true>}, {2, 2, 1, 2, 1, 1, convp_launch_t<2, 2, 1, 2, true>},
+    // two k-groups (512 threads, 30 ...)
+    {1, 4, 3, 1, 0, 2, convp_launch_t<1, 4, 3, 1, false, 2>}, {1, 4, 2, 1, 0, 2, convp_launch_t<1, 4, 2, 1, false, 2>},
+    {1, 4, 4, 1, 0, 2, convp_launch_t<1, 4, 4, 1, false, 2>}, {2, 2, 3, 1, 0, 2, convp_launch_t<2, 2, 3, 1, false, 2>},
+    {2, 2, 2, 1, 0, 2, convp_launch_t<2, 2, 2, 1, false, 2>}, {1, 4, 2, 2, 0, 2, convp_launch_t<1, 4, 2, 2, false, 2>},
+    {2, 2, 2, 2, 0, 2, convp_launch_t<2, 2, 2, 2, false, 2>}, {4, 1, 3, 1, 0, 2, convp_launch_t<4, 1, 3, 1, false, 2>},
+    {4, 1, 2, 1, 0, 2, convp_launch_t<4, 1, 2, 1, false, 2>}};
+  return t;
+}
+
+// Every bf16 plan, whatever its kernel family, then the K slices' sums
+int convp_launch(const ConvPlan& pl, hipStream_t s) {
+  const ConvP& p = pl.p;
+  const int rc = pl.launch(pl, s);
   if (rc != DFL_OK || p.splits <= 1) return rc;
   int tx = 1;
   while (tx * 2 <= p.a.Ntot && tx * 2 <= FIN_TX) tx *= 2;
@@ -1386,65 +870,4 @@ int convp_launch(const ConvP& p, hipStream_t s) {
   return check_launch("dfl_conv2d (bf16, split-K finish)");
 }
 
-
-// Candidates of the geometry search for one layer (tuners: tools/tune_convp.py): up to `max` rows of 5 integers
-// (tile configuration, images per patch, patch height, patch width, K slices); returns the number of candidates.
-int convp_candidates(const dfl_conv_args* a, int32_t* out, int max) {
-  ConvP p;
-  const int saved_tile = t_force.tile;
-  t_force.tile = -1;
-  const int rc = convp_plan(a, &p, 0);               // validates the arguments and fills the layer constants
-  t_force.tile = saved_tile;
-  if (rc != DFL_OK) return -1;
-  ConvP base = p;
-  int n = 0;
-  for_each_candidate(*a, base, 0, true, [&](int ti, const ConvP& q, double) {
-    if (n < max) {
-      int32_t* o = out + 5 * n;
-      o[0] = ti; o[1] = q.IPP; o[2] = q.PH; o[3] = q.PW; o[4] = q.splits;
-    }
-    ++n;
-  });
-  return n;
-}
-
-int convp_force(const int32_t* g) {
-  if (g == nullptr) t_force.tile = -1;
-  else t_force = ConvGeom{g[0], g[1], g[2], g[3], g[4]};
-  return DFL_OK;
-}
-
-int convp_tune_add(const int32_t* key, const int32_t* g) {
-  memo_clear();
-  std::lock_guard<std::mutex> lock(g_tune_mu);
-  if (key == nullptr) {
-    g_tune.clear();
-    return DFL_OK;
-  }
-  TuneEntry e;
-  for (int i = 0; i < 10; ++i) e.key[i] = key[i];
-  e.g = ConvGeom{g[0], g[1], g[2], g[3], g[4]};
-  for (TuneEntry& o : g_tune)
-    if (memcmp(o.key, e.key, sizeof(e.key)) == 0) {
-      o = e;
-      return DFL_OK;
-    }
-  g_tune.push_back(e);
-  return DFL_OK;
-}
-
 }  // namespace dfl
-
-// ---- C ABI of the geometry search (include/dfl_hip.h)
-extern "C" int dfl_conv_candidates(const dfl_conv_args* a, int32_t* out, int32_t max_rows) {
-  DFL_REQUIRE(a != nullptr && (out != nullptr || max_rows <= 0) && a->x_bf16, "dfl_conv_candidates: bf16 convolution arguments and an output table are required");
-  const int n = dfl::convp_candidates(a, out, max_rows);
-  return n < 0 ? (int)DFL_ERR_INVALID_ARG : n;
-}
-
-extern "C" int dfl_conv_force_geometry(const int32_t* geom) { return dfl::convp_force(geom); }
-
-extern "C" int dfl_conv_tune_add(const int32_t* key, const int32_t* geom) {
-  DFL_REQUIRE(key == nullptr || geom != nullptr, "dfl_conv_tune_add: a key needs a geometry");
-  return dfl::convp_tune_add(key, geom);
-}

@@ -519,13 +519,9 @@ __global__ void __launch_bounds__(64 * WM * WN * KS, 2) convq_kernel(const ConvP
   }
 }
 
-struct QCfg { int WM, WN, KS; };
-// tile configuration CONVQ_TILE + index (csrc/convp_bf16.hip kTiles lists the same triples)
-constexpr QCfg kQ[] = {{1, 4, 1}, {1, 4, 2}, {2, 4, 1}, {2, 2, 1}, {4, 2, 1}, {2, 2, 2}, {4, 1, 1}, {8, 1, 1}, {4, 1, 2}};
-constexpr int kNumQ = (int)(sizeof(kQ) / sizeof(kQ[0]));
-
-size_t q_tab_off(int ck, int mode, int blk_per_slice, int pers) {
-  const QCfg c = kQ[mode];
+// LDS of a configuration: its image(s), the epilogue's pass image and statistics scratch, then the tables from tab_off
+static size_t q_tab_off(int ck, int layout, int blk_per_slice, int pers) {
+  const QLayout c = convq_layouts()[layout];
   if (pers != 0) return 2 * (size_t)q_buf_bytes(ck, c.WM, c.WN, c.KS, 1);
   const int NT = 64 * c.WM * c.WN * c.KS, BN = 32 * c.WN, EPP = c.WN == 4 ? 1 : 3;
   size_t lds = (size_t)(blk_per_slice > 1 ? 2 : 1) * (8 * c.WM + 2) * q_row_pitch(ck);
@@ -540,19 +536,16 @@ size_t q_tab_off(int ck, int mode, int blk_per_slice, int pers) {
 constexpr bool q_pers_ok(int ck, int nt, int x_mode, int pers) { return pers == 0 || !(ck == 128 && nt == 256 && x_mode != 0); }
 
 template <int CK, int WM, int WN, int KS, int PERS>
-int convq_launch_t(const ConvP& p, int mode, hipStream_t s) {
+int convq_launch_t(const ConvPlan& pl, hipStream_t s) {
   constexpr int NT = 64 * WM * WN * KS;
-  ConvP pl = p;
-  pl.tab_off = (int)q_tab_off(CK, mode, p.blk_per_slice, PERS);
-  const size_t lds = convq_lds_bytes(CK, mode, p.blk_per_slice, PERS);
-  DFL_REQUIRE(lds <= 160 * 1024, "dfl_conv2d (bf16, unrolled 3x3): %zu bytes of LDS", lds);
+  const ConvP& p = pl.p;
   const bool aff = p.a.in_scale != nullptr || p.a.in_tot != nullptr;
   dim3 grid((unsigned)p.grid);
 #define DFL_CQ_LAUNCH(AFF_)                                                                                                   \
   {                                                                                                                             \
     auto k = convq_kernel<CK, WM, WN, KS, AFF_, PERS>;                                                                          \
-    DFL_LDS_OPT_IN(k, 160 * 1024, "dfl_conv2d (bf16, unrolled 3x3)") \
-    hipLaunchKernelGGL(k, grid, dim3(NT), lds, s, pl);                                                                          \
+    DFL_LDS_OPT_IN(k, kLdsOptIn, "dfl_conv2d (bf16, unrolled 3x3)")                                                            \
+    hipLaunchKernelGGL(k, grid, dim3(NT), pl.lds, s, p);                                                                        \
   }
   if (p.a.x_mode != 0) {
     if constexpr (q_pers_ok(CK, NT, 1, PERS) && PERS != 2) DFL_CQ_LAUNCH(2)
@@ -570,66 +563,63 @@ constexpr bool q_inst(int ck, int wm, int wn, int ks) {
 }
 
 template <int CK, int WM, int WN, int KS>
-int convq_launch_p(const ConvP& p, int mode, int pers, hipStream_t s) {
-  if (pers == 0) return convq_launch_t<CK, WM, WN, KS, 0>(p, mode, s);
+int convq_launch_p(const ConvPlan& pl, hipStream_t s) {
+  const ConvP& p = pl.p;
+  if (pl.pers == 0) return convq_launch_t<CK, WM, WN, KS, 0>(pl, s);
   // persistent: patches of one channel block keep the next patch's loads in flight across the epilogue, longer ones stage it in their last block
   // (128 resident channels are 72 k-steps: long enough for the chunked staging, and the whole image in registers would spill)
   // ... as would the two-tensor operand's)
   if constexpr (CK <= 64) {
-    if (p.blk_per_slice == 1 && p.a.x_mode == 0) return convq_launch_t<CK, WM, WN, KS, 2>(p, mode, s);
+    if (p.blk_per_slice == 1 && p.a.x_mode == 0) return convq_launch_t<CK, WM, WN, KS, 2>(pl, s);
   }
-  return convq_launch_t<CK, WM, WN, KS, 1>(p, mode, s);
+  return convq_launch_t<CK, WM, WN, KS, 1>(pl, s);
 }
 
 template <int WM, int WN, int KS>
-int convq_launch_ck(const ConvP& p, int mode, int pers, hipStream_t s) {
-  if (p.CK == 128) {
-    if constexpr (q_inst(128, WM, WN, KS)) return convq_launch_p<128, WM, WN, KS>(p, mode, pers, s);
-  } else if (p.CK == 64) {
-    if constexpr (q_inst(64, WM, WN, KS)) return convq_launch_p<64, WM, WN, KS>(p, mode, pers, s);
-  } else if (p.CK == 32) {
-    if constexpr (q_inst(32, WM, WN, KS)) return convq_launch_p<32, WM, WN, KS>(p, mode, pers, s);
+int convq_launch_ck(const ConvPlan& pl, hipStream_t s) {
+  if (pl.p.CK == 128) {
+    if constexpr (q_inst(128, WM, WN, KS)) return convq_launch_p<128, WM, WN, KS>(pl, s);
+  } else if (pl.p.CK == 64) {
+    if constexpr (q_inst(64, WM, WN, KS)) return convq_launch_p<64, WM, WN, KS>(pl, s);
+  } else if (pl.p.CK == 32) {
+    if constexpr (q_inst(32, WM, WN, KS)) return convq_launch_p<32, WM, WN, KS>(pl, s);
   }
-  set_error("dfl_conv2d (bf16, unrolled 3x3): no instantiation for %d resident channels in configuration %d", p.CK, mode);
+  set_error("dfl_conv2d (bf16, unrolled 3x3): no instantiation for %d resident channels in configuration %d", pl.p.CK, pl.p.tile);
   return DFL_ERR_INVALID_ARG;
 }
 
 }  // namespace
 
-// The layer shapes this form takes (the caller has validated the argument block as convp_plan_search does)
+// Wave layouts (the planner's configurations 40 ... 48, persistent 49 ... 57): WM x WN x KS waves
+const QLayout* convq_layouts() {
+  static const QLayout t[kNumQ] = {{1, 4, 1, convq_launch_ck<1, 4, 1>}, {1, 4, 2, convq_launch_ck<1, 4, 2>}, {2, 4, 1, convq_launch_ck<2, 4, 1>},
+                                   {2, 2, 1, convq_launch_ck<2, 2, 1>}, {4, 2, 1, convq_launch_ck<4, 2, 1>}, {2, 2, 2, convq_launch_ck<2, 2, 2>},
+                                   {4, 1, 1, convq_launch_ck<4, 1, 1>}, {8, 1, 1, convq_launch_ck<8, 1, 1>}, {4, 1, 2, convq_launch_ck<4, 1, 2>}};
+  return t;
+}
+
+// The layer shapes this form takes (the caller has validated the argument block as convp_validate of conv_plan.hip does)
 bool convq_shape_ok(const dfl_conv_args& a) {
   return a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.scatter2x2 == 0 && a.Cin % 32 == 0 && a.Ntot % 8 == 0 &&
          a.Hout == a.Hin && a.Wout == a.Win && a.out_scale == nullptr;
 }
 
-// Resident channels a configuration is instantiated for (q_inst)
-bool convq_ck_ok(int mode, int ck) {
-  if (mode < 0 || mode >= kNumQ || (ck != 32 && ck != 64 && ck != 128)) return false;
-  const QCfg c = kQ[mode];
+// Resident channels a layout is instantiated for (q_inst)
+bool convq_ck_ok(int layout, int ck) {
+  if (layout < 0 || layout >= kNumQ || (ck != 32 && ck != 64 && ck != 128)) return false;
+  const QLayout c = convq_layouts()[layout];
   return q_inst(ck, c.WM, c.WN, c.KS);
 }
 
-size_t convq_lds_bytes(int ck, int mode, int blk_per_slice, int pers) {
-  return q_tab_off(ck, mode, blk_per_slice, pers) + (size_t)(3 * 32 * kQ[mode].WN + 3 * blk_per_slice * ck) * sizeof(float);
+size_t convq_lds_bytes(int ck, int layout, int blk_per_slice, int pers, int* tab_off) {
+  const size_t off = q_tab_off(ck, layout, blk_per_slice, pers);
+  if (tab_off != nullptr) *tab_off = (int)off;
+  return off + (size_t)(3 * 32 * convq_layouts()[layout].WN + 3 * blk_per_slice * ck) * sizeof(float);
 }
 
-bool convq_pers_ok(int mode, int ck, int x_mode) { return q_pers_ok(ck, convq_threads(mode), x_mode, 1); }
-
-int convq_threads(int mode) { return 64 * kQ[mode].WM * kQ[mode].WN * kQ[mode].KS; }
-
-int convq_launch(const ConvP& p, int mode, int pers, hipStream_t s) {
-  DFL_REQUIRE(convq_ck_ok(mode, p.CK), "dfl_conv2d (bf16, unrolled 3x3): resident channel block %d, configuration %d", p.CK, mode);
-  switch (mode) {
-    case 0: return convq_launch_ck<1, 4, 1>(p, mode, pers, s);
-    case 1: return convq_launch_ck<1, 4, 2>(p, mode, pers, s);
-    case 2: return convq_launch_ck<2, 4, 1>(p, mode, pers, s);
-    case 3: return convq_launch_ck<2, 2, 1>(p, mode, pers, s);
-    case 4: return convq_launch_ck<4, 2, 1>(p, mode, pers, s);
-    case 5: return convq_launch_ck<2, 2, 2>(p, mode, pers, s);
-    case 6: return convq_launch_ck<4, 1, 1>(p, mode, pers, s);
-    case 7: return convq_launch_ck<8, 1, 1>(p, mode, pers, s);
-    default: return convq_launch_ck<4, 1, 2>(p, mode, pers, s);
-  }
+bool convq_pers_ok(int layout, int ck, int x_mode) {
+  const QLayout c = convq_layouts()[layout];
+  return q_pers_ok(ck, 64 * c.WM * c.WN * c.KS, x_mode, 1);
 }
 
 }  // namespace dfl

@@ -404,17 +404,9 @@ __global__ void __launch_bounds__(64 * SWAVES, SWAVES == 8 ? 1 : 2) convs_kernel
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 
-static bool convs_switch() {
-  static const bool on = [] {
-    const char* e = getenv("DFL_CONVS");               // 0: the latency form is never taken (A/B against the patch kernels)
-    return e == nullptr || atoi(e) != 0;
-  }();
-  return on;
-}
-
-// Can these arguments take the latency form?  (the caller has validated them as convp_plan_search does)
+// Can these arguments take the latency form?  (the caller has validated them as convp_validate of conv_plan.hip does)
 bool convs_eligible(const dfl_conv_args& a, const ConvP& p) {
-  if (!a.latency_form || !convs_switch()) return false;
+  if (!a.latency_form || !convs_enabled()) return false;
   if (a.x_mode != 0 || a.x_out != nullptr || a.stat_partials != nullptr || a.stat_totals != nullptr || a.stat_other != nullptr) return false;
   if (a.in_tot != nullptr || a.add_tot != nullptr) return false;
   if (a.out_scale != nullptr && a.accumulate) return false;
@@ -468,9 +460,10 @@ void convs_plan(const dfl_conv_args& a, ConvP* p, int force_splits) {
   p->lds_bytes = (W * 16 * 64 + W * SCONST_PER_WAVE + 2 * a.Cin) * 4;
 }
 
-int convs_launch(const ConvP& p, hipStream_t s) {
+int convs_launch(const ConvPlan& pl, hipStream_t s) {
+  const ConvP& p = pl.p;
   dim3 grid((unsigned)p.grid, (unsigned)p.splits);
-  const size_t lds = (size_t)p.lds_bytes;
+  const size_t lds = pl.lds;
   ConvPair none;
   memset(&none, 0, sizeof(none));
   const int W = convs_waves(p.s_ksplit_shift);
@@ -506,20 +499,15 @@ static bool pair_ok(const dfl_conv_args* a, const dfl_conv_args* b, const ConvP&
   return true;
 }
 
-int convs_pair_ok(const dfl_conv_args* a, const dfl_conv_args* b) {
-  if (a == nullptr || b == nullptr || !a->x_bf16 || !a->latency_form) return 0;
-  ConvP pa;
-  if (convp_plan(a, &pa, a->splits > 1 ? a->splits : 1) != DFL_OK) return 0;
+int convs_pair_ok(const dfl_conv_args* a, const dfl_conv_args* b, const ConvP& pa) {
   if (!pair_ok(a, b, pa)) return 0;
   return pa.splits > 1 ? 2 : 1;            // 2: K slices -- a->partial holds [2][splits][M][Ntot] floats
 }
 
-// a then b as ONE launch (the caller has checked convs_pair_ok)
-int convs_pair_launch(const dfl_conv_args* a, const dfl_conv_args* b, hipStream_t s) {
-  ConvP p;
-  int rc = convp_plan(a, &p, a->splits > 1 ? a->splits : 1);
-  if (rc != DFL_OK) return rc;
-  DFL_REQUIRE(pair_ok(a, b, p), "dfl_conv2d_pair: these two convolutions do not form a pair");
+// a then b as ONE launch (the caller has checked convs_pair_ok; p = a's plan)
+int convs_pair_launch(const ConvP& p, const dfl_conv_args* b, hipStream_t s) {
+  const dfl_conv_args* a = &p.a;
+  int rc;
   ConvPair q;
   memset(&q, 0, sizeof(q));
   q.x3 = b->x;
@@ -669,7 +657,7 @@ __global__ void __launch_bounds__(256) convs_first_kernel(const dfl_conv_args a,
 }
 
 bool convs_first_ok(const dfl_conv_args* a) {
-  if (!a->latency_form || !convs_switch()) return false;
+  if (!a->latency_form || !convs_enabled()) return false;
   if (a->x_bf16 || a->Cin != 1 || a->KH != 3 || a->KW != 3 || a->stride != 1 || a->w_split != 0 || a->x_split != 0) return false;
   if (a->Ntot % 8 != 0 || a->Ntot > 64 || a->ldy % 8 != 0 || !aligned16(a->y)) return false;
   if (a->add != nullptr || a->accumulate || a->scatter2x2 || a->splits > 1 || a->in_scale != nullptr || a->in_tot != nullptr) return false;

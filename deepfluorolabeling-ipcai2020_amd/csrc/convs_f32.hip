@@ -436,17 +436,9 @@ __global__ void __launch_bounds__(256) convs32_pair_finish_kernel(const ConvS32 
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 
-static bool convs32_switch() {
-  static const bool on = [] {
-    const char* e = getenv("DFL_CONVS");               // 0: the latency form is never taken (A/B against the GEMM kernels)
-    return e == nullptr || atoi(e) != 0;
-  }();
-  return on;
-}
-
-// Validates like dfl::prepare of conv_gemm.hip does for what it uses, and plans; false = not a problem for this form
+// Validates like dfl::conv_prepare of conv_gemm.hip does for what it uses, and plans; false = not a problem for this form
 static bool convs32_plan(const dfl_conv_args* a, ConvS32* p, int force_splits) {
-  if (a == nullptr || !a->latency_form || !convs32_switch() || a->x_bf16 || a->y_bf16) return false;
+  if (a == nullptr || !a->latency_form || !convs_enabled() || a->x_bf16 || a->y_bf16) return false;
   const int mm = math_mode();
   if (mm != 0 && mm != 1) return false;
   if (a->x == nullptr || a->w == nullptr || a->y == nullptr || a->N <= 0 || a->Hin <= 0 || a->Win <= 0 || a->Cin <= 0 || a->Ntot <= 0) return false;
@@ -515,14 +507,9 @@ static bool convs32_plan(const dfl_conv_args* a, ConvS32* p, int force_splits) {
   return true;
 }
 
-bool convs32_eligible(const dfl_conv_args* a) {
+int convs32_splits(const dfl_conv_args* a, int force_splits) {
   ConvS32 p;
-  return convs32_plan(a, &p, a != nullptr && a->splits > 1 ? a->splits : 1);
-}
-
-int convs32_suggest_splits(const dfl_conv_args* a) {
-  ConvS32 p;
-  return convs32_plan(a, &p, 0) ? p.splits : 0;
+  return convs32_plan(a, &p, force_splits) ? p.splits : 0;
 }
 
 template <int MATH, bool PAIR>

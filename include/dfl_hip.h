@@ -174,8 +174,11 @@ int dfl_conv_pair_ok(const dfl_conv_args* a, const dfl_conv_args* b);
 int dfl_conv_grid_m(const dfl_conv_args* a);
 /* Suggested split-K factor for these args (>= 1); the caller sizes `partial` as splits*M*Ntot floats. */
 int dfl_conv_suggest_splits(const dfl_conv_args* a);
+/* dfl_conv_config, dfl_conv_grid_m and dfl_conv_suggest_splits answer for the kernel the block selects (csrc/conv_plan.hip), and
+ * the fields that select it are the shapes, latency_form, add, accumulate, x_mode, x_out, scatter2x2 and splits -- for the latency
+ * form also whether statistics are asked for (stat_partials / stat_totals / stat_other).  Set these before asking. */
 
-/* Geometry search of the bf16 convolution (csrc/convp_bf16.hip).  A geometry is 5 integers: tile configuration (the
+/* Geometry search of the bf16 convolution (csrc/conv_plan.hip).  A geometry is 5 integers: tile configuration (the
  * value dfl_conv_config reports - 16), images per patch, patch height, patch width, K slices.  By default a cost model
  * picks one per layer; a tuning table (measured on the device: tools/tune_convp.py -> dfl_amd/tune/gfx950_convp.txt,
  * loaded when the library is opened) overrides it for the layers it lists.
@@ -1013,8 +1016,8 @@ int dfl_graph_capture(const dfl_op* ops, int32_t n_ops, dfl_stream_t stream, dfl
 int dfl_graph_launch(dfl_graph_t graph, dfl_stream_t stream);
 int dfl_graph_nodes(dfl_graph_t graph);      /* kernel / memset nodes captured (diagnostics), negative = error */
 int dfl_graph_destroy(dfl_graph_t graph);
-/* Tile configuration the launcher picks for these arguments (index into the instantiation tables documented in
- * csrc/conv_gemm.hip / csrc/wgrad_gemm.hip); lets a profile be matched to kernel template names. */
+/* Tile configuration the launcher picks for these arguments (dfl_conv_config: csrc/conv_plan.hip, 16 + the bf16 tile
+ * configurations it lists; dfl_wgrad_config: csrc/wgrad_gemm.hip); lets a profile be matched to kernel template names. */
 int dfl_conv_config(const dfl_conv_args* a);
 int dfl_wgrad_config(const dfl_wgrad_args* a);
 

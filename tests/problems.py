@@ -4,6 +4,7 @@ to rounding noise and commits it under tests/golden/floors/).  Test infrastructu
 
 A problem = (constructor flags, initial state_dict, input, targets).  build(key) is deterministic: seeded generators only.
 """
+import ctypes as C
 import os
 
 import numpy as np
@@ -11,6 +12,7 @@ import torch
 
 from conftest import TINY_CFGS, PAPER_CFGS, PAPER_BATCH, paper_key, load_golden
 from oracle import ref_cpu as R
+from dfl_amd import _native as nat
 
 
 class Problem:
@@ -233,3 +235,18 @@ for _m in ('zeros', 'circular'):
 REGISTRY['upsample__circular__wf5'] = lambda: upsample('circular', wf=5)     # (wide enough for the bf16 storage arithmetic)
 
 FLOOR_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'floors')
+
+
+def conv_candidates(N, Cin, Cout, H, W, K, stride, pad):
+    """Geometry candidates of a bf16 layer (dfl_conv_candidates needs pointers only to be non-null)."""
+    lib = nat.lib()
+    a = nat.ConvArgs()
+    a.x = a.w = a.y = 4096
+    a.x_bf16, a.y_bf16, a.w_split = 1, 1, 2
+    a.N, a.Hin, a.Win, a.Cin, a.ldx = N, H, W, Cin, Cin
+    a.KH, a.KW, a.stride, a.pad = K, K, stride, pad
+    a.Hout, a.Wout = (H + 2 * pad - K) // stride + 1, (W + 2 * pad - K) // stride + 1
+    a.Ntot = a.ldy = Cout
+    out = (C.c_int32 * (5 * 4096))()
+    n = nat.check(lib.dfl_conv_candidates(C.addressof(a), C.addressof(out), 4096), 'candidates')
+    return [tuple(out[5 * i + j] for j in range(5)) for i in range(min(n, 4096))]

@@ -13,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from dfl_amd import _native as nat
+import problems as PR
 import test_gpu_bf16 as T
 from test_gpu_bf16 import rb, nhwc, pack16, conv_bf16, brb_reference, _mode4  # noqa: F401
 from test_gpu_convq import close_bf16
@@ -40,7 +41,7 @@ _CANDS = {}
 def _valid(N, Cin, Cout, H, W, tile):
     key = (N, Cin, Cout, H, W)
     if key not in _CANDS:
-        _CANDS[key] = set(g for g in T._candidates(N, Cin, Cout, H, W, 3, 1, 1) if g[0] >= 58)
+        _CANDS[key] = set(g for g in PR.conv_candidates(N, Cin, Cout, H, W, 3, 1, 1) if g[0] >= 58)
     return (tile, 1, NPATCH[tile][0], NPATCH[tile][1], 1) in _CANDS[key]
 
 
@@ -62,7 +63,7 @@ def test_candidates_list_the_narrow_form_where_it_applies():
     assert all(_valid(2, 64, 64, 40, 25, t) for t in (58, 60, 62, 63)) and not _valid(2, 64, 64, 40, 25, 59) and not _valid(2, 64, 64, 40, 25, 61)   # (64 columns: at most four rows per wave)
     assert not any(_valid(2, 64, 128, 24, 24, t) for t in TILES)               # 32 or 64 output columns
     assert not any(_valid(2, 16, 32, 24, 24, t) for t in TILES)                # channel blocks of 32
-    assert not any(g[0] >= 58 for g in T._candidates(2, 64, 64, 16, 16, 1, 1, 0))   # 3x3 / stride 1 / pad 1 only
+    assert not any(g[0] >= 58 for g in PR.conv_candidates(2, 64, 64, 16, 16, 1, 1, 0))   # 3x3 / stride 1 / pad 1 only
 
 
 def test_the_two_tensor_operand_of_a_wide_layer_stays_with_the_patch_kernel():

@@ -12,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 from dfl_amd import _native as nat
+import problems as PR
 import test_gpu_bf16 as T
 from test_gpu_bf16 import rb, nhwc, pack16, conv_bf16, brb_reference, _mode4  # noqa: F401
 
@@ -52,7 +53,7 @@ def _valid(N, Cin, Cout, H, W, tile, splits):
     """Is (tile, splits) among the layer's candidates?  (The candidate list of a layer is asked for once: a few thousand geometries.)"""
     key = (N, Cin, Cout, H, W)
     if key not in _CANDS:
-        _CANDS[key] = set(g for g in T._candidates(N, Cin, Cout, H, W, 3, 1, 1) if g[0] >= 40)
+        _CANDS[key] = set(g for g in PR.conv_candidates(N, Cin, Cout, H, W, 3, 1, 1) if g[0] >= 40)
     return (tile, 1, 8 * QCFG[tile][0], 12, splits) in _CANDS[key]
 
 
@@ -115,7 +116,7 @@ def test_candidates_list_the_unrolled_form_where_it_applies():
     assert all(_valid(2, 32, 32, 24, 24, t, 1) for t in (46, 47)) and not any(_valid(2, 32, 32, 24, 24, t, 1) for t in (40, 41, 42, 43, 44, 45))
     assert _valid(2, 64, 64, 24, 24, 43, 1) and _valid(2, 64, 64, 24, 24, 44, 1) and not _valid(2, 64, 64, 24, 24, 46, 1)   # (a 64-column layer takes 64-column tiles)
     assert not any(_valid(2, 16, 32, 24, 24, t, 1) for t in TILES)             # needs 32 resident channels
-    assert not any(g[0] >= 39 for g in T._candidates(2, 64, 128, 16, 16, 1, 1, 0))   # 3x3 / stride 1 / pad 1 only
+    assert not any(g[0] >= 39 for g in PR.conv_candidates(2, 64, 128, 16, 16, 1, 1, 0))   # 3x3 / stride 1 / pad 1 only
 
 
 @pytest.mark.parametrize('tile', TILES)

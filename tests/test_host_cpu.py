@@ -14,6 +14,7 @@ import dfl_amd
 from conftest import TINY_CFGS, PAPER_CFGS, load_golden, ROOT
 from dfl_amd import _native as nat
 from dfl_amd.plan import UNetPlan
+import problems as PR
 
 
 def test_library_exports_every_declared_symbol():
@@ -40,6 +41,63 @@ def test_argument_validation_reports_errors_without_a_gpu():
     assert L.dfl_conv_grid_m(C.addressof(a)) == -1 and b'do not match' in L.dfl_last_error()
     assert L.dfl_rowblock_count(5000, 32) == 20
     assert L.dfl_head_scratch_ld(32) % 4 == 0
+
+
+def test_convp_tuning_table_entry_is_used_and_validated():
+    lib = nat.lib()
+    case = (2, 64, 128, 16, 16, 3, 1, 1)
+    a = nat.ConvArgs()
+    a.x = a.w = a.y = 4096
+    a.x_bf16, a.y_bf16, a.w_split = 1, 1, 2
+    a.N, a.Hin, a.Win, a.Cin, a.ldx = 2, 16, 16, 64, 64
+    a.KH = a.KW = 3
+    a.stride, a.pad, a.Hout, a.Wout, a.Ntot, a.ldy = 1, 1, 16, 16, 128, 128
+    model = lib.dfl_conv_config(C.addressof(a))
+    other = [gm for gm in PR.conv_candidates(*case) if gm[0] + 16 != model and gm[4] == 1][0]
+    key = (C.c_int32 * 10)(2, 16, 16, 64, 128, 3, 3, 1, 1, 0)
+    gv = (C.c_int32 * 5)(*other)
+    try:
+        nat.check(lib.dfl_conv_tune_add(C.addressof(key), C.addressof(gv)), 'tune_add')
+        assert lib.dfl_conv_config(C.addressof(a)) == other[0] + 16
+        bad = (C.c_int32 * 5)(other[0], 1, 64, 64, 1)            # a patch larger than the tile: ignored, the model decides
+        nat.check(lib.dfl_conv_tune_add(C.addressof(key), C.addressof(bad)), 'tune_add')
+        assert lib.dfl_conv_config(C.addressof(a)) == model
+    finally:
+        # leave the table as the library loaded it
+        lib.dfl_conv_tune_add(None, None)
+        nat.load_tuning(lib, nat.TUNE_PATH)
+
+
+def test_narrow_form_refuses_outputs_beyond_32_bit_offsets():
+    """The narrow 3x3 form (tiles 58 ... 65) addresses y with 32-bit byte offsets: a layer whose y spans 2^32 bytes or more
+    (here through a wide pixel stride, every other bound holding) is not a geometry of that form, forced or listed."""
+    lib = nat.lib()
+
+    def layer(ldy):
+        a = nat.ConvArgs()
+        a.x = a.w = a.y = 4096
+        a.x_bf16, a.y_bf16, a.w_split = 1, 1, 2
+        a.N, a.Hin, a.Win, a.Cin, a.ldx = 1, 1456, 1456, 32, 32
+        a.KH = a.KW = 3
+        a.stride, a.pad, a.Hout, a.Wout, a.Ntot, a.ldy = 1, 1, 1456, 1456, 32, ldy
+        return a
+
+    geom = (C.c_int32 * 5)(58, 1, 8, 64, 1)
+    out = (C.c_int32 * (5 * 4096))()
+    for ldy, fits in ((32, True), (1024, False)):        # 1456^2 pixels x 1024 x 2 bytes >= 2^32
+        a = layer(ldy)
+        n = nat.check(lib.dfl_conv_candidates(C.addressof(a), C.addressof(out), 4096), 'candidates')
+        narrow = [out[5 * i] for i in range(n) if out[5 * i] >= 58]
+        assert bool(narrow) == fits, (ldy, narrow)
+        nat.check(lib.dfl_conv_force_geometry(C.addressof(geom)), 'force')
+        try:
+            cfg = lib.dfl_conv_config(C.addressof(a))
+        finally:
+            lib.dfl_conv_force_geometry(None)
+        if fits:
+            assert cfg == 16 + 58
+        else:
+            assert cfg < 0 and b'forced geometry' in lib.dfl_last_error()
 
 
 def test_cpu_tensors_are_refused():
