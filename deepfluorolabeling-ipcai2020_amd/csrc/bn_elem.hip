@@ -1,30 +1,28 @@
-// Streaming (HBM-bound) kernels around the convolutions: BatchNorm finalize / backward, per-channel reductions,
-// affine copy, 2x2 max-pool, weight re-layout, SGD.  All operate on NHWC rows [M][C] with float4 (= 4 channels)
-// accesses when C, ld and the pointers allow it, 4-byte accesses otherwise.
+// Streaming (HBM-bound) kernels around the convolutions, in the order of this file: per-channel statistics (colstats),
+// BatchNorm finalize (forward, "live", eval, backward), BatchNorm + ReLU backward, partial-sum reductions (one and batched),
+// affine copy, 2x2 max-pool, weight re-layout (pack), and the three optimizers (SGD, Adam, RMSprop; alone and fused with the
+// re-layout).  The tensor kernels work on NHWC rows [M][C] and are written once over the channel unit of chan_unit.h:
+// 8 bf16 channels, or 4 fp32 channels (float4) when C, ld and the pointers allow it, 1 fp32 channel otherwise.
 // Reference behaviour: nn.BatchNorm2d (train_test_code/unet.py:215,222), nn.ReLU (:213,220), F.max_pool2d (:169),
 // torch.optim.SGD (train.py:333-334), torch.optim.Adam / RMSprop (train.py:331-352).  Contracts: include/dfl_hip.h.
-#include "common.h"
+#include "chan_unit.h"
 
 namespace dfl {
 
 // ------------------------------------------------------------------------------------------------ helpers
+// A workgroup of the row kernels (colstats, bn_relu_bwd): UX threads along the row x RY = 256 / UX row lanes; blockIdx.x = a
+// block of rows, blockIdx.y = a block of UX units.
 struct RowGeom {
-  int vec;    // 1: float4 units
-  int units;  // units per row (C/4 or C)
   int UX;     // threads along the row (power of two <= 256)
-  int RY;     // rows per pass = 256 / UX
   int gy;     // grid.y = ceil(units / UX)
 };
 
-static RowGeom row_geom(int C, bool vec_ok) {
+static RowGeom row_geom(int C, int W) {
+  const int units = C / W;
   RowGeom g;
-  g.vec = (vec_ok && C % 4 == 0) ? 1 : 0;
-  g.units = g.vec ? C / 4 : C;
-  int ux = 1;
-  while (ux * 2 <= g.units && ux * 2 <= 256) ux *= 2;
-  g.UX = ux;
-  g.RY = 256 / ux;
-  g.gy = (int)ceil_div(g.units, ux);
+  g.UX = 1;
+  while (g.UX * 2 <= units && g.UX * 2 <= 256) g.UX *= 2;
+  g.gy = (int)ceil_div(units, g.UX);
   return g;
 }
 
@@ -36,65 +34,71 @@ static int rowblocks(int64_t M, int C) {
   return (int)nb;
 }
 
-__device__ __forceinline__ float4 ld4(const float* p, bool vec, int c, int C) {
-  if (vec) return *reinterpret_cast<const float4*>(p);
-  (void)c; (void)C;
-  return make_float4(p[0], 0.f, 0.f, 0.f);
+// this thread's place in such a workgroup: unit ux (first channel c, cok: inside the row), rows r0 + uy, + RY, ... < r1
+struct RowLane {
+  int ux, uy, RY, c;
+  bool cok;
+  int64_t r0, r1;
+};
+
+template <int W>
+__device__ __forceinline__ RowLane row_lane(int UX, int rows_per_block, int64_t M, int C) {
+  RowLane t;
+  t.RY = 256 / UX;
+  t.ux = threadIdx.x % UX;
+  t.uy = threadIdx.x / UX;
+  t.c = (blockIdx.y * UX + t.ux) * W;
+  t.cok = t.c < C;
+  t.r0 = (int64_t)blockIdx.x * rows_per_block;
+  t.r1 = t.r0 + rows_per_block;
+  if (t.r1 > M) t.r1 = M;
+  return t;
+}
+
+// NS running sums per channel of every thread -> the workgroup's sums, out[n * C + j] for the unit's channel j: the threads
+// of row lane 0 add the RY lanes up in lane order.  One barrier; every thread of the workgroup must call it.
+template <int NS, int W>
+__device__ __forceinline__ void block_colsum(const float (&s)[NS][W], const RowLane& t, int UX, float* out, int C) {
+  __shared__ float red[NS][256][W];
+#pragma unroll
+  for (int n = 0; n < NS; ++n)
+#pragma unroll
+    for (int j = 0; j < W; ++j) red[n][threadIdx.x][j] = s[n][j];
+  __syncthreads();
+  if (t.uy == 0 && t.cok) {
+#pragma unroll
+    for (int n = 0; n < NS; ++n)
+#pragma unroll
+      for (int j = 0; j < W; ++j) {
+        float sum = 0.f;
+        for (int y = 0; y < t.RY; ++y) sum += red[n][y * UX + t.ux][j];
+        out[(int64_t)n * C + j] = sum;
+      }
+  }
 }
 
 // ------------------------------------------------------------------------------------------------ colstats
-// partials[blk][0][c] = sum a, partials[blk][1][c] = sum a*b over the block's rows.
-template <int VEC>
-__global__ void __launch_bounds__(256) colstats_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                      float* __restrict__ partials, int64_t M, int C, int lda, int ldb,
-                                                      int UX, int rows_per_block) {
-  __shared__ float red[2][256][VEC ? 4 : 1];
-  const int RY = 256 / UX;
-  const int ux = threadIdx.x % UX, uy = threadIdx.x / UX;
-  const int unit = blockIdx.y * UX + ux;
-  const int c = VEC ? unit * 4 : unit;
-  const bool cok = c < C;
-  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-  int64_t r1 = r0 + rows_per_block;
-  if (r1 > M) r1 = M;
-  float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
-  if (cok) {
-    for (int64_t r = r0 + uy; r < r1; r += RY) {
-      if constexpr (VEC) {
-        const float4 va = *reinterpret_cast<const float4*>(a + r * lda + c);
-        const float4 vb = b ? *reinterpret_cast<const float4*>(b + r * ldb + c) : va;
-        s1[0] += va.x; s1[1] += va.y; s1[2] += va.z; s1[3] += va.w;
-        s2[0] = fmaf(va.x, vb.x, s2[0]); s2[1] = fmaf(va.y, vb.y, s2[1]);
-        s2[2] = fmaf(va.z, vb.z, s2[2]); s2[3] = fmaf(va.w, vb.w, s2[3]);
-      } else {
-        const float va = a[r * lda + c];
-        const float vb = b ? b[r * ldb + c] : va;
-        s1[0] += va;
-        s2[0] = fmaf(va, vb, s2[0]);
+// partials[blk][0][c] = sum a, partials[blk][1][c] = sum a*b over the block's rows (b == NULL: a*a).
+template <int W, bool BF>
+__global__ void __launch_bounds__(256) colstats_kernel(const dfl_colstats_args a, int UX, int rows_per_block) {
+  using U = ChanUnit<W, BF>;
+  const RowLane t = row_lane<W>(UX, rows_per_block, a.M, a.C);
+  float s[2][W];
+#pragma unroll
+  for (int j = 0; j < W; ++j) s[0][j] = s[1][j] = 0.f;
+  if (t.cok) {
+    for (int64_t r = t.r0 + t.uy; r < t.r1; r += t.RY) {
+      float va[W], vb[W];
+      U::load(a.a, r * a.lda + t.c, va);
+      if (a.b != nullptr) U::load(a.b, r * a.ldb + t.c, vb);
+#pragma unroll
+      for (int j = 0; j < W; ++j) {
+        s[0][j] += va[j];
+        s[1][j] = fmaf(va[j], a.b != nullptr ? vb[j] : va[j], s[1][j]);
       }
     }
   }
-  constexpr int W = VEC ? 4 : 1;
-#pragma unroll
-  for (int j = 0; j < W; ++j) {
-    red[0][threadIdx.x][j] = s1[j];
-    red[1][threadIdx.x][j] = s2[j];
-  }
-  __syncthreads();
-  if (uy == 0 && cok) {
-#pragma unroll
-    for (int j = 0; j < W; ++j) {
-      float t1 = 0.f, t2 = 0.f;
-      for (int y = 0; y < RY; ++y) {
-        t1 += red[0][y * UX + ux][j];
-        t2 += red[1][y * UX + ux][j];
-      }
-      if (c + j < C) {
-        partials[((int64_t)blockIdx.x * 2 + 0) * C + c + j] = t1;
-        partials[((int64_t)blockIdx.x * 2 + 1) * C + c + j] = t2;
-      }
-    }
-  }
+  block_colsum<2, W>(s, t, UX, a.partials + (int64_t)blockIdx.x * 2 * a.C + t.c, a.C);
 }
 
 // ------------------------------------------------------------------------------------------------ BN finalize
@@ -238,68 +242,63 @@ __global__ void __launch_bounds__(256) bn_bwd_finalize_kernel(const dfl_bn_bwd_f
   }
 }
 
-// dpre = [r > 0] * (A*dy + B*r + C); partials[blk][c] = column sums of dpre.
-template <int VEC>
+// dpre = [r > 0] * (A*dy + B*r + C); partials[blk][c] = column sums of dpre, of the values as stored.
+template <int W, bool BF>
 __global__ void __launch_bounds__(256) bn_relu_bwd_kernel(const dfl_bn_relu_bwd_args a, int UX, int rows_per_block) {
-  __shared__ float red[256][VEC ? 4 : 1];
-  const int RY = 256 / UX;
-  const int ux = threadIdx.x % UX, uy = threadIdx.x / UX;
-  const int unit = blockIdx.y * UX + ux;
-  const int c = VEC ? unit * 4 : unit;
-  const int C = a.C;
-  const bool cok = c < C;
-  constexpr int W = VEC ? 4 : 1;
-  float cA[W], cB[W], cC[W], s[W];
+  using U = ChanUnit<W, BF>;
+  const RowLane t = row_lane<W>(UX, rows_per_block, a.M, a.C);
+  const int C = a.C, c = t.c, RY = t.RY;
+  float cA[W], cB[W], cC[W], s[1][W];
 #pragma unroll
   for (int j = 0; j < W; ++j) {
-    cA[j] = 1.f; cB[j] = 0.f; cC[j] = 0.f; s[j] = 0.f;
-    if (a.coef != nullptr && cok && c + j < C) {
+    cA[j] = 1.f; cB[j] = 0.f; cC[j] = 0.f; s[0][j] = 0.f;
+    if (a.coef != nullptr && t.cok) {
       cA[j] = a.coef[c + j];
       cB[j] = a.coef[C + c + j];
       cC[j] = a.coef[2 * C + c + j];
     }
   }
-  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-  int64_t r1 = r0 + rows_per_block;
-  if (r1 > a.M) r1 = a.M;
-  if (cok) {
-    for (int64_t r = r0 + uy; r < r1; r += RY) {
-      if constexpr (VEC) {
-        const float4 dy = *reinterpret_cast<const float4*>(a.dy + r * a.lddy + c);
-        const float4 rv = *reinterpret_cast<const float4*>(a.r + r * a.ldr + c);
-        float4 o;
-        o.x = rv.x > 0.f ? fmaf(cA[0], dy.x, fmaf(cB[0], rv.x, cC[0])) : 0.f;
-        o.y = rv.y > 0.f ? fmaf(cA[1], dy.y, fmaf(cB[1], rv.y, cC[1])) : 0.f;
-        o.z = rv.z > 0.f ? fmaf(cA[2], dy.z, fmaf(cB[2], rv.z, cC[2])) : 0.f;
-        o.w = rv.w > 0.f ? fmaf(cA[3], dy.w, fmaf(cB[3], rv.w, cC[3])) : 0.f;
-        if (a.split_out) {   // hi4 | lo4 bf16 in the float4's slot (consumers: split-bf16 GEMMs only)
+  if (t.cok) {
+    auto one = [&](const float* dy, const float* rv, int64_t r) {
+      float o[W];
+#pragma unroll
+      for (int j = 0; j < W; ++j) o[j] = rv[j] > 0.f ? fmaf(cA[j], dy[j], fmaf(cB[j], rv[j], cC[j])) : 0.f;
+      if (W == 4 && a.split_out) {
+        // split_out exists for the float4 form only (the launcher refuses it elsewhere): hi4 | lo4 bf16 in the float4's
+        // slot (consumers: split-bf16 GEMMs only); the sums are taken from the fp32 values
+        if constexpr (W == 4) {
           uint2 parts[2];
-          split_bf16<2>(o, parts);
+          split_bf16<2>(make_float4(o[0], o[1], o[2], o[3]), parts);
           *reinterpret_cast<uint4*>(a.dpre + r * a.ldo + c) = make_uint4(parts[0].x, parts[0].y, parts[1].x, parts[1].y);
-        } else {
-          *reinterpret_cast<float4*>(a.dpre + r * a.ldo + c) = o;
         }
-        s[0] += o.x; s[1] += o.y; s[2] += o.z; s[3] += o.w;
       } else {
-        const float dy = a.dy[r * a.lddy + c], rv = a.r[r * a.ldr + c];
-        const float o = rv > 0.f ? fmaf(cA[0], dy, fmaf(cB[0], rv, cC[0])) : 0.f;
-        a.dpre[r * a.ldo + c] = o;
-        s[0] += o;
+        U::store(a.dpre, r * a.ldo + c, o, o);
       }
+#pragma unroll
+      for (int j = 0; j < W; ++j) s[0][j] += o[j];
+    };
+    // rows in flight per thread: four, but two in the float4 form, where four take it past 64 registers (8 -> 5 waves per SIMD;
+    // the bf16 form is at 3 waves with or without them).  The rows are taken in row order whatever R is.
+    constexpr int R = (W == 4) ? 2 : 4;
+    int64_t r = t.r0 + t.uy;
+    for (; r + (R - 1) * RY < t.r1; r += R * RY) {
+      float dy[R][W], rv[R][W];
+#pragma unroll
+      for (int u = 0; u < R; ++u) U::load(a.dy, (r + u * RY) * a.lddy + c, dy[u]);
+#pragma unroll
+      for (int u = 0; u < R; ++u) U::load(a.r, (r + u * RY) * a.ldr + c, rv[u]);
+#pragma unroll
+      for (int u = 0; u < R; ++u) one(dy[u], rv[u], r + u * RY);
+    }
+    for (; r < t.r1; r += RY) {
+      float dy[W], rv[W];
+      U::load(a.dy, r * a.lddy + c, dy);
+      U::load(a.r, r * a.ldr + c, rv);
+      one(dy, rv, r);
     }
   }
   if (a.partials == nullptr) return;
-#pragma unroll
-  for (int j = 0; j < W; ++j) red[threadIdx.x][j] = s[j];
-  __syncthreads();
-  if (uy == 0 && cok) {
-#pragma unroll
-    for (int j = 0; j < W; ++j) {
-      float t = 0.f;
-      for (int y = 0; y < RY; ++y) t += red[y * UX + ux][j];
-      if (c + j < C) a.partials[(int64_t)blockIdx.x * C + c + j] = t;
-    }
-  }
+  block_colsum<1, W>(s, t, UX, a.partials + (int64_t)blockIdx.x * C + c, C);
 }
 
 // out[c] = sum_b partials[b*stride + c] in fp64
@@ -413,69 +412,65 @@ __global__ void __launch_bounds__(RB_T) reduce_batch_kernel(const dfl_reduce_job
 }
 
 // ------------------------------------------------------------------------------------------------ affine copy
-template <int VEC>
+// y window = x window (* scale + shift per channel) (+ y window); a thread per (pixel, unit), grid-stride
+template <int W, bool BF>
 __global__ void __launch_bounds__(256) affine_copy_kernel(const dfl_affine_copy_args a, int64_t total_units, int cq) {
+  using U = ChanUnit<W, BF>;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total_units; i += stride) {
-    const int u = (int)(i % cq);
-    int64_t pix = i / cq;
-    const int xw = (int)(pix % a.W);
-    pix /= a.W;
-    const int yh = (int)(pix % a.H);
-    const int n = (int)(pix / a.H);
-    const int c = VEC ? u * 4 : u;
-    const float* src = a.x + (((int64_t)n * a.xH + a.xoy + yh) * a.xW + a.xox + xw) * a.ldx + c;
-    float* dst = a.y + (((int64_t)n * a.yH + a.yoy + yh) * a.yW + a.yox + xw) * a.ldy + c;
-    if constexpr (VEC) {
-      float4 v = *reinterpret_cast<const float4*>(src);
-      if (a.scale != nullptr) {
-        const float4 sc = *reinterpret_cast<const float4*>(a.scale + c);
-        const float4 sh = *reinterpret_cast<const float4*>(a.shift + c);
-        v.x = fmaf(v.x, sc.x, sh.x); v.y = fmaf(v.y, sc.y, sh.y);
-        v.z = fmaf(v.z, sc.z, sh.z); v.w = fmaf(v.w, sc.w, sh.w);
+    int u, xw, yh, n;
+    unit_coords(i, cq, a.W, a.H, &u, &xw, &yh, &n);
+    const int c = u * W;
+    const int64_t so = (((int64_t)n * a.xH + a.xoy + yh) * a.xW + a.xox + xw) * a.ldx + c;
+    const int64_t dof = (((int64_t)n * a.yH + a.yoy + yh) * a.yW + a.yox + xw) * a.ldy + c;
+    float v[W];
+    U::load(a.x, so, v);
+    if (a.scale != nullptr) {
+      float sc[W], sh[W];
+      if constexpr (W == 4) {   // fp32 scale / shift as one float4 each in the float4 form only: the launcher asks for
+        ChanUnit<4, false>::load(a.scale, c, sc);   // their 16-byte alignment there and nowhere else
+        ChanUnit<4, false>::load(a.shift, c, sh);
+      } else {
+#pragma unroll
+        for (int j = 0; j < W; ++j) { sc[j] = a.scale[c + j]; sh[j] = a.shift[c + j]; }
       }
-      if (a.accumulate) {
-        const float4 o = *reinterpret_cast<const float4*>(dst);
-        v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
-      }
-      *reinterpret_cast<float4*>(dst) = v;
-    } else {
-      float v = *src;
-      if (a.scale != nullptr) v = fmaf(v, a.scale[c], a.shift[c]);
-      if (a.accumulate) v += *dst;
-      *dst = v;
+#pragma unroll
+      for (int j = 0; j < W; ++j) v[j] = fmaf(v[j], sc[j], sh[j]);
     }
+    if (a.accumulate) {
+      float o[W];
+      U::load(a.y, dof, o);
+#pragma unroll
+      for (int j = 0; j < W; ++j) v[j] += o[j];
+    }
+    U::store(a.y, dof, v);
   }
 }
 
 // ------------------------------------------------------------------------------------------------ max pool
-template <int VEC>
+// the four inputs of output pixel (n, oy, ox): element offsets of the first (pixel stride ld, row stride W * ld)
+__device__ __forceinline__ int64_t pool_src(const dfl_pool_args& a, int n, int oy, int ox, int ld) {
+  return (((int64_t)n * a.H + 2 * oy) * a.W + 2 * ox) * ld;
+}
+
+template <int W, bool BF>
 __global__ void __launch_bounds__(256) maxpool_fwd_kernel(const dfl_pool_args a, int64_t total_units, int cq) {
+  using U = ChanUnit<W, BF>;
   const int Ho = a.H / 2, Wo = a.W / 2;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total_units; i += stride) {
-    const int u = (int)(i % cq);
-    int64_t pix = i / cq;
-    const int ox = (int)(pix % Wo);
-    pix /= Wo;
-    const int oy = (int)(pix % Ho);
-    const int n = (int)(pix / Ho);
-    const int c = VEC ? u * 4 : u;
-    const float* s00 = a.x + (((int64_t)n * a.H + 2 * oy) * a.W + 2 * ox) * a.ldx + c;
-    const float* s10 = s00 + (int64_t)a.W * a.ldx;
-    float* dst = a.y + (((int64_t)n * Ho + oy) * Wo + ox) * a.ldy + c;
-    if constexpr (VEC) {
-      const float4 v0 = *reinterpret_cast<const float4*>(s00), v1 = *reinterpret_cast<const float4*>(s00 + a.ldx);
-      const float4 v2 = *reinterpret_cast<const float4*>(s10), v3 = *reinterpret_cast<const float4*>(s10 + a.ldx);
-      float4 m;
-      m.x = fmaxf(fmaxf(v0.x, v1.x), fmaxf(v2.x, v3.x));
-      m.y = fmaxf(fmaxf(v0.y, v1.y), fmaxf(v2.y, v3.y));
-      m.z = fmaxf(fmaxf(v0.z, v1.z), fmaxf(v2.z, v3.z));
-      m.w = fmaxf(fmaxf(v0.w, v1.w), fmaxf(v2.w, v3.w));
-      *reinterpret_cast<float4*>(dst) = m;
-    } else {
-      *dst = fmaxf(fmaxf(s00[0], s00[a.ldx]), fmaxf(s10[0], s10[a.ldx]));
-    }
+    int u, ox, oy, n;
+    unit_coords(i, cq, Wo, Ho, &u, &ox, &oy, &n);
+    const int c = u * W;
+    const int64_t s00 = pool_src(a, n, oy, ox, a.ldx) + c, s10 = s00 + (int64_t)a.W * a.ldx;
+    float v0[W], v1[W], v2[W], v3[W], m[W];
+    U::load(a.x, s00, v0);
+    U::load(a.x, s00 + a.ldx, v1);
+    U::load(a.x, s10, v2);
+    U::load(a.x, s10 + a.ldx, v3);
+#pragma unroll
+    for (int j = 0; j < W; ++j) m[j] = fmaxf(fmaxf(v0[j], v1[j]), fmaxf(v2[j], v3[j]));
+    U::store(a.y, (((int64_t)n * Ho + oy) * Wo + ox) * a.ldy + c, m);
   }
 }
 
@@ -488,253 +483,52 @@ __device__ __forceinline__ int first_max4(float v0, float v1, float v2, float v3
   return k;
 }
 
-template <int VEC>
+// dx += the gradient y at the first maximum of each 2x2 window of x
+template <int W, bool BF>
 __global__ void __launch_bounds__(256) maxpool_bwd_kernel(const dfl_pool_args a, int64_t total_units, int cq) {
+  using U = ChanUnit<W, BF>;
   const int Ho = a.H / 2, Wo = a.W / 2;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total_units; i += stride) {
-    const int u = (int)(i % cq);
-    int64_t pix = i / cq;
-    const int ox = (int)(pix % Wo);
-    pix /= Wo;
-    const int oy = (int)(pix % Ho);
-    const int n = (int)(pix / Ho);
-    const int c = VEC ? u * 4 : u;
-    const int64_t ipix = ((int64_t)n * a.H + 2 * oy) * a.W + 2 * ox;
-    const float* s00 = a.x + ipix * a.ldx + c;
-    const float* s10 = s00 + (int64_t)a.W * a.ldx;
-    float* d00 = a.dx + ipix * a.lddx + c;
-    float* d10 = d00 + (int64_t)a.W * a.lddx;
-    const float* g = a.y + (((int64_t)n * Ho + oy) * Wo + ox) * a.ldy + c;
-    constexpr int W = VEC ? 4 : 1;
+    int u, ox, oy, n;
+    unit_coords(i, cq, Wo, Ho, &u, &ox, &oy, &n);
+    const int c = u * W;
+    const int64_t s00 = pool_src(a, n, oy, ox, a.ldx) + c, s10 = s00 + (int64_t)a.W * a.ldx;
+    const int64_t d00 = pool_src(a, n, oy, ox, a.lddx) + c, d10 = d00 + (int64_t)a.W * a.lddx;
+    float v0[W], v1[W], v2[W], v3[W], g[W];
+    U::load(a.x, s00, v0);
+    U::load(a.x, s00 + a.ldx, v1);
+    U::load(a.x, s10, v2);
+    U::load(a.x, s10 + a.ldx, v3);
+    U::load(a.y, (((int64_t)n * Ho + oy) * Wo + ox) * a.ldy + c, g);
+    if constexpr (BF) {
+      // bf16: a 2-byte read-modify-write per winner would be slow, so all four 16-byte units of dx are rewritten, the
+      // losers with + 0 (which is the identity on every bf16 value but -0.0: hence not the fp32 way below)
+      float e0[W], e1[W], e2[W], e3[W];
+      U::load(a.dx, d00, e0);
+      U::load(a.dx, d00 + a.lddx, e1);
+      U::load(a.dx, d10, e2);
+      U::load(a.dx, d10 + a.lddx, e3);
 #pragma unroll
-    for (int j = 0; j < W; ++j) {
-      const int k = first_max4(s00[j], s00[a.ldx + j], s10[j], s10[a.ldx + j]);
-      float* d = (k == 0) ? d00 + j : (k == 1) ? d00 + a.lddx + j : (k == 2) ? d10 + j : d10 + a.lddx + j;
-      *d += g[j];
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------ bf16 tensors (math mode 4)
-// The same streaming kernels for bf16 activations: units of 8 channels (16 bytes), fp32 arithmetic, one rounding at the
-// store.  Sums are taken from the values as stored.
-typedef unsigned int bu32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void unpack8(const bu32x4 w, float* f) {
-  f[0] = __uint_as_float(w.x << 16); f[1] = __uint_as_float(w.x & 0xffff0000u);
-  f[2] = __uint_as_float(w.y << 16); f[3] = __uint_as_float(w.y & 0xffff0000u);
-  f[4] = __uint_as_float(w.z << 16); f[5] = __uint_as_float(w.z & 0xffff0000u);
-  f[6] = __uint_as_float(w.w << 16); f[7] = __uint_as_float(w.w & 0xffff0000u);
-}
-__device__ __forceinline__ bu32x4 pack8(const float* f) {
-  bu32x4 w;
-  w.x = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_t){f[0], f[1]}, bf16x2_t));
-  w.y = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_t){f[2], f[3]}, bf16x2_t));
-  w.z = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_t){f[4], f[5]}, bf16x2_t));
-  w.w = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_t){f[6], f[7]}, bf16x2_t));
-  return w;
-}
-__device__ __forceinline__ bu32x4 ld8(const float* base, int64_t elem) {
-  return *reinterpret_cast<const bu32x4*>(reinterpret_cast<const unsigned short*>(base) + elem);
-}
-__device__ __forceinline__ void st8(float* base, int64_t elem, bu32x4 w) {
-  *reinterpret_cast<bu32x4*>(reinterpret_cast<unsigned short*>(base) + elem) = w;
-}
-
-static RowGeom row_geom8(int C) {
-  RowGeom g;
-  g.vec = 1;
-  g.units = C / 8;
-  int ux = 1;
-  while (ux * 2 <= g.units && ux * 2 <= 256) ux *= 2;
-  g.UX = ux;
-  g.RY = 256 / ux;
-  g.gy = (int)ceil_div(g.units, ux);
-  return g;
-}
-
-// per-unit partial sums of a workgroup -> partials row (red: [256][8])
-__device__ __forceinline__ void reduce_units8(float (*red)[8], const float* s, int ux, int uy, int UX, int RY, bool cok,
-                                              float* out, int c) {
+      for (int j = 0; j < W; ++j) {
+        const int k = first_max4(v0[j], v1[j], v2[j], v3[j]);
+        e0[j] += k == 0 ? g[j] : 0.f;
+        e1[j] += k == 1 ? g[j] : 0.f;
+        e2[j] += k == 2 ? g[j] : 0.f;
+        e3[j] += k == 3 ? g[j] : 0.f;
+      }
+      U::store(a.dx, d00, e0);
+      U::store(a.dx, d00 + a.lddx, e1);
+      U::store(a.dx, d10, e2);
+      U::store(a.dx, d10 + a.lddx, e3);
+    } else {
+      // fp32: only the winning pixel of each channel is touched (the other three keep their bits, a -0.0 included)
 #pragma unroll
-  for (int j = 0; j < 8; ++j) red[threadIdx.x][j] = s[j];
-  __syncthreads();
-  if (uy == 0 && cok) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float t = 0.f;
-      for (int y = 0; y < RY; ++y) t += red[y * UX + ux][j];
-      out[c + j] = t;
-    }
-  }
-  __syncthreads();
-}
-
-__global__ void __launch_bounds__(256) colstats_bf16_kernel(const dfl_colstats_args a, int UX, int rows_per_block) {
-  __shared__ float red[256][8];
-  const int RY = 256 / UX;
-  const int ux = threadIdx.x % UX, uy = threadIdx.x / UX;
-  const int c = (blockIdx.y * UX + ux) * 8;
-  const bool cok = c < a.C;
-  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-  int64_t r1 = r0 + rows_per_block;
-  if (r1 > a.M) r1 = a.M;
-  float s1[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, s2[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (cok) {
-    for (int64_t r = r0 + uy; r < r1; r += RY) {
-      float va[8], vb[8];
-      unpack8(ld8(a.a, r * a.lda + c), va);
-      if (a.b != nullptr) unpack8(ld8(a.b, r * a.ldb + c), vb);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        s1[j] += va[j];
-        s2[j] = fmaf(va[j], a.b != nullptr ? vb[j] : va[j], s2[j]);
+      for (int j = 0; j < W; ++j) {
+        const int k = first_max4(v0[j], v1[j], v2[j], v3[j]);
+        a.dx[(k < 2 ? d00 : d10) + ((k & 1) ? a.lddx : 0) + j] += g[j];
       }
     }
-  }
-  reduce_units8(red, s1, ux, uy, UX, RY, cok, a.partials + ((int64_t)blockIdx.x * 2 + 0) * a.C, c);
-  reduce_units8(red, s2, ux, uy, UX, RY, cok, a.partials + ((int64_t)blockIdx.x * 2 + 1) * a.C, c);
-}
-
-__global__ void __launch_bounds__(256) bn_relu_bwd_bf16_kernel(const dfl_bn_relu_bwd_args a, int UX, int rows_per_block) {
-  __shared__ float red[256][8];
-  const int RY = 256 / UX;
-  const int ux = threadIdx.x % UX, uy = threadIdx.x / UX;
-  const int C = a.C;
-  const int c = (blockIdx.y * UX + ux) * 8;
-  const bool cok = c < C;
-  float cA[8], cB[8], cC[8], s[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    cA[j] = 1.f; cB[j] = 0.f; cC[j] = 0.f; s[j] = 0.f;
-    if (a.coef != nullptr && cok) {
-      cA[j] = a.coef[c + j];
-      cB[j] = a.coef[C + c + j];
-      cC[j] = a.coef[2 * C + c + j];
-    }
-  }
-  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-  int64_t r1 = r0 + rows_per_block;
-  if (r1 > a.M) r1 = a.M;
-  if (cok) {
-    auto one = [&](const bu32x4 wdy, const bu32x4 wr, int64_t r) {
-      float dy[8], rv[8], o[8];
-      unpack8(wdy, dy);
-      unpack8(wr, rv);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] = rv[j] > 0.f ? fmaf(cA[j], dy[j], fmaf(cB[j], rv[j], cC[j])) : 0.f;
-      const bu32x4 w = pack8(o);
-      st8(a.dpre, r * a.ldo + c, w);
-      unpack8(w, o);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) s[j] += o[j];
-    };
-    int64_t r = r0 + uy;
-    for (; r + 3 * RY < r1; r += 4 * RY) {     // four rows in flight per thread
-      const bu32x4 d0 = ld8(a.dy, r * a.lddy + c), d1 = ld8(a.dy, (r + RY) * a.lddy + c);
-      const bu32x4 d2 = ld8(a.dy, (r + 2 * RY) * a.lddy + c), d3 = ld8(a.dy, (r + 3 * RY) * a.lddy + c);
-      const bu32x4 q0 = ld8(a.r, r * a.ldr + c), q1 = ld8(a.r, (r + RY) * a.ldr + c);
-      const bu32x4 q2 = ld8(a.r, (r + 2 * RY) * a.ldr + c), q3 = ld8(a.r, (r + 3 * RY) * a.ldr + c);
-      one(d0, q0, r);
-      one(d1, q1, r + RY);
-      one(d2, q2, r + 2 * RY);
-      one(d3, q3, r + 3 * RY);
-    }
-    for (; r < r1; r += RY) one(ld8(a.dy, r * a.lddy + c), ld8(a.r, r * a.ldr + c), r);
-  }
-  if (a.partials == nullptr) return;
-  reduce_units8(red, s, ux, uy, UX, RY, cok, a.partials + (int64_t)blockIdx.x * C, c);
-}
-
-__global__ void __launch_bounds__(256) affine_copy_bf16_kernel(const dfl_affine_copy_args a, int64_t total_units, int cq) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total_units; i += stride) {
-    const int u = (int)(i % cq);
-    int64_t pix = i / cq;
-    const int xw = (int)(pix % a.W);
-    pix /= a.W;
-    const int yh = (int)(pix % a.H);
-    const int n = (int)(pix / a.H);
-    const int c = u * 8;
-    const int64_t so = (((int64_t)n * a.xH + a.xoy + yh) * a.xW + a.xox + xw) * a.ldx + c;
-    const int64_t dof = (((int64_t)n * a.yH + a.yoy + yh) * a.yW + a.yox + xw) * a.ldy + c;
-    float v[8];
-    unpack8(ld8(a.x, so), v);
-    if (a.scale != nullptr) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = fmaf(v[j], a.scale[c + j], a.shift[c + j]);
-    }
-    if (a.accumulate) {
-      float o[8];
-      unpack8(ld8(a.y, dof), o);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] += o[j];
-    }
-    st8(a.y, dof, pack8(v));
-  }
-}
-
-__global__ void __launch_bounds__(256) maxpool_fwd_bf16_kernel(const dfl_pool_args a, int64_t total_units, int cq) {
-  const int Ho = a.H / 2, Wo = a.W / 2;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total_units; i += stride) {
-    const int u = (int)(i % cq);
-    int64_t pix = i / cq;
-    const int ox = (int)(pix % Wo);
-    pix /= Wo;
-    const int oy = (int)(pix % Ho);
-    const int n = (int)(pix / Ho);
-    const int c = u * 8;
-    const int64_t s00 = (((int64_t)n * a.H + 2 * oy) * a.W + 2 * ox) * a.ldx + c;
-    const int64_t s10 = s00 + (int64_t)a.W * a.ldx;
-    float v0[8], v1[8], v2[8], v3[8], m[8];
-    unpack8(ld8(a.x, s00), v0);
-    unpack8(ld8(a.x, s00 + a.ldx), v1);
-    unpack8(ld8(a.x, s10), v2);
-    unpack8(ld8(a.x, s10 + a.ldx), v3);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) m[j] = fmaxf(fmaxf(v0[j], v1[j]), fmaxf(v2[j], v3[j]));
-    st8(a.y, (((int64_t)n * Ho + oy) * Wo + ox) * a.ldy + c, pack8(m));
-  }
-}
-
-__global__ void __launch_bounds__(256) maxpool_bwd_bf16_kernel(const dfl_pool_args a, int64_t total_units, int cq) {
-  const int Ho = a.H / 2, Wo = a.W / 2;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total_units; i += stride) {
-    const int u = (int)(i % cq);
-    int64_t pix = i / cq;
-    const int ox = (int)(pix % Wo);
-    pix /= Wo;
-    const int oy = (int)(pix % Ho);
-    const int n = (int)(pix / Ho);
-    const int c = u * 8;
-    const int64_t ipix = ((int64_t)n * a.H + 2 * oy) * a.W + 2 * ox;
-    const int64_t s00 = ipix * a.ldx + c, s10 = s00 + (int64_t)a.W * a.ldx;
-    const int64_t d00 = ipix * a.lddx + c, d10 = d00 + (int64_t)a.W * a.lddx;
-    float v0[8], v1[8], v2[8], v3[8], g[8], e0[8], e1[8], e2[8], e3[8];
-    unpack8(ld8(a.x, s00), v0);
-    unpack8(ld8(a.x, s00 + a.ldx), v1);
-    unpack8(ld8(a.x, s10), v2);
-    unpack8(ld8(a.x, s10 + a.ldx), v3);
-    unpack8(ld8(a.y, (((int64_t)n * Ho + oy) * Wo + ox) * a.ldy + c), g);
-    unpack8(ld8(a.dx, d00), e0);
-    unpack8(ld8(a.dx, d00 + a.lddx), e1);
-    unpack8(ld8(a.dx, d10), e2);
-    unpack8(ld8(a.dx, d10 + a.lddx), e3);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int k = first_max4(v0[j], v1[j], v2[j], v3[j]);
-      e0[j] += k == 0 ? g[j] : 0.f;
-      e1[j] += k == 1 ? g[j] : 0.f;
-      e2[j] += k == 2 ? g[j] : 0.f;
-      e3[j] += k == 3 ? g[j] : 0.f;
-    }
-    st8(a.dx, d00, pack8(e0));
-    st8(a.dx, d00 + a.lddx, pack8(e1));
-    st8(a.dx, d10, pack8(e2));
-    st8(a.dx, d10 + a.lddx, pack8(e3));
   }
 }
 
@@ -817,7 +611,7 @@ __global__ void __launch_bounds__(256) pack_kernel(const dfl_pack_job* __restric
           cell = (int64_t)(a0 / 16 + blk) * N + cp * B + b0 + x;
         }
         if (ok) {
-          bu32x4* d = reinterpret_cast<bu32x4*>(dst16 + cell * 16);
+          u32x4* d = reinterpret_cast<u32x4*>(dst16 + cell * 16);
           d[0] = pack8(f);
           d[1] = pack8(f + 8);
         }
@@ -839,7 +633,7 @@ __global__ void __launch_bounds__(256) pack_kernel(const dfl_pack_job* __restric
         const int k = kc * 16 + r;
         f[r] = k < K ? pack_src(j, k, n) : 0.f;
       }
-      bu32x4* d = reinterpret_cast<bu32x4*>(reinterpret_cast<unsigned short*>(j.dst) + i * 16);
+      u32x4* d = reinterpret_cast<u32x4*>(reinterpret_cast<unsigned short*>(j.dst) + i * 16);
       d[0] = pack8(f);
       d[1] = pack8(f + 8);
     }
@@ -915,7 +709,7 @@ __device__ __forceinline__ void pack_emit_cells(const float (*tile)[PK_T * PK_CM
       for (int r = 0; r < 16; ++r) f[r] = tile[16 * blk + r][x * Cc + cp];
       cell = (int64_t)(a0 / 16 + blk) * N + cp * B + b0 + x;
     }
-    bu32x4* d = reinterpret_cast<bu32x4*>(dst16 + cell * 16);
+    u32x4* d = reinterpret_cast<u32x4*>(dst16 + cell * 16);
     d[0] = pack8(f);
     d[1] = pack8(f + 8);
   }
@@ -1126,23 +920,11 @@ extern "C" int dfl_rowblock_count(int64_t M, int32_t C) { return rowblocks(M, C)
 extern "C" int dfl_colstats(const dfl_colstats_args* a, dfl_stream_t stream) {
   DFL_REQUIRE(a && a->a && a->partials && a->M > 0 && a->C > 0, "dfl_colstats: bad args");
   DFL_REQUIRE(a->nblocks == rowblocks(a->M, a->C), "dfl_colstats: nblocks must be dfl_rowblock_count(M, C)");
-  if (a->bf16) {
-    DFL_REQUIRE(a->C % 8 == 0 && a->lda % 8 == 0 && aligned16(a->a) && (a->b == nullptr || (a->ldb % 8 == 0 && aligned16(a->b))),
-                "dfl_colstats (bf16): C and ld must be multiples of 8, tensors 16-byte aligned");
-    const RowGeom g8 = row_geom8(a->C);
-    hipLaunchKernelGGL(colstats_bf16_kernel, dim3((unsigned)a->nblocks, (unsigned)g8.gy), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       *a, g8.UX, (int)ceil_div(a->M, a->nblocks));
-    return check_launch("dfl_colstats");
-  }
-  const bool vec_ok = a->lda % 4 == 0 && aligned16(a->a) && (a->b == nullptr || (a->ldb % 4 == 0 && aligned16(a->b)));
-  const RowGeom g = row_geom(a->C, vec_ok);
-  const int rpb = (int)ceil_div(a->M, a->nblocks);
-  dim3 grid((unsigned)a->nblocks, (unsigned)g.gy);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (g.vec)
-    hipLaunchKernelGGL(colstats_kernel<1>, grid, dim3(256), 0, s, a->a, a->b, a->partials, a->M, a->C, a->lda, a->ldb, g.UX, rpb);
-  else
-    hipLaunchKernelGGL(colstats_kernel<0>, grid, dim3(256), 0, s, a->a, a->b, a->partials, a->M, a->C, a->lda, a->ldb, g.UX, rpb);
+  int W;
+  const int rc = chan_unit_width("dfl_colstats", a->bf16, a->C, {{a->a, a->lda}, {a->b, a->ldb}}, &W);
+  if (rc != DFL_OK) return rc;
+  const RowGeom g = row_geom(a->C, W);
+  DFL_LAUNCH_UNIT(W, colstats_kernel, dim3((unsigned)a->nblocks, (unsigned)g.gy), stream, *a, g.UX, (int)ceil_div(a->M, a->nblocks));
   return check_launch("dfl_colstats");
 }
 
@@ -1193,26 +975,13 @@ extern "C" int dfl_bn_bwd_finalize(const dfl_bn_bwd_finalize_args* a, dfl_stream
 extern "C" int dfl_bn_relu_bwd_apply(const dfl_bn_relu_bwd_args* a, dfl_stream_t stream) {
   DFL_REQUIRE(a && a->dy && a->r && a->dpre && a->M > 0 && a->C > 0, "dfl_bn_relu_bwd_apply: bad args");
   DFL_REQUIRE(a->nblocks == rowblocks(a->M, a->C), "dfl_bn_relu_bwd_apply: nblocks must be dfl_rowblock_count(M, C)");
-  if (a->bf16) {
-    DFL_REQUIRE(a->C % 8 == 0 && a->lddy % 8 == 0 && a->ldr % 8 == 0 && a->ldo % 8 == 0 && aligned16(a->dy) && aligned16(a->r) &&
-                    aligned16(a->dpre) && !a->split_out,
-                "dfl_bn_relu_bwd_apply (bf16): C and ld must be multiples of 8, tensors 16-byte aligned, no split output");
-    const RowGeom g8 = row_geom8(a->C);
-    hipLaunchKernelGGL(bn_relu_bwd_bf16_kernel, dim3((unsigned)a->nblocks, (unsigned)g8.gy), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), *a, g8.UX, (int)ceil_div(a->M, a->nblocks));
-    return check_launch("dfl_bn_relu_bwd_apply");
-  }
-  const bool vec_ok = a->lddy % 4 == 0 && a->ldr % 4 == 0 && a->ldo % 4 == 0 && aligned16(a->dy) && aligned16(a->r) &&
-                      aligned16(a->dpre);
-  const RowGeom g = row_geom(a->C, vec_ok);
-  DFL_REQUIRE(!a->split_out || g.vec, "dfl_bn_relu_bwd_apply: split_out needs the vector layout (C, ld % 4 == 0, 16-byte alignment)");
-  const int rpb = (int)ceil_div(a->M, a->nblocks);
-  dim3 grid((unsigned)a->nblocks, (unsigned)g.gy);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (g.vec)
-    hipLaunchKernelGGL(bn_relu_bwd_kernel<1>, grid, dim3(256), 0, s, *a, g.UX, rpb);
-  else
-    hipLaunchKernelGGL(bn_relu_bwd_kernel<0>, grid, dim3(256), 0, s, *a, g.UX, rpb);
+  int W;
+  const int rc = chan_unit_width("dfl_bn_relu_bwd_apply", a->bf16, a->C, {{a->dy, a->lddy}, {a->r, a->ldr}, {a->dpre, a->ldo}}, &W,
+                                 "ld", !a->split_out, ", no split output");
+  if (rc != DFL_OK) return rc;
+  DFL_REQUIRE(!a->split_out || W == 4, "dfl_bn_relu_bwd_apply: split_out needs the vector layout (C, ld % 4 == 0, 16-byte alignment)");
+  const RowGeom g = row_geom(a->C, W);
+  DFL_LAUNCH_UNIT(W, bn_relu_bwd_kernel, dim3((unsigned)a->nblocks, (unsigned)g.gy), stream, *a, g.UX, (int)ceil_div(a->M, a->nblocks));
   return check_launch("dfl_bn_relu_bwd_apply");
 }
 
@@ -1241,74 +1010,43 @@ extern "C" int dfl_affine_copy(const dfl_affine_copy_args* a, dfl_stream_t strea
   DFL_REQUIRE(a->xoy >= 0 && a->xox >= 0 && a->xoy + a->H <= a->xH && a->xox + a->W <= a->xW, "dfl_affine_copy: source window");
   DFL_REQUIRE(a->yoy >= 0 && a->yox >= 0 && a->yoy + a->H <= a->yH && a->yox + a->W <= a->yW, "dfl_affine_copy: dest window");
   DFL_REQUIRE((a->scale == nullptr) == (a->shift == nullptr), "dfl_affine_copy: scale/shift go together");
-  if (a->bf16) {
-    DFL_REQUIRE(a->C % 8 == 0 && a->ldx % 8 == 0 && a->ldy % 8 == 0 && aligned16(a->x) && aligned16(a->y),
-                "dfl_affine_copy (bf16): C and ld must be multiples of 8, tensors 16-byte aligned");
-    const int cq8 = a->C / 8;
-    const int64_t tot8 = (int64_t)a->N * a->H * a->W * cq8;
-    hipLaunchKernelGGL(affine_copy_bf16_kernel, dim3(stream_grid(tot8)), dim3(256), 0, static_cast<hipStream_t>(stream), *a, tot8, cq8);
-    return check_launch("dfl_affine_copy");
-  }
-  const bool vec = a->C % 4 == 0 && a->ldx % 4 == 0 && a->ldy % 4 == 0 && aligned16(a->x) && aligned16(a->y) &&
-                   (a->scale == nullptr || (aligned16(a->scale) && aligned16(a->shift)));
-  const int cq = vec ? a->C / 4 : a->C;
+  int W;
+  const int rc = chan_unit_width("dfl_affine_copy", a->bf16, a->C, {{a->x, a->ldx}, {a->y, a->ldy}}, &W);
+  if (rc != DFL_OK) return rc;
+  // the float4 form reads scale / shift as float4 too (the other two forms read them one channel at a time)
+  if (W == 4 && a->scale != nullptr && !(aligned16(a->scale) && aligned16(a->shift))) W = 1;
+  const int cq = a->C / W;
   const int64_t total = (int64_t)a->N * a->H * a->W * cq;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (vec)
-    hipLaunchKernelGGL(affine_copy_kernel<1>, dim3(stream_grid(total)), dim3(256), 0, s, *a, total, cq);
-  else
-    hipLaunchKernelGGL(affine_copy_kernel<0>, dim3(stream_grid(total)), dim3(256), 0, s, *a, total, cq);
+  DFL_LAUNCH_UNIT(W, affine_copy_kernel, dim3(stream_grid(total)), stream, *a, total, cq);
   return check_launch("dfl_affine_copy");
 }
 
-static int pool_common(const dfl_pool_args* a, bool bwd, bool* vec, int* cq, int64_t* total) {
+// validation and unit form of both pool directions: units per pixel and units in all (one thread each, grid-stride)
+static int pool_form(const dfl_pool_args* a, bool bwd, int* W, int* cq, int64_t* total) {
   DFL_REQUIRE(a && a->x && a->y && a->N > 0 && a->H >= 2 && a->W >= 2 && a->C > 0, "dfl_maxpool2x2: bad args");
   DFL_REQUIRE(!bwd || a->dx != nullptr, "dfl_maxpool2x2_bwd: dx required");
-  *vec = a->C % 4 == 0 && a->ldx % 4 == 0 && a->ldy % 4 == 0 && aligned16(a->x) && aligned16(a->y) &&
-         (!bwd || (a->lddx % 4 == 0 && aligned16(a->dx)));
-  *cq = *vec ? a->C / 4 : a->C;
-  *total = (int64_t)a->N * (a->H / 2) * (a->W / 2) * *cq;
-  return DFL_OK;
-}
-
-static int pool_bf16_check(const dfl_pool_args* a, bool bwd, int* cq, int64_t* total) {
-  DFL_REQUIRE(a->C % 8 == 0 && a->ldx % 8 == 0 && a->ldy % 8 == 0 && aligned16(a->x) && aligned16(a->y) &&
-                  (!bwd || (a->lddx % 8 == 0 && aligned16(a->dx))),
-              "dfl_maxpool2x2 (bf16): C and ld must be multiples of 8, tensors 16-byte aligned");
-  *cq = a->C / 8;
+  const int rc = chan_unit_width("dfl_maxpool2x2", a->bf16, a->C, {{a->x, a->ldx}, {a->y, a->ldy}, {bwd ? a->dx : nullptr, a->lddx}}, W);
+  if (rc != DFL_OK) return rc;
+  *cq = a->C / *W;
   *total = (int64_t)a->N * (a->H / 2) * (a->W / 2) * *cq;
   return DFL_OK;
 }
 
 extern "C" int dfl_maxpool2x2_fwd(const dfl_pool_args* a, dfl_stream_t stream) {
-  bool vec; int cq; int64_t total;
-  int rc = pool_common(a, false, &vec, &cq, &total);
+  int W, cq;
+  int64_t total;
+  const int rc = pool_form(a, false, &W, &cq, &total);
   if (rc != DFL_OK) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (a->bf16) {
-    rc = pool_bf16_check(a, false, &cq, &total);
-    if (rc != DFL_OK) return rc;
-    hipLaunchKernelGGL(maxpool_fwd_bf16_kernel, dim3(stream_grid(total)), dim3(256), 0, s, *a, total, cq);
-    return check_launch("dfl_maxpool2x2_fwd");
-  }
-  if (vec) hipLaunchKernelGGL(maxpool_fwd_kernel<1>, dim3(stream_grid(total)), dim3(256), 0, s, *a, total, cq);
-  else hipLaunchKernelGGL(maxpool_fwd_kernel<0>, dim3(stream_grid(total)), dim3(256), 0, s, *a, total, cq);
+  DFL_LAUNCH_UNIT(W, maxpool_fwd_kernel, dim3(stream_grid(total)), stream, *a, total, cq);
   return check_launch("dfl_maxpool2x2_fwd");
 }
 
 extern "C" int dfl_maxpool2x2_bwd(const dfl_pool_args* a, dfl_stream_t stream) {
-  bool vec; int cq; int64_t total;
-  int rc = pool_common(a, true, &vec, &cq, &total);
+  int W, cq;
+  int64_t total;
+  const int rc = pool_form(a, true, &W, &cq, &total);
   if (rc != DFL_OK) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (a->bf16) {
-    rc = pool_bf16_check(a, true, &cq, &total);
-    if (rc != DFL_OK) return rc;
-    hipLaunchKernelGGL(maxpool_bwd_bf16_kernel, dim3(stream_grid(total)), dim3(256), 0, s, *a, total, cq);
-    return check_launch("dfl_maxpool2x2_bwd");
-  }
-  if (vec) hipLaunchKernelGGL(maxpool_bwd_kernel<1>, dim3(stream_grid(total)), dim3(256), 0, s, *a, total, cq);
-  else hipLaunchKernelGGL(maxpool_bwd_kernel<0>, dim3(stream_grid(total)), dim3(256), 0, s, *a, total, cq);
+  DFL_LAUNCH_UNIT(W, maxpool_bwd_kernel, dim3(stream_grid(total)), stream, *a, total, cq);
   return check_launch("dfl_maxpool2x2_bwd");
 }
 

@@ -13,7 +13,13 @@ jobs_max="${MAX_JOBS:-16}"
 for s in "${srcs[@]}"; do
   o="$out/${s%.hip}.o"
   objs+=("$o")
-  if [ ! -f "$o" ] || [ "$here/$s" -nt "$o" ] || [ "$here/common.h" -nt "$o" ] || [ "$here/direct_small.h" -nt "$o" ] || [ "$here/conv_epilogue.h" -nt "$o" ] || [ "$here/conv_rows.h" -nt "$o" ] || [ "$here/convp.h" -nt "$o" ] || [ "$here/conv_plan.h" -nt "$o" ] || [ "$here/head_caps.inc" -nt "$o" ] || [ "$here/head_mfma.inc" -nt "$o" ] || [ "$here/../../include/dfl_hip.h" -nt "$o" ]; then
+  stale=0
+  if [ ! -f "$o" ]; then stale=1; fi
+  # any header may reach any source: an object is stale when its source or any *.h / *.inc here or the C API is newer
+  for d in "$here/$s" "$here"/*.h "$here"/*.inc "$here/../../include/dfl_hip.h"; do
+    if [ "$d" -nt "$o" ]; then stale=1; fi
+  done
+  if [ "$stale" = 1 ]; then
     # the two patch-resident kernels live at 1-3 waves per SIMD: schedule them for instruction-level parallelism instead of
     # register pressure (same instructions, same results; measured 4.47 -> 4.45 ms per step), and so are the streaming kernels of
     # bn_elem.hip (the batched sums issue their loads earlier: 0.23 -> 0.21 ms per step)

@@ -446,7 +446,8 @@ def test_wgrad_affine_and_convT():
     aclose(dwt.numpy(), wt.grad.numpy(), rtol=1e-4, atol=1e-4)
 
 
-@pytest.mark.parametrize('C_,M', [(32, 5000), (8, 777), (1024, 576), (4, 33)])
+# (6, 333): C not a multiple of 4 -> the one-channel form of colstats / bn_relu_bwd_apply (the others take the float4 form)
+@pytest.mark.parametrize('C_,M', [(32, 5000), (8, 777), (1024, 576), (4, 33), (6, 333)])
 def test_batchnorm_forward_backward(C_, M):
     """colstats + bn_finalize + bn_bwd_finalize + bn_relu_bwd_apply against torch's batch_norm autograd (fp64)."""
     lib = nat.lib()
@@ -538,18 +539,19 @@ def test_maxpool(shape):
 def test_affine_copy_window():
     lib = nat.lib()
     g = torch.Generator().manual_seed(4)
-    N, C_, H, W = 2, 8, 9, 11
-    x = torch.randn(N, H, W, C_, generator=g)
-    sc, sh = torch.rand(C_, generator=g), torch.randn(C_, generator=g)
-    xd, scd, shd = x.to(DEV), sc.to(DEV), sh.to(DEV)
-    yd = torch.zeros(N, 5, 6, 2 * C_, device=DEV)
-    a = nat.AffineCopyArgs(x=xd.data_ptr(), y=yd.data_ptr() + 4 * C_, scale=scd.data_ptr(), shift=shd.data_ptr(), N=N, H=5, W=6,
-                           C=C_, ldx=C_, xH=H, xW=W, xoy=2, xox=3, ldy=2 * C_, yH=5, yW=6)
-    nat.check(lib.dfl_affine_copy(C.addressof(a), stream()))
-    torch.cuda.synchronize()
-    ref = x[:, 2:7, 3:9, :] * sc + sh
-    aclose(yd.cpu()[..., C_:].numpy(), ref.numpy(), rtol=1e-6, atol=1e-6)
-    assert float(yd.cpu()[..., :C_].abs().max()) == 0.0
+    N, H, W = 2, 9, 11
+    for C_ in (8, 6):       # the float4 form, and (C not a multiple of 4) the one-channel form
+        x = torch.randn(N, H, W, C_, generator=g)
+        sc, sh = torch.rand(C_, generator=g), torch.randn(C_, generator=g)
+        xd, scd, shd = x.to(DEV), sc.to(DEV), sh.to(DEV)
+        yd = torch.zeros(N, 5, 6, 2 * C_, device=DEV)
+        a = nat.AffineCopyArgs(x=xd.data_ptr(), y=yd.data_ptr() + 4 * C_, scale=scd.data_ptr(), shift=shd.data_ptr(), N=N, H=5, W=6,
+                               C=C_, ldx=C_, xH=H, xW=W, xoy=2, xox=3, ldy=2 * C_, yH=5, yW=6)
+        nat.check(lib.dfl_affine_copy(C.addressof(a), stream()))
+        torch.cuda.synchronize()
+        ref = x[:, 2:7, 3:9, :] * sc + sh
+        aclose(yd.cpu()[..., C_:].numpy(), ref.numpy(), rtol=1e-6, atol=1e-6)
+        assert float(yd.cpu()[..., :C_].abs().max()) == 0.0
 
 
 @pytest.mark.parametrize('NC,L,two,softmax,F_', [(7, 14, True, True, 32), (3, 14, False, True, 8), (5, 0, True, False, 8),
