@@ -4,7 +4,7 @@ set -euo pipefail
 here="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 out="$here/../lib"
 mkdir -p "$out"
-srcs=(api.hip conv_gemm.hip conv_plan.hip conv_rows.hip convp_bf16.hip convq_bf16.hip convn_bf16.hip convs_bf16.hip convs_f32.hip wgradp_bf16.hip wgrad_gemm.hip direct_small.hip bn_elem.hip head.hip loss.hip prep.hip augment.hip upsample.hip overlay.hip overlay_fullres.hip mesh.hip)
+srcs=(api.hip conv_gemm.hip conv_plan.hip conv_rows.hip convp_bf16.hip convq_bf16.hip convn_bf16.hip convs.hip wgradp_bf16.hip wgrad_gemm.hip direct_small.hip bn_elem.hip head.hip loss.hip prep.hip augment.hip upsample.hip overlay.hip overlay_fullres.hip mesh.hip)
 objs=()
 pids=()
 # one hipcc per source, at most $MAX_JOBS (default 16) at a time
@@ -24,7 +24,7 @@ for s in "${srcs[@]}"; do
     # register pressure (same instructions, same results; measured 4.47 -> 4.45 ms per step), and so are the streaming kernels of
     # bn_elem.hip (the batched sums issue their loads earlier: 0.23 -> 0.21 ms per step)
     extra=""
-    case "$s" in convp_bf16.hip|convq_bf16.hip|convn_bf16.hip|convs_bf16.hip|convs_f32.hip|wgradp_bf16.hip|bn_elem.hip) extra="-mllvm -amdgpu-sched-strategy=max-ilp";; esac
+    case "$s" in convp_bf16.hip|convq_bf16.hip|convn_bf16.hip|convs.hip|wgradp_bf16.hip|bn_elem.hip) extra="-mllvm -amdgpu-sched-strategy=max-ilp";; esac
     # the augmentation rounds every product and sum separately, as its numpy restatement (tests/aug_ref.py) does, and the
     # overlays as torch's CPU ops do (an FMA moves results across the 8-bit truncation boundaries)
     case "$s" in augment.hip|overlay.hip|overlay_fullres.hip) extra="-ffp-contract=off";; esac

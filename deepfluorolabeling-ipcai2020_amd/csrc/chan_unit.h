@@ -9,8 +9,6 @@
 
 namespace dfl {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 // 8 bf16 (16 bytes, channel j in half-word j) <-> 8 fp32; pack8 rounds to nearest even
 __device__ __forceinline__ void unpack8(const u32x4 w, float* f) {
   f[0] = __uint_as_float(w.x << 16); f[1] = __uint_as_float(w.x & 0xffff0000u);

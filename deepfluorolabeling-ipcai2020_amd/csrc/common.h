@@ -58,6 +58,16 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+// Two bf16 in a 32-bit word, the even channel in the low half: the halves as fp32, and two fp32 rounded into a word
+__device__ __forceinline__ float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
+__device__ __forceinline__ uint32_t pack_bf2(float a, float b) {
+  const bf16x2_t h = __builtin_convertvector((f32x2_t){a, b}, bf16x2_t);   // round to nearest even (v_cvt_pk_bf16_f32)
+  return __builtin_bit_cast(uint32_t, h);
+}
 
 // x = p[0] + p[1] (+ p[2]) + O(2^-8NP |x|): successive bf16 roundings of the residual; 4 values -> 4 bf16 per part
 template <int NP>

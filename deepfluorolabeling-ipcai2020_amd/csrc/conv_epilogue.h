@@ -17,8 +17,6 @@ struct ConvK {
   uint32_t x_bytes, w_bytes, y_bytes, so_bytes;
 };
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ float4 buf_load4(__amdgpu_buffer_rsrc_t rs, uint32_t voff, uint32_t soff) {
   const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0);
   return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));

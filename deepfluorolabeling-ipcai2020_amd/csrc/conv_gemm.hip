@@ -820,10 +820,7 @@ extern "C" int dfl_set_conv_rows_min_tiles(int32_t n) {
 extern "C" int dfl_conv2d_pair(const dfl_conv_args* a, const dfl_conv_args* b, dfl_stream_t stream) {
   DFL_REQUIRE(a != nullptr && b != nullptr, "dfl_conv2d_pair: null arguments");
   dfl::ConvRoute r;
-  if (dfl::conv_pair_route(a, b, &r) > 0) {
-    if (r.form == dfl::FORM_BF16) return dfl::convs_pair_launch(r.plan.p, b, static_cast<hipStream_t>(stream));
-    return dfl::convs32_pair_launch(a, b, static_cast<hipStream_t>(stream));
-  }
+  if (dfl::conv_pair_route(a, b, &r) > 0) return dfl::convs_pair_launch(r.plan.p, b, static_cast<hipStream_t>(stream));
   const int rc = dfl_conv2d(a, stream);
   return rc != DFL_OK ? rc : dfl_conv2d(b, stream);
 }
@@ -842,10 +839,10 @@ extern "C" int dfl_conv2d(const dfl_conv_args* a, dfl_stream_t stream) {
     case dfl::FORM_BF16: return dfl::convp_launch(r.plan, s);
     case dfl::FORM_FIRST: return dfl::convs_first_launch(a, s);
     case dfl::FORM_LATENCY32: {
-      int sp = 1;
-      rc = dfl::convs32_launch(a, s, &sp);
-      if (rc != DFL_OK || sp <= 1) return rc;
-      k.splits = sp;
+      DFL_REQUIRE(r.splits <= 1 || a->partial != nullptr, "dfl_conv2d: splits > 1 needs the partial buffer");
+      rc = dfl::convs_launch(r.plan, s);
+      if (rc != DFL_OK || r.splits <= 1) return rc;
+      k.splits = r.splits;
       return dfl::conv_finish(k, s, "dfl_conv2d (latency form, split-K finish)");
     }
     default: break;

@@ -14,8 +14,8 @@ int conv_finish_rows(int M, int Ntot);                 // row blocks of conv_fin
 
 enum ConvForm {
   FORM_BF16,        // bf16 tensors: plan.p.tile names the family (patch, latency, unrolled 3x3, narrow 3x3)
-  FORM_FIRST,       // the 1-channel 3x3 first layer in latency form (convs_bf16.hip)
-  FORM_LATENCY32,   // the latency form of fp32 tensors (convs_f32.hip)
+  FORM_FIRST,       // the 1-channel 3x3 first layer in latency form (convs.hip)
+  FORM_LATENCY32,   // the latency form of fp32 tensors (convs.hip; its K slices end in conv_finish of conv_gemm.hip)
   FORM_DIRECT,      // direct small-K kernels (direct_small.hip)
   FORM_ROWS,        // row-tiled 3x3 kernels (conv_rows.hip)
   FORM_GEMM,        // generic GEMM kernels (conv_gemm.hip)
@@ -25,7 +25,7 @@ struct ConvRoute {
   ConvForm form;    // what dfl_conv2d launches
   int cfg;          // what dfl_conv_config reports
   int splits;       // K slices: the planned ones, or with none requested the form's suggestion
-  ConvPlan plan;    // FORM_BF16
+  ConvPlan plan;    // FORM_BF16, FORM_LATENCY32
   ConvK k;          // fp32 tensors: the validated block
   ConvForm stat_form;   // fp32 tensors: the form without the latency forms, which take no statistics -- what sizes stat_partials
   int stat_cfg;         // ... and its tile

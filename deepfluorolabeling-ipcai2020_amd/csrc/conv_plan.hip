@@ -1,6 +1,6 @@
 // Host-side planning of dfl_conv2d: which kernel family takes an argument block and, for bf16 tensors, its geometry (tile
 // configuration, patch shape, resident channels, K slices) and the LDS of its launch.  No kernels here: the kernel files
-// (convp_bf16.hip, convq_bf16.hip, convn_bf16.hip, convs_bf16.hip, conv_gemm.hip, ...) launch what this file decides.
+// (convp_bf16.hip, convq_bf16.hip, convn_bf16.hip, convs.hip, conv_gemm.hip, ...) launch what this file decides.
 #include <stdlib.h>
 #include <string.h>
 
@@ -33,7 +33,7 @@ struct Tile {
 
 // Numbered as dfl_conv_config (16 + index), the tuning file and dfl_conv_force_geometry know them:
 //   0 ... 38   patch-resident (convp_bf16.hip); 22 ... 29 (streamed 1x1 / 2x2 windows) and 30 ... 38 (two k-groups) measured only
-//   39         the latency form (convs_bf16.hip): plans itself, never through the search
+//   39         the latency form (convs.hip): plans itself, never through the search
 //   40 ... 48  the unrolled 3x3 form (convq_bf16.hip), its nine layouts; 49 ... 57 the same, persistent
 //   58 ... 63  the narrow 3x3 form (convn_bf16.hip), its six layouts; 64, 65 the persistent form of its layouts of three rows per wave
 static const std::vector<Tile>& tiles() {
@@ -461,7 +461,7 @@ static int convp_plan_search(const dfl_conv_args* a, ConvPlan* pl, int force_spl
   const int rc = convp_validate(a, &pl->p);
   if (rc != DFL_OK) return rc;
 
-  // the latency form (dfl_conv_args.latency_form: small problems of a batch-1 inference forward, convs_bf16.hip) plans itself
+  // the latency form (dfl_conv_args.latency_form: small problems of a batch-1 inference forward, convs.hip) plans itself
   if (t_force.tile < 0 && convs_eligible(*a, pl->p)) {
     convs_plan(*a, &pl->p, force_splits);
     pl->lds = (size_t)pl->p.lds_bytes;
@@ -573,6 +573,26 @@ static int convp_candidates(const dfl_conv_args* a, int32_t* out, int max) {
   return n;
 }
 
+// The latency plan of an fp32 block: the layer constants conv_prepare has validated, then the form's own conditions and work split
+static bool latency32_plan(const ConvK& k, int force_splits, ConvPlan* pl) {
+  if (!k.a.latency_form || !convs_enabled()) return false;      // (training blocks: nothing is copied)
+  memset(pl, 0, sizeof(*pl));
+  ConvP* p = &pl->p;
+  p->a = k.a;
+  p->Mtot = k.Mtot;
+  p->Hg = k.Hg;
+  p->Wg = k.Wg;
+  p->Cout = k.Cout;
+  p->T = k.a.KH * k.a.KW;
+  p->x_bytes = k.x_bytes;
+  p->w_bytes = k.w_bytes;
+  if (!convs_eligible(k.a, *p)) return false;
+  convs_plan(k.a, p, force_splits);
+  pl->lds = (size_t)p->lds_bytes;
+  pl->launch = convs_launch;
+  return true;
+}
+
 // ---- the route of dfl_conv2d and its queries
 int conv_route(const dfl_conv_args* a, int want_splits, ConvRoute* r) {
   if (a != nullptr && a->x_bf16) {                    // bf16 tensors: the plan's tile configuration names the family
@@ -603,14 +623,14 @@ int conv_route(const dfl_conv_args* a, int want_splits, ConvRoute* r) {
   r->form = r->stat_form;
   r->cfg = r->stat_cfg;
   r->splits = want_splits > 0 ? want_splits : sug;
-  if (convs_first_ok(a)) {                            // the 1-channel 3x3 first layer (convs_bf16.hip)
+  if (convs_first_ok(a)) {                            // the 1-channel 3x3 first layer (convs.hip)
     r->form = FORM_FIRST;
     r->cfg = 16 + CONVS_TILE;
     r->splits = 1;
-  } else if (const int zs = convs32_splits(a, want_splits)) {     // the latency form of fp32 tensors (convs_f32.hip)
+  } else if (latency32_plan(k, want_splits, &r->plan)) {          // the latency form of fp32 tensors (convs.hip)
     r->form = FORM_LATENCY32;
     r->cfg = 16 + CONVS_TILE;
-    r->splits = zs;
+    r->splits = r->plan.p.splits;
   }
   return DFL_OK;
 }
@@ -619,8 +639,7 @@ static int want_splits(const dfl_conv_args* a) { return a != nullptr && a->split
 
 int conv_pair_route(const dfl_conv_args* a, const dfl_conv_args* b, ConvRoute* r) {
   if (a == nullptr || b == nullptr || !a->latency_form || conv_route(a, want_splits(a), r) != DFL_OK) return 0;
-  if (r->form == FORM_BF16) return convs_pair_ok(a, b, r->plan.p);
-  return r->form == FORM_LATENCY32 ? convs32_pair_ok(a, b) : 0;
+  return r->form == FORM_BF16 || r->form == FORM_LATENCY32 ? convs_pair_ok(a, b, r->plan.p) : 0;
 }
 
 }  // namespace dfl

@@ -31,12 +31,6 @@ namespace {
 constexpr uint32_t NOOB = 0x80000000u;
 typedef unsigned int nu32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ float n_lo(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float n_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-__device__ __forceinline__ uint32_t n_pack(float a, float b) {
-  const bf16x2_t h = __builtin_convertvector((f32x2_t){a, b}, bf16x2_t);   // round to nearest even (v_cvt_pk_bf16_f32)
-  return __builtin_bit_cast(uint32_t, h);
-}
 
 // layouts (convn_layouts): waves side by side (32 pixels each) x rows per wave; the patch is 32 WX pixels wide and R (4 / WX) rows high
 
@@ -200,19 +194,19 @@ __global__ void __launch_bounds__(256, PERS ? 2 : n_occ(NCT, R, MB)) convn_kerne
     nu32x4 w = un.v;
     if constexpr (AFF == 1) {                      // zero padding applies AFTER the BatchNorm affine: outside pixels stay 0
       if (ok) {
-        w.x = n_pack(fmaf(n_lo(w.x), tA[0], tB[0]), fmaf(n_hi(w.x), tA[1], tB[1]));
-        w.y = n_pack(fmaf(n_lo(w.y), tA[2], tB[2]), fmaf(n_hi(w.y), tA[3], tB[3]));
-        w.z = n_pack(fmaf(n_lo(w.z), tA[4], tB[4]), fmaf(n_hi(w.z), tA[5], tB[5]));
-        w.w = n_pack(fmaf(n_lo(w.w), tA[6], tB[6]), fmaf(n_hi(w.w), tA[7], tB[7]));
+        w.x = pack_bf2(fmaf(bf_lo(w.x), tA[0], tB[0]), fmaf(bf_hi(w.x), tA[1], tB[1]));
+        w.y = pack_bf2(fmaf(bf_lo(w.y), tA[2], tB[2]), fmaf(bf_hi(w.y), tA[3], tB[3]));
+        w.z = pack_bf2(fmaf(bf_lo(w.z), tA[4], tB[4]), fmaf(bf_hi(w.z), tA[5], tB[5]));
+        w.w = pack_bf2(fmaf(bf_lo(w.w), tA[6], tB[6]), fmaf(bf_hi(w.w), tA[7], tB[7]));
       }
     }
     if constexpr (AFF == 2) {                      // outside pixels were loaded as zeros: r = 0 there, the value stays 0
       const nu32x4 r = un.v2;
       auto brb = [](float dy, float rv, float A, float B, float Cc) { return rv > 0.f ? fmaf(A, dy, fmaf(B, rv, Cc)) : 0.f; };
-      w.x = n_pack(brb(n_lo(w.x), n_lo(r.x), tA[0], tB[0], tC[0]), brb(n_hi(w.x), n_hi(r.x), tA[1], tB[1], tC[1]));
-      w.y = n_pack(brb(n_lo(w.y), n_lo(r.y), tA[2], tB[2], tC[2]), brb(n_hi(w.y), n_hi(r.y), tA[3], tB[3], tC[3]));
-      w.z = n_pack(brb(n_lo(w.z), n_lo(r.z), tA[4], tB[4], tC[4]), brb(n_hi(w.z), n_hi(r.z), tA[5], tB[5], tC[5]));
-      w.w = n_pack(brb(n_lo(w.w), n_lo(r.w), tA[6], tB[6], tC[6]), brb(n_hi(w.w), n_hi(r.w), tA[7], tB[7], tC[7]));
+      w.x = pack_bf2(brb(bf_lo(w.x), bf_lo(r.x), tA[0], tB[0], tC[0]), brb(bf_hi(w.x), bf_hi(r.x), tA[1], tB[1], tC[1]));
+      w.y = pack_bf2(brb(bf_lo(w.y), bf_lo(r.y), tA[2], tB[2], tC[2]), brb(bf_hi(w.y), bf_hi(r.y), tA[3], tB[3], tC[3]));
+      w.z = pack_bf2(brb(bf_lo(w.z), bf_lo(r.z), tA[4], tB[4], tC[4]), brb(bf_hi(w.z), bf_hi(r.z), tA[5], tB[5], tC[5]));
+      w.w = pack_bf2(brb(bf_lo(w.w), bf_lo(r.w), tA[6], tB[6], tC[6]), brb(bf_hi(w.w), bf_hi(r.w), tA[7], tB[7], tC[7]));
     }
     return w;
   };
@@ -437,14 +431,14 @@ __global__ void __launch_bounds__(256, PERS ? 2 : n_occ(NCT, R, MB)) convn_kerne
 #pragma unroll
       for (int d = 0; d < 8; ++d) {
         const float v0 = fmaxf(acc[ct][r][2 * d] + bias[2 * d], relu_floor), v1 = fmaxf(acc[ct][r][2 * d + 1] + bias[2 * d + 1], relu_floor);
-        pk[d] = n_pack(v0, v1);
+        pk[d] = pack_bf2(v0, v1);
       }
       if (do_stats) {                               // statistics of the values as stored (columns beyond a ragged edge: none)
         float vs[16];
 #pragma unroll
         for (int d = 0; d < 8; ++d) {
-          vs[2 * d] = n_lo(pk[d]);
-          vs[2 * d + 1] = n_hi(pk[d]);
+          vs[2 * d] = bf_lo(pk[d]);
+          vs[2 * d + 1] = bf_hi(pk[d]);
         }
         if (ragged) {
 #pragma unroll
@@ -457,10 +451,10 @@ __global__ void __launch_bounds__(256, PERS ? 2 : n_occ(NCT, R, MB)) convn_kerne
           for (int g4 = 0; g4 < 4; ++g4) {
             uint2 o = make_uint2(0u, 0u);
             if (ocol_ok) o = *reinterpret_cast<const uint2*>(sop + ((size_t)rowpix * (size_t)a.ldso + (size_t)(ct * 32 + g4 * 8)) + (so_voff >> 1));
-            s2[ct][g4 * 4 + 0] = fmaf(vs[g4 * 4 + 0], n_lo(o.x), s2[ct][g4 * 4 + 0]);
-            s2[ct][g4 * 4 + 1] = fmaf(vs[g4 * 4 + 1], n_hi(o.x), s2[ct][g4 * 4 + 1]);
-            s2[ct][g4 * 4 + 2] = fmaf(vs[g4 * 4 + 2], n_lo(o.y), s2[ct][g4 * 4 + 2]);
-            s2[ct][g4 * 4 + 3] = fmaf(vs[g4 * 4 + 3], n_hi(o.y), s2[ct][g4 * 4 + 3]);
+            s2[ct][g4 * 4 + 0] = fmaf(vs[g4 * 4 + 0], bf_lo(o.x), s2[ct][g4 * 4 + 0]);
+            s2[ct][g4 * 4 + 1] = fmaf(vs[g4 * 4 + 1], bf_hi(o.x), s2[ct][g4 * 4 + 1]);
+            s2[ct][g4 * 4 + 2] = fmaf(vs[g4 * 4 + 2], bf_lo(o.y), s2[ct][g4 * 4 + 2]);
+            s2[ct][g4 * 4 + 3] = fmaf(vs[g4 * 4 + 3], bf_hi(o.y), s2[ct][g4 * 4 + 3]);
           }
         } else {
 #pragma unroll

@@ -21,7 +21,7 @@ struct ConvP {
   uint32_t x2_bytes, xo_bytes;  // extent of the second input tensor (dfl_conv_args.x_mode) and of x_out
   uint32_t mPP, mPW;            // ceil(2^32 / (PH * PW)), ceil(2^32 / PW): divisions of patch row indices by multiply-high
   int tab_off, pad1;            // LDS offset of the live-BatchNorm tables (set by the planner)
-  // latency form (convs_bf16.hip; tile == CONVS_TILE): 32 x 32 tiles over (pixels, columns), waves of a workgroup per tile (log2),
+  // latency form (convs.hip; tile == CONVS_TILE): 32 x 32 tiles over (pixels, columns), waves of a workgroup per tile (log2),
   // 16-channel chunks per tap (log2), k-steps of the layer and per wave
   int s_mt, s_nt, s_ksplit_shift, s_cpk_shift, s_ksteps, s_kper;
   // unrolled 3x3 form (convq_bf16.hip; tiles 40 ... 57): ceil(2^32 / d) for d = npatch, ntiles, patches per image, npx
@@ -75,20 +75,15 @@ bool convn_layout_ok(int layout, int ntot, int cin);              // is the layo
 size_t convn_lds_bytes(int layout, int cin, int ntot, int pers, int* tab_off);
 bool convn_pers_ok(int layout, const dfl_conv_args& a);            // is the persistent form built for this layout / layer?
 
-// Latency form for the small problems of a batch-1 inference forward (convs_bf16.hip)
+// Latency form for the small problems of a batch-1 inference forward (convs.hip): bf16 tensors, and fp32 tensors in math modes 0
+// (fp32 matrix instructions) and 1 (bf16x3).  p: the validated block's layer constants; the plan is its s_* fields
 bool convs_eligible(const dfl_conv_args& a, const ConvP& p);
 void convs_plan(const dfl_conv_args& a, ConvP* p, int force_splits);
-int convs_launch(const ConvPlan& pl, hipStream_t s);
+int convs_launch(const ConvPlan& pl, hipStream_t s);                      // (the K-slice finish is the caller's)
 bool convs_first_ok(const dfl_conv_args* a);                              // the 1-channel 3x3 first layer
 int convs_first_launch(const dfl_conv_args* a, hipStream_t s);
 int convs_pair_ok(const dfl_conv_args* a, const dfl_conv_args* b, const ConvP& pa);   // dfl_conv_pair_ok; pa = a's plan
 int convs_pair_launch(const ConvP& pa, const dfl_conv_args* b, hipStream_t s);
-
-// ... and for fp32 tensors, math modes 0 (fp32 matrix instructions) and 1 (bf16x3): convs_f32.hip
-int convs32_splits(const dfl_conv_args* a, int force_splits);             // K slices of the form (force_splits as convp_plan); 0: not this form
-int convs32_launch(const dfl_conv_args* a, hipStream_t s, int* splits_out);
-int convs32_pair_ok(const dfl_conv_args* a, const dfl_conv_args* b);
-int convs32_pair_launch(const dfl_conv_args* a, const dfl_conv_args* b, hipStream_t s);
 
 struct WgP;
 int wgradp_suggest_splits(const dfl_wgrad_args* a);

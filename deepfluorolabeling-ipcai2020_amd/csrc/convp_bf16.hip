@@ -37,12 +37,6 @@ constexpr uint32_t POOB = 0x80000000u;
 #endif
 typedef unsigned int pu32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-__device__ __forceinline__ uint32_t pack_bf2(float a, float b) {
-  const bf16x2_t h = __builtin_convertvector((f32x2_t){a, b}, bf16x2_t);   // round to nearest even (v_cvt_pk_bf16_f32)
-  return __builtin_bit_cast(uint32_t, h);
-}
 __device__ __forceinline__ float round_bf(float v) { return (float)(__bf16)v; }
 // q / d for the small row indices of a patch (q < 65536, d < 65536): one multiply-high with m = ceil(2^32 / d) from the host
 // (the epilogue decodes a patch row into (image, y, x) for every row it stores: two 35-instruction divisions each before)

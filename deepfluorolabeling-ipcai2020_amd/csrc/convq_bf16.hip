@@ -30,15 +30,9 @@ namespace {
 constexpr uint32_t QOOB = 0x80000000u;
 typedef unsigned int qu32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ float q_lo(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float q_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-__device__ __forceinline__ uint32_t q_pack(float a, float b) {
-  const bf16x2_t h = __builtin_convertvector((f32x2_t){a, b}, bf16x2_t);   // round to nearest even (v_cvt_pk_bf16_f32)
-  return __builtin_bit_cast(uint32_t, h);
-}
 __device__ __forceinline__ void q_unpack(const qu32x4 w, float* f) {
-  f[0] = q_lo(w.x); f[1] = q_hi(w.x); f[2] = q_lo(w.y); f[3] = q_hi(w.y);
-  f[4] = q_lo(w.z); f[5] = q_hi(w.z); f[6] = q_lo(w.w); f[7] = q_hi(w.w);
+  f[0] = bf_lo(w.x); f[1] = bf_hi(w.x); f[2] = bf_lo(w.y); f[3] = bf_hi(w.y);
+  f[4] = bf_lo(w.z); f[5] = bf_hi(w.z); f[6] = bf_lo(w.w); f[7] = bf_hi(w.w);
 }
 
 constexpr int QPW = 12, QIW = 14, QTM = 3;   // patch width, staged width, 32-row tiles per wave
@@ -209,10 +203,10 @@ __global__ void __launch_bounds__(64 * WM * WN * KS, 2) convq_kernel(const ConvP
       if (ok) {
         const float4 s0 = *reinterpret_cast<const float4*>(in_tab + crel + cg * 8), s1 = *reinterpret_cast<const float4*>(in_tab + crel + cg * 8 + 4);
         const float4 h0 = *reinterpret_cast<const float4*>(in_tab + CKS + crel + cg * 8), h1 = *reinterpret_cast<const float4*>(in_tab + CKS + crel + cg * 8 + 4);
-        w.x = q_pack(fmaf(q_lo(w.x), s0.x, h0.x), fmaf(q_hi(w.x), s0.y, h0.y));
-        w.y = q_pack(fmaf(q_lo(w.y), s0.z, h0.z), fmaf(q_hi(w.y), s0.w, h0.w));
-        w.z = q_pack(fmaf(q_lo(w.z), s1.x, h1.x), fmaf(q_hi(w.z), s1.y, h1.y));
-        w.w = q_pack(fmaf(q_lo(w.w), s1.z, h1.z), fmaf(q_hi(w.w), s1.w, h1.w));
+        w.x = pack_bf2(fmaf(bf_lo(w.x), s0.x, h0.x), fmaf(bf_hi(w.x), s0.y, h0.y));
+        w.y = pack_bf2(fmaf(bf_lo(w.y), s0.z, h0.z), fmaf(bf_hi(w.y), s0.w, h0.w));
+        w.z = pack_bf2(fmaf(bf_lo(w.z), s1.x, h1.x), fmaf(bf_hi(w.z), s1.y, h1.y));
+        w.w = pack_bf2(fmaf(bf_lo(w.w), s1.z, h1.z), fmaf(bf_hi(w.w), s1.w, h1.w));
       }
     }
     if constexpr (AFF == 2) {                      // outside pixels were loaded as zeros: r = 0 there, the value stays 0
@@ -221,10 +215,10 @@ __global__ void __launch_bounds__(64 * WM * WN * KS, 2) convq_kernel(const ConvP
       const float4 B0 = *reinterpret_cast<const float4*>(in_tab + CKS + crel + cg * 8), B1 = *reinterpret_cast<const float4*>(in_tab + CKS + crel + cg * 8 + 4);
       const float4 C0 = *reinterpret_cast<const float4*>(in_tab + 2 * CKS + crel + cg * 8), C1 = *reinterpret_cast<const float4*>(in_tab + 2 * CKS + crel + cg * 8 + 4);
       auto brb = [](float dy, float rv, float A, float B, float Cc) { return rv > 0.f ? fmaf(A, dy, fmaf(B, rv, Cc)) : 0.f; };
-      w.x = q_pack(brb(q_lo(w.x), q_lo(r.x), A0.x, B0.x, C0.x), brb(q_hi(w.x), q_hi(r.x), A0.y, B0.y, C0.y));
-      w.y = q_pack(brb(q_lo(w.y), q_lo(r.y), A0.z, B0.z, C0.z), brb(q_hi(w.y), q_hi(r.y), A0.w, B0.w, C0.w));
-      w.z = q_pack(brb(q_lo(w.z), q_lo(r.z), A1.x, B1.x, C1.x), brb(q_hi(w.z), q_hi(r.z), A1.y, B1.y, C1.y));
-      w.w = q_pack(brb(q_lo(w.w), q_lo(r.w), A1.z, B1.z, C1.z), brb(q_hi(w.w), q_hi(r.w), A1.w, B1.w, C1.w));
+      w.x = pack_bf2(brb(bf_lo(w.x), bf_lo(r.x), A0.x, B0.x, C0.x), brb(bf_hi(w.x), bf_hi(r.x), A0.y, B0.y, C0.y));
+      w.y = pack_bf2(brb(bf_lo(w.y), bf_lo(r.y), A0.z, B0.z, C0.z), brb(bf_hi(w.y), bf_hi(r.y), A0.w, B0.w, C0.w));
+      w.z = pack_bf2(brb(bf_lo(w.z), bf_lo(r.z), A1.x, B1.x, C1.x), brb(bf_hi(w.z), bf_hi(r.z), A1.y, B1.y, C1.y));
+      w.w = pack_bf2(brb(bf_lo(w.w), bf_lo(r.w), A1.z, B1.z, C1.z), brb(bf_hi(w.w), bf_hi(r.w), A1.w, B1.w, C1.w));
       if (store_on) {                              // x_out: the interior of the patch, this slice's channels
         const bool own = ok && (unsigned)(iy - 1) < (unsigned)QPH && (unsigned)(ix - 1) < (unsigned)QPW;
         const uint32_t pixel = ((uint32_t)ps.img * (uint32_t)a.Hin + (uint32_t)gy) * (uint32_t)a.Win + (uint32_t)gx;
@@ -466,10 +460,10 @@ __global__ void __launch_bounds__(64 * WM * WN * KS, 2) convq_kernel(const ConvP
           for (int e = 0; e < 8; ++e) v[e] += o[e];
         }
         qu32x4 w;
-        w.x = q_pack(v[0], v[1]);
-        w.y = q_pack(v[2], v[3]);
-        w.z = q_pack(v[4], v[5]);
-        w.w = q_pack(v[6], v[7]);
+        w.x = pack_bf2(v[0], v[1]);
+        w.y = pack_bf2(v[2], v[3]);
+        w.z = pack_bf2(v[4], v[5]);
+        w.w = pack_bf2(v[6], v[7]);
         *reinterpret_cast<qu32x4*>(yp + yo) = w;
         if (do_stats) {
           float vr[8], u[8];

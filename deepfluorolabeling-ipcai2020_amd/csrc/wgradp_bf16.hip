@@ -50,12 +50,6 @@ struct WgP {
   int xcd_map;                         // workgroup -> (tile, slice) map, see the kernel
 };
 
-__device__ __forceinline__ float wbf_lo(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float wbf_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-__device__ __forceinline__ uint32_t wpack_bf2(float a, float b) {
-  const bf16x2_t h = __builtin_convertvector((f32x2_t){a, b}, bf16x2_t);
-  return __builtin_bit_cast(uint32_t, h);
-}
 
 // 8 consecutive pixels of one channel: two transposing reads (pixel rows at byte addresses r0 and r1 as seen by this lane)
 __device__ __forceinline__ bf16x8_t wtr_read8(const unsigned char* base, uint32_t r0, uint32_t r1) {
@@ -253,10 +247,10 @@ __global__ void __launch_bounds__(256 * KH, KH == 2 ? 4 : 3) wgradp_kernel(const
           const float4 b0 = *reinterpret_cast<const float4*>(dco + p.CMT + dcq * 8), b1 = *reinterpret_cast<const float4*>(dco + p.CMT + dcq * 8 + 4);
           const float4 c0 = *reinterpret_cast<const float4*>(dco + 2 * p.CMT + dcq * 8), c1 = *reinterpret_cast<const float4*>(dco + 2 * p.CMT + dcq * 8 + 4);
           auto brb = [](float dy, float rv, float A, float B, float Cc) { return rv > 0.f ? fmaf(A, dy, fmaf(B, rv, Cc)) : 0.f; };
-          v.x = wpack_bf2(brb(wbf_lo(v.x), wbf_lo(r.x), a0.x, b0.x, c0.x), brb(wbf_hi(v.x), wbf_hi(r.x), a0.y, b0.y, c0.y));
-          v.y = wpack_bf2(brb(wbf_lo(v.y), wbf_lo(r.y), a0.z, b0.z, c0.z), brb(wbf_hi(v.y), wbf_hi(r.y), a0.w, b0.w, c0.w));
-          v.z = wpack_bf2(brb(wbf_lo(v.z), wbf_lo(r.z), a1.x, b1.x, c1.x), brb(wbf_hi(v.z), wbf_hi(r.z), a1.y, b1.y, c1.y));
-          v.w = wpack_bf2(brb(wbf_lo(v.w), wbf_lo(r.w), a1.z, b1.z, c1.z), brb(wbf_hi(v.w), wbf_hi(r.w), a1.w, b1.w, c1.w));
+          v.x = pack_bf2(brb(bf_lo(v.x), bf_lo(r.x), a0.x, b0.x, c0.x), brb(bf_hi(v.x), bf_hi(r.x), a0.y, b0.y, c0.y));
+          v.y = pack_bf2(brb(bf_lo(v.y), bf_lo(r.y), a0.z, b0.z, c0.z), brb(bf_hi(v.y), bf_hi(r.y), a0.w, b0.w, c0.w));
+          v.z = pack_bf2(brb(bf_lo(v.z), bf_lo(r.z), a1.x, b1.x, c1.x), brb(bf_hi(v.z), bf_hi(r.z), a1.y, b1.y, c1.y));
+          v.w = pack_bf2(brb(bf_lo(v.w), bf_lo(r.w), a1.z, b1.z, c1.z), brb(bf_hi(v.w), bf_hi(r.w), a1.w, b1.w, c1.w));
         }
         *reinterpret_cast<wpu32x4*>(Ds + (uint32_t)k * (uint32_t)p.sd + (uint32_t)dcq * 16u) = v;
       }
@@ -271,10 +265,10 @@ __global__ void __launch_bounds__(256 * KH, KH == 2 ? 4 : 3) wgradp_kernel(const
             const float4 s0 = *reinterpret_cast<const float4*>(aff + gcq * 8), s1 = *reinterpret_cast<const float4*>(aff + gcq * 8 + 4);
             const float4 h0 = *reinterpret_cast<const float4*>(aff + p.CGT + gcq * 8), h1 = *reinterpret_cast<const float4*>(aff + p.CGT + gcq * 8 + 4);
             const float sc[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w}, sh[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
-            v.x = wpack_bf2(fmaf(wbf_lo(v.x), sc[0], sh[0]), fmaf(wbf_hi(v.x), sc[1], sh[1]));
-            v.y = wpack_bf2(fmaf(wbf_lo(v.y), sc[2], sh[2]), fmaf(wbf_hi(v.y), sc[3], sh[3]));
-            v.z = wpack_bf2(fmaf(wbf_lo(v.z), sc[4], sh[4]), fmaf(wbf_hi(v.z), sc[5], sh[5]));
-            v.w = wpack_bf2(fmaf(wbf_lo(v.w), sc[6], sh[6]), fmaf(wbf_hi(v.w), sc[7], sh[7]));
+            v.x = pack_bf2(fmaf(bf_lo(v.x), sc[0], sh[0]), fmaf(bf_hi(v.x), sc[1], sh[1]));
+            v.y = pack_bf2(fmaf(bf_lo(v.y), sc[2], sh[2]), fmaf(bf_hi(v.y), sc[3], sh[3]));
+            v.z = pack_bf2(fmaf(bf_lo(v.z), sc[4], sh[4]), fmaf(bf_hi(v.z), sc[5], sh[5]));
+            v.w = pack_bf2(fmaf(bf_lo(v.w), sc[6], sh[6]), fmaf(bf_hi(v.w), sc[7], sh[7]));
           }
         }
         *reinterpret_cast<wpu32x4*>(Gs + (uint32_t)pix * (uint32_t)p.sg + (uint32_t)gcq * 16u) = v;

@@ -145,7 +145,7 @@ def conv_bf16(x, wp, Ntot, KH, KW, stride, pad, Hout, Wout, bias=None, in_aff=No
     a.KH, a.KW, a.stride, a.pad = KH, KW, stride, pad
     a.Hout, a.Wout, a.Ntot, a.ldy = Hout, Wout, Ntot, ldy
     a.relu, a.accumulate, a.scatter2x2 = relu, accumulate, scatter
-    a.latency_form = 1 if latency else 0              # (the latency form of csrc/convs_bf16.hip: tests/test_gpu_latency_form.py)
+    a.latency_form = 1 if latency else 0              # (the latency form of csrc/convs.hip: tests/test_gpu_latency_form.py)
     sp = force_splits or nat.check(lib.dfl_conv_suggest_splits(C.addressof(a)), 'suggest')
     if sp > 1:
         Mrows = N * (Hin * Win if scatter else Hout * Wout)

@@ -64,7 +64,7 @@ def conv_call(x, wp, Ntot, KH, KW, stride, pad, Hout, Wout, bias=None, in_aff=No
               y_init=None, accumulate=0, scatter=0, stats=False, stat_other=None, ldy=None, ldx_pad=0,
               force_splits=None, w_split=0, x_split=0, latency=False, out_aff=None):
     """x: NCHW cpu tensor -> runs dfl_conv2d -> returns y as NHWC cpu tensor [N,Hout,Wout,Cout] (+ stats).
-    latency: the latency form (dfl_conv_args.latency_form, csrc/convs_f32.hip; tests/test_gpu_latency_form_f32.py)."""
+    latency: the latency form (dfl_conv_args.latency_form, csrc/convs.hip; tests/test_gpu_latency_form_f32.py)."""
     lib = nat.lib()
     N, Cin, Hin, Win = x.shape
     xh = nhwc(x)

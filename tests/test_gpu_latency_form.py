@@ -1,4 +1,4 @@
-"""The latency form of the bf16 convolution (csrc/convs_bf16.hip, dfl_conv_args.latency_form: the kernel inference plans ask
+"""The latency form of the convolution with bf16 tensors (csrc/convs.hip, element form ElemBF16; dfl_conv_args.latency_form: the kernel inference plans ask
 for on the small problems of a batch-1 forward; reference loops: train_test_code/util.py:116-165, :318-356) through the C ABI
 against fp64 PyTorch on the same bf16 operands -- the bars of tests/test_gpu_bf16.py -- and against the patch-resident kernel
 on the same argument block; then a whole inference forward with and without it.  pytest -m gpu."""

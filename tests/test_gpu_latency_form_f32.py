@@ -1,4 +1,4 @@
-"""The latency form of the convolution for fp32 tensors (csrc/convs_f32.hip: math modes fp32 and bf16x3 -- the arithmetics that hold
+"""The latency form of the convolution for fp32 tensors (csrc/convs.hip, element form ElemF32: math modes fp32 and bf16x3 -- the arithmetics that hold
 the 1e-4 forward bar; reference loops: train_test_code/util.py:116-165, :318-356) through the C ABI against fp64 PyTorch at the
 bars of tests/test_gpu_kernels.py and against the GEMM kernels on the same argument block; pairs, the output affine, the first
 layer; then a whole batch-1 inference forward with and without it.  pytest -m gpu."""
