@@ -13,6 +13,10 @@ from .optim import SGD, Adam, RMSprop
 from . import parallel
 from .parallel import DataParallel
 from .dataset import DeviceAugment
+from . import preprocess
+from .preprocess import (out_size, map_lands, unmap_lands, preprocess_projs, preprocess_segs, restore_labels,
+                         convert_file)
 
 __all__ = ['UNet', 'DiceLoss2D', 'DiceAndHeatMapLoss2D', 'ncc_2d', 'center_crop', 'get_device', 'WarmRestartLR', 'SGD',
-           'Adam', 'RMSprop', 'DataParallel', 'parallel', 'DeviceAugment']
+           'Adam', 'RMSprop', 'DataParallel', 'parallel', 'DeviceAugment', 'preprocess', 'out_size', 'map_lands', 'unmap_lands',
+           'preprocess_projs', 'preprocess_segs', 'restore_labels', 'convert_file']

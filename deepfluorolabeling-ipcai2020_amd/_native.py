@@ -274,6 +274,24 @@ class MeshNormalsArgs(C.Structure):
     _fields_ = [('pos', fp), ('tris', fp), ('vt_ptr', fp), ('vt_tri', fp), ('normals', fp), ('V', i64)]
 
 
+PREPROC_MAX_FACTOR = 16                                                     # include/dfl_hip.h: DFL_PREPROC_MAX_FACTOR
+
+
+class PreprocProjsArgs(C.Structure):
+    _fields_ = [('pixels', fp), ('rot180', fp), ('out', fp), ('scratch', fp), ('N', i32), ('R', i32), ('C', i32),
+                ('crop', i32), ('factor', i32), ('u16', i32), ('log', i32), ('min_intensity', f32)]
+
+
+class PreprocSegsArgs(C.Structure):
+    _fields_ = [('segs', fp), ('rot180', fp), ('out', fp), ('status', fp), ('N', i32), ('R', i32), ('C', i32),
+                ('crop', i32), ('factor', i32), ('reserved', i32)]
+
+
+class RestoreLabelsArgs(C.Structure):
+    _fields_ = [('labels', fp), ('rot180', fp), ('out', fp), ('N', i32), ('R', i32), ('C', i32), ('crop', i32),
+                ('factor', i32), ('reserved', i32)]
+
+
 class UpsampleArgs(C.Structure):
     _fields_ = [('x', fp), ('y', fp), ('N', i32), ('H', i32), ('W', i32), ('C', i32), ('ldx', i32), ('ldy', i32),
                 ('bf16', i32), ('accumulate', i32)]
@@ -309,7 +327,8 @@ _KIND_OF = {ConvArgs: OP_CONV, WgradArgs: OP_WGRAD, SumPartialsArgs: OP_SUM_PART
 _SIZEOF_ORDER = [ConvArgs, WgradArgs, PackJob, BnFinalizeArgs, ColstatsArgs, BnBwdFinalizeArgs, BnReluBwdArgs,
                  AffineCopyArgs, PoolArgs, HeadFwdArgs, HeadBwdArgs, LossArgs, EnsembleArgs, Op, ReduceJob, PrepArgs, EstLandsArgs,
                  UpsampleArgs, AugmentArgs, AugmentItem, OverlayArgs, ResamplePlan, ResampleArgs, FullresArgs, MeshMcArgs, MeshDecodeArgs,
-                 MeshTopoArgs, MeshCsrArgs, MeshSmoothArgs, MeshXformArgs, MeshNormalsArgs, OptimPackArgs]
+                 MeshTopoArgs, MeshCsrArgs, MeshSmoothArgs, MeshXformArgs, MeshNormalsArgs, PreprocProjsArgs, PreprocSegsArgs,
+                 RestoreLabelsArgs, OptimPackArgs]
 
 EXPORTS = ['dfl_version', 'dfl_last_error', 'dfl_sizeof', 'dfl_conv2d', 'dfl_conv_grid_m', 'dfl_conv2d_wgrad',
            'dfl_wgrad_suggest_splits', 'dfl_sum_partials', 'dfl_pack_weights', 'dfl_bn_finalize',
@@ -326,7 +345,8 @@ EXPORTS = ['dfl_version', 'dfl_last_error', 'dfl_sizeof', 'dfl_conv2d', 'dfl_con
            'dfl_sgd_pack_tiled', 'dfl_conv2d_pair', 'dfl_conv_pair_ok', 'dfl_augment_batch',
            'dfl_augment_scratch_bytes', 'dfl_overlay_batch', 'dfl_resample_bilinear_u8', 'dfl_fullres_overlay',
            'dfl_mesh_mc_count', 'dfl_mesh_mc_emit', 'dfl_mesh_decode', 'dfl_mesh_topology', 'dfl_mesh_csr', 'dfl_mesh_smooth',
-           'dfl_mesh_transform', 'dfl_mesh_normals', 'dfl_adam_step', 'dfl_rmsprop_step', 'dfl_optim_pack_tiled']
+           'dfl_mesh_transform', 'dfl_mesh_normals', 'dfl_adam_step', 'dfl_rmsprop_step', 'dfl_optim_pack_tiled',
+           'dfl_preproc_projs', 'dfl_preproc_segs', 'dfl_restore_labels']
 
 
 class DflError(RuntimeError):
@@ -372,6 +392,8 @@ def lib():
     L.dfl_overlay_batch.argtypes = [fp, fp]
     L.dfl_resample_bilinear_u8.argtypes = [fp, fp]
     L.dfl_fullres_overlay.argtypes = [fp, fp]
+    for fn in ('dfl_preproc_projs', 'dfl_preproc_segs', 'dfl_restore_labels'):
+        getattr(L, fn).argtypes = [fp, fp]
     for fn in ('dfl_mesh_mc_count', 'dfl_mesh_mc_emit', 'dfl_mesh_decode', 'dfl_mesh_topology', 'dfl_mesh_csr',
                'dfl_mesh_smooth', 'dfl_mesh_transform', 'dfl_mesh_normals'):
         getattr(L, fn).argtypes = [fp, fp]

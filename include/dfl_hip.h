@@ -934,6 +934,53 @@ typedef struct {
 int dfl_mesh_normals(const dfl_mesh_normals_args* a, dfl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Training files from the full-resolution dataset (the reference's README: crop 50 pixels from each border,
+ * log-transform, rotate by 180 degrees where 'rot-180-for-up' is set, downsample), restated in DESIGN.md section 14.
+ *
+ * The crop window is rows crop .. R-crop-1 and the columns likewise, Rc x Cc = (R - 2 crop) x (C - 2 crop); with the
+ * flag of image n set, cropped pixel (r, c) moves to (Rc-1-r, Cc-1-c).  Output pixel (i, j) of Ro x Co =
+ * ceil(Rc / factor) x ceil(Cc / factor) covers rows i*factor .. min((i+1)*factor, Rc)-1 of that (rotated) crop and
+ * the columns likewise: boxes of the bottom and right edges are clipped.  factor is 1..DFL_PREPROC_MAX_FACTOR.
+ *
+ * dfl_preproc_projs: out = the box mean of log(I0) - log(max(I, min_intensity)) with I0 the largest
+ * max(I, min_intensity) of that image's crop window (log != 0; min_intensity > 0), or the box mean of I (log == 0).
+ * Logarithms are fp32, box sums fp64.  Two launches: the reduction, which also takes the maximum (scratch), and one
+ * over the outputs that adds log(I0).
+ * dfl_preproc_segs: out = the most frequent label of the box, of equally frequent ones the smallest.  Labels are
+ * 0..15; *status is set to 1 when a larger one was met (the outputs are then undefined), else 0.
+ * dfl_restore_labels: the inverse for labels.  Pixel (r, c) of the crop window takes the label of the box that
+ * contains it (rotation undone); the border of `crop` pixels is 0.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define DFL_PREPROC_MAX_FACTOR 16
+typedef struct {
+  const void* pixels;             /* [N][R][C] fp32, or uint16 when u16 */
+  const int32_t* rot180;          /* [N] */
+  float* out;                     /* [N][Ro][Co] */
+  uint32_t* scratch;              /* [N] words (log only) */
+  int32_t N, R, C, crop, factor;
+  int32_t u16, log;
+  float min_intensity;
+} dfl_preproc_projs_args;
+int dfl_preproc_projs(const dfl_preproc_projs_args* a, dfl_stream_t stream);
+
+typedef struct {
+  const unsigned char* segs;      /* [N][R][C] */
+  const int32_t* rot180;          /* [N] */
+  unsigned char* out;             /* [N][Ro][Co] */
+  int32_t* status;                /* one word */
+  int32_t N, R, C, crop, factor, reserved;
+} dfl_preproc_segs_args;
+int dfl_preproc_segs(const dfl_preproc_segs_args* a, dfl_stream_t stream);
+
+typedef struct {
+  const unsigned char* labels;    /* [N][Ro][Co] */
+  const int32_t* rot180;          /* [N] */
+  unsigned char* out;             /* [N][R][C] */
+  int32_t N, R, C, crop, factor, reserved;
+} dfl_restore_labels_args;
+int dfl_restore_labels(const dfl_restore_labels_args* a, dfl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Product arithmetic of the convolution / weight-gradient GEMMs (fast paths; odd channel counts always use fp32):
  *   0 "fp32"    v_mfma_f32_32x32x2_f32: fp32 products, fp32 accumulation.
  *   1 "bf16x3"  every fp32 operand value is split into hi + lo bf16 parts when it is staged in LDS and the product is
