@@ -292,6 +292,19 @@ class RestoreLabelsArgs(C.Structure):
                 ('factor', i32), ('reserved', i32)]
 
 
+DRR_EXACT, DRR_TRILINEAR, DRR_MAX_LABELS = 0, 1, 16                        # include/dfl_hip.h: DFL_DRR_*
+
+
+class DrrObject(C.Structure):
+    _fields_ = [('o', f32 * 3), ('M', f32 * 9), ('box_lo', i32 * 3), ('box_hi', i32 * 3), ('mask', C.c_uint32)]
+
+
+class DrrArgs(C.Structure):
+    _fields_ = [('mu', fp), ('labels', fp), ('objects', fp), ('att', fp), ('plen', fp), ('label_map', fp), ('qscale', f32 * 9),
+                ('nx', i32), ('ny', i32), ('nz', i32), ('H', i32), ('W', i32), ('views', i32), ('n_obj', i32), ('n_labels', i32),
+                ('interp', i32), ('mapping', i32), ('step_mm', f32), ('min_len_mm', f32), ('reserved', i32)]
+
+
 class UpsampleArgs(C.Structure):
     _fields_ = [('x', fp), ('y', fp), ('N', i32), ('H', i32), ('W', i32), ('C', i32), ('ldx', i32), ('ldy', i32),
                 ('bf16', i32), ('accumulate', i32)]
@@ -328,7 +341,7 @@ _SIZEOF_ORDER = [ConvArgs, WgradArgs, PackJob, BnFinalizeArgs, ColstatsArgs, BnB
                  AffineCopyArgs, PoolArgs, HeadFwdArgs, HeadBwdArgs, LossArgs, EnsembleArgs, Op, ReduceJob, PrepArgs, EstLandsArgs,
                  UpsampleArgs, AugmentArgs, AugmentItem, OverlayArgs, ResamplePlan, ResampleArgs, FullresArgs, MeshMcArgs, MeshDecodeArgs,
                  MeshTopoArgs, MeshCsrArgs, MeshSmoothArgs, MeshXformArgs, MeshNormalsArgs, PreprocProjsArgs, PreprocSegsArgs,
-                 RestoreLabelsArgs, OptimPackArgs]
+                 RestoreLabelsArgs, DrrObject, DrrArgs, OptimPackArgs]
 
 EXPORTS = ['dfl_version', 'dfl_last_error', 'dfl_sizeof', 'dfl_conv2d', 'dfl_conv_grid_m', 'dfl_conv2d_wgrad',
            'dfl_wgrad_suggest_splits', 'dfl_sum_partials', 'dfl_pack_weights', 'dfl_bn_finalize',
@@ -346,7 +359,7 @@ EXPORTS = ['dfl_version', 'dfl_last_error', 'dfl_sizeof', 'dfl_conv2d', 'dfl_con
            'dfl_augment_scratch_bytes', 'dfl_overlay_batch', 'dfl_resample_bilinear_u8', 'dfl_fullres_overlay',
            'dfl_mesh_mc_count', 'dfl_mesh_mc_emit', 'dfl_mesh_decode', 'dfl_mesh_topology', 'dfl_mesh_csr', 'dfl_mesh_smooth',
            'dfl_mesh_transform', 'dfl_mesh_normals', 'dfl_adam_step', 'dfl_rmsprop_step', 'dfl_optim_pack_tiled',
-           'dfl_preproc_projs', 'dfl_preproc_segs', 'dfl_restore_labels']
+           'dfl_preproc_projs', 'dfl_preproc_segs', 'dfl_restore_labels', 'dfl_drr_render']
 
 
 class DflError(RuntimeError):
@@ -392,7 +405,7 @@ def lib():
     L.dfl_overlay_batch.argtypes = [fp, fp]
     L.dfl_resample_bilinear_u8.argtypes = [fp, fp]
     L.dfl_fullres_overlay.argtypes = [fp, fp]
-    for fn in ('dfl_preproc_projs', 'dfl_preproc_segs', 'dfl_restore_labels'):
+    for fn in ('dfl_preproc_projs', 'dfl_preproc_segs', 'dfl_restore_labels', 'dfl_drr_render'):
         getattr(L, fn).argtypes = [fp, fp]
     for fn in ('dfl_mesh_mc_count', 'dfl_mesh_mc_emit', 'dfl_mesh_decode', 'dfl_mesh_topology', 'dfl_mesh_csr',
                'dfl_mesh_smooth', 'dfl_mesh_transform', 'dfl_mesh_normals'):

@@ -1,0 +1,294 @@
+// Digitally reconstructed radiographs, per-label path lengths and a 2D label map from the CT and its 3D annotation.
+// Contract: include/dfl_hip.h (dfl_drr_object, dfl_drr_args); the semantics are stated in DESIGN.md section 15 and
+// restated in numpy float64 by tests/drr_ref.py.
+//
+// One thread per ray and view; the objects are looped over inside the thread, so the per-label lengths and the
+// attenuation stay in registers and every output is written once, with no atomics.  A wave covers an 8 x 8 pixel tile
+// (lane & 7, lane >> 3) and a workgroup of four waves 16 x 16: neighbouring rays walk neighbouring voxels (their label
+// and mu cache lines are shared) and leave the box after about as many steps.  MAP = 1 is the 64 x 1 row mapping that
+// tools/bench_drr.py compares against.
+//
+// Exact mode is an incremental grid traversal.  Per axis the thread keeps the INTEGER index k of the next plane it will
+// cross and computes that crossing from it, t = (k - 1/2 - o) / d -- never t += dt, whose rounding would accumulate over
+// several hundred steps.  The voxel index follows from the plane indices, so nothing is rounded to find it.  The box
+// exit plane is one of these planes with the same formula, so the walk ends exactly at t1; the index test of the loop
+// and the clamp in front of each load keep every address inside the volume whatever the arithmetic does.
+// A run of voxels of one label adds s (t_end - t_start) to that label at once: the 16-way select that finds the
+// accumulator (no register array is indexed with a run-time value) runs once per run, not once per voxel.
+// mu is loaded only where the label passes the mask.
+#include "common.h"
+
+namespace dfl {
+
+constexpr int DRR_NL = DFL_DRR_MAX_LABELS;
+
+struct DrrParams {
+  const float* mu;
+  const unsigned char* labels;
+  const dfl_drr_object* objects;
+  float* att;
+  float* plen;
+  unsigned char* label_map;
+  float q[9];
+  int nx, ny, nz, H, W, n_obj, n_labels;
+  float step_mm, min_len_mm;
+};
+
+__device__ __forceinline__ float drr_dot(const float* m, float c, float r) { return m[0] * c + m[1] * r + m[2]; }
+
+// t of plane k of one axis: the plane between voxels k - 1 and k
+__device__ __forceinline__ float drr_plane(int k, float o, float d) { return ((float)k - 0.5f - o) / d; }
+
+// Clip [t0, t1] to the slab [lo - 1/2, hi + 1/2] of one axis; false: the ray misses it
+__device__ __forceinline__ bool drr_clip(float o, float d, int lo, int hi, float& t0, float& t1) {
+  if (d == 0.f) return o >= (float)lo - 0.5f && o < (float)hi + 0.5f;
+  const float ta = drr_plane(lo, o, d), tb = drr_plane(hi + 1, o, d);
+  t0 = fmaxf(t0, fminf(ta, tb));
+  t1 = fminf(t1, fmaxf(ta, tb));
+  return true;
+}
+
+// Start of the walk on one axis: k = the first plane crossed after t0, i = the voxel index at t0+, step = +-1 (0: the
+// axis is never crossed, tn = inf).  Planes lo .. hi + 1 bound the voxels lo .. hi; their t are monotonic in k.
+__device__ __forceinline__ void drr_axis_start(float o, float d, int lo, int hi, float t0, int& k, int& i, int& step, float& tn) {
+  const float p = fminf(fmaxf(o + t0 * d, (float)lo - 1.f), (float)hi + 1.f);
+  const int est = min(max((int)floorf(p + 0.5f), lo), hi);
+  if (d == 0.f) {
+    step = 0;
+    k = 0;
+    i = est;
+    tn = __builtin_inff();
+    return;
+  }
+  if (d > 0.f) {
+    step = 1;
+    k = est + 1;                                         // smallest k in lo .. hi + 1 with t(k) > t0
+    while (k > lo && drr_plane(k - 1, o, d) > t0) --k;
+    while (k < hi + 1 && !(drr_plane(k, o, d) > t0)) ++k;
+    i = max(k - 1, lo);
+  } else {
+    step = -1;
+    k = est;                                             // largest k in lo .. hi + 1 with t(k) > t0
+    while (k < hi + 1 && drr_plane(k + 1, o, d) > t0) ++k;
+    while (k > lo && !(drr_plane(k, o, d) > t0)) --k;
+    i = min(k, hi);
+  }
+  tn = drr_plane(k, o, d);
+}
+
+__device__ __forceinline__ void drr_flush(float (&acc)[DRR_NL], uint32_t label, float len) {
+#pragma unroll
+  for (int l = 0; l < DRR_NL; ++l) acc[l] += label == (uint32_t)l ? len : 0.f;
+}
+
+constexpr uint32_t DRR_NONE = 255u;         // "not in an admitted run"
+
+template <bool PLEN>
+__device__ __forceinline__ void drr_exact_object(const DrrParams& P, const dfl_drr_object& ob, float c, float r, float s, float& att,
+                                                 float (&acc)[DRR_NL]) {
+  const float o[3] = {ob.o[0], ob.o[1], ob.o[2]};
+  const float d[3] = {drr_dot(ob.M, c, r), drr_dot(ob.M + 3, c, r), drr_dot(ob.M + 6, c, r)};
+  const int lo[3] = {max(ob.box_lo[0], 0), max(ob.box_lo[1], 0), max(ob.box_lo[2], 0)};
+  const int hi[3] = {min(ob.box_hi[0], P.nx - 1), min(ob.box_hi[1], P.ny - 1), min(ob.box_hi[2], P.nz - 1)};
+  if (hi[0] < lo[0] || hi[1] < lo[1] || hi[2] < lo[2]) return;
+  float t0 = 0.f, t1 = __builtin_inff();
+  bool ok = true;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) ok = drr_clip(o[a], d[a], lo[a], hi[a], t0, t1) && ok;
+  if (!ok || !(t1 > t0) || !(t1 < __builtin_inff())) return;
+  int k[3], i[3], step[3];
+  float tn[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) drr_axis_start(o[a], d[a], lo[a], hi[a], t0, k[a], i[a], step[a], tn[a]);
+  const uint32_t mask = ob.mask;
+  const int sy = P.nx, sz = P.nx * P.ny;
+  float t_cur = t0, run_start = t0;
+  uint32_t run = DRR_NONE;
+  // every step moves one index by one inside the box, so the trip count is bounded by the box's extent
+  while (i[0] >= lo[0] && i[0] <= hi[0] && i[1] >= lo[1] && i[1] <= hi[1] && i[2] >= lo[2] && i[2] <= hi[2]) {
+    const float t_next = fminf(fminf(tn[0], tn[1]), fminf(tn[2], t1));
+    const int idx = i[2] * sz + i[1] * sy + i[0];
+    const uint32_t lab = P.labels[idx];
+    const bool in = lab < (uint32_t)DRR_NL && ((mask >> lab) & 1u) != 0u;
+    if (in) att += (s * (t_next - t_cur)) * P.mu[idx];
+    if (PLEN) {
+      const uint32_t now = in ? lab : DRR_NONE;
+      if (now != run) {
+        if (run != DRR_NONE) drr_flush(acc, run, s * (t_cur - run_start));
+        run = now;
+        run_start = t_cur;
+      }
+    }
+    t_cur = t_next;
+    if (t_next >= t1) break;
+    // the axis with the smallest crossing advances; equal crossings follow in the next trips with length 0
+    const int a = tn[0] <= tn[1] ? (tn[0] <= tn[2] ? 0 : 2) : (tn[1] <= tn[2] ? 1 : 2);
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      if (b == a) {
+        k[b] += step[b];
+        i[b] += step[b];
+        tn[b] = drr_plane(k[b], o[b], d[b]);
+      }
+    }
+  }
+  if (PLEN && run != DRR_NONE) drr_flush(acc, run, s * (t_cur - run_start));
+}
+
+// mu of voxel (x, y, z) if its label is admitted, else 0; the indices are inside the volume
+__device__ __forceinline__ float drr_masked(const DrrParams& P, uint32_t mask, int x, int y, int z) {
+  const int idx = (z * P.ny + y) * P.nx + x;
+  const uint32_t lab = P.labels[idx];
+  return lab < (uint32_t)DRR_NL && ((mask >> lab) & 1u) != 0u ? P.mu[idx] : 0.f;
+}
+
+__device__ __forceinline__ void drr_corner(float p, int n, int& i0, int& i1, float& w) {
+  const float q = fminf(fmaxf(p, -2.f), (float)n + 1.f);
+  const float f = floorf(q);
+  w = q - f;
+  i0 = min(max((int)f, 0), n - 1);
+  i1 = min(max((int)f + 1, 0), n - 1);
+}
+
+__device__ __forceinline__ void drr_trilinear_object(const DrrParams& P, const dfl_drr_object& ob, float c, float r, float s, float& att) {
+  const float o[3] = {ob.o[0], ob.o[1], ob.o[2]};
+  const float d[3] = {drr_dot(ob.M, c, r), drr_dot(ob.M + 3, c, r), drr_dot(ob.M + 6, c, r)};
+  const int lo[3] = {max(ob.box_lo[0], 0), max(ob.box_lo[1], 0), max(ob.box_lo[2], 0)};
+  const int hi[3] = {min(ob.box_hi[0], P.nx - 1), min(ob.box_hi[1], P.ny - 1), min(ob.box_hi[2], P.nz - 1)};
+  if (hi[0] < lo[0] || hi[1] < lo[1] || hi[2] < lo[2]) return;
+  float t0 = 0.f, t1 = __builtin_inff();
+  bool ok = true;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) ok = drr_clip(o[a], d[a], lo[a], hi[a], t0, t1) && ok;
+  if (!ok || !(t1 > t0) || !(t1 < __builtin_inff())) return;
+  const float span = t1 - t0;
+  const float nf = fmaxf(1.f, ceilf(s * span / P.step_mm));
+  const int N = (int)fminf(nf, 2147483520.f);
+  const float dt = span / nf;
+  const uint32_t mask = ob.mask;
+  float sum = 0.f;
+  for (int j = 0; j < N; ++j) {
+    const float t = t0 + ((float)j + 0.5f) * dt;
+    int x0, x1, y0, y1, z0, z1;
+    float wx, wy, wz;
+    drr_corner(o[0] + t * d[0], P.nx, x0, x1, wx);
+    drr_corner(o[1] + t * d[1], P.ny, y0, y1, wy);
+    drr_corner(o[2] + t * d[2], P.nz, z0, z1, wz);
+    const float v000 = drr_masked(P, mask, x0, y0, z0), v100 = drr_masked(P, mask, x1, y0, z0);
+    const float v010 = drr_masked(P, mask, x0, y1, z0), v110 = drr_masked(P, mask, x1, y1, z0);
+    const float v001 = drr_masked(P, mask, x0, y0, z1), v101 = drr_masked(P, mask, x1, y0, z1);
+    const float v011 = drr_masked(P, mask, x0, y1, z1), v111 = drr_masked(P, mask, x1, y1, z1);
+    const float a00 = v000 + wx * (v100 - v000), a10 = v010 + wx * (v110 - v010);
+    const float a01 = v001 + wx * (v101 - v001), a11 = v011 + wx * (v111 - v011);
+    const float b0 = a00 + wy * (a10 - a00), b1 = a01 + wy * (a11 - a01);
+    sum += b0 + wz * (b1 - b0);
+  }
+  att += (s * span / nf) * sum;
+}
+
+// INTERP: DFL_DRR_EXACT / DFL_DRR_TRILINEAR; PLEN: plen or label_map is wanted; MAP 0: 8 x 8 tiles per wave, 1: 64 x 1
+template <int INTERP, bool PLEN, int MAP>
+__global__ __launch_bounds__(256) void drr_kernel(DrrParams P) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int col, row;
+  if (MAP == 0) {
+    col = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
+    row = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+  } else {
+    col = blockIdx.x * 64 + lane;
+    row = blockIdx.y * 4 + wave;
+  }
+  if (col >= P.W || row >= P.H) return;
+  const int view = blockIdx.z;
+  const float c = (float)col, r = (float)row;
+  const float qx = drr_dot(P.q, c, r), qy = drr_dot(P.q + 3, c, r), qz = drr_dot(P.q + 6, c, r);
+  const float s = sqrtf(qx * qx + qy * qy + qz * qz);
+  float att = 0.f;
+  float acc[DRR_NL];
+#pragma unroll
+  for (int l = 0; l < DRR_NL; ++l) acc[l] = 0.f;
+  const dfl_drr_object* obs = P.objects + (size_t)view * P.n_obj;
+  for (int n = 0; n < P.n_obj; ++n) {
+    if (INTERP == DFL_DRR_EXACT) drr_exact_object<PLEN>(P, obs[n], c, r, s, att, acc);
+    else drr_trilinear_object(P, obs[n], c, r, s, att);
+  }
+  const size_t HW = (size_t)P.H * P.W, pix = (size_t)row * P.W + col;
+  P.att[(size_t)view * HW + pix] = att;
+  if (PLEN) {
+    if (P.plen != nullptr) {
+      float* pl = P.plen + (size_t)view * P.n_labels * HW + pix;
+#pragma unroll
+      for (int l = 0; l < DRR_NL; ++l)
+        if (l < P.n_labels) pl[(size_t)l * HW] = acc[l];
+    }
+    if (P.label_map != nullptr) {
+      float best = 0.f;
+      int arg = 0;
+#pragma unroll
+      for (int l = 1; l < DRR_NL; ++l) {
+        if (l < P.n_labels && (arg == 0 || acc[l] > best)) {
+          best = acc[l];
+          arg = l;
+        }
+      }
+      P.label_map[(size_t)view * HW + pix] = (unsigned char)(arg != 0 && best >= P.min_len_mm ? arg : 0);
+    }
+  }
+}
+
+}  // namespace dfl
+
+extern "C" int dfl_drr_render(const dfl_drr_args* a, dfl_stream_t stream) {
+  DFL_REQUIRE(a != nullptr, "dfl_drr_render: null args");
+  DFL_REQUIRE(a->mu != nullptr && a->labels != nullptr && a->objects != nullptr && a->att != nullptr,
+              "dfl_drr_render: mu, labels, objects and att are required");
+  DFL_REQUIRE(a->nx >= 1 && a->ny >= 1 && a->nz >= 1 && a->H >= 1 && a->W >= 1 && a->views >= 1 && a->n_obj >= 1,
+              "dfl_drr_render: bad sizes (volume %d x %d x %d, detector %d x %d, views %d, objects %d)", a->nx, a->ny, a->nz, a->H, a->W,
+              a->views, a->n_obj);
+  DFL_REQUIRE((int64_t)a->nx * a->ny * a->nz < ((int64_t)1 << 31), "dfl_drr_render: a volume of %d x %d x %d exceeds 2^31 voxels", a->nx,
+              a->ny, a->nz);
+  DFL_REQUIRE(a->views <= 65535, "dfl_drr_render: at most 65535 views per call, got %d", a->views);
+  DFL_REQUIRE((int64_t)a->H * a->W < ((int64_t)1 << 31) && a->H <= 65535 * 4, "dfl_drr_render: a detector of %d x %d is too large", a->H, a->W);
+  DFL_REQUIRE(a->n_labels >= 1 && a->n_labels <= DFL_DRR_MAX_LABELS, "dfl_drr_render: n_labels must be 1..%d, got %d",
+              DFL_DRR_MAX_LABELS, a->n_labels);
+  DFL_REQUIRE(a->interp == DFL_DRR_EXACT || a->interp == DFL_DRR_TRILINEAR, "dfl_drr_render: unknown interp %d (0 exact, 1 trilinear)",
+              a->interp);
+  DFL_REQUIRE(a->mapping == 0 || a->mapping == 1, "dfl_drr_render: unknown mapping %d (0: 8 x 8 tiles, 1: 64 x 1 rows)", a->mapping);
+  DFL_REQUIRE(a->step_mm > 0.f && a->step_mm < __builtin_inff(), "dfl_drr_render: step_mm must be positive, got %g", (double)a->step_mm);
+  DFL_REQUIRE(a->interp == DFL_DRR_EXACT || (a->plen == nullptr && a->label_map == nullptr),
+              "dfl_drr_render: plen and label_map need the exact interpolation");
+  DFL_REQUIRE(a->min_len_mm >= 0.f, "dfl_drr_render: min_len_mm must not be negative, got %g", (double)a->min_len_mm);
+  dfl::DrrParams P;
+  P.mu = a->mu;
+  P.labels = a->labels;
+  P.objects = a->objects;
+  P.att = a->att;
+  P.plen = a->plen;
+  P.label_map = a->label_map;
+  for (int k = 0; k < 9; ++k) P.q[k] = a->qscale[k];
+  P.nx = a->nx;
+  P.ny = a->ny;
+  P.nz = a->nz;
+  P.H = a->H;
+  P.W = a->W;
+  P.n_obj = a->n_obj;
+  P.n_labels = a->n_labels;
+  P.step_mm = a->step_mm;
+  P.min_len_mm = a->min_len_mm;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool plen = a->plen != nullptr || a->label_map != nullptr;
+  const dim3 grid = a->mapping == 0 ? dim3((unsigned)dfl::ceil_div(a->W, 16), (unsigned)dfl::ceil_div(a->H, 16), (unsigned)a->views)
+                                    : dim3((unsigned)dfl::ceil_div(a->W, 64), (unsigned)dfl::ceil_div(a->H, 4), (unsigned)a->views);
+#define DRR_GO(INTERP, PLEN)                                               \
+  if (a->mapping == 0) dfl::drr_kernel<INTERP, PLEN, 0><<<grid, 256, 0, s>>>(P); \
+  else dfl::drr_kernel<INTERP, PLEN, 1><<<grid, 256, 0, s>>>(P)
+  if (a->interp == DFL_DRR_TRILINEAR) {
+    DRR_GO(DFL_DRR_TRILINEAR, false);
+  } else if (plen) {
+    DRR_GO(DFL_DRR_EXACT, true);
+  } else {
+    DRR_GO(DFL_DRR_EXACT, false);
+  }
+#undef DRR_GO
+  return dfl::check_launch("dfl_drr_render");
+}

@@ -981,6 +981,52 @@ typedef struct {
 int dfl_restore_labels(const dfl_restore_labels_args* a, dfl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Digitally reconstructed radiographs and 2D labels from the CT (csrc/drr.hip; DESIGN.md section 15 states the
+ * semantics, tests/drr_ref.py restates them in numpy float64).
+ *
+ * mu [nz][ny][nx] is the attenuation per mm and labels the 3D annotation (0..15), both in volume index order.  Voxel i
+ * occupies [i - 1/2, i + 1/2] on each index axis.  An object is a rigid pose and a label mask: the ray of output pixel
+ * (c, r) is o + t d, t >= 0, in that object's index coordinates, with d = M [c, r, 1]; it is clipped to the voxel box
+ * box_lo .. box_hi (inclusive voxel indices: [box_lo - 1/2, box_hi + 1/2]); a voxel counts when bit `label` of mask is
+ * set.  One unit of t is s = |qscale [c, r, 1]| mm.  A direction component that is exactly 0 has no crossings on its
+ * axis and the ray counts only if o lies in [box_lo - 1/2, box_hi + 1/2) there.
+ *
+ * interp DFL_DRR_EXACT: the radiological path.  att = sum over objects and admitted voxels of (length in the voxel) mu;
+ * plen[l] = the summed length in admitted voxels of label l; label_map = the lowest l >= 1 with the largest plen[l], or
+ * 0 when that length is below min_len_mm.
+ * interp DFL_DRR_TRILINEAR (att only): per object N = max(1, ceil(s (t1 - t0) / step_mm)) samples at
+ * t0 + (k + 1/2)(t1 - t0) / N of the trilinear interpolation of the masked volume (a corner voxel gives mu when its
+ * label is admitted, else 0; corner indices are clamped to the volume); att += s (t1 - t0) / N * their sum.
+ *
+ * One thread per ray and view, every object inside the thread; one launch.  Rays that miss every box write 0.
+ * mapping 0: a wave covers 8 x 8 pixels and a workgroup 16 x 16; 1: a wave covers 64 x 1 (tools/bench_drr.py compares).
+ * ------------------------------------------------------------------------------------------------------------ */
+#define DFL_DRR_EXACT 0
+#define DFL_DRR_TRILINEAR 1
+#define DFL_DRR_MAX_LABELS 16
+typedef struct {
+  float o[3];                     /* ray origin in index coordinates (x, y, z) */
+  float M[9];                     /* row-major: d = M [c, r, 1] */
+  int32_t box_lo[3], box_hi[3];   /* inclusive voxel box (x, y, z); box_hi < box_lo: the object is empty */
+  uint32_t mask;                  /* bit l: voxels labelled l belong to the object */
+} dfl_drr_object;
+
+typedef struct {
+  const float* mu;                /* [nz][ny][nx] */
+  const unsigned char* labels;    /* [nz][ny][nx] */
+  const dfl_drr_object* objects;  /* device, [views][n_obj] */
+  float* att;                     /* [views][H][W] */
+  float* plen;                    /* [views][n_labels][H][W], or NULL (exact only) */
+  unsigned char* label_map;       /* [views][H][W], or NULL (exact only) */
+  float qscale[9];                /* row-major */
+  int32_t nx, ny, nz, H, W, views, n_obj, n_labels;
+  int32_t interp, mapping;
+  float step_mm, min_len_mm;
+  int32_t reserved;
+} dfl_drr_args;
+int dfl_drr_render(const dfl_drr_args* a, dfl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Product arithmetic of the convolution / weight-gradient GEMMs (fast paths; odd channel counts always use fp32):
  *   0 "fp32"    v_mfma_f32_32x32x2_f32: fp32 products, fp32 accumulation.
  *   1 "bf16x3"  every fp32 operand value is split into hi + lo bf16 parts when it is staged in LDS and the product is

@@ -1,0 +1,306 @@
+"""dfl_amd.drr on the GPU (csrc/drr.hip) against tests/drr_ref.py, the numpy float64 restatement of the semantics.
+
+Bars: 8 x the floors of tests/golden/floors/drr.json -- the largest |float32 model - float64 model| on the same scenes
+(tests/drr_floor.py; both sides the model, never the kernel).  The factor covers FMA contraction and a different but
+legitimate summation order in the kernel.  Exact mode is compared with the tight-box model whether the kernel gets
+tight boxes or not: the two models agree to 1e-9 (tests/test_drr_cpu.py), five orders below the bars.
+
+Label map: a pixel is left out when the model's top length is within the plen bar of its runner-up or of min_len_mm
+(at most 2 % may be); every other pixel must match exactly.  Trilinear: a ray whose s (t1 - t0) / step lies within 1e-4
+of an integer in the model is left out (its sample count could differ by one; at most 0.5 % may be).
+"""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import ROOT
+
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+sys.path.insert(0, os.path.join(ROOT, 'examples'))
+import drr_floor as FL  # noqa: E402
+import drr_ref as D  # noqa: E402
+import dfl_amd  # noqa: E402,F401
+from dfl_amd import _native as nat, drr, h5lite, png, preprocess as pp  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+DEV = torch.device('cuda', 0)
+_VOLS = {}
+
+
+def _volume(kind):
+    if kind not in _VOLS:
+        S = D.scene(kind)
+        _VOLS[kind] = drr.Volume(torch.from_numpy(S['mu'].copy()).to(DEV), torch.from_numpy(S['lab'].copy()).to(DEV))
+    return _VOLS[kind]
+
+
+def _objects(S, extra=()):
+    return [[drr.Obj(A, m) for A, m in zip(view, D.MASKS)] + [drr.Obj(view[0], m) for m in extra] for view in D.scene_views(S)]
+
+
+def _grid(S):
+    return drr.Grid(S['Q'], S['rows'], S['cols'])
+
+
+@pytest.mark.parametrize('tight', [True, False])
+@pytest.mark.parametrize('interp', ['exact', 'trilinear'])
+@pytest.mark.parametrize('kind', ['tilted', 'aligned'])
+def test_scenes_match_the_model(kind, interp, tight):
+    S = D.scene(kind)
+    vol, grid, objs = _volume(kind), _grid(S), _objects(S)
+    assert vol.n_labels == D.N_LABELS
+    recs = drr.pack_objects(vol, objs, grid, interp, tight)
+    for view in (0, 1):                                       # the records the kernel gets are the records the model gets
+        want = D.pack(D.scene_views(S)[view], D.MASKS, S['Q'], S['lab'], tight, interp)
+        assert recs[view].tobytes() == want.tobytes()
+    att, plen, lab = drr.render(vol, objs, grid, interp=interp, step_mm=D.STEP_MM, want_plen=True, tight_boxes=tight)
+    assert att.dtype == torch.float32 and tuple(att.shape) == (2, S['rows'], S['cols']) and att.is_cuda
+    att_bar, plen_bar = FL.bars(kind, interp)
+    att = att.cpu().numpy().astype(np.float64)
+    for view in (0, 1):
+        m_att, m_plen, frac, _ = D.model(kind, interp, view, tight=tight if interp == 'trilinear' else True)
+        miss = np.isnan(frac).all(0)
+        assert miss.mean() >= (0.2 if tight else 0.05) and not att[view][miss].any()     # rays that miss every box: exactly 0
+        if interp == 'trilinear':
+            assert plen is None and lab is None
+            out = D.near_integer(frac)
+            err = float(np.abs(att[view] - m_att)[~out].max())
+            print('drr %s trilinear view %d tight %d: att max |error| %.3e (bar %.3e), %.2f %% of rays left out'
+                  % (kind, view, tight, err, att_bar, 100 * out.mean()))
+            assert out.mean() <= 0.005
+            assert err <= att_bar, err
+            continue
+        assert plen.dtype == torch.float32 and tuple(plen.shape) == (2, D.N_LABELS, S['rows'], S['cols'])
+        assert lab.dtype == torch.uint8 and tuple(lab.shape) == (2, S['rows'], S['cols'])
+        p = plen[view].cpu().numpy().astype(np.float64)
+        err_a, err_p = float(np.abs(att[view] - m_att).max()), float(np.abs(p - m_plen).max())
+        left = D.near_tie(m_plen, plen_bar)
+        wrong = int(((lab[view].cpu().numpy() != D.label_map(m_plen)) & ~left).sum())
+        print('drr %s exact view %d tight %d: att max |error| %.3e (bar %.3e), plen %.3e mm (bar %.3e), %.2f %% of pixels left '
+              'out of the label comparison, %d wrong' % (kind, view, tight, err_a, att_bar, err_p, plen_bar, 100 * left.mean(), wrong))
+        nothing = m_plen.sum(0) == 0
+        assert not p[:, nothing].any() and not att[view][nothing].any() and not lab[view].cpu().numpy()[nothing].any()
+        assert err_a <= att_bar, err_a
+        assert err_p <= plen_bar, err_p
+        assert left.mean() <= 0.02
+        assert wrong == 0
+
+
+@pytest.mark.parametrize('kind', ['tilted', 'aligned'])
+def test_outputs_on_request_and_the_row_mapping(kind):
+    """att alone, labels alone and the 64 x 1 mapping of tools/bench_drr.py give the same bits as the full call; a single
+    view without a view axis is view 0; min_len_mm moves the threshold."""
+    S = D.scene(kind)
+    vol, grid, objs = _volume(kind), _grid(S), _objects(S)
+    att, plen, lab = drr.render(vol, objs, grid, want_plen=True)
+    a1, p1, l1 = drr.render(vol, objs, grid, want_plen=False, want_labels=False)
+    assert p1 is None and l1 is None and torch.equal(a1, att)
+    a2, p2, l2 = drr.render(vol, objs, grid, want_plen=True, mapping=1)
+    assert torch.equal(a2, att) and torch.equal(p2, plen) and torch.equal(l2, lab)
+    a3 = drr.render(vol, objs, grid, interp='trilinear', mapping=1)[0]
+    assert torch.equal(a3, drr.render(vol, objs, grid, interp='trilinear')[0])
+    a4, p4, l4 = drr.render(vol, objs[0], grid, want_plen=True)
+    assert a4.dim() == 2 and torch.equal(a4, att[0]) and torch.equal(p4, plen[0]) and torch.equal(l4, lab[0])
+    l5 = drr.render(vol, objs, grid, min_len_mm=5.0)[2]
+    top = plen[:, 1:].max(1).values
+    assert torch.equal(l5 != 0, top >= 5.0) and torch.equal(l5[l5 != 0], lab[l5 != 0])
+
+
+@pytest.mark.parametrize('tight', [True, False])
+@pytest.mark.parametrize('interp', ['exact', 'trilinear'])
+def test_an_object_that_matches_no_voxel_changes_nothing(interp, tight):
+    S = D.scene('tilted')
+    vol, grid = _volume('tilted'), _grid(S)
+    assert vol.box(1 << 9) == ((0, 0, 0), (-1, -1, -1)) and vol.box(0x20) == D.label_box(S['lab'], 0x20)
+    base = drr.render(vol, _objects(S), grid, interp=interp, want_plen=True, tight_boxes=tight)
+    more = drr.render(vol, _objects(S, extra=(1 << 9, 1 << 15)), grid, interp=interp, want_plen=True, tight_boxes=tight)
+    for a, b in zip(base, more):
+        assert (a is None and b is None) or torch.equal(a, b)
+
+
+def test_soft_tissue_object_and_hu_to_mu():
+    """bones_only=False adds the pelvis pose with bit 0: every voxel of the volume is then counted once."""
+    S = D.scene('tilted')
+    hu = torch.from_numpy(S['hu'].copy()).to(DEV)
+    mu = dfl_amd.hu_to_mu(hu)
+    assert mu.dtype == torch.float32 and float((mu.cpu() - torch.from_numpy(S['mu'])).abs().max()) <= 1e-8
+    assert float(drr.hu_to_mu(hu.to(torch.int16).to(torch.float32), mu_water=0.019).max()) < float(mu.max())
+    vol = _volume('tilted')
+    poses = dict(zip(drr.POSES, S['poses']))
+    obs = drr.default_objects(S['E'], poses, S['I2P'], bones_only=False)
+    att, plen, lab = drr.render(vol, obs, _grid(S), want_plen=True)
+    recs = D.pack([o.c2i for o in obs], [o.mask for o in obs], S['Q'], S['lab'])
+    m_att, m_plen, _ = D.render(S['mu'], S['lab'], recs, S['Q'].astype(np.float32), S['rows'], S['cols'])
+    # four objects, one of them the whole volume: the same rule as the committed floors, worked out for this case
+    f_att, f_plen, _ = D.render(S['mu'], S['lab'], recs, S['Q'].astype(np.float32), S['rows'], S['cols'], dtype=np.float32)
+    att_bar, plen_bar = FL.BAR_FACTOR * float(np.abs(f_att - m_att).max()), FL.BAR_FACTOR * float(np.abs(f_plen - m_plen).max())
+    err_a, err_p = float(np.abs(att.cpu().numpy() - m_att).max()), float(np.abs(plen.cpu().numpy() - m_plen).max())
+    print('drr with soft tissue: att max |error| %.3e (bar %.3e), plen %.3e mm (bar %.3e)' % (err_a, att_bar, err_p, plen_bar))
+    assert err_a <= att_bar and err_p <= plen_bar
+    assert float(plen[0].max()) > 10 and not (lab.cpu().numpy() == 0)[m_plen[1:].max(0) >= 1.0 + plen_bar].any()
+    with pytest.raises(nat.DflError, match='15'):
+        bad = torch.from_numpy(S['lab'].copy()).to(DEV)
+        bad[3, 4, 5] = 16
+        drr.Volume(vol.mu, bad)
+    with pytest.raises(nat.DflError, match='dtype'):
+        drr.Volume(vol.mu.double(), vol.labels)
+    with pytest.raises(nat.DflError, match='step_mm'):
+        drr.render(vol, obs, _grid(S), interp='trilinear', step_mm=0.0)
+    with pytest.raises(nat.DflError, match='interp'):
+        drr.render(vol, obs, _grid(S), interp='cubic')
+
+
+def test_published_detector_size_on_a_lattice():
+    """1536 x 1536 at factor 1 over a 96 x 112 x 128 volume: grid and index arithmetic at size, on a fixed 15 x 15 lattice
+    of pixels.  Bars: 8 x the larger of the committed floor of the tilted scene and the float32-model floor on this
+    lattice (the rays start as far away, 800 mm, so t has the same ulp; they cross more planes)."""
+    lab, hu = D.phantom(96, 112, 128, scale=2.4)
+    mu = D.hu_to_mu(hu)
+    I2P = np.eye(4)
+    I2P[:3, :3] = np.diag([1.5, 1.4, 1.6])
+    I2P[:3, 3] = [-40.0, 11.5, 100.25]
+    f = 1000.0 / 0.194
+    K = np.array([[-f, 0, 768.3], [0, -f, 770.6], [0, 0, 1]])
+    ctr = (I2P @ np.array([47.5, 55.5, 63.5, 1]))[:3]
+    c2is = []
+    for R, shift in ((D.rot(0, 0.5) @ D.rot(2, 0.3), (3, -4, -800)), (D.rot(0, 0.6) @ D.rot(2, 0.25), (6, -2, -790)),
+                     (D.rot(0, 0.4) @ D.rot(1, 0.2), (-1, -6, -810))):
+        V2C = np.eye(4)
+        V2C[:3, :3] = R[:3, :3]
+        V2C[:3, 3] = np.array(shift) - R[:3, :3] @ ctr
+        c2is.append(np.linalg.inv(I2P) @ np.linalg.inv(V2C))              # C2I = inv(I2P) P inv(E), and V2C = E inv(P)
+    Q = -np.linalg.inv(K)
+    vol = drr.Volume(torch.from_numpy(mu).to(DEV), torch.from_numpy(lab).to(DEV))
+    grid = drr.Grid(Q, 1536, 1536)
+    objs = [drr.Obj(A, m) for A, m in zip(c2is, D.MASKS)]
+    att, plen, labels = drr.render(vol, objs, grid, want_plen=True)
+    assert tuple(att.shape) == (1536, 1536) and tuple(plen.shape) == (7, 1536, 1536)
+    rr, cc = np.meshgrid(68 + 100 * np.arange(15), 68 + 100 * np.arange(15), indexing='ij')
+    rr, cc = rr.reshape(-1), cc.reshape(-1)
+    recs = D.pack(c2is, D.MASKS, Q, lab)
+    assert recs.tobytes() == drr.pack_objects(vol, objs, grid)[0].tobytes()
+    m_att, m_plen, _ = D.render(mu, lab, recs, Q.astype(np.float32), 1536, 1536, pixels=(rr, cc))
+    f_att, f_plen, _ = D.render(mu, lab, recs, Q.astype(np.float32), 1536, 1536, pixels=(rr, cc), dtype=np.float32)
+    t_att, t_plen = FL.bars('tilted', 'exact')
+    att_bar = max(t_att, FL.BAR_FACTOR * float(np.abs(f_att - m_att).max()))
+    plen_bar = max(t_plen, FL.BAR_FACTOR * float(np.abs(f_plen - m_plen).max()))
+    ri, ci = torch.from_numpy(rr).to(DEV), torch.from_numpy(cc).to(DEV)
+    err_a = float(np.abs(att[ri, ci].cpu().numpy() - m_att).max())
+    err_p = float(np.abs(plen[:, ri, ci].cpu().numpy() - m_plen).max())
+    left = D.near_tie(m_plen, plen_bar)
+    hit = int((m_plen[1:].max(0) >= 1.0).sum())
+    print('drr 1536 x 1536 lattice: att max |error| %.3e (bar %.3e), plen %.3e mm (bar %.3e), %d of 225 rays labelled, %d left out'
+          % (err_a, att_bar, err_p, plen_bar, hit, int(left.sum())))
+    assert hit >= 40 and m_plen.max() > 40
+    assert err_a <= att_bar and err_p <= plen_bar
+    assert np.array_equal(labels[ri, ci].cpu().numpy()[~left], D.label_map(m_plen)[~left]) and left.sum() <= 4
+    # the last row and column are rays of their own, not copies or leftovers
+    edge = (np.array([1535, 1535, 0, 1535]), np.array([1535, 0, 1535, 700]))
+    e_att = D.render(mu, lab, recs, Q.astype(np.float32), 1536, 1536, pixels=edge)[0]
+    assert float(np.abs(att[torch.from_numpy(edge[0]).to(DEV), torch.from_numpy(edge[1]).to(DEV)].cpu().numpy() - e_att).max()) <= att_bar
+
+
+# ---- the example, end to end -------------------------------------------------------------------------------------------
+SPEC, CROP = '17-1882', 2
+_FILE = {}
+
+
+def _file_model():
+    """(poses, att, plen) of the container's projection: the tilted scene with its three poses in reverse order, so that
+    every one of the six labels is the longest on some pixels (16 to 411 of them; labels 5 and 6 on 16 and 92).  Under
+    the scene's own order the femurs project onto the thicker pelvis ellipsoids and label 6 wins nowhere."""
+    if not _FILE:
+        S = D.scene('tilted')
+        poses = S['poses'][::-1]
+        recs = D.pack([D.c2i(S['I2P'], P, S['E']) for P in poses], D.MASKS, S['Q'], S['lab'])
+        att, plen, _ = D.render(S['mu'], S['lab'], recs, S['Q'].astype(np.float32), S['rows'], S['cols'])
+        _FILE['m'] = (poses, att, plen)
+    return _FILE['m']
+
+
+def _write_container(path, rot180):
+    """The tilted scene as a full-resolution file: vol, vol-seg, vol-landmarks, proj-params and one projection whose
+    image, gt-seg and gt-landmarks are the model's own rendering on the full detector grid."""
+    S = D.scene('tilted')
+    poses, att, plen = _file_model()
+    names = pp.LAND_ORDER[:6]
+    pts = np.array([(S['I2P'] @ np.array(c + (1.0,)))[:3] for c, _, _ in D.ELLIPSOIDS]).astype(np.float32)
+    cam = (S['E'] @ np.linalg.inv(poses[0])) @ np.concatenate([pts.astype(np.float64), np.ones((6, 1))], 1).T
+    uv = S['K'] @ cam[:3]
+    uv = (uv / uv[2])[:2]                                     # the reference's intrinsic * land_3d, on the detector grid
+    with h5lite.File(path, 'w') as f:
+        f['proj-params/intrinsic'] = S['K']
+        f['proj-params/extrinsic'] = S['E']
+        f['proj-params/num-rows'] = np.int64(S['rows'])
+        f['proj-params/num-cols'] = np.int64(S['cols'])
+        for grp, px in ((SPEC + '/vol/', S['hu']), (SPEC + '/vol-seg/image/', S['lab'])):
+            f[grp + 'pixels'] = px
+            f[grp + 'dir-mat'] = np.eye(3)
+            f[grp + 'spacing'] = np.array([0.8, 0.75, 1.1])
+            f[grp + 'origin'] = S['I2P'][:3, 3]
+        for l, name in enumerate(names):
+            f[SPEC + '/vol-landmarks/' + name] = pts[l]
+        pfx = SPEC + '/projections/000/'
+        f[pfx + 'image/pixels'] = (1000.0 * np.exp(-att)).astype(np.float32)
+        f[pfx + 'gt-seg/pixels'] = D.label_map(plen)
+        for l, name in enumerate(names):
+            f[pfx + 'gt-landmarks/' + name] = uv[:, l].astype(np.float32)
+        for k, P in zip(drr.POSES, poses):
+            f[pfx + 'gt-poses/' + k] = P
+        f[pfx + 'rot-180-for-up'] = np.int64(rot180)
+    return uv
+
+
+@pytest.mark.parametrize('rot180', [0, 1])
+def test_example_end_to_end(tmp_path, capsys, rot180):
+    import full_res_drr as cli
+    S = D.scene('tilted')
+    path = os.path.join(str(tmp_path), 'full.h5')
+    uv = _write_container(path, rot180)
+    prefix = os.path.join(str(tmp_path), 'view')
+    assert cli.main([path, SPEC, '0', '--out', prefix, '--crop', str(CROP), '--ds-factor', '1', '--bones-only', '--compare']) == 0
+    out = capsys.readouterr().out
+    H, W = pp.out_size(S['rows'], S['cols'], CROP, 1)
+    for name in ('view_drr.png', 'view_labels.png', 'view.npz'):
+        assert os.path.getsize(os.path.join(str(tmp_path), name)) > 0
+    z = np.load(prefix + '.npz')
+    assert z['att'].shape == (H, W) and z['att'].dtype == np.float32 and z['labels'].shape == (H, W) and z['labels'].dtype == np.uint8
+    assert z['lands'].shape == (2, 14) and np.isfinite(z['lands'][:, :6]).all() and np.isinf(z['lands'][:, 6:]).all()
+    assert png.read(prefix + '_drr.png').shape == (H, W, 3) and png.read(prefix + '_labels.png').shape == (H, W, 3)
+    # against the model on the example's own records (G is folded into M before the rounding to fp32) ...
+    from make_full_res_overlays import Source
+    src = Source(path)
+    geom = drr.geometry(src, SPEC, 0, crop=CROP, factor=1)
+    src.close()
+    assert geom.size == (H, W) and (geom.G[0, 0] < 0) == bool(rot180)
+    recs = D.pack([o.c2i for o in geom.objects], [o.mask for o in geom.objects], geom.grid.Q, S['lab'])
+    m_att, m_plen, _ = D.render(S['mu'], S['lab'], recs, geom.grid.Q.astype(np.float32), H, W)
+    att_bar, plen_bar = FL.bars('tilted', 'exact')
+    assert float(np.abs(z['att'] - m_att).max()) <= att_bar
+    assert np.array_equal(z['labels'], D.label_map(m_plen)) or \
+        (z['labels'] != D.label_map(m_plen))[~D.near_tie(m_plen, plen_bar)].sum() == 0
+    # ... which is the model's full detector grid, cropped and turned (1e-4: only the matrices' rounding differs)
+    _, att, plen = _file_model()
+    want = att[CROP:-CROP, CROP:-CROP]
+    want = want[::-1, ::-1] if rot180 else want
+    assert float(np.abs(m_att - want).max()) <= 1e-4
+    np.testing.assert_allclose(z['lands'][:, :6], pp.map_lands(uv[None], [rot180], S['rows'], S['cols'], CROP, 1)[0], atol=1e-3)
+    lines = out.strip().split('\n')
+    assert lines[0].startswith('wrote ') and '%d x %d' % (H, W) in lines[0]
+    vals = {ln.split(' = ')[0]: float(ln.split(' = ')[1].split()[0]) for ln in lines[1:]}
+    print(out)
+    assert vals['NCC(DRR, projection)'] >= 0.999
+    present = [l for l in range(1, 7) if (D.label_map(plen)[CROP:-CROP, CROP:-CROP] == l).any()]
+    assert present == [1, 2, 3, 4, 5, 6]
+    for l in present:
+        assert vals['Dice of label %d' % l] >= 0.99, (l, vals)
+    assert vals['largest landmark distance'] < 1e-3
+    # trilinear, reduced by 2, with the soft tissue: the three files again
+    assert cli.main([path, SPEC, '0', '--out', prefix + '2', '--crop', '0', '--ds-factor', '2', '--interp', 'trilinear', '--step', '0.25']) == 0
+    z2 = np.load(prefix + '2.npz')
+    assert z2['att'].shape == pp.out_size(S['rows'], S['cols'], 0, 2) == z2['labels'].shape and float(z2['att'].max()) > 1.0
+    assert os.path.getsize(prefix + '2_drr.png') > 0 and os.path.getsize(prefix + '2_labels.png') > 0
