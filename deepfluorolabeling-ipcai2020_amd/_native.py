@@ -305,6 +305,18 @@ class DrrArgs(C.Structure):
                 ('interp', i32), ('mapping', i32), ('step_mm', f32), ('min_len_mm', f32), ('reserved', i32)]
 
 
+SIM_TOTALS = 5                                                             # include/dfl_hip.h: DFL_SIM_TOTALS
+
+
+class SimPrepareArgs(C.Structure):
+    _fields_ = [('fixed', fp), ('mask', fp), ('fx', fp), ('fy', fp), ('counted', fp), ('totals', fp), ('H', i32), ('W', i32)]
+
+
+class SimGradnccArgs(C.Structure):
+    _fields_ = [('moving', fp), ('fx', fp), ('fy', fp), ('counted', fp), ('totals', fp), ('scratch', fp), ('cost', fp),
+                ('scratch_doubles', i64), ('V', i32), ('H', i32), ('W', i32), ('reserved', i32)]
+
+
 class UpsampleArgs(C.Structure):
     _fields_ = [('x', fp), ('y', fp), ('N', i32), ('H', i32), ('W', i32), ('C', i32), ('ldx', i32), ('ldy', i32),
                 ('bf16', i32), ('accumulate', i32)]
@@ -341,7 +353,7 @@ _SIZEOF_ORDER = [ConvArgs, WgradArgs, PackJob, BnFinalizeArgs, ColstatsArgs, BnB
                  AffineCopyArgs, PoolArgs, HeadFwdArgs, HeadBwdArgs, LossArgs, EnsembleArgs, Op, ReduceJob, PrepArgs, EstLandsArgs,
                  UpsampleArgs, AugmentArgs, AugmentItem, OverlayArgs, ResamplePlan, ResampleArgs, FullresArgs, MeshMcArgs, MeshDecodeArgs,
                  MeshTopoArgs, MeshCsrArgs, MeshSmoothArgs, MeshXformArgs, MeshNormalsArgs, PreprocProjsArgs, PreprocSegsArgs,
-                 RestoreLabelsArgs, DrrObject, DrrArgs, OptimPackArgs]
+                 RestoreLabelsArgs, SimPrepareArgs, SimGradnccArgs, DrrObject, DrrArgs, OptimPackArgs]
 
 EXPORTS = ['dfl_version', 'dfl_last_error', 'dfl_sizeof', 'dfl_conv2d', 'dfl_conv_grid_m', 'dfl_conv2d_wgrad',
            'dfl_wgrad_suggest_splits', 'dfl_sum_partials', 'dfl_pack_weights', 'dfl_bn_finalize',
@@ -359,7 +371,8 @@ EXPORTS = ['dfl_version', 'dfl_last_error', 'dfl_sizeof', 'dfl_conv2d', 'dfl_con
            'dfl_augment_scratch_bytes', 'dfl_overlay_batch', 'dfl_resample_bilinear_u8', 'dfl_fullres_overlay',
            'dfl_mesh_mc_count', 'dfl_mesh_mc_emit', 'dfl_mesh_decode', 'dfl_mesh_topology', 'dfl_mesh_csr', 'dfl_mesh_smooth',
            'dfl_mesh_transform', 'dfl_mesh_normals', 'dfl_adam_step', 'dfl_rmsprop_step', 'dfl_optim_pack_tiled',
-           'dfl_preproc_projs', 'dfl_preproc_segs', 'dfl_restore_labels', 'dfl_drr_render']
+           'dfl_preproc_projs', 'dfl_preproc_segs', 'dfl_restore_labels', 'dfl_drr_render', 'dfl_sim_prepare', 'dfl_sim_gradncc',
+           'dfl_sim_scratch_doubles']
 
 
 class DflError(RuntimeError):
@@ -405,11 +418,13 @@ def lib():
     L.dfl_overlay_batch.argtypes = [fp, fp]
     L.dfl_resample_bilinear_u8.argtypes = [fp, fp]
     L.dfl_fullres_overlay.argtypes = [fp, fp]
-    for fn in ('dfl_preproc_projs', 'dfl_preproc_segs', 'dfl_restore_labels', 'dfl_drr_render'):
+    for fn in ('dfl_preproc_projs', 'dfl_preproc_segs', 'dfl_restore_labels', 'dfl_drr_render', 'dfl_sim_prepare', 'dfl_sim_gradncc'):
         getattr(L, fn).argtypes = [fp, fp]
     for fn in ('dfl_mesh_mc_count', 'dfl_mesh_mc_emit', 'dfl_mesh_decode', 'dfl_mesh_topology', 'dfl_mesh_csr',
                'dfl_mesh_smooth', 'dfl_mesh_transform', 'dfl_mesh_normals'):
         getattr(L, fn).argtypes = [fp, fp]
+    L.dfl_sim_scratch_doubles.restype = i64
+    L.dfl_sim_scratch_doubles.argtypes = [i32, i32, i32]
     L.dfl_set_math_mode.argtypes = [i32]
     L.dfl_hard_dice.argtypes = [fp, fp, i64, i32, i32, fp, fp, fp]
     L.dfl_sgd_step.argtypes = [fp, fp, fp, i64, f32, f32, f32, f32, i32, i32, fp]

@@ -1,0 +1,197 @@
+// Batched gradient-NCC between V rendered views and one fixed image: the similarity of dfl_amd.register.
+// Contract: include/dfl_hip.h (dfl_sim_prepare_args, dfl_sim_gradncc_args); the semantics are stated in DESIGN.md
+// section 16 and restated in numpy float64 by tests/reg_ref.py.
+//
+// dfl_sim_prepare (once per fixed image): one workgroup writes the Sobel planes of the fixed image, the counted-pixel
+// plane and the five fixed-only totals.  dfl_sim_gradncc (once per generation): a workgroup owns SIM_ROWS interior rows
+// of one view (grid = bands x views); thread t takes the pixels t, t + 256, ... of its band in that order, reads the
+// eight neighbours of the moving image straight from global memory (consecutive lanes read consecutive columns; a
+// batch of 32 views of 180 x 180 is 4 MB and stays in L2, and a row is re-read by its two neighbouring rows out of
+// the vector L1) and adds six sums in float64.  Wave shuffles, then LDS across the four waves, then ONE record of six
+// doubles per workgroup with plain stores; sim_finish_kernel adds a view's records in index order and writes its cost.
+// No atomics: the bits of a view's cost depend on that view's pixels and on H and W only.
+#include "common.h"
+
+namespace dfl {
+
+constexpr int SIM_ROWS = 8;          // interior rows per workgroup
+constexpr int SIM_THREADS = 256;
+constexpr int SIM_SUMS = 6;          // sum mx, mx^2, mx fx, my, my^2, my fy
+
+// Sobel gradients of p at interior pixel (r, c): each sum left to right, so the fixed and the moving image share bits
+__device__ __forceinline__ void sim_sobel(const float* __restrict__ p, int W, int r, int c, float& gx, float& gy) {
+  const float* up = p + (size_t)(r - 1) * W + c;
+  const float* mid = up + W;
+  const float* dn = mid + W;
+  const float a = up[-1], b = up[0], cc = up[1], d = mid[-1], f = mid[1], g = dn[-1], h = dn[0], i = dn[1];
+  gx = ((cc + 2.f * f) + i) - ((a + 2.f * d) + g);
+  gy = ((g + 2.f * h) + i) - ((a + 2.f * b) + cc);
+}
+
+__device__ __forceinline__ double sim_wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+
+// N sums of a workgroup of SIM_THREADS threads -> thread 0's v[]; lds holds N * 4 doubles
+template <int N>
+__device__ __forceinline__ void sim_block_sum(double (&v)[N], double* lds) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < N; ++k) v[k] = sim_wave_sum(v[k]);
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) lds[wave * N + k] = v[k];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = ((lds[k] + lds[N + k]) + lds[2 * N + k]) + lds[3 * N + k];
+  }
+}
+
+__global__ __launch_bounds__(SIM_THREADS) void sim_prepare_kernel(const float* __restrict__ fixed, const unsigned char* __restrict__ mask,
+                                                                  float* __restrict__ fx, float* __restrict__ fy,
+                                                                  unsigned char* __restrict__ counted, double* __restrict__ totals,
+                                                                  int H, int W) {
+  __shared__ double lds[5 * 4];
+  double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  const int64_t n = (int64_t)H * W;
+  for (int64_t p = threadIdx.x; p < n; p += SIM_THREADS) {
+    const int r = (int)(p / W), c = (int)(p - (int64_t)r * W);
+    float gx = 0.f, gy = 0.f;
+    unsigned char on = 0;
+    if (r >= 1 && r <= H - 2 && c >= 1 && c <= W - 2) {
+      sim_sobel(fixed, W, r, c, gx, gy);
+      on = 1;
+      if (mask != nullptr) {
+#pragma unroll
+        for (int dr = -1; dr <= 1; ++dr)
+#pragma unroll
+          for (int dc = -1; dc <= 1; ++dc)
+            if (mask[(size_t)(r + dr) * W + (c + dc)] == 0) on = 0;
+      }
+    }
+    fx[p] = gx;
+    fy[p] = gy;
+    counted[p] = on;
+    if (on) {
+      const double x = (double)gx, y = (double)gy;
+      s[0] += 1.0;
+      s[1] += x;
+      s[2] += x * x;
+      s[3] += y;
+      s[4] += y * y;
+    }
+  }
+  sim_block_sum<5>(s, lds);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < 5; ++k) totals[k] = s[k];
+  }
+}
+
+__global__ __launch_bounds__(SIM_THREADS) void sim_gradncc_kernel(const float* __restrict__ moving, const float* __restrict__ fx,
+                                                                  const float* __restrict__ fy, const unsigned char* __restrict__ counted,
+                                                                  double* __restrict__ scratch, int H, int W) {
+  __shared__ double lds[SIM_SUMS * 4];
+  const int band = blockIdx.x, view = blockIdx.y;
+  const int r0 = 1 + band * SIM_ROWS;                                   // first interior row of the band
+  const int rows = min(SIM_ROWS, H - 1 - r0);                           // interior rows are 1 .. H - 2
+  const int wi = W - 2;
+  const float* img = moving + (size_t)view * H * W;
+  double s[SIM_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int p = threadIdx.x; p < rows * wi; p += SIM_THREADS) {
+    const int r = r0 + p / wi, c = 1 + p % wi;
+    const size_t at = (size_t)r * W + c;
+    if (counted[at]) {
+      float gx, gy;
+      sim_sobel(img, W, r, c, gx, gy);
+      const double mx = (double)gx, my = (double)gy;
+      s[0] += mx;
+      s[1] += mx * mx;
+      s[2] += mx * (double)fx[at];
+      s[3] += my;
+      s[4] += my * my;
+      s[5] += my * (double)fy[at];
+    }
+  }
+  sim_block_sum<SIM_SUMS>(s, lds);
+  if (threadIdx.x == 0) {
+    double* rec = scratch + ((size_t)view * gridDim.x + band) * SIM_SUMS;
+#pragma unroll
+    for (int k = 0; k < SIM_SUMS; ++k) rec[k] = s[k];
+  }
+}
+
+// A variance is 0 when it is at most 2^-40 of the sum of squares: below that the one-pass form cannot tell
+__device__ __forceinline__ double sim_ncc(double n, double sa, double saa, double sb, double sbb, double sab) {
+  const double va = saa - sa * sa / n, vb = sbb - sb * sb / n;
+  const double eps = 9.094947017729282e-13;                             // 2^-40
+  if (!(va > eps * saa) || !(vb > eps * sbb)) return 0.0;
+  return (sab - sa * sb / n) / sqrt(va * vb);
+}
+
+// One wave per view: lanes 0..5 add one of the six sums each over the view's records, in index order
+__global__ __launch_bounds__(64) void sim_finish_kernel(const double* __restrict__ scratch, const double* __restrict__ totals,
+                                                        double* __restrict__ cost, int bands) {
+  __shared__ double m[SIM_SUMS];
+  const int view = blockIdx.x;
+  if (threadIdx.x < SIM_SUMS) {
+    const double* rec = scratch + (size_t)view * bands * SIM_SUMS + threadIdx.x;
+    double acc = 0.0;
+    for (int b = 0; b < bands; ++b) acc += rec[(size_t)b * SIM_SUMS];
+    m[threadIdx.x] = acc;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double n = totals[0];
+    double c = 1.0;
+    if (n >= 1.0)
+      c = 1.0 - 0.5 * (sim_ncc(n, m[0], m[1], totals[1], totals[2], m[2]) + sim_ncc(n, m[3], m[4], totals[3], totals[4], m[5]));
+    cost[view] = c;
+  }
+}
+
+inline int sim_bands(int H) { return (int)ceil_div(H - 2, SIM_ROWS); }
+
+}  // namespace dfl
+
+extern "C" int64_t dfl_sim_scratch_doubles(int32_t V, int32_t H, int32_t W) {
+  if (V < 1 || V > 65535 || H < 3 || W < 3 || (int64_t)H * W >= ((int64_t)1 << 31)) {
+    dfl::set_error("dfl_sim_scratch_doubles: bad sizes (views %d of 1..65535, image %d x %d of at least 3 x 3)", V, H, W);
+    return DFL_ERR_INVALID_ARG;
+  }
+  return (int64_t)V * dfl::sim_bands(H) * dfl::SIM_SUMS;
+}
+
+extern "C" int dfl_sim_prepare(const dfl_sim_prepare_args* a, dfl_stream_t stream) {
+  DFL_REQUIRE(a != nullptr, "dfl_sim_prepare: null args");
+  DFL_REQUIRE(a->fixed != nullptr && a->fx != nullptr && a->fy != nullptr && a->counted != nullptr && a->totals != nullptr,
+              "dfl_sim_prepare: fixed, fx, fy, counted and totals are required");
+  DFL_REQUIRE(a->H >= 3 && a->W >= 3, "dfl_sim_prepare: an image of %d x %d (at least 3 x 3)", a->H, a->W);
+  DFL_REQUIRE((int64_t)a->H * a->W < ((int64_t)1 << 31), "dfl_sim_prepare: an image of %d x %d is too large", a->H, a->W);
+  dfl::sim_prepare_kernel<<<1, dfl::SIM_THREADS, 0, static_cast<hipStream_t>(stream)>>>(a->fixed, a->mask, a->fx, a->fy, a->counted,
+                                                                                          a->totals, a->H, a->W);
+  return dfl::check_launch("dfl_sim_prepare");
+}
+
+extern "C" int dfl_sim_gradncc(const dfl_sim_gradncc_args* a, dfl_stream_t stream) {
+  DFL_REQUIRE(a != nullptr, "dfl_sim_gradncc: null args");
+  DFL_REQUIRE(a->moving != nullptr && a->fx != nullptr && a->fy != nullptr && a->counted != nullptr && a->totals != nullptr &&
+                  a->scratch != nullptr && a->cost != nullptr,
+              "dfl_sim_gradncc: moving, fx, fy, counted, totals, scratch and cost are required");
+  DFL_REQUIRE(a->H >= 3 && a->W >= 3, "dfl_sim_gradncc: an image of %d x %d (at least 3 x 3)", a->H, a->W);
+  DFL_REQUIRE((int64_t)a->H * a->W < ((int64_t)1 << 31), "dfl_sim_gradncc: an image of %d x %d is too large", a->H, a->W);
+  DFL_REQUIRE(a->V >= 1 && a->V <= 65535, "dfl_sim_gradncc: 1..65535 views per call, got %d", a->V);
+  const int bands = dfl::sim_bands(a->H);
+  const int64_t need = (int64_t)a->V * bands * dfl::SIM_SUMS;
+  DFL_REQUIRE(a->scratch_doubles >= need, "dfl_sim_gradncc: a scratch of %lld doubles, %lld are needed (dfl_sim_scratch_doubles)",
+              (long long)a->scratch_doubles, (long long)need);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  dfl::sim_gradncc_kernel<<<dim3((unsigned)bands, (unsigned)a->V), dfl::SIM_THREADS, 0, s>>>(a->moving, a->fx, a->fy, a->counted,
+                                                                                               a->scratch, a->H, a->W);
+  dfl::sim_finish_kernel<<<(unsigned)a->V, 64, 0, s>>>(a->scratch, a->totals, a->cost, bands);
+  return dfl::check_launch("dfl_sim_gradncc");
+}

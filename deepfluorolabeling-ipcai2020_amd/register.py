@@ -1,0 +1,446 @@
+"""2D/3D registration of the CT to one projection: a start pose from 2D landmarks (pnp), then a CMA-ES over six pose
+parameters whose cost is the gradient-NCC between rendered DRRs and the fixed image.
+
+The geometry is float64 numpy on the host, as in dfl_amd.drr; the pixels stay on the device.  One generation of the
+optimiser is one dfl_drr_render launch (trilinear, tight boxes, lambda views), one dfl_sim_gradncc launch
+(csrc/sim.hip) and one copy of lambda doubles to the host.  DESIGN.md section 16 states the semantics of the
+similarity; tests/reg_ref.py restates them in numpy float64.
+
+    D(theta) = [[R, centre - R centre + theta[3:]], [0, 1]],  R = exp(rot_unit theta[:3])      (pose_delta)
+    P(theta) = D(theta) P0                                   a cam-to-*-vol matrix as in gt-poses
+    C2I(theta) = inv(I2P) D(theta) I2P C2I0                  what the renderer gets (drr.Obj.c2i)
+
+With rot_unit 0.02 one unit of any parameter moves a point 50 mm from the centre by about 1 mm, so one sigma serves
+all six.  Tensors on the CPU are refused: there is no CPU path.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _native as nat
+from . import drr, preprocess
+
+__all__ = ['se3_exp', 'se3_log', 'pose_delta', 'pose_deltas', 'pnp', 'cma_es', 'CmaResult', 'Similarity', 'register',
+           'Registration', 'with_pelvis_pose', 'volume_centre']
+
+ROT_UNIT = 0.02
+
+
+# ---- rigid motions -----------------------------------------------------------------------------------------------------
+def _hat(w):
+    return np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+
+
+def _abc(t):
+    """sin t / t, (1 - cos t) / t^2, (t - sin t) / t^3, by their series below 1e-4."""
+    if t < 1e-4:
+        t2 = t * t
+        return 1.0 - t2 / 6.0, 0.5 - t2 / 24.0, 1.0 / 6.0 - t2 / 120.0
+    return np.sin(t) / t, (1.0 - np.cos(t)) / (t * t), (t - np.sin(t)) / (t ** 3)
+
+
+def se3_exp(xi):
+    """(rotation vector [3], v [3]) -> the 4 x 4 rigid motion exp of the twist: R = exp(hat w), t = V v."""
+    xi = np.asarray(xi, np.float64).reshape(6)
+    w, v = xi[:3], xi[3:]
+    a, b, c = _abc(float(np.linalg.norm(w)))
+    W = _hat(w)
+    T = np.eye(4)
+    T[:3, :3] = np.eye(3) + a * W + b * (W @ W)
+    T[:3, 3] = (np.eye(3) + b * W + c * (W @ W)) @ v
+    return T
+
+
+def se3_log(T):
+    """The inverse of se3_exp for rotations below pi: a 4 x 4 rigid motion -> [6]."""
+    T = np.asarray(T, np.float64).reshape(4, 4)
+    R = T[:3, :3]
+    skew = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    s, c = float(np.linalg.norm(skew)), 0.5 * (np.trace(R) - 1.0)
+    t = float(np.arctan2(s, c))
+    if s < 1e-12 and c < 0:
+        raise nat.DflError('register.se3_log: a rotation by pi has no unique logarithm')
+    w = skew * (t / s if s > 1e-8 else 1.0 + t * t / 6.0)
+    a, b, c3 = _abc(t)
+    W = _hat(w)
+    V = np.eye(3) + b * W + c3 * (W @ W)
+    return np.concatenate([w, np.linalg.solve(V, T[:3, 3])])
+
+
+def pose_deltas(thetas, centre, rot_unit=ROT_UNIT):
+    """[n, 6] -> [n, 4, 4]: pose_delta of every row, with batched numpy products (Rodrigues' formula)."""
+    th = np.asarray(thetas, np.float64).reshape(-1, 6)
+    ctr = np.asarray(centre, np.float64).reshape(3)
+    w = th[:, :3] * float(rot_unit)
+    t = np.linalg.norm(w, axis=1)
+    small = t < 1e-4
+    ts = np.where(small, 1.0, t)
+    a = np.where(small, 1.0 - t * t / 6.0, np.sin(ts) / ts)
+    b = np.where(small, 0.5 - t * t / 24.0, (1.0 - np.cos(ts)) / (ts * ts))
+    W = np.zeros((th.shape[0], 3, 3))
+    W[:, 0, 1], W[:, 0, 2], W[:, 1, 0] = -w[:, 2], w[:, 1], w[:, 2]
+    W[:, 1, 2], W[:, 2, 0], W[:, 2, 1] = -w[:, 0], -w[:, 1], w[:, 0]
+    R = np.eye(3)[None] + a[:, None, None] * W + b[:, None, None] * (W @ W)
+    D = np.zeros((th.shape[0], 4, 4))
+    D[:, :3, :3] = R
+    D[:, :3, 3] = ctr[None] - R @ ctr + th[:, 3:]
+    D[:, 3, 3] = 1.0
+    return D
+
+
+def pose_delta(theta, centre, rot_unit=ROT_UNIT):
+    """Six parameters -> the 4 x 4 D: the rotation exp(theta[:3] rot_unit) (rotation vector, radians) about `centre` in
+    the volume's physical frame, followed by the translation theta[3:] in mm."""
+    return pose_deltas(np.asarray(theta, np.float64).reshape(1, 6), centre, rot_unit)[0]
+
+
+def volume_centre(volume_shape, I2P):
+    """The physical position of the middle of a [nz, ny, nx] volume."""
+    nz, ny, nx = volume_shape
+    return (np.asarray(I2P, np.float64) @ np.array([(nx - 1) / 2.0, (ny - 1) / 2.0, (nz - 1) / 2.0, 1.0]))[:3]
+
+
+def with_pelvis_pose(geom, P):
+    """A copy of geom whose pelvis pose (the one drr.project_points uses) is P."""
+    poses = dict(geom.poses)
+    poses[drr.POSES[0]] = np.array(P, np.float64).reshape(4, 4)
+    return drr.Geometry(geom.K, geom.E, poses, geom.I2P, geom.G, geom.objects, geom.grid)
+
+
+# ---- pose from landmarks -----------------------------------------------------------------------------------------------
+def _project(Kt, V2C, X):
+    cam = V2C[:3, :3] @ X.T + V2C[:3, 3:4]
+    p = Kt @ cam
+    return p[:2] / p[2:3]
+
+
+def _dlt(Kt, X, x):
+    """V2C (volume physical frame -> camera projective frame) from >= 6 points, or None when they do not determine it."""
+    n = X.shape[0]
+    Xm, xm = X.mean(0), x.mean(1)
+    Xs = np.sqrt(3.0) / max(float(np.sqrt(((X - Xm) ** 2).sum(1)).mean()), 1e-300)
+    xs = np.sqrt(2.0) / max(float(np.sqrt(((x - xm[:, None]) ** 2).sum(0)).mean()), 1e-300)
+    TX = np.diag([Xs, Xs, Xs, 1.0])
+    TX[:3, 3] = -Xs * Xm
+    Tx = np.diag([xs, xs, 1.0])
+    Tx[:2, 2] = -xs * xm
+    Xh = (TX @ np.concatenate([X, np.ones((n, 1))], 1).T).T
+    xh = Tx @ np.concatenate([x, np.ones((1, n))], 0)
+    A = np.zeros((2 * n, 12))
+    A[0::2, 0:4], A[0::2, 8:12] = Xh, -xh[0][:, None] * Xh
+    A[1::2, 4:8], A[1::2, 8:12] = Xh, -xh[1][:, None] * Xh
+    _, sv, Vt = np.linalg.svd(A)
+    if sv[10] <= 1e-9 * sv[0]:                                 # a null space of more than one dimension: coplanar points
+        return None
+    M = np.linalg.inv(Tx) @ Vt[-1].reshape(3, 4) @ TX
+    T = np.linalg.inv(Kt) @ M
+    det = float(np.linalg.det(T[:, :3]))
+    if abs(det) < 1e-300:
+        return None
+    T = T / (np.sign(det) * abs(det) ** (1.0 / 3.0))
+    U, _, Wt = np.linalg.svd(T[:, :3])
+    V2C = np.eye(4)
+    V2C[:3, :3] = U @ Wt
+    V2C[:3, 3] = T[:, 3]
+    return V2C
+
+
+def pnp(geom, X3d, x2d, P_init=None, iterations=100):
+    """The cam-to-pelvis-vol pose under which drr.project_points maps X3d [L, 3] (volume physical frame) onto x2d [2, L]
+    ((column, row) on geom's output grid), in the least-squares sense of the reprojection error.  Columns of x2d holding
+    NaN are skipped (est_lands_csv.py marks a landmark it did not find that way).  The start is the linear solution
+    (DLT) where at least 6 usable, non-coplanar points exist, else P_init; Levenberg-Marquardt follows.  Fewer than 4
+    usable points are refused."""
+    X = np.asarray(X3d, np.float64).reshape(-1, 3)
+    x = np.asarray(x2d, np.float64)
+    if x.ndim != 2 or x.shape[0] != 2 or x.shape[1] != X.shape[0]:
+        raise nat.DflError('register.pnp: X3d is %s and x2d %s: [L, 3] and [2, L] expected' % (X.shape, x.shape))
+    use = np.isfinite(x).all(0) & np.isfinite(X).all(1)
+    if int(use.sum()) < 4:
+        raise nat.DflError('register.pnp: %d usable landmarks (at least 4 are needed)' % int(use.sum()))
+    X, x = X[use], x[:, use]
+    Kt = np.linalg.inv(geom.G) @ geom.K
+    V2C = _dlt(Kt, X, x) if X.shape[0] >= 6 else None
+    if V2C is None:
+        if P_init is None:
+            raise nat.DflError('register.pnp: %d usable landmarks do not determine a pose linearly (6 non-coplanar ones do) '
+                               'and no P_init was given' % X.shape[0])
+        V2C = geom.E @ np.linalg.inv(np.asarray(P_init, np.float64).reshape(4, 4))
+    ctr = X.mean(0)
+
+    def moved(T, xi):                                          # turn about the landmarks' centroid, then shift, in mm units
+        return T @ pose_delta(xi, ctr)
+
+    def resid(T):
+        return (_project(Kt, T, X) - x).reshape(-1)
+
+    r = resid(V2C)
+    lam, h = 1e-3, 1e-6
+    for _ in range(int(iterations)):
+        J = np.stack([(resid(moved(V2C, h * e)) - resid(moved(V2C, -h * e))) / (2 * h) for e in np.eye(6)], 1)
+        H, g = J.T @ J, J.T @ r
+        better = False
+        for _ in range(12):
+            step = np.linalg.solve(H + lam * np.diag(np.diag(H) + 1e-12), -g)
+            cand = moved(V2C, step)
+            rc = resid(cand)
+            if rc @ rc < r @ r:
+                V2C, r, lam, better = cand, rc, max(lam / 10.0, 1e-12), True
+                break
+            lam *= 10.0
+        if not better or float(np.abs(step).max()) < 1e-13:
+            break
+    U, _, Wt = np.linalg.svd(V2C[:3, :3])                      # products of rotations drift by rounding only
+    V2C[:3, :3] = U @ Wt
+    return np.linalg.inv(V2C) @ geom.E                         # V2C = E inv(P)
+
+
+# ---- the optimiser -----------------------------------------------------------------------------------------------------
+class CmaResult:
+    """mean: the final mean; best_x, best_f: the best candidate evaluated; trace: the best cost of every generation;
+    evaluations: how many candidates were evaluated; sigma: the final step size."""
+
+    def __init__(self, mean, best_x, best_f, trace, evaluations, sigma):
+        self.mean, self.best_x, self.best_f, self.trace, self.evaluations, self.sigma = mean, best_x, best_f, trace, evaluations, sigma
+
+
+def cma_es(cost_fn, x0, sigma0, popsize=None, generations=100, seed=0):
+    """A plain (mu/mu_w, lambda) CMA-ES with Hansen's default constants (The CMA Evolution Strategy: A Tutorial, 2016).
+    cost_fn takes [lambda, n] and returns [lambda].  Random draws come from numpy.random.default_rng(seed) on the host and
+    the ranking is a stable sort, so a run repeats bit for bit."""
+    x0 = np.asarray(x0, np.float64).reshape(-1)
+    n = x0.size
+    lam = int(popsize) if popsize else 4 + int(3 * np.log(n))
+    if lam < 4 or not float(sigma0) > 0 or int(generations) < 0:
+        raise nat.DflError('register.cma_es: popsize %d (at least 4), sigma0 %r (positive), generations %r' % (lam, sigma0, generations))
+    rng = np.random.default_rng(seed)
+    mu = lam // 2
+    w = np.log(mu + 0.5) - np.log(np.arange(1, mu + 1))
+    w = w / w.sum()
+    mueff = 1.0 / float((w ** 2).sum())
+    cc = (4 + mueff / n) / (n + 4 + 2 * mueff / n)
+    cs = (mueff + 2) / (n + mueff + 5)
+    c1 = 2 / ((n + 1.3) ** 2 + mueff)
+    cmu = min(1 - c1, 2 * (mueff - 2 + 1 / mueff) / ((n + 2) ** 2 + mueff))
+    damps = 1 + 2 * max(0.0, np.sqrt((mueff - 1) / (n + 1)) - 1) + cs
+    chin = np.sqrt(n) * (1 - 1 / (4.0 * n) + 1 / (21.0 * n * n))
+    mean, sigma = x0.copy(), float(sigma0)
+    pc, ps = np.zeros(n), np.zeros(n)
+    Cm, B, Dg = np.eye(n), np.eye(n), np.ones(n)
+    best_x, best_f, trace = x0.copy(), np.inf, []
+    for gen in range(int(generations)):
+        z = rng.standard_normal((lam, n))
+        y = (z * Dg[None]) @ B.T
+        xs = mean[None] + sigma * y
+        f = np.asarray(cost_fn(xs), np.float64).reshape(-1)
+        if f.size != lam:
+            raise nat.DflError('register.cma_es: cost_fn returned %d values for %d candidates' % (f.size, lam))
+        f = np.where(np.isfinite(f), f, np.inf)
+        order = np.argsort(f, kind='stable')
+        if f[order[0]] < best_f:
+            best_f, best_x = float(f[order[0]]), xs[order[0]].copy()
+        trace.append(float(f[order[0]]))
+        ysel = y[order[:mu]]
+        yw = w @ ysel
+        mean = mean + sigma * yw
+        ps = (1 - cs) * ps + np.sqrt(cs * (2 - cs) * mueff) * (B @ ((B.T @ yw) / Dg))
+        hsig = float(np.linalg.norm(ps) / np.sqrt(1 - (1 - cs) ** (2 * (gen + 1))) / chin < 1.4 + 2 / (n + 1.0))
+        pc = (1 - cc) * pc + hsig * np.sqrt(cc * (2 - cc) * mueff) * yw
+        Cm = (1 - c1 - cmu) * Cm + c1 * (np.outer(pc, pc) + (1 - hsig) * cc * (2 - cc) * Cm) + cmu * (ysel.T * w[None]) @ ysel
+        sigma = sigma * float(np.exp((cs / damps) * (np.linalg.norm(ps) / chin - 1)))
+        Cm = 0.5 * (Cm + Cm.T)
+        ev, B = np.linalg.eigh(Cm)
+        Dg = np.sqrt(np.maximum(ev, 1e-300))
+    return CmaResult(mean, best_x, best_f, np.array(trace), lam * int(generations), sigma)
+
+
+# ---- the similarity on the device --------------------------------------------------------------------------------------
+def _device_image(t, what, dims, dtypes=(torch.float32,)):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise nat.DflError('register: %s must be a tensor on the GPU (no CPU path)' % what)
+    if t.dim() != dims or t.dtype not in dtypes:
+        raise nat.DflError('register: %s has shape %s and dtype %s: %d dimensions of %s expected'
+                           % (what, tuple(t.shape), t.dtype, dims, ' or '.join(str(d) for d in dtypes)))
+    return t.detach().contiguous()
+
+
+def pack_poses(volume, c2is, masks, grid, interp='exact', tight_boxes=True):
+    """drr.pack_objects for an array of poses: c2is [views, n_obj, 4, 4] float64 and one mask per object -> the same
+    bytes, with batched numpy products in place of the loop over views x objects."""
+    A = np.asarray(c2is, np.float64)
+    if A.ndim != 4 or A.shape[2:] != (4, 4) or A.shape[1] != len(masks) or A.shape[0] < 1 or A.shape[1] < 1:
+        raise nat.DflError('register.pack_poses: c2is of shape %s for %d masks: [views, n_obj, 4, 4] expected' % (A.shape, len(masks)))
+    out = np.zeros(A.shape[:2], drr.OBJECT_DTYPE)
+    flo, fhi = volume.full_box
+    out['o'] = A[:, :, :3, 3]
+    out['M'] = (A[:, :, :3, :3] @ grid.Q).reshape(A.shape[0], A.shape[1], 9)
+    for n, mask in enumerate(masks):
+        mask = drr.Obj(np.eye(4), mask).mask
+        lo, hi = volume.box(mask) if tight_boxes else (flo, fhi)
+        if tight_boxes and interp == 'trilinear' and hi[0] >= lo[0]:
+            lo = tuple(max(a - 1, 0) for a in lo)
+            hi = tuple(min(a + 1, b) for a, b in zip(hi, fhi))
+        out['box_lo'][:, n], out['box_hi'][:, n], out['mask'][:, n] = lo, hi, mask
+    return out
+
+
+class Similarity:
+    """The gradient-NCC cost of `views` moving images against one fixed image [H, W] (float32, on the GPU) with an
+    optional uint8 [H, W] mask: dfl_sim_prepare runs here, once; cost(moving) is one dfl_sim_gradncc launch and
+    returns a float64 tensor [V] on the device."""
+
+    def __init__(self, fixed, mask=None, views=1):
+        self.fixed = _device_image(fixed, 'the fixed image', 2)
+        dev = self.fixed.device
+        H, W = (int(s) for s in self.fixed.shape)
+        self.H, self.W, self.views = H, W, int(views)
+        self.mask = None
+        if mask is not None:
+            self.mask = _device_image(mask, 'the mask', 2, (torch.uint8,))
+            if tuple(self.mask.shape) != (H, W) or self.mask.device != dev:
+                raise nat.DflError('register: the mask is %s on %s, the fixed image %s on %s'
+                                   % (tuple(self.mask.shape), self.mask.device, (H, W), dev))
+        lib = nat.lib()
+        need = int(lib.dfl_sim_scratch_doubles(self.views, H, W))
+        if need < 0:
+            raise nat.DflError('register: %s' % lib.dfl_last_error().decode())
+        self.fx = torch.empty((H, W), dtype=torch.float32, device=dev)
+        self.fy = torch.empty((H, W), dtype=torch.float32, device=dev)
+        self.counted = torch.empty((H, W), dtype=torch.uint8, device=dev)
+        self.totals = torch.empty(nat.SIM_TOTALS, dtype=torch.float64, device=dev)
+        self.scratch = torch.empty(max(need, 1), dtype=torch.float64, device=dev)
+        self.out = torch.empty(self.views, dtype=torch.float64, device=dev)
+        a = nat.SimPrepareArgs(fixed=self.fixed.data_ptr(), mask=nat.ptr(self.mask), fx=self.fx.data_ptr(), fy=self.fy.data_ptr(),
+                               counted=self.counted.data_ptr(), totals=self.totals.data_ptr(), H=H, W=W)
+        with torch.cuda.device(dev):
+            nat.call('dfl_sim_prepare', a, torch.cuda.current_stream(dev).cuda_stream)
+
+    def args(self, moving, out=None):
+        out = self.out if out is None else out
+        return nat.SimGradnccArgs(moving=moving.data_ptr(), fx=self.fx.data_ptr(), fy=self.fy.data_ptr(), counted=self.counted.data_ptr(),
+                                  totals=self.totals.data_ptr(), scratch=self.scratch.data_ptr(), cost=out.data_ptr(),
+                                  scratch_doubles=self.scratch.numel(), V=int(moving.shape[0]), H=self.H, W=self.W)
+
+    def cost(self, moving):
+        mv = _device_image(moving, 'the moving images', 3)
+        if tuple(mv.shape[1:]) != (self.H, self.W) or mv.device != self.fixed.device or not 1 <= mv.shape[0] <= self.views:
+            raise nat.DflError('register: moving images of shape %s on %s for a fixed image of %d x %d on %s and at most %d views'
+                               % (tuple(mv.shape), mv.device, self.H, self.W, self.fixed.device, self.views))
+        out = torch.empty(mv.shape[0], dtype=torch.float64, device=mv.device)
+        with torch.cuda.device(mv.device):
+            nat.call('dfl_sim_gradncc', self.args(mv, out), torch.cuda.current_stream(mv.device).cuda_stream)
+        return out
+
+
+# ---- registration ------------------------------------------------------------------------------------------------------
+class Registration:
+    """pose: D(theta) P0 of the first moving object (a cam-to-*-vol matrix); poses: the same for every moving object;
+    theta; delta = D(theta); cost: the best cost of every generation (all levels, in order); final_cost: the cost at
+    theta; renders: views rendered; levels: [(factor, generations, H, W)]."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+class _Level:
+    """The buffers and argument blocks of one resolution level: lambda views of every object on one grid."""
+
+    def __init__(self, volume, grid, fixed, mask, lam, step_mm):
+        self.volume, self.grid, self.lam = volume, grid, lam
+        if tuple(fixed.shape) != (grid.H, grid.W):
+            raise nat.DflError('register: the fixed image is %s, the output grid %d x %d' % (tuple(fixed.shape), grid.H, grid.W))
+        self.sim = Similarity(fixed, mask, lam)
+        self.step_mm = float(step_mm)
+
+    def costs(self, c2is, masks):
+        """[views <= lambda, n_obj, 4, 4] -> float64 [views] on the host: one render, one similarity launch, one copy."""
+        recs = pack_poses(self.volume, c2is, masks, self.grid, 'trilinear', True)
+        V, n_obj = recs.shape
+        dev = self.volume.mu.device
+        nz, ny, nx = self.volume.shape
+        d_objs = torch.from_numpy(recs.view(np.uint8).reshape(-1)).to(dev)
+        att = torch.empty((V, self.grid.H, self.grid.W), dtype=torch.float32, device=dev)
+        a = nat.DrrArgs(mu=self.volume.mu.data_ptr(), labels=self.volume.labels.data_ptr(), objects=d_objs.data_ptr(),
+                        att=att.data_ptr(), plen=None, label_map=None, qscale=(nat.f32 * 9)(*self.grid.Q.astype(np.float32).reshape(-1)),
+                        nx=nx, ny=ny, nz=nz, H=self.grid.H, W=self.grid.W, views=V, n_obj=n_obj, n_labels=self.volume.n_labels,
+                        interp=nat.DRR_TRILINEAR, mapping=0, step_mm=self.step_mm, min_len_mm=1.0)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            nat.call('dfl_drr_render', a, stream)
+            nat.call('dfl_sim_gradncc', self.sim.args(att), stream)
+        return self.sim.out[:V].cpu().numpy()
+
+
+def register(volume, geom, fixed, moving=(0, 1, 2), theta0=None, P0=None, levels=None, popsize=16, generations=80, sigma0=2.0,
+             step_mm=1.0, mask=None, seed=0, centre=None, rot_unit=ROT_UNIT, crop=0, rot180=False, sigma_shrink=0.5):
+    """Find theta such that the DRR of `volume` under P = D(theta) P0 matches `fixed`.
+
+    moving selects the objects of geom.objects that share the pose under optimisation; the others are rendered at their
+    own poses.  Every moving object starts from its own pose in geom.objects, or all of them from P0 (a cam-to-*-vol
+    matrix) when it is given; theta0 is the start of the search (default 0).  centre (default: the middle of the
+    volume) is the point the rotation turns about.
+
+    levels=None: `fixed` is a float32 [H, W] image on geom.grid (what preprocess_projs gives: it grows with attenuation,
+    as the DRR does) and `mask` a uint8 [H, W] or None.  levels=[(factor, generations), ...], coarse to fine: `fixed` is
+    the detector's own intensities [rows, cols] (float32 or uint16); every level gets its grid from drr.training_grid(rows,
+    cols, crop, factor, rot180) and its fixed image from preprocess_projs at that factor, starts from the previous
+    level's mean and multiplies sigma by sigma_shrink; mask is not supported there.
+    """
+    if not isinstance(volume, drr.Volume):
+        raise nat.DflError('register needs a drr.Volume (device tensors; no CPU path)')
+    if not torch.is_tensor(fixed) or not fixed.is_cuda:
+        raise nat.DflError('register needs the fixed image on the GPU (no CPU path)')
+    n_obj = len(geom.objects)
+    moving = tuple(int(m) for m in moving)
+    if not moving or len(set(moving)) != len(moving) or any(not 0 <= m < n_obj for m in moving):
+        raise nat.DflError('register: moving = %r selects no or unknown objects (%d objects)' % (moving, n_obj))
+    lam = int(popsize)
+    if lam < 4:
+        raise nat.DflError('register: a population of %d (at least 4)' % lam)
+    theta0 = np.zeros(6) if theta0 is None else np.asarray(theta0, np.float64).reshape(6)
+    I2P = np.asarray(geom.I2P, np.float64)
+    back, Ei = np.linalg.inv(I2P), np.linalg.inv(geom.E)
+    ctr = volume_centre(volume.shape, I2P) if centre is None else np.asarray(centre, np.float64).reshape(3)
+    base = np.stack([ob.c2i for ob in geom.objects])                        # [n_obj, 4, 4]
+    if P0 is not None:
+        P0 = np.asarray(P0, np.float64).reshape(4, 4)
+        for m in moving:
+            base[m] = back @ P0 @ Ei
+    masks = [ob.mask for ob in geom.objects]
+    mv = np.zeros(n_obj, bool)
+    mv[list(moving)] = True
+
+    def c2is_of(thetas):
+        A = back[None] @ pose_deltas(thetas, ctr, rot_unit) @ I2P[None]     # [views, 4, 4]
+        return np.where(mv[None, :, None, None], A[:, None] @ base[None], base[None])
+
+    if levels is None:
+        plan = [(None, int(generations), geom.grid, _device_image(fixed, 'the fixed image', 2))]
+    else:
+        if mask is not None:
+            raise nat.DflError('register: a mask belongs to one grid; it is not supported together with levels')
+        px = _device_image(fixed, 'the detector image', 2, (torch.float32, torch.uint16))
+        rows, cols = (int(s) for s in px.shape)
+        Kinv = np.linalg.inv(geom.K)
+        plan = []
+        for factor, gens in levels:
+            G, (H, W) = drr.training_grid(rows, cols, crop, int(factor), bool(rot180))
+            img = preprocess.preprocess_projs(px[None], [bool(rot180)], int(crop), int(factor))[0]
+            plan.append((int(factor), int(gens), drr.Grid(-Kinv @ G, H, W), img))
+        if not plan:
+            raise nat.DflError('register: an empty list of levels')
+    mean, sigma, trace, renders, done = theta0, float(sigma0), [], 0, []
+    for k, (factor, gens, grid, img) in enumerate(plan):
+        level = _Level(volume, grid, img, mask, lam, step_mm)
+        res = cma_es(lambda th: level.costs(c2is_of(th), masks), mean, sigma, lam, gens, seed + k)
+        mean, sigma = res.mean, sigma * float(sigma_shrink)
+        trace.extend(res.trace.tolist())
+        renders += res.evaluations
+        done.append((factor, gens, grid.H, grid.W))
+    final_cost = float(level.costs(c2is_of(mean[None]), masks)[0])
+    renders += 1
+    D = pose_delta(mean, ctr, rot_unit)
+    poses = [D @ I2P @ base[m] @ geom.E for m in moving]                    # P = I2P C2I E
+    return Registration(pose=poses[0], poses=poses, theta=mean, delta=D, cost=np.array(trace), final_cost=final_cost,
+                        renders=renders, levels=done, centre=ctr)

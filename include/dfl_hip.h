@@ -47,7 +47,8 @@ const char* dfl_last_error(void);
 /* sizeof() of the argument structs, in declaration order (conv, wgrad, pack_job, bn_finalize, colstats,
  * bn_bwd_finalize, bn_relu_bwd, affine_copy, pool, head_fwd, head_bwd, loss, ensemble, op, reduce_job, prep,
  * est_lands, upsample, augment_args, augment_item, overlay, resample_plan, resample_args, fullres, mesh_mc,
- * mesh_decode, mesh_topo, mesh_csr, mesh_smooth, mesh_xform, mesh_normals, optim_pack): lets a binding written
+ * mesh_decode, mesh_topo, mesh_csr, mesh_smooth, mesh_xform, mesh_normals, preproc_projs, preproc_segs, restore_labels,
+ * sim_prepare, sim_gradncc, drr_object, drr_args, optim_pack): lets a binding written
  * in another language verify its struct mirrors at load time.  Returns -1 past the end. */
 int dfl_sizeof(int which);
 
@@ -1025,6 +1026,50 @@ typedef struct {
   int32_t reserved;
 } dfl_drr_args;
 int dfl_drr_render(const dfl_drr_args* a, dfl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Gradient-NCC between V rendered views and one fixed image (csrc/sim.hip; DESIGN.md section 16 states the semantics,
+ * tests/reg_ref.py restates them in numpy float64): the similarity of dfl_amd.register.
+ *
+ * Sobel gradients on the interior pixels 1 <= r <= H - 2, 1 <= c <= W - 2:
+ *   gx = (p[r-1][c+1] + 2 p[r][c+1] + p[r+1][c+1]) - (p[r-1][c-1] + 2 p[r][c-1] + p[r+1][c-1]), gy likewise along rows.
+ * An interior pixel counts when mask is NULL, else when the nine mask bytes of its 3 x 3 neighbourhood are non-zero.
+ * Over the counted pixels ncc(a, b) = sum (a - mean a)(b - mean b) / sqrt(sum (a - mean a)^2 sum (b - mean b)^2), 0 when
+ * either variance is 0 (at most 2^-40 of the sum of squares) or nothing is counted;
+ *   cost[v] = 1 - (ncc(gx_v, gx_f) + ncc(gy_v, gy_f)) / 2.
+ *
+ * dfl_sim_prepare, once per fixed image: fx, fy [H][W] (0 on the border), counted [H][W] (1 / 0) and
+ * totals[DFL_SIM_TOTALS] = n, sum fx, sum fx^2, sum fy, sum fy^2 over the counted pixels.
+ * dfl_sim_gradncc, once per batch: one pass over moving [V][H][W]; per workgroup (a band of rows of one view) one record
+ * of six float64 sums in scratch, added in index order by a second kernel.  No atomics: a view's cost has the same bits
+ * whatever else is in the batch.  scratch holds at least dfl_sim_scratch_doubles(V, H, W) doubles (negative: bad sizes).
+ * Refused with nothing launched: NULL pointers (mask may be NULL), H < 3, W < 3, V < 1, V > 65535, a short scratch.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define DFL_SIM_TOTALS 5
+typedef struct {
+  const float* fixed;             /* [H][W] */
+  const unsigned char* mask;      /* [H][W], or NULL */
+  float* fx;                      /* [H][W] */
+  float* fy;                      /* [H][W] */
+  unsigned char* counted;         /* [H][W] */
+  double* totals;                 /* [DFL_SIM_TOTALS] */
+  int32_t H, W;
+} dfl_sim_prepare_args;
+int dfl_sim_prepare(const dfl_sim_prepare_args* a, dfl_stream_t stream);
+
+typedef struct {
+  const float* moving;            /* [V][H][W] */
+  const float* fx;                /* the four outputs of dfl_sim_prepare for the same H, W */
+  const float* fy;
+  const unsigned char* counted;
+  const double* totals;
+  double* scratch;                /* [V][bands][6] */
+  double* cost;                   /* [V] */
+  int64_t scratch_doubles;        /* what scratch holds */
+  int32_t V, H, W, reserved;
+} dfl_sim_gradncc_args;
+int dfl_sim_gradncc(const dfl_sim_gradncc_args* a, dfl_stream_t stream);
+int64_t dfl_sim_scratch_doubles(int32_t V, int32_t H, int32_t W);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Product arithmetic of the convolution / weight-gradient GEMMs (fast paths; odd channel counts always use fp32):

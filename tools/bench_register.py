@@ -1,0 +1,142 @@
+"""Times of one optimiser generation of dfl_amd.register on one GPU, split into its three parts.
+
+tools/bench_drr.py's phantom (384 x 320 x 400 voxels of 0.8 mm, three label blobs under three poses) on the training
+grid, crop 50 and factor 8 (180 x 180), lambda = 32 candidates per generation; the fixed image is the exact DRR at the
+phantom's poses and the candidates are drawn around a start 2 units away in every parameter.
+
+  render      dfl_drr_render, trilinear, step 1 mm, tight boxes, 32 views
+  similarity  dfl_sim_gradncc on those 32 views (two kernels), and the same cost computed with torch ops on the device
+              (conv2d Sobel, float64 sums) as the yardstick for the kernel
+  host        what is left of a whole generation of register(): sampling, the batched packing, the upload of the
+              records, the copy of 32 doubles and the CMA-ES update
+
+Render and similarity are timed with device events around back-to-back calls of the C entry points (argument blocks
+built once), after a warm-up, `reps` windows of at least --window seconds each; the median is reported with the
+spread.  A generation is timed by the wall clock around register() over enough generations to fill a window (it ends
+with a copy to the host, so the device is idle when the clock stops).  There is no earlier implementation to compare
+against.
+
+    python tools/bench_register.py [--window 0.3] [--reps 5] [--out profiles/register_bench.json]
+"""
+import argparse
+import datetime
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
+import bench_drr as B  # noqa: E402
+
+FACTOR, LAMBDA, STEP_MM = 8, 32, 1.0
+THETA0 = (2.0, -2.0, 2.0, 2.0, -2.0, 2.0)
+
+
+def torch_cost(moving, fixed):
+    """The semantics of DESIGN.md section 16 with torch ops on the device, no mask: [V] float64."""
+    import torch
+    kx = torch.tensor([[-1.0, 0.0, 1.0], [-2.0, 0.0, 2.0], [-1.0, 0.0, 1.0]], device=moving.device)
+    k = torch.stack([kx, kx.t()])[:, None]
+    gm = torch.nn.functional.conv2d(moving[:, None], k).double().flatten(2)          # [V, 2, n]
+    gf = torch.nn.functional.conv2d(fixed[None, None], k).double().flatten(2)        # [1, 2, n]
+    gm = gm - gm.mean(2, keepdim=True)
+    gf = gf - gf.mean(2, keepdim=True)
+    ncc = (gm * gf).sum(2) / torch.sqrt((gm * gm).sum(2) * (gf * gf).sum(2))
+    return 1.0 - 0.5 * ncc.sum(1)
+
+
+def windows(fn, window, reps):
+    fn_ms = B.timed(fn, 1)                                                            # warm-up
+    iters = max(int(1e3 * window / max(B.timed(fn, 1), 1e-3)) + 1, 1)
+    ms = [B.timed(fn, iters) for _ in range(reps)]
+    return {'ms': round(statistics.median(ms), 4), 'min_ms': round(min(ms), 4), 'max_ms': round(max(ms), 4), 'calls_per_window': iters,
+            'first_call_ms': round(fn_ms, 3)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--window', type=float, default=0.3, help='seconds of work per timed window, at least')
+    ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'register_bench.json'))
+    args = ap.parse_args()
+    import torch
+    from dfl_amd import _native as nat, drr, register as reg
+    if not torch.cuda.is_available():
+        raise SystemExit('bench_register.py needs a GPU: a time taken anywhere else says nothing')
+    dev = torch.device('cuda', 0)
+    mu, lab = B.phantom(dev)
+    vol = drr.Volume(mu, lab)
+    f = 1000.0 / B.PIXEL_MM
+    K = np.array([[-f, 0, 767.5], [0, -f, 767.5], [0, 0, 1]])
+    G, (H, W) = drr.training_grid(B.DET, B.DET, B.CROP, FACTOR)
+    grid = drr.Grid(-np.linalg.inv(K) @ G, H, W)
+    I2P = np.eye(4)
+    I2P[:3, :3] *= B.SPACING
+    I2P[:3, 3] = [-150.0, -120.0, -160.0]
+    c2is = B.poses(1)[0]
+    objects = [drr.Obj(A, m) for A, m in zip(c2is, drr.DEFAULT_MASKS)]
+    E = np.eye(4)
+    poses = {k: I2P @ A for k, A in zip(drr.POSES, c2is)}                             # P = I2P C2I E
+    geom = drr.Geometry(K, E, poses, I2P, G, objects, grid)
+    fixed = drr.render(vol, objects, grid, want_labels=False)[0]
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    prop = torch.cuda.get_device_properties(dev)
+    # the candidates of one generation around the start
+    ctr = reg.volume_centre(vol.shape, I2P)
+    thetas = np.asarray(THETA0)[None] + 2.0 * np.random.default_rng(0).standard_normal((LAMBDA, 6))
+    A = np.linalg.inv(I2P)[None] @ reg.pose_deltas(thetas, ctr) @ I2P[None]
+    views = [[drr.Obj(A[v] @ ob.c2i, ob.mask) for ob in objects] for v in range(LAMBDA)]
+    a, (att, _, _), keep = drr.render_args(vol, views, grid, interp='trilinear', step_mm=STEP_MM, want_labels=False)
+    sim = reg.Similarity(fixed, None, LAMBDA)
+    sa = sim.args(att)
+    nat.call('dfl_drr_render', a, stream)
+    nat.call('dfl_sim_gradncc', sa, stream)
+    ours, theirs = sim.out.cpu().numpy(), torch_cost(att, fixed).cpu().numpy()
+    assert np.abs(ours - theirs).max() <= 1e-5, (ours, theirs)                        # float32 conv2d against float32 Sobel sums
+    res = {'tool': 'tools/bench_register.py --window %g --reps %d (device events around back-to-back calls for render and similarity; '
+                   'wall clock around register() for a generation; median of the repetitions)' % (args.window, args.reps),
+           'date': datetime.date.today().isoformat(), 'device': torch.cuda.get_device_name(dev),
+           'arch': getattr(prop, 'gcnArchName', ''), 'compute_units': prop.multi_processor_count, 'torch': torch.__version__,
+           'hip': torch.version.hip, 'volume': [B.NX, B.NY, B.NZ], 'output': [H, W], 'lambda': LAMBDA, 'step_mm': STEP_MM,
+           'bytes_read_per_generation_by_the_similarity': LAMBDA * H * W * 4,
+           'largest_difference_kernel_torch': float(np.abs(ours - theirs).max())}
+    res['render'] = windows(lambda: nat.call('dfl_drr_render', a, stream), args.window, args.reps)
+    res['similarity'] = windows(lambda: nat.call('dfl_sim_gradncc', sa, stream), args.window, args.reps)
+    res['similarity_torch_ops'] = windows(lambda: torch_cost(att, fixed), args.window, args.reps)
+    res['pack_poses_host_ms'] = None
+    t0 = time.perf_counter()
+    for _ in range(50):
+        reg.pack_poses(vol, A[:, None] @ np.stack([ob.c2i for ob in objects])[None], [ob.mask for ob in objects], grid, 'trilinear', True)
+    res['pack_poses_host_ms'] = round((time.perf_counter() - t0) / 50 * 1e3, 4)
+    reg.register(vol, geom, fixed, theta0=THETA0, popsize=LAMBDA, generations=3, step_mm=STEP_MM)     # warm-up
+    gens, per = 20, []
+    for rep in range(args.reps + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        reg.register(vol, geom, fixed, theta0=THETA0, popsize=LAMBDA, generations=gens, step_mm=STEP_MM, seed=rep)
+        dt = time.perf_counter() - t0
+        if rep == 0:                                                                  # size the window from the first run
+            gens = max(int(args.window / (dt / (gens + 1))) + 1, 5)
+            continue
+        per.append(1e3 * dt / (gens + 1))                                             # + 1: the evaluation of the final mean
+    res['generation'] = {'ms': round(statistics.median(per), 4), 'min_ms': round(min(per), 4), 'max_ms': round(max(per), 4),
+                         'generations_per_window': gens}
+    res['host_side'] = {'ms': round(res['generation']['ms'] - res['render']['ms'] - res['similarity']['ms'], 4)}
+    print('180 x 180, lambda 32: generation %.3f ms = render %.3f + similarity %.3f (torch ops %.3f) + host %.3f (of which packing %.3f)'
+          % (res['generation']['ms'], res['render']['ms'], res['similarity']['ms'], res['similarity_torch_ops']['ms'], res['host_side']['ms'],
+             res['pack_poses_host_ms']), flush=True)
+    del keep
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, 'w') as fh:
+        json.dump(res, fh, indent=1)
+        fh.write('\n')
+    print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    main()
