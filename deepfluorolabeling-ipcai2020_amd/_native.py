@@ -317,6 +317,15 @@ class SimGradnccArgs(C.Structure):
                 ('scratch_doubles', i64), ('V', i32), ('H', i32), ('W', i32), ('reserved', i32)]
 
 
+EXPOSE_MAX_RADIUS = 8                                                      # include/dfl_hip.h: DFL_EXPOSE_MAX_RADIUS
+
+
+class ExposeArgs(C.Structure):
+    _fields_ = [('att', fp), ('out', fp), ('key_q', fp), ('key_e', fp), ('z1', fp), ('z2', fp),
+                ('taps', f32 * (2 * EXPOSE_MAX_RADIUS + 1)), ('rho', i32), ('V', i32), ('R', i32), ('C', i32), ('u16', i32),
+                ('quantum', i32), ('electronic', i32), ('photons', f32), ('gain', f32), ('electronic_sigma', f32)]
+
+
 class UpsampleArgs(C.Structure):
     _fields_ = [('x', fp), ('y', fp), ('N', i32), ('H', i32), ('W', i32), ('C', i32), ('ldx', i32), ('ldy', i32),
                 ('bf16', i32), ('accumulate', i32)]
@@ -353,7 +362,7 @@ _SIZEOF_ORDER = [ConvArgs, WgradArgs, PackJob, BnFinalizeArgs, ColstatsArgs, BnB
                  AffineCopyArgs, PoolArgs, HeadFwdArgs, HeadBwdArgs, LossArgs, EnsembleArgs, Op, ReduceJob, PrepArgs, EstLandsArgs,
                  UpsampleArgs, AugmentArgs, AugmentItem, OverlayArgs, ResamplePlan, ResampleArgs, FullresArgs, MeshMcArgs, MeshDecodeArgs,
                  MeshTopoArgs, MeshCsrArgs, MeshSmoothArgs, MeshXformArgs, MeshNormalsArgs, PreprocProjsArgs, PreprocSegsArgs,
-                 RestoreLabelsArgs, SimPrepareArgs, SimGradnccArgs, DrrObject, DrrArgs, OptimPackArgs]
+                 RestoreLabelsArgs, SimPrepareArgs, SimGradnccArgs, ExposeArgs, DrrObject, DrrArgs, OptimPackArgs]
 
 EXPORTS = ['dfl_version', 'dfl_last_error', 'dfl_sizeof', 'dfl_conv2d', 'dfl_conv_grid_m', 'dfl_conv2d_wgrad',
            'dfl_wgrad_suggest_splits', 'dfl_sum_partials', 'dfl_pack_weights', 'dfl_bn_finalize',
@@ -372,7 +381,7 @@ EXPORTS = ['dfl_version', 'dfl_last_error', 'dfl_sizeof', 'dfl_conv2d', 'dfl_con
            'dfl_mesh_mc_count', 'dfl_mesh_mc_emit', 'dfl_mesh_decode', 'dfl_mesh_topology', 'dfl_mesh_csr', 'dfl_mesh_smooth',
            'dfl_mesh_transform', 'dfl_mesh_normals', 'dfl_adam_step', 'dfl_rmsprop_step', 'dfl_optim_pack_tiled',
            'dfl_preproc_projs', 'dfl_preproc_segs', 'dfl_restore_labels', 'dfl_drr_render', 'dfl_sim_prepare', 'dfl_sim_gradncc',
-           'dfl_sim_scratch_doubles']
+           'dfl_sim_scratch_doubles', 'dfl_drr_expose']
 
 
 class DflError(RuntimeError):
@@ -418,7 +427,8 @@ def lib():
     L.dfl_overlay_batch.argtypes = [fp, fp]
     L.dfl_resample_bilinear_u8.argtypes = [fp, fp]
     L.dfl_fullres_overlay.argtypes = [fp, fp]
-    for fn in ('dfl_preproc_projs', 'dfl_preproc_segs', 'dfl_restore_labels', 'dfl_drr_render', 'dfl_sim_prepare', 'dfl_sim_gradncc'):
+    for fn in ('dfl_preproc_projs', 'dfl_preproc_segs', 'dfl_restore_labels', 'dfl_drr_render', 'dfl_sim_prepare', 'dfl_sim_gradncc',
+               'dfl_drr_expose'):
         getattr(L, fn).argtypes = [fp, fp]
     for fn in ('dfl_mesh_mc_count', 'dfl_mesh_mc_emit', 'dfl_mesh_decode', 'dfl_mesh_topology', 'dfl_mesh_csr',
                'dfl_mesh_smooth', 'dfl_mesh_transform', 'dfl_mesh_normals'):

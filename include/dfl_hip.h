@@ -48,7 +48,7 @@ const char* dfl_last_error(void);
  * bn_bwd_finalize, bn_relu_bwd, affine_copy, pool, head_fwd, head_bwd, loss, ensemble, op, reduce_job, prep,
  * est_lands, upsample, augment_args, augment_item, overlay, resample_plan, resample_args, fullres, mesh_mc,
  * mesh_decode, mesh_topo, mesh_csr, mesh_smooth, mesh_xform, mesh_normals, preproc_projs, preproc_segs, restore_labels,
- * sim_prepare, sim_gradncc, drr_object, drr_args, optim_pack): lets a binding written
+ * sim_prepare, sim_gradncc, expose, drr_object, drr_args, optim_pack): lets a binding written
  * in another language verify its struct mirrors at load time.  Returns -1 past the end. */
 int dfl_sizeof(int which);
 
@@ -1070,6 +1070,35 @@ typedef struct {
 } dfl_sim_gradncc_args;
 int dfl_sim_gradncc(const dfl_sim_gradncc_args* a, dfl_stream_t stream);
 int64_t dfl_sim_scratch_doubles(int32_t V, int32_t H, int32_t W);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Detector model: rendered line integrals -> detector intensities (csrc/expose.hip; DESIGN.md section 17 states the
+ * semantics, tests/expose_ref.py restates them in numpy).  Per view v and pixel i = r C + c, all in fp32:
+ *   T = expf(-att);  B = the separable blur of T with taps[0 .. 2 rho] (rows first, then columns, indices clamped to
+ *   the image; each sum runs from tap 0 upwards; rho = 0: B = T);  N = photons B;
+ *   noisy = N (+ sqrtf(N) z1 when quantum) (+ electronic_sigma z2 when electronic);  I = gain noisy.
+ * z1, z2 are the standard normals of csrc/philox.h (Philox4x32-10, counter i, Box-Muller) under the 64-bit keys
+ * key_q[v], key_e[v]; a term that is off reads no key and adds nothing.  out is fp32, or uint16 when u16: I clamped to
+ * [0, 65535] and rounded to nearest even.  z1 / z2 (tests only) receive the normals when not NULL.
+ * One launch; a workgroup owns a 16 x 64 tile of one view; no atomics.  Refused with nothing launched: NULL att or out,
+ * V < 1 or > 65535, R < 1, C < 1, R C >= 2^31, rho outside 0..DFL_EXPOSE_MAX_RADIUS, photons <= 0, gain <= 0,
+ * electronic_sigma < 0 (or any of them not finite), a noise flag with a NULL key array.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define DFL_EXPOSE_MAX_RADIUS 8
+typedef struct {
+  const float* att;               /* [V][R][C], finite and >= 0 */
+  void* out;                      /* [V][R][C] fp32, or uint16 when u16 */
+  const uint64_t* key_q;          /* [V], device; NULL allowed when quantum == 0 */
+  const uint64_t* key_e;          /* [V], device; NULL allowed when electronic == 0 */
+  float* z1;                      /* [V][R][C] or NULL */
+  float* z2;                      /* [V][R][C] or NULL */
+  float taps[2 * DFL_EXPOSE_MAX_RADIUS + 1];   /* taps[0 .. 2 rho] */
+  int32_t rho;
+  int32_t V, R, C;
+  int32_t u16, quantum, electronic;
+  float photons, gain, electronic_sigma;
+} dfl_expose_args;
+int dfl_drr_expose(const dfl_expose_args* a, dfl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Product arithmetic of the convolution / weight-gradient GEMMs (fast paths; odd channel counts always use fp32):

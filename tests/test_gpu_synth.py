@@ -1,0 +1,263 @@
+"""dfl_amd.synth.synthesize end to end on the GPU, on a container built here from tests/drr_ref.py's tilted scene: a
+37 x 45 x 53 volume, a 45 x 61 detector, six landmarks and two acquired projections (one of each 'rot-180-for-up').
+Small sigmas keep the objects in view; views = 5, crop = 2.  The files are written once and shared by the tests.
+
+Bars: the label map rendered again from the written poses is the written 'gt-seg' bit for bit; the numpy model of
+tests/drr_ref.py gives Dice >= 0.99 per class against it (the bar of DESIGN.md section 15); landmarks 1e-3 px; images,
+the preprocessed arrays and repeated runs bit for bit.
+
+The seed is one at which the Dice bar can be met in float32 at all: between the float32 and the float64 numpy model, no
+kernel involved, the five views give Dice >= 0.998 per class at seed 6, while e.g. seed 3 puts two near-tie pixels into a
+47-pixel class (0.979 between the two models).  tests/test_synth_cpu.py pins that property of the seed.
+"""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import ROOT
+
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+sys.path.insert(0, os.path.join(ROOT, 'examples'))
+sys.path.insert(0, ROOT)
+import drr_ref as D  # noqa: E402
+import expose_ref as X  # noqa: E402
+import dfl_amd  # noqa: E402,F401
+from dfl_amd import _native as nat, dataset, drr, h5lite, preprocess as pp, register, synth  # noqa: E402
+from make_full_res_overlays import Source  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+DEV = torch.device('cuda', 0)
+SPEC, CROP, FACTOR, VIEWS, SEED = '17-1882', 2, 2, 5, 6
+NAMES = pp.LAND_ORDER[:6]
+KW = dict(crop=CROP, factor=FACTOR, rot_sigma_deg=2.0, trans_sigma_mm=(1.0, 1.0, 5.0), femur_sigma_deg=2.0, photons=5000.0, gain=1.5,
+          electronic_sigma=4.0, blur_sigma_px=1.0, chunk=2)
+_VOL = {}
+
+
+def _volume():
+    if not _VOL:
+        S = D.scene('tilted')
+        _VOL['v'] = drr.Volume(torch.from_numpy(S['mu'].copy()).to(DEV), torch.from_numpy(S['lab'].copy()).to(DEV))
+    return _VOL['v']
+
+
+def _write_source(path):
+    S = D.scene('tilted')
+    pts = np.array([(S['I2P'] @ np.array(c + (1.0,)))[:3] for c, _, _ in D.ELLIPSOIDS])
+    with h5lite.File(path, 'w') as f:
+        f['proj-params/intrinsic'] = S['K']
+        f['proj-params/extrinsic'] = S['E']
+        f['proj-params/num-rows'] = np.int64(S['rows'])
+        f['proj-params/num-cols'] = np.int64(S['cols'])
+        f['proj-params/pixel-row-spacing'] = np.float64(1.0)
+        f['proj-params/pixel-col-spacing'] = np.float64(1.0)
+        for grp, px in ((SPEC + '/vol/', S['hu']), (SPEC + '/vol-seg/image/', S['lab'])):
+            f[grp + 'pixels'] = px
+            f[grp + 'dir-mat'] = np.eye(3)
+            f[grp + 'spacing'] = np.array([0.8, 0.75, 1.1])
+            f[grp + 'origin'] = S['I2P'][:3, 3]
+        for l in range(1, 7):
+            f[SPEC + '/vol-seg/labels-def/%d' % l] = 'ellipsoid-%d' % l
+        for l, name in enumerate(NAMES):
+            f[SPEC + '/vol-landmarks/' + name] = pts[l].reshape(3, 1)
+        for p, (poses, rot) in enumerate(((S['poses'], 0), (D.perturbed(S), 1))):
+            pfx = SPEC + '/projections/%03d/' % p
+            for g, dt in (('image/', np.uint16), ('gt-seg/', np.uint8)):
+                f[pfx + g + 'pixels'] = np.zeros((S['rows'], S['cols']), dt)
+                f[pfx + g + 'dir-mat'] = np.eye(2)
+                f[pfx + g + 'origin'] = np.zeros(2)
+                f[pfx + g + 'spacing'] = np.array([1.0, 1.0]) * (1 + p)      # told apart: the views take their seed's
+            for k, P in zip(drr.POSES, poses):
+                f[pfx + 'gt-poses/' + k] = P
+            f[pfx + 'gt-poses/left-femur-good-fov'] = np.int64(1)
+            f[pfx + 'gt-poses/right-femur-good-fov'] = np.int64(1)
+            f[pfx + 'rot-180-for-up'] = np.int64(rot)
+
+
+@pytest.fixture(scope='module')
+def files(tmp_path_factory):
+    d = str(tmp_path_factory.mktemp('synth'))
+    paths = {k: os.path.join(d, k + '.h5') for k in ('src', 'full', 'pre', 'full_again', 'pre_again', 'full_other', 'clean', 'bare')}
+    _write_source(paths['src'])
+    lines = []
+    done = synth.synthesize(paths['src'], paths['full'], VIEWS, seed=SEED, layout='full-res', report=lines.append, **KW)
+    assert done == [(SPEC, 1, VIEWS, done[0][3])] and len(lines) == 1 and lines[0].startswith(SPEC + ' -> ' + SPEC) and '45 x 61' in lines[0]
+    lines = []
+    synth.synthesize(paths['src'], paths['pre'], VIEWS, seed=SEED, layout='preprocessed', report=lines.append, **KW)
+    assert len(lines) == 1 and lines[0].startswith(SPEC + ' -> 01: 5 synthetic projections from 2 acquired')
+    return paths
+
+
+def _all(path):
+    """{dataset path: value} of a whole file."""
+    out = {}
+
+    def walk(node, pre):
+        for k in node.keys():
+            child = node[k]
+            if isinstance(child, h5lite.Group):
+                walk(child, pre + k + '/')
+            else:
+                out[pre + k] = child[()]
+
+    with h5lite.File(path, 'r') as f:
+        walk(f, '')
+    return out
+
+
+def _same(a, b):
+    return sorted(a) == sorted(b) and all(np.asarray(a[k]).tobytes() == np.asarray(b[k]).tobytes() and
+                                          np.asarray(a[k]).dtype == np.asarray(b[k]).dtype for k in a)
+
+
+def _render(src, n, bones_only=False):
+    """(geometry on the full detector grid, att, labels) of projection n of a written file, from its written poses."""
+    geom = drr.geometry(src, SPEC, n, crop=0, factor=1, rot180=False, bones_only=bones_only)
+    att, _, lab = drr.render(_volume(), geom.objects, geom.grid)
+    return geom, att, lab
+
+
+def test_full_res_layout(files):
+    S = D.scene('tilted')
+    src = Source(files['full'])
+    assert src.children('') == sorted(['proj-params', SPEC]) and src.children(SPEC + '/projections') == ['%03d' % n for n in range(VIEWS)]
+    assert src.children(SPEC) == ['projections', 'vol', 'vol-landmarks', 'vol-seg']
+    orig = _all(files['src'])
+    got = _all(files['full'])
+    for k, v in orig.items():                                   # proj-params, vol, vol-seg with labels-def, vol-landmarks: copied
+        if '/projections/' not in k:
+            assert np.asarray(got[k]).tobytes() == np.asarray(v).tobytes() and np.asarray(got[k]).shape == np.asarray(v).shape, k
+    assert got[SPEC + '/vol-seg/labels-def/3'] == b'ellipsoid-3'
+    pts = np.array([orig[SPEC + '/vol-landmarks/' + n].reshape(-1) for n in NAMES])
+    pelvis = []
+    for n in range(VIEWS):
+        pfx = SPEC + '/projections/%03d/' % n
+        assert src.children(pfx) == ['gt-landmarks', 'gt-poses', 'gt-seg', 'image', 'rot-180-for-up']
+        assert src.children(pfx + 'gt-poses') == sorted(drr.POSES + ('left-femur-good-fov', 'right-femur-good-fov'))
+        img, seg = got[pfx + 'image/pixels'], got[pfx + 'gt-seg/pixels']
+        assert img.dtype == np.uint16 and seg.dtype == np.uint8 and img.shape == seg.shape == (S['rows'], S['cols'])
+        geom, att, lab = _render(src, n)
+        assert geom.size == (S['rows'], S['cols'])
+        # the written gt-seg is the label map of the written poses, bit for bit ...
+        assert np.array_equal(lab.cpu().numpy(), seg)
+        # ... and the numpy model agrees: Dice >= 0.99 per class
+        recs = D.pack([o.c2i for o in geom.objects], [o.mask for o in geom.objects], geom.grid.Q, S['lab'])
+        _, m_plen, _ = D.render(S['mu'], S['lab'], recs, geom.grid.Q.astype(np.float32), S['rows'], S['cols'])
+        want = D.label_map(m_plen)
+        present = [l for l in range(1, 7) if (want == l).any()]
+        assert len(present) >= 4
+        for l in present:
+            dice = 2.0 * ((want == l) & (seg == l)).sum() / ((want == l).sum() + (seg == l).sum())
+            assert dice >= 0.99, (n, l, dice)
+        # landmarks: project_points under the written pelvis pose
+        uv = np.stack([got[pfx + 'gt-landmarks/' + name].reshape(-1) for name in NAMES], 1)
+        assert got[pfx + 'gt-landmarks/FH-l'].shape == (2, 1) and src.children(pfx + 'gt-landmarks') == sorted(NAMES)
+        assert np.abs(uv - drr.project_points(geom, pts)).max() <= 1e-3
+        assert ((uv[0] >= CROP) & (uv[0] <= S['cols'] - 1 - CROP) & (uv[1] >= CROP) & (uv[1] <= S['rows'] - 1 - CROP)).sum() >= 4
+        # the image: dfl_drr_expose of that render under the view's keys
+        kq, ke = synth.noise_keys(SEED, 0, n)
+        again = synth.expose(att[None], KW['photons'], KW['gain'], KW['electronic_sigma'], KW['blur_sigma_px'], [kq], [ke], u16=True)
+        assert np.array_equal(again[0].cpu().numpy(), img)
+        assert img.max() > 1000 and len(np.unique(img)) > 500
+        # good-fov: the femoral head under that femur's pose, inside the detector
+        for side, (name, flag) in enumerate((('FH-l', 'left'), ('FH-r', 'right'))):
+            head = drr.project_points(register.with_pelvis_pose(geom, geom.poses[drr.POSES[1 + side]]), pts[NAMES.index(name)])[:, 0]
+            inside = 0 <= head[0] <= S['cols'] - 1 and 0 <= head[1] <= S['rows'] - 1
+            assert int(got[pfx + 'gt-poses/%s-femur-good-fov' % flag]) == int(inside)
+        # the seed's rotation flag and image geometry: seeds alternate
+        assert int(got[pfx + 'rot-180-for-up']) == n % 2
+        for g in ('image/', 'gt-seg/'):
+            assert np.array_equal(got[pfx + g + 'spacing'], [1.0 + n % 2] * 2) and np.array_equal(got[pfx + g + 'dir-mat'], np.eye(2))
+        pelvis.append(geom.poses[drr.POSES[0]])
+        seed_pose = orig[SPEC + '/projections/%03d/gt-poses/%s' % (n % 2, drr.POSES[0])]
+        assert 1e-3 < np.abs(pelvis[-1] - seed_pose).max() < 200
+    assert all(not np.array_equal(pelvis[0], P) for P in pelvis[1:])
+    src.close()
+
+
+def test_preprocessed_layout_is_the_converted_full_res_file(files, tmp_path):
+    conv = os.path.join(str(tmp_path), 'converted.h5')
+    pp.convert_file(files['full'], conv, factor=FACTOR, crop=CROP)
+    a, b = _all(conv), _all(files['pre'])
+    assert sorted(a) == sorted(b) and {'01/projs', '01/segs', '01/lands', 'land-names/num-lands', 'land-names/land-05'} <= set(a)
+    for k in a:
+        assert np.asarray(a[k]).dtype == np.asarray(b[k]).dtype and np.asarray(a[k]).tobytes() == np.asarray(b[k]).tobytes(), k
+    Ro, Co = pp.out_size(45, 61, CROP, FACTOR)
+    assert b['01/projs'].shape == (VIEWS, Ro, Co) == b['01/segs'].shape and b['01/lands'].shape == (VIEWS, 2, 6)
+    assert b['01/projs'].dtype == np.float32 and b['01/segs'].dtype == np.uint8 and b['01/lands'].dtype == np.float32
+    assert [b['land-names/land-%02d' % l].decode() for l in range(6)] == NAMES and int(b['land-names/num-lands']) == 6
+    assert b['01/segs'].max() <= 6 and len(np.unique(b['01/segs'])) >= 5 and float(b['01/projs'].max()) > 0.5
+    # the loader opens it as train.py does: one batch of the right shapes, labels in range
+    ds = dataset.get_dataset(files['pre'], [1], num_classes=7, pad_img_dim=0, device=DEV)
+    assert len(ds) == VIEWS
+    x, masks, lands, heats = next(iter(ds.batches(VIEWS, shuffle=False)))
+    assert tuple(x.shape) == (VIEWS, 1, Ro, Co) and tuple(masks.shape) == (VIEWS, 7, Ro, Co) and tuple(heats.shape) == (VIEWS, 6, 1, Ro, Co)
+    assert bool(torch.isfinite(x).all()) and float(masks.sum(1).min()) == 1.0 == float(masks.sum(1).max())
+    assert np.array_equal(masks.argmax(1).cpu().numpy(), b['01/segs'])
+    assert tuple(lands.shape) == (VIEWS, 2, 6) and int(torch.isfinite(lands[:, 0]).sum()) >= VIEWS
+
+
+def test_seeds(files):
+    synth.synthesize(files['src'], files['full_again'], VIEWS, seed=SEED, layout='full-res', **KW)
+    synth.synthesize(files['src'], files['pre_again'], VIEWS, seed=SEED, layout='preprocessed', **dict(KW, chunk=5))
+    synth.synthesize(files['src'], files['full_other'], VIEWS, seed=SEED + 1, layout='full-res', **KW)
+    first, again, other = _all(files['full']), _all(files['full_again']), _all(files['full_other'])
+    assert _same(first, again) and _same(_all(files['pre']), _all(files['pre_again']))        # (chunk does not move a bit)
+    assert open(files['full'], 'rb').read() == open(files['full_again'], 'rb').read()
+    pfx = SPEC + '/projections/000/'
+    assert sorted(first) == sorted(other)
+    for k in ('image/pixels', 'gt-seg/pixels', 'gt-poses/' + drr.POSES[0], 'gt-landmarks/FH-l'):
+        assert not np.array_equal(first[pfx + k], other[pfx + k]), k
+
+
+def test_no_noise_and_no_volumes(files):
+    synth.synthesize(files['src'], files['clean'], VIEWS, seed=SEED, layout='full-res', noise=False, bones_only=True,
+                     **dict(KW, blur_sigma_px=0.0))
+    src = Source(files['clean'])
+    top = np.float32(np.float32(KW['gain']) * np.float32(KW['photons']))
+    noisy = _all(files['full'])
+    for n in range(VIEWS):
+        pfx = SPEC + '/projections/%03d/' % n
+        img = np.asarray(src.get(pfx + 'image/pixels'))
+        geom, att, lab = _render(src, n, bones_only=True)
+        assert np.array_equal(lab.cpu().numpy(), src.get(pfx + 'gt-seg/pixels'))
+        a = att.cpu().numpy()
+        exact = np.float64(KW['gain']) * KW['photons'] * np.exp(-a.astype(np.float64))
+        # gain photons exp(-att), rounded: the kernel's fp32 value lies within 8 ulp of the exact one (expf within a couple
+        # of ulp, two products), so the rounded count may differ by one only where the exact value is that close to a tie
+        slack = 8 * np.spacing(top)
+        lo, hi = np.rint(np.clip(exact - slack, 0, 65535)), np.rint(np.clip(exact + slack, 0, 65535))
+        assert ((img >= lo) & (img <= hi)).all() and (img == np.rint(np.clip(exact, 0, 65535))).mean() >= 0.99
+        assert (img[a == 0] == int(top)).all() and (a == 0).mean() > 0.2
+        # the poses are those of the noisy file of the same seed; the pixels are not
+        assert np.array_equal(geom.poses[drr.POSES[1]], noisy[pfx + 'gt-poses/' + drr.POSES[1]])
+        assert not np.array_equal(img, noisy[pfx + 'image/pixels'])
+    src.close()
+    synth.synthesize(files['src'], files['bare'], VIEWS, seed=SEED, layout='full-res', volumes=False, **KW)
+    full, bare = _all(files['full']), _all(files['bare'])
+    dropped = sorted(k for k in full if k.startswith(SPEC + '/vol/') or k.startswith(SPEC + '/vol-seg/'))
+    assert len(dropped) == 4 + 4 + 6 and sorted(set(full) - set(bare)) == dropped and not set(bare) - set(full)
+    assert _same({k: v for k, v in full.items() if k not in dropped}, bare)
+    with h5lite.File(files['bare'], 'r') as f:
+        assert f[SPEC].keys() == ['projections', 'vol-landmarks']
+
+
+def test_refusals(files, tmp_path):
+    out = os.path.join(str(tmp_path), 'x.h5')
+    with pytest.raises(nat.DflError, match='no specimen'):
+        synth.synthesize(files['src'], out, 2, specimens=['nobody'], **KW)
+    with pytest.raises(nat.DflError, match=SPEC):
+        synth.synthesize(files['src'], out, 2, **dict(KW, trans_sigma_mm=(500.0, 500.0, 5.0), min_lands=6))
+    with pytest.raises(nat.DflError, match='radius'):
+        synth.synthesize(files['src'], out, 2, **dict(KW, blur_sigma_px=3.0))
+    with pytest.raises(nat.DflError, match='layout'):
+        synth.synthesize(files['src'], out, 2, layout='npz', **KW)
+    import synthesize_dataset as cli
+    assert cli.main([files['src'], out, '--views', '2', '--crop', '2', '--ds-factor', '2', '--rot-sigma-deg', '2', '--trans-sigma-mm', '1,1,5',
+                     '--femur-sigma-deg', '2', '--chunk', '2']) == 0
+    with h5lite.File(out, 'r') as f:
+        assert f['01/projs'].shape == (2,) + pp.out_size(45, 61, 2, 2)
