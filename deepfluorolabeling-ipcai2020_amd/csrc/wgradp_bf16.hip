@@ -18,7 +18,9 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -29,6 +31,8 @@ namespace dfl {
 constexpr uint32_t WPOOB = 0x80000000u;
 typedef unsigned int wpu32x4 __attribute__((ext_vector_type(4)));
 typedef short ws16x4_t __attribute__((ext_vector_type(4)));
+
+struct WgStep { int img, y, x; };
 
 struct WgP {
   dfl_wgrad_args a;
@@ -48,7 +52,20 @@ struct WgP {
   uint32_t g_bytes, d_bytes;
   uint32_t d2_bytes;                   // extent of the second dense tensor (dfl_wgrad_args.d_mode)
   int xcd_map;                         // workgroup -> (tile, slice) map, see the kernel
+  int red_all;                         // cross-phase sums: 1 = all KW taps of a wave in one pass (the scratch holds them), 0 = tap by tap
+  // one thread's step from a unit to its next one as (images, rows, columns) of the box the units walk: the d patch
+  // (NT / dupp pixels), the gathered patch (NT / gupp pixels) and the offset table (NT pixels of the d patch)
+  WgStep dadv, gadv, tadv;
 };
+
+// box position (img, y, x) + step s inside a box of H x W pixels per image: one carry per digit, no division
+__device__ __forceinline__ void wgp_advance(int& img, int& y, int& x, const WgStep& s, int H, int W) {
+  x += s.x;
+  if (x >= W) { x -= W; ++y; }
+  y += s.y;
+  if (y >= H) { y -= H; ++img; }
+  img += s.img;
+}
 
 
 // 8 consecutive pixels of one channel: two transposing reads (pixel rows at byte addresses r0 and r1 as seen by this lane)
@@ -71,9 +88,13 @@ __device__ __forceinline__ wpu32x2 wtr_read4(const unsigned char* base, uint32_t
 // 48 accumulator registers (3x3) instead of 4 waves of 144: three waves per SIMD cover each other's LDS latency, the patch
 // is staged by three times the threads, and the register budget leaves room for the prefetch below.
 // Units (16 bytes) of the d / g images a workgroup may hold in flight in registers, per window height: the 3x3 kernel
-// (768 threads) fills a CU alone; the 2x2 and 1x1 kernels (512 / 256 threads) keep their register count at 128 so that
-// two / four workgroups share a CU and cover each other's barriers and load waits.
+// (768 threads) fills a CU alone; the 2x2 kernel (512 threads) keeps its register count below 128 so that two workgroups
+// share a CU and cover each other's barriers and load waits; the 1x1 kernel (256 threads) needs more than 128 registers,
+// which is three workgroups per CU.
 // (dbrb: the fused BatchNorm + ReLU backward operand keeps TWO tensors of the d patch in flight: smaller patches pay for its registers)
+// waves per SIMD the kernel is compiled for (its __launch_bounds__): a workgroup is KH waves per SIMD, so a CU holds
+// wgp_waves_per_simd(KH) / KH workgroups as far as registers go (1 / 2 / 3 for the 3x3 / 2x2 / 1x1 windows)
+__host__ __device__ constexpr int wgp_waves_per_simd(int KH) { return KH == 2 ? 4 : 3; }
 __host__ __device__ constexpr int wgp_max_d_units(int KH, bool dbrb = false) { return KH == 3 ? (dbrb ? 1536 : 2304) : 1024; }
 __host__ __device__ constexpr int wgp_max_g_units(int KH, bool dbrb = false) { return KH == 3 ? (dbrb ? 3072 : 4608) : 2048; }
 
@@ -81,7 +102,7 @@ __host__ __device__ constexpr int wgp_max_g_units(int KH, bool dbrb = false) { r
 // (dfl_wgrad_args.d_mode), and the column sums of it -- the layer's bias gradient -- leave with the slice (bias_partial).
 // BIAS: the column sums also leave when d is a plain tensor (the operand materialised by dfl_conv_args.x_out).
 template <int KH, int KW, bool AFF, bool DBRB = false, bool BIAS = DBRB>
-__global__ void __launch_bounds__(256 * KH, KH == 2 ? 4 : 3) wgradp_kernel(const WgP p) {
+__global__ void __launch_bounds__(256 * KH, wgp_waves_per_simd(KH)) wgradp_kernel(const WgP p) {
   constexpr int NT = 256 * KH;
   constexpr int T = KH * KW;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -89,12 +110,15 @@ __global__ void __launch_bounds__(256 * KH, KH == 2 ? 4 : 3) wgradp_kernel(const
 #ifdef DFL_WGP_TRACE
   const long long tr_entry = __builtin_amdgcn_s_memtime();
 #endif
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // (the wave number through readfirstlane: kernel row, slot, pair, phase and with them the trip count of the k-step loop
+  //  are scalars -- the loop is a scalar loop and EXEC is all ones at every transposing read by construction)
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 31, lh = lane >> 5;
   const int ty = wave % KH, slot = wave / KH;
-  const int pair = slot % p.pairs, phase = slot / p.pairs;
-  const int pairs_n = p.CGT >> 5;                       // pairs along cg
-  const int pm = pair / pairs_n, pn = pair - pm * pairs_n;
+  const int pairs_sh = p.pairs >> 1;                    // log2(pairs): pairs and phases are 1, 2 or 4
+  const int pair = slot & (p.pairs - 1), phase = slot >> pairs_sh;
+  const int pairs_n = p.CGT >> 5;                       // pairs along cg (1 or 2)
+  const int pm = pair >> (pairs_n - 1), pn = pair & (pairs_n - 1);
   // ---- which tile, which pixel slice.  Workgroup L of the linear dispatch order runs on XCD L % 8 (observed; convp_bf16.hip),
   //      and each XCD has an L2 of its own.  With the hardware's order (cm tile fastest, then cg tile, then slice) the 8 XCDs
   //      share every slice: an XCD sees one or two cm tiles and ALL cg tiles, so the gathered tensor is fetched by all eight
@@ -156,30 +180,41 @@ __global__ void __launch_bounds__(256 * KH, KH == 2 ? 4 : 3) wgradp_kernel(const
   const int dc = cm0 + dcq * 8, gc = cg0 + gcq * 8;
   const uint32_t dpitch = (uint32_t)a.ldd * 2u, gpitch = (uint32_t)a.ldg * 2u, d2pitch = (uint32_t)a.ldd2 * 2u;
   const int nd = (p.P16 * dupp + NT - 1) / NT, ng = (npix_g * gupp + NT - 1) / NT;   // units per thread actually in use (uniform)
+  // (a thread's first unit is placed by division, its later ones by the host's (images, rows, columns) step: wgp_advance)
   {
     const int PHW = p.PH * p.PW;
+    int k = tid >> p.dupp_shift;
+    int img = k / PHW, r = k - img * PHW;
+    int y = r / p.PW, x = r - y * p.PW;
 #pragma unroll
     for (int u = 0; u < MAXD; ++u) {
-      const int k = (tid >> p.dupp_shift) + u * ddk;
-      const int img = k / PHW, r = k - img * PHW;
-      const int y = r / p.PW, x = r - y * p.PW;
       const bool live = k < p.P16 && img < p.IPP && dc < a.Cm;
       dpos[u] = (uint32_t)y | ((uint32_t)x << 12) | ((uint32_t)(img & 127) << 24) | (live ? 0x80000000u : 0u);
+      k += ddk;
+      wgp_advance(img, y, x, p.dadv, p.PH, p.PW);
     }
     const int IHW = p.IH * p.IW;
+    k = tid >> p.gupp_shift;
+    img = k / IHW, r = k - img * IHW;
+    y = r / p.IW, x = r - y * p.IW;
 #pragma unroll
     for (int u = 0; u < MAXG; ++u) {
-      const int k = (tid >> p.gupp_shift) + u * gdk;
-      const int img = k / IHW, r = k - img * IHW;
-      const int y = r / p.IW, x = r - y * p.IW;
       const bool live = k < npix_g && gc < a.Cg;
       gpos[u] = (uint32_t)y | ((uint32_t)x << 12) | ((uint32_t)(img & 127) << 24) | (live ? 0x80000000u : 0u);
+      k += gdk;
+      wgp_advance(img, y, x, p.gadv, p.IH, p.IW);
     }
+  }
+  // the offset table: two divisions for a thread's first entry, then the host's step.  (It stays in front of the first
+  // patch's loads: filled behind them, the 3x3 instances spill 144 - 244 bytes per lane in the patch loop instead of 0 - 12)
+  {
+    const int PHW = p.PH * p.PW;
+    int img = tid / PHW, r = tid - img * PHW;
+    int y = r / p.PW, x = r - y * p.PW;
     for (int j = tid; j < p.P16; j += NT) {
-      const int img = j / PHW, r = j - img * PHW;
-      const int y = r / p.PW, x = r - y * p.PW;
       // rows beyond the patch: d is zero there, any valid g row will do
       gtab[j] = img < p.IPP ? (uint32_t)((img * p.IH + y * a.stride) * p.IW + x * a.stride) * (uint32_t)p.sg : 0u;
+      wgp_advance(img, y, x, p.tadv, p.PH, p.PW);
     }
   }
   // BatchNorm affine of the gathered tensor (applied when a unit is written to LDS): this thread's 8 channels, kept in LDS
@@ -324,28 +359,51 @@ __global__ void __launch_bounds__(256 * KH, KH == 2 ? 4 : 3) wgradp_kernel(const
     __syncthreads();
     WTR(1, tb1)
     WT0(ti0)
-    issue(patch + 1, patch + 1 < pend);
+    if (patch + 1 < pend) issue(patch + 1, true);       // (nothing is requested behind the last patch)
     WTR(3, ti0)
+    // this wave's k-steps of the patch: phase, phase + phases, ... (a scalar count); the table entries of its first step are
+    // requested here, those of step k + 1 inside step k, so that a step waits for one LDS round trip (its fragments), not two
+    const int nk = nsteps > phase ? (nsteps - phase + p.phases - 1) >> (p.phases >> 1) : 0;
+    const uint32_t* tp = gtab + phase * 16 + trow;
+    uint32_t t0 = 0, t1 = 0;
+    if (nk > 0) {
+      // (relaxed atomic loads, plain ds_read_b32: two loads of the loop's own kind here and the compiler folds them and the
+      //  loop's into one at the loop's head -- the round trip is back; a volatile load becomes a flat load that waits for vmcnt,
+      //  that is for the requests of the next patch)
+      t0 = __hip_atomic_load(tp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+      t1 = __hip_atomic_load(tp + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    }
     if constexpr (BIAS) {
       // bias gradient: column sums of the d image as stored -- thread t owns channel t % CMT and every (NT / CMT)-th pixel row
-      // (rows beyond the patch are zero); one accumulator register instead of eight in the staging path
+      // (rows beyond the patch are zero); one accumulator register instead of eight in the staging path.  Four reads in flight
+      // in front of their four adds, the rows in the same order as one by one
       if (bias_on) {
-        const int bc = tid & (p.CMT - 1), bstride = NT / p.CMT;
-        for (int r = tid / p.CMT; r < p.P16; r += bstride)
-          bsum += __uint_as_float((uint32_t)*reinterpret_cast<const unsigned short*>(Ds + (uint32_t)r * (uint32_t)p.sd + (uint32_t)bc * 2u) << 16);
+        const int csh = p.dupp_shift + 3;                 // log2(CMT)
+        const int bc = tid & (p.CMT - 1), bstride = NT >> csh;
+        const uint32_t brow = (uint32_t)bstride * (uint32_t)p.sd;
+        const unsigned char* bp = Ds + (uint32_t)(tid >> csh) * (uint32_t)p.sd + (uint32_t)bc * 2u;
+        auto bld = [](const unsigned char* q) { return (uint32_t)*reinterpret_cast<const unsigned short*>(q); };
+        int r = tid >> csh;
+        for (; r + 3 * bstride < p.P16; r += 4 * bstride, bp += 4u * brow) {
+          const uint32_t v0 = bld(bp), v1 = bld(bp + brow), v2 = bld(bp + 2u * brow), v3 = bld(bp + 3u * brow);
+          bsum += __uint_as_float(v0 << 16);
+          bsum += __uint_as_float(v1 << 16);
+          bsum += __uint_as_float(v2 << 16);
+          bsum += __uint_as_float(v3 << 16);
+        }
+        for (; r < p.P16; r += bstride, bp += brow) bsum += __uint_as_float(bld(bp) << 16);
       }
     }
     WT0(tk0)
     // ---- k-steps of this patch (16 pixels each), this wave's phase; this lane's two pixel rows of a step are the
     //      patch pixels j0 = 16 ks + trow and j0 + 4: their d rows are j0 * sd, their g rows come from the offset table
     uint32_t dr0 = (uint32_t)(phase * 16 + trow) * (uint32_t)p.sd + d_col;
-    const uint32_t* tp = gtab + phase * 16 + trow;
-    int ks = phase;
-    auto kstep = [&]() {
-      const uint32_t gr0 = tp[0] + gadd, gr1 = tp[4] + gadd;
+    const int tstep = 16 * p.phases;
+    auto kstep = [&](auto al8_c, bool last) {
+      const uint32_t gr0 = t0 + gadd, gr1 = t1 + gadd;
       const bf16x8_t df = wtr_read8(Ds, dr0, dr0 + 4u * (uint32_t)p.sd);
       bf16x8_t gf[KW];
-      if (KW == 3 && al8) {
+      if constexpr (decltype(al8_c)::value) {
         // the 8 pixels of this lane's half of the k-step are consecutive pixels of one image row (PW % 8 == 0, stride 1): 12
         // consecutive gathered pixels -- three transposing reads -- hold all three taps of the kernel row; tap 1 is the same
         // registers shifted by one pixel (v_alignbit).  3 LDS reads instead of 6 in a loop that is bound by them (round 5)
@@ -358,15 +416,26 @@ __global__ void __launch_bounds__(256 * KH, KH == 2 ? 4 : 3) wgradp_kernel(const
 #pragma unroll
         for (int t = 0; t < KW; ++t) gf[t] = wtr_read8(Gs, gr0 + (uint32_t)(t * p.sg), gr1 + (uint32_t)(t * p.sg));
       }
+      tp += last ? 0 : tstep;                             // (the last step asks for its own entries again: inside the table)
+      t0 = tp[0];
+      t1 = tp[4];
 #pragma unroll
       for (int t = 0; t < KW; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(df, gf[t], acc[t], 0, 0, 0);
       dr0 += dstep;
-      tp += 16 * p.phases;
-      ks += p.phases;
     };
-    while (ks < nsteps) kstep();
+    // two loop bodies, chosen once per patch
+    if (KW == 3 && al8) {
+      if constexpr (KW == 3)
+        for (int k = nk; k > 0; --k) kstep(std::true_type(), k == 1);
+    } else {
+      for (int k = nk; k > 0; --k) kstep(std::false_type(), k == 1);
+    }
     WTR(4, tk0)
   }
+  // Nothing is in flight behind the loop: every request was waited for by its commit().  The compiler cannot know that the last
+  // patch requested nothing, and where the accumulators end up in a register of that pipeline it waits for the memory counter in
+  // front of EVERY store of the output -- a store then waits for the one before it (vmcnt counts stores as well).  Said once here.
+  __builtin_amdgcn_s_waitcnt(0x0F70);                   // vmcnt(0), the other counters left alone
 #ifdef DFL_WGP_TRACE
   tr[5] = __builtin_amdgcn_s_memtime();
 #endif
@@ -388,23 +457,41 @@ __global__ void __launch_bounds__(256 * KH, KH == 2 ? 4 : 3) wgradp_kernel(const
 
   // ---- waves that split the k-steps of the patches (phases > 1) add their accumulators through LDS, tap by tap, in a
   //      fixed order; the waves of phase 0 then own the workgroup's result for their (cm, cg) pair and kernel row
+  //      Where the scratch holds all KW taps of a wave (red_all, the host's choice) they cross in one pass -- two barriers
+  //      instead of 2 KW; every element is added in the same phase order either way.
   if (p.phases > 1) {
-    float* red = reinterpret_cast<float*>(smem);        // [phases - 1][pairs][KH][16][64]
+    float* red = reinterpret_cast<float*>(smem);        // [phases - 1][pairs][KH][taps per pass][16][64]
+    const int tpp = (KW > 1 && p.red_all) ? KW : 1;     // taps per pass
+    auto put = [&](int t, int i) {                      // tap t into place i of this wave's scratch
+      float* dst = red + (((((phase - 1) * p.pairs + pair) * KH + ty) * tpp + i) * 16) * 64 + lane;
 #pragma unroll
-    for (int t = 0; t < KW; ++t) {
+      for (int r = 0; r < 16; ++r) dst[r * 64] = acc[t][r];
+    };
+    auto get = [&](int t, int i) {
+      for (int ph = 1; ph < p.phases; ++ph) {
+        const float* src = red + (((((ph - 1) * p.pairs + pair) * KH + ty) * tpp + i) * 16) * 64 + lane;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][r] += src[r * 64];
+      }
+    };
+    if (tpp == KW) {
       __syncthreads();
       if (phase > 0) {
-        float* dst = red + ((((phase - 1) * p.pairs + pair) * KH + ty) * 16) * 64 + lane;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) dst[r * 64] = acc[t][r];
+        for (int t = 0; t < KW; ++t) put(t, t);
       }
       __syncthreads();
       if (phase == 0) {
-        for (int ph = 1; ph < p.phases; ++ph) {
-          const float* src = red + ((((ph - 1) * p.pairs + pair) * KH + ty) * 16) * 64 + lane;
 #pragma unroll
-          for (int r = 0; r < 16; ++r) acc[t][r] += src[r * 64];
-        }
+        for (int t = 0; t < KW; ++t) get(t, t);
+      }
+    } else {
+#pragma unroll
+      for (int t = 0; t < KW; ++t) {
+        __syncthreads();
+        if (phase > 0) put(t, 0);
+        __syncthreads();
+        if (phase == 0) get(t, 0);
       }
     }
     if (phase > 0 && p.zslices > 1) return;
@@ -619,8 +706,24 @@ static int wgp_plan(const dfl_wgrad_args* a, WgP* p, bool need_out) {
   p->tab_off = (p->g_off + (ipp * p->IH * p->IW + 2) * p->sg + 255) / 256 * 256;   // (+ 2 pixels: the third read of a row's last run of 8)
   p->lds_bytes = p->tab_off + p->P16 * 4 + 2 * p->CGT * 4 + 3 * p->CMT * 4;
   if ((a->d_mode != 0 || a->bias_partial != nullptr) && p->lds_bytes < 256 * a->KH * 4) p->lds_bytes = 256 * a->KH * 4;   // room for the bias-gradient sums
-  const int red_bytes = (p->phases - 1) * p->pairs * a->KH * 16 * 64 * 4;   // room for the cross-phase sums
+  const int red_bytes = (p->phases - 1) * p->pairs * a->KH * 16 * 64 * 4;   // room for the cross-phase sums, one tap of every wave
   if (p->lds_bytes < red_bytes) p->lds_bytes = red_bytes;
+  // ... and for all KW taps at once where that does not cost a workgroup per CU: the 3x3 kernel has a CU to itself; the
+  // 2x2 kernel shares one between two workgroups (registers) or as many as the 160 KB of LDS hold
+  if (p->phases > 1 && a->KW > 1) {
+    const int red_all = red_bytes * a->KW;
+    const int reg_wgs = wgp_waves_per_simd(a->KH) / a->KH;
+    auto wgs = [&](int bytes) { return std::min(reg_wgs, 160 * 1024 / bytes); };
+    if (red_all <= 150 * 1024 && wgs(std::max(p->lds_bytes, red_all)) == wgs(p->lds_bytes)) {
+      p->red_all = 1;
+      if (p->lds_bytes < red_all) p->lds_bytes = red_all;
+    }
+  }
+  const int NT = 256 * a->KH;
+  auto step_of = [](int k, int H, int W) { return WgStep{k / (H * W), k % (H * W) / W, k % (H * W) % W}; };
+  p->dadv = step_of(NT >> p->dupp_shift, p->PH, p->PW);
+  p->gadv = step_of(NT >> p->gupp_shift, p->IH, p->IW);
+  p->tadv = step_of(NT, p->PH, p->PW);
   return DFL_OK;
 }
 
