@@ -3,9 +3,9 @@ the 3D annotation and the ground-truth poses of the full-resolution file, on the
 
 The geometry is float64 on the host, chained as the reference's full_res_3d_viz.py chains its matrices
 (examples/full_res_3d_viz.py restates that chain); the rays are cast by csrc/drr.hip (dfl_drr_render).  DESIGN.md
-section 15 states the semantics, tests/drr_ref.py restates them in numpy.
+section 15 states the semantics, tests/drr_ref.py restates them in numpy.  The file is read through dfl_amd.fullres.
 
-    K = proj-params/intrinsic, E = proj-params/extrinsic, P_o = gt-poses/cam-to-{pelvis,left-femur,right-femur}-vol
+    K, E = the intrinsic and extrinsic matrix of proj-params, P_o = the projection's cam-to-{pelvis,left-femur,right-femur}-vol
     I2P = [dir-mat * spacing | origin] of the volume; index coordinates are (x, y, z) = (column, row, slice)
     C2I_o = inv(I2P) P_o inv(E)                      camera projective frame -> volume index coordinates
     ray of output pixel (c, r): q = -inv(K) G [c, r, 1]; o = C2I_o[:3, 3]; d = C2I_o[:3, :3] q; points o + t d, t >= 0;
@@ -33,12 +33,12 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from . import preprocess
+from . import fullres, preprocess
+from .fullres import POSES
 
-__all__ = ['Obj', 'Grid', 'Geometry', 'Volume', 'geometry', 'training_grid', 'default_objects', 'pack_objects', 'render', 'render_args',
-           'project_points', 'hu_to_mu', 'label_mask', 'POSES', 'DEFAULT_MASKS']
+__all__ = ['Obj', 'Grid', 'Geometry', 'Volume', 'geometry', 'read_volume', 'training_grid', 'default_objects', 'pack', 'pack_objects',
+           'render', 'render_args', 'args_for_records', 'project', 'project_points', 'hu_to_mu', 'label_mask', 'POSES', 'DEFAULT_MASKS']
 
-POSES = ('cam-to-pelvis-vol', 'cam-to-left-femur-vol', 'cam-to-right-femur-vol')
 # labels of the 3D annotation: 1, 2 hemipelves, 3 vertebrae, 4 sacrum, 5, 6 femurs
 DEFAULT_MASKS = ((1, 2, 3, 4), (5,), (6,))
 OBJECT_DTYPE = np.dtype([('o', np.float32, 3), ('M', np.float32, 9), ('box_lo', np.int32, 3), ('box_hi', np.int32, 3),
@@ -116,33 +116,35 @@ def default_objects(E, poses, I2P, bones_only=True):
     return obs
 
 
-def _get(src, path):
-    return np.asarray(src.get(path))
-
-
 def geometry(src, spec, proj, crop=0, factor=1, rot180=None, bones_only=True):
-    """The float64 matrices of projection `proj` of specimen `spec`, read from src (get(path) -> array: the Source of
-    examples/make_full_res_overlays.py), its objects and its output grid.  rot180=None reads 'rot-180-for-up'."""
-    K = _get(src, 'proj-params/intrinsic').astype(np.float64).reshape(3, 3)
-    E = _get(src, 'proj-params/extrinsic').astype(np.float64).reshape(4, 4)
-    rows = int(_get(src, 'proj-params/num-rows').reshape(-1)[0])
-    cols = int(_get(src, 'proj-params/num-cols').reshape(-1)[0])
-    pfx = '%s/projections/%03d/' % (spec, int(proj))
-    poses = {k: _get(src, pfx + 'gt-poses/' + k).astype(np.float64).reshape(4, 4) for k in POSES}
-    I2P = inds_to_phys(_get(src, spec + '/vol/dir-mat'), _get(src, spec + '/vol/spacing'), _get(src, spec + '/vol/origin'))
+    """The float64 matrices of projection `proj` of specimen `spec`, read from src (a fullres.Source, or anything with
+    its get(path)), its objects and its output grid.  rot180=None reads the projection's own flag."""
+    K, E, rows, cols = fullres.proj_params(src)
+    pfx = fullres.projection_prefix(spec, proj)
+    poses = fullres.gt_poses(src, pfx)
+    I2P = inds_to_phys(*fullres.volume_frame(src, spec))
     if rot180 is None:
-        rot180 = bool(_get(src, pfx + 'rot-180-for-up').reshape(-1)[0])
+        rot180 = fullres.rot180(src, pfx)
     G, (H, W) = training_grid(rows, cols, crop, factor, rot180)
     return Geometry(K, E, poses, I2P, G, default_objects(E, poses, I2P, bones_only), Grid(-np.linalg.inv(K) @ G, H, W))
 
 
-def project_points(geom, xyz):
-    """3D points of the volume's physical frame, [L, 3] (or [3]), -> [2, L] (column, row) on the output grid, float64."""
+def _project(K, E, P, xyz):
     X = np.asarray(xyz, np.float64).reshape(-1, 3)
-    cam = (geom.E @ np.linalg.inv(geom.poses[POSES[0]])) @ np.concatenate([X, np.ones((X.shape[0], 1))], 1).T
-    p = geom.K @ cam[:3]
-    p = p / p[2:3]
-    return (np.linalg.inv(geom.G) @ p)[:2]
+    cam = (E @ np.linalg.inv(P)) @ np.concatenate([X, np.ones((X.shape[0], 1))], 1).T
+    p = K @ cam[:3]
+    return p / p[2:3]
+
+
+def project(K, E, P, xyz):
+    """3D points of the volume's physical frame, [L, 3] (or [3]), -> detector (column, row) [2, L], float64: K (E inv(P) X)
+    divided by its third component."""
+    return _project(K, E, P, xyz)[:2]
+
+
+def project_points(geom, xyz):
+    """project() under geom's pelvis pose, pulled through inv(G): [2, L] (column, row) on the output grid."""
+    return (np.linalg.inv(geom.G) @ _project(geom.K, geom.E, geom.poses[POSES[0]], xyz))[:2]
 
 
 def hu_to_mu(vol, mu_water=0.02):
@@ -217,44 +219,67 @@ def _views(objects):
     return views, True
 
 
-def pack_objects(volume, objects, grid, interp='exact', tight_boxes=True):
+def read_volume(src, spec, dev, cast_labels=False):
+    """The drr.Volume of a specimen of the full-resolution file on `dev`: mu from 'vol/pixels' (Hounsfield units), the
+    labels from 'vol-seg/image/pixels'.  Labels that are not uint8 are refused, or cast with cast_labels=True."""
+    hu = np.asarray(src.get(spec + '/vol/pixels'))
+    lab = np.asarray(src.get(spec + '/vol-seg/image/pixels'))
+    if hu.ndim != 3 or lab.shape != hu.shape:
+        raise nat.DflError('%s: vol/pixels has shape %s, vol-seg/image/pixels %s: two equal [z, y, x] volumes expected'
+                           % (spec, hu.shape, lab.shape))
+    if cast_labels:
+        lab = lab.astype(np.uint8, copy=False)
+    elif lab.dtype != np.uint8:
+        raise nat.DflError('%s/vol-seg/image/pixels has dtype %s: uint8 expected' % (spec, lab.dtype))
+    mu = hu_to_mu(torch.from_numpy(np.ascontiguousarray(hu.astype(np.float32, copy=False))).to(dev))
+    return Volume(mu, torch.from_numpy(np.ascontiguousarray(lab)).to(dev))
+
+
+def pack(volume, c2is, masks, grid, interp='exact', tight_boxes=True):
     """The fp32 argument records of the kernel, a numpy array [views, n_obj] of OBJECT_DTYPE, rounded from float64:
-    o = C2I[:3, 3], M = C2I[:3, :3] Q, the object's box and mask.  Trilinear samples reach half a voxel past the voxels
-    they read, so their tight boxes are one voxel wider (clipped to the volume)."""
-    views, _ = _views(objects)
-    out = np.zeros((len(views), len(views[0])), OBJECT_DTYPE)
-    (flo, fhi) = volume.full_box
-    for v, obs in enumerate(views):
-        for n, ob in enumerate(obs):
-            lo, hi = volume.box(ob.mask) if tight_boxes else (flo, fhi)
-            if tight_boxes and interp == 'trilinear' and hi[0] >= lo[0]:
-                lo = tuple(max(a - 1, 0) for a in lo)
-                hi = tuple(min(a + 1, b) for a, b in zip(hi, fhi))
-            out[v, n]['o'] = ob.c2i[:3, 3]
-            out[v, n]['M'] = (ob.c2i[:3, :3] @ grid.Q).reshape(-1)
-            out[v, n]['box_lo'], out[v, n]['box_hi'], out[v, n]['mask'] = lo, hi, ob.mask
+    o = C2I[:3, 3], M = C2I[:3, :3] Q, the object's box and mask.  c2is is [views, n_obj, 4, 4] float64; masks (integers,
+    as Obj.mask) is [n_obj], or [views, n_obj] where the views differ.  Trilinear samples reach half a voxel past the
+    voxels they read, so their tight boxes are one voxel wider (clipped to the volume)."""
+    A, m = np.asarray(c2is, np.float64), np.asarray(masks)
+    if A.ndim != 4 or A.shape[2:] != (4, 4) or A.shape[0] < 1 or A.shape[1] < 1 or m.shape not in (A.shape[1:2], A.shape[:2]):
+        raise nat.DflError('drr.pack: c2is of shape %s for masks of shape %s: [views, n_obj, 4, 4] and [n_obj] or [views, n_obj] '
+                           'expected' % (A.shape, m.shape))
+    flat = m.ravel().tolist()
+    if m.dtype.kind not in 'iu' or not all(0 <= x <= 0xffff for x in flat):
+        raise nat.DflError('drr.pack: masks must be integers of 16 bits (labels 0..15; label_mask makes one of a set of labels)')
+    flo, fhi = volume.full_box
+    boxes = {}
+    for mask in set(flat):
+        lo, hi = volume.box(mask) if tight_boxes else (flo, fhi)
+        if tight_boxes and interp == 'trilinear' and hi[0] >= lo[0]:
+            lo = tuple(max(a - 1, 0) for a in lo)
+            hi = tuple(min(a + 1, b) for a, b in zip(hi, fhi))
+        boxes[mask] = lo, hi
+    out = np.zeros(A.shape[:2], OBJECT_DTYPE)
+    out['o'] = A[:, :, :3, 3]
+    out['M'] = (A[:, :, :3, :3] @ grid.Q).reshape(A.shape[0], A.shape[1], 9)
+    out['mask'] = m                                                            # masks [n_obj] serve every view, and so do their boxes
+    out['box_lo'] = np.array([boxes[x][0] for x in flat], np.int32).reshape(m.shape + (3,))
+    out['box_hi'] = np.array([boxes[x][1] for x in flat], np.int32).reshape(m.shape + (3,))
     return out
 
 
-def render_args(volume, objects, grid, interp='exact', step_mm=0.5, want_plen=False, want_labels=True, min_len_mm=1.0,
-                tight_boxes=True, mapping=0):
-    """(DrrArgs, (att, plen, labels) with the view axis, tensors to keep alive): the argument block of dfl_drr_render
-    and its freshly allocated outputs, nothing launched -- render() below, and tools/bench_drr.py for repeated calls."""
-    if not isinstance(volume, Volume):
-        raise nat.DflError('drr.render needs a drr.Volume (device tensors; no CPU path)')
-    if interp not in _INTERP:
-        raise nat.DflError("drr.render: interp must be 'exact' or 'trilinear', got %r" % (interp,))
-    if not float(step_mm) > 0:
-        raise nat.DflError('drr.render: step_mm must be positive, got %r' % (step_mm,))
-    if not float(min_len_mm) >= 0:
-        raise nat.DflError('drr.render: min_len_mm must not be negative, got %r' % (min_len_mm,))
-    recs = pack_objects(volume, objects, grid, interp, tight_boxes)
+def pack_objects(volume, objects, grid, interp='exact', tight_boxes=True):
+    """pack() of [Obj], or of [[Obj]] with a leading view axis."""
+    views, _ = _views(objects)
+    return pack(volume, [[ob.c2i for ob in obs] for obs in views], [[ob.mask for ob in obs] for obs in views], grid, interp,
+                tight_boxes)
+
+
+def args_for_records(volume, recs, grid, interp='exact', step_mm=0.5, want_plen=False, want_labels=True, min_len_mm=1.0, mapping=0):
+    """(DrrArgs, (att, plen, labels) with the view axis, tensors to keep alive) for packed records [views, n_obj]: the
+    upload, the freshly allocated outputs and the argument block of dfl_drr_render, nothing launched."""
     V, n_obj = recs.shape
     exact = interp == 'exact'
     dev = volume.mu.device
     H, W, NL = grid.H, grid.W, volume.n_labels
     nz, ny, nx = volume.shape
-    d_objs = torch.from_numpy(recs.view(np.uint8).reshape(-1).copy()).to(dev)
+    d_objs = torch.from_numpy(np.ascontiguousarray(recs).view(np.uint8).reshape(-1)).to(dev)
     att = torch.empty((V, H, W), dtype=torch.float32, device=dev)
     plen = torch.empty((V, NL, H, W), dtype=torch.float32, device=dev) if exact and want_plen else None
     lab = torch.empty((V, H, W), dtype=torch.uint8, device=dev) if exact and want_labels else None
@@ -263,6 +288,22 @@ def render_args(volume, objects, grid, interp='exact', step_mm=0.5, want_plen=Fa
                     nx=nx, ny=ny, nz=nz, H=H, W=W, views=V, n_obj=n_obj, n_labels=NL, interp=_INTERP[interp],
                     mapping=int(mapping), step_mm=float(step_mm), min_len_mm=float(min_len_mm))
     return a, (att, plen, lab), [d_objs, volume]
+
+
+def render_args(volume, objects, grid, interp='exact', step_mm=0.5, want_plen=False, want_labels=True, min_len_mm=1.0,
+                tight_boxes=True, mapping=0):
+    """args_for_records of pack_objects(objects), after the checks of render() -- render() below, and tools/bench_drr.py
+    for repeated calls."""
+    if not isinstance(volume, Volume):
+        raise nat.DflError('drr.render needs a drr.Volume (device tensors; no CPU path)')
+    if interp not in _INTERP:
+        raise nat.DflError("drr.render: interp must be 'exact' or 'trilinear', got %r" % (interp,))
+    if not float(step_mm) > 0:
+        raise nat.DflError('drr.render: step_mm must be positive, got %r' % (step_mm,))
+    if not float(min_len_mm) >= 0:
+        raise nat.DflError('drr.render: min_len_mm must not be negative, got %r' % (min_len_mm,))
+    return args_for_records(volume, pack_objects(volume, objects, grid, interp, tight_boxes), grid, interp, step_mm, want_plen,
+                            want_labels, min_len_mm, mapping)
 
 
 def render(volume, objects, grid, interp='exact', step_mm=0.5, want_plen=False, want_labels=True, min_len_mm=1.0,

@@ -1,9 +1,10 @@
 """Training files from the full-resolution dataset.
 
 The reference's README says how its preprocessed files were made from the full-resolution file -- crop 50 pixels from
-each border, log-transform, rotate by 180 degrees where 'rot-180-for-up' is set, downsample by 2, 4, 8 or 16 -- but
-the program that did it is not part of the reference.  This module is that step (DESIGN.md section 14 pins the
-arithmetic; tests/preproc_ref.py restates it in numpy), and its inverse for labels and landmarks:
+each border, log-transform, rotate by 180 degrees where the projection's flag (rot180 in dfl_amd.fullres) is set,
+downsample by 2, 4, 8 or 16 -- but the program that did it is not part of the reference.  This module is that step
+(DESIGN.md section 14 pins the arithmetic; tests/preproc_ref.py restates it in numpy), and its inverse for labels and
+landmarks:
 
     crop window   rows crop .. R-crop-1, columns likewise: Rc x Cc = (R - 2 crop) x (C - 2 crop)
     rotation      cropped pixel (r, c) -> (Rc-1-r, Cc-1-c) where the flag is set
@@ -17,15 +18,11 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from . import fullres, h5lite
+from .fullres import SPECIMEN_ORDER, LAND_ORDER, specimen_order, land_order  # noqa: F401  (defined there, used from here)
 
 __all__ = ['out_size', 'map_lands', 'unmap_lands', 'preprocess_projs', 'preprocess_segs', 'restore_labels',
-           'convert_file', 'SPECIMEN_ORDER', 'LAND_ORDER']
-
-# README of the reference: the preprocessed files number the specimens 01..06 in this order
-SPECIMEN_ORDER = ['17-1882', '18-1109', '18-0725', '18-2799', '18-2800', '17-1905']
-# the reference's landmark list (land-00 .. land-13 of its preprocessed files)
-LAND_ORDER = ['FH-l', 'FH-r', 'GSN-l', 'GSN-r', 'IOF-l', 'IOF-r', 'MOF-l', 'MOF-r', 'SPS-l', 'SPS-r', 'IPS-l', 'IPS-r',
-              'ASIS-l', 'ASIS-r']
+           'convert_file', 'write_land_names', 'create_specimen', 'SPECIMEN_ORDER', 'LAND_ORDER']
 
 
 def _check(R, C, crop, factor):
@@ -154,94 +151,79 @@ def restore_labels(labels, rot180, R, C, crop=50, factor=8):
 
 
 # ---- the full-resolution file -> the preprocessed file ----------------------------------------------------------------
-def specimen_order(ids):
-    """The README's numbering when exactly its six specimens are present, else sorted."""
-    ids = list(ids)
-    return list(SPECIMEN_ORDER) if sorted(ids) == sorted(SPECIMEN_ORDER) else sorted(ids)
+def write_land_names(out, names):
+    """The 'land-names' group of a training file: 'num-lands' and 'land-XX'."""
+    g = out.create_group('land-names')
+    g['num-lands'] = len(names)
+    for l, name in enumerate(names):
+        g['land-%02d' % l] = name
 
 
-def land_order(present):
-    """The reference's list filtered to the names present, then any other names, sorted."""
-    present = set(present)
-    return [n for n in LAND_ORDER if n in present] + sorted(present - set(LAND_ORDER))
-
-
-def _scalar(v):
-    return np.asarray(v).reshape(-1)[0]
+def create_specimen(out, index, n, Ro, Co, compression=None):
+    """(group name 'NN', its 'projs' float32 and 'segs' uint8 datasets [n, Ro, Co], one image per chunk) of specimen
+    number `index` (from 1) of a training file; the caller fills them and writes 'NN/lands'."""
+    grp = '%02d' % index
+    kw = dict(compression='gzip') if compression else {}
+    d_projs = out.create_dataset(grp + '/projs', (n, Ro, Co), dtype='f4', chunks=(1, Ro, Co), **kw)
+    d_segs = out.create_dataset(grp + '/segs', (n, Ro, Co), dtype='u1', chunks=(1, Ro, Co), **kw)
+    return grp, d_projs, d_segs
 
 
 def convert_file(src, dst, factor=8, crop=50, specimens=None, land_names=None, chunk=32, compression=None, log=True,
                  min_intensity=1.0, device=None, report=None):
-    """Full-resolution layout ('proj-params', '<id>/projections/NNN/{image/pixels, gt-seg/pixels, gt-landmarks/<name>,
-    rot-180-for-up}') -> preprocessed layout ('land-names/num-lands', 'land-names/land-XX', 'NN/projs' float32,
-    'NN/segs' uint8, 'NN/lands' float32 [N, 2, L] with row 0 the column), both through h5lite, `chunk` projections on the
+    """Full-resolution layout (dfl_amd.fullres) -> preprocessed layout ('land-names/num-lands', 'land-names/land-XX',
+    'NN/projs' float32, 'NN/segs' uint8, 'NN/lands' float32 [N, 2, L] with row 0 the column), `chunk` projections on the
     device at a time.  Returns [(specimen id, index, projections, (Ro, Co))]; report(line) gets one line per specimen."""
-    from . import h5lite
     if not torch.cuda.is_available():
         raise nat.DflError('preprocess.convert_file: no GPU visible (the reduction runs in HIP kernels; no CPU path)')
     dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
     if int(chunk) < 1:
         raise nat.DflError('preprocess.convert_file: chunk must be at least 1')
-    f = h5lite.File(src, 'r')
+    f = fullres.Source(src)
     try:
-        R = int(_scalar(f['proj-params/num-rows'][()]))
-        Cn = int(_scalar(f['proj-params/num-cols'][()]))
+        R, Cn = fullres.detector_size(f)
         Ro, Co = out_size(R, Cn, crop, factor)
-        found = [k for k in f.keys() if k != 'proj-params']
-        if specimens is None:
-            specimens = specimen_order(found)
-        else:
-            specimens = list(specimens)
-            missing = [s for s in specimens if s not in found]
-            if missing:
-                raise nat.DflError('preprocess.convert_file: %s has no specimen %s' % (src, ', '.join(missing)))
-        if not specimens:
-            raise nat.DflError('preprocess.convert_file: %s holds no specimen' % src)
-        counts = {s: len(f[s + '/projections'].keys()) for s in specimens}
+        specimens = fullres.specimens(f, specimens, 'preprocess.convert_file: %s' % src)
+        counts = {s: fullres.n_projections(f, s) for s in specimens}
         if land_names is None:
             present = set()
             for s in specimens:
                 for p in range(counts[s]):
-                    present.update(f['%s/projections/%03d/gt-landmarks' % (s, p)].keys())
+                    present.update(f.children(fullres.projection_prefix(s, p) + 'gt-landmarks'))
             land_names = land_order(present)
         land_names = list(land_names)
         L = len(land_names)
         done = []
         out = h5lite.File(dst, 'w')
         try:
-            g = out.create_group('land-names')
-            g['num-lands'] = L
-            for l, name in enumerate(land_names):
-                g['land-%02d' % l] = name
-            kw = dict(compression='gzip') if compression else {}
+            write_land_names(out, land_names)
             for k, s in enumerate(specimens):
-                num, grp = counts[s], '%02d' % (k + 1)
+                num = counts[s]
                 if num < 1:
                     raise nat.DflError('preprocess.convert_file: specimen %s has no projections' % s)
-                d_projs = out.create_dataset(grp + '/projs', (num, Ro, Co), dtype='f4', chunks=(1, Ro, Co), **kw)
-                d_segs = out.create_dataset(grp + '/segs', (num, Ro, Co), dtype='u1', chunks=(1, Ro, Co), **kw)
+                grp, d_projs, d_segs = create_specimen(out, k + 1, num, Ro, Co, compression)
                 lands = np.zeros((num, 2, L), np.float64)
                 flags = []
                 for p0 in range(0, num, int(chunk)):
                     imgs, segs, rots = [], [], []
                     for p in range(p0, min(p0 + int(chunk), num)):
-                        pfx = '%s/projections/%03d/' % (s, p)
-                        img = np.asarray(f[pfx + 'image/pixels'][()])
-                        seg = np.asarray(f[pfx + 'gt-seg/pixels'][()])
+                        pfx = fullres.projection_prefix(s, p)
+                        img = np.asarray(f.get(pfx + 'image/pixels'))
+                        seg = np.asarray(f.get(pfx + 'gt-seg/pixels'))
                         if img.shape != (R, Cn) or seg.shape != (R, Cn):
                             raise nat.DflError('preprocess.convert_file: %s is %s / %s, proj-params say %s'
                                                % (pfx, img.shape, seg.shape, (R, Cn)))
                         if img.dtype != np.uint16:
                             img = img.astype(np.float32, copy=False)
-                        have = f[pfx + 'gt-landmarks'].keys()
+                        have = fullres.gt_landmarks(f, pfx, land_names)
                         for l, name in enumerate(land_names):
                             if name not in have:
                                 raise nat.DflError('preprocess.convert_file: specimen %s, projection %03d has no landmark %s'
                                                    % (s, p, name))
-                            lands[p, :, l] = np.asarray(f[pfx + 'gt-landmarks/' + name][()], np.float64).reshape(-1)[:2]
+                            lands[p, :, l] = have[name]
                         imgs.append(img)
                         segs.append(seg.astype(np.uint8, copy=False))
-                        rots.append(bool(_scalar(f[pfx + 'rot-180-for-up'][()])))
+                        rots.append(fullres.rot180(f, pfx))
                     if len({im.dtype for im in imgs}) > 1:          # uint16 next to float pixels: all as fp32, said out loud
                         imgs = [im.astype(np.float32) for im in imgs]
                     px = torch.from_numpy(np.stack(imgs)).to(dev)

@@ -3,8 +3,9 @@ parameters whose cost is the gradient-NCC between rendered DRRs and the fixed im
 
 The geometry is float64 numpy on the host, as in dfl_amd.drr; the pixels stay on the device.  One generation of the
 optimiser is one dfl_drr_render launch (trilinear, tight boxes, lambda views), one dfl_sim_gradncc launch
-(csrc/sim.hip) and one copy of lambda doubles to the host.  DESIGN.md section 16 states the semantics of the
-similarity; tests/reg_ref.py restates them in numpy float64.
+(csrc/sim.hip) and one copy of lambda doubles to the host; the records and the argument block of the render are
+drr.pack and drr.args_for_records.  DESIGN.md section 16 states the semantics of the similarity; tests/reg_ref.py
+restates them in numpy float64.
 
     D(theta) = [[R, centre - R centre + theta[3:]], [0, 1]],  R = exp(rot_unit theta[:3])      (pose_delta)
     P(theta) = D(theta) P0                                   a cam-to-*-vol matrix as in gt-poses
@@ -13,8 +14,6 @@ similarity; tests/reg_ref.py restates them in numpy float64.
 With rot_unit 0.02 one unit of any parameter moves a point 50 mm from the centre by about 1 mm, so one sigma serves
 all six.  Tensors on the CPU are refused: there is no CPU path.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -265,26 +264,6 @@ def _device_image(t, what, dims, dtypes=(torch.float32,)):
     return t.detach().contiguous()
 
 
-def pack_poses(volume, c2is, masks, grid, interp='exact', tight_boxes=True):
-    """drr.pack_objects for an array of poses: c2is [views, n_obj, 4, 4] float64 and one mask per object -> the same
-    bytes, with batched numpy products in place of the loop over views x objects."""
-    A = np.asarray(c2is, np.float64)
-    if A.ndim != 4 or A.shape[2:] != (4, 4) or A.shape[1] != len(masks) or A.shape[0] < 1 or A.shape[1] < 1:
-        raise nat.DflError('register.pack_poses: c2is of shape %s for %d masks: [views, n_obj, 4, 4] expected' % (A.shape, len(masks)))
-    out = np.zeros(A.shape[:2], drr.OBJECT_DTYPE)
-    flo, fhi = volume.full_box
-    out['o'] = A[:, :, :3, 3]
-    out['M'] = (A[:, :, :3, :3] @ grid.Q).reshape(A.shape[0], A.shape[1], 9)
-    for n, mask in enumerate(masks):
-        mask = drr.Obj(np.eye(4), mask).mask
-        lo, hi = volume.box(mask) if tight_boxes else (flo, fhi)
-        if tight_boxes and interp == 'trilinear' and hi[0] >= lo[0]:
-            lo = tuple(max(a - 1, 0) for a in lo)
-            hi = tuple(min(a + 1, b) for a, b in zip(hi, fhi))
-        out['box_lo'][:, n], out['box_hi'][:, n], out['mask'][:, n] = lo, hi, mask
-    return out
-
-
 class Similarity:
     """The gradient-NCC cost of `views` moving images against one fixed image [H, W] (float32, on the GPU) with an
     optional uint8 [H, W] mask: dfl_sim_prepare runs here, once; cost(moving) is one dfl_sim_gradncc launch and
@@ -355,21 +334,14 @@ class _Level:
 
     def costs(self, c2is, masks):
         """[views <= lambda, n_obj, 4, 4] -> float64 [views] on the host: one render, one similarity launch, one copy."""
-        recs = pack_poses(self.volume, c2is, masks, self.grid, 'trilinear', True)
-        V, n_obj = recs.shape
-        dev = self.volume.mu.device
-        nz, ny, nx = self.volume.shape
-        d_objs = torch.from_numpy(recs.view(np.uint8).reshape(-1)).to(dev)
-        att = torch.empty((V, self.grid.H, self.grid.W), dtype=torch.float32, device=dev)
-        a = nat.DrrArgs(mu=self.volume.mu.data_ptr(), labels=self.volume.labels.data_ptr(), objects=d_objs.data_ptr(),
-                        att=att.data_ptr(), plen=None, label_map=None, qscale=(nat.f32 * 9)(*self.grid.Q.astype(np.float32).reshape(-1)),
-                        nx=nx, ny=ny, nz=nz, H=self.grid.H, W=self.grid.W, views=V, n_obj=n_obj, n_labels=self.volume.n_labels,
-                        interp=nat.DRR_TRILINEAR, mapping=0, step_mm=self.step_mm, min_len_mm=1.0)
+        recs = drr.pack(self.volume, c2is, masks, self.grid, 'trilinear', True)
+        a, (att, _, _), keep = drr.args_for_records(self.volume, recs, self.grid, 'trilinear', self.step_mm)
+        V, dev = recs.shape[0], att.device
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
             nat.call('dfl_drr_render', a, stream)
             nat.call('dfl_sim_gradncc', self.sim.args(att), stream)
-        return self.sim.out[:V].cpu().numpy()
+        return self.sim.out[:V].cpu().numpy()                       # the copy waits for both launches: `keep` lives until then
 
 
 def register(volume, geom, fixed, moving=(0, 1, 2), theta0=None, P0=None, levels=None, popsize=16, generations=80, sigma0=2.0,

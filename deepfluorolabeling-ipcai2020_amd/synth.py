@@ -3,7 +3,7 @@ detector images by csrc/expose.hip (dfl_drr_expose) and written as a full-resolu
 'gt-seg', 'gt-landmarks' and 'gt-poses' are exact by construction.  DESIGN.md section 17 is the specification;
 tests/expose_ref.py restates the detector model in numpy.
 
-Poses (float64 numpy on the host; P_o = gt-poses/cam-to-*-vol maps the camera world frame to the volume):
+Poses (float64 numpy on the host; P_o = the acquired cam-to-*-vol (fullres.gt_poses) maps the camera world frame to the volume):
 
     seed          synthetic view n starts from acquired projection n mod (number of acquired projections)
     common motion Wm = register.pose_delta([w, t_w], c_w, rot_unit=1): the rotation exp(hat w) about c_w, then the
@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from . import drr, preprocess, register
+from . import drr, fullres, h5lite, preprocess, register
 
 __all__ = ['gaussian_taps', 'noise_keys', 'expose', 'expose_args', 'draw_motion', 'apply_motion', 'lands_in_window', 'fov_flags',
            'sample_pose', 'sample_poses', 'synthesize', 'MAX_DRAWS', 'DEFAULTS']
@@ -126,16 +126,12 @@ def draw_motion(rng, rot_sigma_deg=DEFAULTS['rot_sigma_deg'], trans_sigma_mm=DEF
     return {'rot_deg': z[0:3] * float(rot_sigma_deg), 'trans_mm': z[3:6] * ts, 'femur_deg': z[6:12].reshape(2, 3) * float(femur_sigma_deg)}
 
 
-def _homog(x):
-    return np.concatenate([np.asarray(x, np.float64).reshape(3), [1.0]])
-
-
 def apply_motion(poses, E, lands3d, motion):
     """The seed poses {name: P} under one draw: {name: P''} (module docstring)."""
     P = {k: np.asarray(poses[k], np.float64).reshape(4, 4) for k in drr.POSES}
     E = np.asarray(E, np.float64).reshape(4, 4)
     pts = np.array([np.asarray(v, np.float64).reshape(-1)[:3] for v in lands3d.values()]).reshape(-1, 3)
-    c_w = (np.linalg.inv(P[drr.POSES[0]]) @ _homog(pts.mean(0)))[:3]
+    c_w = (np.linalg.inv(P[drr.POSES[0]]) @ np.append(pts.mean(0), 1.0))[:3]
     theta = np.concatenate([np.radians(motion['rot_deg']), E[:3, :3].T @ np.asarray(motion['trans_mm'], np.float64)])
     back = np.linalg.inv(register.pose_delta(theta, c_w, 1.0))
     out = {k: P[k] @ back for k in drr.POSES}
@@ -147,17 +143,9 @@ def apply_motion(poses, E, lands3d, motion):
     return out
 
 
-def _project(K, E, P, xyz):
-    """3D points of the volume's physical frame [L, 3] -> detector (column, row) [2, L]: K (E inv(P) X), as drr.project_points."""
-    X = np.asarray(xyz, np.float64).reshape(-1, 3)
-    cam = (E @ np.linalg.inv(P)) @ np.concatenate([X, np.ones((X.shape[0], 1))], 1).T
-    p = K @ cam[:3]
-    return (p / p[2:3])[:2]
-
-
 def lands_in_window(K, E, P_pelvis, lands3d, rows, cols, crop):
     """How many 3D landmarks project inside the crop window under the pelvis pose."""
-    uv = _project(K, E, P_pelvis, [np.asarray(v, np.float64).reshape(-1)[:3] for v in lands3d.values()])
+    uv = drr.project(K, E, P_pelvis, [np.asarray(v, np.float64).reshape(-1)[:3] for v in lands3d.values()])
     ok = (uv[0] >= crop) & (uv[0] <= cols - 1 - crop) & (uv[1] >= crop) & (uv[1] <= rows - 1 - crop) & np.isfinite(uv).all(0)
     return int(ok.sum())
 
@@ -169,7 +157,7 @@ def fov_flags(K, E, poses, lands3d, rows, cols, seed_flags=(0, 0)):
         if name not in lands3d:
             out.append(int(seed_flags[side]))
             continue
-        uv = _project(K, E, poses[drr.POSES[1 + side]], np.asarray(lands3d[name], np.float64).reshape(-1)[:3])[:, 0]
+        uv = drr.project(K, E, poses[drr.POSES[1 + side]], np.asarray(lands3d[name], np.float64).reshape(-1)[:3])[:, 0]
         out.append(int(0 <= uv[0] <= cols - 1 and 0 <= uv[1] <= rows - 1))
     return tuple(out)
 
@@ -202,26 +190,21 @@ def sample_poses(seed, specimen_index, specimen, seeds, views, K, E, lands3d, ro
 
 
 # ---- the pipeline ------------------------------------------------------------------------------------------------------
-def _scalar(v):
-    return np.asarray(v).reshape(-1)[0]
-
-
-def _copy(src, out, path):
-    """Copy group or dataset `path` of an open h5lite file into the writer, as it is stored."""
-    from . import h5lite
-    node = src[path]
+def _copy(src, out, path, to=None):
+    """Copy group or dataset `path` of an open h5lite file into the writer (at `to`), as it is stored."""
+    node, to = src[path], to or path
     if isinstance(node, h5lite.Group):
-        out.create_group(path)
+        out.create_group(to)
         for k in node.keys():
-            _copy(src, out, path.rstrip('/') + '/' + k)
+            _copy(src, out, path.rstrip('/') + '/' + k, to.rstrip('/') + '/' + k)
         return
     v = node[()]
     if isinstance(v, (bytes, str)):
-        out[path] = v
+        out[to] = v
     elif np.asarray(v).dtype.kind in 'iuf':
-        out[path] = np.asarray(v)
+        out[to] = np.asarray(v)
     else:
-        out.create_dataset(path, data=np.asarray(v), dtype=np.asarray(v).dtype)
+        out.create_dataset(to, data=np.asarray(v), dtype=np.asarray(v).dtype)
 
 
 def synthesize(src, dst, views, seed=0, layout='preprocessed', specimens=None, crop=50, factor=8,
@@ -235,7 +218,6 @@ def synthesize(src, dst, views, seed=0, layout='preprocessed', specimens=None, c
     preprocess.convert_file(crop, factor) makes of it, without the detour.  crop also bounds the acceptance window;
     factor is used by 'preprocessed' only.  Returns [(specimen id, index, views, rejected draws)]; report(line) gets one
     line per specimen."""
-    from . import h5lite
     if layout not in ('full-res', 'preprocessed'):
         raise nat.DflError("synth.synthesize: layout must be 'full-res' or 'preprocessed', got %r" % (layout,))
     if not torch.cuda.is_available():
@@ -246,25 +228,14 @@ def synthesize(src, dst, views, seed=0, layout='preprocessed', specimens=None, c
     dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
     views, chunk, pre = int(views), int(chunk), layout == 'preprocessed'
     kw_pose = dict(rot_sigma_deg=rot_sigma_deg, trans_sigma_mm=trans_sigma_mm, femur_sigma_deg=femur_sigma_deg, min_lands=min_lands)
-    f = h5lite.File(src, 'r')
+    f = fullres.Source(src)
     try:
-        K = np.asarray(f['proj-params/intrinsic'][()], np.float64).reshape(3, 3)
-        E = np.asarray(f['proj-params/extrinsic'][()], np.float64).reshape(4, 4)
-        R = int(_scalar(f['proj-params/num-rows'][()]))
-        Cn = int(_scalar(f['proj-params/num-cols'][()]))
+        if not pre and f.h5 is None:
+            raise nat.DflError("synth.synthesize: layout 'full-res' copies groups as they are stored and needs an HDF5 source, not .npz")
+        K, E, R, Cn = fullres.proj_params(f)
         Ro, Co = preprocess.out_size(R, Cn, crop, factor if pre else 1)
-        found = [k for k in f.keys() if k != 'proj-params']
-        if specimens is None:
-            specimens = preprocess.specimen_order(found)
-        else:
-            specimens = list(specimens)
-            missing = [s for s in specimens if s not in found]
-            if missing:
-                raise nat.DflError('synth.synthesize: %s has no specimen %s' % (src, ', '.join(missing)))
-        if not specimens:
-            raise nat.DflError('synth.synthesize: %s holds no specimen' % src)
-        lands3d = {s: {n: np.asarray(f['%s/vol-landmarks/%s' % (s, n)][()], np.float64).reshape(-1)[:3]
-                       for n in f[s + '/vol-landmarks'].keys()} for s in specimens}
+        specimens = fullres.specimens(f, specimens, 'synth.synthesize: %s' % src)
+        lands3d = {s: fullres.volume_landmarks(f, s) for s in specimens}
         land_names = preprocess.land_order(set().union(*[set(v) for v in lands3d.values()]))
         if pre:
             for s in specimens:
@@ -272,47 +243,31 @@ def synthesize(src, dst, views, seed=0, layout='preprocessed', specimens=None, c
                 if lack:
                     raise nat.DflError('synth.synthesize: specimen %s has no landmark %s' % (s, ', '.join(lack)))
         grid = drr.Grid(-np.linalg.inv(K), R, Cn)                          # the full detector grid: G = identity
-        kw = dict(compression='gzip') if compression else {}
-        kw_img = dict(kw, chunks=(R, Cn)) if compression else {}            # one chunk per image
+        kw_img = dict(compression='gzip', chunks=(R, Cn)) if compression else {}      # one chunk per image
         done = []
         out = h5lite.File(dst, 'w')
         try:
             if pre:
-                g = out.create_group('land-names')
-                g['num-lands'] = len(land_names)
-                for l, name in enumerate(land_names):
-                    g['land-%02d' % l] = name
+                preprocess.write_land_names(out, land_names)
             else:
-                _copy(f, out, 'proj-params')
+                _copy(f.h5, out, 'proj-params')
             for k, s in enumerate(specimens):
-                acquired = len(f[s + '/projections'].keys())
+                acquired = fullres.n_projections(f, s)
                 if acquired < 1:
                     raise nat.DflError('synth.synthesize: specimen %s has no acquired projection to start from' % s)
-                seeds = []
-                for p in range(acquired):
-                    pfx = '%s/projections/%03d/' % (s, p)
-                    fov = tuple(int(_scalar(f[pfx + 'gt-poses/%s-femur-good-fov' % sd][()])) if (sd + '-femur-good-fov') in
-                                f[pfx + 'gt-poses'].keys() else 0 for sd in ('left', 'right'))
-                    seeds.append(dict(poses={n: np.asarray(f[pfx + 'gt-poses/' + n][()], np.float64).reshape(4, 4) for n in drr.POSES},
-                                      rot=int(bool(_scalar(f[pfx + 'rot-180-for-up'][()]))), fov=fov, pfx=pfx))
+                seeds = [dict(poses=fullres.gt_poses(f, pfx), rot=int(fullres.rot180(f, pfx)), fov=fullres.femur_fov(f, pfx, default=0),
+                              pfx=pfx) for pfx in (fullres.projection_prefix(s, p) for p in range(acquired))]
                 plan = sample_poses(seed, k, s, [sd['poses'] for sd in seeds], views, K, E, lands3d[s], R, Cn, crop, **kw_pose)
-                I2P = drr.inds_to_phys(f[s + '/vol/dir-mat'][()], f[s + '/vol/spacing'][()], f[s + '/vol/origin'][()])
-                hu = torch.from_numpy(np.ascontiguousarray(np.asarray(f[s + '/vol/pixels'][()]))).to(dev)
-                seg = torch.from_numpy(np.ascontiguousarray(np.asarray(f[s + '/vol-seg/image/pixels'][()]).astype(np.uint8, copy=False))).to(dev)
-                volume = drr.Volume(drr.hu_to_mu(hu), seg)
-                del hu, seg
+                I2P = drr.inds_to_phys(*fullres.volume_frame(f, s))
+                volume = drr.read_volume(f, s, dev, cast_labels=True)
                 names = list(lands3d[s]) if not pre else land_names
                 pts = np.array([lands3d[s][n] for n in names]).reshape(-1, 3)
                 if pre:
-                    grp = '%02d' % (k + 1)
-                    d_projs = out.create_dataset(grp + '/projs', (views, Ro, Co), dtype='f4', chunks=(1, Ro, Co), **kw)
-                    d_segs = out.create_dataset(grp + '/segs', (views, Ro, Co), dtype='u1', chunks=(1, Ro, Co), **kw)
+                    grp, d_projs, d_segs = preprocess.create_specimen(out, k + 1, views, Ro, Co, compression)
                     lands2d = np.zeros((views, 2, len(names)), np.float64)
                 else:
-                    if volumes:
-                        _copy(f, out, s + '/vol')
-                        _copy(f, out, s + '/vol-seg')
-                    _copy(f, out, s + '/vol-landmarks')
+                    for g in (('/vol', '/vol-seg') if volumes else ()) + ('/vol-landmarks',):
+                        _copy(f.h5, out, s + g)
                 for n0 in range(0, views, chunk):
                     part = plan[n0:n0 + chunk]
                     objs = [drr.default_objects(E, poses, I2P, bones_only) for poses, _, _ in part]
@@ -321,7 +276,7 @@ def synthesize(src, dst, views, seed=0, layout='preprocessed', specimens=None, c
                     img = expose(att, photons, gain, electronic_sigma, blur_sigma_px, keys_q=[q for q, _ in keys] if noise else None,
                                  keys_e=[e for _, e in keys] if noise else None, u16=True)
                     rots = [seeds[sd]['rot'] for _, sd, _ in part]
-                    uv = [_project(K, E, poses[drr.POSES[0]], pts) for poses, _, _ in part]
+                    uv = [drr.project(K, E, poses[drr.POSES[0]], pts) for poses, _, _ in part]
                     if pre:
                         d_projs[n0:n0 + len(part)] = preprocess.preprocess_projs(img, rots, crop, factor).cpu().numpy()
                         d_segs[n0:n0 + len(part)] = preprocess.preprocess_segs(lab, rots, crop, factor).cpu().numpy()
@@ -329,20 +284,19 @@ def synthesize(src, dst, views, seed=0, layout='preprocessed', specimens=None, c
                         continue
                     img, lab = img.cpu().numpy(), lab.cpu().numpy()
                     for j, (poses, sd, _) in enumerate(part):
-                        pfx, spfx = '%s/projections/%03d/' % (s, n0 + j), seeds[sd]['pfx']
+                        pfx, spfx = fullres.projection_prefix(s, n0 + j), seeds[sd]['pfx']
                         out.create_dataset(pfx + 'image/pixels', data=img[j], dtype=np.uint16, **kw_img)
                         out.create_dataset(pfx + 'gt-seg/pixels', data=lab[j], dtype=np.uint8, **kw_img)
                         for g in ('image/', 'gt-seg/'):
                             for item in ('dir-mat', 'origin', 'spacing'):
-                                if item in f[spfx + g].keys():
-                                    _copy_as(f, out, spfx + g + item, pfx + g + item)
+                                if item in f.children(spfx + g):
+                                    _copy(f.h5, out, spfx + g + item, pfx + g + item)
                         for l, name in enumerate(names):
                             out[pfx + 'gt-landmarks/' + name] = uv[j][:, l].reshape(2, 1)
                         for name in drr.POSES:
                             out[pfx + 'gt-poses/' + name] = poses[name]
-                        fl = fov_flags(K, E, poses, lands3d[s], R, Cn, seeds[sd]['fov'])
-                        out[pfx + 'gt-poses/left-femur-good-fov'] = np.int64(fl[0])
-                        out[pfx + 'gt-poses/right-femur-good-fov'] = np.int64(fl[1])
+                        for side, flag in zip(('left', 'right'), fov_flags(K, E, poses, lands3d[s], R, Cn, seeds[sd]['fov'])):
+                            out[pfx + 'gt-poses/%s-femur-good-fov' % side] = np.int64(flag)
                         out[pfx + 'rot-180-for-up'] = np.int64(seeds[sd]['rot'])
                 if pre:
                     out[grp + '/lands'] = preprocess.map_lands(lands2d, [seeds[sd]['rot'] for _, sd, _ in plan], R, Cn, crop,
@@ -360,8 +314,3 @@ def synthesize(src, dst, views, seed=0, layout='preprocessed', specimens=None, c
     finally:
         f.close()
     return done
-
-
-def _copy_as(src, out, path, new_path):
-    v = src[path][()]
-    out[new_path] = v if isinstance(v, (bytes, str)) else np.asarray(v)

@@ -22,8 +22,8 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dfl_amd  # noqa: E402,F401
-from dfl_amd import _native as nat, gltf, mesh  # noqa: E402
-from make_full_res_overlays import Source  # noqa: E402
+from dfl_amd import _native as nat, drr, fullres, gltf, mesh  # noqa: E402
+from dfl_amd.fullres import Source  # noqa: E402
 
 USAGE = 'Usage: {} <HDF5 full-res data file> <specimen ID> <projection index>'
 # (node name, progress name, label, colour, pose)
@@ -61,31 +61,24 @@ def vertex_xform(ny):
     return X
 
 
-def get(src, path):
-    return np.asarray(src.get(path))
-
-
 def host_geometry(src, spec, idx, log=print):
     """Everything of the scene but the surfaces, in fp64 as the script computes it, plus the volume and the 4x4 that
     takes each label's marching-cubes index coordinates into the camera projective frame."""
     g = {}
     log('reading projection parameters...')
-    extrinsic = get(src, 'proj-params/extrinsic').astype(np.float64)
-    intrinsic = get(src, 'proj-params/intrinsic').astype(np.float64)
+    intrinsic, extrinsic, rows, cols = fullres.proj_params(src)
     intrinsic_inv = np.linalg.inv(intrinsic)
-    cols = int(get(src, 'proj-params/num-cols').reshape(-1)[0])
-    rows = int(get(src, 'proj-params/num-rows').reshape(-1)[0])
-    col_sp = float(get(src, 'proj-params/pixel-col-spacing').reshape(-1)[0])
-    row_sp = float(get(src, 'proj-params/pixel-row-spacing').reshape(-1)[0])
+    col_sp = float(fullres.scalar(src.get('proj-params/pixel-col-spacing')))
+    row_sp = float(fullres.scalar(src.get('proj-params/pixel-row-spacing')))
     focal_len = abs((intrinsic[0, 0] * col_sp) + (intrinsic[1, 1] * row_sp)) / 2.0
 
     def det(x):
         return (intrinsic_inv * -focal_len) @ np.asarray(x, np.float64).reshape(3)
 
     g['detector'] = np.stack([det([0, 0, 1]), det([0, rows - 1, 1]), det([cols - 1, rows - 1, 1]), det([cols - 1, 0, 1])])
-    pfx = '{}/projections/{:03d}/'.format(spec, idx)
+    pfx = fullres.projection_prefix(spec, idx)
     log('reading projection...')
-    pix = get(src, pfx + 'image/pixels')
+    pix = np.asarray(src.get(pfx + 'image/pixels'))
     if pix.dtype.kind != 'f':
         raise nat.DflError('%simage/pixels has dtype %s: a float type expected' % (pfx, pix.dtype))
     lo, hi = pix.min(), pix.max()
@@ -95,18 +88,15 @@ def host_geometry(src, spec, idx, log=print):
     if g['texture'].shape != (rows, cols):
         raise nat.DflError('%simage/pixels has shape %s, proj-params say %s' % (pfx, pix.shape, (rows, cols)))
     log('reading GT poses...')
-    poses = {k: extrinsic @ invert_rigid(get(src, pfx + 'gt-poses/' + k).astype(np.float64))
-             for k in ('cam-to-pelvis-vol', 'cam-to-left-femur-vol', 'cam-to-right-femur-vol')}
+    poses = {k: extrinsic @ invert_rigid(P) for k, P in fullres.gt_poses(src, pfx).items()}
     log('reading GT 2D landmarks...')
     lands_2d = {}
-    for name in src.children(pfx + 'gt-landmarks'):
-        l2 = get(src, pfx + 'gt-landmarks/' + name).astype(np.float64).reshape(-1)
+    for name, l2 in fullres.gt_landmarks(src, pfx).items():
         if l2[0] >= 0 and l2[1] >= 0 and l2[0] < cols - 1 and l2[1] < rows - 1:
             lands_2d[name] = det(np.append(l2, 1))
     log('reading 3D landmarks...')
     lands_3d = {}
-    for name in src.children(spec + '/vol-landmarks'):
-        l3 = get(src, spec + '/vol-landmarks/' + name).astype(np.float64).reshape(-1)
+    for name, l3 in fullres.volume_landmarks(src, spec).items():
         lands_3d[name] = poses['cam-to-pelvis-vol'] @ np.append(l3, 1)
     g['lands_3d'] = {k: v[:3] for k, v in lands_3d.items()}
     g['lands_2d'] = lands_2d
@@ -116,17 +106,12 @@ def host_geometry(src, spec, idx, log=print):
         g['rays'][name] = det(p / p[2])
     log('reading 3D segmentation...')
     img = spec + '/vol-seg/image/'
-    vol = get(src, img + 'pixels')
+    vol = np.asarray(src.get(img + 'pixels'))
     if vol.dtype != np.uint8:
         raise nat.DflError('%spixels has dtype %s: uint8 expected (the reference reads it as unsigned char)' % (img, vol.dtype))
     if vol.ndim != 3:
         raise nat.DflError('%spixels has shape %s: [z, y, x] expected' % (img, vol.shape))
-    spacing = get(src, img + 'spacing').astype(np.float64).reshape(-1)
-    dir_mat = get(src, img + 'dir-mat').astype(np.float64).reshape(3, 3)
-    origin = get(src, img + 'origin').astype(np.float64).reshape(-1)
-    inds_to_phys = np.eye(4)
-    inds_to_phys[:3, :3] = dir_mat * spacing[None, :]
-    inds_to_phys[:3, 3] = origin
+    inds_to_phys = drr.inds_to_phys(*fullres.volume_frame(src, spec, 'vol-seg/image'))     # the annotation's own frame
     ny = vol.shape[1]
     g['volume'] = vol
     g['surface_xforms'] = [poses[pose] @ inds_to_phys @ vertex_xform(ny) @ flip_y(ny) for _, _, _, _, pose in SURFACES]

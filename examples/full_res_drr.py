@@ -24,8 +24,7 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dfl_amd  # noqa: E402,F401
-from dfl_amd import _native as nat, drr, ncc, overlay, png, preprocess, util  # noqa: E402
-from make_full_res_overlays import Source  # noqa: E402
+from dfl_amd import _native as nat, drr, fullres, ncc, overlay, png, preprocess, util  # noqa: E402
 
 USAGE = ('Usage: {} <HDF5 full-res data file> <specimen ID> <projection index> [--out PREFIX] [--crop 50] [--ds-factor 8] '
          '[--interp exact|trilinear] [--step 0.5] [--bones-only] [--compare]')
@@ -33,22 +32,21 @@ VALUED = {'--out': str, '--crop': int, '--ds-factor': int, '--interp': str, '--s
 FLAGS = ('--bones-only', '--compare')
 
 
-def parse(argv):
-    """(positional, options) or None when the command line is not understood."""
-    opts = {'--out': None, '--crop': 50, '--ds-factor': 8, '--interp': 'exact', '--step': 0.5, '--bones-only': False,
-            '--compare': False}
+def parse_options(argv, valued, flags, opts):
+    """(three positional arguments, options over the defaults `opts`) or None when the command line is not understood."""
+    opts = dict(opts, **{a: False for a in flags})
     pos, k = [], 0
     while k < len(argv):
         a = argv[k]
-        if a in VALUED:
+        if a in valued:
             if k + 1 >= len(argv):
                 return None
             try:
-                opts[a] = VALUED[a](argv[k + 1])
+                opts[a] = valued[a](argv[k + 1])
             except ValueError:
                 return None
             k += 2
-        elif a in FLAGS:
+        elif a in flags:
             opts[a] = True
             k += 1
         elif a.startswith('--'):
@@ -56,9 +54,13 @@ def parse(argv):
         else:
             pos.append(a)
             k += 1
-    if len(pos) != 3 or opts['--interp'] not in ('exact', 'trilinear'):
-        return None
-    return pos, opts
+    return (pos, opts) if len(pos) == 3 else None
+
+
+def parse(argv):
+    """(positional, options) or None when the command line is not understood."""
+    parsed = parse_options(argv, VALUED, FLAGS, {'--out': None, '--crop': 50, '--ds-factor': 8, '--interp': 'exact', '--step': 0.5})
+    return parsed if parsed and parsed[1]['--interp'] in ('exact', 'trilinear') else None
 
 
 def to_u8(img):
@@ -69,32 +71,16 @@ def to_u8(img):
     return np.where(np.isfinite(scaled), scaled, 0).astype(np.uint8)
 
 
-def read_volume(src, spec, dev):
-    hu = np.asarray(src.get(spec + '/vol/pixels'))
-    lab = np.asarray(src.get(spec + '/vol-seg/image/pixels'))
-    if hu.ndim != 3 or lab.shape != hu.shape:
-        raise nat.DflError('%s: vol/pixels has shape %s, vol-seg/image/pixels %s: two equal [z, y, x] volumes expected'
-                           % (spec, hu.shape, lab.shape))
-    if lab.dtype != np.uint8:
-        raise nat.DflError('%s/vol-seg/image/pixels has dtype %s: uint8 expected' % (spec, lab.dtype))
-    mu = drr.hu_to_mu(torch.from_numpy(np.ascontiguousarray(hu.astype(np.float32, copy=False))).to(dev))
-    return drr.Volume(mu, torch.from_numpy(np.ascontiguousarray(lab)).to(dev))
-
-
 def projected_landmarks(src, spec, geom):
     """[2, L] in preprocess.LAND_ORDER; inf where the name is absent."""
-    have = set(src.children(spec + '/vol-landmarks'))
-    out = np.full((2, len(preprocess.LAND_ORDER)), np.inf)
-    for l, name in enumerate(preprocess.LAND_ORDER):
-        if name in have:
-            out[:, l] = drr.project_points(geom, np.asarray(src.get(spec + '/vol-landmarks/' + name), np.float64).reshape(-1)[:3])[:, 0]
-    return out
+    have = fullres.volume_landmarks(src, spec)
+    return np.stack([drr.project_points(geom, have[n])[:, 0] if n in have else np.full(2, np.inf) for n in preprocess.LAND_ORDER], 1)
 
 
 def compare(src, spec, idx, crop, factor, geom, att, labels, lands, n_classes, dev, log=print):
     """The file's own projection, labels and landmarks on the same grid against the rendered ones."""
-    pfx = '{}/projections/{:03d}/'.format(spec, idx)
-    rot = [bool(np.asarray(src.get(pfx + 'rot-180-for-up')).reshape(-1)[0])]
+    pfx = fullres.projection_prefix(spec, idx)
+    rot = [fullres.rot180(src, pfx)]
     pix = np.asarray(src.get(pfx + 'image/pixels'))
     if pix.dtype != np.uint16:
         pix = pix.astype(np.float32, copy=False)
@@ -107,12 +93,11 @@ def compare(src, spec, idx, crop, factor, geom, att, labels, lands, n_classes, d
     res['dice'] = dice
     for l, v in enumerate(dice):
         log('Dice of label {} = {:.6f}'.format(l + 1, v))
-    have = set(src.children(pfx + 'gt-landmarks'))
+    have = fullres.gt_landmarks(src, pfx)
     dist = 0.0
     for l, name in enumerate(preprocess.LAND_ORDER):
         if name in have and np.all(np.isfinite(lands[:, l])):
-            g2 = np.asarray(src.get(pfx + 'gt-landmarks/' + name), np.float64).reshape(-1)[:2]
-            m = preprocess.map_lands(g2.reshape(1, 2, 1), rot, pix.shape[0], pix.shape[1], crop, factor)[0, :, 0]
+            m = preprocess.map_lands(have[name].reshape(1, 2, 1), rot, pix.shape[0], pix.shape[1], crop, factor)[0, :, 0]
             dist = max(dist, float(np.hypot(*(m - lands[:, l]))))
     res['land_dist'] = dist
     log('largest landmark distance = {:.6f} px'.format(dist))
@@ -130,10 +115,10 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise nat.DflError('no GPU visible: the rays are cast by a HIP kernel (no CPU path)')
     dev = dfl_amd.get_device()
-    src = Source(path)
+    src = fullres.Source(path)
     try:
         geom = drr.geometry(src, spec, idx, crop=o['--crop'], factor=o['--ds-factor'], bones_only=o['--bones-only'])
-        vol = read_volume(src, spec, dev)
+        vol = drr.read_volume(src, spec, dev)
         att, _, labels = drr.render(vol, geom.objects, geom.grid)
         if o['--interp'] == 'trilinear':
             att, _, _ = drr.render(vol, geom.objects, geom.grid, interp='trilinear', step_mm=o['--step'])

@@ -7,8 +7,8 @@ make_grid(nrow=8, padding=2) canvas.
     python examples/make_full_res_overlays.py ipcai_2020_full_res_data.h5     # writes <specimen>.png into the working directory
 
 Per projection NNN of '<specimen>/projections': 'image/pixels' (fp32; fp64 is accepted and rounded to fp32),
-'gt-seg/pixels', 'gt-landmarks/<name>' ((2,) or (2, 1): column, row), 'rot-180-for-up',
-'gt-poses/{left,right}-femur-good-fov'; 'proj-params/num-cols' / 'num-rows' give the size (hdf5_layouts/Readme.md).
+'gt-seg/pixels', 'gt-landmarks/<name>' ((2,) or (2, 1): column, row), the rotation flag and the two femur good-fov
+flags; the detector size comes from 'proj-params' (hdf5_layouts/Readme.md; the names live in dfl_amd.fullres).
 A landmark is drawn when x >= 0, y >= 0, x < cols and y < cols (the reference compares the row with the column count).
 Files: the reference's HDF5 (dfl_amd.h5lite) or .npz with the same names as keys.
 """
@@ -20,39 +20,10 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 import dfl_amd  # noqa: E402,F401
-from dfl_amd import _native as nat, overlay, png  # noqa: E402
+from dfl_amd import _native as nat, fullres, overlay, png  # noqa: E402
+from dfl_amd.fullres import Source  # noqa: E402,F401
 
 CHUNK = 16          # projections uploaded per call: host and device memory stay bounded
-
-
-class Source:
-    """get(path) -> numpy value, children(path) -> sorted names below path, for an .h5 (h5lite) or .npz file."""
-
-    def __init__(self, path):
-        self._f = None
-        if str(path).endswith('.npz'):
-            self._z = np.load(path)
-            self._keys = list(self._z.files)
-        else:
-            from dfl_amd import h5lite
-            self._f = h5lite.File(path, 'r')
-            self._z = None
-
-    def get(self, path):
-        if self._z is not None:
-            return self._z[path]
-        return self._f[path][()]
-
-    def children(self, path=''):
-        if self._z is not None:
-            pre = path.rstrip('/') + '/' if path else ''
-            return sorted({k[len(pre):].split('/')[0] for k in self._keys if k.startswith(pre) and len(k) > len(pre)})
-        node = self._f[path] if path else self._f
-        return sorted(node.keys())
-
-    def close(self):
-        if self._f is not None:
-            self._f.close()
 
 
 def read_projection(src, pfx):
@@ -61,20 +32,18 @@ def read_projection(src, pfx):
     if img.dtype not in (np.float32, np.float64):
         raise nat.DflError('%simage/pixels has dtype %s: float32 or float64 expected' % (pfx, img.dtype))
     seg = np.asarray(src.get(pfx + 'gt-seg/pixels'))
-    lands = [(n, np.asarray(src.get(pfx + 'gt-landmarks/' + n), np.float32).reshape(-1)[:2])
-             for n in src.children(pfx + 'gt-landmarks')]
-    rot = bool(np.asarray(src.get(pfx + 'rot-180-for-up')).reshape(-1)[0])
-    fov = tuple(bool(np.asarray(src.get(pfx + 'gt-poses/%s-femur-good-fov' % s)).reshape(-1)[0]) for s in ('left', 'right'))
-    return img.astype(np.float32, copy=False), seg, lands, rot, fov
+    lands = [(n, v.astype(np.float32)) for n, v in fullres.gt_landmarks(src, pfx).items()]
+    fov = tuple(bool(v) for v in fullres.femur_fov(src, pfx))
+    return img.astype(np.float32, copy=False), seg, lands, fullres.rot180(src, pfx), fov
 
 
 def render_specimen(src, spec, rows, cols, dev, chunk=CHUNK):
     """The tiled canvas of one specimen, [rows, cols, 3] uint8 on dev."""
-    num = len(src.children(spec + '/projections'))
+    num = fullres.n_projections(src, spec)
     size = overlay.fullres_size(rows, cols)
     canvas = None
     for c0 in range(0, num, chunk):
-        items = [read_projection(src, '%s/projections/%03d/' % (spec, p)) for p in range(c0, min(c0 + chunk, num))]
+        items = [read_projection(src, fullres.projection_prefix(spec, p)) for p in range(c0, min(c0 + chunk, num))]
         for img, seg, _, _, _ in items:
             if img.shape != (rows, cols) or seg.shape != (rows, cols):
                 raise nat.DflError('%s: projection of shape %s / %s, proj-params say %s' % (spec, img.shape, seg.shape, (rows, cols)))
@@ -94,8 +63,7 @@ def main(argv=None):
         raise nat.DflError('no GPU visible: the overlays are drawn by HIP kernels (no CPU path)')
     dev = dfl_amd.get_device()
     src = Source(argv[0])
-    cols = int(np.asarray(src.get('proj-params/num-cols')).reshape(-1)[0])
-    rows = int(np.asarray(src.get('proj-params/num-rows')).reshape(-1)[0])
+    rows, cols = fullres.detector_size(src)
     for spec in src.children():
         if spec == 'proj-params':
             continue

@@ -32,9 +32,8 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dfl_amd  # noqa: E402,F401
-from dfl_amd import _native as nat, drr, png, preprocess, register as reg  # noqa: E402
-from full_res_drr import read_volume, to_u8  # noqa: E402
-from make_full_res_overlays import Source  # noqa: E402
+from dfl_amd import _native as nat, drr, fullres, png, preprocess, register as reg  # noqa: E402
+from full_res_drr import parse_options, to_u8  # noqa: E402
 
 USAGE = ('Usage: {} <HDF5 full-res data file> <specimen ID> <projection index> (--lands-csv FILE | --gt-lands | --offset '
          'rx,ry,rz,tx,ty,tz) [--femurs] [--out PREFIX] [--crop 50] [--ds-factor 8] [--popsize 16] [--generations 80] [--sigma 2.0] '
@@ -55,31 +54,13 @@ FLAGS = ('--femurs', '--gt-lands')
 
 def parse(argv):
     """(positional, options), or None when the command line is not understood or names no start or more than one."""
-    opts = {'--out': None, '--crop': 50, '--ds-factor': 8, '--popsize': 16, '--generations': 80, '--seed': 0, '--sigma': 2.0,
-            '--step': 1.0, '--lands-csv': None, '--offset': None, '--femurs': False, '--gt-lands': False}
-    pos, k = [], 0
-    while k < len(argv):
-        a = argv[k]
-        if a in VALUED:
-            if k + 1 >= len(argv):
-                return None
-            try:
-                opts[a] = VALUED[a](argv[k + 1])
-            except ValueError:
-                return None
-            k += 2
-        elif a in FLAGS:
-            opts[a] = True
-            k += 1
-        elif a.startswith('--'):
-            return None
-        else:
-            pos.append(a)
-            k += 1
-    starts = (opts['--lands-csv'] is not None) + bool(opts['--gt-lands']) + (opts['--offset'] is not None)
-    if len(pos) != 3 or starts != 1 or opts['--popsize'] < 4 or opts['--generations'] < 1:
+    parsed = parse_options(argv, VALUED, FLAGS, {'--out': None, '--crop': 50, '--ds-factor': 8, '--popsize': 16, '--generations': 80,
+                                                 '--seed': 0, '--sigma': 2.0, '--step': 1.0, '--lands-csv': None, '--offset': None})
+    if parsed is None:
         return None
-    return pos, opts
+    opts = parsed[1]
+    starts = (opts['--lands-csv'] is not None) + bool(opts['--gt-lands']) + (opts['--offset'] is not None)
+    return parsed if starts == 1 and opts['--popsize'] >= 4 and opts['--generations'] >= 1 else None
 
 
 def read_lands_csv(path, proj, n_lands):
@@ -98,13 +79,6 @@ def read_lands_csv(path, proj, n_lands):
     return out
 
 
-def volume_landmarks(src, spec):
-    """([names], [L, 3]) of '<specimen>/vol-landmarks', in preprocess.LAND_ORDER."""
-    have = set(src.children(spec + '/vol-landmarks'))
-    names = [n for n in preprocess.LAND_ORDER if n in have]
-    return names, np.array([np.asarray(src.get(spec + '/vol-landmarks/' + n), np.float64).reshape(-1)[:3] for n in names]).reshape(-1, 3)
-
-
 class _WithPoses:
     """A source whose missing gt-poses read as the identity (drr.geometry needs the three names)."""
 
@@ -115,7 +89,7 @@ class _WithPoses:
         try:
             return self.src.get(path)
         except KeyError:
-            if '/gt-poses/' not in path:
+            if path.rsplit('/', 1)[-1] not in drr.POSES:
                 raise
             self.missing = True
             return np.eye(4)
@@ -139,21 +113,23 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise nat.DflError('no GPU visible: the DRRs and the similarity are HIP kernels (no CPU path)')
     dev = dfl_amd.get_device()
-    src = Source(path)
+    src = fullres.Source(path)
     try:
         wrapped = _WithPoses(src)
         geom = drr.geometry(wrapped, spec, idx, crop=o['--crop'], factor=o['--ds-factor'], bones_only=True)
         has_gt = not wrapped.missing
         if o['--offset'] is not None and not has_gt:
             raise nat.DflError('--offset starts from the ground-truth poses, and this projection has none')
-        vol = read_volume(src, spec, dev)
-        pfx = '{}/projections/{:03d}/'.format(spec, idx)
-        rot = [bool(np.asarray(src.get(pfx + 'rot-180-for-up')).reshape(-1)[0])]
+        vol = drr.read_volume(src, spec, dev)
+        pfx = fullres.projection_prefix(spec, idx)
+        rot = [fullres.rot180(src, pfx)]
         pix = np.asarray(src.get(pfx + 'image/pixels'))
         if pix.dtype != np.uint16:
             pix = pix.astype(np.float32, copy=False)
         fixed = preprocess.preprocess_projs(torch.from_numpy(np.ascontiguousarray(pix))[None].to(dev), rot, o['--crop'], o['--ds-factor'])[0]
-        names, X3d = volume_landmarks(src, spec)
+        lands3d = fullres.volume_landmarks(src, spec)
+        names = [n for n in preprocess.LAND_ORDER if n in lands3d]
+        X3d = np.array([lands3d[n] for n in names]).reshape(-1, 3)
         centre = reg.volume_centre(vol.shape, geom.I2P)
         back, Ei = np.linalg.inv(geom.I2P), np.linalg.inv(geom.E)
         kw = dict(popsize=o['--popsize'], generations=o['--generations'], sigma0=o['--sigma'], step_mm=o['--step'], seed=o['--seed'])
@@ -163,12 +139,11 @@ def main(argv=None):
             res = reg.register(vol, geom, fixed, moving=(0, 1, 2), theta0=o['--offset'], **kw)
         else:
             if o['--gt-lands']:
-                have = set(src.children(pfx + 'gt-landmarks'))
+                have = fullres.gt_landmarks(src, pfx)
                 x2d = np.full((2, len(names)), np.nan)
                 for l, n in enumerate(names):
                     if n in have:
-                        g2 = np.asarray(src.get(pfx + 'gt-landmarks/' + n), np.float64).reshape(-1)[:2]
-                        x2d[:, l] = preprocess.map_lands(g2.reshape(1, 2, 1), rot, pix.shape[0], pix.shape[1], o['--crop'], o['--ds-factor'])[0, :, 0]
+                        x2d[:, l] = preprocess.map_lands(have[n].reshape(1, 2, 1), rot, pix.shape[0], pix.shape[1], o['--crop'], o['--ds-factor'])[0, :, 0]
             else:
                 full = read_lands_csv(o['--lands-csv'], idx, len(preprocess.LAND_ORDER))
                 x2d = np.stack([full[:, preprocess.LAND_ORDER.index(n)] for n in names], 1) if names else np.zeros((2, 0))

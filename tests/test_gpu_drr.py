@@ -272,7 +272,7 @@ def test_example_end_to_end(tmp_path, capsys, rot180):
     assert z['lands'].shape == (2, 14) and np.isfinite(z['lands'][:, :6]).all() and np.isinf(z['lands'][:, 6:]).all()
     assert png.read(prefix + '_drr.png').shape == (H, W, 3) and png.read(prefix + '_labels.png').shape == (H, W, 3)
     # against the model on the example's own records (G is folded into M before the rounding to fp32) ...
-    from make_full_res_overlays import Source
+    from dfl_amd.fullres import Source
     src = Source(path)
     geom = drr.geometry(src, SPEC, 0, crop=CROP, factor=1)
     src.close()

@@ -26,7 +26,7 @@ import drr_ref as D  # noqa: E402
 import expose_ref as X  # noqa: E402
 import dfl_amd  # noqa: E402,F401
 from dfl_amd import _native as nat, dataset, drr, h5lite, preprocess as pp, register, synth  # noqa: E402
-from make_full_res_overlays import Source  # noqa: E402
+from dfl_amd.fullres import Source  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -256,6 +256,13 @@ def test_refusals(files, tmp_path):
         synth.synthesize(files['src'], out, 2, **dict(KW, blur_sigma_px=3.0))
     with pytest.raises(nat.DflError, match='layout'):
         synth.synthesize(files['src'], out, 2, layout='npz', **KW)
+    # the same container as .npz: the training file comes out the same; the full-res layout copies groups and needs HDF5
+    npz = os.path.join(str(tmp_path), 'src.npz')
+    np.savez(npz, **_all(files['src']))
+    synth.synthesize(npz, out, VIEWS, seed=SEED, layout='preprocessed', **KW)
+    assert _same(_all(out), _all(files['pre']))
+    with pytest.raises(nat.DflError, match='HDF5'):
+        synth.synthesize(npz, out, 2, layout='full-res', **KW)
     import synthesize_dataset as cli
     assert cli.main([files['src'], out, '--views', '2', '--crop', '2', '--ds-factor', '2', '--rot-sigma-deg', '2', '--trans-sigma-mm', '1,1,5',
                      '--femur-sigma-deg', '2', '--chunk', '2']) == 0

@@ -148,7 +148,7 @@ def test_cma_es_on_an_ill_conditioned_quadratic():
 
 # ---- packing -----------------------------------------------------------------------------------------------------------
 class _Boxes:
-    """What pack_objects and pack_poses read of a drr.Volume, from the numpy labels."""
+    """What drr.pack reads of a drr.Volume, from the numpy labels."""
 
     def __init__(self, lab):
         self.lab, self.shape = lab, lab.shape
@@ -162,27 +162,44 @@ class _Boxes:
         return D.label_box(self.lab, mask)
 
 
+def _pack_inputs():
+    """16 views x 4 objects on the tilted scene: one object held, the last mask matching no voxel."""
+    S = D.scene('tilted')
+    thetas = np.random.default_rng(5).standard_normal((16, 6)) * 3
+    A = np.linalg.inv(S['I2P'])[None] @ reg.pose_deltas(thetas, R.volume_centre(S)) @ S['I2P'][None]
+    base = np.stack(D.scene_views(S)[0] + D.scene_views(S)[0][:1])
+    c2is = A[:, None] @ base[None]
+    c2is[:, 2] = base[2]
+    return S, _Boxes(S['lab']), drr.Grid(S['Q'], S['rows'], S['cols']), c2is, list(D.MASKS) + [1 << 9]
+
+
 @pytest.mark.parametrize('tight', [True, False])
 @pytest.mark.parametrize('interp', ['exact', 'trilinear'])
 def test_the_vectorised_pack_gives_the_bytes_of_pack_objects(interp, tight):
-    S = D.scene('tilted')
-    vol = _Boxes(S['lab'])
-    grid = drr.Grid(S['Q'], S['rows'], S['cols'])
-    rng = np.random.default_rng(5)
-    thetas = rng.standard_normal((16, 6)) * 3
-    A = np.linalg.inv(S['I2P'])[None] @ reg.pose_deltas(thetas, R.volume_centre(S)) @ S['I2P'][None]
-    base = np.stack(D.scene_views(S)[0] + D.scene_views(S)[0][:1])
-    masks = list(D.MASKS) + [1 << 9]                               # the last object matches no voxel
-    c2is = A[:, None] @ base[None]
-    c2is[:, 2] = base[2]                                           # one object held
+    """drr.pack against the independent numpy model tests/drr_ref.pack, view by view, and against its adapter
+    drr.pack_objects over the equivalent [[Obj]]: equal bytes."""
+    S, vol, grid, c2is, masks = _pack_inputs()
+    got = drr.pack(vol, c2is, masks, grid, interp, tight)
+    assert got.dtype == drr.OBJECT_DTYPE == D.OBJECT_DTYPE and got.shape == (16, 4)
+    for v in range(16):
+        assert got[v].tobytes() == D.pack(c2is[v], masks, S['Q'], S['lab'], tight, interp).tobytes(), v
     want = drr.pack_objects(vol, [[drr.Obj(c2is[v, n], masks[n]) for n in range(4)] for v in range(16)], grid, interp, tight)
-    got = reg.pack_poses(vol, c2is, masks, grid, interp, tight)
-    assert got.dtype == want.dtype == drr.OBJECT_DTYPE and got.shape == want.shape == (16, 4)
-    assert got.tobytes() == want.tobytes()
-    one = reg.pack_poses(vol, c2is[:1], masks, grid, interp, tight)
+    assert want.dtype == drr.OBJECT_DTYPE and want.shape == (16, 4) and got.tobytes() == want.tobytes()
+    one = drr.pack(vol, c2is[:1], masks, grid, interp, tight)
     assert one.tobytes() == want[:1].tobytes()
     with pytest.raises(nat.DflError, match='masks'):
-        reg.pack_poses(vol, c2is, masks[:3], grid, interp, tight)
+        drr.pack(vol, c2is, masks[:3], grid, interp, tight)
+    for bad in ([0.5] * 4, masks[:3] + [1 << 16], masks[:3] + [-1]):             # masks are 16-bit integers, as Obj.mask
+        with pytest.raises(nat.DflError, match='16 bits'):
+            drr.pack(vol, c2is, bad, grid, interp, tight)
+    # masks that differ between the views: [views, n_obj], as pack_objects allows per Obj
+    per_view = np.array([masks[v % 4:] + masks[:v % 4] for v in range(16)])
+    assert len({tuple(r) for r in per_view.tolist()}) == 4
+    got = drr.pack(vol, c2is, per_view, grid, interp, tight)
+    want = drr.pack_objects(vol, [[drr.Obj(c2is[v, n], int(per_view[v, n])) for n in range(4)] for v in range(16)], grid, interp, tight)
+    assert got.tobytes() == want.tobytes()
+    for v in range(16):
+        assert got[v].tobytes() == D.pack(c2is[v], per_view[v].tolist(), S['Q'], S['lab'], tight, interp).tobytes(), v
 
 
 # ---- the model of the similarity ---------------------------------------------------------------------------------------

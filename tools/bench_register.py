@@ -111,7 +111,7 @@ def main():
     res['pack_poses_host_ms'] = None
     t0 = time.perf_counter()
     for _ in range(50):
-        reg.pack_poses(vol, A[:, None] @ np.stack([ob.c2i for ob in objects])[None], [ob.mask for ob in objects], grid, 'trilinear', True)
+        drr.pack(vol, A[:, None] @ np.stack([ob.c2i for ob in objects])[None], [ob.mask for ob in objects], grid, 'trilinear', True)
     res['pack_poses_host_ms'] = round((time.perf_counter() - t0) / 50 * 1e3, 4)
     reg.register(vol, geom, fixed, theta0=THETA0, popsize=LAMBDA, generations=3, step_mm=STEP_MM)     # warm-up
     gens, per = 20, []
