@@ -317,6 +317,20 @@ class SimGradnccArgs(C.Structure):
                 ('scratch_doubles', i64), ('V', i32), ('H', i32), ('W', i32), ('reserved', i32)]
 
 
+SIM_PATCH_MAX_W = 1538                                                     # include/dfl_hip.h: DFL_SIM_PATCH_MAX_W
+
+
+class SimPatchPrepareArgs(C.Structure):
+    _fields_ = [('fx', fp), ('fy', fp), ('counted', fp), ('ptotals', fp), ('pflags', fp), ('pcount', fp), ('H', i32), ('W', i32),
+                ('rho', i32), ('stride', i32), ('min_count', i32), ('reserved', i32)]
+
+
+class SimPatchGradnccArgs(C.Structure):
+    _fields_ = [('moving', fp), ('fx', fp), ('fy', fp), ('counted', fp), ('ptotals', fp), ('pflags', fp), ('pcount', fp),
+                ('scratch', fp), ('cost', fp), ('scratch_doubles', i64), ('V', i32), ('H', i32), ('W', i32), ('rho', i32),
+                ('stride', i32), ('reserved', i32)]
+
+
 EXPOSE_MAX_RADIUS = 8                                                      # include/dfl_hip.h: DFL_EXPOSE_MAX_RADIUS
 
 
@@ -362,7 +376,8 @@ _SIZEOF_ORDER = [ConvArgs, WgradArgs, PackJob, BnFinalizeArgs, ColstatsArgs, BnB
                  AffineCopyArgs, PoolArgs, HeadFwdArgs, HeadBwdArgs, LossArgs, EnsembleArgs, Op, ReduceJob, PrepArgs, EstLandsArgs,
                  UpsampleArgs, AugmentArgs, AugmentItem, OverlayArgs, ResamplePlan, ResampleArgs, FullresArgs, MeshMcArgs, MeshDecodeArgs,
                  MeshTopoArgs, MeshCsrArgs, MeshSmoothArgs, MeshXformArgs, MeshNormalsArgs, PreprocProjsArgs, PreprocSegsArgs,
-                 RestoreLabelsArgs, SimPrepareArgs, SimGradnccArgs, ExposeArgs, DrrObject, DrrArgs, OptimPackArgs]
+                 RestoreLabelsArgs, SimPrepareArgs, SimGradnccArgs, ExposeArgs, SimPatchPrepareArgs, SimPatchGradnccArgs,
+                 DrrObject, DrrArgs, OptimPackArgs]
 
 EXPORTS = ['dfl_version', 'dfl_last_error', 'dfl_sizeof', 'dfl_conv2d', 'dfl_conv_grid_m', 'dfl_conv2d_wgrad',
            'dfl_wgrad_suggest_splits', 'dfl_sum_partials', 'dfl_pack_weights', 'dfl_bn_finalize',
@@ -381,7 +396,8 @@ EXPORTS = ['dfl_version', 'dfl_last_error', 'dfl_sizeof', 'dfl_conv2d', 'dfl_con
            'dfl_mesh_mc_count', 'dfl_mesh_mc_emit', 'dfl_mesh_decode', 'dfl_mesh_topology', 'dfl_mesh_csr', 'dfl_mesh_smooth',
            'dfl_mesh_transform', 'dfl_mesh_normals', 'dfl_adam_step', 'dfl_rmsprop_step', 'dfl_optim_pack_tiled',
            'dfl_preproc_projs', 'dfl_preproc_segs', 'dfl_restore_labels', 'dfl_drr_render', 'dfl_sim_prepare', 'dfl_sim_gradncc',
-           'dfl_sim_scratch_doubles', 'dfl_drr_expose']
+           'dfl_sim_scratch_doubles', 'dfl_drr_expose', 'dfl_sim_patch_prepare', 'dfl_sim_patch_gradncc', 'dfl_sim_patch_count',
+           'dfl_sim_patch_scratch_doubles']
 
 
 class DflError(RuntimeError):
@@ -428,13 +444,17 @@ def lib():
     L.dfl_resample_bilinear_u8.argtypes = [fp, fp]
     L.dfl_fullres_overlay.argtypes = [fp, fp]
     for fn in ('dfl_preproc_projs', 'dfl_preproc_segs', 'dfl_restore_labels', 'dfl_drr_render', 'dfl_sim_prepare', 'dfl_sim_gradncc',
-               'dfl_drr_expose'):
+               'dfl_drr_expose', 'dfl_sim_patch_prepare', 'dfl_sim_patch_gradncc'):
         getattr(L, fn).argtypes = [fp, fp]
     for fn in ('dfl_mesh_mc_count', 'dfl_mesh_mc_emit', 'dfl_mesh_decode', 'dfl_mesh_topology', 'dfl_mesh_csr',
                'dfl_mesh_smooth', 'dfl_mesh_transform', 'dfl_mesh_normals'):
         getattr(L, fn).argtypes = [fp, fp]
     L.dfl_sim_scratch_doubles.restype = i64
     L.dfl_sim_scratch_doubles.argtypes = [i32, i32, i32]
+    L.dfl_sim_patch_count.restype = i64
+    L.dfl_sim_patch_count.argtypes = [i32, i32, i32, i32]
+    L.dfl_sim_patch_scratch_doubles.restype = i64
+    L.dfl_sim_patch_scratch_doubles.argtypes = [i32, i32, i32, i32, i32]
     L.dfl_set_math_mode.argtypes = [i32]
     L.dfl_hard_dice.argtypes = [fp, fp, i64, i32, i32, fp, fp, fp]
     L.dfl_sgd_step.argtypes = [fp, fp, fp, i64, f32, f32, f32, f32, i32, i32, fp]

@@ -10,46 +10,12 @@
 // the vector L1) and adds six sums in float64.  Wave shuffles, then LDS across the four waves, then ONE record of six
 // doubles per workgroup with plain stores; sim_finish_kernel adds a view's records in index order and writes its cost.
 // No atomics: the bits of a view's cost depend on that view's pixels and on H and W only.
-#include "common.h"
+#include "sim.h"
 
 namespace dfl {
 
 constexpr int SIM_ROWS = 8;          // interior rows per workgroup
-constexpr int SIM_THREADS = 256;
 constexpr int SIM_SUMS = 6;          // sum mx, mx^2, mx fx, my, my^2, my fy
-
-// Sobel gradients of p at interior pixel (r, c): each sum left to right, so the fixed and the moving image share bits
-__device__ __forceinline__ void sim_sobel(const float* __restrict__ p, int W, int r, int c, float& gx, float& gy) {
-  const float* up = p + (size_t)(r - 1) * W + c;
-  const float* mid = up + W;
-  const float* dn = mid + W;
-  const float a = up[-1], b = up[0], cc = up[1], d = mid[-1], f = mid[1], g = dn[-1], h = dn[0], i = dn[1];
-  gx = ((cc + 2.f * f) + i) - ((a + 2.f * d) + g);
-  gy = ((g + 2.f * h) + i) - ((a + 2.f * b) + cc);
-}
-
-__device__ __forceinline__ double sim_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-// N sums of a workgroup of SIM_THREADS threads -> thread 0's v[]; lds holds N * 4 doubles
-template <int N>
-__device__ __forceinline__ void sim_block_sum(double (&v)[N], double* lds) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < N; ++k) v[k] = sim_wave_sum(v[k]);
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) lds[wave * N + k] = v[k];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) v[k] = ((lds[k] + lds[N + k]) + lds[2 * N + k]) + lds[3 * N + k];
-  }
-}
 
 __global__ __launch_bounds__(SIM_THREADS) void sim_prepare_kernel(const float* __restrict__ fixed, const unsigned char* __restrict__ mask,
                                                                   float* __restrict__ fx, float* __restrict__ fy,
@@ -123,14 +89,6 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_gradncc_kernel(const float* _
 #pragma unroll
     for (int k = 0; k < SIM_SUMS; ++k) rec[k] = s[k];
   }
-}
-
-// A variance is 0 when it is at most 2^-40 of the sum of squares: below that the one-pass form cannot tell
-__device__ __forceinline__ double sim_ncc(double n, double sa, double saa, double sb, double sbb, double sab) {
-  const double va = saa - sa * sa / n, vb = sbb - sb * sb / n;
-  const double eps = 9.094947017729282e-13;                             // 2^-40
-  if (!(va > eps * saa) || !(vb > eps * sbb)) return 0.0;
-  return (sab - sa * sb / n) / sqrt(va * vb);
 }
 
 // One wave per view: lanes 0..5 add one of the six sums each over the view's records, in index order

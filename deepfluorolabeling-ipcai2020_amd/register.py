@@ -1,11 +1,14 @@
 """2D/3D registration of the CT to one projection: a start pose from 2D landmarks (pnp), then a CMA-ES over six pose
-parameters whose cost is the gradient-NCC between rendered DRRs and the fixed image.
+parameters whose cost is the gradient-NCC between rendered DRRs and the fixed image: one correlation over the whole
+image (similarity='global') or the mean over patches (similarity='patch'), and optionally a reprojection term that
+keeps the pose near detected landmarks.
 
 The geometry is float64 numpy on the host, as in dfl_amd.drr; the pixels stay on the device.  One generation of the
 optimiser is one dfl_drr_render launch (trilinear, tight boxes, lambda views), one dfl_sim_gradncc launch
 (csrc/sim.hip) and one copy of lambda doubles to the host; the records and the argument block of the render are
 drr.pack and drr.args_for_records.  DESIGN.md section 16 states the semantics of the similarity; tests/reg_ref.py
-restates them in numpy float64.
+restates them in numpy float64.  The patch cost (dfl_sim_patch_gradncc, csrc/sim_patch.hip) and the landmark term are
+section 18 and tests/patch_ref.py.
 
     D(theta) = [[R, centre - R centre + theta[3:]], [0, 1]],  R = exp(rot_unit theta[:3])      (pose_delta)
     P(theta) = D(theta) P0                                   a cam-to-*-vol matrix as in gt-poses
@@ -20,8 +23,8 @@ import torch
 from . import _native as nat
 from . import drr, preprocess
 
-__all__ = ['se3_exp', 'se3_log', 'pose_delta', 'pose_deltas', 'pnp', 'cma_es', 'CmaResult', 'Similarity', 'register',
-           'Registration', 'with_pelvis_pose', 'volume_centre']
+__all__ = ['se3_exp', 'se3_log', 'pose_delta', 'pose_deltas', 'pnp', 'cma_es', 'CmaResult', 'Similarity', 'PatchSimilarity',
+           'landmark_penalty', 'register', 'Registration', 'with_pelvis_pose', 'volume_centre']
 
 ROT_UNIT = 0.02
 
@@ -312,11 +315,99 @@ class Similarity:
         return out
 
 
+def _patch_params(radius, stride, min_count):
+    """(rho, stride, min_count) as integers; min_count=None is half a patch, rounded up."""
+    ok = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in (radius, stride)) and \
+        (min_count is None or (isinstance(min_count, (int, np.integer)) and not isinstance(min_count, bool)))
+    if not ok or radius < 1 or stride < 1 or (min_count is not None and min_count < 1):
+        raise nat.DflError('register: a patch radius of %r, a stride of %r and a min_count of %r (integers, at least 1 each)'
+                           % (radius, stride, min_count))
+    side = 2 * int(radius) + 1
+    return int(radius), int(stride), (side * side + 1) // 2 if min_count is None else int(min_count)
+
+
+class PatchSimilarity(Similarity):
+    """The patch-wise gradient-NCC cost with the interface of Similarity: patches of side
+    2 radius + 1 every `stride` interior pixels; a patch with fewer than min_count counted pixels (default: half of it,
+    rounded up), or whose fixed gradient does not vary, does not take part.  dfl_sim_prepare and dfl_sim_patch_prepare
+    run here, once; cost(moving) is one dfl_sim_patch_gradncc launch."""
+
+    def __init__(self, fixed, mask=None, views=1, radius=7, stride=4, min_count=None):
+        self.radius, self.stride, self.min_count = _patch_params(radius, stride, min_count)
+        Similarity.__init__(self, fixed, mask, views)
+        lib = nat.lib()
+        dev, H, W = self.fixed.device, self.H, self.W
+        P = int(lib.dfl_sim_patch_count(H, W, self.radius, self.stride))
+        need = int(lib.dfl_sim_patch_scratch_doubles(self.views, H, W, self.radius, self.stride)) if P >= 0 else -1
+        if P < 0 or need < 0:
+            raise nat.DflError('register: %s' % lib.dfl_last_error().decode())
+        self.patches = P
+        self.ptotals = torch.empty((P, nat.SIM_TOTALS), dtype=torch.float64, device=dev)
+        self.pflags = torch.empty(P, dtype=torch.uint8, device=dev)
+        self.pcount = torch.empty(2, dtype=torch.int32, device=dev)
+        self.pscratch = torch.empty(need, dtype=torch.float64, device=dev)
+        a = nat.SimPatchPrepareArgs(fx=self.fx.data_ptr(), fy=self.fy.data_ptr(), counted=self.counted.data_ptr(),
+                                    ptotals=self.ptotals.data_ptr(), pflags=self.pflags.data_ptr(), pcount=self.pcount.data_ptr(),
+                                    H=H, W=W, rho=self.radius, stride=self.stride, min_count=self.min_count)
+        with torch.cuda.device(dev):
+            nat.call('dfl_sim_patch_prepare', a, torch.cuda.current_stream(dev).cuda_stream)
+
+    def args(self, moving, out=None):
+        out = self.out if out is None else out
+        return nat.SimPatchGradnccArgs(moving=moving.data_ptr(), fx=self.fx.data_ptr(), fy=self.fy.data_ptr(),
+                                       counted=self.counted.data_ptr(), ptotals=self.ptotals.data_ptr(), pflags=self.pflags.data_ptr(),
+                                       pcount=self.pcount.data_ptr(), scratch=self.pscratch.data_ptr(), cost=out.data_ptr(),
+                                       scratch_doubles=self.pscratch.numel(), V=int(moving.shape[0]), H=self.H, W=self.W,
+                                       rho=self.radius, stride=self.stride)
+
+    def cost(self, moving):
+        mv = _device_image(moving, 'the moving images', 3)
+        if tuple(mv.shape[1:]) != (self.H, self.W) or mv.device != self.fixed.device or not 1 <= mv.shape[0] <= self.views:
+            raise nat.DflError('register: moving images of shape %s on %s for a fixed image of %d x %d on %s and at most %d views'
+                               % (tuple(mv.shape), mv.device, self.H, self.W, self.fixed.device, self.views))
+        out = torch.empty(mv.shape[0], dtype=torch.float64, device=mv.device)
+        with torch.cuda.device(mv.device):
+            nat.call('dfl_sim_patch_gradncc', self.args(mv, out), torch.cuda.current_stream(mv.device).cuda_stream)
+        return out
+
+
+# ---- the landmark term -------------------------------------------------------------------------------------------------
+def _usable_landmarks(X3d, x2d, who):
+    X = np.asarray(X3d, np.float64)
+    x = np.asarray(x2d, np.float64)
+    if X.ndim != 2 or X.shape[1] != 3 or x.ndim != 2 or x.shape[0] != 2 or x.shape[1] != X.shape[0]:
+        raise nat.DflError('%s: X3d is %s and x2d %s: [L, 3] and [2, L] expected' % (who, X.shape, x.shape))
+    use = np.isfinite(x).all(0) & np.isfinite(X).all(1)
+    if int(use.sum()) < 1:
+        raise nat.DflError('%s: no usable landmark (a finite 2D column with a finite 3D point)' % who)
+    return X[use], x[:, use]
+
+
+def landmark_penalty(geom, poses, X3d, x2d, weight):
+    """weight * the mean over the landmarks of |proj_l - x2d_l|^2, for every pelvis pose of poses [n, 4, 4] (or [4, 4]):
+    float64 [n].  proj is drr.project_points under that pose, so distances are pixels on geom.grid and weight is per
+    square pixel; columns of x2d that are not finite are skipped.  A weight of 0 gives exact zeros."""
+    weight = float(weight)
+    if not weight >= 0.0 or not np.isfinite(weight):
+        raise nat.DflError('register.landmark_penalty: a weight of %r (finite, not negative)' % weight)
+    P = np.asarray(poses, np.float64).reshape(-1, 4, 4)
+    X, x = _usable_landmarks(X3d, x2d, 'register.landmark_penalty')
+    if weight == 0.0:
+        return np.zeros(P.shape[0])
+    Xh = np.concatenate([X, np.ones((X.shape[0], 1))], 1).T                  # [4, L]
+    cam = (np.asarray(geom.E, np.float64)[None] @ np.linalg.inv(P)) @ Xh[None]   # [n, 4, L]
+    p = np.asarray(geom.K, np.float64)[None] @ cam[:, :3]
+    q = np.linalg.inv(geom.G)[None] @ (p / p[:, 2:3])
+    d = q[:, :2] - x[None]
+    return weight * (d * d).sum(1).mean(1)
+
+
 # ---- registration ------------------------------------------------------------------------------------------------------
 class Registration:
     """pose: D(theta) P0 of the first moving object (a cam-to-*-vol matrix); poses: the same for every moving object;
     theta; delta = D(theta); cost: the best cost of every generation (all levels, in order); final_cost: the cost at
-    theta; renders: views rendered; levels: [(factor, generations, H, W)]."""
+    theta = similarity_cost + landmark_cost (0 without the landmark term); renders: views rendered; levels: [(factor,
+    generations, H, W)]."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -325,11 +416,12 @@ class Registration:
 class _Level:
     """The buffers and argument blocks of one resolution level: lambda views of every object on one grid."""
 
-    def __init__(self, volume, grid, fixed, mask, lam, step_mm):
+    def __init__(self, volume, grid, fixed, mask, lam, step_mm, patch=None):
         self.volume, self.grid, self.lam = volume, grid, lam
         if tuple(fixed.shape) != (grid.H, grid.W):
             raise nat.DflError('register: the fixed image is %s, the output grid %d x %d' % (tuple(fixed.shape), grid.H, grid.W))
-        self.sim = Similarity(fixed, mask, lam)
+        self.sim = Similarity(fixed, mask, lam) if patch is None else PatchSimilarity(fixed, mask, lam, *patch)
+        self.entry = 'dfl_sim_gradncc' if patch is None else 'dfl_sim_patch_gradncc'
         self.step_mm = float(step_mm)
 
     def costs(self, c2is, masks):
@@ -340,12 +432,13 @@ class _Level:
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
             nat.call('dfl_drr_render', a, stream)
-            nat.call('dfl_sim_gradncc', self.sim.args(att), stream)
+            nat.call(self.entry, self.sim.args(att), stream)
         return self.sim.out[:V].cpu().numpy()                       # the copy waits for both launches: `keep` lives until then
 
 
 def register(volume, geom, fixed, moving=(0, 1, 2), theta0=None, P0=None, levels=None, popsize=16, generations=80, sigma0=2.0,
-             step_mm=1.0, mask=None, seed=0, centre=None, rot_unit=ROT_UNIT, crop=0, rot180=False, sigma_shrink=0.5):
+             step_mm=1.0, mask=None, seed=0, centre=None, rot_unit=ROT_UNIT, crop=0, rot180=False, sigma_shrink=0.5,
+             similarity='global', patch_radius=7, patch_stride=4, patch_min_count=None, landmarks=None, landmark_weight=0.0):
     """Find theta such that the DRR of `volume` under P = D(theta) P0 matches `fixed`.
 
     moving selects the objects of geom.objects that share the pose under optimisation; the others are rendered at their
@@ -358,7 +451,28 @@ def register(volume, geom, fixed, moving=(0, 1, 2), theta0=None, P0=None, levels
     the detector's own intensities [rows, cols] (float32 or uint16); every level gets its grid from drr.training_grid(rows,
     cols, crop, factor, rot180) and its fixed image from preprocess_projs at that factor, starts from the previous
     level's mean and multiplies sigma by sigma_shrink; mask is not supported there.
+
+    similarity='global' is one gradient-NCC over all counted pixels (Similarity); 'patch' is the mean over patches of
+    radius patch_radius every patch_stride pixels with at least patch_min_count counted pixels (PatchSimilarity; with
+    levels the same numbers apply on every level's own grid).  landmarks=(X3d [L, 3], x2d [2, L]) with landmark_weight w
+    adds landmark_penalty of the pelvis pose D(theta) P_pelvis to every cost (object 0 must move; not with levels).
     """
+    if similarity not in ('global', 'patch'):
+        raise nat.DflError("register: similarity = %r ('global' or 'patch')" % (similarity,))
+    patch = _patch_params(patch_radius, patch_stride, patch_min_count) if similarity == 'patch' else None
+    landmark_weight = float(landmark_weight)
+    if not landmark_weight >= 0.0 or not np.isfinite(landmark_weight):
+        raise nat.DflError('register: a landmark_weight of %r (finite, not negative)' % landmark_weight)
+    if landmarks is not None:
+        if levels is not None:
+            raise nat.DflError('register: landmarks belong to one grid; they are not supported together with levels')
+        if 0 not in tuple(int(m) for m in moving):
+            raise nat.DflError('register: the landmark term follows the pelvis (object 0), which moving = %r holds still' % (tuple(moving),))
+        try:
+            X3d, x2d = landmarks
+        except (TypeError, ValueError):
+            raise nat.DflError('register: landmarks = (X3d [L, 3], x2d [2, L]) expected') from None
+        lands = _usable_landmarks(X3d, x2d, 'register: landmarks')
     if not isinstance(volume, drr.Volume):
         raise nat.DflError('register needs a drr.Volume (device tensors; no CPU path)')
     if not torch.is_tensor(fixed) or not fixed.is_cuda:
@@ -387,6 +501,13 @@ def register(volume, geom, fixed, moving=(0, 1, 2), theta0=None, P0=None, levels
         A = back[None] @ pose_deltas(thetas, ctr, rot_unit) @ I2P[None]     # [views, 4, 4]
         return np.where(mv[None, :, None, None], A[:, None] @ base[None], base[None])
 
+    penalty = None
+    if landmarks is not None and landmark_weight > 0.0:
+        P_pelvis = I2P @ base[0] @ geom.E                                       # P = I2P C2I E
+
+        def penalty(thetas):
+            return landmark_penalty(geom, pose_deltas(thetas, ctr, rot_unit) @ P_pelvis[None], lands[0], lands[1], landmark_weight)
+
     if levels is None:
         plan = [(None, int(generations), geom.grid, _device_image(fixed, 'the fixed image', 2))]
     else:
@@ -398,21 +519,29 @@ def register(volume, geom, fixed, moving=(0, 1, 2), theta0=None, P0=None, levels
         plan = []
         for factor, gens in levels:
             G, (H, W) = drr.training_grid(rows, cols, crop, int(factor), bool(rot180))
+            if patch is not None and min(H, W) - 2 < 2 * patch[0] + 1:
+                raise nat.DflError('register: level %d (factor %d) has a grid of %d x %d, too small for one patch of side %d'
+                                   % (len(plan), int(factor), H, W, 2 * patch[0] + 1))
             img = preprocess.preprocess_projs(px[None], [bool(rot180)], int(crop), int(factor))[0]
             plan.append((int(factor), int(gens), drr.Grid(-Kinv @ G, H, W), img))
         if not plan:
             raise nat.DflError('register: an empty list of levels')
     mean, sigma, trace, renders, done = theta0, float(sigma0), [], 0, []
     for k, (factor, gens, grid, img) in enumerate(plan):
-        level = _Level(volume, grid, img, mask, lam, step_mm)
-        res = cma_es(lambda th: level.costs(c2is_of(th), masks), mean, sigma, lam, gens, seed + k)
+        level = _Level(volume, grid, img, mask, lam, step_mm, patch)
+        if penalty is None:
+            res = cma_es(lambda th: level.costs(c2is_of(th), masks), mean, sigma, lam, gens, seed + k)
+        else:
+            res = cma_es(lambda th: level.costs(c2is_of(th), masks) + penalty(th), mean, sigma, lam, gens, seed + k)
         mean, sigma = res.mean, sigma * float(sigma_shrink)
         trace.extend(res.trace.tolist())
         renders += res.evaluations
         done.append((factor, gens, grid.H, grid.W))
-    final_cost = float(level.costs(c2is_of(mean[None]), masks)[0])
+    similarity_cost = float(level.costs(c2is_of(mean[None]), masks)[0])
+    landmark_cost = 0.0 if penalty is None else float(penalty(mean[None])[0])
+    final_cost = similarity_cost if penalty is None else similarity_cost + landmark_cost
     renders += 1
     D = pose_delta(mean, ctr, rot_unit)
     poses = [D @ I2P @ base[m] @ geom.E for m in moving]                    # P = I2P C2I E
     return Registration(pose=poses[0], poses=poses, theta=mean, delta=D, cost=np.array(trace), final_cost=final_cost,
-                        renders=renders, levels=done, centre=ctr)
+                        similarity_cost=similarity_cost, landmark_cost=landmark_cost, renders=renders, levels=done, centre=ctr)

@@ -7,6 +7,7 @@ same --crop and --ds-factor.
     python examples/register_2d3d.py full_res.h5 17-1882 0 --lands-csv lands.csv          # the start the paper uses
     python examples/register_2d3d.py full_res.h5 17-1882 0 --gt-lands --femurs
     python examples/register_2d3d.py full_res.h5 17-1882 0 --offset 2,-1.5,2.5,4,-3,15 --seed 1 --out run1
+    python examples/register_2d3d.py full_res.h5 17-1882 0 --lands-csv lands.csv --similarity patch --landmark-weight 0.01
 
 The start pose comes from exactly one of
   --lands-csv FILE   2D landmarks as est_lands_csv.py writes them (pat,proj,land,row,col,time on this grid; land indexes
@@ -14,10 +15,15 @@ The start pose comes from exactly one of
   --gt-lands         the projection's gt-landmarks, solved the same way;
   --offset rx,ry,rz,tx,ty,tz   the ground-truth poses moved by register.pose_delta of these six parameters (rotation
                      in units of 0.02 rad about the volume centre, translation in mm).
+--similarity global (the default) compares the whole image with one gradient-NCC; --similarity patch takes the mean over
+patches of radius --patch-radius (7) every --patch-stride (4) pixels, which is less sensitive to what the CT does not hold.
+--landmark-weight W (per square pixel, default 0) adds W times the mean squared distance between the projected 3D
+landmarks and the 2D landmarks that gave the start to the pelvis cost; it needs a landmark start, not --offset.
 With a landmark start all bones begin at the pelvis pose (the anatomy as it was scanned).  The pelvis is registered with
 every bone following it; --femurs then registers each femur on its own with the others held.
 PREFIX_reg.npz holds start_poses and poses ([3, 4, 4] cam-to-{pelvis, left-femur, right-femur}-vol), cost (the best cost
-of every generation), theta and start_lands / lands ([2, L] projected 3D landmarks).  PREFIX_reg.png shows the projection,
+of every generation), theta, similarity_cost and landmark_cost (the two parts of the pelvis cost at theta) and
+start_lands / lands ([2, L] projected 3D landmarks).  PREFIX_reg.png shows the projection,
 the DRR at the start pose and the DRR at the final pose side by side.  Where the file has gt-poses the rotation error
 (degrees), the translation error (mm, of the volume centre) and the largest reprojection distance of the 3D landmarks
 (pixels) of the pelvis are printed.
@@ -37,7 +43,7 @@ from full_res_drr import parse_options, to_u8  # noqa: E402
 
 USAGE = ('Usage: {} <HDF5 full-res data file> <specimen ID> <projection index> (--lands-csv FILE | --gt-lands | --offset '
          'rx,ry,rz,tx,ty,tz) [--femurs] [--out PREFIX] [--crop 50] [--ds-factor 8] [--popsize 16] [--generations 80] [--sigma 2.0] '
-         '[--step 1.0] [--seed 0]')
+         '[--step 1.0] [--seed 0] [--similarity global|patch] [--patch-radius 7] [--patch-stride 4] [--landmark-weight 0]')
 
 
 def _six(text):
@@ -61,6 +67,29 @@ def parse(argv):
     opts = parsed[1]
     starts = (opts['--lands-csv'] is not None) + bool(opts['--gt-lands']) + (opts['--offset'] is not None)
     return parsed if starts == 1 and opts['--popsize'] >= 4 and opts['--generations'] >= 1 else None
+
+
+SIMILARITY = {'--similarity': str, '--patch-radius': int, '--patch-stride': int, '--landmark-weight': float}
+
+
+def parse_similarity(argv):
+    """(the command line without the options of the cost, those options), or None when one of them has no or a bad value.
+    '--landmark-weight' is None when it was not given."""
+    rest, opts = [], {'--similarity': 'global', '--patch-radius': 7, '--patch-stride': 4, '--landmark-weight': None}
+    it = iter(argv)
+    for a in it:
+        if a not in SIMILARITY:
+            rest.append(a)
+            continue
+        try:
+            opts[a] = SIMILARITY[a](next(it))
+        except (StopIteration, ValueError):
+            return None
+    w = opts['--landmark-weight']
+    if opts['--similarity'] not in ('global', 'patch') or opts['--patch-radius'] < 1 or opts['--patch-stride'] < 1 or \
+            (w is not None and not (w >= 0.0 and np.isfinite(w))):
+        return None
+    return rest, opts
 
 
 def read_lands_csv(path, proj, n_lands):
@@ -104,11 +133,13 @@ def pose_errors(P, P_gt, centre):
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
-    parsed = parse(argv)
-    if parsed is None:
+    cost = parse_similarity(argv)
+    parsed = None if cost is None else parse(cost[0])
+    if parsed is None or (cost[1]['--landmark-weight'] is not None and parsed[1]['--offset'] is not None):
         print(USAGE.format(os.path.basename(sys.argv[0])))
         return 1
     (path, spec, idx), o = parsed
+    so = cost[1]
     idx = int(idx)
     if not torch.cuda.is_available():
         raise nat.DflError('no GPU visible: the DRRs and the similarity are HIP kernels (no CPU path)')
@@ -132,7 +163,8 @@ def main(argv=None):
         X3d = np.array([lands3d[n] for n in names]).reshape(-1, 3)
         centre = reg.volume_centre(vol.shape, geom.I2P)
         back, Ei = np.linalg.inv(geom.I2P), np.linalg.inv(geom.E)
-        kw = dict(popsize=o['--popsize'], generations=o['--generations'], sigma0=o['--sigma'], step_mm=o['--step'], seed=o['--seed'])
+        kw = dict(popsize=o['--popsize'], generations=o['--generations'], sigma0=o['--sigma'], step_mm=o['--step'], seed=o['--seed'],
+                  similarity=so['--similarity'], patch_radius=so['--patch-radius'], patch_stride=so['--patch-stride'])
         if o['--offset'] is not None:
             Dm = reg.pose_delta(o['--offset'], centre)
             start = [Dm @ geom.poses[k] for k in drr.POSES]
@@ -149,9 +181,12 @@ def main(argv=None):
                 x2d = np.stack([full[:, preprocess.LAND_ORDER.index(n)] for n in names], 1) if names else np.zeros((2, 0))
             P_start = reg.pnp(geom, X3d, x2d)
             start = [P_start] * 3
-            res = reg.register(vol, geom, fixed, moving=(0, 1, 2), P0=P_start, **kw)
+            res = reg.register(vol, geom, fixed, moving=(0, 1, 2), P0=P_start, landmarks=(X3d, x2d),
+                               landmark_weight=so['--landmark-weight'] or 0.0, **kw)
         poses, trace, renders = list(res.poses), [res.cost], res.renders
         print('pelvis: cost {:.6f} -> {:.6f} in {} renders'.format(res.cost[0], res.final_cost, res.renders))
+        if res.landmark_cost:
+            print('pelvis: similarity {:.6f}, landmark term {:.6f}'.format(res.similarity_cost, res.landmark_cost))
         if o['--femurs']:
             for n in (1, 2):
                 held = drr.Geometry(geom.K, geom.E, geom.poses, geom.I2P, geom.G,
@@ -173,7 +208,7 @@ def main(argv=None):
         panel = np.concatenate([to_u8(fixed.cpu().numpy()), to_u8(view(start)), to_u8(view(poses))], 1)
         png.write(prefix + '_reg.png', np.repeat(panel[:, :, None], 3, 2))
         np.savez(prefix + '_reg.npz', start_poses=np.stack(start), poses=np.stack(poses), cost=np.concatenate(trace), theta=res.theta,
-                 start_lands=lands(start[0]), lands=lands(poses[0]), land_names=np.array(names))
+                 similarity_cost=res.similarity_cost, landmark_cost=res.landmark_cost, start_lands=lands(start[0]), lands=lands(poses[0]), land_names=np.array(names))
         print('wrote {0}_reg.npz, {0}_reg.png ({1} x {2}, {3} renders)'.format(prefix, geom.size[0], geom.size[1], renders))
         if has_gt:
             P_gt = geom.poses[drr.POSES[0]]

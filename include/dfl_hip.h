@@ -48,8 +48,8 @@ const char* dfl_last_error(void);
  * bn_bwd_finalize, bn_relu_bwd, affine_copy, pool, head_fwd, head_bwd, loss, ensemble, op, reduce_job, prep,
  * est_lands, upsample, augment_args, augment_item, overlay, resample_plan, resample_args, fullres, mesh_mc,
  * mesh_decode, mesh_topo, mesh_csr, mesh_smooth, mesh_xform, mesh_normals, preproc_projs, preproc_segs, restore_labels,
- * sim_prepare, sim_gradncc, expose, drr_object, drr_args, optim_pack): lets a binding written
- * in another language verify its struct mirrors at load time.  Returns -1 past the end. */
+ * sim_prepare, sim_gradncc, expose, sim_patch_prepare, sim_patch_gradncc, drr_object, drr_args, optim_pack): lets a
+ * binding written in another language verify its struct mirrors at load time.  Returns -1 past the end. */
 int dfl_sizeof(int which);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -1070,6 +1070,58 @@ typedef struct {
 } dfl_sim_gradncc_args;
 int dfl_sim_gradncc(const dfl_sim_gradncc_args* a, dfl_stream_t stream);
 int64_t dfl_sim_scratch_doubles(int32_t V, int32_t H, int32_t W);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Patch-wise gradient-NCC (csrc/sim_patch.hip; DESIGN.md section 18 states the semantics, tests/patch_ref.py restates
+ * them in numpy float64).  Gradients, counted pixels and the "variance is 0" rule are those of dfl_sim_prepare above.
+ *
+ * Interior coordinates i = r - 1 in [0, H - 2), j = c - 1 in [0, W - 2); radius rho >= 1, side S = 2 rho + 1, stride
+ * s >= 1.  Patch (a, b) covers i in [a s, a s + S), j in [b s, b s + S); a = 0 .. PR - 1, PR = (H - 2 - S) / s + 1 (integer
+ * division), b = 0 .. PC - 1 likewise: patches lie wholly inside the interior, and trailing rows and columns that no
+ * patch reaches are not used.  A patch lives when it holds at least min_count counted pixels; it counts in x when it
+ * lives and the variance of the fixed gx over its counted pixels is not 0, in y likewise.  Per patch and direction ncc
+ * is the ncc above over the patch's counted pixels (0 when the moving variance is 0);
+ *   cost[v] = 1 - (X + Y) / 2,  X = the mean of ncc_x over the patches that count in x (0 when none does), Y likewise.
+ *
+ * dfl_sim_patch_prepare, once per fixed image, from the planes dfl_sim_prepare wrote: ptotals[P][DFL_SIM_TOTALS] =
+ * n, sum fx, sum fx^2, sum fy, sum fy^2 per patch, P = PR PC = dfl_sim_patch_count(H, W, rho, stride) in row-major (a, b)
+ * order; pflags[P]: bit 0 = counts in x, bit 1 = counts in y; pcount[2] = how many patches count in x, in y.
+ * dfl_sim_patch_gradncc, once per batch: a workgroup owns one patch row of one view: column sums of the band in LDS
+ * (6 (W - 2) doubles, hence DFL_SIM_PATCH_MAX_W), one thread per patch, ONE record of two doubles (sum ncc_x, sum ncc_y)
+ * per workgroup in scratch; a second kernel adds a view's PR records in index order and divides by pcount.  No atomics: a
+ * view's cost has the same bits whatever else is in the batch.  scratch holds at least
+ * dfl_sim_patch_scratch_doubles(V, H, W, rho, stride) = 2 V PR doubles.  Both size functions are negative on bad sizes.
+ * Refused with nothing launched: NULL pointers, H < 3, W < 3, H W >= 2^31, V < 1, V > 65535, rho < 1, stride < 1,
+ * min_count < 1, a patch larger than the interior (H - 2 < S or W - 2 < S), W > DFL_SIM_PATCH_MAX_W, a short scratch.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define DFL_SIM_PATCH_MAX_W 1538
+typedef struct {
+  const float* fx;                /* the three planes of dfl_sim_prepare for the same H, W */
+  const float* fy;
+  const unsigned char* counted;
+  double* ptotals;                /* [P][DFL_SIM_TOTALS] */
+  unsigned char* pflags;          /* [P] */
+  int32_t* pcount;                /* [2] */
+  int32_t H, W, rho, stride, min_count, reserved;
+} dfl_sim_patch_prepare_args;
+int dfl_sim_patch_prepare(const dfl_sim_patch_prepare_args* a, dfl_stream_t stream);
+
+typedef struct {
+  const float* moving;            /* [V][H][W] */
+  const float* fx;                /* the planes of dfl_sim_prepare and the outputs of dfl_sim_patch_prepare, same sizes */
+  const float* fy;
+  const unsigned char* counted;
+  const double* ptotals;
+  const unsigned char* pflags;
+  const int32_t* pcount;
+  double* scratch;                /* [V][PR][2] */
+  double* cost;                   /* [V] */
+  int64_t scratch_doubles;        /* what scratch holds */
+  int32_t V, H, W, rho, stride, reserved;
+} dfl_sim_patch_gradncc_args;
+int dfl_sim_patch_gradncc(const dfl_sim_patch_gradncc_args* a, dfl_stream_t stream);
+int64_t dfl_sim_patch_count(int32_t H, int32_t W, int32_t rho, int32_t stride);
+int64_t dfl_sim_patch_scratch_doubles(int32_t V, int32_t H, int32_t W, int32_t rho, int32_t stride);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Detector model: rendered line integrals -> detector intensities (csrc/expose.hip; DESIGN.md section 17 states the

@@ -7,6 +7,8 @@ phantom's poses and the candidates are drawn around a start 2 units away in ever
   render      dfl_drr_render, trilinear, step 1 mm, tight boxes, 32 views
   similarity  dfl_sim_gradncc on those 32 views (two kernels), and the same cost computed with torch ops on the device
               (conv2d Sobel, float64 sums) as the yardstick for the kernel
+  patch       dfl_sim_patch_gradncc on the same views (two kernels; radius 7, stride 4: 41 x 41 patches of 15 x 15), timed
+              the same way, and a whole generation of register(similarity='patch') next to one with the global cost
   host        what is left of a whole generation of register(): sampling, the batched packing, the upload of the
               records, the copy of 32 doubles and the CMA-ES update
 
@@ -34,6 +36,7 @@ sys.path.insert(0, os.path.join(ROOT, 'tools'))
 import bench_drr as B  # noqa: E402
 
 FACTOR, LAMBDA, STEP_MM = 8, 32, 1.0
+PATCH_RADIUS, PATCH_STRIDE = 7, 4
 THETA0 = (2.0, -2.0, 2.0, 2.0, -2.0, 2.0)
 
 
@@ -108,28 +111,49 @@ def main():
     res['render'] = windows(lambda: nat.call('dfl_drr_render', a, stream), args.window, args.reps)
     res['similarity'] = windows(lambda: nat.call('dfl_sim_gradncc', sa, stream), args.window, args.reps)
     res['similarity_torch_ops'] = windows(lambda: torch_cost(att, fixed), args.window, args.reps)
+    psim = reg.PatchSimilarity(fixed, None, LAMBDA, PATCH_RADIUS, PATCH_STRIDE)
+    pa = psim.args(att)
+    nat.call('dfl_sim_patch_gradncc', pa, stream)
+    pcost = psim.out.cpu().numpy()
+    assert np.isfinite(pcost).all() and (pcost > 0).all() and (pcost < 2).all(), pcost
+    res['similarity_patch'] = dict(windows(lambda: nat.call('dfl_sim_patch_gradncc', pa, stream), args.window, args.reps),
+                                   radius=PATCH_RADIUS, stride=PATCH_STRIDE, patches=psim.patches,
+                                   patches_counting=psim.pcount.cpu().numpy().tolist())
     res['pack_poses_host_ms'] = None
     t0 = time.perf_counter()
     for _ in range(50):
         drr.pack(vol, A[:, None] @ np.stack([ob.c2i for ob in objects])[None], [ob.mask for ob in objects], grid, 'trilinear', True)
     res['pack_poses_host_ms'] = round((time.perf_counter() - t0) / 50 * 1e3, 4)
-    reg.register(vol, geom, fixed, theta0=THETA0, popsize=LAMBDA, generations=3, step_mm=STEP_MM)     # warm-up
-    gens, per = 20, []
-    for rep in range(args.reps + 1):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        reg.register(vol, geom, fixed, theta0=THETA0, popsize=LAMBDA, generations=gens, step_mm=STEP_MM, seed=rep)
-        dt = time.perf_counter() - t0
-        if rep == 0:                                                                  # size the window from the first run
-            gens = max(int(args.window / (dt / (gens + 1))) + 1, 5)
-            continue
-        per.append(1e3 * dt / (gens + 1))                                             # + 1: the evaluation of the final mean
-    res['generation'] = {'ms': round(statistics.median(per), 4), 'min_ms': round(min(per), 4), 'max_ms': round(max(per), 4),
-                         'generations_per_window': gens}
+
+    def generation(**kw):
+        reg.register(vol, geom, fixed, theta0=THETA0, popsize=LAMBDA, generations=3, step_mm=STEP_MM, **kw)  # warm-up
+        gens, per = 20, []
+        for rep in range(args.reps + 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            reg.register(vol, geom, fixed, theta0=THETA0, popsize=LAMBDA, generations=gens, step_mm=STEP_MM, seed=rep, **kw)
+            dt = time.perf_counter() - t0
+            if rep == 0:                                                              # size the window from the first run
+                gens = max(int(args.window / (dt / (gens + 1))) + 1, 5)
+                continue
+            per.append(1e3 * dt / (gens + 1))                                         # + 1: the evaluation of the final mean
+        return {'ms': round(statistics.median(per), 4), 'min_ms': round(min(per), 4), 'max_ms': round(max(per), 4),
+                'generations_per_window': gens}
+
+    res['generation'] = generation()
+    res['generation_patch'] = generation(similarity='patch', patch_radius=PATCH_RADIUS, patch_stride=PATCH_STRIDE)
+    g, gp = res['generation'], res['generation_patch']
+    spread = max(g['max_ms'] - g['min_ms'], gp['max_ms'] - gp['min_ms'])
+    res['patch_generation_check'] = {'rule': 'generation_patch.ms <= generation.ms * 1.01 + the larger spread (max - min) of the two',
+                                     'spread_ms': round(spread, 4), 'limit_ms': round(g['ms'] * 1.01 + spread, 4),
+                                     'ok': bool(gp['ms'] <= g['ms'] * 1.01 + spread)}
     res['host_side'] = {'ms': round(res['generation']['ms'] - res['render']['ms'] - res['similarity']['ms'], 4)}
     print('180 x 180, lambda 32: generation %.3f ms = render %.3f + similarity %.3f (torch ops %.3f) + host %.3f (of which packing %.3f)'
           % (res['generation']['ms'], res['render']['ms'], res['similarity']['ms'], res['similarity_torch_ops']['ms'], res['host_side']['ms'],
              res['pack_poses_host_ms']), flush=True)
+    print('patch cost (radius %d, stride %d, %d patches): similarity %.4f ms (global %.4f), generation %.3f ms (global %.3f, limit %.3f: %s)'
+          % (PATCH_RADIUS, PATCH_STRIDE, psim.patches, res['similarity_patch']['ms'], res['similarity']['ms'], gp['ms'], g['ms'],
+             res['patch_generation_check']['limit_ms'], 'ok' if res['patch_generation_check']['ok'] else 'TOO SLOW'), flush=True)
     del keep
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, 'w') as fh:
