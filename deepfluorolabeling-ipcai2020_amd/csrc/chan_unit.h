@@ -9,22 +9,6 @@
 
 namespace dfl {
 
-// 8 bf16 (16 bytes, channel j in half-word j) <-> 8 fp32; pack8 rounds to nearest even
-__device__ __forceinline__ void unpack8(const u32x4 w, float* f) {
-  f[0] = __uint_as_float(w.x << 16); f[1] = __uint_as_float(w.x & 0xffff0000u);
-  f[2] = __uint_as_float(w.y << 16); f[3] = __uint_as_float(w.y & 0xffff0000u);
-  f[4] = __uint_as_float(w.z << 16); f[5] = __uint_as_float(w.z & 0xffff0000u);
-  f[6] = __uint_as_float(w.w << 16); f[7] = __uint_as_float(w.w & 0xffff0000u);
-}
-__device__ __forceinline__ u32x4 pack8(const float* f) {
-  u32x4 w;
-  w.x = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_t){f[0], f[1]}, bf16x2_t));
-  w.y = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_t){f[2], f[3]}, bf16x2_t));
-  w.z = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_t){f[4], f[5]}, bf16x2_t));
-  w.w = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_t){f[6], f[7]}, bf16x2_t));
-  return w;
-}
-
 // `base` is the tensor, `elem` the offset of the unit's first channel in elements (2 bytes for bf16, 4 for fp32).
 template <int W, bool BF>
 struct ChanUnit {

@@ -53,6 +53,7 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+constexpr uint32_t OOB = 0x80000000u;   // buffer offset beyond any tensor we accept (< 2 GiB): the load returns 0, the store is dropped
 
 // ---- split-bf16 products (DFL math modes 1 "bf16x3" and 2 "bf16x6"; see conv_gemm.hip) ------------------------------
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
@@ -67,6 +68,19 @@ __device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 
 __device__ __forceinline__ uint32_t pack_bf2(float a, float b) {
   const bf16x2_t h = __builtin_convertvector((f32x2_t){a, b}, bf16x2_t);   // round to nearest even (v_cvt_pk_bf16_f32)
   return __builtin_bit_cast(uint32_t, h);
+}
+// 8 bf16 (16 bytes, channel j in half-word j) <-> 8 fp32; pack8 rounds to nearest even
+__device__ __forceinline__ void unpack8(const u32x4 w, float* f) {
+  f[0] = bf_lo(w.x); f[1] = bf_hi(w.x); f[2] = bf_lo(w.y); f[3] = bf_hi(w.y);
+  f[4] = bf_lo(w.z); f[5] = bf_hi(w.z); f[6] = bf_lo(w.w); f[7] = bf_hi(w.w);
+}
+__device__ __forceinline__ u32x4 pack8(const float* f) {
+  u32x4 w;
+  w.x = pack_bf2(f[0], f[1]);
+  w.y = pack_bf2(f[2], f[3]);
+  w.z = pack_bf2(f[4], f[5]);
+  w.w = pack_bf2(f[6], f[7]);
+  return w;
 }
 
 // x = p[0] + p[1] (+ p[2]) + O(2^-8NP |x|): successive bf16 roundings of the residual; 4 values -> 4 bf16 per part

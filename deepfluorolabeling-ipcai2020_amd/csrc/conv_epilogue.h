@@ -6,7 +6,6 @@
 namespace dfl {
 
 constexpr int KC = 16;
-constexpr uint32_t OOB = 0x80000000u;   // buffer offset beyond any tensor we accept (< 2 GiB): the load returns 0
 
 struct ConvK {
   dfl_conv_args a;

@@ -28,27 +28,17 @@
 namespace dfl {
 namespace {
 
-constexpr uint32_t NOOB = 0x80000000u;
-typedef unsigned int nu32x4 __attribute__((ext_vector_type(4)));
 
 
 // layouts (convn_layouts): waves side by side (32 pixels each) x rows per wave; the patch is 32 WX pixels wide and R (4 / WX) rows high
-
-#ifndef DFL_CONVN_WL
-#define DFL_CONVN_WL 0       // several channel blocks: a block's weights through LDS and the next block requested ahead (0: the register ring; A/B builds)
-#endif
-#ifndef DFL_CONVN_OCC4
-#define DFL_CONVN_OCC4 0
-#endif
 #ifndef DFL_CONVN_UGM
 #define DFL_CONVN_UGM 10
 #endif
-// waves per SIMD the registers are budgeted for: three (168 registers) for layers of ONE channel block with one column tile and up
-// to four rows per wave; two (256) otherwise -- several blocks keep the next block's units in registers through the k loop
-constexpr int n_occ(int nct, int r, bool mb) { return (!mb || !DFL_CONVN_WL) && nct == 1 ? (r <= 3 && !mb && DFL_CONVN_OCC4 ? 4 : r <= 4 ? 3 : 2) : 2; }
-// (two column tiles x six rows are 192 accumulator registers: not built; nor two column tiles x four rows for several channel blocks,
-// where the next block's units would have to sit beside 128 accumulator registers)
-constexpr bool n_inst(int nct, int r, bool mb) { return !(nct == 2 && (r > 4 || (mb && DFL_CONVN_WL != 0 && r >= 4))); }
+// waves per SIMD the registers are budgeted for: three (168 registers) with one column tile and up to four rows per wave; two (256)
+// otherwise
+constexpr int n_occ(int nct, int r) { return nct == 1 && r <= 4 ? 3 : 2; }
+// (two column tiles x six rows are 192 accumulator registers: not built)
+constexpr bool n_inst(int nct, int r) { return !(nct == 2 && r > 4); }
 
 // PERS (layers of ONE channel block and 32 columns; rows per wave <= 3): the workgroup is PERSISTENT -- it walks patches pr, pr + q_stride,
 // ... of its XCD's run.  The layer's 18 KB of weights sit in LDS, so the k loop waits on LDS only and the NEXT patch's units, requested
@@ -57,7 +47,7 @@ constexpr bool n_inst(int nct, int r, bool mb) { return !(nct == 2 && (r > 4 || 
 // of the current patch runs behind that.  The statistics stay in registers over all patches of the workgroup and cross lanes and waves
 // once, at the end (rows of stat_partials: the workgroup's first patch carries its sum, its other patches zeros).
 template <int CK, int NCT, int WX, int R, int AFF, bool MB, bool PERS>
-__global__ void __launch_bounds__(256, PERS ? 2 : n_occ(NCT, R, MB)) convn_kernel(const ConvP p) {
+__global__ void __launch_bounds__(256, PERS ? 2 : n_occ(NCT, R)) convn_kernel(const ConvP p) {
   static_assert(!PERS || (!MB && NCT == 1 && R <= 3), "the persistent form: one channel block, 32 columns, three rows per wave");
   constexpr int NT = 256, WY = 4 / WX, PW = 32 * WX, PH = R * WY, IW = PW + 2, IH = PH + 2;
   constexpr int S = 2 * CK + 16;               // bytes per staged pixel: an odd multiple of 16, so the 32 pixels of a fragment read hit 16 bank quads twice
@@ -115,35 +105,31 @@ __global__ void __launch_bounds__(256, PERS ? 2 : n_occ(NCT, R, MB)) convn_kerne
   const uint32_t w_voff = (uint32_t)(li * 32 + lh * 16);
   const uint32_t nt32 = (uint32_t)a.Ntot * 32u;
   const uint32_t tapS = (uint32_t)(a.Cin >> 4) * nt32;
-  // MB (several channel blocks): a block's weights -- 9 CKC pieces of NCT KB, piece (tap, chunk) -- pass through LDS beside the
-  // image instead: the k loop then waits on LDS only, and the NEXT block's image and weights, requested before the loop, are in
-  // flight through it (vector memory returns in order: a wait for a weight fragment would be a wait for the image).
-  constexpr bool WL = (MB && DFL_CONVN_WL != 0) || PERS;
-  constexpr int WRS = WL ? 2 : RING;
-  nu32x4 wreg[WRS][3 * NCT];
+  // PERS: the layer's weights -- 9 CKC pieces of NCT KB, piece (tap, chunk) -- sit in LDS beside the image instead (see above)
+  constexpr int WRS = PERS ? 2 : RING;
+  u32x4 wreg[WRS][3 * NCT];
   auto load_w = [&](const int gi, const uint32_t wb, const bool live) __attribute__((always_inline)) {
     const int c = gi / 3, dx = gi % 3;
 #pragma unroll
     for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
       for (int ct = 0; ct < NCT; ++ct) {
-        if constexpr (WL) {
-          wreg[gi % WRS][dy * NCT + ct] = *reinterpret_cast<const nu32x4*>(smem + p.tab_off - 9 * CKC * 1024 * NCT + ((dy * 3 + dx) * CKC + c) * 1024 * NCT + ct * 1024 + w_voff);
+        if constexpr (PERS) {
+          wreg[gi % WRS][dy * NCT + ct] = *reinterpret_cast<const u32x4*>(smem + p.tab_off - 9 * CKC * 1024 * NCT + ((dy * 3 + dx) * CKC + c) * 1024 * NCT + ct * 1024 + w_voff);
         } else {
           const uint32_t soff = wb + (uint32_t)(dy * 3 + dx) * tapS + (uint32_t)c * nt32 + (uint32_t)ct * 1024u;
-          wreg[gi % WRS][dy * NCT + ct] = __builtin_amdgcn_raw_buffer_load_b128(rsW, live ? w_voff : NOOB, live ? soff : 0u, 0);
+          wreg[gi % WRS][dy * NCT + ct] = __builtin_amdgcn_raw_buffer_load_b128(rsW, live ? w_voff : OOB, live ? soff : 0u, 0);
         }
       }
   };
   auto wbase = [&](int blk) { return (uint32_t)(blk * CKC) * nt32; };
-  if constexpr (!WL) {
+  if constexpr (!PERS) {
 #pragma unroll
     for (int g = 0; g < RING - 1; ++g) load_w(g, 0u, true);
   }
-  // (MB) weight unit j of this thread: 16 bytes at LDS offset (tid + 256 j) 16 of the block's 9 CKC NCT KB; piece (tid + 256 j) / (64 NCT)
-  constexpr int WU = WL ? (9 * CKC * 64 * NCT + NT - 1) / NT : 1;
-  constexpr bool WPRE = true;
-  nu32x4 wu[WU];
+  // (PERS) weight unit j of this thread: 16 bytes at LDS offset (tid + 256 j) 16 of the block's 9 CKC NCT KB; piece (tid + 256 j) / (64 NCT)
+  constexpr int WU = PERS ? (9 * CKC * 64 * NCT + NT - 1) / NT : 1;
+  u32x4 wu[WU];
   auto wstage_load = [&](int blk) __attribute__((always_inline)) {
 #pragma unroll
     for (int j = 0; j < WU; ++j) {
@@ -151,14 +137,14 @@ __global__ void __launch_bounds__(256, PERS ? 2 : n_occ(NCT, R, MB)) convn_kerne
       const int pc = __builtin_amdgcn_readfirstlane(u / (64 * NCT));        // (wave-uniform: 64 NCT units per piece)
       const int t = pc / CKC, c = pc - t * CKC;
       const bool live = pc < 9 * CKC;
-      wu[j] = __builtin_amdgcn_raw_buffer_load_b128(rsW, live ? (uint32_t)((u & (64 * NCT - 1)) * 16) : NOOB, live ? (uint32_t)t * tapS + (uint32_t)(blk * CKC + c) * nt32 : 0u, 0);
+      wu[j] = __builtin_amdgcn_raw_buffer_load_b128(rsW, live ? (uint32_t)((u & (64 * NCT - 1)) * 16) : OOB, live ? (uint32_t)t * tapS + (uint32_t)(blk * CKC + c) * nt32 : 0u, 0);
     }
   };
   auto wstage_store = [&]() __attribute__((always_inline)) {
 #pragma unroll
     for (int j = 0; j < WU; ++j) {
       const int u = tid + j * NT;
-      if (u < 9 * CKC * 64 * NCT) *reinterpret_cast<nu32x4*>(smem + p.tab_off - 9 * CKC * 1024 * NCT + u * 16) = wu[j];
+      if (u < 9 * CKC * 64 * NCT) *reinterpret_cast<u32x4*>(smem + p.tab_off - 9 * CKC * 1024 * NCT + u * 16) = wu[j];
     }
   };
 
@@ -175,9 +161,9 @@ __global__ void __launch_bounds__(256, PERS ? 2 : n_occ(NCT, R, MB)) convn_kerne
   uint32_t x_voff, x2_voff, xo_voff, hpix;
   auto patch_lanes = [&]() {                        // this thread's offsets in the patch being staged
     col_ok = gx0 + px < a.Win;
-    x_voff = col_ok ? (uint32_t)((gx0 + px) * a.ldx * 2 + cg * 16) : NOOB;
-    x2_voff = col_ok ? (uint32_t)((gx0 + px) * a.ldx2 * 2 + cg * 16) : NOOB;
-    xo_voff = col_ok ? (uint32_t)((gx0 + px) * a.ldxo * 2 + cg * 16) : NOOB;
+    x_voff = col_ok ? (uint32_t)((gx0 + px) * a.ldx * 2 + cg * 16) : OOB;
+    x2_voff = col_ok ? (uint32_t)((gx0 + px) * a.ldx2 * 2 + cg * 16) : OOB;
+    xo_voff = col_ok ? (uint32_t)((gx0 + px) * a.ldxo * 2 + cg * 16) : OOB;
     const int hgx = hside ? gx0 + PW : gx0 - 1, hgy = gy0 - 1 + hrow;
     h_ok = tid < NUH && (unsigned)hgx < (unsigned)a.Win && (unsigned)hgy < (unsigned)a.Hin;
     hpix = ((uint32_t)img * (uint32_t)a.Hin + (uint32_t)hgy) * (uint32_t)a.Win + (uint32_t)hgx;
@@ -188,10 +174,10 @@ __global__ void __launch_bounds__(256, PERS ? 2 : n_occ(NCT, R, MB)) convn_kerne
   float* col_tab = in_tab + 3 * a.Cin;                               // [NB]: bias
   float* red2 = col_tab + NB;                                        // [2][NB][4]: the statistics' partial sums
 
-  struct Unit { nu32x4 v, v2; };
+  struct Unit { u32x4 v, v2; };
   float tA[8], tB[8], tC[8];                                         // coefficients of this thread's 8 channels of the current block
   auto transform = [&](const Unit& un, const bool ok) __attribute__((always_inline)) {
-    nu32x4 w = un.v;
+    u32x4 w = un.v;
     if constexpr (AFF == 1) {                      // zero padding applies AFTER the BatchNorm affine: outside pixels stay 0
       if (ok) {
         w.x = pack_bf2(fmaf(bf_lo(w.x), tA[0], tB[0]), fmaf(bf_hi(w.x), tA[1], tB[1]));
@@ -201,7 +187,7 @@ __global__ void __launch_bounds__(256, PERS ? 2 : n_occ(NCT, R, MB)) convn_kerne
       }
     }
     if constexpr (AFF == 2) {                      // outside pixels were loaded as zeros: r = 0 there, the value stays 0
-      const nu32x4 r = un.v2;
+      const u32x4 r = un.v2;
       auto brb = [](float dy, float rv, float A, float B, float Cc) { return rv > 0.f ? fmaf(A, dy, fmaf(B, rv, Cc)) : 0.f; };
       w.x = pack_bf2(brb(bf_lo(w.x), bf_lo(r.x), tA[0], tB[0], tC[0]), brb(bf_hi(w.x), bf_hi(r.x), tA[1], tB[1], tC[1]));
       w.y = pack_bf2(brb(bf_lo(w.y), bf_lo(r.y), tA[2], tB[2], tC[2]), brb(bf_hi(w.y), bf_hi(r.y), tA[3], tB[3], tC[3]));
@@ -223,14 +209,13 @@ __global__ void __launch_bounds__(256, PERS ? 2 : n_occ(NCT, R, MB)) convn_kerne
     }
   };
   // requests of a block's image (at most UG interior units per thread in flight at once behind the first round), then their transform
-  // and LDS writes.  The first round of the FIRST block takes UG0 units; of a later block UGP units, requested before the previous
-  // block's k loop and held in registers through it (as many as the register budget of two waves per SIMD leaves).
+  // and LDS writes.  The first round takes UG units; in the persistent form UGP units of the NEXT patch, requested before the current
+  // patch's k loop and held in registers through it (as many as the register budget of two waves per SIMD leaves).
   constexpr int UPR_ = AFF == 2 ? 8 : 4;                            // registers per unit
   constexpr int UGM = AFF == 2 ? 5 : DFL_CONVN_UGM;
   constexpr int UG = (UI + (UI + UGM - 1) / UGM - 1) / ((UI + UGM - 1) / UGM);
-  constexpr int P_AVAIL = PERS ? (256 - (16 * R + 8 * (R + 2) + 24 + 44 + 32)) / UPR_ - 1      // (the statistics' 32 registers; weights and tables are read again)
-                               : (256 - (16 * R * NCT + 8 * (R + 2) + 24 * NCT + (WPRE ? 4 * WU : 0) + 44 + (AFF == 2 ? 24 : AFF == 1 ? 16 : 0))) / UPR_ - 1;   // (- 1: the halo unit)
-  constexpr int UGP = !WL ? 0 : (P_AVAIL >= UI ? UI : (P_AVAIL > 0 ? P_AVAIL : 0));
+  constexpr int P_AVAIL = (256 - (16 * R + 8 * (R + 2) + 24 + 44 + 32)) / UPR_ - 1;   // (the statistics' 32 registers; weights and tables are read again; - 1: the halo unit)
+  constexpr int UGP = !PERS ? 0 : (P_AVAIL >= UI ? UI : (P_AVAIL > 0 ? P_AVAIL : 0));
   constexpr int UGX = UG > UGP ? UG : UGP;
   Unit ui[UGX], uh;
   auto stage_load = [&](int c0, const int j0, const int cnt) __attribute__((always_inline)) {
@@ -242,12 +227,12 @@ __global__ void __launch_bounds__(256, PERS ? 2 : n_occ(NCT, R, MB)) convn_kerne
       const int gy = gy0 - 1 + prow0 + j * RPP;
       const bool rok = (unsigned)gy < (unsigned)a.Hin;
       const uint32_t rowpix = ((uint32_t)img * (uint32_t)a.Hin + (uint32_t)gy) * (uint32_t)a.Win;
-      ui[jj].v = __builtin_amdgcn_raw_buffer_load_b128(rsX, rok ? x_voff : NOOB, rok ? rowpix * (uint32_t)a.ldx * 2u + cb : 0u, 0);
-      if constexpr (AFF == 2) ui[jj].v2 = __builtin_amdgcn_raw_buffer_load_b128(rsR, rok ? x2_voff : NOOB, rok ? rowpix * (uint32_t)a.ldx2 * 2u + cb : 0u, 0);
+      ui[jj].v = __builtin_amdgcn_raw_buffer_load_b128(rsX, rok ? x_voff : OOB, rok ? rowpix * (uint32_t)a.ldx * 2u + cb : 0u, 0);
+      if constexpr (AFF == 2) ui[jj].v2 = __builtin_amdgcn_raw_buffer_load_b128(rsR, rok ? x2_voff : OOB, rok ? rowpix * (uint32_t)a.ldx2 * 2u + cb : 0u, 0);
     }
     if (j0 == 0) {
-      uh.v = __builtin_amdgcn_raw_buffer_load_b128(rsX, h_ok ? hpix * (uint32_t)a.ldx * 2u + cb + (uint32_t)(cg * 16) : NOOB, 0, 0);
-      if constexpr (AFF == 2) uh.v2 = __builtin_amdgcn_raw_buffer_load_b128(rsR, h_ok ? hpix * (uint32_t)a.ldx2 * 2u + cb + (uint32_t)(cg * 16) : NOOB, 0, 0);
+      uh.v = __builtin_amdgcn_raw_buffer_load_b128(rsX, h_ok ? hpix * (uint32_t)a.ldx * 2u + cb + (uint32_t)(cg * 16) : OOB, 0, 0);
+      if constexpr (AFF == 2) uh.v2 = __builtin_amdgcn_raw_buffer_load_b128(rsR, h_ok ? hpix * (uint32_t)a.ldx2 * 2u + cb + (uint32_t)(cg * 16) : OOB, 0, 0);
     }
   };
   auto stage_store = [&](int c0, const int j0, const int cnt) __attribute__((always_inline)) {
@@ -257,16 +242,16 @@ __global__ void __launch_bounds__(256, PERS ? 2 : n_occ(NCT, R, MB)) convn_kerne
       if (j >= UI) break;
       const int row = prow0 + j * RPP, gy = gy0 - 1 + row;
       const bool rok = (unsigned)gy < (unsigned)a.Hin;
-      const nu32x4 w = transform(ui[jj], rok && col_ok);
+      const u32x4 w = transform(ui[jj], rok && col_ok);
       if constexpr (AFF == 2) {
         if (store_on && row >= 1 && row <= PH && rok) {            // x_out: the patch's own pixels (wave-uniform condition)
           const uint32_t rowpix = ((uint32_t)img * (uint32_t)a.Hin + (uint32_t)gy) * (uint32_t)a.Win;
           __builtin_amdgcn_raw_buffer_store_b128(w, rsO, xo_voff, rowpix * (uint32_t)a.ldxo * 2u + (uint32_t)(c0 * 2), 0);
         }
       }
-      *reinterpret_cast<nu32x4*>(smem + lds_i + (uint32_t)(row * RPB)) = w;
+      *reinterpret_cast<u32x4*>(smem + lds_i + (uint32_t)(row * RPB)) = w;
     }
-    if (j0 == 0 && tid < NUH) *reinterpret_cast<nu32x4*>(smem + lds_h) = transform(uh, h_ok);
+    if (j0 == 0 && tid < NUH) *reinterpret_cast<u32x4*>(smem + lds_h) = transform(uh, h_ok);
   };
   auto stage_rest = [&](int c0, const int from) __attribute__((always_inline)) {      // the rounds behind the first
 #pragma unroll
@@ -278,7 +263,7 @@ __global__ void __launch_bounds__(256, PERS ? 2 : n_occ(NCT, R, MB)) convn_kerne
 
   // ---- first block: its loads go out first, the tables are derived while they fly
   stage_load(0, 0, UG);
-  if constexpr (WL) wstage_load(0);
+  if constexpr (PERS) wstage_load(0);
   if (tid < NB) {
     const int col = tid;
     col_tab[tid] = (a.bias != nullptr && col < a.Ntot) ? a.bias[col] : 0.f;
@@ -305,7 +290,7 @@ __global__ void __launch_bounds__(256, PERS ? 2 : n_occ(NCT, R, MB)) convn_kerne
   __syncthreads();                                  // tables complete
   load_tab(0);
   stage_store(0, 0, UG);
-  if constexpr (WL) wstage_store();
+  if constexpr (PERS) wstage_store();
   stage_rest(0, UG);
 
   // ---- k loop
@@ -332,7 +317,7 @@ __global__ void __launch_bounds__(256, PERS ? 2 : n_occ(NCT, R, MB)) convn_kerne
     const int c = gi / 3, dx = gi % 3;
 #pragma unroll
     for (int rr = 0; rr < R + 2; ++rr)
-      fr[gi % 2][rr] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const nu32x4*>(smem + f_addr + (uint32_t)(rr * RPB + dx * S + c * 32)));
+      fr[gi % 2][rr] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4*>(smem + f_addr + (uint32_t)(rr * RPB + dx * S + c * 32)));
   };
   for (;;) {                                        // (PERS: the patches of this workgroup; else one pass)
   const int o_pidx = pidx, o_img = img, o_gy0 = gy0, o_gx0 = gx0;     // the patch whose image is in LDS: the one the epilogue writes
@@ -355,18 +340,12 @@ __global__ void __launch_bounds__(256, PERS ? 2 : n_occ(NCT, R, MB)) convn_kerne
         if constexpr (UGP > 0) stage_load(0, 0, UGP);
       }
       load_w(0, 0u, true);
-    } else if constexpr (WL) {
-      if (more) {                                   // the next block: in flight through this block's k loop
-        if constexpr (WPRE) wstage_load(blk + 1);
-        if constexpr (UGP > 0) stage_load((blk + 1) * CK, 0, UGP);
-      }
-      load_w(0, 0u, true);
     }
     const uint32_t wb = wbase(blk), wbn = wbase(blk + 1);
     fetch_f(0);
 #pragma unroll
     for (int gi = 0; gi < NG; ++gi) {
-      if constexpr (WL) {
+      if constexpr (PERS) {
         if (gi + 1 < NG) load_w(gi + 1, 0u, true);
       } else {
         const int g = gi + RING - 1;
@@ -385,13 +364,11 @@ __global__ void __launch_bounds__(256, PERS ? 2 : n_occ(NCT, R, MB)) convn_kerne
       __builtin_amdgcn_sched_barrier(0);            // keep the prefetch distance as written
     }
     if (MB && more) {
-      if constexpr (!WPRE) wstage_load(blk + 1);
-      if constexpr (UGP == 0) stage_load((blk + 1) * CK, 0, UG);
+      stage_load((blk + 1) * CK, 0, UG);
       load_tab((blk + 1) * CK);
       __syncthreads();                              // every wave is through this block's fragments
-      stage_store((blk + 1) * CK, 0, UGP > 0 ? UGP : UG);
-      if constexpr (WL) wstage_store();
-      stage_rest((blk + 1) * CK, UGP > 0 ? UGP : UG);
+      stage_store((blk + 1) * CK, 0, UG);
+      stage_rest((blk + 1) * CK, UG);
     }
   }
   if constexpr (PERS) {
@@ -409,7 +386,7 @@ __global__ void __launch_bounds__(256, PERS ? 2 : n_occ(NCT, R, MB)) convn_kerne
   const bool do_stats = a.stat_partials != nullptr || a.stat_totals != nullptr;
   const int ogx = o_gx0 + wx * 32 + li;
   const bool ocol_ok = ogx < p.Wg;
-  const uint32_t y_voff = ocol_ok ? (uint32_t)(ogx * a.ldy * 2 + lh * 16) : NOOB;
+  const uint32_t y_voff = ocol_ok ? (uint32_t)(ogx * a.ldy * 2 + lh * 16) : OOB;
   const uint32_t so_voff = (uint32_t)(ogx * a.ldso * 2 + lh * 8);
   const unsigned short* sop = reinterpret_cast<const unsigned short*>(a.stat_other);
   const float relu_floor = a.relu ? 0.f : -__builtin_inff();
@@ -466,7 +443,7 @@ __global__ void __launch_bounds__(256, PERS ? 2 : n_occ(NCT, R, MB)) convn_kerne
       for (int gp = 0; gp < 2; ++gp) {
         const auto sw0 = __builtin_amdgcn_permlane32_swap(pk[gp * 4 + 0], pk[gp * 4 + 2], false, false);
         const auto sw1 = __builtin_amdgcn_permlane32_swap(pk[gp * 4 + 1], pk[gp * 4 + 3], false, false);
-        nu32x4 w;
+        u32x4 w;
         w.x = sw0[0]; w.y = sw1[0]; w.z = sw0[1]; w.w = sw1[1];
         __builtin_amdgcn_raw_buffer_store_b128(w, rsY, y_voff, rowpix * (uint32_t)a.ldy * 2u + (uint32_t)((ct * 32 + gp * 16) * 2), 0);
       }
@@ -521,10 +498,10 @@ __global__ void __launch_bounds__(256, PERS ? 2 : n_occ(NCT, R, MB)) convn_kerne
 }
 
 // LDS: the image, (several channel blocks) a block's weights, the tables
-static size_t n_tab_off(int layout, int cin, int ntot, int pers) {
+static size_t n_tab_off(int layout, int ntot, int pers) {
   const NLayout c = convn_layouts()[layout];
   const size_t img = (size_t)(c.R * (4 / c.WX) + 2) * (32 * c.WX + 2) * (2 * 32 + 16);
-  return (img + 15) / 16 * 16 + ((cin > 32 && DFL_CONVN_WL != 0) || pers != 0 ? (size_t)18 * 1024 * (ntot / 32) : 0);
+  return (img + 15) / 16 * 16 + (pers != 0 ? (size_t)18 * 1024 * (ntot / 32) : 0);
 }
 
 template <int NCT, int WX, int R, bool MB, bool PERS>
@@ -557,9 +534,9 @@ int convn_launch_n(const ConvPlan& pl, hipStream_t s) {
   }
   if (p.a.Ntot == 32) return p.nblk > 1 ? convn_launch_t<1, WX, R, true, false>(pl, s) : convn_launch_t<1, WX, R, false, false>(pl, s);
   if (p.nblk > 1) {
-    if constexpr (n_inst(2, R, true)) return convn_launch_t<2, WX, R, true, false>(pl, s);
+    if constexpr (n_inst(2, R)) return convn_launch_t<2, WX, R, true, false>(pl, s);
   } else {
-    if constexpr (n_inst(2, R, false)) return convn_launch_t<2, WX, R, false, false>(pl, s);
+    if constexpr (n_inst(2, R)) return convn_launch_t<2, WX, R, false, false>(pl, s);
   }
   set_error("dfl_conv2d (bf16, narrow 3x3): configuration %d is not built for 64 columns and %d input channels", p.tile, p.a.Cin);
   return DFL_ERR_INVALID_ARG;
@@ -583,12 +560,12 @@ bool convn_shape_ok(const dfl_conv_args& a) {
   // registers -- measured slower than convp: 29 against 27 us for the 96 x 96 64 -> 64 data gradient)
 }
 
-bool convn_layout_ok(int layout, int ntot, int cin) { return layout >= 0 && layout < kNumN && n_inst(ntot / 32, convn_layouts()[layout].R, cin > 32); }
+bool convn_layout_ok(int layout, int ntot, int cin) { return layout >= 0 && layout < kNumN && n_inst(ntot / 32, convn_layouts()[layout].R); }
 
 bool convn_pers_ok(int layout, const dfl_conv_args& a) { return layout >= 0 && layout < kNumN && convn_layouts()[layout].R <= 3 && a.Cin == 32 && a.Ntot == 32; }
 
 size_t convn_lds_bytes(int layout, int cin, int ntot, int pers, int* tab_off) {
-  size_t img = n_tab_off(layout, cin, ntot, pers);
+  size_t img = n_tab_off(layout, ntot, pers);
   if (tab_off != nullptr) *tab_off = (int)img;
   const size_t red = (size_t)4 * (ntot / 32) * 16 * 64 * sizeof(float);      // the statistics' pass through LDS
   if (img < red) img = red;

@@ -27,15 +27,14 @@
 // Geometry (patch shape, resident channels, K slices, tile configuration) is chosen on the host per layer
 // (convp_plan, conv_plan.hip): candidates are scored by matrix work x rounds over the 256 CUs, including the fill of the last tiles.
 #include "common.h"
+#include "conv_ep_bf16.h"
 #include "convp.h"
 
 namespace dfl {
 
-constexpr uint32_t POOB = 0x80000000u;
 #ifndef DFL_BRB_U
 #define DFL_BRB_U 4
 #endif
-typedef unsigned int pu32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float round_bf(float v) { return (float)(__bf16)v; }
 // q / d for the small row indices of a patch (q < 65536, d < 65536): one multiply-high with m = ceil(2^32 / d) from the host
@@ -53,16 +52,10 @@ __device__ __forceinline__ float ld_bf(const __bf16* p) { return (float)*p; }
 #ifndef DFL_CONVP_G1
 #define DFL_CONVP_G1 4
 #endif
-#ifndef DFL_CONVP_PRIME
-#define DFL_CONVP_PRIME 0   // 1: request a block's first two weight groups before its image is staged.  Measured (round 3): 20-30
-#endif                      // more registers live across the staging, 4.75 -> 4.84 ms/step; six k-steps per ring set: 4.87
-template <int WM, int WN, int TM, int TN, int AFF, bool GA, int KS = 1>
-#ifndef DFL_CONVP_ADEPTH
-#define DFL_CONVP_ADEPTH 1    // k-steps the A fragments run ahead (2, a second register set, measured: no faster)
-#endif
 #ifndef DFL_CONVP_MINW3
 #define DFL_CONVP_MINW3 2
 #endif
+template <int WM, int WN, int TM, int TN, int AFF, bool GA, int KS = 1>
 __global__ void __launch_bounds__(256 * KS, (TM * TN >= 6 || KS == 2) ? 1 : (TM * TN <= 3 ? DFL_CONVP_MINW3 : 2)) convp_kernel(const ConvP p) {
   static_assert(WM * WN == 4, "four waves per k-group");
   static_assert(KS == 1 || (KS == 2 && !GA), "two k-groups: LDS-image form only");
@@ -130,7 +123,7 @@ __global__ void __launch_bounds__(256 * KS, (TM * TN >= 6 || KS == 2) ? 1 : (TM 
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
     const int n = n0 + (wn * TN + j) * 32 + li;
-    b_voff[j] = n < a.Ntot ? (uint32_t)(n * 32 + lh * 16) : POOB;
+    b_voff[j] = n < a.Ntot ? (uint32_t)(n * 32 + lh * 16) : OOB;
   }
 
   f32x16 acc[TM][TN];
@@ -155,14 +148,8 @@ __global__ void __launch_bounds__(256 * KS, (TM * TN >= 6 || KS == 2) ? 1 : (TM 
     const bool scat0 = a.scatter2x2 != 0;
     for (int col = tid; col < BN0; col += NT) {
       const int n = n0 + col;
-      float sc_ = 1.f, sh_ = 0.f, b_ = 0.f;
-      if (n < a.Ntot) {
-        if (a.bias != nullptr) b_ = a.bias[scat0 ? n % p.Cout : n];
-        if (a.add != nullptr) {
-          if (a.add_scale != nullptr) sc_ = a.add_scale[n], sh_ = a.add_shift[n];
-          else if (a.add_tot != nullptr) bn_live_affine(a.add_tot, a.add_gamma, a.add_beta, a.add_count, a.bn_eps, a.Ntot, n, &sc_, &sh_);
-        }
-      }
+      float sc_, sh_, b_;
+      ep_col_consts(a, n, scat0 ? n % p.Cout : n, n < a.Ntot, true, &b_, &sc_, &sh_);
       add_tab[col] = sc_;
       add_tab[BN0 + col] = sh_;
       add_tab[2 * BN0 + col] = b_;
@@ -214,13 +201,13 @@ __global__ void __launch_bounds__(256 * KS, (TM * TN >= 6 || KS == 2) ? 1 : (TM 
       const int py = pdiv(r, p.mPW, p.PW), px = r - py * p.PW;
       const int n = img0 + img, gy = gy0 + py, gx = gx0 + px;
       const bool ok = img < p.IPP && n < a.N && gy < p.Hg && gx < p.Wg;
-      a_goff[i] = ok ? (uint32_t)(((n * a.Hin + gy * a.stride) * a.Win + gx * a.stride) * a.ldx) * 2u + (uint32_t)lh * 16u : POOB;
+      a_goff[i] = ok ? (uint32_t)(((n * a.Hin + gy * a.stride) * a.Win + gx * a.stride) * a.ldx) * 2u + (uint32_t)lh * 16u : OOB;
     }
     constexpr int GG = 2;
     const int chunks = a.Cin >> 4;
     const int steps = p.T * chunks;                    // k = tap * Cin + c, as the weights are packed
     const int ngr = (steps + GG - 1) / GG;
-    pu32x4 areg[3][GG][TM], bqreg[3][GG][TN];
+    u32x4 areg[3][GG][TM], bqreg[3][GG][TN];
     int ls = 0, lcc = 0, ltx = 0;
     uint32_t lao = 0;                                  // byte offset of (tap, chunk) from the window's first pixel
     const uint32_t bstep = (uint32_t)a.Ntot * 32u;
@@ -232,9 +219,9 @@ __global__ void __launch_bounds__(256 * KS, (TM * TN >= 6 || KS == 2) ? 1 : (TM 
         const bool live = ls < steps;
         const uint32_t ao = live ? lao : 0u, bo = live ? (uint32_t)ls * bstep : 0u;
 #pragma unroll
-        for (int i = 0; i < TM; ++i) areg[set][e][i] = __builtin_amdgcn_raw_buffer_load_b128(rsX, live ? a_goff[i] : POOB, ao, 0);
+        for (int i = 0; i < TM; ++i) areg[set][e][i] = __builtin_amdgcn_raw_buffer_load_b128(rsX, live ? a_goff[i] : OOB, ao, 0);
 #pragma unroll
-        for (int j = 0; j < TN; ++j) bqreg[set][e][j] = __builtin_amdgcn_raw_buffer_load_b128(rsW, live ? b_voff[j] : POOB, bo, 0);
+        for (int j = 0; j < TN; ++j) bqreg[set][e][j] = __builtin_amdgcn_raw_buffer_load_b128(rsW, live ? b_voff[j] : OOB, bo, 0);
         ++ls;
         lao += 32u;
         if (++lcc == chunks) {
@@ -278,7 +265,7 @@ __global__ void __launch_bounds__(256 * KS, (TM * TN >= 6 || KS == 2) ? 1 : (TM 
   const int ngroups_all = (S_steps + G - 1) / G;
   // k-group kg takes the ring groups kg, kg + KS, ...: local group gl is global group gl * KS + kg
   const int ngroups = (ngroups_all - kg + KS - 1) / KS;
-  pu32x4 breg[3][G][TN];
+  u32x4 breg[3][G][TN];
   auto load_group = [&](int blk, int gl, int set) {
     const int g = gl * KS + kg;
 #pragma unroll
@@ -288,17 +275,13 @@ __global__ void __launch_bounds__(256 * KS, (TM * TN >= 6 || KS == 2) ? 1 : (TM 
       const int tap = s >> ckc_sh, cc = s & (CKC - 1);
       const uint32_t soff = live ? (uint32_t)((tap * cin_chunks + blk * CKC + cc)) * (uint32_t)a.Ntot * 32u : 0u;
 #pragma unroll
-      for (int j = 0; j < TN; ++j) breg[set][e][j] = __builtin_amdgcn_raw_buffer_load_b128(rsW, live ? b_voff[j] : POOB, soff, 0);
+      for (int j = 0; j < TN; ++j) breg[set][e][j] = __builtin_amdgcn_raw_buffer_load_b128(rsW, live ? b_voff[j] : OOB, soff, 0);
     }
   };
   const int blk_begin = bslice * p.blk_per_slice;
   const int blk_end = min(blk_begin + p.blk_per_slice, p.nblk);
   for (int blk = blk_begin; blk < blk_end; ++blk) {
     const int c0 = blk * p.CK;
-    if (DFL_CONVP_PRIME) {
-      load_group(blk, 0, 0);
-      load_group(blk, 1, 1);
-    }
     // ================================================================ stage the patch image of channels [c0, c0 + CK)
     if (blk != blk_begin) __syncthreads();         // every wave is done reading the previous image
 #ifdef DFL_CONVP_TRACE
@@ -357,7 +340,7 @@ __global__ void __launch_bounds__(256 * KS, (TM * TN >= 6 || KS == 2) ? 1 : (TM 
       const uint32_t cbyte = (uint32_t)((c0 + cg * 8) * 2);
       constexpr int U = AFF == 2 ? DFL_BRB_U : 8;  // loads in flight per thread (two tensors in mode 2)
       for (; pix < npix; pix += U * dpix) {
-        pu32x4 v[U], v2[AFF == 2 ? U : 1];
+        u32x4 v[U], v2[AFF == 2 ? U : 1];
         uint32_t offo[AFF == 2 ? U : 1];
         bool ok[U];
         int pixs[U];
@@ -367,13 +350,13 @@ __global__ void __launch_bounds__(256 * KS, (TM * TN >= 6 || KS == 2) ? 1 : (TM 
           pixs[u] = pix + u * dpix;
           ok[u] = pixs[u] < npix && n < a.N && (unsigned)gy < (unsigned)a.Hin && (unsigned)gx < (unsigned)a.Win;
           const uint32_t off = (uint32_t)(((n * a.Hin + gy) * a.Win + gx) * a.ldx) * 2u + cbyte;
-          v[u] = __builtin_amdgcn_raw_buffer_load_b128(rsX, ok[u] ? off : POOB, 0, 0);
+          v[u] = __builtin_amdgcn_raw_buffer_load_b128(rsX, ok[u] ? off : OOB, 0, 0);
           if constexpr (AFF == 2) {
             const uint32_t off2 = (uint32_t)(((n * a.Hin + gy) * a.Win + gx) * a.ldx2) * 2u + cbyte;
-            v2[u] = __builtin_amdgcn_raw_buffer_load_b128(rsR, ok[u] ? off2 : POOB, 0, 0);
+            v2[u] = __builtin_amdgcn_raw_buffer_load_b128(rsR, ok[u] ? off2 : OOB, 0, 0);
             // (stride 1: gathered pixel (iy, ix) is output pixel (iy - pad, ix - pad) of the patch)
             const bool own = store_on && ok[u] && (unsigned)(iy - a.pad) < (unsigned)p.PH && (unsigned)(ix - a.pad) < (unsigned)p.PW;
-            offo[u] = own ? (uint32_t)(((n * a.Hin + gy) * a.Win + gx) * a.ldxo) * 2u + cbyte : POOB;
+            offo[u] = own ? (uint32_t)(((n * a.Hin + gy) * a.Win + gx) * a.ldxo) * 2u + cbyte : OOB;
           }
           ix += dpix_x;
           iy += dpix_y;
@@ -389,7 +372,7 @@ __global__ void __launch_bounds__(256 * KS, (TM * TN >= 6 || KS == 2) ? 1 : (TM 
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           if (pixs[u] < npix) {
-            pu32x4 w = v[u];
+            u32x4 w = v[u];
             if constexpr (AFF == 1) {              // zero padding applies AFTER the BatchNorm affine: outside pixels stay 0
               if (ok[u]) {
                 w.x = pack_bf2(fmaf(bf_lo(w.x), sc[0], sh[0]), fmaf(bf_hi(w.x), sc[1], sh[1]));
@@ -399,7 +382,7 @@ __global__ void __launch_bounds__(256 * KS, (TM * TN >= 6 || KS == 2) ? 1 : (TM 
               }
             }
             if constexpr (AFF == 2) {              // outside pixels were loaded as zeros: r = 0 there, the value stays 0
-              const pu32x4 r = v2[u];
+              const u32x4 r = v2[u];
               auto brb = [](float dy, float rv, float A, float B, float Cc) { return rv > 0.f ? fmaf(A, dy, fmaf(B, rv, Cc)) : 0.f; };
               w.x = pack_bf2(brb(bf_lo(w.x), bf_lo(r.x), sc[0], sh[0], sq[0]), brb(bf_hi(w.x), bf_hi(r.x), sc[1], sh[1], sq[1]));
               w.y = pack_bf2(brb(bf_lo(w.y), bf_lo(r.y), sc[2], sh[2], sq[2]), brb(bf_hi(w.y), bf_hi(r.y), sc[3], sh[3], sq[3]));
@@ -407,7 +390,7 @@ __global__ void __launch_bounds__(256 * KS, (TM * TN >= 6 || KS == 2) ? 1 : (TM 
               w.w = pack_bf2(brb(bf_lo(w.w), bf_lo(r.w), sc[6], sh[6], sq[6]), brb(bf_hi(w.w), bf_hi(r.w), sc[7], sh[7], sq[7]));
               if (store_on) __builtin_amdgcn_raw_buffer_store_b128(w, rsO, offo[u], 0, 0);     // (outside the interior: out of range, dropped)
             }
-            *reinterpret_cast<pu32x4*>(smem + (uint32_t)pixs[u] * (uint32_t)S + (uint32_t)cg * 16u) = w;
+            *reinterpret_cast<u32x4*>(smem + (uint32_t)pixs[u] * (uint32_t)S + (uint32_t)cg * 16u) = w;
           }
         }
       }
@@ -419,19 +402,17 @@ __global__ void __launch_bounds__(256 * KS, (TM * TN >= 6 || KS == 2) ? 1 : (TM 
 #endif
 
     // ================================================================ k-steps of this block: s = tap * CKC + chunk
-    // A fragments run DFL_CONVP_ADEPTH (1) k-steps ahead of the matrix instructions that use them: the reads of step s + 1 are
-    // issued before the instructions of step s (a fragment read takes 64-128 cycles plus the scalar cursor arithmetic in front of
-    // its address, an instruction 32).  With depth 2 two register sets take turns (G is even: a group always starts on set 0).
-    static_assert(G % 2 == 0 || DFL_CONVP_ADEPTH == 1, "the A-fragment sets alternate inside a group");
-    constexpr int AD = DFL_CONVP_ADEPTH;
-    bf16x8_t afq[AD][TM];
-    auto fetch_a = [&](int s, int slot) {
+    // A fragments run one k-step ahead of the matrix instructions that use them: the reads of step s + 1 are issued before the
+    // instructions of step s (a fragment read takes 64-128 cycles plus the scalar cursor arithmetic in front of its address, an
+    // instruction 32).  (Two steps ahead, a second register set: measured no faster.)
+    bf16x8_t afq[TM];
+    auto fetch_a = [&](int s) {
       s = s < S_steps ? s : S_steps - 1;           // dead steps of the last group: weights were loaded as zeros
       const int tap = s >> ckc_sh, cc = s & (CKC - 1);
       const int ty = (tap * kw_magic) >> 8, tx = tap - ty * KW;
       const uint32_t aoff = (uint32_t)((ty * p.IW + tx) * S + cc * 32);
 #pragma unroll
-      for (int i = 0; i < TM; ++i) afq[slot][i] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const pu32x4*>(smem + a_base[i] + aoff));
+      for (int i = 0; i < TM; ++i) afq[i] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4*>(smem + a_base[i] + aoff));
     };
     auto compute_group = [&](int gl, int set) {
       const int g = gl * KS + kg;
@@ -439,9 +420,9 @@ __global__ void __launch_bounds__(256 * KS, (TM * TN >= 6 || KS == 2) ? 1 : (TM 
       for (int e = 0; e < G; ++e) {
         bf16x8_t af[TM];
 #pragma unroll
-        for (int i = 0; i < TM; ++i) af[i] = afq[e % AD][i];
-        // the step this k-group takes AD steps from now
-        fetch_a(e + AD < G ? g * G + e + AD : (g + KS) * G + (e + AD - G), e % AD);
+        for (int i = 0; i < TM; ++i) af[i] = afq[i];
+        // the step this k-group takes next
+        fetch_a(e + 1 < G ? g * G + e + 1 : (g + KS) * G);
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
           const bf16x8_t bf = __builtin_bit_cast(bf16x8_t, breg[set][e][j]);
@@ -450,12 +431,9 @@ __global__ void __launch_bounds__(256 * KS, (TM * TN >= 6 || KS == 2) ? 1 : (TM 
         }
       }
     };
-#pragma unroll
-    for (int d = 0; d < AD; ++d) fetch_a(kg * G + d, d);
-    if (!DFL_CONVP_PRIME) {
-      load_group(blk, 0, 0);
-      load_group(blk, 1, 1);
-    }
+    fetch_a(kg * G);
+    load_group(blk, 0, 0);
+    load_group(blk, 1, 1);
     for (int g = 0; g < ngroups; g += 3) {
       load_group(blk, g + 2, 2);
       compute_group(g, 0);
@@ -560,7 +538,7 @@ __global__ void __launch_bounds__(256 * KS, (TM * TN >= 6 || KS == 2) ? 1 : (TM 
   const bool cok = ncol < a.Ntot;                     // (Ntot % 8 == 0: a unit is inside or outside as a whole)
   const int cab = (scat && cok) ? ncol / p.Cout : 0;
   const int cco = scat ? ncol - cab * p.Cout : ncol;
-  float cbias[8], casc[8], cash[8], s1[8], s2[8];
+  float cbias[8] __attribute__((aligned(16))), casc[8] __attribute__((aligned(16))), cash[8] __attribute__((aligned(16))), s1[8], s2[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) {                       // (from the table filled at kernel start; barriers passed since)
     casc[e] = add_tab[ucol + e];
@@ -569,10 +547,6 @@ __global__ void __launch_bounds__(256 * KS, (TM * TN >= 6 || KS == 2) ? 1 : (TM 
     s1[e] = 0.f;
     s2[e] = 0.f;
   }
-  auto unpack = [](const pu32x4 w, float* f) {
-    f[0] = bf_lo(w.x); f[1] = bf_hi(w.x); f[2] = bf_lo(w.y); f[3] = bf_hi(w.y);
-    f[4] = bf_lo(w.z); f[5] = bf_hi(w.z); f[6] = bf_lo(w.w); f[7] = bf_hi(w.w);
-  };
   // The per-column constants above must have ARRIVED before the row loops: with a load still outstanding at the loop header the
   // compiler covers their first use inside the loop by s_waitcnt vmcnt(0) -- which, on every iteration, also waits for the
   // previous row's STORE to be acknowledged by memory (measured: 3 us of a workgroup's 13 on a 32-column layer).
@@ -613,48 +587,11 @@ __global__ void __launch_bounds__(256 * KS, (TM * TN >= 6 || KS == 2) ? 1 : (TM 
       const float4 v0 = *reinterpret_cast<const float4*>(ep + rl * EP + ucol);
       const float4 v1 = *reinterpret_cast<const float4*>(ep + rl * EP + ucol + 4);
       v[0] = v0.x; v[1] = v0.y; v[2] = v0.z; v[3] = v0.w; v[4] = v1.x; v[5] = v1.y; v[6] = v1.z; v[7] = v1.w;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        v[e] += cbias[e];
-        if (a.relu) v[e] = fmaxf(v[e], 0.f);
-      }
-      if (addp != nullptr) {
-        float o[8];
-        unpack(*reinterpret_cast<const pu32x4*>(addp + (m * (uint32_t)a.ldadd + (uint32_t)ncol)), o);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] += fmaf(o[e], casc[e], cash[e]);
-      }
       // pixel and column of this unit in y (scatter2x2: the 2x2 position its column group stands for)
       const uint32_t opix = scat ? (uint32_t)((n * a.Hout + 2 * gy + (cab >> 1)) * a.Wout + 2 * gx + (cab & 1)) : m;
       const int ocol = scat ? cco : ncol;
-      const uint32_t yo = opix * (uint32_t)a.ldy + (uint32_t)ocol;
-      if (a.accumulate) {
-        float o[8];
-        unpack(*reinterpret_cast<const pu32x4*>(yp + yo), o);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] += o[e];
-      }
-      pu32x4 w;
-      w.x = pack_bf2(v[0], v[1]);
-      w.y = pack_bf2(v[2], v[3]);
-      w.z = pack_bf2(v[4], v[5]);
-      w.w = pack_bf2(v[6], v[7]);
-      *reinterpret_cast<pu32x4*>(yp + yo) = w;
-      if (do_stats) {
-        float vr[8], u[8];
-        unpack(w, vr);                                // statistics of the values as stored
-        if (sop != nullptr) {
-          unpack(*reinterpret_cast<const pu32x4*>(sop + (opix * (uint32_t)a.ldso + (uint32_t)ocol)), u);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) u[e] = vr[e];
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          s1[e] += vr[e];
-          s2[e] = fmaf(vr[e], u[e], s2[e]);
-        }
-      }
+      ep_row8(a, v, cbias, casc, cash, addp, m * (uint32_t)a.ldadd + (uint32_t)ncol, yp, opix * (uint32_t)a.ldy + (uint32_t)ocol, sop,
+              opix * (uint32_t)a.ldso + (uint32_t)ocol, do_stats, s1, s2);
     }
     TRACC(8, te2)
   }
@@ -669,33 +606,17 @@ __global__ void __launch_bounds__(256 * KS, (TM * TN >= 6 || KS == 2) ? 1 : (TM 
   if (!do_stats) return;
   // per-column sums of the workgroup -> one row of stat_partials (rows = patches): threads of one column unit add up
   // through LDS in a fixed order
-  __syncthreads();
-  float* red = reinterpret_cast<float*>(smem);        // [RPS][2][BN]
-  if (rowthread) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      red[(urow * 2 + 0) * BN + ucol + e] = s1[e];
-      red[(urow * 2 + 1) * BN + ucol + e] = s2[e];
+  ep_stats_tail<BN, RPS, NT>(reinterpret_cast<float*>(smem), s1, s2, urow, ucol, rowthread, n0, a.Ntot, [&](int which, int n, float sum) {
+    if (scat) {                                        // rows = (patch, 2x2 position): [.][2][Cout], the sums of y's Cout channels
+      const int ab = n / p.Cout, co = n - ab * p.Cout;
+      if (a.stat_totals != nullptr) bn_live_add(a.stat_totals, bpatch * 4 + ab, which, p.Cout, co, sum);
+      else a.stat_partials[(((int64_t)bpatch * 4 + ab) * 2 + which) * p.Cout + co] = sum;
+    } else if (a.stat_totals != nullptr) {             // live statistics: added to the layer's totals (hardware fp64 atomics)
+      bn_live_add(a.stat_totals, bpatch, which, a.Ntot, n, sum);
+    } else {
+      a.stat_partials[((int64_t)bpatch * 2 + which) * a.Ntot + n] = sum;
     }
-  }
-  __syncthreads();
-  for (int idx = tid; idx < 2 * BN; idx += NT) {
-    const int which = idx / BN, col = idx - which * BN;
-    const int n = n0 + col;
-    if (n < a.Ntot) {
-      float sum = 0.f;
-      for (int w = 0; w < RPS; ++w) sum += red[(w * 2 + which) * BN + col];
-      if (scat) {                                      // rows = (patch, 2x2 position): [.][2][Cout], the sums of y's Cout channels
-        const int ab = n / p.Cout, co = n - ab * p.Cout;
-        if (a.stat_totals != nullptr) bn_live_add(a.stat_totals, bpatch * 4 + ab, which, p.Cout, co, sum);
-        else a.stat_partials[(((int64_t)bpatch * 4 + ab) * 2 + which) * p.Cout + co] = sum;
-      } else if (a.stat_totals != nullptr) {           // live statistics: added to the layer's totals (hardware fp64 atomics)
-        bn_live_add(a.stat_totals, bpatch, which, a.Ntot, n, sum);
-      } else {
-        a.stat_partials[((int64_t)bpatch * 2 + which) * a.Ntot + n] = sum;
-      }
-    }
-  }
+  });
 }
 
 // K-slice finish: y = epilogue(sum_s partial[s]) -- conv_finish_kernel of conv_gemm.hip for bf16 tensors.
@@ -712,14 +633,8 @@ __global__ void __launch_bounds__(256) convp_finish_kernel(const ConvP p, int TX
     ab = n / p.Cout;
     co = n - ab * p.Cout;
   }
-  const float bias = (a.bias != nullptr && nok) ? a.bias[co] : 0.f;
-  float asc = 1.f, ash = 0.f;
-  if (a.add != nullptr && a.add_scale != nullptr && nok) {
-    asc = a.add_scale[n];
-    ash = a.add_shift[n];
-  } else if (a.add != nullptr && a.add_tot != nullptr && nok) {
-    bn_live_affine(a.add_tot, a.add_gamma, a.add_beta, a.add_count, a.bn_eps, Ntot, n, &asc, &ash);
-  }
+  float bias, asc, ash;
+  ep_col_consts(a, n, co, nok, true, &bias, &asc, &ash);
   const __bf16* addp = reinterpret_cast<const __bf16*>(a.add);
   const __bf16* sop = reinterpret_cast<const __bf16*>(a.stat_other);
   __bf16* yp = reinterpret_cast<__bf16*>(a.y);

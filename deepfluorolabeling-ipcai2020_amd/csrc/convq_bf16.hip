@@ -22,18 +22,12 @@
 // Summation order differs from convp's (chunks inside taps inside channel blocks, k-groups by chunk halves): results agree
 // to fp32 rounding, as between two convp geometries.
 #include "common.h"
+#include "conv_ep_bf16.h"
 #include "convp.h"
 
 namespace dfl {
 namespace {
 
-constexpr uint32_t QOOB = 0x80000000u;
-typedef unsigned int qu32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void q_unpack(const qu32x4 w, float* f) {
-  f[0] = bf_lo(w.x); f[1] = bf_hi(w.x); f[2] = bf_lo(w.y); f[3] = bf_hi(w.y);
-  f[4] = bf_lo(w.z); f[5] = bf_hi(w.z); f[6] = bf_lo(w.w); f[7] = bf_hi(w.w);
-}
 
 constexpr int QPW = 12, QIW = 14, QTM = 3;   // patch width, staged width, 32-row tiles per wave
 constexpr int q_row_pitch(int ck) {
@@ -158,16 +152,16 @@ __global__ void __launch_bounds__(64 * WM * WN * KS, 2) convq_kernel(const ConvP
 
   // ---- weight ring: group g of a block = k-steps g*GS .. g*GS + GS - 1 of this k-group; step s = (tap s / CCL, chunk s % CCL)
   const int ncol = n0 + wn * 32 + li;
-  const uint32_t b_voff = ncol < a.Ntot ? (uint32_t)(ncol * 32 + lh * 16) : QOOB;
+  const uint32_t b_voff = ncol < a.Ntot ? (uint32_t)(ncol * 32 + lh * 16) : OOB;
   const uint32_t nt32 = (uint32_t)a.Ntot * 32u;
   const uint32_t tapS = (uint32_t)(a.Cin >> 4) * nt32;
-  qu32x4 breg[3][GS];
+  u32x4 breg[3][GS];
   auto load_group = [&](const int g, const uint32_t wb, const bool live) __attribute__((always_inline)) {
 #pragma unroll
     for (int e = 0; e < GS; ++e) {
       const int s = g * GS + e, t = s / CCL, c = s % CCL;
       const uint32_t soff = wb + (uint32_t)t * tapS + (uint32_t)c * nt32;
-      breg[g % 3][e] = __builtin_amdgcn_raw_buffer_load_b128(rsW, live ? b_voff : QOOB, live ? soff : 0u, 0);
+      breg[g % 3][e] = __builtin_amdgcn_raw_buffer_load_b128(rsW, live ? b_voff : OOB, live ? soff : 0u, 0);
     }
   };
   auto wbase = [&](int blk) { return (uint32_t)(blk * CKC + kg * CCL) * nt32; };
@@ -179,7 +173,7 @@ __global__ void __launch_bounds__(64 * WM * WN * KS, 2) convq_kernel(const ConvP
   const int pix0 = tid / UPX;
   float* col_tab = reinterpret_cast<float*>(smem + p.tab_off);   // [3][QBN]: bias, scale and shift of "+ BN(add)" of the workgroup's columns
   float* in_tab = col_tab + 3 * QBN;                              // [3][CKS]: scale, shift (AFF 1) / A, B, C (AFF 2) of the slice's channels
-  struct Unit { qu32x4 v, v2; };
+  struct Unit { u32x4 v, v2; };
   auto unit_pix = [&](int j) { return pix0 + j * (NT / UPX); };
   auto unit_load = [&](int j, const Pos& ps, int c0, bool live, Unit* un) __attribute__((always_inline)) {
     const int pix = unit_pix(j);
@@ -188,8 +182,8 @@ __global__ void __launch_bounds__(64 * WM * WN * KS, 2) convq_kernel(const ConvP
     const bool ok = live && pix < QNPIX && (unsigned)gy < (unsigned)a.Hin && (unsigned)gx < (unsigned)a.Win;
     const uint32_t pixel = ((uint32_t)ps.img * (uint32_t)a.Hin + (uint32_t)gy) * (uint32_t)a.Win + (uint32_t)gx;
     const uint32_t cb = (uint32_t)((c0 + cg * 8) * 2);
-    un->v = __builtin_amdgcn_raw_buffer_load_b128(rsX, ok ? pixel * (uint32_t)a.ldx * 2u + cb : QOOB, 0, 0);
-    if constexpr (AFF == 2) un->v2 = __builtin_amdgcn_raw_buffer_load_b128(rsR, ok ? pixel * (uint32_t)a.ldx2 * 2u + cb : QOOB, 0, 0);
+    un->v = __builtin_amdgcn_raw_buffer_load_b128(rsX, ok ? pixel * (uint32_t)a.ldx * 2u + cb : OOB, 0, 0);
+    if constexpr (AFF == 2) un->v2 = __builtin_amdgcn_raw_buffer_load_b128(rsR, ok ? pixel * (uint32_t)a.ldx2 * 2u + cb : OOB, 0, 0);
   };
   // (the decode is repeated here instead of carried in registers: a dozen integer instructions per unit against 6-10 live registers)
   auto unit_store = [&](int j, const Pos& ps, int c0, int crel, uint32_t buf, const Unit& un) __attribute__((always_inline)) {
@@ -198,7 +192,7 @@ __global__ void __launch_bounds__(64 * WM * WN * KS, 2) convq_kernel(const ConvP
     const int iy = pix / QIW, ix = pix - iy * QIW;
     const int gy = ps.gy0 - 1 + iy, gx = ps.gx0 - 1 + ix;
     const bool ok = (unsigned)gy < (unsigned)a.Hin && (unsigned)gx < (unsigned)a.Win;
-    qu32x4 w = un.v;
+    u32x4 w = un.v;
     if constexpr (AFF == 1) {                      // zero padding applies AFTER the BatchNorm affine: outside pixels stay 0
       if (ok) {
         const float4 s0 = *reinterpret_cast<const float4*>(in_tab + crel + cg * 8), s1 = *reinterpret_cast<const float4*>(in_tab + crel + cg * 8 + 4);
@@ -210,7 +204,7 @@ __global__ void __launch_bounds__(64 * WM * WN * KS, 2) convq_kernel(const ConvP
       }
     }
     if constexpr (AFF == 2) {                      // outside pixels were loaded as zeros: r = 0 there, the value stays 0
-      const qu32x4 r = un.v2;
+      const u32x4 r = un.v2;
       const float4 A0 = *reinterpret_cast<const float4*>(in_tab + crel + cg * 8), A1 = *reinterpret_cast<const float4*>(in_tab + crel + cg * 8 + 4);
       const float4 B0 = *reinterpret_cast<const float4*>(in_tab + CKS + crel + cg * 8), B1 = *reinterpret_cast<const float4*>(in_tab + CKS + crel + cg * 8 + 4);
       const float4 C0 = *reinterpret_cast<const float4*>(in_tab + 2 * CKS + crel + cg * 8), C1 = *reinterpret_cast<const float4*>(in_tab + 2 * CKS + crel + cg * 8 + 4);
@@ -222,10 +216,10 @@ __global__ void __launch_bounds__(64 * WM * WN * KS, 2) convq_kernel(const ConvP
       if (store_on) {                              // x_out: the interior of the patch, this slice's channels
         const bool own = ok && (unsigned)(iy - 1) < (unsigned)QPH && (unsigned)(ix - 1) < (unsigned)QPW;
         const uint32_t pixel = ((uint32_t)ps.img * (uint32_t)a.Hin + (uint32_t)gy) * (uint32_t)a.Win + (uint32_t)gx;
-        __builtin_amdgcn_raw_buffer_store_b128(w, rsO, own ? pixel * (uint32_t)a.ldxo * 2u + (uint32_t)((c0 + cg * 8) * 2) : QOOB, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(w, rsO, own ? pixel * (uint32_t)a.ldxo * 2u + (uint32_t)((c0 + cg * 8) * 2) : OOB, 0, 0);
       }
     }
-    *reinterpret_cast<qu32x4*>(smem + buf + (uint32_t)(iy * RPB + ix * S) + (uint32_t)cg * 16u) = w;
+    *reinterpret_cast<u32x4*>(smem + buf + (uint32_t)(iy * RPB + ix * S) + (uint32_t)cg * 16u) = w;
   };
 
   // ---- first image: its loads go out first, the tables are derived while they fly
@@ -240,13 +234,8 @@ __global__ void __launch_bounds__(64 * WM * WN * KS, 2) convq_kernel(const ConvP
     // whole workgroup waited 1.4-2 us for them: phase clocks of round 6)
     if (tid < QBN) {                                 // (QBN <= 128 < NT)
       const int col = n0 + tid;
-      const bool ok = col < a.Ntot;
-      float b_ = 0.f, sc_ = 1.f, sh_ = 0.f;
-      if (a.bias != nullptr && ok && p.splits <= 1) b_ = a.bias[col];
-      if (a.add != nullptr && ok) {
-        if (a.add_scale != nullptr) sc_ = a.add_scale[col], sh_ = a.add_shift[col];
-        else if (a.add_tot != nullptr) bn_live_affine(a.add_tot, a.add_gamma, a.add_beta, a.add_count, a.bn_eps, a.Ntot, col, &sc_, &sh_);
-      }
+      float b_, sc_, sh_;
+      ep_col_consts(a, col, col, col < a.Ntot, p.splits <= 1, &b_, &sc_, &sh_);     // (K slices: the finish kernel adds the bias)
       col_tab[tid] = b_;
       col_tab[QBN + tid] = sc_;
       col_tab[2 * QBN + tid] = sh_;
@@ -307,7 +296,7 @@ __global__ void __launch_bounds__(64 * WM * WN * KS, 2) convq_kernel(const ConvP
     const int t = s / CCL, c = s % CCL;
     const int off = (t / 3) * RPB + (t % 3) * S + c * 32;
 #pragma unroll
-    for (int i = 0; i < QTM; ++i) afr[s % 3][i] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const qu32x4*>(smem + a_addr[i] + off));
+    for (int i = 0; i < QTM; ++i) afr[s % 3][i] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4*>(smem + a_addr[i] + off));
   };
   // epilogue constants of this thread
   const int ucol = (tid % UPR) * 8, urow = tid / UPR;
@@ -434,74 +423,17 @@ __global__ void __launch_bounds__(64 * WM * WN * KS, 2) convq_kernel(const ConvP
           *reinterpret_cast<float4*>(part + 4) = make_float4(v[4], v[5], v[6], v[7]);
           continue;
         }
-        {                                           // (the per-column constants come from the LDS table row by row: 24 registers less to hold)
-          const float4 b0 = *reinterpret_cast<const float4*>(col_tab + ucol), b1 = *reinterpret_cast<const float4*>(col_tab + ucol + 4);
-          const float cb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            v[e] += cb[e];
-            if (a.relu) v[e] = fmaxf(v[e], 0.f);
-          }
-        }
-        if (addp != nullptr) {
-          float o[8];
-          q_unpack(*reinterpret_cast<const qu32x4*>(addp + (m * (uint32_t)a.ldadd + (uint32_t)ecol)), o);
-          const float4 c0 = *reinterpret_cast<const float4*>(col_tab + QBN + ucol), c1 = *reinterpret_cast<const float4*>(col_tab + QBN + ucol + 4);
-          const float4 h0 = *reinterpret_cast<const float4*>(col_tab + 2 * QBN + ucol), h1 = *reinterpret_cast<const float4*>(col_tab + 2 * QBN + ucol + 4);
-          const float sc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w}, sh[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] += fmaf(o[e], sc[e], sh[e]);
-        }
-        const uint32_t yo = m * (uint32_t)a.ldy + (uint32_t)ecol;
-        if (a.accumulate) {
-          float o[8];
-          q_unpack(*reinterpret_cast<const qu32x4*>(yp + yo), o);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] += o[e];
-        }
-        qu32x4 w;
-        w.x = pack_bf2(v[0], v[1]);
-        w.y = pack_bf2(v[2], v[3]);
-        w.z = pack_bf2(v[4], v[5]);
-        w.w = pack_bf2(v[6], v[7]);
-        *reinterpret_cast<qu32x4*>(yp + yo) = w;
-        if (do_stats) {
-          float vr[8], u[8];
-          q_unpack(w, vr);                          // statistics of the values as stored
-          if (sop != nullptr) {
-            q_unpack(*reinterpret_cast<const qu32x4*>(sop + (m * (uint32_t)a.ldso + (uint32_t)ecol)), u);
-          } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) u[e] = vr[e];
-          }
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            s1[e] += vr[e];
-            s2[e] = fmaf(vr[e], u[e], s2[e]);
-          }
-        }
+        // (the per-column constants come from the LDS table row by row: 24 registers less to hold)
+        ep_row8(a, v, col_tab + ucol, col_tab + QBN + ucol, col_tab + 2 * QBN + ucol, addp, m * (uint32_t)a.ldadd + (uint32_t)ecol, yp,
+                m * (uint32_t)a.ldy + (uint32_t)ecol, sop, m * (uint32_t)a.ldso + (uint32_t)ecol, do_stats, s1, s2);
       }
     }
     if (do_stats) {
       // per-column sums of this patch -> one row of stat_partials (rows = patches) or the layer's live totals; fixed order
-      __syncthreads();
-      float* red = ep;                              // [RPS][2][QBN]
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        red[(urow * 2 + 0) * QBN + ucol + e] = s1[e];
-        red[(urow * 2 + 1) * QBN + ucol + e] = s2[e];
-      }
-      __syncthreads();
-      for (int idx = tid; idx < 2 * QBN; idx += NT) {
-        const int which = idx / QBN, col = idx - which * QBN;
-        const int n = n0 + col;
-        if (n < a.Ntot) {
-          float sum = 0.f;
-          for (int w = 0; w < RPS; ++w) sum += red[(w * 2 + which) * QBN + col];
-          if (a.stat_totals != nullptr) bn_live_add(a.stat_totals, pidx, which, a.Ntot, n, sum);
-          else a.stat_partials[((int64_t)pidx * 2 + which) * a.Ntot + n] = sum;
-        }
-      }
+      ep_stats_tail<QBN, RPS, NT>(ep, s1, s2, urow, ucol, true, n0, a.Ntot, [&](int which, int n, float sum) {
+        if (a.stat_totals != nullptr) bn_live_add(a.stat_totals, pidx, which, a.Ntot, n, sum);
+        else a.stat_partials[((int64_t)pidx * 2 + which) * a.Ntot + n] = sum;
+      });
     }
     if (!next_ok) break;
     __syncthreads();                                // the epilogue's image region goes back to the staging of the patch after the next

@@ -48,7 +48,6 @@
 
 namespace dfl {
 
-constexpr uint32_t SOOB = 0x80000000u;
 // Waves per workgroup, a template parameter: 8 (512 threads, one workgroup per CU) where eight waves share a tile's k-steps, 4 (256
 // threads, two workgroups per CU) otherwise -- a layer of 1152 wave tasks then is 288 workgroups over all 256 CUs instead of 144 on 144
 // (the fragments of this form are not reused across waves: a CU's L1 fill is what a 36-k-step layer waits for).
@@ -126,10 +125,10 @@ struct ElemBF16 : StoreBF16 {
   struct WAddr { uint32_t row, col; };               // chunk-packed [k/16][n][16]: bytes per k-step, this lane's column and half
   static __device__ __forceinline__ WAddr w_addr(int Ntot, int n, int lh) { return {(uint32_t)Ntot * 32u, (uint32_t)n * 32u + (uint32_t)lh * 16u}; }
   static __device__ __forceinline__ Frag load_x(__amdgpu_buffer_rsrc_t rs, bool ok, uint32_t off) {
-    return __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? off : SOOB, 0, 0);
+    return __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? off : OOB, 0, 0);
   }
   static __device__ __forceinline__ Frag load_w(__amdgpu_buffer_rsrc_t rs, bool ok, int s, const WAddr& wa) {
-    return __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? (uint32_t)s * wa.row + wa.col : SOOB, 0, 0);
+    return __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? (uint32_t)s * wa.row + wa.col : OOB, 0, 0);
   }
   static __device__ __forceinline__ void affine(Frag& x, const float4 s0, const float4 s1, const float4 h0, const float4 h1, bool ok) {
     Frag y;
@@ -172,15 +171,15 @@ struct ElemF32 : StoreF32 {
   static __device__ __forceinline__ WAddr w_addr(int Ntot, int n, int lh) { return {(uint32_t)Ntot * 16u, (uint32_t)n * 16u, 2 * lh}; }
   static __device__ __forceinline__ Frag load_x(__amdgpu_buffer_rsrc_t rs, bool ok, uint32_t off) {
     Frag f;
-    f.v0 = __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? off : SOOB, 0, 0);
-    f.v1 = __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? off + 16u : SOOB, 0, 0);
+    f.v0 = __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? off : OOB, 0, 0);
+    f.v1 = __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? off + 16u : OOB, 0, 0);
     return f;
   }
   static __device__ __forceinline__ Frag load_w(__amdgpu_buffer_rsrc_t rs, bool ok, int s, const WAddr& wa) {
     const uint32_t wo = (uint32_t)(s * 4 + wa.lh2) * wa.row + wa.col;
     Frag f;
-    f.v0 = __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? wo : SOOB, 0, 0);
-    f.v1 = __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? wo + wa.row : SOOB, 0, 0);
+    f.v0 = __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? wo : OOB, 0, 0);
+    f.v1 = __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? wo + wa.row : OOB, 0, 0);
     return f;
   }
   static __device__ __forceinline__ void affine(Frag& x, const float4 s0, const float4 s1, const float4 h0, const float4 h1, bool ok) {

@@ -28,8 +28,6 @@
 
 namespace dfl {
 
-constexpr uint32_t WPOOB = 0x80000000u;
-typedef unsigned int wpu32x4 __attribute__((ext_vector_type(4)));
 typedef short ws16x4_t __attribute__((ext_vector_type(4)));
 
 struct WgStep { int img, y, x; };
@@ -76,11 +74,10 @@ __device__ __forceinline__ bf16x8_t wtr_read8(const unsigned char* base, uint32_
   return __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(x, y, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
-typedef unsigned int wpu32x2 __attribute__((ext_vector_type(2)));
 // 4 consecutive pixel rows of one channel (one transposing read), as two dwords
-__device__ __forceinline__ wpu32x2 wtr_read4(const unsigned char* base, uint32_t r0) {
+__device__ __forceinline__ u32x2 wtr_read4(const unsigned char* base, uint32_t r0) {
   typedef __attribute__((address_space(3))) ws16x4_t* lds_p;
-  return __builtin_bit_cast(wpu32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(base + r0)));
+  return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(base + r0)));
 }
 
 // KH x KW window.  4 * KH waves: wave w owns kernel row w % KH (KW taps, KW accumulator tiles) of "slot" w / KH; a slot is
@@ -169,8 +166,8 @@ __global__ void __launch_bounds__(256 * KH, wgp_waves_per_simd(KH)) wgradp_kerne
   // its position inside the patch (y | x << 12 | image << 24 | live << 31) and its byte offset from the patch origin;
   // per patch a unit costs a bounds test against the image and one add.
   constexpr int MAXD = wgp_max_d_units(KH, DBRB) / NT, MAXG = wgp_max_g_units(KH, DBRB) / NT;   // host: P16 * dupp and npix_g * gupp stay below these
-  wpu32x4 dreg[MAXD], greg[MAXG];
-  wpu32x4 d2reg[DBRB ? MAXD : 1];
+  u32x4 dreg[MAXD], greg[MAXG];
+  u32x4 d2reg[DBRB ? MAXD : 1];
   float bsum = 0.f;                                               // DBRB: this thread's share of the bias gradient (one channel)
   const bool bias_on = BIAS && a.bias_partial != nullptr && by == 0;
   uint32_t dpos[MAXD], gpos[MAXG];
@@ -246,10 +243,10 @@ __global__ void __launch_bounds__(256 * KH, wgp_waves_per_simd(KH)) wgradp_kerne
       const int qy = (int)(q & 0xfffu), qx = (int)((q >> 12) & 0xfffu), qi = (int)((q >> 24) & 127u);
       const bool ok = (int)q < 0 && qi < is_nleft && is_oy0 + qy < a.Hout && is_ox0 + qx < a.Wout;
       const uint32_t rel = (uint32_t)((qi * a.Hout + qy) * a.Wout + qx) * dpitch;
-      dreg[u] = __builtin_amdgcn_raw_buffer_load_b128(rsD, ok ? is_dbase + rel : WPOOB, 0, 0);
+      dreg[u] = __builtin_amdgcn_raw_buffer_load_b128(rsD, ok ? is_dbase + rel : OOB, 0, 0);
       if constexpr (DBRB) {
         const uint32_t rel2 = (uint32_t)((qi * a.Hout + qy) * a.Wout + qx) * d2pitch;
-        d2reg[u] = __builtin_amdgcn_raw_buffer_load_b128(rsD2, ok ? is_dbase2 + rel2 : WPOOB, 0, 0);
+        d2reg[u] = __builtin_amdgcn_raw_buffer_load_b128(rsD2, ok ? is_dbase2 + rel2 : OOB, 0, 0);
       }
     }
   };
@@ -260,7 +257,7 @@ __global__ void __launch_bounds__(256 * KH, wgp_waves_per_simd(KH)) wgradp_kerne
       const bool ok = (int)q < 0 && qi < is_nleft && (unsigned)(is_ybase + qy) < (unsigned)a.Hin && (unsigned)(is_xbase + qx) < (unsigned)a.Win;
       gok |= ok ? (1u << u) : 0u;
       const uint32_t rel = (uint32_t)((qi * a.Hin + qy) * a.Win + qx) * gpitch;
-      greg[u] = __builtin_amdgcn_raw_buffer_load_b128(rsG, ok ? is_gbase + rel : WPOOB, 0, 0);
+      greg[u] = __builtin_amdgcn_raw_buffer_load_b128(rsG, ok ? is_gbase + rel : OOB, 0, 0);
     }
   };
   auto issue = [&](int patch, bool live) {
@@ -275,9 +272,9 @@ __global__ void __launch_bounds__(256 * KH, wgp_waves_per_simd(KH)) wgradp_kerne
     for (int u = 0; u < MAXD; ++u) {
       const int k = (tid >> p.dupp_shift) + u * ddk;
       if (u < nd && k < p.P16) {
-        wpu32x4 v = dreg[u];
+        u32x4 v = dreg[u];
         if constexpr (DBRB) {     // [r > 0] * (A dy + B r + C); rows outside the patch / image were loaded as zeros: r = 0, value 0
-          const wpu32x4 r = d2reg[u];
+          const u32x4 r = d2reg[u];
           const float4 a0 = *reinterpret_cast<const float4*>(dco + dcq * 8), a1 = *reinterpret_cast<const float4*>(dco + dcq * 8 + 4);
           const float4 b0 = *reinterpret_cast<const float4*>(dco + p.CMT + dcq * 8), b1 = *reinterpret_cast<const float4*>(dco + p.CMT + dcq * 8 + 4);
           const float4 c0 = *reinterpret_cast<const float4*>(dco + 2 * p.CMT + dcq * 8), c1 = *reinterpret_cast<const float4*>(dco + 2 * p.CMT + dcq * 8 + 4);
@@ -287,14 +284,14 @@ __global__ void __launch_bounds__(256 * KH, wgp_waves_per_simd(KH)) wgradp_kerne
           v.z = pack_bf2(brb(bf_lo(v.z), bf_lo(r.z), a1.x, b1.x, c1.x), brb(bf_hi(v.z), bf_hi(r.z), a1.y, b1.y, c1.y));
           v.w = pack_bf2(brb(bf_lo(v.w), bf_lo(r.w), a1.z, b1.z, c1.z), brb(bf_hi(v.w), bf_hi(r.w), a1.w, b1.w, c1.w));
         }
-        *reinterpret_cast<wpu32x4*>(Ds + (uint32_t)k * (uint32_t)p.sd + (uint32_t)dcq * 16u) = v;
+        *reinterpret_cast<u32x4*>(Ds + (uint32_t)k * (uint32_t)p.sd + (uint32_t)dcq * 16u) = v;
       }
     }
 #pragma unroll
     for (int u = 0; u < MAXG; ++u) {
       const int pix = (tid >> p.gupp_shift) + u * gdk;
       if (u < ng && pix < npix_g) {
-        wpu32x4 v = greg[u];
+        u32x4 v = greg[u];
         if constexpr (AFF) {   // zero padding applies AFTER the BatchNorm affine: outside pixels stay 0
           if ((gok >> u) & 1u) {
             const float4 s0 = *reinterpret_cast<const float4*>(aff + gcq * 8), s1 = *reinterpret_cast<const float4*>(aff + gcq * 8 + 4);
@@ -306,7 +303,7 @@ __global__ void __launch_bounds__(256 * KH, wgp_waves_per_simd(KH)) wgradp_kerne
             v.w = pack_bf2(fmaf(bf_lo(v.w), sc[6], sh[6]), fmaf(bf_hi(v.w), sc[7], sh[7]));
           }
         }
-        *reinterpret_cast<wpu32x4*>(Gs + (uint32_t)pix * (uint32_t)p.sg + (uint32_t)gcq * 16u) = v;
+        *reinterpret_cast<u32x4*>(Gs + (uint32_t)pix * (uint32_t)p.sg + (uint32_t)gcq * 16u) = v;
       }
     }
   };
@@ -407,11 +404,11 @@ __global__ void __launch_bounds__(256 * KH, wgp_waves_per_simd(KH)) wgradp_kerne
         // the 8 pixels of this lane's half of the k-step are consecutive pixels of one image row (PW % 8 == 0, stride 1): 12
         // consecutive gathered pixels -- three transposing reads -- hold all three taps of the kernel row; tap 1 is the same
         // registers shifted by one pixel (v_alignbit).  3 LDS reads instead of 6 in a loop that is bound by them (round 5)
-        const wpu32x2 g0 = wtr_read4(Gs, gr0), g1 = wtr_read4(Gs, gr1), g2 = wtr_read4(Gs, gr0 + 8u * (uint32_t)p.sg);
-        gf[0] = __builtin_bit_cast(bf16x8_t, (wpu32x4){g0.x, g0.y, g1.x, g1.y});
-        gf[1] = __builtin_bit_cast(bf16x8_t, (wpu32x4){__builtin_amdgcn_alignbit(g0.y, g0.x, 16), __builtin_amdgcn_alignbit(g1.x, g0.y, 16),
+        const u32x2 g0 = wtr_read4(Gs, gr0), g1 = wtr_read4(Gs, gr1), g2 = wtr_read4(Gs, gr0 + 8u * (uint32_t)p.sg);
+        gf[0] = __builtin_bit_cast(bf16x8_t, (u32x4){g0.x, g0.y, g1.x, g1.y});
+        gf[1] = __builtin_bit_cast(bf16x8_t, (u32x4){__builtin_amdgcn_alignbit(g0.y, g0.x, 16), __builtin_amdgcn_alignbit(g1.x, g0.y, 16),
                                                         __builtin_amdgcn_alignbit(g1.y, g1.x, 16), __builtin_amdgcn_alignbit(g2.x, g1.y, 16)});
-        gf[KW - 1] = __builtin_bit_cast(bf16x8_t, (wpu32x4){g0.y, g1.x, g1.y, g2.x});
+        gf[KW - 1] = __builtin_bit_cast(bf16x8_t, (u32x4){g0.y, g1.x, g1.y, g2.x});
       } else {
 #pragma unroll
         for (int t = 0; t < KW; ++t) gf[t] = wtr_read8(Gs, gr0 + (uint32_t)(t * p.sg), gr1 + (uint32_t)(t * p.sg));

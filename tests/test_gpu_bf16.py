@@ -90,9 +90,11 @@ def test_pack_bf16_chunk_layout():
 
 def conv_bf16(x, wp, Ntot, KH, KW, stride, pad, Hout, Wout, bias=None, in_aff=None, relu=0, add=None, add_aff=None,
               y_init=None, accumulate=0, scatter=0, stats=False, stat_other=None, ldy=None, ldx_pad=0, force_splits=None, brb=None, x_out=False,
-              latency=False, stats_fill=0.0, live_totals=False):
+              latency=False, stats_fill=0.0, live_totals=False, add_live=None, whole=False):
     """x: NCHW fp32 cpu tensor (bf16-representable) -> dfl_conv2d with bf16 tensors -> y NHWC fp32 cpu tensor (+ stats).
-    x_out (with brb): also returns the operand tensor the kernel wrote (dfl_conv_args.x_out; NHWC with 8 channels of padding)."""
+    x_out (with brb): also returns the operand tensor the kernel wrote (dfl_conv_args.x_out; NHWC with 8 channels of padding).
+    add_live = (totals [8][2][Ntot] fp64, gamma, beta, count, eps): the scale / shift of `add` derived by the kernel (add_tot).
+    whole: y with all ldy channels of a pixel and the statistics as the rows the kernel wrote, not their sum."""
     lib = nat.lib()
     N, Cin, Hin, Win = x.shape
     xh = nhwc(x)
@@ -128,6 +130,10 @@ def conv_bf16(x, wp, Ntot, KH, KW, stride, pad, Hout, Wout, bias=None, in_aff=No
             asc, ash = add_aff[0].to(DEV), add_aff[1].to(DEV)
             keep += [asc, ash]
             a.add_scale, a.add_shift = asc.data_ptr(), ash.data_ptr()
+        if add_live is not None:
+            tot, gam, bet = add_live[0].to(DEV), add_live[1].to(DEV), add_live[2].to(DEV)
+            keep += [tot, gam, bet]
+            a.add_tot, a.add_gamma, a.add_beta, a.add_count, a.bn_eps = tot.data_ptr(), gam.data_ptr(), bet.data_ptr(), add_live[3], add_live[4]
     if brb is not None:                                 # x is dy; operand = [r > 0] * (A dy + B r + C) formed in the staging (x_mode)
         r_, coef = brb
         rd = F.pad(nhwc(r_), (0, 8)).to(DEV).to(BF).contiguous()       # (its own pixel stride)
@@ -170,9 +176,11 @@ def conv_bf16(x, wp, Ntot, KH, KW, stride, pad, Hout, Wout, bias=None, in_aff=No
     assert not latency or cfg == 16 + LATENCY_CFG, 'the latency form was asked for and is eligible here'
     nat.check(lib.dfl_conv2d(C.addressof(a), stream()), 'dfl_conv2d')
     torch.cuda.synchronize()
-    y = yd.float().cpu()[..., :Cout]
+    y = yd.float().cpu() if whole else yd.float().cpu()[..., :Cout]
     if x_out:
         return y, xo.float().cpu()
+    if stats and whole:
+        return y, part.cpu()
     return (y, part.cpu().double().sum(0)) if stats else y
 
 
