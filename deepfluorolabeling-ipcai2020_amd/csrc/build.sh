@@ -15,8 +15,8 @@ for s in "${srcs[@]}"; do
   objs+=("$o")
   stale=0
   if [ ! -f "$o" ]; then stale=1; fi
-  # any header may reach any source: an object is stale when its source or any *.h / *.inc here or the C API is newer
-  for d in "$here/$s" "$here"/*.h "$here"/*.inc "$here/../../include/dfl_hip.h"; do
+  # any header may reach any source: an object is stale when its source or any *.h here or the C API is newer
+  for d in "$here/$s" "$here"/*.h "$here/../../include/dfl_hip.h"; do
     if [ "$d" -nt "$o" ]; then stale=1; fi
   done
   if [ "$stale" = 1 ]; then

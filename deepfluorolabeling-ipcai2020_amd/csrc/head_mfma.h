@@ -1,5 +1,4 @@
-// Heads on the matrix cores (bf16 features, F = 32, up to 8 classes / 24 mid channels / 16 landmarks; round 3).  Included by
-// head.hip inside namespace dfl; not a translation unit of its own.
+// Heads on the matrix cores (bf16 features, F = 32, up to 8 classes / 24 mid channels / 16 landmarks; round 3).
 //
 // Channel-major products: D[channel][pixel] = W[channel][k] * B[k][pixel] with v_mfma_f32_32x32x16_bf16 -- the weights are the
 // A operand (32 rows), 32 consecutive pixels the columns.  A lane then owns ONE pixel (column lane & 31) in every product,
@@ -11,8 +10,13 @@
 //   rows of U  = [logits (0..7) | mid (8..31)]      mid = (W1x + W1c Wseg) x   (folded once per wave, fp32)
 //   rows of V  = [dlogits (0..7) | dmid (8..31)]    dmid = W2^T dheat;  dlogits = softmax'(seg, dseg) + W1c^T dmid
 //   dx         = [Wseg^T | W1x^T] V
-// The three weight gradients are taken as before (head_caps.inc): the tile's rows [V | dheat] and [x | U] go to LDS as bf16
-// -- a lane's B fragments ARE 16-byte pieces of those rows -- and four waves contract them over the 128 pixels of the tile.
+// The three weight gradients are taken from the tile's row image (head_wgrad.h): the rows [V | dheat] and [x | U] go to LDS as
+// bf16 -- a lane's B fragments ARE 16-byte pieces of those rows -- and four waves contract them over the 128 pixels of the tile.
+#pragma once
+#include "common.h"
+#include "head_wgrad.h"
+
+namespace dfl {
 
 struct HFrag { bf16x8_t hi, lo; };
 
@@ -108,7 +112,7 @@ struct HeadW {
   }
 };
 
-constexpr int HM_TILE = 128;   // pixels per workgroup tile (4 waves x 32)
+constexpr int HM_TILE = HEAD_WG_ROWS;   // pixels per workgroup tile (4 waves x 32): one row image
 
 __device__ __forceinline__ bf16x8_t hload_x(const unsigned short* xb, int64_t m, int64_t M, int ldx, int s, int h) {
   uint4 w = make_uint4(0u, 0u, 0u, 0u);
@@ -189,8 +193,7 @@ __global__ void __launch_bounds__(256) head_mfma_fwd_kernel(const dfl_head_fwd_a
 
 template <bool LANDS>
 __global__ void __launch_bounds__(256) head_mfma_bwd_kernel(const dfl_head_bwd_args a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char ab[];       // [128 pixels][320 bytes]: [V | dheat | 0] [x | U]
-  constexpr int ABP = 320;
+  extern __shared__ __attribute__((aligned(16))) unsigned char ab[];       // the tile's row image: HEAD_WG_LDS bytes
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l = lane & 31, h = lane >> 5;
   const bool lands = LANDS && a.dheat != nullptr;                           // (no landmark gradient: dmid = 0)
   const HeadW W{a.w_seg, a.w_l1, a.w_l2, a.NC, a.NM, a.L, 32 + a.NC};
@@ -202,15 +205,12 @@ __global__ void __launch_bounds__(256) head_mfma_bwd_kernel(const dfl_head_bwd_a
     if (LANDS) adl[s] = W.a_dl(l, 16 * s + 8 * h);
   }
   if (LANDS) adm = W.a_dm(l, 8 * h);
-  // weight-gradient tile geometry (as head_bwd_kernel)
-  const int trow = 8 * (lane >> 5) + ((lane & 15) >> 2);
-  const uint32_t tcb = (uint32_t)((16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2);
-  const uint32_t a_col = (uint32_t)((wave >> 1) * 64) + tcb, b_col = 128u + (uint32_t)((wave & 1) * 64) + tcb;
+  const HeadWgLane wg;
   f32x16 wacc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) wacc[r] = 0.f;
-  unsigned char* myrow = ab + (size_t)(wave * 32 + l) * ABP;
-  *reinterpret_cast<uint4*>(myrow + 96 + 16 * h) = make_uint4(0u, 0u, 0u, 0u);    // columns 48..63 of the first row block stay zero
+  unsigned char* myrow = ab + (size_t)(wave * 32 + l) * HEAD_WG_PITCH;
+  *reinterpret_cast<uint4*>(myrow + HEAD_WG_ZERO + 16 * h) = make_uint4(0u, 0u, 0u, 0u);    // stays zero
   const unsigned short* xb = reinterpret_cast<const unsigned short*>(a.x);
   unsigned short* dxb = reinterpret_cast<unsigned short*>(a.dx);
   const unsigned short* sob = reinterpret_cast<const unsigned short*>(a.stat_other);
@@ -278,44 +278,34 @@ __global__ void __launch_bounds__(256) head_mfma_bwd_kernel(const dfl_head_bwd_a
     __syncthreads();                            // the previous tile's weight-gradient reads are done
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      *reinterpret_cast<bf16x8_t*>(myrow + 32 * s + 16 * h) = vf[s].hi;              // V: columns 0..31
-      *reinterpret_cast<bf16x8_t*>(myrow + 192 + 32 * s + 16 * h) = uf[s];           // U: columns 32..63 of the second block
+      *reinterpret_cast<bf16x8_t*>(myrow + HEAD_WG_V + 32 * s + 16 * h) = vf[s].hi;
+      *reinterpret_cast<bf16x8_t*>(myrow + HEAD_WG_U + 32 * s + 16 * h) = uf[s];
     }
-    *reinterpret_cast<bf16x8_t*>(myrow + 64 + 16 * h) = dhf.hi;                      // dheat: columns 32..47
-    *reinterpret_cast<bf16x8_t*>(myrow + 128 + 16 * h) = x0;                         // x: columns 0..31 of the second block
-    *reinterpret_cast<bf16x8_t*>(myrow + 128 + 32 + 16 * h) = x1;
+    *reinterpret_cast<bf16x8_t*>(myrow + HEAD_WG_DHEAT + 16 * h) = dhf.hi;
+    *reinterpret_cast<bf16x8_t*>(myrow + HEAD_WG_X + 16 * h) = x0;
+    *reinterpret_cast<bf16x8_t*>(myrow + HEAD_WG_X + 32 + 16 * h) = x1;
     // dx rows: 8 consecutive features per lane and 16-row group
     if (live) {
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         float t8[8];
         acc_to_b(dx, s, t8);
-        uint4 w;
-        w.x = hpack2(t8[0], t8[1]); w.y = hpack2(t8[2], t8[3]); w.z = hpack2(t8[4], t8[5]); w.w = hpack2(t8[6], t8[7]);
-        *reinterpret_cast<uint4*>(dxb + m * a.lddx + 16 * s + 8 * h) = w;
+        const u32x4 w = pack8(t8);
+        *reinterpret_cast<u32x4*>(dxb + m * a.lddx + 16 * s + 8 * h) = w;
         if (a.stat_totals != nullptr) {                                    // sums of the values as stored
-          const uint4 rr = *reinterpret_cast<const uint4*>(sob + m * a.ldso + 16 * s + 8 * h);
-          const unsigned dw_[4] = {w.x, w.y, w.z, w.w}, rw_[4] = {rr.x, rr.y, rr.z, rr.w};
+          const u32x4 rr = *reinterpret_cast<const u32x4*>(sob + m * a.ldso + 16 * s + 8 * h);
 #pragma unroll
           for (int e2 = 0; e2 < 4; ++e2) {
-            const float d0 = __uint_as_float(dw_[e2] << 16), d1 = __uint_as_float(dw_[e2] & 0xffff0000u);
-            const float r0 = __uint_as_float(rw_[e2] << 16), r1 = __uint_as_float(rw_[e2] & 0xffff0000u);
-            st1[8 * s + 2 * e2] += d0;
-            st1[8 * s + 2 * e2 + 1] += d1;
-            st2[8 * s + 2 * e2] = fmaf(d0, r0, st2[8 * s + 2 * e2]);
-            st2[8 * s + 2 * e2 + 1] = fmaf(d1, r1, st2[8 * s + 2 * e2 + 1]);
+            st1[8 * s + 2 * e2] += bf_lo(w[e2]);
+            st1[8 * s + 2 * e2 + 1] += bf_hi(w[e2]);
+            st2[8 * s + 2 * e2] = fmaf(bf_lo(w[e2]), bf_lo(rr[e2]), st2[8 * s + 2 * e2]);
+            st2[8 * s + 2 * e2 + 1] = fmaf(bf_hi(w[e2]), bf_hi(rr[e2]), st2[8 * s + 2 * e2 + 1]);
           }
         }
       }
     }
     __syncthreads();
-#pragma unroll
-    for (int ks = 0; ks < HM_TILE / 16; ++ks) {
-      const uint32_t r0 = (uint32_t)(ks * 16 + trow) * (uint32_t)ABP, r1 = r0 + 4u * (uint32_t)ABP;
-      const bf16x8_t af = htr_read8(ab, r0 + a_col, r1 + a_col);
-      const bf16x8_t bf = htr_read8(ab, r0 + b_col, r1 + b_col);
-      wacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bf, wacc, 0, 0, 0);
-    }
+    wg.product(ab, wacc);
   }
   if (a.stat_totals != nullptr) {
     // live statistics of dx (include/dfl_hip.h): this lane's sums over its pixels -> the 32 lanes of its half (same channels,
@@ -338,8 +328,7 @@ __global__ void __launch_bounds__(256) head_mfma_bwd_kernel(const dfl_head_bwd_a
       bn_live_add(a.stat_totals, (int)blockIdx.x, which, 32, 16 * s_ + 8 * hh + e, t);
     }
   }
-  float* part = a.wg_partial + (int64_t)blockIdx.x * 4096;                 // partial[block][row of A (64)][column of B (64)]
-  const int col = (wave & 1) * 32 + (lane & 31);
-#pragma unroll
-  for (int r = 0; r < 16; ++r) part[((wave >> 1) * 32 + mfma32_row(r, lane)) * 64 + col] = wacc[r];
+  wg.store(a.wg_partial, wacc);
 }
+
+}  // namespace dfl

@@ -940,15 +940,16 @@ class UNetPlan:
         sld = self.lib.dfl_head_scratch_ld_for(Fx, NC, nm, nl)
         M_ = N * H_ * W_
         dx = self._act(N, H_, W_, Fx)
-        fused_head = bool(x_act.bf16) and Fx == 32 and NC <= 8 and nm <= 24 and nl <= 16 and os.environ.get('DFL_HEAD_FUSED', '1') != '0'
+        fused_head = bool(x_act.bf16) and Fx == 32 and NC <= 8 and nm <= 24 and nl <= 16
         hb = HeadBwdArgs(x=x_act.ptr, w_seg=ws.data_ptr(), w_l1=nat.ptr(w1), w_l2=nat.ptr(w2), dx=dx.ptr, N=N, H=H_, W=W_, F=Fx,
                          ldx=x_act.ld, lddx=dx.ld, NC=NC, NM=nm, L=nl, softmax=1 if self.cfg['do_soft_max'] else 0, scratch_ld=sld,
                          x_bf16=x_act.bf16)
         # bf16 features of the paper's width: the head kernel takes its three weight gradients itself (include/dfl_hip.h);
         # otherwise it leaves a per-pixel scratch row and three 1x1 weight-gradient launches follow
         live = None
-        mfma_head = fused_head and nm <= 24 and (nl == 0 or w2 is not None) and x_act.ld % 8 == 0 and os.environ.get('DFL_HEAD_MFMA', '1') != '0'
-        if mfma_head and live_r is not None and Fx == 32:
+        # mirrors head_mfma_ok (csrc/head.hip), whose 16-byte alignment of w_seg is taken for granted here
+        mfma_head = fused_head and (nl == 0 or w2 is not None) and x_act.ld % 8 == 0
+        if mfma_head and live_r is not None:
             tot = self._bn_totals(Fx, bwd=True)
             hb.stat_other, hb.ldso, hb.stat_totals = live_r.ptr, live_r.ld, tot
             live = ('live', tot)

@@ -1,4 +1,4 @@
-"""Kernel-by-kernel comparison of two builds of the bf16 convolution sources.
+"""Kernel-by-kernel comparison of two builds of some sources (by default the bf16 convolution sources).
 
 For each source both builds are compiled to gfx950 assembly with the resource remarks on stderr:
 
@@ -9,9 +9,13 @@ For each source both builds are compiled to gfx950 assembly with the resource re
 -- comments, directives outside the body and the numbering of local labels dropped -- and, for the kernels that differ,
 prints a table of the resources of both builds side by side (parent / new).
 
-    python compare_kernels.py PARENT_DIR NEW_DIR [NAME ...]
+    python compare_kernels.py [--map MAP.json] PARENT_DIR NEW_DIR [NAME ...]
+
+NAME ...: the sources to compare (without .hip).  MAP.json: {parent symbol: new symbol, or null for a kernel deleted on purpose},
+for kernels whose mangled names changed; a deleted kernel is listed and left out of the comparison.
 
 Exit status 1 if a kernel gained scratch bytes or lost an occupancy step, or if the two builds do not hold the same kernels."""
+import json
 import re
 import sys
 
@@ -42,8 +46,23 @@ def kernels(path):
 
 def short(sym):
     """_ZN3dfl...12convq_kernelILi128ELi1E...EEvNS_5ConvPE -> convq_kernel<128,1,...>"""
-    m = re.search(r'\d+([a-z][a-z_]*_kernel)(?:I((?:L[ib]\d+E)+)E)?', sym)
-    return m.group(1) + ('<%s>' % ','.join(re.findall(r'L[ib](\d+)E', m.group(2))) if m.group(2) else '')
+    m = re.search(r'\d+([a-z][a-z_]*_kernel)(I\S*)?', sym)      # every literal template argument, nested ones included
+    lits = re.findall(r'L[ib](\d+)E', m.group(2) or '')
+    return m.group(1) + ('<%s>' % ','.join(lits) if lits else '')
+
+
+def renamed(table, mapping, body=False):
+    """the parent's table under the new build's symbol names; kernels mapped to null are dropped"""
+    out = {}
+    for k, v in table.items():
+        if k in mapping and mapping[k] is None:
+            continue
+        if body:
+            for old, new in mapping.items():
+                if new is not None:
+                    v = [line.replace(old, new) for line in v]
+        out[mapping.get(k, k)] = v
+    return out
 
 
 def resources(path):
@@ -62,12 +81,18 @@ def resources(path):
 
 
 def main():
-    parent, new = sys.argv[1], sys.argv[2]
-    names = sys.argv[3:] or NAMES
+    argv, mapping = sys.argv[1:], {}
+    if argv[0] == '--map':
+        mapping, argv = json.load(open(argv[1])), argv[2:]
+    parent, new = argv[0], argv[1]
+    names = argv[2:] or NAMES
     bad = False
     for n in names:
         kp, kn = kernels('%s/%s.s' % (parent, n)), kernels('%s/%s.s' % (new, n))
         rp, rn = resources('%s/%s.remarks' % (parent, n)), resources('%s/%s.remarks' % (new, n))
+        for k in sorted(k for k in rp if k in mapping and mapping[k] is None):
+            print('%s: deleted on purpose: %s (%s VGPRs)' % (n, k, rp[k].get('VGPRs')))
+        kp, rp = renamed(kp, mapping, body=True), renamed(rp, mapping)
         glob_p = sorted(k for k in kp if k in rp)
         glob_n = sorted(k for k in kn if k in rn)
         if glob_p != glob_n:

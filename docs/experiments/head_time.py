@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""dfl_head_fwd / dfl_head_bwd alone at the benchmark shape (16 x 192 x 192 pixels, 32 bf16 features, 7 classes, 21 mid, 14 landmarks)."""
+"""dfl_head_fwd / dfl_head_bwd alone at the benchmark shape (16 x 192 x 192 pixels, 32 bf16 features, 7 classes, 21 mid, 14 landmarks).
+DFL_LIB_OVERRIDE=<library> times another build of the library."""
 import os
 import sys
 
@@ -50,5 +51,4 @@ def timed(name, a, reps=20):
     return tot / reps * 1e3
 
 
-print('%s: fwd %.1f us  bwd %.1f us' % (' '.join('%s=%s' % (k, v) for k, v in os.environ.items() if k.startswith('DFL_HEAD')),
-                                         timed('dfl_head_fwd', fa), timed('dfl_head_bwd', ba)))
+print('%s: fwd %.2f us  bwd %.2f us' % (os.environ.get('DFL_LIB_OVERRIDE', 'this tree'), timed('dfl_head_fwd', fa), timed('dfl_head_bwd', ba)))

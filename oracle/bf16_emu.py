@@ -42,7 +42,7 @@ accuracy.  The network is the composition of the steps, so this pins the headlin
 calibrated on the run under test (tests/test_gpu_bf16_stepwise.py).
 
 Only tests/ import this.  Citations: the rounding places are csrc/convp_bf16.hip (staging :344-366, epilogue :569-610),
-csrc/wgradp_bf16.hip (:236-275), csrc/bn_elem.hip (bn_finalize_kernel, bn_bwd_finalize_kernel), csrc/head_mfma.inc.
+csrc/wgradp_bf16.hip (:236-275), csrc/bn_elem.hip (bn_finalize_kernel, bn_bwd_finalize_kernel), csrc/head_mfma.h.
 """
 import torch
 import torch.nn as nn

@@ -659,6 +659,18 @@ def test_head_backward_fused_weight_gradients(NC, L, two, softmax):
     The weight gradients round [dlogits | dmid | dheat] and [logits | mid] to bf16 (x is bf16 already): 2^-9 relative per
     product, averaged over the pixels -- the bar is 2^-8 of the largest gradient magnitude of each tensor, dx keeps the bar
     of a bf16 result."""
+    _head_fused_case(NC, L, two, softmax)
+
+
+@pytest.mark.parametrize('NC,L,two,softmax', [(7, 14, True, 1), (7, 0, True, 1)])
+def test_head_fused_weight_gradients_with_misaligned_w_seg(NC, L, two, softmax):
+    """The same checks with a w_seg that starts 4 bytes into a 16-byte aligned buffer (everything else aligned): the matrix-core
+    kernels load rows of w_seg 16 bytes at a time and refuse it, so the forward pass runs thread-per-pixel on bf16 features and
+    the backward pass in the thread-per-pixel kernel that takes the weight gradients itself, with run-time channel bounds."""
+    _head_fused_case(NC, L, two, softmax, w_seg_offset=1)
+
+
+def _head_fused_case(NC, L, two, softmax, w_seg_offset=0):
     lib = nat.lib()
     g = torch.Generator().manual_seed(NC + L + 1)
     N, H, W, F_ = 3, 37, 29, 32                                     # 3219 pixels: ragged last tile, images that straddle tiles
@@ -682,6 +694,12 @@ def test_head_backward_fused_weight_gradients(NC, L, two, softmax):
     dv = lambda t: t.detach().float().contiguous().to(DEV)
     xd = F.pad(nhwc(x.detach().float()), (0, 8)).to(DEV).to(BF).contiguous()      # pixel stride 40
     wsd, w1d, w2d = dv(wseg), (dv(w1) if w1 is not None else None), (dv(w2) if w2 is not None else None)
+    if w_seg_offset:                                                 # a view that starts w_seg_offset floats into its buffer
+        buf = torch.zeros(wsd.numel() + 4, device=DEV)
+        assert buf.data_ptr() % 16 == 0
+        buf[w_seg_offset:w_seg_offset + wsd.numel()] = wsd.reshape(-1)
+        wsd = buf[w_seg_offset:w_seg_offset + wsd.numel()]
+        assert wsd.data_ptr() % 16 == 4 * w_seg_offset
     seg_out = torch.full((N, NC, H, W), float('nan'), device=DEV)
     heat_out = torch.full((N, L, H, W), float('nan'), device=DEV) if L > 0 else None
     nat.call('dfl_head_fwd', nat.HeadFwdArgs(

@@ -13,7 +13,7 @@ inputs of that step ("teacher forcing").  Then
   Two documented exceptions: tensors written by an ACCUMULATING epilogue (`dxin:` residual 1x1 data gradient on top of the 3x3
   one, `dout:` down-sampling gradient on top of the bridge gradient) were rounded twice, the first value is gone, and a one-ulp
   flip of a large first value that the sum cancels is many ulps of the result: EXCESS_BAR_TWICE; and the matrix-core heads
-  multiply fp32 operands as hi + lo bf16 pairs (2^-17 per product, csrc/head_mfma.inc -- the accuracy of the bf16x3 arithmetic),
+  multiply fp32 operands as hi + lo bf16 pairs (2^-17 per product, csrc/head_mfma.h -- the accuracy of the bf16x3 arithmetic),
   which the emulation does not restate: `dfeat` and the three head weight gradients get HEAD_* bars.
 Nothing is calibrated on the run under test and no bar depends on the arithmetic's own noise:
 a wrong ReLU mask rule, a statistic taken from unrounded values or a 1 % error in one bias gradient fails here.
