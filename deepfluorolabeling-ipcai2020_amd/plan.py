@@ -90,7 +90,7 @@ class UNetPlan:
     DPRE_OUT_BYTES = int(float(os.environ.get('DFL_DPRE_OUT_MB', '12')) * (1 << 20))   # data gradient also writes the operand it forms up to this size
     LIVE_BN = os.environ.get('DFL_LIVE_BN', '1') != '0'           # BatchNorm statistics completed by their consumers (live totals)
     LIVE_HEAD = os.environ.get('DFL_LIVE_HEAD', '1') != '0'       # ... and the head's backward kernel adds the sums of its dx itself (no colstats pass)
-    BN_R = 8                                                      # include/dfl_hip.h: DFL_BN_R
+    BN_R = nat.BN_R
 
     def __init__(self, cfg, params, buffers, N, H, W, training, need_grad, device, input_grad=False):
         """cfg: dict of the UNet constructor flags; params / buffers: name -> tensor (module state)."""

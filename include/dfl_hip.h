@@ -49,7 +49,9 @@ const char* dfl_last_error(void);
  * est_lands, upsample, augment_args, augment_item, overlay, resample_plan, resample_args, fullres, mesh_mc,
  * mesh_decode, mesh_topo, mesh_csr, mesh_smooth, mesh_xform, mesh_normals, preproc_projs, preproc_segs, restore_labels,
  * sim_prepare, sim_gradncc, expose, sim_patch_prepare, sim_patch_gradncc, drr_object, drr_args, optim_pack): lets a
- * binding written in another language verify its struct mirrors at load time.  Returns -1 past the end. */
+ * binding written in another language verify the size of its struct mirrors at load time.  Returns -1 past the end.
+ * Sizes say nothing about field order or type: the Python binding derives its structs, constants and signatures from this
+ * file (dfl_amd/_cabi.py), and tests/test_cabi_cpu.py holds every field offset against a C compiler's offsetof. */
 int dfl_sizeof(int which);
 
 /* ------------------------------------------------------------------------------------------------------------
