@@ -16,11 +16,9 @@
 // A run of voxels of one label adds s (t_end - t_start) to that label at once: the 16-way select that finds the
 // accumulator (no register array is indexed with a run-time value) runs once per run, not once per voxel.
 // mu is loaded only where the label passes the mask.
-#include "common.h"
+#include "drr.h"
 
 namespace dfl {
-
-constexpr int DRR_NL = DFL_DRR_MAX_LABELS;
 
 struct DrrParams {
   const float* mu;
@@ -33,20 +31,6 @@ struct DrrParams {
   int nx, ny, nz, H, W, n_obj, n_labels;
   float step_mm, min_len_mm;
 };
-
-__device__ __forceinline__ float drr_dot(const float* m, float c, float r) { return m[0] * c + m[1] * r + m[2]; }
-
-// t of plane k of one axis: the plane between voxels k - 1 and k
-__device__ __forceinline__ float drr_plane(int k, float o, float d) { return ((float)k - 0.5f - o) / d; }
-
-// Clip [t0, t1] to the slab [lo - 1/2, hi + 1/2] of one axis; false: the ray misses it
-__device__ __forceinline__ bool drr_clip(float o, float d, int lo, int hi, float& t0, float& t1) {
-  if (d == 0.f) return o >= (float)lo - 0.5f && o < (float)hi + 0.5f;
-  const float ta = drr_plane(lo, o, d), tb = drr_plane(hi + 1, o, d);
-  t0 = fmaxf(t0, fminf(ta, tb));
-  t1 = fminf(t1, fmaxf(ta, tb));
-  return true;
-}
 
 // Start of the walk on one axis: k = the first plane crossed after t0, i = the voxel index at t0+, step = +-1 (0: the
 // axis is never crossed, tn = inf).  Planes lo .. hi + 1 bound the voxels lo .. hi; their t are monotonic in k.
@@ -140,14 +124,6 @@ __device__ __forceinline__ float drr_masked(const DrrParams& P, uint32_t mask, i
   const int idx = (z * P.ny + y) * P.nx + x;
   const uint32_t lab = P.labels[idx];
   return lab < (uint32_t)DRR_NL && ((mask >> lab) & 1u) != 0u ? P.mu[idx] : 0.f;
-}
-
-__device__ __forceinline__ void drr_corner(float p, int n, int& i0, int& i1, float& w) {
-  const float q = fminf(fmaxf(p, -2.f), (float)n + 1.f);
-  const float f = floorf(q);
-  w = q - f;
-  i0 = min(max((int)f, 0), n - 1);
-  i1 = min(max((int)f + 1, 0), n - 1);
 }
 
 __device__ __forceinline__ void drr_trilinear_object(const DrrParams& P, const dfl_drr_object& ob, float c, float r, float s, float& att) {

@@ -114,6 +114,100 @@ __global__ __launch_bounds__(64) void sim_finish_kernel(const double* __restrict
 
 inline int sim_bands(int H) { return (int)ceil_div(H - 2, SIM_ROWS); }
 
+// ---- the adjoint: d cost[v] / d moving[v][r][c] (dfl_sim_gradncc_bwd) ----------------------------------------------------------
+// With a the moving and b the fixed Sobel values of one direction, d(-ncc / 2) / d a_p = alpha (b_p - mean b) + beta (a_p - mean a)
+// at a counted pixel, alpha = -1 / (2 sqrt(va vb)), beta = cab / (2 va sqrt(va vb)); both 0 where the forward rule makes the ncc 0.
+constexpr int SIM_COEF = 8;          // per view: alpha, beta, mean a, mean b of x, then of y (float32)
+constexpr int SIM_TILE = 16;         // the adjoint kernel's tile of output pixels; 16 x 16 = SIM_THREADS
+
+// One thread per view: the view's records added in index order (as sim_finish_kernel adds them), the coefficients in float64
+__global__ __launch_bounds__(64) void sim_coef_kernel(const double* __restrict__ scratch, const double* __restrict__ totals,
+                                                      float* __restrict__ coef, int bands, int V) {
+  const int view = blockIdx.x * 64 + threadIdx.x;
+  if (view >= V) return;
+  double m[SIM_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  const double* rec = scratch + (size_t)view * bands * SIM_SUMS;
+  for (int b = 0; b < bands; ++b) {
+#pragma unroll
+    for (int k = 0; k < SIM_SUMS; ++k) m[k] += rec[(size_t)b * SIM_SUMS + k];
+  }
+  const double n = totals[0];
+  const double eps = 9.094947017729282e-13;                             // 2^-40, the rule of sim_ncc
+#pragma unroll
+  for (int dir = 0; dir < 2; ++dir) {
+    const double sa = m[3 * dir], saa = m[3 * dir + 1], sab = m[3 * dir + 2], sb = totals[1 + 2 * dir], sbb = totals[2 + 2 * dir];
+    double alpha = 0.0, beta = 0.0, ma = 0.0, mb = 0.0;
+    if (n >= 1.0) {
+      const double va = saa - sa * sa / n, vb = sbb - sb * sb / n;
+      if (va > eps * saa && vb > eps * sbb) {
+        const double root = sqrt(va * vb);
+        alpha = -0.5 / root;
+        beta = 0.5 * (sab - sa * sb / n) / (va * root);
+        ma = sa / n;
+        mb = sb / n;
+      }
+    }
+    float* out = coef + (size_t)view * SIM_COEF + 4 * dir;
+    out[0] = (float)alpha;
+    out[1] = (float)beta;
+    out[2] = (float)ma;
+    out[3] = (float)mb;
+  }
+}
+
+// A workgroup owns a 16 x 16 tile of one view's d_moving.  The tile of `moving` with a halo of 2 goes to LDS (0 outside the
+// image); from it the 18 x 18 pixels around the tile get g = d cost / d (Sobel value), 0 where the pixel is not counted; every
+// output pixel then gathers the nine pixels whose window holds it with the Sobel weight it has there.
+__global__ __launch_bounds__(SIM_THREADS) void sim_adjoint_kernel(const float* __restrict__ moving, const float* __restrict__ fx,
+                                                                  const float* __restrict__ fy, const unsigned char* __restrict__ counted,
+                                                                  const float* __restrict__ coef, float* __restrict__ d_moving, int H, int W) {
+  // every product is rounded on its own: where moving matches fixed the two terms of g cancel exactly, which an FMA would undo
+#pragma clang fp contract(off)
+  constexpr int IN = SIM_TILE + 4, G = SIM_TILE + 2;
+  __shared__ float sm[IN][IN + 1];
+  __shared__ float sgx[G][G + 1], sgy[G][G + 1];
+  const int view = blockIdx.z;
+  const int r0 = blockIdx.y * SIM_TILE, c0 = blockIdx.x * SIM_TILE;
+  const float* img = moving + (size_t)view * H * W;
+  for (int i = threadIdx.x; i < IN * IN; i += SIM_THREADS) {
+    const int lr = i / IN, lc = i % IN, r = r0 - 2 + lr, c = c0 - 2 + lc;
+    sm[lr][lc] = r >= 0 && r < H && c >= 0 && c < W ? img[(size_t)r * W + c] : 0.f;
+  }
+  const float* cf = coef + (size_t)view * SIM_COEF;
+  const float ax = cf[0], bx = cf[1], max_ = cf[2], mbx = cf[3], ay = cf[4], by = cf[5], may = cf[6], mby = cf[7];
+  __syncthreads();
+  for (int i = threadIdx.x; i < G * G; i += SIM_THREADS) {
+    const int lr = i / G, lc = i % G, r = r0 - 1 + lr, c = c0 - 1 + lc;
+    float gx = 0.f, gy = 0.f;
+    if (r >= 1 && r <= H - 2 && c >= 1 && c <= W - 2) {
+      const size_t at = (size_t)r * W + c;
+      if (counted[at]) {
+        // sim_sobel on the staged tile: pixel (r, c) sits at sm[lr + 1][lc + 1]
+        const float a = sm[lr][lc], b = sm[lr][lc + 1], cc = sm[lr][lc + 2], d = sm[lr + 1][lc], f = sm[lr + 1][lc + 2];
+        const float g = sm[lr + 2][lc], h = sm[lr + 2][lc + 1], k = sm[lr + 2][lc + 2];
+        const float mx = ((cc + 2.f * f) + k) - ((a + 2.f * d) + g);
+        const float my = ((g + 2.f * h) + k) - ((a + 2.f * b) + cc);
+        gx = ax * (fx[at] - mbx) + bx * (mx - max_);
+        gy = ay * (fy[at] - mby) + by * (my - may);
+      }
+    }
+    sgx[lr][lc] = gx;
+    sgy[lr][lc] = gy;
+  }
+  __syncthreads();
+  const int tr = threadIdx.x / SIM_TILE, tc = threadIdx.x % SIM_TILE, r = r0 + tr, c = c0 + tc;
+  if (r < H && c < W) {
+    // pixel q is at offset (dr, dc) in the window of p = q - (dr, dc); p sits at sg[tr + 1 - dr][tc + 1 - dc].
+    // Sobel x has weight dc (2 - |dr|) there, Sobel y dr (2 - |dc|)
+    const float x = ((sgx[tr + 2][tc] + 2.f * sgx[tr + 1][tc]) + sgx[tr][tc]) - ((sgx[tr + 2][tc + 2] + 2.f * sgx[tr + 1][tc + 2]) + sgx[tr][tc + 2]);
+    const float y = ((sgy[tr][tc + 2] + 2.f * sgy[tr][tc + 1]) + sgy[tr][tc]) - ((sgy[tr + 2][tc + 2] + 2.f * sgy[tr + 2][tc + 1]) + sgy[tr + 2][tc]);
+    d_moving[((size_t)view * H + r) * W + c] = x + y;
+  }
+}
+
+// records [V][bands][6], then the coefficients [V][8] float32
+inline int64_t sim_bwd_need(int64_t V, int H) { return V * sim_bands(H) * SIM_SUMS + V * (SIM_COEF / 2); }
+
 }  // namespace dfl
 
 extern "C" int64_t dfl_sim_scratch_doubles(int32_t V, int32_t H, int32_t W) {
@@ -152,4 +246,38 @@ extern "C" int dfl_sim_gradncc(const dfl_sim_gradncc_args* a, dfl_stream_t strea
                                                                                                a->scratch, a->H, a->W);
   dfl::sim_finish_kernel<<<(unsigned)a->V, 64, 0, s>>>(a->scratch, a->totals, a->cost, bands);
   return dfl::check_launch("dfl_sim_gradncc");
+}
+
+extern "C" int dfl_sim_gradncc_bwd_scratch_doubles(int32_t V, int32_t H, int32_t W) {
+  if (V < 1 || V > 65535 || H < 3 || W < 3 || (int64_t)H * W >= ((int64_t)1 << 31) || dfl::sim_bwd_need(V, H) >= ((int64_t)1 << 31)) {
+    dfl::set_error("dfl_sim_gradncc_bwd_scratch_doubles: bad sizes (views %d of 1..65535, image %d x %d of at least 3 x 3), or more than "
+                   "2^31 - 1 doubles", V, H, W);
+    return DFL_ERR_INVALID_ARG;
+  }
+  return (int)dfl::sim_bwd_need(V, H);
+}
+
+extern "C" int dfl_sim_gradncc_bwd(const dfl_sim_gradncc_bwd_args* a, dfl_stream_t stream) {
+  DFL_REQUIRE(a != nullptr, "dfl_sim_gradncc_bwd: null args");
+  DFL_REQUIRE(a->moving != nullptr && a->fx != nullptr && a->fy != nullptr && a->counted != nullptr && a->totals != nullptr &&
+                  a->scratch != nullptr && a->cost != nullptr && a->d_moving != nullptr,
+              "dfl_sim_gradncc_bwd: moving, fx, fy, counted, totals, scratch, cost and d_moving are required");
+  DFL_REQUIRE(a->H >= 3 && a->W >= 3, "dfl_sim_gradncc_bwd: an image of %d x %d (at least 3 x 3)", a->H, a->W);
+  DFL_REQUIRE((int64_t)a->H * a->W < ((int64_t)1 << 31), "dfl_sim_gradncc_bwd: an image of %d x %d is too large", a->H, a->W);
+  DFL_REQUIRE(a->V >= 1 && a->V <= 65535, "dfl_sim_gradncc_bwd: 1..65535 views per call, got %d", a->V);
+  const int bands = dfl::sim_bands(a->H);
+  const int64_t need = dfl::sim_bwd_need(a->V, a->H);
+  DFL_REQUIRE(a->scratch_doubles >= need, "dfl_sim_gradncc_bwd: a scratch of %lld doubles, %lld are needed (dfl_sim_gradncc_bwd_scratch_doubles)",
+              (long long)a->scratch_doubles, (long long)need);
+  DFL_REQUIRE(dfl::ceil_div(a->H, dfl::SIM_TILE) <= 65535, "dfl_sim_gradncc_bwd: an image of %d rows is too tall", a->H);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  float* coef = reinterpret_cast<float*>(a->scratch + (size_t)a->V * bands * dfl::SIM_SUMS);
+  // the forward's own two kernels: the cost has the forward's bits
+  dfl::sim_gradncc_kernel<<<dim3((unsigned)bands, (unsigned)a->V), dfl::SIM_THREADS, 0, s>>>(a->moving, a->fx, a->fy, a->counted,
+                                                                                               a->scratch, a->H, a->W);
+  dfl::sim_finish_kernel<<<(unsigned)a->V, 64, 0, s>>>(a->scratch, a->totals, a->cost, bands);
+  dfl::sim_coef_kernel<<<(unsigned)dfl::ceil_div(a->V, 64), 64, 0, s>>>(a->scratch, a->totals, coef, bands, a->V);
+  const dim3 grid((unsigned)dfl::ceil_div(a->W, dfl::SIM_TILE), (unsigned)dfl::ceil_div(a->H, dfl::SIM_TILE), (unsigned)a->V);
+  dfl::sim_adjoint_kernel<<<grid, dfl::SIM_THREADS, 0, s>>>(a->moving, a->fx, a->fy, a->counted, coef, a->d_moving, a->H, a->W);
+  return dfl::check_launch("dfl_sim_gradncc_bwd");
 }

@@ -37,7 +37,7 @@ from . import fullres, preprocess
 from .fullres import POSES
 
 __all__ = ['Obj', 'Grid', 'Geometry', 'Volume', 'geometry', 'read_volume', 'training_grid', 'default_objects', 'pack', 'pack_objects',
-           'render', 'render_args', 'args_for_records', 'project', 'project_points', 'hu_to_mu', 'label_mask', 'POSES', 'DEFAULT_MASKS']
+           'render', 'render_args', 'args_for_records', 'pose_gradient', 'box_pivots', 'project', 'project_points', 'hu_to_mu', 'label_mask', 'POSES', 'DEFAULT_MASKS']
 
 # labels of the 3D annotation: 1, 2 hemipelves, 3 vertebrae, 4 sacrum, 5, 6 femurs
 DEFAULT_MASKS = ((1, 2, 3, 4), (5,), (6,))
@@ -288,6 +288,55 @@ def args_for_records(volume, recs, grid, interp='exact', step_mm=0.5, want_plen=
                     nx=nx, ny=ny, nz=nz, H=H, W=W, views=V, n_obj=n_obj, n_labels=NL, interp=_INTERP[interp],
                     mapping=int(mapping), step_mm=float(step_mm), min_len_mm=float(min_len_mm))
     return a, (att, plen, lab), [d_objs, volume]
+
+
+def box_pivots(recs):
+    """float32 [..., 3]: the middle of every record's box in index coordinates (0 for an empty box): the default pivots
+    of pose_gradient."""
+    lo, hi = recs['box_lo'].astype(np.float64), recs['box_hi'].astype(np.float64)
+    return np.where((hi < lo).any(-1, keepdims=True), 0.0, (lo + hi) / 2).astype(np.float32)
+
+
+def pose_gradient(volume, recs, grid, d_att, pivots=None, step_mm=0.5):
+    """The force F and moment Mom that the detector-space adjoint d_att [V, H, W] (float32, on the GPU) exerts on every
+    object of the trilinear DRR of the packed records recs [V, n_obj] (pack(..., interp='trilinear')), with the
+    renderer's sampling frozen (dfl_drr_pose_grad): float64 [V, n_obj, 12] on the device, F[3] then
+    Mom[3][3] row-major about pivots [V, n_obj, 3] (index coordinates; default: box_pivots(recs)).  For a motion
+    x -> x + eps (L (x - pivot) + tau) of an object, d (sum d_att att) / d eps = <Mom, L> + F . tau."""
+    if not isinstance(volume, Volume):
+        raise nat.DflError('drr.pose_gradient needs a drr.Volume (device tensors; no CPU path)')
+    recs = np.asarray(recs)
+    if recs.dtype != OBJECT_DTYPE or recs.ndim != 2 or recs.shape[0] < 1 or recs.shape[1] < 1:
+        raise nat.DflError('drr.pose_gradient: records [views, n_obj] of drr.OBJECT_DTYPE expected (drr.pack)')
+    if not float(step_mm) > 0:
+        raise nat.DflError('drr.pose_gradient: step_mm must be positive, got %r' % (step_mm,))
+    V, n_obj = recs.shape
+    dev, H, W = volume.mu.device, grid.H, grid.W
+    if not torch.is_tensor(d_att) or not d_att.is_cuda:
+        raise nat.DflError('drr.pose_gradient needs d_att on the GPU (no CPU path)')
+    if d_att.dtype != torch.float32 or tuple(d_att.shape) != (V, H, W) or d_att.device != dev:
+        raise nat.DflError('drr.pose_gradient: d_att has shape %s and dtype %s on %s: float32 %s on %s expected'
+                           % (tuple(d_att.shape), d_att.dtype, d_att.device, (V, H, W), dev))
+    piv = box_pivots(recs) if pivots is None else np.asarray(pivots, np.float32)
+    if piv.shape != (V, n_obj, 3) or not np.isfinite(piv).all():
+        raise nat.DflError('drr.pose_gradient: pivots of shape %s: finite [%d, %d, 3] expected' % (piv.shape, V, n_obj))
+    lib = nat.lib()
+    need = int(lib.dfl_drr_pose_grad_scratch_doubles(V, n_obj, H, W))
+    if need < 0:
+        raise nat.DflError('drr.pose_gradient: %s' % lib.dfl_last_error().decode())
+    nz, ny, nx = volume.shape
+    d_att = d_att.detach().contiguous()
+    d_objs = torch.from_numpy(np.ascontiguousarray(recs).view(np.uint8).reshape(-1)).to(dev)
+    d_piv = torch.from_numpy(np.ascontiguousarray(piv)).to(dev)
+    grad = torch.empty((V, n_obj, 12), dtype=torch.float64, device=dev)
+    scratch = torch.empty(need, dtype=torch.float64, device=dev)
+    a = nat.DrrPoseGradArgs(mu=volume.mu.data_ptr(), labels=volume.labels.data_ptr(), objects=d_objs.data_ptr(), d_att=d_att.data_ptr(),
+                            pivots=d_piv.data_ptr(), grad=grad.data_ptr(), scratch=scratch.data_ptr(), scratch_doubles=need,
+                            qscale=(nat.f32 * 9)(*grid.Q.astype(np.float32).reshape(-1)), nx=nx, ny=ny, nz=nz, H=H, W=W, views=V,
+                            n_obj=n_obj, interp=nat.DRR_TRILINEAR, step_mm=float(step_mm))
+    with torch.cuda.device(dev):
+        nat.call('dfl_drr_pose_grad', a, torch.cuda.current_stream(dev).cuda_stream)
+    return grad                                                   # stream order keeps the uploads alive until the kernels ran
 
 
 def render_args(volume, objects, grid, interp='exact', step_mm=0.5, want_plen=False, want_labels=True, min_len_mm=1.0,

@@ -8,7 +8,10 @@ optimiser is one dfl_drr_render launch (trilinear, tight boxes, lambda views), o
 (csrc/sim.hip) and one copy of lambda doubles to the host; the records and the argument block of the render are
 drr.pack and drr.args_for_records.  DESIGN.md section 16 states the semantics of the similarity; tests/reg_ref.py
 restates them in numpy float64.  The patch cost (dfl_sim_patch_gradncc, csrc/sim_patch.hip) and the landmark term are
-section 18 and tests/patch_ref.py.
+section 18 and tests/patch_ref.py.  register(refine=K) finishes with a dense BFGS (bfgs) on the gradient of the cost with
+respect to the six parameters: one render, the adjoint of the similarity (dfl_sim_gradncc_bwd) and the forces and moments
+it exerts on every object (dfl_drr_pose_grad, sampling frozen), chained to theta through pose_delta_jacobians; section 19
+and tests/grad_ref.py.
 
     D(theta) = [[R, centre - R centre + theta[3:]], [0, 1]],  R = exp(rot_unit theta[:3])      (pose_delta)
     P(theta) = D(theta) P0                                   a cam-to-*-vol matrix as in gt-poses
@@ -23,8 +26,8 @@ import torch
 from . import _native as nat
 from . import drr, preprocess
 
-__all__ = ['se3_exp', 'se3_log', 'pose_delta', 'pose_deltas', 'pnp', 'cma_es', 'CmaResult', 'Similarity', 'PatchSimilarity',
-           'landmark_penalty', 'register', 'Registration', 'with_pelvis_pose', 'volume_centre']
+__all__ = ['se3_exp', 'se3_log', 'pose_delta', 'pose_deltas', 'pose_delta_jacobians', 'pnp', 'cma_es', 'CmaResult', 'bfgs', 'BfgsResult',
+           'Similarity', 'PatchSimilarity', 'landmark_penalty', 'register', 'Registration', 'with_pelvis_pose', 'volume_centre']
 
 ROT_UNIT = 0.02
 
@@ -95,6 +98,29 @@ def pose_delta(theta, centre, rot_unit=ROT_UNIT):
     """Six parameters -> the 4 x 4 D: the rotation exp(theta[:3] rot_unit) (rotation vector, radians) about `centre` in
     the volume's physical frame, followed by the translation theta[3:] in mm."""
     return pose_deltas(np.asarray(theta, np.float64).reshape(1, 6), centre, rot_unit)[0]
+
+
+def pose_delta_jacobians(thetas, centre, rot_unit=ROT_UNIT):
+    """[n, 6] -> [n, 6, 4, 4] float64: d pose_delta(theta) / d theta_i, analytic.  With w = rot_unit theta[:3] and
+    R = exp(hat w), d R / d w_i = hat(w_i w + w x (I - R) e_i) R / |w|^2 (Gallego and Yezzi 2015), below |w| = 1e-4 the
+    series of the exponential to third order; a translation parameter moves the translation column alone."""
+    th = np.asarray(thetas, np.float64).reshape(-1, 6)
+    ctr = np.asarray(centre, np.float64).reshape(3)
+    R = pose_deltas(th, ctr, rot_unit)[:, :3, :3]
+    out = np.zeros((th.shape[0], 6, 4, 4))
+    for k in range(th.shape[0]):
+        w = th[k, :3] * float(rot_unit)
+        t2, W = float(w @ w), _hat(w)
+        for i in range(3):
+            E = _hat(np.eye(3)[i])
+            if t2 < 1e-8:
+                dR = E + (E @ W + W @ E) / 2.0 + (E @ W @ W + W @ E @ W + W @ W @ E) / 6.0
+            else:
+                dR = _hat(w[i] * w + np.cross(w, (np.eye(3) - R[k])[:, i])) @ R[k] / t2
+            out[k, i, :3, :3] = float(rot_unit) * dR
+            out[k, i, :3, 3] = -float(rot_unit) * (dR @ ctr)
+            out[k, 3 + i, i, 3] = 1.0
+    return out
 
 
 def volume_centre(volume_shape, I2P):
@@ -257,6 +283,62 @@ def cma_es(cost_fn, x0, sigma0, popsize=None, generations=100, seed=0):
     return CmaResult(mean, best_x, best_f, np.array(trace), lam * int(generations), sigma)
 
 
+class BfgsResult:
+    """x, f: the last accepted point and its cost; trace: the accepted costs, the start's first (never increasing);
+    evaluations: calls of the cost-and-gradient function; iterations: steps accepted."""
+
+    def __init__(self, x, f, trace, evaluations, iterations):
+        self.x, self.f, self.trace, self.evaluations, self.iterations = x, f, trace, evaluations, iterations
+
+
+def bfgs(fun, x0, iterations=30, tol=1e-4, c1=1e-4, min_step=1e-6):
+    """A dense BFGS with Armijo backtracking (halving): the local finish of register().  fun takes [n] and returns
+    (cost, gradient [n]).  The inverse-Hessian estimate starts as the identity and returns to it when its direction is
+    not a descent direction; from the identity the first trial step is min(1, 1 / |g|), else 1.  A trial whose cost is
+    not finite or fails f <= f0 + c1 t g.p is rejected, so the accepted costs never increase.  It stops after
+    `iterations` accepted steps, when an accepted step is shorter than tol, or when the trial step |t p| falls below min_step."""
+    x = np.asarray(x0, np.float64).reshape(-1).copy()
+    n = x.size
+    f, g = fun(x)
+    f, g = float(f), np.asarray(g, np.float64).reshape(n)
+    if not np.isfinite(f) or not np.isfinite(g).all():
+        raise nat.DflError('register.bfgs: the cost or its gradient is not finite at the start (%r)' % f)
+    Hm, fresh = np.eye(n), True
+    trace, evals, done = [f], 1, 0
+    while done < int(iterations):
+        p = -Hm @ g
+        if not g @ p < 0.0:
+            Hm, fresh, p = np.eye(n), True, -g
+        slope = float(g @ p)
+        if not slope < 0.0:                                        # a zero gradient
+            break
+        t = min(1.0, 1.0 / float(np.linalg.norm(g))) if fresh else 1.0
+        accepted = None
+        while t * float(np.linalg.norm(p)) >= min_step:
+            xn = x + t * p
+            fn, gn = fun(xn)
+            fn, gn = float(fn), np.asarray(gn, np.float64).reshape(n)
+            evals += 1
+            if np.isfinite(fn) and np.isfinite(gn).all() and fn <= f + c1 * t * slope:
+                accepted = (xn, fn, gn)
+                break
+            t *= 0.5
+        if accepted is None:
+            break
+        xn, fn, gn = accepted
+        s, y = xn - x, gn - g
+        sy = float(s @ y)
+        if sy > 1e-12 * float(np.linalg.norm(s) * np.linalg.norm(y)):
+            A = np.eye(n) - np.outer(s, y) / sy
+            Hm, fresh = A @ Hm @ A.T + np.outer(s, s) / sy, False
+        x, f, g = xn, fn, gn
+        trace.append(f)
+        done += 1
+        if float(np.linalg.norm(s)) < tol:
+            break
+    return BfgsResult(x, f, np.array(trace), evals, done)
+
+
 # ---- the similarity on the device --------------------------------------------------------------------------------------
 def _device_image(t, what, dims, dtypes=(torch.float32,)):
     if not torch.is_tensor(t) or not t.is_cuda:
@@ -314,6 +396,29 @@ class Similarity:
             nat.call('dfl_sim_gradncc', self.args(mv, out), torch.cuda.current_stream(mv.device).cuda_stream)
         return out
 
+    def cost_and_adjoint(self, moving):
+        """(cost [V] float64, d_moving [V, H, W] float32 = d cost[v] / d moving[v]) on the device: one dfl_sim_gradncc_bwd
+        launch.  The cost has the bits cost(moving) gives."""
+        mv = _device_image(moving, 'the moving images', 3)
+        if tuple(mv.shape[1:]) != (self.H, self.W) or mv.device != self.fixed.device or not 1 <= mv.shape[0] <= self.views:
+            raise nat.DflError('register: moving images of shape %s on %s for a fixed image of %d x %d on %s and at most %d views'
+                               % (tuple(mv.shape), mv.device, self.H, self.W, self.fixed.device, self.views))
+        V, dev = int(mv.shape[0]), mv.device
+        if getattr(self, 'bwd_scratch', None) is None:
+            lib = nat.lib()
+            need = int(lib.dfl_sim_gradncc_bwd_scratch_doubles(self.views, self.H, self.W))
+            if need < 0:
+                raise nat.DflError('register: %s' % lib.dfl_last_error().decode())
+            self.bwd_scratch = torch.empty(need, dtype=torch.float64, device=dev)
+        out = torch.empty(V, dtype=torch.float64, device=dev)
+        d_moving = torch.empty((V, self.H, self.W), dtype=torch.float32, device=dev)
+        a = nat.SimGradnccBwdArgs(moving=mv.data_ptr(), fx=self.fx.data_ptr(), fy=self.fy.data_ptr(), counted=self.counted.data_ptr(),
+                                  totals=self.totals.data_ptr(), scratch=self.bwd_scratch.data_ptr(), cost=out.data_ptr(),
+                                  d_moving=d_moving.data_ptr(), scratch_doubles=self.bwd_scratch.numel(), V=V, H=self.H, W=self.W)
+        with torch.cuda.device(dev):
+            nat.call('dfl_sim_gradncc_bwd', a, torch.cuda.current_stream(dev).cuda_stream)
+        return out, d_moving
+
 
 def _patch_params(radius, stride, min_count):
     """(rho, stride, min_count) as integers; min_count=None is half a patch, rounded up."""
@@ -370,6 +475,9 @@ class PatchSimilarity(Similarity):
             nat.call('dfl_sim_patch_gradncc', self.args(mv, out), torch.cuda.current_stream(mv.device).cuda_stream)
         return out
 
+    def cost_and_adjoint(self, moving):
+        raise nat.DflError('register: the patch similarity has no adjoint kernel yet (DESIGN.md section 19 names it as next)')
+
 
 # ---- the landmark term -------------------------------------------------------------------------------------------------
 def _usable_landmarks(X3d, x2d, who):
@@ -407,7 +515,9 @@ class Registration:
     """pose: D(theta) P0 of the first moving object (a cam-to-*-vol matrix); poses: the same for every moving object;
     theta; delta = D(theta); cost: the best cost of every generation (all levels, in order); final_cost: the cost at
     theta = similarity_cost + landmark_cost (0 without the landmark term); renders: views rendered; levels: [(factor,
-    generations, H, W)]."""
+    generations, H, W)]; theta_cma: the CMA-ES mean the
+    refinement started from (theta itself without one); refine_cost: the costs bfgs accepted, the start's first;
+    gradient_evaluations: cost-and-gradient evaluations (each renders one view and is counted in renders)."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -435,10 +545,31 @@ class _Level:
             nat.call(self.entry, self.sim.args(att), stream)
         return self.sim.out[:V].cpu().numpy()                       # the copy waits for both launches: `keep` lives until then
 
+    def costs_and_grads(self, c2is, masks, xis, moving):
+        """[views <= lambda, n_obj, 4, 4], xis [views, 6, 4, 4] (the motion of the moving objects in index coordinates per
+        unit of every parameter) -> (float64 [views], float64 [views, 6]) on the host: one render, one dfl_sim_gradncc_bwd,
+        one dfl_drr_pose_grad, one copy; the chain from forces and moments to the parameters is float64 numpy."""
+        recs = drr.pack(self.volume, c2is, masks, self.grid, 'trilinear', True)
+        a, (att, _, _), keep = drr.args_for_records(self.volume, recs, self.grid, 'trilinear', self.step_mm)
+        V, dev = recs.shape[0], att.device
+        with torch.cuda.device(dev):
+            nat.call('dfl_drr_render', a, torch.cuda.current_stream(dev).cuda_stream)
+        cost, d_att = self.sim.cost_and_adjoint(att)
+        piv = drr.box_pivots(recs)
+        grad = drr.pose_gradient(self.volume, recs, self.grid, d_att, piv, self.step_mm)
+        both = torch.cat([cost[:, None], grad.reshape(V, -1)], 1).cpu().numpy()     # the copy waits for every launch
+        del keep
+        g = both[:, 1:].reshape(V, -1, 12)
+        F, Mom = g[:, moving, :3], g[:, moving, 3:].reshape(V, len(moving), 3, 3)   # [V, m, 3], [V, m, 3, 3]
+        L, tau = xis[:, :, None, :3, :3], xis[:, :, None, :3, 3]                    # [V, 6, 1, 3, 3], [V, 6, 1, 3]
+        lever = (L @ piv[:, None, moving, :, None].astype(np.float64))[..., 0] + tau  # [V, 6, m, 3]
+        return both[:, 0], ((Mom[:, None] * L).sum((-1, -2)) + (F[:, None] * lever).sum(-1)).sum(-1)
+
 
 def register(volume, geom, fixed, moving=(0, 1, 2), theta0=None, P0=None, levels=None, popsize=16, generations=80, sigma0=2.0,
              step_mm=1.0, mask=None, seed=0, centre=None, rot_unit=ROT_UNIT, crop=0, rot180=False, sigma_shrink=0.5,
-             similarity='global', patch_radius=7, patch_stride=4, patch_min_count=None, landmarks=None, landmark_weight=0.0):
+             similarity='global', patch_radius=7, patch_stride=4, patch_min_count=None, landmarks=None, landmark_weight=0.0,
+             refine=0, refine_tol=1e-4):
     """Find theta such that the DRR of `volume` under P = D(theta) P0 matches `fixed`.
 
     moving selects the objects of geom.objects that share the pose under optimisation; the others are rendered at their
@@ -456,7 +587,17 @@ def register(volume, geom, fixed, moving=(0, 1, 2), theta0=None, P0=None, levels
     radius patch_radius every patch_stride pixels with at least patch_min_count counted pixels (PatchSimilarity; with
     levels the same numbers apply on every level's own grid).  landmarks=(X3d [L, 3], x2d [2, L]) with landmark_weight w
     adds landmark_penalty of the pelvis pose D(theta) P_pelvis to every cost (object 0 must move; not with levels).
+
+    refine=K > 0 finishes with at most K iterations of bfgs() from the CMA-ES mean, on the last level's grid, with the
+    gradient of the frozen-sampling renderer and the adjoint of the global similarity (the landmark
+    term joins with central differences of its host function); refine_tol is the step length that ends it.  The result
+    never costs more than the CMA-ES mean (Registration.theta_cma).  generations=0 with refine=K refines theta0 alone.
+    similarity='patch' has no adjoint yet and is refused together with refine.
     """
+    if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or refine < 0 or not float(refine_tol) >= 0.0:
+        raise nat.DflError('register: refine = %r (an integer, at least 0) and refine_tol = %r (not negative)' % (refine, refine_tol))
+    if refine > 0 and similarity == 'patch':
+        raise nat.DflError("register: refine needs the adjoint of the similarity, which similarity='patch' does not have yet")
     if similarity not in ('global', 'patch'):
         raise nat.DflError("register: similarity = %r ('global' or 'patch')" % (similarity,))
     patch = _patch_params(patch_radius, patch_stride, patch_min_count) if similarity == 'patch' else None
@@ -537,6 +678,22 @@ def register(volume, geom, fixed, moving=(0, 1, 2), theta0=None, P0=None, levels
         trace.extend(res.trace.tolist())
         renders += res.evaluations
         done.append((factor, gens, grid.H, grid.W))
+    theta_cma, refine_cost, gradient_evaluations = mean, np.zeros(0), 0
+    if refine > 0:
+        def cost_and_grad(theta):
+            th = theta[None]
+            xis = back[None, None] @ pose_delta_jacobians(th, ctr, rot_unit) @ (np.linalg.inv(pose_deltas(th, ctr, rot_unit)) @ I2P[None])[:, None]
+            c, g = level.costs_and_grads(c2is_of(th), masks, xis, list(moving))
+            c, g = float(c[0]), g[0]
+            if penalty is not None:                                 # float64 on the host and cheap: central differences
+                h = 1e-5
+                c += float(penalty(th)[0])
+                g = g + (penalty(th + h * np.eye(6)) - penalty(th - h * np.eye(6))) / (2 * h)
+            return c, g
+
+        fin = bfgs(cost_and_grad, mean, int(refine), float(refine_tol))
+        mean, refine_cost, gradient_evaluations = fin.x, fin.trace, fin.evaluations
+        renders += fin.evaluations
     similarity_cost = float(level.costs(c2is_of(mean[None]), masks)[0])
     landmark_cost = 0.0 if penalty is None else float(penalty(mean[None])[0])
     final_cost = similarity_cost if penalty is None else similarity_cost + landmark_cost
@@ -544,4 +701,5 @@ def register(volume, geom, fixed, moving=(0, 1, 2), theta0=None, P0=None, levels
     D = pose_delta(mean, ctr, rot_unit)
     poses = [D @ I2P @ base[m] @ geom.E for m in moving]                    # P = I2P C2I E
     return Registration(pose=poses[0], poses=poses, theta=mean, delta=D, cost=np.array(trace), final_cost=final_cost,
-                        similarity_cost=similarity_cost, landmark_cost=landmark_cost, renders=renders, levels=done, centre=ctr)
+                        similarity_cost=similarity_cost, landmark_cost=landmark_cost, renders=renders, levels=done, centre=ctr,
+                        theta_cma=theta_cma, refine_cost=refine_cost, gradient_evaluations=gradient_evaluations)

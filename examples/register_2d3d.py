@@ -8,6 +8,7 @@ same --crop and --ds-factor.
     python examples/register_2d3d.py full_res.h5 17-1882 0 --gt-lands --femurs
     python examples/register_2d3d.py full_res.h5 17-1882 0 --offset 2,-1.5,2.5,4,-3,15 --seed 1 --out run1
     python examples/register_2d3d.py full_res.h5 17-1882 0 --lands-csv lands.csv --similarity patch --landmark-weight 0.01
+    python examples/register_2d3d.py full_res.h5 17-1882 0 --offset 2,-1.5,2.5,4,-3,15 --generations 25 --refine 30
 
 The start pose comes from exactly one of
   --lands-csv FILE   2D landmarks as est_lands_csv.py writes them (pat,proj,land,row,col,time on this grid; land indexes
@@ -19,6 +20,8 @@ The start pose comes from exactly one of
 patches of radius --patch-radius (7) every --patch-stride (4) pixels, which is less sensitive to what the CT does not hold.
 --landmark-weight W (per square pixel, default 0) adds W times the mean squared distance between the projected 3D
 landmarks and the 2D landmarks that gave the start to the pelvis cost; it needs a landmark start, not --offset.
+--refine K (default 0) finishes every registration with at most K quasi-Newton iterations on the pose gradient of the
+renderer (dfl_drr_pose_grad, dfl_sim_gradncc_bwd; global similarity only) and prints the cost before and after them.
 With a landmark start all bones begin at the pelvis pose (the anatomy as it was scanned).  The pelvis is registered with
 every bone following it; --femurs then registers each femur on its own with the others held.
 PREFIX_reg.npz holds start_poses and poses ([3, 4, 4] cam-to-{pelvis, left-femur, right-femur}-vol), cost (the best cost
@@ -43,7 +46,7 @@ from full_res_drr import parse_options, to_u8  # noqa: E402
 
 USAGE = ('Usage: {} <HDF5 full-res data file> <specimen ID> <projection index> (--lands-csv FILE | --gt-lands | --offset '
          'rx,ry,rz,tx,ty,tz) [--femurs] [--out PREFIX] [--crop 50] [--ds-factor 8] [--popsize 16] [--generations 80] [--sigma 2.0] '
-         '[--step 1.0] [--seed 0] [--similarity global|patch] [--patch-radius 7] [--patch-stride 4] [--landmark-weight 0]')
+         '[--step 1.0] [--refine 0] [--seed 0] [--similarity global|patch] [--patch-radius 7] [--patch-stride 4] [--landmark-weight 0]')
 
 
 def _six(text):
@@ -92,6 +95,23 @@ def parse_similarity(argv):
     return rest, opts
 
 
+def parse_refine(argv):
+    """(the command line without --refine K, K), K = 0 when it was not given; None when it has no or a bad value."""
+    rest, refine = [], 0
+    it = iter(argv)
+    for a in it:
+        if a != '--refine':
+            rest.append(a)
+            continue
+        try:
+            refine = int(next(it))
+        except (StopIteration, ValueError):
+            return None
+        if refine < 0:
+            return None
+    return rest, refine
+
+
 def read_lands_csv(path, proj, n_lands):
     """[2, n_lands] (column, row), NaN where the landmark was not found or is not listed for projection `proj`."""
     out = np.full((2, n_lands), np.nan)
@@ -133,9 +153,11 @@ def pose_errors(P, P_gt, centre):
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
-    cost = parse_similarity(argv)
+    fine = parse_refine(argv)
+    cost = None if fine is None else parse_similarity(fine[0])
     parsed = None if cost is None else parse(cost[0])
-    if parsed is None or (cost[1]['--landmark-weight'] is not None and parsed[1]['--offset'] is not None):
+    if parsed is None or (cost[1]['--landmark-weight'] is not None and parsed[1]['--offset'] is not None) or \
+            (fine[1] > 0 and cost[1]['--similarity'] == 'patch'):
         print(USAGE.format(os.path.basename(sys.argv[0])))
         return 1
     (path, spec, idx), o = parsed
@@ -164,7 +186,13 @@ def main(argv=None):
         centre = reg.volume_centre(vol.shape, geom.I2P)
         back, Ei = np.linalg.inv(geom.I2P), np.linalg.inv(geom.E)
         kw = dict(popsize=o['--popsize'], generations=o['--generations'], sigma0=o['--sigma'], step_mm=o['--step'], seed=o['--seed'],
-                  similarity=so['--similarity'], patch_radius=so['--patch-radius'], patch_stride=so['--patch-stride'])
+                  similarity=so['--similarity'], patch_radius=so['--patch-radius'], patch_stride=so['--patch-stride'], refine=fine[1])
+
+        def refined(what, r):
+            if len(r.refine_cost):
+                print('{}: refinement cost {:.6f} -> {:.6f} in {} gradient evaluations'.format(what, r.refine_cost[0], r.refine_cost[-1],
+                                                                                                r.gradient_evaluations))
+
         if o['--offset'] is not None:
             Dm = reg.pose_delta(o['--offset'], centre)
             start = [Dm @ geom.poses[k] for k in drr.POSES]
@@ -185,6 +213,7 @@ def main(argv=None):
                                landmark_weight=so['--landmark-weight'] or 0.0, **kw)
         poses, trace, renders = list(res.poses), [res.cost], res.renders
         print('pelvis: cost {:.6f} -> {:.6f} in {} renders'.format(res.cost[0], res.final_cost, res.renders))
+        refined('pelvis', res)
         if res.landmark_cost:
             print('pelvis: similarity {:.6f}, landmark term {:.6f}'.format(res.similarity_cost, res.landmark_cost))
         if o['--femurs']:
@@ -196,6 +225,7 @@ def main(argv=None):
                 trace.append(r.cost)
                 renders += r.renders
                 print('{}: cost {:.6f} -> {:.6f} in {} renders'.format(drr.POSES[n], r.cost[0], r.final_cost, r.renders))
+                refined(drr.POSES[n], r)
 
         def view(ps):
             return drr.render(vol, [drr.Obj(back @ P @ Ei, ob.mask) for P, ob in zip(ps, geom.objects)], geom.grid,

@@ -48,7 +48,8 @@ const char* dfl_last_error(void);
  * bn_bwd_finalize, bn_relu_bwd, affine_copy, pool, head_fwd, head_bwd, loss, ensemble, op, reduce_job, prep,
  * est_lands, upsample, augment_args, augment_item, overlay, resample_plan, resample_args, fullres, mesh_mc,
  * mesh_decode, mesh_topo, mesh_csr, mesh_smooth, mesh_xform, mesh_normals, preproc_projs, preproc_segs, restore_labels,
- * sim_prepare, sim_gradncc, expose, sim_patch_prepare, sim_patch_gradncc, drr_object, drr_args, optim_pack): lets a
+ * sim_prepare, sim_gradncc, expose, sim_patch_prepare, sim_patch_gradncc, sim_gradncc_bwd, drr_pose_grad, drr_object,
+ * drr_args, optim_pack): lets a
  * binding written in another language verify the size of its struct mirrors at load time.  Returns -1 past the end.
  * Sizes say nothing about field order or type: the Python binding derives its structs, constants and signatures from this
  * file (dfl_amd/_cabi.py), and tests/test_cabi_cpu.py holds every field offset against a C compiler's offsetof. */
@@ -1029,6 +1030,45 @@ typedef struct {
 } dfl_drr_args;
 int dfl_drr_render(const dfl_drr_args* a, dfl_stream_t stream);
 
+/* The pose gradient of the trilinear DRR with its sampling frozen (csrc/drr_grad.hip; DESIGN.md section 19 states the
+ * semantics, tests/grad_ref.py restates them in numpy).
+ *
+ * Take the samples x_k = o + t_k d of DFL_DRR_TRILINEAR exactly as dfl_drr_render places them for the same records,
+ * qscale and step_mm (the same clip, N and t_k, the same clamped corners and masked corner values) and the ray weight
+ * w = s (t1 - t0) / N.  grad f(x_k) is the gradient of the trilinear interpolant in the cell of that sample: per axis the
+ * bilinear blend of the four corner differences along it; corners that were clamped together give 0.  For an
+ * infinitesimal motion of object n in index coordinates, x -> x + eps (L (x - pivot_n) + tau),
+ *   d (sum_rays d_att att) / d eps = <Mom, L> + F . tau,
+ *   F[a]      = sum_rays d_att[v][r][c] w sum_k grad f_a(x_k),
+ *   Mom[a][b] = sum_rays d_att[v][r][c] w sum_k grad f_a(x_k) (x_k - pivot_n)_b,
+ * and grad[v][n] = F[0..2], then Mom row-major.  The moments are taken about the pivot inside the kernel: the raw
+ * derivatives with respect to (o, M) carry t of about the source distance and cancel in the chain rule.
+ * What the frozen sampling leaves out is the dependence of N, t0 and t1 on the pose.
+ *
+ * One thread per ray and view (8 x 8 pixels per wave), twelve float32 sums per ray and object, float64 across rays: wave
+ * shuffles, LDS across the four waves, one record of twelve doubles per workgroup and object, added in index order by a
+ * second kernel.  No atomics: a view's numbers have the same bits whatever else is in the batch.  Empty objects and rays
+ * that miss give zeros.  scratch holds at least dfl_drr_pose_grad_scratch_doubles(views, n_obj, H, W) doubles
+ * (negative: bad sizes, or more than 2^31 - 1).  Refused with nothing launched: NULL pointers, sizes that dfl_drr_render
+ * refuses, interp other than DFL_DRR_TRILINEAR, a step_mm that is not positive, a short scratch.
+ * The fields are those of dfl_drr_args that the trilinear renderer reads. */
+typedef struct {
+  const float* mu;                /* [nz][ny][nx] */
+  const unsigned char* labels;    /* [nz][ny][nx] */
+  const dfl_drr_object* objects;  /* device, [views][n_obj] */
+  const float* d_att;             /* [views][H][W] */
+  const float* pivots;            /* [views][n_obj][3], index coordinates (x, y, z) */
+  double* grad;                   /* [views][n_obj][12] */
+  double* scratch;
+  int64_t scratch_doubles;        /* what scratch holds */
+  float qscale[9];                /* row-major */
+  int32_t nx, ny, nz, H, W, views, n_obj;
+  int32_t interp;                 /* DFL_DRR_TRILINEAR */
+  float step_mm;
+} dfl_drr_pose_grad_args;
+int dfl_drr_pose_grad(const dfl_drr_pose_grad_args* a, dfl_stream_t stream);
+int dfl_drr_pose_grad_scratch_doubles(int32_t views, int32_t n_obj, int32_t H, int32_t W);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Gradient-NCC between V rendered views and one fixed image (csrc/sim.hip; DESIGN.md section 16 states the semantics,
  * tests/reg_ref.py restates them in numpy float64): the similarity of dfl_amd.register.
@@ -1072,6 +1112,38 @@ typedef struct {
 } dfl_sim_gradncc_args;
 int dfl_sim_gradncc(const dfl_sim_gradncc_args* a, dfl_stream_t stream);
 int64_t dfl_sim_scratch_doubles(int32_t V, int32_t H, int32_t W);
+
+/* The adjoint of that cost (csrc/sim.hip; DESIGN.md section 19, tests/grad_ref.py): cost[V] with the bits dfl_sim_gradncc
+ * gives for the same inputs (it is computed by the same two kernels), and d_moving[v][r][c] = d cost[v] / d moving[v][r][c]
+ * for every pixel, the border included.
+ *
+ * For one direction let a be the moving and b the fixed Sobel values over the counted pixels, S_aa = sum (a - mean a)^2,
+ * S_bb = sum (b - mean b)^2, S_ab = sum (a - mean a)(b - mean b).  At a counted pixel p
+ *   d ncc / d a_p = (b_p - mean b) / sqrt(S_aa S_bb) - S_ab (a_p - mean a) / (S_aa^(3/2) S_bb^(1/2)),
+ * and 0 at every p when the forward rule makes that ncc 0 (either variance 0, or nothing counted).  g_x = -1/2 d ncc_x / d a,
+ * g_y likewise; d_moving = Sobel^T (g_x, g_y): a pixel gathers, from the counted interior pixels whose 3 x 3 window holds it,
+ * g_x and g_y with the Sobel weight the pixel has in that window.
+ *
+ * The six sums per view are those of dfl_sim_gradncc (float64 band records added in index order); the four coefficients
+ * per direction (the two factors and the two means) are computed in float64 and used per pixel in float32.  A workgroup
+ * stages a 16 x 16 tile of moving with a halo of 2 in LDS.  No atomics: a view's outputs have the same bits whatever else
+ * is in the batch.  scratch holds at least dfl_sim_gradncc_bwd_scratch_doubles(V, H, W) doubles (the forward's records and
+ * 4 V more; negative: bad sizes, or more than 2^31 - 1).  Refused with nothing launched: what dfl_sim_gradncc refuses, and
+ * a NULL d_moving. */
+typedef struct {
+  const float* moving;            /* [V][H][W] */
+  const float* fx;                /* the four outputs of dfl_sim_prepare for the same H, W */
+  const float* fy;
+  const unsigned char* counted;
+  const double* totals;
+  double* scratch;
+  double* cost;                   /* [V] */
+  float* d_moving;                /* [V][H][W] */
+  int64_t scratch_doubles;        /* what scratch holds */
+  int32_t V, H, W, reserved;
+} dfl_sim_gradncc_bwd_args;
+int dfl_sim_gradncc_bwd(const dfl_sim_gradncc_bwd_args* a, dfl_stream_t stream);
+int dfl_sim_gradncc_bwd_scratch_doubles(int32_t V, int32_t H, int32_t W);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Patch-wise gradient-NCC (csrc/sim_patch.hip; DESIGN.md section 18 states the semantics, tests/patch_ref.py restates

@@ -9,6 +9,10 @@ phantom's poses and the candidates are drawn around a start 2 units away in ever
               (conv2d Sobel, float64 sums) as the yardstick for the kernel
   patch       dfl_sim_patch_gradncc on the same views (two kernels; radius 7, stride 4: 41 x 41 patches of 15 x 15), timed
               the same way, and a whole generation of register(similarity='patch') next to one with the global cost
+  gradient    one cost-and-gradient evaluation of the quasi-Newton finish (register(refine=K)) on ONE view: the render, the
+              adjoint of the similarity (dfl_sim_gradncc_bwd) and the pose gradient (dfl_drr_pose_grad) timed as calls with
+              device events, the whole evaluation (with packing, uploads, the copy and the chain on the host) by the wall
+              clock, next to one cost evaluation of one view; in render-equivalents = (render + adjoint + pose gradient) / render
   host        what is left of a whole generation of register(): sampling, the batched packing, the upload of the
               records, the copy of 32 doubles and the CMA-ES update
 
@@ -147,6 +151,37 @@ def main():
     res['patch_generation_check'] = {'rule': 'generation_patch.ms <= generation.ms * 1.01 + the larger spread (max - min) of the two',
                                      'spread_ms': round(spread, 4), 'limit_ms': round(g['ms'] * 1.01 + spread, 4),
                                      'ok': bool(gp['ms'] <= g['ms'] * 1.01 + spread)}
+    # one evaluation of the quasi-Newton finish: one view at the start pose
+    th1 = np.asarray(THETA0)[None]
+    back, masks = np.linalg.inv(I2P), [ob.mask for ob in objects]
+    c2i1 = (back[None] @ reg.pose_deltas(th1, ctr) @ I2P[None])[:, None] @ np.stack([ob.c2i for ob in objects])[None]
+    xis1 = back[None, None] @ reg.pose_delta_jacobians(th1, ctr) @ (np.linalg.inv(reg.pose_deltas(th1, ctr)) @ I2P[None])[:, None]
+    recs1 = drr.pack(vol, c2i1, masks, grid, 'trilinear', True)
+    a1, (att1, _, _), keep1 = drr.args_for_records(vol, recs1, grid, 'trilinear', STEP_MM)
+    nat.call('dfl_drr_render', a1, stream)
+    sim1 = reg.Similarity(fixed, None, 1)
+    d_att1 = sim1.cost_and_adjoint(att1)[1]
+    level1 = reg._Level(vol, grid, fixed, None, 1, STEP_MM)
+
+    def wall(fn, n=40):
+        fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            fn()
+        return round((time.perf_counter() - t0) / n * 1e3, 4)       # fn ends with a copy to the host
+
+    grad = {'render': windows(lambda: nat.call('dfl_drr_render', a1, stream), args.window, args.reps),
+            'adjoint': windows(lambda: sim1.cost_and_adjoint(att1), args.window, args.reps),
+            'pose_gradient': windows(lambda: drr.pose_gradient(vol, recs1, grid, d_att1, None, STEP_MM), args.window, args.reps),
+            'cost_wall_ms': wall(lambda: level1.costs(c2i1, masks)),
+            'cost_and_gradient_wall_ms': wall(lambda: level1.costs_and_grads(c2i1, masks, xis1, [0, 1, 2]))}
+    grad['render_equivalents'] = round((grad['render']['ms'] + grad['adjoint']['ms'] + grad['pose_gradient']['ms']) / grad['render']['ms'], 2)
+    res['gradient_one_view'] = grad
+    del keep1
+    print('one view: render %.4f ms, adjoint %.4f ms, pose gradient %.4f ms = %.2f render-equivalents; wall clock of an evaluation: cost '
+          '%.3f ms, cost and gradient %.3f ms' % (grad['render']['ms'], grad['adjoint']['ms'], grad['pose_gradient']['ms'],
+                                                   grad['render_equivalents'], grad['cost_wall_ms'], grad['cost_and_gradient_wall_ms']), flush=True)
     res['host_side'] = {'ms': round(res['generation']['ms'] - res['render']['ms'] - res['similarity']['ms'], 4)}
     print('180 x 180, lambda 32: generation %.3f ms = render %.3f + similarity %.3f (torch ops %.3f) + host %.3f (of which packing %.3f)'
           % (res['generation']['ms'], res['render']['ms'], res['similarity']['ms'], res['similarity_torch_ops']['ms'], res['host_side']['ms'],
