@@ -21,15 +21,12 @@
 namespace dfl {
 
 struct DrrParams {
-  const float* mu;
-  const unsigned char* labels;
-  const dfl_drr_object* objects;
+  DrrScene S;
   float* att;
   float* plen;
   unsigned char* label_map;
-  float q[9];
-  int nx, ny, nz, H, W, n_obj, n_labels;
-  float step_mm, min_len_mm;
+  int n_labels;
+  float min_len_mm;
 };
 
 // Start of the walk on one axis: k = the first plane crossed after t0, i = the voxel index at t0+, step = +-1 (0: the
@@ -68,33 +65,27 @@ __device__ __forceinline__ void drr_flush(float (&acc)[DRR_NL], uint32_t label, 
 constexpr uint32_t DRR_NONE = 255u;         // "not in an admitted run"
 
 template <bool PLEN>
-__device__ __forceinline__ void drr_exact_object(const DrrParams& P, const dfl_drr_object& ob, float c, float r, float s, float& att,
+__device__ __forceinline__ void drr_exact_object(const DrrScene& S, const dfl_drr_object& ob, float c, float r, float s, float& att,
                                                  float (&acc)[DRR_NL]) {
-  const float o[3] = {ob.o[0], ob.o[1], ob.o[2]};
-  const float d[3] = {drr_dot(ob.M, c, r), drr_dot(ob.M + 3, c, r), drr_dot(ob.M + 6, c, r)};
-  const int lo[3] = {max(ob.box_lo[0], 0), max(ob.box_lo[1], 0), max(ob.box_lo[2], 0)};
-  const int hi[3] = {min(ob.box_hi[0], P.nx - 1), min(ob.box_hi[1], P.ny - 1), min(ob.box_hi[2], P.nz - 1)};
-  if (hi[0] < lo[0] || hi[1] < lo[1] || hi[2] < lo[2]) return;
-  float t0 = 0.f, t1 = __builtin_inff();
-  bool ok = true;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) ok = drr_clip(o[a], d[a], lo[a], hi[a], t0, t1) && ok;
-  if (!ok || !(t1 > t0) || !(t1 < __builtin_inff())) return;
+  DrrRay R;
+  if (!drr_ray(ob, S.nx, S.ny, S.nz, c, r, R)) return;
+  const float(&o)[3] = R.o, (&d)[3] = R.d, t0 = R.t0, t1 = R.t1;
+  const int(&lo)[3] = R.lo, (&hi)[3] = R.hi;
   int k[3], i[3], step[3];
   float tn[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) drr_axis_start(o[a], d[a], lo[a], hi[a], t0, k[a], i[a], step[a], tn[a]);
   const uint32_t mask = ob.mask;
-  const int sy = P.nx, sz = P.nx * P.ny;
+  const int sy = S.nx, sz = S.nx * S.ny;
   float t_cur = t0, run_start = t0;
   uint32_t run = DRR_NONE;
   // every step moves one index by one inside the box, so the trip count is bounded by the box's extent
   while (i[0] >= lo[0] && i[0] <= hi[0] && i[1] >= lo[1] && i[1] <= hi[1] && i[2] >= lo[2] && i[2] <= hi[2]) {
     const float t_next = fminf(fminf(tn[0], tn[1]), fminf(tn[2], t1));
     const int idx = i[2] * sz + i[1] * sy + i[0];
-    const uint32_t lab = P.labels[idx];
+    const uint32_t lab = S.labels[idx];
     const bool in = lab < (uint32_t)DRR_NL && ((mask >> lab) & 1u) != 0u;
-    if (in) att += (s * (t_next - t_cur)) * P.mu[idx];
+    if (in) att += (s * (t_next - t_cur)) * S.mu[idx];
     if (PLEN) {
       const uint32_t now = in ? lab : DRR_NONE;
       if (now != run) {
@@ -119,76 +110,48 @@ __device__ __forceinline__ void drr_exact_object(const DrrParams& P, const dfl_d
   if (PLEN && run != DRR_NONE) drr_flush(acc, run, s * (t_cur - run_start));
 }
 
-// mu of voxel (x, y, z) if its label is admitted, else 0; the indices are inside the volume
-__device__ __forceinline__ float drr_masked(const DrrParams& P, uint32_t mask, int x, int y, int z) {
-  const int idx = (z * P.ny + y) * P.nx + x;
-  const uint32_t lab = P.labels[idx];
-  return lab < (uint32_t)DRR_NL && ((mask >> lab) & 1u) != 0u ? P.mu[idx] : 0.f;
-}
-
-__device__ __forceinline__ void drr_trilinear_object(const DrrParams& P, const dfl_drr_object& ob, float c, float r, float s, float& att) {
-  const float o[3] = {ob.o[0], ob.o[1], ob.o[2]};
-  const float d[3] = {drr_dot(ob.M, c, r), drr_dot(ob.M + 3, c, r), drr_dot(ob.M + 6, c, r)};
-  const int lo[3] = {max(ob.box_lo[0], 0), max(ob.box_lo[1], 0), max(ob.box_lo[2], 0)};
-  const int hi[3] = {min(ob.box_hi[0], P.nx - 1), min(ob.box_hi[1], P.ny - 1), min(ob.box_hi[2], P.nz - 1)};
-  if (hi[0] < lo[0] || hi[1] < lo[1] || hi[2] < lo[2]) return;
-  float t0 = 0.f, t1 = __builtin_inff();
-  bool ok = true;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) ok = drr_clip(o[a], d[a], lo[a], hi[a], t0, t1) && ok;
-  if (!ok || !(t1 > t0) || !(t1 < __builtin_inff())) return;
-  const float span = t1 - t0;
-  const float nf = fmaxf(1.f, ceilf(s * span / P.step_mm));
-  const int N = (int)fminf(nf, 2147483520.f);
-  const float dt = span / nf;
-  const uint32_t mask = ob.mask;
+__device__ __forceinline__ void drr_trilinear_object(const DrrScene& S, const dfl_drr_object& ob, float c, float r, float s, float& att) {
+  DrrRay R;
+  if (!drr_ray(ob, S.nx, S.ny, S.nz, c, r, R)) return;
+  const DrrSamples sm = drr_samples(R, s, S.step_mm);
   float sum = 0.f;
-  for (int j = 0; j < N; ++j) {
-    const float t = t0 + ((float)j + 0.5f) * dt;
-    int x0, x1, y0, y1, z0, z1;
-    float wx, wy, wz;
-    drr_corner(o[0] + t * d[0], P.nx, x0, x1, wx);
-    drr_corner(o[1] + t * d[1], P.ny, y0, y1, wy);
-    drr_corner(o[2] + t * d[2], P.nz, z0, z1, wz);
-    const float v000 = drr_masked(P, mask, x0, y0, z0), v100 = drr_masked(P, mask, x1, y0, z0);
-    const float v010 = drr_masked(P, mask, x0, y1, z0), v110 = drr_masked(P, mask, x1, y1, z0);
-    const float v001 = drr_masked(P, mask, x0, y0, z1), v101 = drr_masked(P, mask, x1, y0, z1);
-    const float v011 = drr_masked(P, mask, x0, y1, z1), v111 = drr_masked(P, mask, x1, y1, z1);
-    const float a00 = v000 + wx * (v100 - v000), a10 = v010 + wx * (v110 - v010);
-    const float a01 = v001 + wx * (v101 - v001), a11 = v011 + wx * (v111 - v011);
-    const float b0 = a00 + wy * (a10 - a00), b1 = a01 + wy * (a11 - a01);
-    sum += b0 + wz * (b1 - b0);
+  for (int j = 0; j < sm.N; ++j) {
+    DrrCell C;
+    drr_gather(S, ob.mask, R, R.t0 + ((float)j + 0.5f) * sm.dt, C);
+    const float* v = C.v;                                  // v[x + 2 y + 4 z]
+    const float a00 = v[0] + C.wx * (v[1] - v[0]), a10 = v[2] + C.wx * (v[3] - v[2]);
+    const float a01 = v[4] + C.wx * (v[5] - v[4]), a11 = v[6] + C.wx * (v[7] - v[6]);
+    const float b0 = a00 + C.wy * (a10 - a00), b1 = a01 + C.wy * (a11 - a01);
+    sum += b0 + C.wz * (b1 - b0);
   }
-  att += (s * span / nf) * sum;
+  att += sm.w * sum;
 }
 
 // INTERP: DFL_DRR_EXACT / DFL_DRR_TRILINEAR; PLEN: plen or label_map is wanted; MAP 0: 8 x 8 tiles per wave, 1: 64 x 1
 template <int INTERP, bool PLEN, int MAP>
 __global__ __launch_bounds__(256) void drr_kernel(DrrParams P) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const DrrScene& S = P.S;
   int col, row;
   if (MAP == 0) {
-    col = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
-    row = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+    drr_tile_pixel(col, row);
   } else {
-    col = blockIdx.x * 64 + lane;
-    row = blockIdx.y * 4 + wave;
+    col = blockIdx.x * 64 + (threadIdx.x & 63);
+    row = blockIdx.y * 4 + (threadIdx.x >> 6);
   }
-  if (col >= P.W || row >= P.H) return;
+  if (col >= S.W || row >= S.H) return;
   const int view = blockIdx.z;
   const float c = (float)col, r = (float)row;
-  const float qx = drr_dot(P.q, c, r), qy = drr_dot(P.q + 3, c, r), qz = drr_dot(P.q + 6, c, r);
-  const float s = sqrtf(qx * qx + qy * qy + qz * qz);
+  const float s = drr_ray_scale(S.q, c, r);
   float att = 0.f;
   float acc[DRR_NL];
 #pragma unroll
   for (int l = 0; l < DRR_NL; ++l) acc[l] = 0.f;
-  const dfl_drr_object* obs = P.objects + (size_t)view * P.n_obj;
-  for (int n = 0; n < P.n_obj; ++n) {
-    if (INTERP == DFL_DRR_EXACT) drr_exact_object<PLEN>(P, obs[n], c, r, s, att, acc);
-    else drr_trilinear_object(P, obs[n], c, r, s, att);
+  const dfl_drr_object* obs = S.objects + (size_t)view * S.n_obj;
+  for (int n = 0; n < S.n_obj; ++n) {
+    if (INTERP == DFL_DRR_EXACT) drr_exact_object<PLEN>(S, obs[n], c, r, s, att, acc);
+    else drr_trilinear_object(S, obs[n], c, r, s, att);
   }
-  const size_t HW = (size_t)P.H * P.W, pix = (size_t)row * P.W + col;
+  const size_t HW = (size_t)S.H * S.W, pix = (size_t)row * S.W + col;
   P.att[(size_t)view * HW + pix] = att;
   if (PLEN) {
     if (P.plen != nullptr) {
@@ -218,13 +181,8 @@ extern "C" int dfl_drr_render(const dfl_drr_args* a, dfl_stream_t stream) {
   DFL_REQUIRE(a != nullptr, "dfl_drr_render: null args");
   DFL_REQUIRE(a->mu != nullptr && a->labels != nullptr && a->objects != nullptr && a->att != nullptr,
               "dfl_drr_render: mu, labels, objects and att are required");
-  DFL_REQUIRE(a->nx >= 1 && a->ny >= 1 && a->nz >= 1 && a->H >= 1 && a->W >= 1 && a->views >= 1 && a->n_obj >= 1,
-              "dfl_drr_render: bad sizes (volume %d x %d x %d, detector %d x %d, views %d, objects %d)", a->nx, a->ny, a->nz, a->H, a->W,
-              a->views, a->n_obj);
-  DFL_REQUIRE((int64_t)a->nx * a->ny * a->nz < ((int64_t)1 << 31), "dfl_drr_render: a volume of %d x %d x %d exceeds 2^31 voxels", a->nx,
-              a->ny, a->nz);
-  DFL_REQUIRE(a->views <= 65535, "dfl_drr_render: at most 65535 views per call, got %d", a->views);
-  DFL_REQUIRE((int64_t)a->H * a->W < ((int64_t)1 << 31) && a->H <= 65535 * 4, "dfl_drr_render: a detector of %d x %d is too large", a->H, a->W);
+  const int rc = dfl::drr_sizes_ok("dfl_drr_render", a->nx, a->ny, a->nz, a->H, a->W, a->views, a->n_obj);
+  if (rc != DFL_OK) return rc;
   DFL_REQUIRE(a->n_labels >= 1 && a->n_labels <= DFL_DRR_MAX_LABELS, "dfl_drr_render: n_labels must be 1..%d, got %d",
               DFL_DRR_MAX_LABELS, a->n_labels);
   DFL_REQUIRE(a->interp == DFL_DRR_EXACT || a->interp == DFL_DRR_TRILINEAR, "dfl_drr_render: unknown interp %d (0 exact, 1 trilinear)",
@@ -234,23 +192,7 @@ extern "C" int dfl_drr_render(const dfl_drr_args* a, dfl_stream_t stream) {
   DFL_REQUIRE(a->interp == DFL_DRR_EXACT || (a->plen == nullptr && a->label_map == nullptr),
               "dfl_drr_render: plen and label_map need the exact interpolation");
   DFL_REQUIRE(a->min_len_mm >= 0.f, "dfl_drr_render: min_len_mm must not be negative, got %g", (double)a->min_len_mm);
-  dfl::DrrParams P;
-  P.mu = a->mu;
-  P.labels = a->labels;
-  P.objects = a->objects;
-  P.att = a->att;
-  P.plen = a->plen;
-  P.label_map = a->label_map;
-  for (int k = 0; k < 9; ++k) P.q[k] = a->qscale[k];
-  P.nx = a->nx;
-  P.ny = a->ny;
-  P.nz = a->nz;
-  P.H = a->H;
-  P.W = a->W;
-  P.n_obj = a->n_obj;
-  P.n_labels = a->n_labels;
-  P.step_mm = a->step_mm;
-  P.min_len_mm = a->min_len_mm;
+  const dfl::DrrParams P = {dfl::drr_scene_of(a), a->att, a->plen, a->label_map, a->n_labels, a->min_len_mm};
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool plen = a->plen != nullptr || a->label_map != nullptr;
   const dim3 grid = a->mapping == 0 ? dim3((unsigned)dfl::ceil_div(a->W, 16), (unsigned)dfl::ceil_div(a->H, 16), (unsigned)a->views)

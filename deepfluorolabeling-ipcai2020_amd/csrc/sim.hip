@@ -8,21 +8,21 @@
 // eight neighbours of the moving image straight from global memory (consecutive lanes read consecutive columns; a
 // batch of 32 views of 180 x 180 is 4 MB and stays in L2, and a row is re-read by its two neighbouring rows out of
 // the vector L1) and adds six sums in float64.  Wave shuffles, then LDS across the four waves, then ONE record of six
-// doubles per workgroup with plain stores; sim_finish_kernel adds a view's records in index order and writes its cost.
+// doubles per workgroup with plain stores; sim_finish_kernel adds a view's records in index order and writes its cost
+// (csrc/fixed_sum.h: block_sum, records_sum).  The sums of a pixel, Sobel and the NCC are csrc/sim.h's.
 // No atomics: the bits of a view's cost depend on that view's pixels and on H and W only.
 #include "sim.h"
 
 namespace dfl {
 
 constexpr int SIM_ROWS = 8;          // interior rows per workgroup
-constexpr int SIM_SUMS = 6;          // sum mx, mx^2, mx fx, my, my^2, my fy
 
 __global__ __launch_bounds__(SIM_THREADS) void sim_prepare_kernel(const float* __restrict__ fixed, const unsigned char* __restrict__ mask,
                                                                   float* __restrict__ fx, float* __restrict__ fy,
                                                                   unsigned char* __restrict__ counted, double* __restrict__ totals,
                                                                   int H, int W) {
-  __shared__ double lds[5 * 4];
-  double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  __shared__ double lds[SIM_FIXED * 4];
+  double s[SIM_FIXED] = {0.0, 0.0, 0.0, 0.0, 0.0};
   const int64_t n = (int64_t)H * W;
   for (int64_t p = threadIdx.x; p < n; p += SIM_THREADS) {
     const int r = (int)(p / W), c = (int)(p - (int64_t)r * W);
@@ -42,66 +42,43 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_prepare_kernel(const float* _
     fx[p] = gx;
     fy[p] = gy;
     counted[p] = on;
-    if (on) {
-      const double x = (double)gx, y = (double)gy;
-      s[0] += 1.0;
-      s[1] += x;
-      s[2] += x * x;
-      s[3] += y;
-      s[4] += y * y;
-    }
+    if (on) sim_fixed_sums(s, gx, gy);
   }
-  sim_block_sum<5>(s, lds);
+  block_sum<SIM_FIXED>(s, lds);
   if (threadIdx.x == 0) {
 #pragma unroll
-    for (int k = 0; k < 5; ++k) totals[k] = s[k];
+    for (int k = 0; k < SIM_FIXED; ++k) totals[k] = s[k];
   }
 }
 
 __global__ __launch_bounds__(SIM_THREADS) void sim_gradncc_kernel(const float* __restrict__ moving, const float* __restrict__ fx,
                                                                   const float* __restrict__ fy, const unsigned char* __restrict__ counted,
                                                                   double* __restrict__ scratch, int H, int W) {
-  __shared__ double lds[SIM_SUMS * 4];
+  __shared__ double lds[SIM_MOVING * 4];
   const int band = blockIdx.x, view = blockIdx.y;
   const int r0 = 1 + band * SIM_ROWS;                                   // first interior row of the band
   const int rows = min(SIM_ROWS, H - 1 - r0);                           // interior rows are 1 .. H - 2
   const int wi = W - 2;
   const float* img = moving + (size_t)view * H * W;
-  double s[SIM_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  double s[SIM_MOVING] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   for (int p = threadIdx.x; p < rows * wi; p += SIM_THREADS) {
     const int r = r0 + p / wi, c = 1 + p % wi;
-    const size_t at = (size_t)r * W + c;
-    if (counted[at]) {
-      float gx, gy;
-      sim_sobel(img, W, r, c, gx, gy);
-      const double mx = (double)gx, my = (double)gy;
-      s[0] += mx;
-      s[1] += mx * mx;
-      s[2] += mx * (double)fx[at];
-      s[3] += my;
-      s[4] += my * my;
-      s[5] += my * (double)fy[at];
-    }
+    if (counted[(size_t)r * W + c]) sim_moving_sums(s, img, fx, fy, W, r, c);
   }
-  sim_block_sum<SIM_SUMS>(s, lds);
+  block_sum<SIM_MOVING>(s, lds);
   if (threadIdx.x == 0) {
-    double* rec = scratch + ((size_t)view * gridDim.x + band) * SIM_SUMS;
+    double* rec = scratch + ((size_t)view * gridDim.x + band) * SIM_MOVING;
 #pragma unroll
-    for (int k = 0; k < SIM_SUMS; ++k) rec[k] = s[k];
+    for (int k = 0; k < SIM_MOVING; ++k) rec[k] = s[k];
   }
 }
 
 // One wave per view: lanes 0..5 add one of the six sums each over the view's records, in index order
 __global__ __launch_bounds__(64) void sim_finish_kernel(const double* __restrict__ scratch, const double* __restrict__ totals,
                                                         double* __restrict__ cost, int bands) {
-  __shared__ double m[SIM_SUMS];
+  __shared__ double m[SIM_MOVING];
   const int view = blockIdx.x;
-  if (threadIdx.x < SIM_SUMS) {
-    const double* rec = scratch + (size_t)view * bands * SIM_SUMS + threadIdx.x;
-    double acc = 0.0;
-    for (int b = 0; b < bands; ++b) acc += rec[(size_t)b * SIM_SUMS];
-    m[threadIdx.x] = acc;
-  }
+  if (threadIdx.x < SIM_MOVING) m[threadIdx.x] = records_sum(scratch + (size_t)view * bands * SIM_MOVING + threadIdx.x, bands, SIM_MOVING);
   __syncthreads();
   if (threadIdx.x == 0) {
     const double n = totals[0];
@@ -125,21 +102,17 @@ __global__ __launch_bounds__(64) void sim_coef_kernel(const double* __restrict__
                                                       float* __restrict__ coef, int bands, int V) {
   const int view = blockIdx.x * 64 + threadIdx.x;
   if (view >= V) return;
-  double m[SIM_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  const double* rec = scratch + (size_t)view * bands * SIM_SUMS;
-  for (int b = 0; b < bands; ++b) {
+  double m[SIM_MOVING];
 #pragma unroll
-    for (int k = 0; k < SIM_SUMS; ++k) m[k] += rec[(size_t)b * SIM_SUMS + k];
-  }
+  for (int k = 0; k < SIM_MOVING; ++k) m[k] = records_sum(scratch + (size_t)view * bands * SIM_MOVING + k, bands, SIM_MOVING);
   const double n = totals[0];
-  const double eps = 9.094947017729282e-13;                             // 2^-40, the rule of sim_ncc
 #pragma unroll
   for (int dir = 0; dir < 2; ++dir) {
     const double sa = m[3 * dir], saa = m[3 * dir + 1], sab = m[3 * dir + 2], sb = totals[1 + 2 * dir], sbb = totals[2 + 2 * dir];
     double alpha = 0.0, beta = 0.0, ma = 0.0, mb = 0.0;
     if (n >= 1.0) {
-      const double va = saa - sa * sa / n, vb = sbb - sb * sb / n;
-      if (va > eps * saa && vb > eps * sbb) {
+      const double va = sim_var(n, sa, saa), vb = sim_var(n, sb, sbb);
+      if (sim_live(va, saa) && sim_live(vb, sbb)) {                     // the rule of sim_ncc
         const double root = sqrt(va * vb);
         alpha = -0.5 / root;
         beta = 0.5 * (sab - sa * sb / n) / (va * root);
@@ -182,11 +155,11 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_adjoint_kernel(const float* _
     if (r >= 1 && r <= H - 2 && c >= 1 && c <= W - 2) {
       const size_t at = (size_t)r * W + c;
       if (counted[at]) {
-        // sim_sobel on the staged tile: pixel (r, c) sits at sm[lr + 1][lc + 1]
-        const float a = sm[lr][lc], b = sm[lr][lc + 1], cc = sm[lr][lc + 2], d = sm[lr + 1][lc], f = sm[lr + 1][lc + 2];
-        const float g = sm[lr + 2][lc], h = sm[lr + 2][lc + 1], k = sm[lr + 2][lc + 2];
-        const float mx = ((cc + 2.f * f) + k) - ((a + 2.f * d) + g);
-        const float my = ((g + 2.f * h) + k) - ((a + 2.f * b) + cc);
+        // Sobel on the staged tile: pixel (r, c) sits at sm[lr + 1][lc + 1].  sim_sobel9 is defined outside this function's
+        // contract(off) and may fuse x + 2 y; that gives the same bits either way, since 2 y is exact
+        float mx, my;
+        sim_sobel9(sm[lr][lc], sm[lr][lc + 1], sm[lr][lc + 2], sm[lr + 1][lc], sm[lr + 1][lc + 2], sm[lr + 2][lc], sm[lr + 2][lc + 1],
+                   sm[lr + 2][lc + 2], mx, my);
         gx = ax * (fx[at] - mbx) + bx * (mx - max_);
         gy = ay * (fy[at] - mby) + by * (my - may);
       }
@@ -206,24 +179,24 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_adjoint_kernel(const float* _
 }
 
 // records [V][bands][6], then the coefficients [V][8] float32
-inline int64_t sim_bwd_need(int64_t V, int H) { return V * sim_bands(H) * SIM_SUMS + V * (SIM_COEF / 2); }
+inline int64_t sim_bwd_need(int64_t V, int H) { return V * sim_bands(H) * SIM_MOVING + V * (SIM_COEF / 2); }
 
 }  // namespace dfl
 
 extern "C" int64_t dfl_sim_scratch_doubles(int32_t V, int32_t H, int32_t W) {
-  if (V < 1 || V > 65535 || H < 3 || W < 3 || (int64_t)H * W >= ((int64_t)1 << 31)) {
+  if (dfl::sim_sizes_ok("", V, H, W) != DFL_OK) {                       // this function's one message replaces sim_sizes_ok's
     dfl::set_error("dfl_sim_scratch_doubles: bad sizes (views %d of 1..65535, image %d x %d of at least 3 x 3)", V, H, W);
     return DFL_ERR_INVALID_ARG;
   }
-  return (int64_t)V * dfl::sim_bands(H) * dfl::SIM_SUMS;
+  return (int64_t)V * dfl::sim_bands(H) * dfl::SIM_MOVING;
 }
 
 extern "C" int dfl_sim_prepare(const dfl_sim_prepare_args* a, dfl_stream_t stream) {
   DFL_REQUIRE(a != nullptr, "dfl_sim_prepare: null args");
   DFL_REQUIRE(a->fixed != nullptr && a->fx != nullptr && a->fy != nullptr && a->counted != nullptr && a->totals != nullptr,
               "dfl_sim_prepare: fixed, fx, fy, counted and totals are required");
-  DFL_REQUIRE(a->H >= 3 && a->W >= 3, "dfl_sim_prepare: an image of %d x %d (at least 3 x 3)", a->H, a->W);
-  DFL_REQUIRE((int64_t)a->H * a->W < ((int64_t)1 << 31), "dfl_sim_prepare: an image of %d x %d is too large", a->H, a->W);
+  const int rc = dfl::sim_sizes_ok("dfl_sim_prepare", 1, a->H, a->W);
+  if (rc != DFL_OK) return rc;
   dfl::sim_prepare_kernel<<<1, dfl::SIM_THREADS, 0, static_cast<hipStream_t>(stream)>>>(a->fixed, a->mask, a->fx, a->fy, a->counted,
                                                                                           a->totals, a->H, a->W);
   return dfl::check_launch("dfl_sim_prepare");
@@ -234,11 +207,10 @@ extern "C" int dfl_sim_gradncc(const dfl_sim_gradncc_args* a, dfl_stream_t strea
   DFL_REQUIRE(a->moving != nullptr && a->fx != nullptr && a->fy != nullptr && a->counted != nullptr && a->totals != nullptr &&
                   a->scratch != nullptr && a->cost != nullptr,
               "dfl_sim_gradncc: moving, fx, fy, counted, totals, scratch and cost are required");
-  DFL_REQUIRE(a->H >= 3 && a->W >= 3, "dfl_sim_gradncc: an image of %d x %d (at least 3 x 3)", a->H, a->W);
-  DFL_REQUIRE((int64_t)a->H * a->W < ((int64_t)1 << 31), "dfl_sim_gradncc: an image of %d x %d is too large", a->H, a->W);
-  DFL_REQUIRE(a->V >= 1 && a->V <= 65535, "dfl_sim_gradncc: 1..65535 views per call, got %d", a->V);
+  const int rc = dfl::sim_sizes_ok("dfl_sim_gradncc", a->V, a->H, a->W);
+  if (rc != DFL_OK) return rc;
   const int bands = dfl::sim_bands(a->H);
-  const int64_t need = (int64_t)a->V * bands * dfl::SIM_SUMS;
+  const int64_t need = (int64_t)a->V * bands * dfl::SIM_MOVING;
   DFL_REQUIRE(a->scratch_doubles >= need, "dfl_sim_gradncc: a scratch of %lld doubles, %lld are needed (dfl_sim_scratch_doubles)",
               (long long)a->scratch_doubles, (long long)need);
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -249,7 +221,7 @@ extern "C" int dfl_sim_gradncc(const dfl_sim_gradncc_args* a, dfl_stream_t strea
 }
 
 extern "C" int dfl_sim_gradncc_bwd_scratch_doubles(int32_t V, int32_t H, int32_t W) {
-  if (V < 1 || V > 65535 || H < 3 || W < 3 || (int64_t)H * W >= ((int64_t)1 << 31) || dfl::sim_bwd_need(V, H) >= ((int64_t)1 << 31)) {
+  if (dfl::sim_sizes_ok("", V, H, W) != DFL_OK || dfl::sim_bwd_need(V, H) >= ((int64_t)1 << 31)) {
     dfl::set_error("dfl_sim_gradncc_bwd_scratch_doubles: bad sizes (views %d of 1..65535, image %d x %d of at least 3 x 3), or more than "
                    "2^31 - 1 doubles", V, H, W);
     return DFL_ERR_INVALID_ARG;
@@ -262,16 +234,15 @@ extern "C" int dfl_sim_gradncc_bwd(const dfl_sim_gradncc_bwd_args* a, dfl_stream
   DFL_REQUIRE(a->moving != nullptr && a->fx != nullptr && a->fy != nullptr && a->counted != nullptr && a->totals != nullptr &&
                   a->scratch != nullptr && a->cost != nullptr && a->d_moving != nullptr,
               "dfl_sim_gradncc_bwd: moving, fx, fy, counted, totals, scratch, cost and d_moving are required");
-  DFL_REQUIRE(a->H >= 3 && a->W >= 3, "dfl_sim_gradncc_bwd: an image of %d x %d (at least 3 x 3)", a->H, a->W);
-  DFL_REQUIRE((int64_t)a->H * a->W < ((int64_t)1 << 31), "dfl_sim_gradncc_bwd: an image of %d x %d is too large", a->H, a->W);
-  DFL_REQUIRE(a->V >= 1 && a->V <= 65535, "dfl_sim_gradncc_bwd: 1..65535 views per call, got %d", a->V);
+  const int rc = dfl::sim_sizes_ok("dfl_sim_gradncc_bwd", a->V, a->H, a->W);
+  if (rc != DFL_OK) return rc;
   const int bands = dfl::sim_bands(a->H);
   const int64_t need = dfl::sim_bwd_need(a->V, a->H);
   DFL_REQUIRE(a->scratch_doubles >= need, "dfl_sim_gradncc_bwd: a scratch of %lld doubles, %lld are needed (dfl_sim_gradncc_bwd_scratch_doubles)",
               (long long)a->scratch_doubles, (long long)need);
   DFL_REQUIRE(dfl::ceil_div(a->H, dfl::SIM_TILE) <= 65535, "dfl_sim_gradncc_bwd: an image of %d rows is too tall", a->H);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  float* coef = reinterpret_cast<float*>(a->scratch + (size_t)a->V * bands * dfl::SIM_SUMS);
+  float* coef = reinterpret_cast<float*>(a->scratch + (size_t)a->V * bands * dfl::SIM_MOVING);
   // the forward's own two kernels: the cost has the forward's bits
   dfl::sim_gradncc_kernel<<<dim3((unsigned)bands, (unsigned)a->V), dfl::SIM_THREADS, 0, s>>>(a->moving, a->fx, a->fy, a->counted,
                                                                                                a->scratch, a->H, a->W);

@@ -1,7 +1,7 @@
 // Patch-wise gradient-NCC between V rendered views and one fixed image: the similarity='patch' cost of dfl_amd.register.
 // Contract: include/dfl_hip.h (dfl_sim_patch_prepare_args, dfl_sim_patch_gradncc_args); the semantics are stated in
-// DESIGN.md section 18 and restated in numpy float64 by tests/patch_ref.py.  Sobel, the block sums and the NCC are
-// csrc/sim.h's, shared with csrc/sim.hip.
+// DESIGN.md section 18 and restated in numpy float64 by tests/patch_ref.py.  Sobel, the sums of a pixel and the NCC are
+// csrc/sim.h's, shared with csrc/sim.hip; the block and record sums are csrc/fixed_sum.h's.
 //
 // Both passes have one shape: a workgroup of 256 threads owns one patch row a (the S interior rows a s .. a s + S - 1) of
 // one image.  Phase 1: thread t takes the interior columns t, t + 256, ... and adds its sums down the S rows of the band,
@@ -12,15 +12,13 @@
 //   sim_patch_count_kernel: one workgroup counts the flags -> pcount (integers in float64: exact, any order).
 //   sim_patch_gradncc_kernel (once per generation): six sums (mx, mx^2, mx fx, my, my^2, my fy) -> the two NCCs of every
 //   patch of the row, gated by pflags; a thread adds its patches' NCCs in index order, the workgroup adds the threads in
-//   sim_block_sum's fixed order and writes ONE record of two doubles with plain stores.
+//   block_sum's fixed order and writes ONE record of two doubles with plain stores.
 //   sim_patch_finish_kernel (one wave per view): adds the PR records in index order, divides by pcount, writes the cost.
 // No atomics: the bits of a view's cost depend on that view's pixels and on H, W, rho and the stride only.
 #include "sim.h"
 
 namespace dfl {
 
-constexpr int SIMP_FIXED = 5;        // n, sum fx, fx^2, fy, fy^2 (DFL_SIM_TOTALS)
-constexpr int SIMP_MOVING = 6;       // sum mx, mx^2, mx fx, my, my^2, my fy
 
 struct patch_grid {
   int S, PR, PC;
@@ -40,41 +38,33 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_patch_prepare_kernel(const fl
                                                                         const unsigned char* __restrict__ counted,
                                                                         double* __restrict__ ptotals, unsigned char* __restrict__ pflags,
                                                                         int W, int S, int stride, int PC, int min_count) {
-  extern __shared__ double cols[];                                      // [SIMP_FIXED][W - 2]
+  extern __shared__ double cols[];                                      // [SIM_FIXED][W - 2]
   const int a = blockIdx.x, wi = W - 2;
   const int r0 = 1 + a * stride;                                        // first image row of the band
   for (int j = threadIdx.x; j < wi; j += SIM_THREADS) {
-    double s[SIMP_FIXED] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    double s[SIM_FIXED] = {0.0, 0.0, 0.0, 0.0, 0.0};
     for (int k = 0; k < S; ++k) {
       const size_t at = (size_t)(r0 + k) * W + (1 + j);
-      if (counted[at]) {
-        const double x = (double)fx[at], y = (double)fy[at];
-        s[0] += 1.0;
-        s[1] += x;
-        s[2] += x * x;
-        s[3] += y;
-        s[4] += y * y;
-      }
+      if (counted[at]) sim_fixed_sums(s, fx[at], fy[at]);
     }
 #pragma unroll
-    for (int q = 0; q < SIMP_FIXED; ++q) cols[q * wi + j] = s[q];
+    for (int q = 0; q < SIM_FIXED; ++q) cols[q * wi + j] = s[q];
   }
   __syncthreads();
-  const double eps = 9.094947017729282e-13;                             // 2^-40, as sim_ncc
   for (int b = threadIdx.x; b < PC; b += SIM_THREADS) {
-    double s[SIMP_FIXED] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    double s[SIM_FIXED] = {0.0, 0.0, 0.0, 0.0, 0.0};
     const int j0 = b * stride;
     for (int k = 0; k < S; ++k) {
 #pragma unroll
-      for (int q = 0; q < SIMP_FIXED; ++q) s[q] += cols[q * wi + j0 + k];
+      for (int q = 0; q < SIM_FIXED; ++q) s[q] += cols[q * wi + j0 + k];
     }
     const size_t p = (size_t)a * PC + b;
 #pragma unroll
-    for (int q = 0; q < SIMP_FIXED; ++q) ptotals[p * SIMP_FIXED + q] = s[q];
+    for (int q = 0; q < SIM_FIXED; ++q) ptotals[p * SIM_FIXED + q] = s[q];
     unsigned char flags = 0;
     if (s[0] >= (double)min_count) {                                    // min_count >= 1: n is not 0 below
-      if (s[2] - s[1] * s[1] / s[0] > eps * s[2]) flags |= 1;
-      if (s[4] - s[3] * s[3] / s[0] > eps * s[4]) flags |= 2;
+      if (sim_live(sim_var(s[0], s[1], s[2]), s[2])) flags |= 1;         // the rule of sim_ncc
+      if (sim_live(sim_var(s[0], s[3], s[4]), s[4])) flags |= 2;
     }
     pflags[p] = flags;
   }
@@ -89,7 +79,7 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_patch_count_kernel(const unsi
     s[0] += (double)(f & 1);
     s[1] += (double)((f >> 1) & 1);
   }
-  sim_block_sum<2>(s, lds);
+  block_sum<2>(s, lds);
   if (threadIdx.x == 0) {
     pcount[0] = (int)s[0];
     pcount[1] = (int)s[1];
@@ -103,30 +93,19 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_patch_gradncc_kernel(const fl
                                                                         const unsigned char* __restrict__ pflags,
                                                                         double* __restrict__ scratch, int H, int W, int S, int stride,
                                                                         int PC) {
-  extern __shared__ double cols[];                                      // [SIMP_MOVING][W - 2]
+  extern __shared__ double cols[];                                      // [SIM_MOVING][W - 2]
   __shared__ double lds[2 * 4];
   const int a = blockIdx.x, view = blockIdx.y, wi = W - 2;
   const int r0 = 1 + a * stride;
   const float* img = moving + (size_t)view * H * W;
   for (int j = threadIdx.x; j < wi; j += SIM_THREADS) {
-    double s[SIMP_MOVING] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double s[SIM_MOVING] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int k = 0; k < S; ++k) {
       const int r = r0 + k, c = 1 + j;
-      const size_t at = (size_t)r * W + c;
-      if (counted[at]) {
-        float gx, gy;
-        sim_sobel(img, W, r, c, gx, gy);
-        const double mx = (double)gx, my = (double)gy;
-        s[0] += mx;
-        s[1] += mx * mx;
-        s[2] += mx * (double)fx[at];
-        s[3] += my;
-        s[4] += my * my;
-        s[5] += my * (double)fy[at];
-      }
+      if (counted[(size_t)r * W + c]) sim_moving_sums(s, img, fx, fy, W, r, c);
     }
 #pragma unroll
-    for (int q = 0; q < SIMP_MOVING; ++q) cols[q * wi + j] = s[q];
+    for (int q = 0; q < SIM_MOVING; ++q) cols[q * wi + j] = s[q];
   }
   __syncthreads();
   double acc[2] = {0.0, 0.0};
@@ -134,17 +113,17 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_patch_gradncc_kernel(const fl
     const size_t p = (size_t)a * PC + b;
     const unsigned char flags = pflags[p];
     if (flags == 0) continue;
-    double s[SIMP_MOVING] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double s[SIM_MOVING] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     const int j0 = b * stride;
     for (int k = 0; k < S; ++k) {
 #pragma unroll
-      for (int q = 0; q < SIMP_MOVING; ++q) s[q] += cols[q * wi + j0 + k];
+      for (int q = 0; q < SIM_MOVING; ++q) s[q] += cols[q * wi + j0 + k];
     }
-    const double* t = ptotals + p * SIMP_FIXED;
+    const double* t = ptotals + p * SIM_FIXED;
     if (flags & 1) acc[0] += sim_ncc(t[0], s[0], s[1], t[1], t[2], s[2]);
     if (flags & 2) acc[1] += sim_ncc(t[0], s[3], s[4], t[3], t[4], s[5]);
   }
-  sim_block_sum<2>(acc, lds);
+  block_sum<2>(acc, lds);
   if (threadIdx.x == 0) {
     double* rec = scratch + ((size_t)view * gridDim.x + a) * 2;
     rec[0] = acc[0];
@@ -158,9 +137,7 @@ __global__ __launch_bounds__(64) void sim_patch_finish_kernel(const double* __re
   __shared__ double m[2];
   const int view = blockIdx.x;
   if (threadIdx.x < 2) {
-    const double* rec = scratch + (size_t)view * PR * 2 + threadIdx.x;
-    double acc = 0.0;
-    for (int a = 0; a < PR; ++a) acc += rec[(size_t)a * 2];
+    const double acc = records_sum(scratch + (size_t)view * PR * 2 + threadIdx.x, PR, 2);
     const int n = pcount[threadIdx.x];
     m[threadIdx.x] = n > 0 ? acc / (double)n : 0.0;
   }
@@ -170,8 +147,8 @@ __global__ __launch_bounds__(64) void sim_patch_finish_kernel(const double* __re
 
 // the checks on sizes that every entry point shares; `who` names it in the message
 static int patch_sizes_ok(const char* who, int H, int W, int rho, int stride, patch_grid* g) {
-  DFL_REQUIRE(H >= 3 && W >= 3, "%s: an image of %d x %d (at least 3 x 3)", who, H, W);
-  DFL_REQUIRE((int64_t)H * W < ((int64_t)1 << 31), "%s: an image of %d x %d is too large", who, H, W);
+  const int rc = sim_sizes_ok(who, 1, H, W);                            // the views are checked after the patches
+  if (rc != DFL_OK) return rc;
   DFL_REQUIRE(rho >= 1, "%s: a patch radius of %d (at least 1)", who, rho);
   DFL_REQUIRE(stride >= 1, "%s: a patch stride of %d (at least 1)", who, stride);
   DFL_REQUIRE(patch_grid_of(H, W, rho, stride, g), "%s: a patch of side %lld does not fit into the %d x %d interior pixels", who,
@@ -207,8 +184,8 @@ extern "C" int dfl_sim_patch_prepare(const dfl_sim_patch_prepare_args* a, dfl_st
   const int rc = dfl::patch_sizes_ok("dfl_sim_patch_prepare", a->H, a->W, a->rho, a->stride, &g);
   if (rc != DFL_OK) return rc;
   DFL_REQUIRE(a->min_count >= 1, "dfl_sim_patch_prepare: a min_count of %d (at least 1)", a->min_count);
-  const int lds = dfl::SIMP_FIXED * (a->W - 2) * (int)sizeof(double);
-  DFL_LDS_OPT_IN(dfl::sim_patch_prepare_kernel, DFL_SIM_PATCH_MAX_W * dfl::SIMP_FIXED * sizeof(double), "dfl_sim_patch_prepare")
+  const int lds = dfl::SIM_FIXED * (a->W - 2) * (int)sizeof(double);
+  DFL_LDS_OPT_IN(dfl::sim_patch_prepare_kernel, DFL_SIM_PATCH_MAX_W * dfl::SIM_FIXED * sizeof(double), "dfl_sim_patch_prepare")
   hipStream_t s = static_cast<hipStream_t>(stream);
   dfl::sim_patch_prepare_kernel<<<(unsigned)g.PR, dfl::SIM_THREADS, lds, s>>>(a->fx, a->fy, a->counted, a->ptotals, a->pflags, a->W, g.S,
                                                                               a->stride, g.PC, a->min_count);
@@ -229,8 +206,8 @@ extern "C" int dfl_sim_patch_gradncc(const dfl_sim_patch_gradncc_args* a, dfl_st
   DFL_REQUIRE(a->scratch_doubles >= need,
               "dfl_sim_patch_gradncc: a scratch of %lld doubles, %lld are needed (dfl_sim_patch_scratch_doubles)",
               (long long)a->scratch_doubles, (long long)need);
-  const int lds = dfl::SIMP_MOVING * (a->W - 2) * (int)sizeof(double);
-  DFL_LDS_OPT_IN(dfl::sim_patch_gradncc_kernel, DFL_SIM_PATCH_MAX_W * dfl::SIMP_MOVING * sizeof(double), "dfl_sim_patch_gradncc")
+  const int lds = dfl::SIM_MOVING * (a->W - 2) * (int)sizeof(double);
+  DFL_LDS_OPT_IN(dfl::sim_patch_gradncc_kernel, DFL_SIM_PATCH_MAX_W * dfl::SIM_MOVING * sizeof(double), "dfl_sim_patch_gradncc")
   hipStream_t s = static_cast<hipStream_t>(stream);
   dfl::sim_patch_gradncc_kernel<<<dim3((unsigned)g.PR, (unsigned)a->V), dfl::SIM_THREADS, lds, s>>>(
       a->moving, a->fx, a->fy, a->counted, a->ptotals, a->pflags, a->scratch, a->H, a->W, g.S, a->stride, g.PC);

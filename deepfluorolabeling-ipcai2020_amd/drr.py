@@ -271,22 +271,33 @@ def pack_objects(volume, objects, grid, interp='exact', tight_boxes=True):
                 tight_boxes)
 
 
+def launch(dev, entry, a):
+    """One call of a C entry point on dev's current stream."""
+    with torch.cuda.device(dev):
+        nat.call(entry, a, torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _scene_fields(volume, recs, grid, step_mm):
+    """(the uploaded records, the fields DrrArgs and DrrPoseGradArgs share) for packed records [views, n_obj]."""
+    nz, ny, nx = volume.shape
+    d_objs = torch.from_numpy(np.ascontiguousarray(recs).view(np.uint8).reshape(-1)).to(volume.mu.device)
+    return d_objs, dict(mu=volume.mu.data_ptr(), labels=volume.labels.data_ptr(), objects=d_objs.data_ptr(),
+                        qscale=(nat.f32 * 9)(*grid.Q.astype(np.float32).reshape(-1)), nx=nx, ny=ny, nz=nz, H=grid.H, W=grid.W,
+                        views=recs.shape[0], n_obj=recs.shape[1], step_mm=float(step_mm))
+
+
 def args_for_records(volume, recs, grid, interp='exact', step_mm=0.5, want_plen=False, want_labels=True, min_len_mm=1.0, mapping=0):
     """(DrrArgs, (att, plen, labels) with the view axis, tensors to keep alive) for packed records [views, n_obj]: the
     upload, the freshly allocated outputs and the argument block of dfl_drr_render, nothing launched."""
-    V, n_obj = recs.shape
     exact = interp == 'exact'
     dev = volume.mu.device
-    H, W, NL = grid.H, grid.W, volume.n_labels
-    nz, ny, nx = volume.shape
-    d_objs = torch.from_numpy(np.ascontiguousarray(recs).view(np.uint8).reshape(-1)).to(dev)
+    V, H, W, NL = recs.shape[0], grid.H, grid.W, volume.n_labels
+    d_objs, shared = _scene_fields(volume, recs, grid, step_mm)
     att = torch.empty((V, H, W), dtype=torch.float32, device=dev)
     plen = torch.empty((V, NL, H, W), dtype=torch.float32, device=dev) if exact and want_plen else None
     lab = torch.empty((V, H, W), dtype=torch.uint8, device=dev) if exact and want_labels else None
-    a = nat.DrrArgs(mu=volume.mu.data_ptr(), labels=volume.labels.data_ptr(), objects=d_objs.data_ptr(), att=att.data_ptr(),
-                    plen=nat.ptr(plen), label_map=nat.ptr(lab), qscale=(nat.f32 * 9)(*grid.Q.astype(np.float32).reshape(-1)),
-                    nx=nx, ny=ny, nz=nz, H=H, W=W, views=V, n_obj=n_obj, n_labels=NL, interp=_INTERP[interp],
-                    mapping=int(mapping), step_mm=float(step_mm), min_len_mm=float(min_len_mm))
+    a = nat.DrrArgs(att=att.data_ptr(), plen=nat.ptr(plen), label_map=nat.ptr(lab), n_labels=NL, interp=_INTERP[interp],
+                    mapping=int(mapping), min_len_mm=float(min_len_mm), **shared)
     return a, (att, plen, lab), [d_objs, volume]
 
 
@@ -324,18 +335,14 @@ def pose_gradient(volume, recs, grid, d_att, pivots=None, step_mm=0.5):
     need = int(lib.dfl_drr_pose_grad_scratch_doubles(V, n_obj, H, W))
     if need < 0:
         raise nat.DflError('drr.pose_gradient: %s' % lib.dfl_last_error().decode())
-    nz, ny, nx = volume.shape
     d_att = d_att.detach().contiguous()
-    d_objs = torch.from_numpy(np.ascontiguousarray(recs).view(np.uint8).reshape(-1)).to(dev)
+    d_objs, shared = _scene_fields(volume, recs, grid, step_mm)
     d_piv = torch.from_numpy(np.ascontiguousarray(piv)).to(dev)
     grad = torch.empty((V, n_obj, 12), dtype=torch.float64, device=dev)
     scratch = torch.empty(need, dtype=torch.float64, device=dev)
-    a = nat.DrrPoseGradArgs(mu=volume.mu.data_ptr(), labels=volume.labels.data_ptr(), objects=d_objs.data_ptr(), d_att=d_att.data_ptr(),
-                            pivots=d_piv.data_ptr(), grad=grad.data_ptr(), scratch=scratch.data_ptr(), scratch_doubles=need,
-                            qscale=(nat.f32 * 9)(*grid.Q.astype(np.float32).reshape(-1)), nx=nx, ny=ny, nz=nz, H=H, W=W, views=V,
-                            n_obj=n_obj, interp=nat.DRR_TRILINEAR, step_mm=float(step_mm))
-    with torch.cuda.device(dev):
-        nat.call('dfl_drr_pose_grad', a, torch.cuda.current_stream(dev).cuda_stream)
+    a = nat.DrrPoseGradArgs(d_att=d_att.data_ptr(), pivots=d_piv.data_ptr(), grad=grad.data_ptr(), scratch=scratch.data_ptr(),
+                            scratch_doubles=need, interp=nat.DRR_TRILINEAR, **shared)
+    launch(dev, 'dfl_drr_pose_grad', a)
     return grad                                                   # stream order keeps the uploads alive until the kernels ran
 
 
@@ -362,9 +369,7 @@ def render(volume, objects, grid, interp='exact', step_mm=0.5, want_plen=False, 
     `objects` ([[Obj]]) every output has one too.  mapping 1 is the row mapping tools/bench_drr.py measures."""
     a, (att, plen, lab), keep = render_args(volume, objects, grid, interp, step_mm, want_plen, want_labels, min_len_mm,
                                             tight_boxes, mapping)
-    dev = att.device
-    with torch.cuda.device(dev):
-        nat.call('dfl_drr_render', a, torch.cuda.current_stream(dev).cuda_stream)
+    launch(att.device, 'dfl_drr_render', a)
     del keep
     if not _views(objects)[1]:
         att, plen, lab = att[0], None if plen is None else plen[0], None if lab is None else lab[0]

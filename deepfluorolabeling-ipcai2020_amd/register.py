@@ -377,8 +377,9 @@ class Similarity:
         self.out = torch.empty(self.views, dtype=torch.float64, device=dev)
         a = nat.SimPrepareArgs(fixed=self.fixed.data_ptr(), mask=nat.ptr(self.mask), fx=self.fx.data_ptr(), fy=self.fy.data_ptr(),
                                counted=self.counted.data_ptr(), totals=self.totals.data_ptr(), H=H, W=W)
-        with torch.cuda.device(dev):
-            nat.call('dfl_sim_prepare', a, torch.cuda.current_stream(dev).cuda_stream)
+        drr.launch(dev, 'dfl_sim_prepare', a)
+
+    entry = 'dfl_sim_gradncc'                                       # what launch() calls with args()
 
     def args(self, moving, out=None):
         out = self.out if out is None else out
@@ -386,23 +387,27 @@ class Similarity:
                                   totals=self.totals.data_ptr(), scratch=self.scratch.data_ptr(), cost=out.data_ptr(),
                                   scratch_doubles=self.scratch.numel(), V=int(moving.shape[0]), H=self.H, W=self.W)
 
-    def cost(self, moving):
+    def _moving(self, moving):
         mv = _device_image(moving, 'the moving images', 3)
         if tuple(mv.shape[1:]) != (self.H, self.W) or mv.device != self.fixed.device or not 1 <= mv.shape[0] <= self.views:
             raise nat.DflError('register: moving images of shape %s on %s for a fixed image of %d x %d on %s and at most %d views'
                                % (tuple(mv.shape), mv.device, self.H, self.W, self.fixed.device, self.views))
+        return mv
+
+    def launch(self, moving, out=None):
+        """One launch of `entry` on checked moving images; the costs go to `out` (default: the first rows of self.out)."""
+        drr.launch(moving.device, self.entry, self.args(moving, out))
+
+    def cost(self, moving):
+        mv = self._moving(moving)
         out = torch.empty(mv.shape[0], dtype=torch.float64, device=mv.device)
-        with torch.cuda.device(mv.device):
-            nat.call('dfl_sim_gradncc', self.args(mv, out), torch.cuda.current_stream(mv.device).cuda_stream)
+        self.launch(mv, out)
         return out
 
     def cost_and_adjoint(self, moving):
         """(cost [V] float64, d_moving [V, H, W] float32 = d cost[v] / d moving[v]) on the device: one dfl_sim_gradncc_bwd
         launch.  The cost has the bits cost(moving) gives."""
-        mv = _device_image(moving, 'the moving images', 3)
-        if tuple(mv.shape[1:]) != (self.H, self.W) or mv.device != self.fixed.device or not 1 <= mv.shape[0] <= self.views:
-            raise nat.DflError('register: moving images of shape %s on %s for a fixed image of %d x %d on %s and at most %d views'
-                               % (tuple(mv.shape), mv.device, self.H, self.W, self.fixed.device, self.views))
+        mv = self._moving(moving)
         V, dev = int(mv.shape[0]), mv.device
         if getattr(self, 'bwd_scratch', None) is None:
             lib = nat.lib()
@@ -415,8 +420,7 @@ class Similarity:
         a = nat.SimGradnccBwdArgs(moving=mv.data_ptr(), fx=self.fx.data_ptr(), fy=self.fy.data_ptr(), counted=self.counted.data_ptr(),
                                   totals=self.totals.data_ptr(), scratch=self.bwd_scratch.data_ptr(), cost=out.data_ptr(),
                                   d_moving=d_moving.data_ptr(), scratch_doubles=self.bwd_scratch.numel(), V=V, H=self.H, W=self.W)
-        with torch.cuda.device(dev):
-            nat.call('dfl_sim_gradncc_bwd', a, torch.cuda.current_stream(dev).cuda_stream)
+        drr.launch(dev, 'dfl_sim_gradncc_bwd', a)
         return out, d_moving
 
 
@@ -454,8 +458,9 @@ class PatchSimilarity(Similarity):
         a = nat.SimPatchPrepareArgs(fx=self.fx.data_ptr(), fy=self.fy.data_ptr(), counted=self.counted.data_ptr(),
                                     ptotals=self.ptotals.data_ptr(), pflags=self.pflags.data_ptr(), pcount=self.pcount.data_ptr(),
                                     H=H, W=W, rho=self.radius, stride=self.stride, min_count=self.min_count)
-        with torch.cuda.device(dev):
-            nat.call('dfl_sim_patch_prepare', a, torch.cuda.current_stream(dev).cuda_stream)
+        drr.launch(dev, 'dfl_sim_patch_prepare', a)
+
+    entry = 'dfl_sim_patch_gradncc'
 
     def args(self, moving, out=None):
         out = self.out if out is None else out
@@ -464,16 +469,6 @@ class PatchSimilarity(Similarity):
                                        pcount=self.pcount.data_ptr(), scratch=self.pscratch.data_ptr(), cost=out.data_ptr(),
                                        scratch_doubles=self.pscratch.numel(), V=int(moving.shape[0]), H=self.H, W=self.W,
                                        rho=self.radius, stride=self.stride)
-
-    def cost(self, moving):
-        mv = _device_image(moving, 'the moving images', 3)
-        if tuple(mv.shape[1:]) != (self.H, self.W) or mv.device != self.fixed.device or not 1 <= mv.shape[0] <= self.views:
-            raise nat.DflError('register: moving images of shape %s on %s for a fixed image of %d x %d on %s and at most %d views'
-                               % (tuple(mv.shape), mv.device, self.H, self.W, self.fixed.device, self.views))
-        out = torch.empty(mv.shape[0], dtype=torch.float64, device=mv.device)
-        with torch.cuda.device(mv.device):
-            nat.call('dfl_sim_patch_gradncc', self.args(mv, out), torch.cuda.current_stream(mv.device).cuda_stream)
-        return out
 
     def cost_and_adjoint(self, moving):
         raise nat.DflError('register: the patch similarity has no adjoint kernel yet (DESIGN.md section 19 names it as next)')
@@ -531,29 +526,27 @@ class _Level:
         if tuple(fixed.shape) != (grid.H, grid.W):
             raise nat.DflError('register: the fixed image is %s, the output grid %d x %d' % (tuple(fixed.shape), grid.H, grid.W))
         self.sim = Similarity(fixed, mask, lam) if patch is None else PatchSimilarity(fixed, mask, lam, *patch)
-        self.entry = 'dfl_sim_gradncc' if patch is None else 'dfl_sim_patch_gradncc'
         self.step_mm = float(step_mm)
+
+    def _render(self, c2is, masks):
+        """(records, att [views, H, W], tensors to keep alive until the render ran): one trilinear render with tight boxes."""
+        recs = drr.pack(self.volume, c2is, masks, self.grid, 'trilinear', True)
+        a, (att, _, _), keep = drr.args_for_records(self.volume, recs, self.grid, 'trilinear', self.step_mm)
+        drr.launch(att.device, 'dfl_drr_render', a)
+        return recs, att, keep
 
     def costs(self, c2is, masks):
         """[views <= lambda, n_obj, 4, 4] -> float64 [views] on the host: one render, one similarity launch, one copy."""
-        recs = drr.pack(self.volume, c2is, masks, self.grid, 'trilinear', True)
-        a, (att, _, _), keep = drr.args_for_records(self.volume, recs, self.grid, 'trilinear', self.step_mm)
-        V, dev = recs.shape[0], att.device
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            nat.call('dfl_drr_render', a, stream)
-            nat.call(self.entry, self.sim.args(att), stream)
-        return self.sim.out[:V].cpu().numpy()                       # the copy waits for both launches: `keep` lives until then
+        recs, att, keep = self._render(c2is, masks)
+        self.sim.launch(att)
+        return self.sim.out[:recs.shape[0]].cpu().numpy()           # the copy waits for both launches: `keep` lives until then
 
     def costs_and_grads(self, c2is, masks, xis, moving):
         """[views <= lambda, n_obj, 4, 4], xis [views, 6, 4, 4] (the motion of the moving objects in index coordinates per
         unit of every parameter) -> (float64 [views], float64 [views, 6]) on the host: one render, one dfl_sim_gradncc_bwd,
         one dfl_drr_pose_grad, one copy; the chain from forces and moments to the parameters is float64 numpy."""
-        recs = drr.pack(self.volume, c2is, masks, self.grid, 'trilinear', True)
-        a, (att, _, _), keep = drr.args_for_records(self.volume, recs, self.grid, 'trilinear', self.step_mm)
-        V, dev = recs.shape[0], att.device
-        with torch.cuda.device(dev):
-            nat.call('dfl_drr_render', a, torch.cuda.current_stream(dev).cuda_stream)
+        recs, att, keep = self._render(c2is, masks)
+        V = recs.shape[0]
         cost, d_att = self.sim.cost_and_adjoint(att)
         piv = drr.box_pivots(recs)
         grad = drr.pose_gradient(self.volume, recs, self.grid, d_att, piv, self.step_mm)
@@ -649,6 +642,10 @@ def register(volume, geom, fixed, moving=(0, 1, 2), theta0=None, P0=None, levels
         def penalty(thetas):
             return landmark_penalty(geom, pose_deltas(thetas, ctr, rot_unit) @ P_pelvis[None], lands[0], lands[1], landmark_weight)
 
+    def costs_of(level, thetas):                                                # what the CMA-ES minimises
+        c = level.costs(c2is_of(thetas), masks)
+        return c if penalty is None else c + penalty(thetas)
+
     if levels is None:
         plan = [(None, int(generations), geom.grid, _device_image(fixed, 'the fixed image', 2))]
     else:
@@ -670,10 +667,7 @@ def register(volume, geom, fixed, moving=(0, 1, 2), theta0=None, P0=None, levels
     mean, sigma, trace, renders, done = theta0, float(sigma0), [], 0, []
     for k, (factor, gens, grid, img) in enumerate(plan):
         level = _Level(volume, grid, img, mask, lam, step_mm, patch)
-        if penalty is None:
-            res = cma_es(lambda th: level.costs(c2is_of(th), masks), mean, sigma, lam, gens, seed + k)
-        else:
-            res = cma_es(lambda th: level.costs(c2is_of(th), masks) + penalty(th), mean, sigma, lam, gens, seed + k)
+        res = cma_es(lambda th: costs_of(level, th), mean, sigma, lam, gens, seed + k)
         mean, sigma = res.mean, sigma * float(sigma_shrink)
         trace.extend(res.trace.tolist())
         renders += res.evaluations
