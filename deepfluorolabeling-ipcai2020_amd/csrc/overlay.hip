@@ -5,14 +5,10 @@
 // then one pass per output pixel whose blocks first combine the partials of their image.  Markers are a per-pixel gather
 // over the image's boxes staged in LDS (no scatter, no races).
 // Built with -ffp-contract=off: every product and sum is rounded on its own, as torch's CPU ops round them.
-#include "common.h"
+// The min / max record, the colour of a pixel, the ellipse test and the canvas are overlay.h's, shared with overlay_fullres.hip.
+#include "overlay.h"
 
 namespace dfl {
-
-constexpr int OVL_NB = 64;          // min / max slices per image (4 floats each: image min, max, heat min, max)
-static_assert(OVL_NB * 4 <= DFL_OVERLAY_SCRATCH_FLOATS, "overlay scratch");
-constexpr int OVL_PAD = 2;          // make_grid padding
-constexpr int OVL_NROW = 8;         // make_grid nrow
 
 __device__ __forceinline__ void ovl_block_minmax(float& mn, float& mx, float* red) {
   for (int o = 32; o > 0; o >>= 1) {
@@ -50,18 +46,9 @@ __global__ void __launch_bounds__(256) ovl_minmax_kernel(const dfl_overlay_args 
   }
   ovl_block_minmax(mn, mx, red[0]);
   ovl_block_minmax(hmn, hmx, red[1]);
-  if (threadIdx.x == 0) {
-    float* p = a.scratch + (int64_t)b * DFL_OVERLAY_SCRATCH_FLOATS + blockIdx.x * 4;
-    p[0] = mn;
-    p[1] = mx;
-    p[2] = hmn;
-    p[3] = hmx;
-  }
+  if (threadIdx.x == 0)
+    reinterpret_cast<OvlSlice*>(a.scratch + (int64_t)b * DFL_OVERLAY_SCRATCH_FLOATS)[blockIdx.x] = OvlSlice{mn, mx, hmn, hmx};
 }
-
-struct OvlBox {
-  int x0, y0, w, h, off;   // box corner, size (x1 - x0, y1 - y0), first row in stamp_spans
-};
 
 // Pillow's box: float coordinates truncated toward zero; clamped far outside int range (such a box is never drawn)
 template <typename T>
@@ -70,6 +57,7 @@ __device__ __forceinline__ int ovl_trunc(T v) {
   return (int)c;
 }
 
+// (the full-resolution overlays build their boxes on the host under another visibility rule: overlay.fullres_marks)
 template <typename T>
 __device__ __forceinline__ bool ovl_box(const T* c, T r, const dfl_overlay_args& a, OvlBox& bx) {
   const T x = c[0], y = c[1];
@@ -90,7 +78,9 @@ __device__ __forceinline__ bool ovl_box(const T* c, T r, const dfl_overlay_args&
 }
 
 // the padding of the grid canvas and its empty tiles: the pixels of three bands, numbered one after the other
-__device__ void ovl_zero_padding(const dfl_overlay_args& a, int xmaps, int ymaps, int64_t Wc) {
+__device__ void ovl_zero_padding(const dfl_overlay_args& a) {
+  const int xmaps = ovl_xmaps(a.B), ymaps = (a.B + xmaps - 1) / xmaps;
+  const int64_t Wc = ovl_canvas_ld(a.B, a.W);
   const int64_t th = a.H + OVL_PAD, tw = a.W + OVL_PAD;
   const int64_t nA = (int64_t)(ymaps + 1) * OVL_PAD * Wc;                  // full-width pad rows
   const int64_t perB = (int64_t)(xmaps + 1) * OVL_PAD;
@@ -127,30 +117,15 @@ __global__ void __launch_bounds__(256) ovl_render_kernel(const dfl_overlay_args 
   __shared__ int n_box, n_cross;
   const int b = blockIdx.y;
   const bool grid = a.grid != 0 && a.B > 1;
-  const int xmaps = a.B < OVL_NROW ? a.B : OVL_NROW, ymaps = (a.B + xmaps - 1) / xmaps;
-  const int64_t Wc = grid ? (int64_t)(a.W + OVL_PAD) * xmaps + OVL_PAD : a.W;
   if (b == a.B) {                                        // (block-uniform) the canvas padding
-    ovl_zero_padding(a, xmaps, ymaps, Wc);
+    ovl_zero_padding(a);
     return;
   }
-  // combine this image's min / max partials (one wave), stage its markers
-  if (threadIdx.x < 64) {
-    const float* p = a.scratch + (int64_t)b * DFL_OVERLAY_SCRATCH_FLOATS + threadIdx.x * 4;
-    float mn = p[0], mx = p[1], hmn = p[2], hmx = p[3];
-    for (int o = 32; o > 0; o >>= 1) {
-      mn = fminf(mn, __shfl_xor(mn, o, 64));
-      mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-      hmn = fminf(hmn, __shfl_xor(hmn, o, 64));
-      hmx = fmaxf(hmx, __shfl_xor(hmx, o, 64));
-    }
-    if (threadIdx.x == 0) {
-      red[0] = mn;
-      red[1] = mx;
-      red[2] = hmn;
-      red[3] = hmx;
-      n_box = 0;
-      n_cross = 0;
-    }
+  // combine this image's min / max slices (one wave), stage its markers
+  if (threadIdx.x < 64) ovl_combine(a.scratch, b, red);
+  if (threadIdx.x == 0) {
+    n_box = 0;
+    n_cross = 0;
   }
   __syncthreads();
   for (int l = threadIdx.x; l < a.n_gt; l += 256) {
@@ -175,28 +150,13 @@ __global__ void __launch_bounds__(256) ovl_render_kernel(const dfl_overlay_args 
   const float* img = a.image + (int64_t)b * a.H * a.ld_image;
   const unsigned char* lab = a.labels != nullptr ? a.labels + (int64_t)b * a.H * a.ld_labels : nullptr;
   const float* heat = a.heat != nullptr ? a.heat + (int64_t)b * a.H * a.ld_heat : nullptr;
-  int64_t obase;                                         // output offset of the image's pixel (0, 0), in pixels
-  if (grid)
-    obase = ((int64_t)(b / xmaps) * (a.H + OVL_PAD) + OVL_PAD) * Wc + (int64_t)(b % xmaps) * (a.W + OVL_PAD) + OVL_PAD;
-  else
-    obase = (int64_t)b * hw;
+  const int64_t Wc = grid ? ovl_canvas_ld(a.B, a.W) : a.W;
+  const int64_t obase = grid ? ovl_tile_origin(b, a.B, a.H, a.W) : (int64_t)b * hw;   // the image's pixel (0, 0) in the output
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < hw; i += (int64_t)gridDim.x * 256) {
     const int y = (int)(i / a.W), x = (int)(i - (int64_t)y * a.W);
-    int g = 0;
-    if (d != 0.f) {                                      // max == min: the grey level is 0
-      const float t = (img[(int64_t)y * a.ld_image + x] - mn) / d;
-      g = (int)(t * 255.f);
-    }
-    const float v = (float)g / 255.f;
+    const float v = ovl_grey(img[(int64_t)y * a.ld_image + x], mn, d);
     float v0 = v, v1 = v, v2 = v;
-    if (lab != nullptr) {
-      const int l = lab[(int64_t)y * a.ld_labels + x];
-      if (l >= 1 && l <= a.n_tint) {
-        v0 = a.tint_scale * v0 + a.tint_add[l - 1][0];
-        v1 = a.tint_scale * v1 + a.tint_add[l - 1][1];
-        v2 = a.tint_scale * v2 + a.tint_add[l - 1][2];
-      }
-    }
+    if (lab != nullptr) ovl_tint(v0, v1, v2, lab[(int64_t)y * a.ld_labels + x], a.n_tint, a.tint_scale, a.tint_add);
     if (heat != nullptr) {
       float h = heat[(int64_t)y * a.ld_heat + x] - hmn;
       if (hdiv) h = h / hd;
@@ -205,23 +165,8 @@ __global__ void __launch_bounds__(256) ovl_render_kernel(const dfl_overlay_args 
       v1 = k * v1 + h * a.heat_color[1];
       v2 = k * v2 + h * a.heat_color[2];
     }
-    float q0 = v0 * 255.f, q1 = v1 * 255.f, q2 = v2 * 255.f;
-    if (a.quant == DFL_OVERLAY_ROUND) {
-      q0 = q0 + 0.5f;
-      q1 = q1 + 0.5f;
-      q2 = q2 + 0.5f;
-    }
-    unsigned r0 = (unsigned)fminf(fmaxf(q0, 0.f), 255.f), r1 = (unsigned)fminf(fmaxf(q1, 0.f), 255.f),
-             r2 = (unsigned)fminf(fmaxf(q2, 0.f), 255.f);
-    bool mark = false;
-    for (int k = 0; k < nb && !mark; ++k) {
-      const OvlBox bx = boxes[k];
-      const unsigned dx = (unsigned)(x - bx.x0), dy = (unsigned)(y - bx.y0);
-      if (dx <= (unsigned)bx.w && dy <= (unsigned)bx.h) {
-        const int s = a.stamp_spans[bx.off + (int)dy];
-        mark = (int)dx >= (s & 0xffff) && (int)dx <= (s >> 16);
-      }
-    }
+    uint32_t r0 = ovl_quant(v0, a.quant), r1 = ovl_quant(v1, a.quant), r2 = ovl_quant(v2, a.quant);
+    bool mark = ovl_in_stamps(boxes, nb, a.stamp_spans, x, y);
     for (int k = 0; k < nc && !mark; ++k) {
       const int2 c = crosses[k];
       mark = (x == c.x && abs(y - c.y) <= a.cross) || (y == c.y && abs(x - c.x) <= a.cross);
@@ -238,8 +183,6 @@ __global__ void __launch_bounds__(256) ovl_render_kernel(const dfl_overlay_args 
   }
 }
 
-// phase 1 alone, for the full-resolution overlays (overlay_fullres.hip): per-image min / max partials of a.image into
-// a.scratch (OVL_NB slices of 4 floats per image)
 void ovl_launch_minmax(const dfl_overlay_args& a, hipStream_t s) {
   hipLaunchKernelGGL(ovl_minmax_kernel, dim3(OVL_NB, a.B), dim3(256), 0, s, a);
 }
@@ -262,7 +205,7 @@ extern "C" int dfl_overlay_batch(const dfl_overlay_args* a, dfl_stream_t stream)
   DFL_REQUIRE(a->n_est == 0 || (a->est_lands != nullptr && a->cross >= 0), "dfl_overlay_batch: crosses need centres and cross >= 0");
   DFL_REQUIRE(a->quant == DFL_OVERLAY_ROUND || a->quant == DFL_OVERLAY_TRUNC, "dfl_overlay_batch: bad quant");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(dfl::ovl_minmax_kernel, dim3(dfl::OVL_NB, a->B), dim3(256), 0, s, *a);
+  dfl::ovl_launch_minmax(*a, s);
   const int64_t hw = (int64_t)a->H * a->W;
   int64_t gx = dfl::ceil_div(hw, 256);
   const int64_t cap = 8192 / a->B > 4 ? 8192 / a->B : 4;

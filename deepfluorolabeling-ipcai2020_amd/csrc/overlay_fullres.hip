@@ -9,12 +9,11 @@
 // the overlay -- then reduced horizontally into a per-tile column buffer in LDS; the vertical pass reads that buffer.
 // The full-resolution RGB image never reaches HBM; the rows shared by vertically adjacent tiles are computed twice.
 // Built with -ffp-contract=off: the grey level and the tint round every product and sum as torch's CPU ops do.
-#include "common.h"
+// The pixel before the text is overlay.h's, shared with overlay.hip: grey level, tint, the TRUNC quantisation, ellipses.
+#include "overlay.h"
 
 namespace dfl {
 
-void ovl_launch_minmax(const dfl_overlay_args& a, hipStream_t s);
-constexpr int FR_NB = 64;           // min / max partials per image written by ovl_launch_minmax (overlay.hip: OVL_NB)
 constexpr int RS_TR = DFL_RESAMPLE_TILE_ROWS, RS_TW = DFL_RESAMPLE_TILE_COLS;
 constexpr int RS_THREADS = 256;
 constexpr int RS_RPI = RS_THREADS / RS_TW;   // input rows produced per step: one horizontal output per thread
@@ -137,17 +136,13 @@ __global__ void __launch_bounds__(RS_THREADS) rs_u8_kernel(const dfl_resample_ar
   rs_tile(a.plan, sp, src, a.out + (int64_t)b * a.plan.h_out * a.plan.w_out * 3, a.plan.w_out, lds);
 }
 
-struct FrBox {
-  int x0, y0, w, h, off;   // ellipse box corner and size (x1 - x0, y1 - y0), first row in stamp_spans
-};
-
 struct FrSrc {
   const float* img;
   const unsigned char* lab;
   const int32_t* spans;
   const unsigned char* masks;
-  const FrBox* boxes;      // LDS
-  const FrBox* texts;      // LDS: x, y, w, h, first byte
+  const OvlBox* boxes;     // LDS
+  const OvlBox* texts;     // LDS: x, y, w, h, first byte
   const float (*tint_add)[3];
   int H, W, rot, nb, nt, n_tint;
   float mn, d, ts;
@@ -155,37 +150,17 @@ struct FrSrc {
   __device__ uint32_t operator()(int y, int x) const {
     const int sy = rot ? H - 1 - y : y, sx = rot ? W - 1 - x : x;
     const int64_t i = (int64_t)sy * W + sx;
-    int g = 0;
-    if (d != 0.f) {                                      // max == min: the grey level is 0
-      const float t = (img[i] - mn) / d;
-      g = (int)(t * 255.f);
-    }
-    const float v = (float)g / 255.f;
+    const float v = ovl_grey(img[i], mn, d);
     float v0 = v, v1 = v, v2 = v;
-    const int l = lab[i];
-    if (l >= 1 && l <= n_tint) {
-      v0 = ts * v0 + tint_add[l - 1][0];
-      v1 = ts * v1 + tint_add[l - 1][1];
-      v2 = ts * v2 + tint_add[l - 1][2];
-    }
-    uint32_t r0 = (uint32_t)fminf(fmaxf(v0 * 255.f, 0.f), 255.f), r1 = (uint32_t)fminf(fmaxf(v1 * 255.f, 0.f), 255.f),
-             r2 = (uint32_t)fminf(fmaxf(v2 * 255.f, 0.f), 255.f);
-    bool mark = false;
-    for (int k = 0; k < nb && !mark; ++k) {
-      const FrBox bx = boxes[k];
-      const unsigned dx = (unsigned)(x - bx.x0), dy = (unsigned)(y - bx.y0);
-      if (dx <= (unsigned)bx.w && dy <= (unsigned)bx.h) {
-        const int s = spans[bx.off + (int)dy];
-        mark = (int)dx >= (s & 0xffff) && (int)dx <= (s >> 16);
-      }
-    }
-    if (mark) {
+    ovl_tint(v0, v1, v2, lab[i], n_tint, ts, tint_add);
+    uint32_t r0 = ovl_quant(v0, DFL_OVERLAY_TRUNC), r1 = ovl_quant(v1, DFL_OVERLAY_TRUNC), r2 = ovl_quant(v2, DFL_OVERLAY_TRUNC);
+    if (ovl_in_stamps(boxes, nb, spans, x, y)) {
       r0 = 255u;
       r1 = 255u;
       r2 = 0u;
     }
     for (int k = 0; k < nt; ++k) {
-      const FrBox t = texts[k];
+      const OvlBox t = texts[k];
       const unsigned dx = (unsigned)(x - t.x0), dy = (unsigned)(y - t.y0);
       if (dx < (unsigned)t.w && dy < (unsigned)t.h) {
         const uint32_t m = masks[t.off + (int)dy * t.w + (int)dx], ink = 255u * m + 128u;
@@ -206,40 +181,26 @@ struct FrSrc {
 __global__ void __launch_bounds__(RS_THREADS) fr_render_kernel(const dfl_fullres_args a) {
   extern __shared__ uint32_t lds[];
   __shared__ RsSpan sp;
-  __shared__ float red[2];
-  __shared__ FrBox boxes[DFL_FULLRES_MAX_BOXES];
-  __shared__ FrBox texts[DFL_FULLRES_MAX_TEXTS];
+  __shared__ float red[4];                               // image min, max (and the heat pair, which nobody reads here)
+  __shared__ OvlBox boxes[DFL_FULLRES_MAX_BOXES];
+  __shared__ OvlBox texts[DFL_FULLRES_MAX_TEXTS];
   __shared__ int n_box, n_text;
   const int b = blockIdx.z;
   rs_span(a.plan, sp);
   if (!sp.ok) return;
-  if (threadIdx.x < 64) {                                // combine this image's min / max partials (one wave)
-    float mn = INFINITY, mx = -INFINITY;
-    if (threadIdx.x < FR_NB) {
-      const float* p = a.scratch + (int64_t)b * DFL_OVERLAY_SCRATCH_FLOATS + threadIdx.x * 4;
-      mn = p[0];
-      mx = p[1];
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-      mn = fminf(mn, __shfl_xor(mn, o, 64));
-      mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    }
-    if (threadIdx.x == 0) {
-      red[0] = mn;
-      red[1] = mx;
-      n_box = 0;
-      n_text = 0;
-      for (int k = 0; k < DFL_FULLRES_MAX_TEXTS; ++k) {  // in order: later text blends over earlier text
-        const int32_t* t = a.texts + ((int64_t)b * DFL_FULLRES_MAX_TEXTS + k) * 3;
-        const int id = t[2];
-        if (id < 0 || id >= a.n_text_stamps) continue;
-        const int32_t* st = a.text_stamps + id * 3;
-        FrBox tx{t[0], t[1], st[0], st[1], st[2]};
-        if (tx.w <= 0 || tx.h <= 0 || tx.x0 >= sp.cx1 || tx.y0 >= sp.ry1 || tx.x0 + tx.w <= sp.cx0 ||
-            tx.y0 + tx.h <= sp.ry0)
-          continue;
-        texts[n_text++] = tx;
-      }
+  if (threadIdx.x < 64) ovl_combine(a.scratch, b, red);  // this image's min / max slices (one wave)
+  if (threadIdx.x == 0) {
+    n_box = 0;
+    n_text = 0;
+    for (int k = 0; k < DFL_FULLRES_MAX_TEXTS; ++k) {    // in order: later text blends over earlier text
+      const int32_t* t = a.texts + ((int64_t)b * DFL_FULLRES_MAX_TEXTS + k) * 3;
+      const int id = t[2];
+      if (id < 0 || id >= a.n_text_stamps) continue;
+      const int32_t* st = a.text_stamps + id * 3;
+      OvlBox tx{t[0], t[1], st[0], st[1], st[2]};
+      if (tx.w <= 0 || tx.h <= 0 || tx.x0 >= sp.cx1 || tx.y0 >= sp.ry1 || tx.x0 + tx.w <= sp.cx0 || tx.y0 + tx.h <= sp.ry0)
+        continue;
+      texts[n_text++] = tx;
     }
   }
   __syncthreads();
@@ -247,7 +208,7 @@ __global__ void __launch_bounds__(RS_THREADS) fr_render_kernel(const dfl_fullres
   const int nbx = min(max(a.n_boxes[b], 0), DFL_FULLRES_MAX_BOXES);
   for (int k = threadIdx.x; k < nbx; k += RS_THREADS) {
     const int32_t* p = a.boxes + ((int64_t)b * DFL_FULLRES_MAX_BOXES + k) * 5;
-    const FrBox bx{p[0], p[1], p[2], p[3], p[4]};
+    const OvlBox bx{p[0], p[1], p[2], p[3], p[4]};
     if (bx.w < 0 || bx.h < 0 || bx.off < 0 || bx.off + bx.h >= a.n_stamp_spans) continue;
     if (bx.x0 >= sp.cx1 || bx.y0 >= sp.ry1 || bx.x0 + bx.w < sp.cx0 || bx.y0 + bx.h < sp.ry0) continue;
     boxes[atomicAdd(&n_box, 1)] = bx;
@@ -272,12 +233,8 @@ __global__ void __launch_bounds__(RS_THREADS) fr_render_kernel(const dfl_fullres
   src.ts = a.tint_scale;
   // tile (tile0 + b) of the make_grid canvas
   const int k = a.tile0 + b, ho = a.plan.h_out, wo = a.plan.w_out;
-  int64_t ld = wo, base = 0;
-  if (a.n_tiles > 1) {
-    const int xmaps = a.n_tiles < 8 ? a.n_tiles : 8;
-    ld = (int64_t)(wo + 2) * xmaps + 2;
-    base = ((int64_t)(k / xmaps) * (ho + 2) + 2) * ld + (int64_t)(k % xmaps) * (wo + 2) + 2;
-  }
+  const bool grid = a.n_tiles > 1;                       // a single image is the canvas
+  const int64_t ld = grid ? ovl_canvas_ld(a.n_tiles, wo) : wo, base = grid ? ovl_tile_origin(k, a.n_tiles, ho, wo) : 0;
   rs_tile(a.plan, sp, src, a.out + base * 3, ld, lds);
 }
 

@@ -23,6 +23,7 @@ ANN_COLORS = ((0.0, 1.0, 0.0),   # pelvis green       (overlay_est_ann.py label_
               (1.0, 0.5, 0.0),   # orange
               (0.5, 0.0, 0.5))   # purple
 HEAT_COLOR = (0.0, 1.0, 0.0)     # overlay_est_heat.py heat_base_color
+NROW, PADDING = 8, 2             # make_grid's nrow and padding, as the kernels have them (csrc/overlay.h: OVL_NROW, OVL_PAD)
 STAMPS_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'data', 'ellipse_stamps.txt')
 
 _stamps_host = None
@@ -75,7 +76,7 @@ def check_radius(radius):
         raise nat.DflError('overlay: radius %g needs ellipse boxes outside the stamp table, e.g. %r' % (radius, missing[0]))
 
 
-def grid_shape(B, H, W, nrow=8, padding=2):
+def grid_shape(B, H, W, nrow=NROW, padding=PADDING):
     """Canvas [rows, cols] of torchvision's make_grid (a single image is returned unchanged)."""
     if B == 1:
         return H, W
@@ -92,6 +93,41 @@ def _batch(t, name, dims):
     return t
 
 
+def _images(images, who, dtypes=None, channel=False):
+    """overlay.<who>'s images, on the GPU (of one of dtypes if given), as fp32 [B,H,W]; channel: [B,1,H,W] is [B,H,W]."""
+    if not torch.is_tensor(images) or not images.is_cuda:
+        raise nat.DflError('overlay.%s needs the images on the GPU (no CPU path)' % who)
+    if dtypes is not None and images.dtype not in dtypes:
+        raise nat.DflError('overlay.%s: image pixels must be float32 or float64, got %s' % (who, images.dtype))
+    img = images.detach()
+    if channel and img.dim() == 4 and img.shape[1] == 1:
+        img = img[:, 0]
+    return _batch(img, 'images', 3).to(torch.float32).contiguous()
+
+
+def _on_dev(t, who, name, img, dtype, per_pixel=True):
+    """overlay.<who>'s tensor `name` as a contiguous batch of dtype on the images' device; per_pixel: at their shape."""
+    if not torch.is_tensor(t) or t.device != img.device:
+        raise nat.DflError('overlay.%s: %s must be a tensor on %s' % (who, name, img.device))
+    t = _batch(t.detach(), name, 3)
+    if per_pixel and t.shape != img.shape:
+        raise nat.DflError('overlay.%s: %s has shape %s, images %s' % (who, name, tuple(t.shape), tuple(img.shape)))
+    if dtype == torch.uint8 and t.dtype != torch.uint8:
+        t = t.clamp(0, 255)                         # labels past 255 stay untinted
+    return t.to(dtype).contiguous()
+
+
+def _fill_tint(a, colors):
+    for l, col in enumerate(colors):
+        for c in range(3):
+            a.tint_add[l][c] = ALPHA * col[c]       # rounded to fp32, as torch does with a Python-float operand
+
+
+def _scratch(img):
+    """The min / max record both entry points write before they render: OVERLAY_SCRATCH_FLOATS per image."""
+    return torch.empty(img.shape[0] * nat.OVERLAY_SCRATCH_FLOATS, dtype=torch.float32, device=img.device)
+
+
 def render(images, segs=None, num_classes=7, heats=None, gt_lands=None, radius=2, est_lands=None, cross=6,
            colors=ANN_COLORS, grid=False, heat_color=HEAT_COLOR):
     """uint8 RGB overlays of a batch, on the images' GPU.
@@ -102,47 +138,26 @@ def render(images, segs=None, num_classes=7, heats=None, gt_lands=None, radius=2
     centres of +-cross crosses (negative = none).  Passing either marker tensor, even an empty one, selects the
     quantisation of the reference's marker path (truncation); otherwise save_image's rounding.
     Returns [B,H,W,3], or with grid=True the make_grid(nrow=8, padding=2) canvas [rows, cols, 3]."""
-    if not torch.is_tensor(images) or not images.is_cuda:
-        raise nat.DflError('overlay.render needs the images on the GPU (no CPU path)')
-    dev = images.device
-    img = images.detach()
-    if img.dim() == 4 and img.shape[1] == 1:
-        img = img[:, 0]
-    img = _batch(img, 'images', 3).to(torch.float32).contiguous()
+    img = _images(images, 'render', channel=True)
+    dev = img.device
     B, H, W = img.shape
     if len(colors) > nat.OVERLAY_MAX_COLORS:
         raise nat.DflError('overlay.render: at most %d colours' % nat.OVERLAY_MAX_COLORS)
     a = nat.OverlayArgs(image=img.data_ptr(), B=B, H=H, W=W, ld_image=W, tint_scale=1 - ALPHA, radius=float(radius),
                         cross=int(cross), grid=int(bool(grid)))
-    keep = [img]
-
-    def on_dev(t, name, dtype, per_pixel):
-        if not torch.is_tensor(t) or t.device != dev:
-            raise nat.DflError('overlay.render: %s must be a tensor on %s' % (name, dev))
-        t = _batch(t.detach(), name, 3)
-        if per_pixel and tuple(t.shape) != (B, H, W):
-            raise nat.DflError('overlay.render: %s has shape %s, images %s' % (name, tuple(t.shape), (B, H, W)))
-        if dtype == torch.uint8 and t.dtype != torch.uint8:
-            t = t.clamp(0, 255)                     # labels past 255 stay untinted
-        t = t.to(dtype).contiguous()
-        keep.append(t)
-        return t
-
     if segs is not None:
-        s = on_dev(segs, 'segs', torch.uint8, True)
+        s = _on_dev(segs, 'render', 'segs', img, torch.uint8)
         a.labels, a.ld_labels = s.data_ptr(), W
         a.n_tint = max(0, min(int(num_classes) - 1, len(colors)))
-        for l, col in enumerate(colors):
-            for c in range(3):
-                a.tint_add[l][c] = ALPHA * col[c]      # rounded to fp32, as torch does with a Python-float operand
+        _fill_tint(a, colors)
     if heats is not None:
-        h = on_dev(heats, 'heats', torch.float32, True)
+        h = _on_dev(heats, 'render', 'heats', img, torch.float32)
         a.heat, a.ld_heat = h.data_ptr(), W
         for c in range(3):
             a.heat_color[c] = heat_color[c]
     if gt_lands is not None:
         dt = torch.float64 if gt_lands.dtype == torch.float64 else torch.float32
-        g = on_dev(gt_lands, 'gt_lands', dt, False)
+        g = _on_dev(gt_lands, 'render', 'gt_lands', img, dt, per_pixel=False)
         if g.shape[0] != B or g.shape[2] != 2 or g.shape[1] > nat.OVERLAY_MAX_MARKERS:
             raise nat.DflError('overlay.render: gt_lands must be [B, L <= %d, 2], got %s' % (nat.OVERLAY_MAX_MARKERS, tuple(g.shape)))
         if g.shape[1] > 0:
@@ -151,7 +166,7 @@ def render(images, segs=None, num_classes=7, heats=None, gt_lands=None, radius=2
             a.gt_lands, a.n_gt, a.gt_f64 = g.data_ptr(), g.shape[1], int(dt == torch.float64)
             a.stamp_index, a.stamp_spans = idx.data_ptr(), spans.data_ptr()
     if est_lands is not None:
-        e = on_dev(est_lands, 'est_lands', torch.int32, False)
+        e = _on_dev(est_lands, 'render', 'est_lands', img, torch.int32, per_pixel=False)
         if e.shape[0] != B or e.shape[2] != 2 or e.shape[1] > nat.OVERLAY_MAX_MARKERS:
             raise nat.DflError('overlay.render: est_lands must be [B, L <= %d, 2], got %s' % (nat.OVERLAY_MAX_MARKERS, tuple(e.shape)))
         if e.shape[1] > 0:
@@ -163,9 +178,8 @@ def render(images, segs=None, num_classes=7, heats=None, gt_lands=None, radius=2
         out = torch.empty(grid_shape(B, H, W) + (3,), dtype=torch.uint8, device=dev)
     else:
         out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
-    scratch = torch.empty(B * nat.OVERLAY_SCRATCH_FLOATS, dtype=torch.float32, device=dev)
+    scratch = _scratch(img)
     a.out, a.scratch = out.data_ptr(), scratch.data_ptr()
-    keep += [scratch]
     nat.call('dfl_overlay_batch', a, torch.cuda.current_stream(dev).cuda_stream)
     return out
 
@@ -377,7 +391,7 @@ def fullres_marks(lands, rot180, fov, H, W, radius=FULLRES_RADIUS):
     for x, y in vis:
         if not (math.isfinite(x) and math.isfinite(y)):
             continue
-        x0, y0, x1, y1 = (int(v) for v in (x - r, y - r, x + r, y + r))      # fp32 box, truncated as Pillow does
+        x0, y0, x1, y1 = (int(v) for v in (x - r, y - r, x + r, y + r))      # fp32, truncated as Pillow does (render's rule: ovl_box, overlay.hip)
         if x1 < 0 or y1 < 0 or x0 >= W or y0 >= H:
             continue
         w, h = x1 - x0, y1 - y0
@@ -405,22 +419,10 @@ def render_full_res(images, segs, rot180, lands, fov, size=None, canvas=None, ti
     tile0 .. tile0 + B - 1 of a make_grid(nrow=8, padding=2) canvas of n_tiles (default B) images; pass the canvas of
     an earlier call to add to it.  Returns the canvas [rows, cols, 3] uint8 (the reduced image itself when n_tiles
     == 1)."""
-    if not torch.is_tensor(images) or not images.is_cuda:
-        raise nat.DflError('overlay.render_full_res needs the images on the GPU (no CPU path)')
-    if images.dtype not in (torch.float32, torch.float64):
-        raise nat.DflError('overlay.render_full_res: image pixels must be float32 or float64, got %s' % images.dtype)
-    dev = images.device
-    img = images.detach()
-    img = _batch(img, 'images', 3).to(torch.float32).contiguous()
+    img = _images(images, 'render_full_res', dtypes=(torch.float32, torch.float64))
+    dev = img.device
     B, H, W = img.shape
-    if not torch.is_tensor(segs) or segs.device != dev:
-        raise nat.DflError('overlay.render_full_res: segs must be a tensor on %s' % dev)
-    seg = _batch(segs.detach(), 'segs', 3)
-    if tuple(seg.shape) != (B, H, W):
-        raise nat.DflError('overlay.render_full_res: segs has shape %s, images %s' % (tuple(seg.shape), (B, H, W)))
-    if seg.dtype != torch.uint8:
-        seg = seg.clamp(0, 255)
-    seg = seg.to(torch.uint8).contiguous()
+    seg = _on_dev(segs, 'render_full_res', 'segs', img, torch.uint8)
     if len(rot180) != B or len(lands) != B or len(fov) != B:
         raise nat.DflError('overlay.render_full_res: rot180, lands and fov need one entry per image')
     check_radius(float(radius))
@@ -449,15 +451,13 @@ def render_full_res(images, segs, rot180, lands, fov, size=None, canvas=None, ti
     _, spans = _stamps_on(dev)
     tstamps, tmasks = _text_on(dev)
     plan, keep = _plan_on(dev, (H, W), (h, w))
-    scratch = torch.empty(B * nat.OVERLAY_SCRATCH_FLOATS, dtype=torch.float32, device=dev)
+    scratch = _scratch(img)
     a = nat.FullresArgs(image=img.data_ptr(), labels=seg.data_ptr(), rot180=rot_d.data_ptr(), boxes=boxes_d.data_ptr(),
                         n_boxes=nb_d.data_ptr(), texts=texts_d.data_ptr(), stamp_spans=spans.data_ptr(),
                         text_stamps=tstamps.data_ptr(), text_masks=tmasks.data_ptr(), scratch=scratch.data_ptr(),
                         out=canvas.data_ptr(), plan=plan, B=B, H=H, W=W, n_tint=len(FULLRES_COLORS),
                         tint_scale=1 - ALPHA, n_text_stamps=len(text_stamps().table), n_stamp_spans=int(spans.numel()),
                         tile0=int(tile0), n_tiles=n_tiles)
-    for l, col in enumerate(FULLRES_COLORS):
-        for c in range(3):
-            a.tint_add[l][c] = ALPHA * col[c]
+    _fill_tint(a, FULLRES_COLORS)
     nat.call('dfl_fullres_overlay', a, torch.cuda.current_stream(dev).cuda_stream)
     return canvas

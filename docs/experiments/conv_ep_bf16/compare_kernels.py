@@ -46,9 +46,11 @@ def kernels(path):
 
 def short(sym):
     """_ZN3dfl...12convq_kernelILi128ELi1E...EEvNS_5ConvPE -> convq_kernel<128,1,...>"""
-    m = re.search(r'\d+([a-z][a-z_]*_kernel)(I\S*)?', sym)      # every literal template argument, nested ones included
-    lits = re.findall(r'L[ib](\d+)E', m.group(2) or '')
-    return m.group(1) + ('<%s>' % ','.join(lits) if lits else '')
+    for m in re.finditer(r'(\d+)(?=([a-z][a-z0-9_]*_kernel)(I\S*)?)', sym):    # <length><name>: rs_u8_kernel has a digit of its own
+        if int(m.group(1)) == len(m.group(2)):
+            lits = re.findall(r'L[ib](\d+)E', m.group(3) or '')    # every literal template argument, nested ones included
+            return m.group(2) + ('<%s>' % ','.join(lits) if lits else '')
+    return sym
 
 
 def renamed(table, mapping, body=False):

@@ -1,7 +1,8 @@
 """dfl_fullres_overlay / dfl_resample_bilinear_u8 on the GPU: bit-identical to examples_dataset/make_full_res_overlays.py
 as restated with torch + Pillow 12.2 (tests/golden/fullres_*.npz, tools/gen_fullres_overlay_golden.py) -- Pillow's
 BILINEAR reduction alone, the L-mask blend of the text, text stamps at fractional / zero / negative starts, whole
-overlays and a 19-projection canvas drawn in chunks -- then examples/make_full_res_overlays.py end to end on an HDF5
+overlays and a 19-projection canvas drawn in chunks, the identity reduction against dfl_overlay_batch's canvas -- then
+examples/make_full_res_overlays.py end to end on an HDF5
 container in the full-resolution layout, and a 1536^2 x 16 batch (timing printed, not asserted)."""
 import glob
 import os
@@ -103,6 +104,39 @@ def test_text_blend_matches_pillow_for_every_coverage_and_background():
     got = out.cpu().numpy()
     exp = table[np.arange(H)[:, None], grey[None, :]]
     same(got, np.repeat(exp[..., None], 3, -1), 'blend')
+
+
+@pytest.mark.parametrize('rot', [False, True])
+def test_identity_reduction_equals_the_batch_overlay(rot):
+    """A resample of equal size is the identity for Pillow's coefficients, so without text render_full_res is the
+    grid=True canvas of render on the same inputs, byte for byte -- rotated: on the flipped images and labels and the
+    landmarks mirrored in fp32 as fullres_marks mirrors them.  9 images of 40 x 72: a full and a partial 64-column
+    tile, five row tiles, a second canvas row with seven empty cells; labels 0..7 (7 untinted on both sides); six
+    landmarks of radius 2, one within 1 px of the left edge, one within 1 px of the bottom edge, two 1.5 px apart."""
+    from dfl_amd import overlay
+    B, H, W, L = 9, 40, 72, 6
+    rng = np.random.default_rng(11)
+    images = rng.standard_normal((B, H, W)).astype(np.float32)
+    segs = rng.integers(0, 8, (B, H, W)).astype(np.uint8)
+    lands = np.stack([rng.uniform(0, W - 1, (B, L)), rng.uniform(0, H - 1, (B, L))], -1).astype(np.float32)
+    lands[:, 0, 0] = rng.uniform(0, 0.99, B)
+    lands[:, 1, 1] = H - 1 + rng.uniform(0.01, 0.99, B)
+    lands[:, 2] = np.stack([rng.uniform(10, 60, B), rng.uniform(10, 30, B)], -1)
+    lands[:, 3] = lands[:, 2] + np.float32([0.9, 1.2])                      # 1.5 px away
+    x, y = lands[..., 0], lands[..., 1]
+    assert (x >= 0).all() and (x < W).all() and (y >= 0).all() and (y < H).all()
+    assert (x[:, 0] < 1).all() and (y[:, 1] > H - 1).all() and sorted(set(segs.ravel().tolist())) == list(range(8))
+    img_d, seg_d = torch.from_numpy(images).cuda(), torch.from_numpy(segs).cuda()
+    got = overlay.render_full_res(img_d, seg_d, [rot] * B, [[('L%02d' % l, lands[b, l]) for l in range(L)] for b in range(B)],
+                                  [(0, 0)] * B, size=(H, W), radius=2)
+    if rot:
+        img_d, seg_d = torch.flip(img_d, (1, 2)), torch.flip(seg_d, (1, 2))
+        lands = np.stack([np.float32(W - 1) - x, np.float32(H - 1) - y], -1)
+    want = overlay.render(img_d, segs=seg_d, gt_lands=torch.from_numpy(lands).cuda(), radius=2, grid=True)
+    assert want.shape == overlay.grid_shape(B, H, W) + (3,)
+    yellow = torch.tensor([255, 255, 0], dtype=torch.uint8, device='cuda')
+    assert int((want == yellow).all(-1).sum()) > B * L * 5                  # the ellipses are there
+    same(got.cpu().numpy(), want.cpu().numpy(), 'rot180 %d' % rot)
 
 
 def write_container(path, specs, rows, cols, seed=5):
