@@ -87,6 +87,7 @@ extern "C" int dfl_sizeof(int which) {
       (int)sizeof(dfl_restore_labels_args), (int)sizeof(dfl_sim_prepare_args),  (int)sizeof(dfl_sim_gradncc_args),
       (int)sizeof(dfl_expose_args),     (int)sizeof(dfl_sim_patch_prepare_args), (int)sizeof(dfl_sim_patch_gradncc_args),
       (int)sizeof(dfl_sim_gradncc_bwd_args), (int)sizeof(dfl_drr_pose_grad_args),
+      (int)sizeof(dfl_sim_bank_gradncc_args), (int)sizeof(dfl_sim_bank_gradncc_bwd_args), (int)sizeof(dfl_sim_patch_bank_gradncc_args),
       (int)sizeof(dfl_drr_object),     (int)sizeof(dfl_drr_args),
       (int)sizeof(dfl_optim_pack_args)};
   if (which < 0 || which >= (int)(sizeof(sizes) / sizeof(sizes[0]))) return -1;

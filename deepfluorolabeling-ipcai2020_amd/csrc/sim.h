@@ -1,6 +1,6 @@
 // What csrc/sim.hip (global gradient-NCC) and csrc/sim_patch.hip (patch-wise gradient-NCC) share: the Sobel gradients, the
-// five fixed and the six moving sums of a counted pixel, the NCC of one-pass sums with its variance rule and the checks
-// on sizes; the fixed-order sums of a workgroup are csrc/fixed_sum.h.  One definition, so that both files give the same bits.
+// five fixed and the six moving sums of a counted pixel, the NCC of one-pass sums with its variance rule, the checks
+// on sizes and which image of a bank a view belongs to; the fixed-order sums of a workgroup are csrc/fixed_sum.h.  One definition, so that both files give the same bits.
 #pragma once
 #include "fixed_sum.h"
 
@@ -16,6 +16,22 @@ inline int sim_sizes_ok(const char* who, int V, int H, int W) {
   DFL_REQUIRE((int64_t)H * W < ((int64_t)1 << 31), "%s: an image of %d x %d is too large", who, H, W);
   DFL_REQUIRE(V >= 1 && V <= 65535, "%s: 1..65535 views per call, got %d", who, V);
   return DFL_OK;
+}
+
+// ... and of a bank of F fixed images (the *_bank_* entry points)
+inline int sim_bank_ok(const char* who, const void* fixed_of, int F, int H, int W) {
+  DFL_REQUIRE(fixed_of != nullptr, "%s: fixed_of is required", who);
+  DFL_REQUIRE(F >= 1 && F <= 65535, "%s: a bank of 1..65535 fixed images, got %d", who, F);
+  DFL_REQUIRE((int64_t)F * H * W < ((int64_t)1 << 31), "%s: a bank of %d images of %d x %d is too large (2^31 pixels or more)", who, F, H, W);
+  return DFL_OK;
+}
+
+// Which fixed image a view is scored against: 0 for the single-image entry points (fixed_of == nullptr), fixed_of[view] for
+// a bank of F images, and -1 when that is outside [0, F): such a view reads nothing from the banks
+__device__ __forceinline__ int sim_image_of(const int32_t* __restrict__ fixed_of, int view, int F) {
+  if (fixed_of == nullptr) return 0;
+  const int f = fixed_of[view];
+  return f >= 0 && f < F ? f : -1;
 }
 
 // Sobel gradients of a 3 x 3 window (a b c / d . f / g h i): each sum left to right, so the fixed and the moving image share bits

@@ -11,6 +11,9 @@
 // doubles per workgroup with plain stores; sim_finish_kernel adds a view's records in index order and writes its cost
 // (csrc/fixed_sum.h: block_sum, records_sum).  The sums of a pixel, Sobel and the NCC are csrc/sim.h's.
 // No atomics: the bits of a view's cost depend on that view's pixels and on H and W only.
+// The *_bank_* entry points launch the same kernels with fixed_of [V] and F: view v then reads the
+// planes and totals of image fixed_of[v] of a bank (sim_image_of, csrc/sim.h); the single-image entry points pass
+// fixed_of = nullptr and every view reads image 0.
 #include "sim.h"
 
 namespace dfl {
@@ -53,15 +56,22 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_prepare_kernel(const float* _
 
 __global__ __launch_bounds__(SIM_THREADS) void sim_gradncc_kernel(const float* __restrict__ moving, const float* __restrict__ fx,
                                                                   const float* __restrict__ fy, const unsigned char* __restrict__ counted,
-                                                                  double* __restrict__ scratch, int H, int W) {
+                                                                  const int32_t* __restrict__ fixed_of, double* __restrict__ scratch,
+                                                                  int H, int W, int F) {
   __shared__ double lds[SIM_MOVING * 4];
   const int band = blockIdx.x, view = blockIdx.y;
+  const int f = sim_image_of(fixed_of, view, F);
+  const size_t plane = f < 0 ? 0 : (size_t)f * H * W;                   // f < 0: the loop below has no pixel
+  fx += plane;
+  fy += plane;
+  counted += plane;
   const int r0 = 1 + band * SIM_ROWS;                                   // first interior row of the band
   const int rows = min(SIM_ROWS, H - 1 - r0);                           // interior rows are 1 .. H - 2
   const int wi = W - 2;
   const float* img = moving + (size_t)view * H * W;
   double s[SIM_MOVING] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int p = threadIdx.x; p < rows * wi; p += SIM_THREADS) {
+  const int pixels = f < 0 ? 0 : rows * wi;
+  for (int p = threadIdx.x; p < pixels; p += SIM_THREADS) {
     const int r = r0 + p / wi, c = 1 + p % wi;
     if (counted[(size_t)r * W + c]) sim_moving_sums(s, img, fx, fy, W, r, c);
   }
@@ -75,9 +85,16 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_gradncc_kernel(const float* _
 
 // One wave per view: lanes 0..5 add one of the six sums each over the view's records, in index order
 __global__ __launch_bounds__(64) void sim_finish_kernel(const double* __restrict__ scratch, const double* __restrict__ totals,
-                                                        double* __restrict__ cost, int bands) {
+                                                        const int32_t* __restrict__ fixed_of, double* __restrict__ cost, int bands,
+                                                        int F) {
   __shared__ double m[SIM_MOVING];
   const int view = blockIdx.x;
+  const int f = sim_image_of(fixed_of, view, F);
+  if (f < 0) {                                                          // the whole workgroup: no barrier is left waiting
+    if (threadIdx.x == 0) cost[view] = __builtin_nan("");
+    return;
+  }
+  totals += (size_t)f * SIM_FIXED;
   if (threadIdx.x < SIM_MOVING) m[threadIdx.x] = records_sum(scratch + (size_t)view * bands * SIM_MOVING + threadIdx.x, bands, SIM_MOVING);
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -99,9 +116,16 @@ constexpr int SIM_TILE = 16;         // the adjoint kernel's tile of output pixe
 
 // One thread per view: the view's records added in index order (as sim_finish_kernel adds them), the coefficients in float64
 __global__ __launch_bounds__(64) void sim_coef_kernel(const double* __restrict__ scratch, const double* __restrict__ totals,
-                                                      float* __restrict__ coef, int bands, int V) {
+                                                      const int32_t* __restrict__ fixed_of, float* __restrict__ coef, int bands, int V,
+                                                      int F) {
   const int view = blockIdx.x * 64 + threadIdx.x;
   if (view >= V) return;
+  const int f = sim_image_of(fixed_of, view, F);
+  if (f < 0) {                                                          // sim_adjoint_kernel writes zeros and reads none of these
+    for (int k = 0; k < SIM_COEF; ++k) coef[(size_t)view * SIM_COEF + k] = 0.f;
+    return;
+  }
+  totals += (size_t)f * SIM_FIXED;
   double m[SIM_MOVING];
 #pragma unroll
   for (int k = 0; k < SIM_MOVING; ++k) m[k] = records_sum(scratch + (size_t)view * bands * SIM_MOVING + k, bands, SIM_MOVING);
@@ -133,7 +157,8 @@ __global__ __launch_bounds__(64) void sim_coef_kernel(const double* __restrict__
 // output pixel then gathers the nine pixels whose window holds it with the Sobel weight it has there.
 __global__ __launch_bounds__(SIM_THREADS) void sim_adjoint_kernel(const float* __restrict__ moving, const float* __restrict__ fx,
                                                                   const float* __restrict__ fy, const unsigned char* __restrict__ counted,
-                                                                  const float* __restrict__ coef, float* __restrict__ d_moving, int H, int W) {
+                                                                  const int32_t* __restrict__ fixed_of, const float* __restrict__ coef,
+                                                                  float* __restrict__ d_moving, int H, int W, int F) {
   // every product is rounded on its own: where moving matches fixed the two terms of g cancel exactly, which an FMA would undo
 #pragma clang fp contract(off)
   constexpr int IN = SIM_TILE + 4, G = SIM_TILE + 2;
@@ -141,6 +166,16 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_adjoint_kernel(const float* _
   __shared__ float sgx[G][G + 1], sgy[G][G + 1];
   const int view = blockIdx.z;
   const int r0 = blockIdx.y * SIM_TILE, c0 = blockIdx.x * SIM_TILE;
+  const int f = sim_image_of(fixed_of, view, F);
+  if (f < 0) {                                                          // the whole workgroup, before its first barrier
+    const int r = r0 + threadIdx.x / SIM_TILE, c = c0 + threadIdx.x % SIM_TILE;
+    if (r < H && c < W) d_moving[((size_t)view * H + r) * W + c] = 0.f;
+    return;
+  }
+  const size_t plane = (size_t)f * H * W;
+  fx += plane;
+  fy += plane;
+  counted += plane;
   const float* img = moving + (size_t)view * H * W;
   for (int i = threadIdx.x; i < IN * IN; i += SIM_THREADS) {
     const int lr = i / IN, lc = i % IN, r = r0 - 2 + lr, c = c0 - 2 + lc;
@@ -202,22 +237,61 @@ extern "C" int dfl_sim_prepare(const dfl_sim_prepare_args* a, dfl_stream_t strea
   return dfl::check_launch("dfl_sim_prepare");
 }
 
+namespace dfl {
+
+// What dfl_sim_gradncc, dfl_sim_gradncc_bwd and their bank forms are called with: fixed_of == nullptr is one fixed image
+// (F = 1), d_moving == nullptr the forward alone.  `bank` and `bwd` say which entry point `who` is.
+struct sim_call {
+  const float *moving, *fx, *fy;
+  const unsigned char* counted;
+  const double* totals;
+  const int32_t* fixed_of;
+  double *scratch, *cost;
+  float* d_moving;
+  int64_t scratch_doubles;
+  int V, H, W, F;
+};
+
+static int sim_launch(const char* who, const sim_call& c, bool bank, bool bwd, dfl_stream_t stream) {
+  DFL_REQUIRE(c.moving != nullptr && c.fx != nullptr && c.fy != nullptr && c.counted != nullptr && c.totals != nullptr &&
+                  c.scratch != nullptr && c.cost != nullptr && (!bwd || c.d_moving != nullptr),
+              "%s: moving, fx, fy, counted, totals, scratch%s are required", who, bwd ? ", cost and d_moving" : " and cost");
+  int rc = sim_sizes_ok(who, c.V, c.H, c.W);
+  if (rc != DFL_OK) return rc;
+  if (bank && (rc = sim_bank_ok(who, c.fixed_of, c.F, c.H, c.W)) != DFL_OK) return rc;
+  const int bands = sim_bands(c.H);
+  const int64_t need = bwd ? sim_bwd_need(c.V, c.H) : (int64_t)c.V * bands * SIM_MOVING;
+  DFL_REQUIRE(c.scratch_doubles >= need, "%s: a scratch of %lld doubles, %lld are needed (%s)", who, (long long)c.scratch_doubles,
+              (long long)need, bwd ? "dfl_sim_gradncc_bwd_scratch_doubles" : "dfl_sim_scratch_doubles");
+  DFL_REQUIRE(!bwd || ceil_div(c.H, SIM_TILE) <= 65535, "%s: an image of %d rows is too tall", who, c.H);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // the adjoint runs the forward's own two kernels first: its cost has the forward's bits
+  sim_gradncc_kernel<<<dim3((unsigned)bands, (unsigned)c.V), SIM_THREADS, 0, s>>>(c.moving, c.fx, c.fy, c.counted, c.fixed_of, c.scratch,
+                                                                                  c.H, c.W, c.F);
+  sim_finish_kernel<<<(unsigned)c.V, 64, 0, s>>>(c.scratch, c.totals, c.fixed_of, c.cost, bands, c.F);
+  if (bwd) {
+    float* coef = reinterpret_cast<float*>(c.scratch + (size_t)c.V * bands * SIM_MOVING);
+    sim_coef_kernel<<<(unsigned)ceil_div(c.V, 64), 64, 0, s>>>(c.scratch, c.totals, c.fixed_of, coef, bands, c.V, c.F);
+    const dim3 grid((unsigned)ceil_div(c.W, SIM_TILE), (unsigned)ceil_div(c.H, SIM_TILE), (unsigned)c.V);
+    sim_adjoint_kernel<<<grid, SIM_THREADS, 0, s>>>(c.moving, c.fx, c.fy, c.counted, c.fixed_of, coef, c.d_moving, c.H, c.W, c.F);
+  }
+  return check_launch(who);
+}
+
+}  // namespace dfl
+
 extern "C" int dfl_sim_gradncc(const dfl_sim_gradncc_args* a, dfl_stream_t stream) {
   DFL_REQUIRE(a != nullptr, "dfl_sim_gradncc: null args");
-  DFL_REQUIRE(a->moving != nullptr && a->fx != nullptr && a->fy != nullptr && a->counted != nullptr && a->totals != nullptr &&
-                  a->scratch != nullptr && a->cost != nullptr,
-              "dfl_sim_gradncc: moving, fx, fy, counted, totals, scratch and cost are required");
-  const int rc = dfl::sim_sizes_ok("dfl_sim_gradncc", a->V, a->H, a->W);
-  if (rc != DFL_OK) return rc;
-  const int bands = dfl::sim_bands(a->H);
-  const int64_t need = (int64_t)a->V * bands * dfl::SIM_MOVING;
-  DFL_REQUIRE(a->scratch_doubles >= need, "dfl_sim_gradncc: a scratch of %lld doubles, %lld are needed (dfl_sim_scratch_doubles)",
-              (long long)a->scratch_doubles, (long long)need);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  dfl::sim_gradncc_kernel<<<dim3((unsigned)bands, (unsigned)a->V), dfl::SIM_THREADS, 0, s>>>(a->moving, a->fx, a->fy, a->counted,
-                                                                                               a->scratch, a->H, a->W);
-  dfl::sim_finish_kernel<<<(unsigned)a->V, 64, 0, s>>>(a->scratch, a->totals, a->cost, bands);
-  return dfl::check_launch("dfl_sim_gradncc");
+  const dfl::sim_call c = {a->moving, a->fx, a->fy, a->counted, a->totals, nullptr, a->scratch, a->cost, nullptr, a->scratch_doubles,
+                           a->V,      a->H,  a->W,  1};
+  return dfl::sim_launch("dfl_sim_gradncc", c, false, false, stream);
+}
+
+extern "C" int dfl_sim_bank_gradncc(const dfl_sim_bank_gradncc_args* a, dfl_stream_t stream) {
+  DFL_REQUIRE(a != nullptr, "dfl_sim_bank_gradncc: null args");
+  const dfl::sim_call c = {a->moving, a->fx, a->fy, a->counted, a->totals, a->fixed_of, a->scratch, a->cost, nullptr, a->scratch_doubles,
+                           a->V,      a->H,  a->W,  a->F};
+  return dfl::sim_launch("dfl_sim_bank_gradncc", c, true, false, stream);
 }
 
 extern "C" int dfl_sim_gradncc_bwd_scratch_doubles(int32_t V, int32_t H, int32_t W) {
@@ -231,24 +305,14 @@ extern "C" int dfl_sim_gradncc_bwd_scratch_doubles(int32_t V, int32_t H, int32_t
 
 extern "C" int dfl_sim_gradncc_bwd(const dfl_sim_gradncc_bwd_args* a, dfl_stream_t stream) {
   DFL_REQUIRE(a != nullptr, "dfl_sim_gradncc_bwd: null args");
-  DFL_REQUIRE(a->moving != nullptr && a->fx != nullptr && a->fy != nullptr && a->counted != nullptr && a->totals != nullptr &&
-                  a->scratch != nullptr && a->cost != nullptr && a->d_moving != nullptr,
-              "dfl_sim_gradncc_bwd: moving, fx, fy, counted, totals, scratch, cost and d_moving are required");
-  const int rc = dfl::sim_sizes_ok("dfl_sim_gradncc_bwd", a->V, a->H, a->W);
-  if (rc != DFL_OK) return rc;
-  const int bands = dfl::sim_bands(a->H);
-  const int64_t need = dfl::sim_bwd_need(a->V, a->H);
-  DFL_REQUIRE(a->scratch_doubles >= need, "dfl_sim_gradncc_bwd: a scratch of %lld doubles, %lld are needed (dfl_sim_gradncc_bwd_scratch_doubles)",
-              (long long)a->scratch_doubles, (long long)need);
-  DFL_REQUIRE(dfl::ceil_div(a->H, dfl::SIM_TILE) <= 65535, "dfl_sim_gradncc_bwd: an image of %d rows is too tall", a->H);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  float* coef = reinterpret_cast<float*>(a->scratch + (size_t)a->V * bands * dfl::SIM_MOVING);
-  // the forward's own two kernels: the cost has the forward's bits
-  dfl::sim_gradncc_kernel<<<dim3((unsigned)bands, (unsigned)a->V), dfl::SIM_THREADS, 0, s>>>(a->moving, a->fx, a->fy, a->counted,
-                                                                                               a->scratch, a->H, a->W);
-  dfl::sim_finish_kernel<<<(unsigned)a->V, 64, 0, s>>>(a->scratch, a->totals, a->cost, bands);
-  dfl::sim_coef_kernel<<<(unsigned)dfl::ceil_div(a->V, 64), 64, 0, s>>>(a->scratch, a->totals, coef, bands, a->V);
-  const dim3 grid((unsigned)dfl::ceil_div(a->W, dfl::SIM_TILE), (unsigned)dfl::ceil_div(a->H, dfl::SIM_TILE), (unsigned)a->V);
-  dfl::sim_adjoint_kernel<<<grid, dfl::SIM_THREADS, 0, s>>>(a->moving, a->fx, a->fy, a->counted, coef, a->d_moving, a->H, a->W);
-  return dfl::check_launch("dfl_sim_gradncc_bwd");
+  const dfl::sim_call c = {a->moving, a->fx, a->fy, a->counted, a->totals, nullptr, a->scratch, a->cost, a->d_moving, a->scratch_doubles,
+                           a->V,      a->H,  a->W,  1};
+  return dfl::sim_launch("dfl_sim_gradncc_bwd", c, false, true, stream);
+}
+
+extern "C" int dfl_sim_bank_gradncc_bwd(const dfl_sim_bank_gradncc_bwd_args* a, dfl_stream_t stream) {
+  DFL_REQUIRE(a != nullptr, "dfl_sim_bank_gradncc_bwd: null args");
+  const dfl::sim_call c = {a->moving, a->fx, a->fy, a->counted, a->totals, a->fixed_of, a->scratch, a->cost, a->d_moving,
+                           a->scratch_doubles, a->V, a->H, a->W, a->F};
+  return dfl::sim_launch("dfl_sim_bank_gradncc_bwd", c, true, true, stream);
 }

@@ -15,6 +15,9 @@
 //   block_sum's fixed order and writes ONE record of two doubles with plain stores.
 //   sim_patch_finish_kernel (one wave per view): adds the PR records in index order, divides by pcount, writes the cost.
 // No atomics: the bits of a view's cost depend on that view's pixels and on H, W, rho and the stride only.
+// dfl_sim_patch_bank_gradncc launches the same two kernels with fixed_of [V] and F: view v reads the
+// planes, patch totals, flags and counts of image fixed_of[v] of a bank (sim_image_of, csrc/sim.h); dfl_sim_patch_gradncc
+// passes fixed_of = nullptr and every view reads image 0.
 #include "sim.h"
 
 namespace dfl {
@@ -91,12 +94,21 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_patch_gradncc_kernel(const fl
                                                                         const unsigned char* __restrict__ counted,
                                                                         const double* __restrict__ ptotals,
                                                                         const unsigned char* __restrict__ pflags,
+                                                                        const int32_t* __restrict__ fixed_of,
                                                                         double* __restrict__ scratch, int H, int W, int S, int stride,
-                                                                        int PC) {
+                                                                        int PC, int F) {
   extern __shared__ double cols[];                                      // [SIM_MOVING][W - 2]
   __shared__ double lds[2 * 4];
   const int a = blockIdx.x, view = blockIdx.y, wi = W - 2;
   const int r0 = 1 + a * stride;
+  const int f = sim_image_of(fixed_of, view, F);
+  if (f < 0) return;                                                    // the whole workgroup: sim_patch_finish_kernel reads no record
+  const size_t plane = (size_t)f * H * W, patches = (size_t)f * gridDim.x * PC;
+  fx += plane;
+  fy += plane;
+  counted += plane;
+  ptotals += patches * SIM_FIXED;
+  pflags += patches;
   const float* img = moving + (size_t)view * H * W;
   for (int j = threadIdx.x; j < wi; j += SIM_THREADS) {
     double s[SIM_MOVING] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -133,9 +145,16 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_patch_gradncc_kernel(const fl
 
 // One wave per view: lanes 0 and 1 add the view's PR records of ncc_x / ncc_y in index order
 __global__ __launch_bounds__(64) void sim_patch_finish_kernel(const double* __restrict__ scratch, const int* __restrict__ pcount,
-                                                              double* __restrict__ cost, int PR) {
+                                                              const int32_t* __restrict__ fixed_of, double* __restrict__ cost, int PR,
+                                                              int F) {
   __shared__ double m[2];
   const int view = blockIdx.x;
+  const int f = sim_image_of(fixed_of, view, F);
+  if (f < 0) {                                                          // the whole workgroup: no barrier is left waiting
+    if (threadIdx.x == 0) cost[view] = __builtin_nan("");
+    return;
+  }
+  pcount += 2 * f;
   if (threadIdx.x < 2) {
     const double acc = records_sum(scratch + (size_t)view * PR * 2 + threadIdx.x, PR, 2);
     const int n = pcount[threadIdx.x];
@@ -193,24 +212,53 @@ extern "C" int dfl_sim_patch_prepare(const dfl_sim_patch_prepare_args* a, dfl_st
   return dfl::check_launch("dfl_sim_patch_prepare");
 }
 
+namespace dfl {
+
+// what dfl_sim_patch_gradncc and its bank form are called with: fixed_of == nullptr is one fixed image (F = 1)
+struct sim_patch_call {
+  const float *moving, *fx, *fy;
+  const unsigned char* counted;
+  const double* ptotals;
+  const unsigned char* pflags;
+  const int32_t *pcount, *fixed_of;
+  double *scratch, *cost;
+  int64_t scratch_doubles;
+  int V, H, W, rho, stride, F;
+};
+
+static int sim_patch_launch(const char* who, const sim_patch_call& c, bool bank, dfl_stream_t stream) {
+  DFL_REQUIRE(c.moving != nullptr && c.fx != nullptr && c.fy != nullptr && c.counted != nullptr && c.ptotals != nullptr &&
+                  c.pflags != nullptr && c.pcount != nullptr && c.scratch != nullptr && c.cost != nullptr,
+              "%s: moving, fx, fy, counted, ptotals, pflags, pcount, scratch and cost are required", who);
+  patch_grid g;
+  int rc = patch_sizes_ok(who, c.H, c.W, c.rho, c.stride, &g);
+  if (rc != DFL_OK) return rc;
+  DFL_REQUIRE(c.V >= 1 && c.V <= 65535, "%s: 1..65535 views per call, got %d", who, c.V);
+  if (bank && (rc = sim_bank_ok(who, c.fixed_of, c.F, c.H, c.W)) != DFL_OK) return rc;
+  const int64_t need = (int64_t)c.V * g.PR * 2;
+  DFL_REQUIRE(c.scratch_doubles >= need, "%s: a scratch of %lld doubles, %lld are needed (dfl_sim_patch_scratch_doubles)", who,
+              (long long)c.scratch_doubles, (long long)need);
+  const int lds = SIM_MOVING * (c.W - 2) * (int)sizeof(double);
+  DFL_LDS_OPT_IN(sim_patch_gradncc_kernel, DFL_SIM_PATCH_MAX_W * SIM_MOVING * sizeof(double), who)
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  sim_patch_gradncc_kernel<<<dim3((unsigned)g.PR, (unsigned)c.V), SIM_THREADS, lds, s>>>(
+      c.moving, c.fx, c.fy, c.counted, c.ptotals, c.pflags, c.fixed_of, c.scratch, c.H, c.W, g.S, c.stride, g.PC, c.F);
+  sim_patch_finish_kernel<<<(unsigned)c.V, 64, 0, s>>>(c.scratch, c.pcount, c.fixed_of, c.cost, g.PR, c.F);
+  return check_launch(who);
+}
+
+}  // namespace dfl
+
 extern "C" int dfl_sim_patch_gradncc(const dfl_sim_patch_gradncc_args* a, dfl_stream_t stream) {
   DFL_REQUIRE(a != nullptr, "dfl_sim_patch_gradncc: null args");
-  DFL_REQUIRE(a->moving != nullptr && a->fx != nullptr && a->fy != nullptr && a->counted != nullptr && a->ptotals != nullptr &&
-                  a->pflags != nullptr && a->pcount != nullptr && a->scratch != nullptr && a->cost != nullptr,
-              "dfl_sim_patch_gradncc: moving, fx, fy, counted, ptotals, pflags, pcount, scratch and cost are required");
-  dfl::patch_grid g;
-  const int rc = dfl::patch_sizes_ok("dfl_sim_patch_gradncc", a->H, a->W, a->rho, a->stride, &g);
-  if (rc != DFL_OK) return rc;
-  DFL_REQUIRE(a->V >= 1 && a->V <= 65535, "dfl_sim_patch_gradncc: 1..65535 views per call, got %d", a->V);
-  const int64_t need = (int64_t)a->V * g.PR * 2;
-  DFL_REQUIRE(a->scratch_doubles >= need,
-              "dfl_sim_patch_gradncc: a scratch of %lld doubles, %lld are needed (dfl_sim_patch_scratch_doubles)",
-              (long long)a->scratch_doubles, (long long)need);
-  const int lds = dfl::SIM_MOVING * (a->W - 2) * (int)sizeof(double);
-  DFL_LDS_OPT_IN(dfl::sim_patch_gradncc_kernel, DFL_SIM_PATCH_MAX_W * dfl::SIM_MOVING * sizeof(double), "dfl_sim_patch_gradncc")
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  dfl::sim_patch_gradncc_kernel<<<dim3((unsigned)g.PR, (unsigned)a->V), dfl::SIM_THREADS, lds, s>>>(
-      a->moving, a->fx, a->fy, a->counted, a->ptotals, a->pflags, a->scratch, a->H, a->W, g.S, a->stride, g.PC);
-  dfl::sim_patch_finish_kernel<<<(unsigned)a->V, 64, 0, s>>>(a->scratch, a->pcount, a->cost, g.PR);
-  return dfl::check_launch("dfl_sim_patch_gradncc");
+  const dfl::sim_patch_call c = {a->moving,  a->fx,   a->fy, a->counted, a->ptotals, a->pflags, a->pcount, nullptr,
+                                 a->scratch, a->cost, a->scratch_doubles, a->V, a->H, a->W, a->rho, a->stride, 1};
+  return dfl::sim_patch_launch("dfl_sim_patch_gradncc", c, false, stream);
+}
+
+extern "C" int dfl_sim_patch_bank_gradncc(const dfl_sim_patch_bank_gradncc_args* a, dfl_stream_t stream) {
+  DFL_REQUIRE(a != nullptr, "dfl_sim_patch_bank_gradncc: null args");
+  const dfl::sim_patch_call c = {a->moving,  a->fx,   a->fy, a->counted, a->ptotals, a->pflags, a->pcount, a->fixed_of,
+                                 a->scratch, a->cost, a->scratch_doubles, a->V, a->H, a->W, a->rho, a->stride, a->F};
+  return dfl::sim_patch_launch("dfl_sim_patch_bank_gradncc", c, true, stream);
 }

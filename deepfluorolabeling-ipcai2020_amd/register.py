@@ -11,7 +11,9 @@ restates them in numpy float64.  The patch cost (dfl_sim_patch_gradncc, csrc/sim
 section 18 and tests/patch_ref.py.  register(refine=K) finishes with a dense BFGS (bfgs) on the gradient of the cost with
 respect to the six parameters: one render, the adjoint of the similarity (dfl_sim_gradncc_bwd) and the forces and moments
 it exerts on every object (dfl_drr_pose_grad, sampling frozen), chained to theta through pose_delta_jacobians; section 19
-and tests/grad_ref.py.
+and tests/grad_ref.py.  register_many registers N projections of one volume at once: the candidates of all problems go through
+one render and one launch against a bank of fixed images (SimilarityBank, dfl_sim_bank_gradncc), the optimisers advance in
+lockstep (cma_steps, bfgs_steps, lockstep), and every result has the bytes register() finds for it alone; section 20.
 
     D(theta) = [[R, centre - R centre + theta[3:]], [0, 1]],  R = exp(rot_unit theta[:3])      (pose_delta)
     P(theta) = D(theta) P0                                   a cam-to-*-vol matrix as in gt-poses
@@ -26,8 +28,9 @@ import torch
 from . import _native as nat
 from . import drr, preprocess
 
-__all__ = ['se3_exp', 'se3_log', 'pose_delta', 'pose_deltas', 'pose_delta_jacobians', 'pnp', 'cma_es', 'CmaResult', 'bfgs', 'BfgsResult',
-           'Similarity', 'PatchSimilarity', 'landmark_penalty', 'register', 'Registration', 'with_pelvis_pose', 'volume_centre']
+__all__ = ['se3_exp', 'se3_log', 'pose_delta', 'pose_deltas', 'pose_delta_jacobians', 'pnp', 'cma_es', 'cma_steps', 'CmaResult', 'bfgs', 'bfgs_steps', 'BfgsResult', 'lockstep',
+           'Similarity', 'PatchSimilarity', 'SimilarityBank', 'PatchSimilarityBank', 'fixed_of_array', 'landmark_penalty', 'register',
+           'register_many', 'default_max_views', 'Registration', 'with_pelvis_pose', 'volume_centre']
 
 ROT_UNIT = 0.02
 
@@ -233,10 +236,52 @@ class CmaResult:
         self.mean, self.best_x, self.best_f, self.trace, self.evaluations, self.sigma = mean, best_x, best_f, trace, evaluations, sigma
 
 
+def _drive(steps, answer):
+    """Run a step-wise optimiser (cma_steps, bfgs_steps) to its end with answer(point) as the reply to every request."""
+    try:
+        x = next(steps)
+        while True:
+            x = steps.send(answer(x))
+    except StopIteration as stop:
+        return stop.value
+
+
+def lockstep(steppers, evaluate):
+    """Advance step-wise optimisers together.  Every round collects the request of each stepper that still runs and calls
+    evaluate(indices, points) once -- indices into `steppers`, ascending, and the point each of them asked for -- which
+    returns one reply per point; a stepper that ends drops out of the later rounds.  Returns every stepper's result."""
+    steppers = list(steppers)
+    results, pending = [None] * len(steppers), {}
+
+    def advance(i, step):
+        try:
+            pending[i] = step()
+        except StopIteration as stop:
+            pending.pop(i, None)
+            results[i] = stop.value
+
+    for i, s in enumerate(steppers):
+        advance(i, lambda s=s: next(s))
+    while pending:
+        idx = sorted(pending)
+        replies = list(evaluate(idx, [pending[i] for i in idx]))
+        if len(replies) != len(idx):
+            raise nat.DflError('register.lockstep: evaluate returned %d replies for %d points' % (len(replies), len(idx)))
+        for i, r in zip(idx, replies):
+            advance(i, lambda i=i, r=r: steppers[i].send(r))
+    return results
+
+
 def cma_es(cost_fn, x0, sigma0, popsize=None, generations=100, seed=0):
     """A plain (mu/mu_w, lambda) CMA-ES with Hansen's default constants (The CMA Evolution Strategy: A Tutorial, 2016).
     cost_fn takes [lambda, n] and returns [lambda].  Random draws come from numpy.random.default_rng(seed) on the host and
-    the ranking is a stable sort, so a run repeats bit for bit."""
+    the ranking is a stable sort, so a run repeats bit for bit.  This is cma_steps driven by cost_fn."""
+    return _drive(cma_steps(x0, sigma0, popsize, generations, seed), cost_fn)
+
+
+def cma_steps(x0, sigma0, popsize=None, generations=100, seed=0):
+    """cma_es as a generator: it yields the candidates [lambda, n] of a generation, is sent their costs [lambda], and
+    returns its CmaResult (StopIteration.value) after `generations` of them.  Several can be advanced together (lockstep)."""
     x0 = np.asarray(x0, np.float64).reshape(-1)
     n = x0.size
     lam = int(popsize) if popsize else 4 + int(3 * np.log(n))
@@ -261,7 +306,7 @@ def cma_es(cost_fn, x0, sigma0, popsize=None, generations=100, seed=0):
         z = rng.standard_normal((lam, n))
         y = (z * Dg[None]) @ B.T
         xs = mean[None] + sigma * y
-        f = np.asarray(cost_fn(xs), np.float64).reshape(-1)
+        f = np.asarray((yield xs), np.float64).reshape(-1)
         if f.size != lam:
             raise nat.DflError('register.cma_es: cost_fn returned %d values for %d candidates' % (f.size, lam))
         f = np.where(np.isfinite(f), f, np.inf)
@@ -297,9 +342,16 @@ def bfgs(fun, x0, iterations=30, tol=1e-4, c1=1e-4, min_step=1e-6):
     not a descent direction; from the identity the first trial step is min(1, 1 / |g|), else 1.  A trial whose cost is
     not finite or fails f <= f0 + c1 t g.p is rejected, so the accepted costs never increase.  It stops after
     `iterations` accepted steps, when an accepted step is shorter than tol, or when the trial step |t p| falls below min_step."""
+    return _drive(bfgs_steps(x0, iterations, tol, c1, min_step), fun)
+
+
+def bfgs_steps(x0, iterations=30, tol=1e-4, c1=1e-4, min_step=1e-6):
+    """bfgs as a generator: it yields the point [n] it wants evaluated, is sent (cost, gradient [n]), and returns its
+    BfgsResult (StopIteration.value).  Problems need different numbers of trials, so generators advanced together
+    (lockstep) end at different rounds."""
     x = np.asarray(x0, np.float64).reshape(-1).copy()
     n = x.size
-    f, g = fun(x)
+    f, g = yield x
     f, g = float(f), np.asarray(g, np.float64).reshape(n)
     if not np.isfinite(f) or not np.isfinite(g).all():
         raise nat.DflError('register.bfgs: the cost or its gradient is not finite at the start (%r)' % f)
@@ -316,7 +368,7 @@ def bfgs(fun, x0, iterations=30, tol=1e-4, c1=1e-4, min_step=1e-6):
         accepted = None
         while t * float(np.linalg.norm(p)) >= min_step:
             xn = x + t * p
-            fn, gn = fun(xn)
+            fn, gn = yield xn
             fn, gn = float(fn), np.asarray(gn, np.float64).reshape(n)
             evals += 1
             if np.isfinite(fn) and np.isfinite(gn).all() and fn <= f + c1 * t * slope:
@@ -474,6 +526,149 @@ class PatchSimilarity(Similarity):
         raise nat.DflError('register: the patch similarity has no adjoint kernel yet (DESIGN.md section 19 names it as next)')
 
 
+# ---- the similarity against a bank of fixed images ---------------------------------------------------------------------
+def fixed_of_array(fixed_of, V, F):
+    """A sequence or array that says which of F fixed images each of V views is scored against -> int32 [V], checked on
+    the host: integers, one per view, each in [0, F)."""
+    a = np.asarray(fixed_of)
+    if a.ndim != 1 or a.shape[0] != V or a.dtype.kind not in 'iu':
+        raise nat.DflError('register: fixed_of has shape %s and dtype %s: %d integers expected, one per view' % (a.shape, a.dtype, V))
+    if V and (int(a.min()) < 0 or int(a.max()) >= F):
+        raise nat.DflError('register: fixed_of holds %d .. %d, the bank has the images 0 .. %d' % (int(a.min()), int(a.max()), F - 1))
+    return np.ascontiguousarray(a, np.int32)
+
+
+class SimilarityBank(Similarity):
+    """Similarity against F fixed images [F, H, W] (float32, on the GPU) with optional uint8 masks [F, H, W]: dfl_sim_prepare
+    runs here, once per image, on that image's slice of the banks.  cost(moving, fixed_of) scores view v against image
+    fixed_of[v] in one dfl_sim_bank_gradncc launch; the bits of a view's cost are those Similarity(fixed[f], masks[f])
+    gives it.  fixed_of is an int32 tensor [V] on the device (not checked: a view whose entry is outside [0, F) costs NaN
+    and gets a zero adjoint) or a sequence, which is checked here (fixed_of_array)."""
+
+    def __init__(self, fixed, masks=None, views=1):
+        self.fixed = _device_image(fixed, 'the fixed images', 3)
+        dev = self.fixed.device
+        F, H, W = (int(s) for s in self.fixed.shape)
+        self.F, self.H, self.W, self.views = F, H, W, int(views)
+        self.mask = None
+        if masks is not None:
+            self.mask = _device_image(masks, 'the masks', 3, (torch.uint8,))
+            if tuple(self.mask.shape) != (F, H, W) or self.mask.device != dev:
+                raise nat.DflError('register: the masks are %s on %s, the fixed images %s on %s'
+                                   % (tuple(self.mask.shape), self.mask.device, (F, H, W), dev))
+        if not 1 <= F <= 65535 or F * H * W >= 2 ** 31:
+            raise nat.DflError('register: a bank of %d images of %d x %d (1..65535 images, fewer than 2^31 pixels)' % (F, H, W))
+        lib = nat.lib()
+        need = int(lib.dfl_sim_scratch_doubles(self.views, H, W))
+        if need < 0:
+            raise nat.DflError('register: %s' % lib.dfl_last_error().decode())
+        self.fx = torch.empty((F, H, W), dtype=torch.float32, device=dev)
+        self.fy = torch.empty((F, H, W), dtype=torch.float32, device=dev)
+        self.counted = torch.empty((F, H, W), dtype=torch.uint8, device=dev)
+        self.totals = torch.empty((F, nat.SIM_TOTALS), dtype=torch.float64, device=dev)
+        self.scratch = torch.empty(max(need, 1), dtype=torch.float64, device=dev)
+        self.out = torch.empty(self.views, dtype=torch.float64, device=dev)
+        self._fixed_of = {}
+        for f in range(F):
+            a = nat.SimPrepareArgs(fixed=self.fixed[f].data_ptr(), mask=None if self.mask is None else self.mask[f].data_ptr(),
+                                   fx=self.fx[f].data_ptr(), fy=self.fy[f].data_ptr(), counted=self.counted[f].data_ptr(),
+                                   totals=self.totals[f].data_ptr(), H=H, W=W)
+            drr.launch(dev, 'dfl_sim_prepare', a)
+
+    entry = 'dfl_sim_bank_gradncc'
+
+    def fixed_of(self, fixed_of, V):
+        """The int32 device tensor [V] the kernels read; sequences are checked on the host and uploaded once each."""
+        if torch.is_tensor(fixed_of):
+            if not fixed_of.is_cuda or fixed_of.dtype != torch.int32 or tuple(fixed_of.shape) != (V,) or fixed_of.device != self.fixed.device:
+                raise nat.DflError('register: fixed_of is a tensor of shape %s and dtype %s on %s: int32 [%d] on %s expected'
+                                   % (tuple(fixed_of.shape), fixed_of.dtype, fixed_of.device, V, self.fixed.device))
+            return fixed_of.detach().contiguous()
+        a = fixed_of_array(fixed_of, V, self.F)
+        key = a.tobytes()
+        if key not in self._fixed_of:
+            if len(self._fixed_of) >= 64:
+                self._fixed_of.clear()
+            self._fixed_of[key] = torch.from_numpy(a).to(self.fixed.device)
+        return self._fixed_of[key]
+
+    def args(self, moving, fixed_of, out=None):
+        out = self.out if out is None else out
+        return nat.SimBankGradnccArgs(moving=moving.data_ptr(), fx=self.fx.data_ptr(), fy=self.fy.data_ptr(), counted=self.counted.data_ptr(),
+                                      totals=self.totals.data_ptr(), fixed_of=fixed_of.data_ptr(), scratch=self.scratch.data_ptr(),
+                                      cost=out.data_ptr(), scratch_doubles=self.scratch.numel(), V=int(moving.shape[0]), H=self.H, W=self.W,
+                                      F=self.F)
+
+    def launch(self, moving, fixed_of, out=None):
+        """One launch of `entry` on checked moving images; the costs go to `out` (default: the first rows of self.out)."""
+        drr.launch(moving.device, self.entry, self.args(moving, self.fixed_of(fixed_of, int(moving.shape[0])), out))
+
+    def cost(self, moving, fixed_of):
+        mv = self._moving(moving)
+        out = torch.empty(mv.shape[0], dtype=torch.float64, device=mv.device)
+        self.launch(mv, fixed_of, out)
+        return out
+
+    def cost_and_adjoint(self, moving, fixed_of):
+        """(cost [V] float64, d_moving [V, H, W] float32) on the device: one dfl_sim_bank_gradncc_bwd launch."""
+        mv = self._moving(moving)
+        V, dev = int(mv.shape[0]), mv.device
+        of = self.fixed_of(fixed_of, V)
+        if getattr(self, 'bwd_scratch', None) is None:
+            lib = nat.lib()
+            need = int(lib.dfl_sim_gradncc_bwd_scratch_doubles(self.views, self.H, self.W))
+            if need < 0:
+                raise nat.DflError('register: %s' % lib.dfl_last_error().decode())
+            self.bwd_scratch = torch.empty(need, dtype=torch.float64, device=dev)
+        out = torch.empty(V, dtype=torch.float64, device=dev)
+        d_moving = torch.empty((V, self.H, self.W), dtype=torch.float32, device=dev)
+        a = nat.SimBankGradnccBwdArgs(moving=mv.data_ptr(), fx=self.fx.data_ptr(), fy=self.fy.data_ptr(), counted=self.counted.data_ptr(),
+                                      totals=self.totals.data_ptr(), fixed_of=of.data_ptr(), scratch=self.bwd_scratch.data_ptr(),
+                                      cost=out.data_ptr(), d_moving=d_moving.data_ptr(), scratch_doubles=self.bwd_scratch.numel(), V=V,
+                                      H=self.H, W=self.W, F=self.F)
+        drr.launch(dev, 'dfl_sim_bank_gradncc_bwd', a)
+        return out, d_moving
+
+
+class PatchSimilarityBank(SimilarityBank):
+    """PatchSimilarity against F fixed images, with the interface of SimilarityBank: dfl_sim_patch_prepare runs once per
+    image on its slice of the patch banks; cost(moving, fixed_of) is one dfl_sim_patch_bank_gradncc launch."""
+
+    def __init__(self, fixed, masks=None, views=1, radius=7, stride=4, min_count=None):
+        self.radius, self.stride, self.min_count = _patch_params(radius, stride, min_count)
+        SimilarityBank.__init__(self, fixed, masks, views)
+        lib = nat.lib()
+        dev, F, H, W = self.fixed.device, self.F, self.H, self.W
+        P = int(lib.dfl_sim_patch_count(H, W, self.radius, self.stride))
+        need = int(lib.dfl_sim_patch_scratch_doubles(self.views, H, W, self.radius, self.stride)) if P >= 0 else -1
+        if P < 0 or need < 0:
+            raise nat.DflError('register: %s' % lib.dfl_last_error().decode())
+        self.patches = P
+        self.ptotals = torch.empty((F, P, nat.SIM_TOTALS), dtype=torch.float64, device=dev)
+        self.pflags = torch.empty((F, P), dtype=torch.uint8, device=dev)
+        self.pcount = torch.empty((F, 2), dtype=torch.int32, device=dev)
+        self.pscratch = torch.empty(need, dtype=torch.float64, device=dev)
+        for f in range(F):
+            a = nat.SimPatchPrepareArgs(fx=self.fx[f].data_ptr(), fy=self.fy[f].data_ptr(), counted=self.counted[f].data_ptr(),
+                                        ptotals=self.ptotals[f].data_ptr(), pflags=self.pflags[f].data_ptr(),
+                                        pcount=self.pcount[f].data_ptr(), H=H, W=W, rho=self.radius, stride=self.stride,
+                                        min_count=self.min_count)
+            drr.launch(dev, 'dfl_sim_patch_prepare', a)
+
+    entry = 'dfl_sim_patch_bank_gradncc'
+
+    def args(self, moving, fixed_of, out=None):
+        out = self.out if out is None else out
+        return nat.SimPatchBankGradnccArgs(moving=moving.data_ptr(), fx=self.fx.data_ptr(), fy=self.fy.data_ptr(),
+                                           counted=self.counted.data_ptr(), ptotals=self.ptotals.data_ptr(), pflags=self.pflags.data_ptr(),
+                                           pcount=self.pcount.data_ptr(), fixed_of=fixed_of.data_ptr(), scratch=self.pscratch.data_ptr(),
+                                           cost=out.data_ptr(), scratch_doubles=self.pscratch.numel(), V=int(moving.shape[0]), H=self.H,
+                                           W=self.W, rho=self.radius, stride=self.stride, F=self.F)
+
+    def cost_and_adjoint(self, moving, fixed_of):
+        raise nat.DflError('register: the patch similarity has no adjoint kernel yet (DESIGN.md section 19 names it as next)')
+
+
 # ---- the landmark term -------------------------------------------------------------------------------------------------
 def _usable_landmarks(X3d, x2d, who):
     X = np.asarray(X3d, np.float64)
@@ -521,11 +716,16 @@ class Registration:
 class _Level:
     """The buffers and argument blocks of one resolution level: lambda views of every object on one grid."""
 
-    def __init__(self, volume, grid, fixed, mask, lam, step_mm, patch=None):
+    def __init__(self, volume, grid, fixed, mask, lam, step_mm, patch=None, bank=None):
+        """bank=(fixed [F, H, W], masks or None) in place of fixed and mask: the views are scored against a bank, and costs()
+        takes fixed_of."""
         self.volume, self.grid, self.lam = volume, grid, lam
-        if tuple(fixed.shape) != (grid.H, grid.W):
-            raise nat.DflError('register: the fixed image is %s, the output grid %d x %d' % (tuple(fixed.shape), grid.H, grid.W))
-        self.sim = Similarity(fixed, mask, lam) if patch is None else PatchSimilarity(fixed, mask, lam, *patch)
+        if bank is not None:
+            self.sim = SimilarityBank(bank[0], bank[1], lam) if patch is None else PatchSimilarityBank(bank[0], bank[1], lam, *patch)
+        else:
+            if tuple(fixed.shape) != (grid.H, grid.W):
+                raise nat.DflError('register: the fixed image is %s, the output grid %d x %d' % (tuple(fixed.shape), grid.H, grid.W))
+            self.sim = Similarity(fixed, mask, lam) if patch is None else PatchSimilarity(fixed, mask, lam, *patch)
         self.step_mm = float(step_mm)
 
     def _render(self, c2is, masks):
@@ -535,10 +735,11 @@ class _Level:
         drr.launch(att.device, 'dfl_drr_render', a)
         return recs, att, keep
 
-    def costs(self, c2is, masks):
-        """[views <= lambda, n_obj, 4, 4] -> float64 [views] on the host: one render, one similarity launch, one copy."""
+    def costs(self, c2is, masks, *fixed_of):
+        """[views <= lambda, n_obj, 4, 4] (and, with a bank, fixed_of [views]) -> float64 [views] on the host: one render, one
+        similarity launch, one copy."""
         recs, att, keep = self._render(c2is, masks)
-        self.sim.launch(att)
+        self.sim.launch(att, *fixed_of)
         return self.sim.out[:recs.shape[0]].cpu().numpy()           # the copy waits for both launches: `keep` lives until then
 
     def costs_and_grads(self, c2is, masks, xis, moving):
@@ -546,17 +747,123 @@ class _Level:
         unit of every parameter) -> (float64 [views], float64 [views, 6]) on the host: one render, one dfl_sim_gradncc_bwd,
         one dfl_drr_pose_grad, one copy; the chain from forces and moments to the parameters is float64 numpy."""
         recs, att, keep = self._render(c2is, masks)
-        V = recs.shape[0]
-        cost, d_att = self.sim.cost_and_adjoint(att)
+        both, piv = self._cost_and_moments(recs, att, *self.sim.cost_and_adjoint(att))
+        del keep
+        return _theta_chain(both, piv, xis, moving)
+
+    def _cost_and_moments(self, recs, att, cost, d_att):
+        """(float64 [views, 1 + n_obj 12] on the host: a view's cost, then the force and moment on every object; the pivots)
+        for rendered records and the similarity's (cost, adjoint): one dfl_drr_pose_grad, one copy."""
         piv = drr.box_pivots(recs)
         grad = drr.pose_gradient(self.volume, recs, self.grid, d_att, piv, self.step_mm)
-        both = torch.cat([cost[:, None], grad.reshape(V, -1)], 1).cpu().numpy()     # the copy waits for every launch
-        del keep
-        g = both[:, 1:].reshape(V, -1, 12)
-        F, Mom = g[:, moving, :3], g[:, moving, 3:].reshape(V, len(moving), 3, 3)   # [V, m, 3], [V, m, 3, 3]
-        L, tau = xis[:, :, None, :3, :3], xis[:, :, None, :3, 3]                    # [V, 6, 1, 3, 3], [V, 6, 1, 3]
-        lever = (L @ piv[:, None, moving, :, None].astype(np.float64))[..., 0] + tau  # [V, 6, m, 3]
-        return both[:, 0], ((Mom[:, None] * L).sum((-1, -2)) + (F[:, None] * lever).sum(-1)).sum(-1)
+        return torch.cat([cost[:, None], grad.reshape(recs.shape[0], -1)], 1).cpu().numpy(), piv    # the copy waits for every launch
+
+
+def _theta_chain(both, piv, xis, moving):
+    """_Level._cost_and_moments' rows and pivots, xis [V, 6, 4, 4] -> (cost [V], d cost / d theta [V, 6]), float64 numpy."""
+    V = both.shape[0]
+    g = both[:, 1:].reshape(V, -1, 12)
+    F, Mom = g[:, moving, :3], g[:, moving, 3:].reshape(V, len(moving), 3, 3)       # [V, m, 3], [V, m, 3, 3]
+    L, tau = xis[:, :, None, :3, :3], xis[:, :, None, :3, 3]                        # [V, 6, 1, 3, 3], [V, 6, 1, 3]
+    lever = (L @ piv[:, None, moving, :, None].astype(np.float64))[..., 0] + tau    # [V, 6, m, 3]
+    return both[:, 0], ((Mom[:, None] * L).sum((-1, -2)) + (F[:, None] * lever).sum(-1)).sum(-1)
+
+
+def _cost_options(refine, refine_tol, similarity, patch_radius, patch_stride, patch_min_count, landmark_weight):
+    """The checks register() and register_many() make first: (the patch parameters or None, the landmark weight)."""
+    if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or refine < 0 or not float(refine_tol) >= 0.0:
+        raise nat.DflError('register: refine = %r (an integer, at least 0) and refine_tol = %r (not negative)' % (refine, refine_tol))
+    if refine > 0 and similarity == 'patch':
+        raise nat.DflError("register: refine needs the adjoint of the similarity, which similarity='patch' does not have yet")
+    if similarity not in ('global', 'patch'):
+        raise nat.DflError("register: similarity = %r ('global' or 'patch')" % (similarity,))
+    patch = _patch_params(patch_radius, patch_stride, patch_min_count) if similarity == 'patch' else None
+    landmark_weight = float(landmark_weight)
+    if not landmark_weight >= 0.0 or not np.isfinite(landmark_weight):
+        raise nat.DflError('register: a landmark_weight of %r (finite, not negative)' % landmark_weight)
+    return patch, landmark_weight
+
+
+def _landmarks_of(landmarks, moving):
+    """The usable (X [L, 3], x [2, L]) of landmarks=(X3d, x2d), or None without landmarks."""
+    if landmarks is None:
+        return None
+    if 0 not in tuple(int(m) for m in moving):
+        raise nat.DflError('register: the landmark term follows the pelvis (object 0), which moving = %r holds still' % (tuple(moving),))
+    try:
+        X3d, x2d = landmarks
+    except (TypeError, ValueError):
+        raise nat.DflError('register: landmarks = (X3d [L, 3], x2d [2, L]) expected') from None
+    return _usable_landmarks(X3d, x2d, 'register: landmarks')
+
+
+def _moving_and_population(geom, moving, popsize):
+    n_obj = len(geom.objects)
+    moving = tuple(int(m) for m in moving)
+    if not moving or len(set(moving)) != len(moving) or any(not 0 <= m < n_obj for m in moving):
+        raise nat.DflError('register: moving = %r selects no or unknown objects (%d objects)' % (moving, n_obj))
+    lam = int(popsize)
+    if lam < 4:
+        raise nat.DflError('register: a population of %d (at least 4)' % lam)
+    return moving, lam
+
+
+class _Problem:
+    """The float64 host side of one registration, shared by register() and register_many(): where the objects start,
+    candidates -> the C2I matrices the renderer gets, the landmark term, the motion of the moving objects per unit of
+    every parameter, and the Registration of a found theta."""
+
+    def __init__(self, volume_shape, geom, moving, P0, centre, rot_unit, lands, landmark_weight):
+        self.geom, self.moving, self.rot_unit = geom, moving, rot_unit
+        n_obj = len(geom.objects)
+        self.I2P = I2P = np.asarray(geom.I2P, np.float64)
+        self.back, Ei = np.linalg.inv(I2P), np.linalg.inv(geom.E)
+        self.ctr = volume_centre(volume_shape, I2P) if centre is None else np.asarray(centre, np.float64).reshape(3)
+        self.base = base = np.stack([ob.c2i for ob in geom.objects])            # [n_obj, 4, 4]
+        if P0 is not None:
+            P0 = np.asarray(P0, np.float64).reshape(4, 4)
+            for m in moving:
+                base[m] = self.back @ P0 @ Ei
+        self.masks = [ob.mask for ob in geom.objects]
+        self.mv = np.zeros(n_obj, bool)
+        self.mv[list(moving)] = True
+        self.lands, self.weight = lands, landmark_weight
+        self.P_pelvis = I2P @ base[0] @ geom.E if lands is not None and landmark_weight > 0.0 else None    # P = I2P C2I E
+
+    def c2is_of(self, thetas):
+        A = self.back[None] @ pose_deltas(thetas, self.ctr, self.rot_unit) @ self.I2P[None]     # [views, 4, 4]
+        return np.where(self.mv[None, :, None, None], A[:, None] @ self.base[None], self.base[None])
+
+    def penalty(self, thetas):
+        return landmark_penalty(self.geom, pose_deltas(thetas, self.ctr, self.rot_unit) @ self.P_pelvis[None], self.lands[0], self.lands[1],
+                                self.weight)
+
+    def with_penalty(self, c, thetas):
+        """What the CMA-ES minimises: the similarity costs c of the candidates plus their landmark term."""
+        return c if self.P_pelvis is None else c + self.penalty(thetas)
+
+    def xis_of(self, th):
+        """[1, 6] -> [1, 6, 4, 4]: the motion of the moving objects in index coordinates per unit of every parameter."""
+        return self.back[None, None] @ pose_delta_jacobians(th, self.ctr, self.rot_unit) @ \
+            (np.linalg.inv(pose_deltas(th, self.ctr, self.rot_unit)) @ self.I2P[None])[:, None]
+
+    def cost_and_grad(self, c, g, th):
+        """(cost, gradient [6]) at th [1, 6] from _theta_chain's (c [1], g [1, 6]): the landmark term joins here."""
+        c, g = float(c[0]), g[0]
+        if self.P_pelvis is not None:                               # float64 on the host and cheap: central differences
+            h = 1e-5
+            c += float(self.penalty(th)[0])
+            g = g + (self.penalty(th + h * np.eye(6)) - self.penalty(th - h * np.eye(6))) / (2 * h)
+        return c, g
+
+    def result(self, mean, similarity_cost, trace, renders, done, theta_cma, refine_cost, gradient_evaluations):
+        landmark_cost = 0.0 if self.P_pelvis is None else float(self.penalty(mean[None])[0])
+        final_cost = similarity_cost if self.P_pelvis is None else similarity_cost + landmark_cost
+        D = pose_delta(mean, self.ctr, self.rot_unit)
+        poses = [D @ self.I2P @ self.base[m] @ self.geom.E for m in self.moving]    # P = I2P C2I E
+        return Registration(pose=poses[0], poses=poses, theta=mean, delta=D, cost=np.array(trace), final_cost=final_cost,
+                            similarity_cost=similarity_cost, landmark_cost=landmark_cost, renders=renders, levels=done, centre=self.ctr,
+                            theta_cma=theta_cma, refine_cost=refine_cost, gradient_evaluations=gradient_evaluations)
 
 
 def register(volume, geom, fixed, moving=(0, 1, 2), theta0=None, P0=None, levels=None, popsize=16, generations=80, sigma0=2.0,
@@ -587,64 +894,18 @@ def register(volume, geom, fixed, moving=(0, 1, 2), theta0=None, P0=None, levels
     never costs more than the CMA-ES mean (Registration.theta_cma).  generations=0 with refine=K refines theta0 alone.
     similarity='patch' has no adjoint yet and is refused together with refine.
     """
-    if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or refine < 0 or not float(refine_tol) >= 0.0:
-        raise nat.DflError('register: refine = %r (an integer, at least 0) and refine_tol = %r (not negative)' % (refine, refine_tol))
-    if refine > 0 and similarity == 'patch':
-        raise nat.DflError("register: refine needs the adjoint of the similarity, which similarity='patch' does not have yet")
-    if similarity not in ('global', 'patch'):
-        raise nat.DflError("register: similarity = %r ('global' or 'patch')" % (similarity,))
-    patch = _patch_params(patch_radius, patch_stride, patch_min_count) if similarity == 'patch' else None
-    landmark_weight = float(landmark_weight)
-    if not landmark_weight >= 0.0 or not np.isfinite(landmark_weight):
-        raise nat.DflError('register: a landmark_weight of %r (finite, not negative)' % landmark_weight)
-    if landmarks is not None:
-        if levels is not None:
-            raise nat.DflError('register: landmarks belong to one grid; they are not supported together with levels')
-        if 0 not in tuple(int(m) for m in moving):
-            raise nat.DflError('register: the landmark term follows the pelvis (object 0), which moving = %r holds still' % (tuple(moving),))
-        try:
-            X3d, x2d = landmarks
-        except (TypeError, ValueError):
-            raise nat.DflError('register: landmarks = (X3d [L, 3], x2d [2, L]) expected') from None
-        lands = _usable_landmarks(X3d, x2d, 'register: landmarks')
+    patch, landmark_weight = _cost_options(refine, refine_tol, similarity, patch_radius, patch_stride, patch_min_count, landmark_weight)
+    if landmarks is not None and levels is not None:
+        raise nat.DflError('register: landmarks belong to one grid; they are not supported together with levels')
+    lands = _landmarks_of(landmarks, moving)
     if not isinstance(volume, drr.Volume):
         raise nat.DflError('register needs a drr.Volume (device tensors; no CPU path)')
     if not torch.is_tensor(fixed) or not fixed.is_cuda:
         raise nat.DflError('register needs the fixed image on the GPU (no CPU path)')
-    n_obj = len(geom.objects)
-    moving = tuple(int(m) for m in moving)
-    if not moving or len(set(moving)) != len(moving) or any(not 0 <= m < n_obj for m in moving):
-        raise nat.DflError('register: moving = %r selects no or unknown objects (%d objects)' % (moving, n_obj))
-    lam = int(popsize)
-    if lam < 4:
-        raise nat.DflError('register: a population of %d (at least 4)' % lam)
+    moving, lam = _moving_and_population(geom, moving, popsize)
     theta0 = np.zeros(6) if theta0 is None else np.asarray(theta0, np.float64).reshape(6)
-    I2P = np.asarray(geom.I2P, np.float64)
-    back, Ei = np.linalg.inv(I2P), np.linalg.inv(geom.E)
-    ctr = volume_centre(volume.shape, I2P) if centre is None else np.asarray(centre, np.float64).reshape(3)
-    base = np.stack([ob.c2i for ob in geom.objects])                        # [n_obj, 4, 4]
-    if P0 is not None:
-        P0 = np.asarray(P0, np.float64).reshape(4, 4)
-        for m in moving:
-            base[m] = back @ P0 @ Ei
-    masks = [ob.mask for ob in geom.objects]
-    mv = np.zeros(n_obj, bool)
-    mv[list(moving)] = True
-
-    def c2is_of(thetas):
-        A = back[None] @ pose_deltas(thetas, ctr, rot_unit) @ I2P[None]     # [views, 4, 4]
-        return np.where(mv[None, :, None, None], A[:, None] @ base[None], base[None])
-
-    penalty = None
-    if landmarks is not None and landmark_weight > 0.0:
-        P_pelvis = I2P @ base[0] @ geom.E                                       # P = I2P C2I E
-
-        def penalty(thetas):
-            return landmark_penalty(geom, pose_deltas(thetas, ctr, rot_unit) @ P_pelvis[None], lands[0], lands[1], landmark_weight)
-
-    def costs_of(level, thetas):                                                # what the CMA-ES minimises
-        c = level.costs(c2is_of(thetas), masks)
-        return c if penalty is None else c + penalty(thetas)
+    prob = _Problem(volume.shape, geom, moving, P0, centre, rot_unit, lands, landmark_weight)
+    masks = prob.masks
 
     if levels is None:
         plan = [(None, int(generations), geom.grid, _device_image(fixed, 'the fixed image', 2))]
@@ -667,7 +928,7 @@ def register(volume, geom, fixed, moving=(0, 1, 2), theta0=None, P0=None, levels
     mean, sigma, trace, renders, done = theta0, float(sigma0), [], 0, []
     for k, (factor, gens, grid, img) in enumerate(plan):
         level = _Level(volume, grid, img, mask, lam, step_mm, patch)
-        res = cma_es(lambda th: costs_of(level, th), mean, sigma, lam, gens, seed + k)
+        res = cma_es(lambda th: prob.with_penalty(level.costs(prob.c2is_of(th), masks), th), mean, sigma, lam, gens, seed + k)
         mean, sigma = res.mean, sigma * float(sigma_shrink)
         trace.extend(res.trace.tolist())
         renders += res.evaluations
@@ -676,24 +937,132 @@ def register(volume, geom, fixed, moving=(0, 1, 2), theta0=None, P0=None, levels
     if refine > 0:
         def cost_and_grad(theta):
             th = theta[None]
-            xis = back[None, None] @ pose_delta_jacobians(th, ctr, rot_unit) @ (np.linalg.inv(pose_deltas(th, ctr, rot_unit)) @ I2P[None])[:, None]
-            c, g = level.costs_and_grads(c2is_of(th), masks, xis, list(moving))
-            c, g = float(c[0]), g[0]
-            if penalty is not None:                                 # float64 on the host and cheap: central differences
-                h = 1e-5
-                c += float(penalty(th)[0])
-                g = g + (penalty(th + h * np.eye(6)) - penalty(th - h * np.eye(6))) / (2 * h)
-            return c, g
+            return prob.cost_and_grad(*level.costs_and_grads(prob.c2is_of(th), masks, prob.xis_of(th), list(moving)), th)
 
         fin = bfgs(cost_and_grad, mean, int(refine), float(refine_tol))
         mean, refine_cost, gradient_evaluations = fin.x, fin.trace, fin.evaluations
         renders += fin.evaluations
-    similarity_cost = float(level.costs(c2is_of(mean[None]), masks)[0])
-    landmark_cost = 0.0 if penalty is None else float(penalty(mean[None])[0])
-    final_cost = similarity_cost if penalty is None else similarity_cost + landmark_cost
-    renders += 1
-    D = pose_delta(mean, ctr, rot_unit)
-    poses = [D @ I2P @ base[m] @ geom.E for m in moving]                    # P = I2P C2I E
-    return Registration(pose=poses[0], poses=poses, theta=mean, delta=D, cost=np.array(trace), final_cost=final_cost,
-                        similarity_cost=similarity_cost, landmark_cost=landmark_cost, renders=renders, levels=done, centre=ctr,
-                        theta_cma=theta_cma, refine_cost=refine_cost, gradient_evaluations=gradient_evaluations)
+    similarity_cost = float(level.costs(prob.c2is_of(mean[None]), masks)[0])
+    return prob.result(mean, similarity_cost, trace, renders + 1, done, theta_cma, refine_cost, gradient_evaluations)
+
+
+def _same(a, b):
+    return np.array_equal(np.asarray(a, np.float64), np.asarray(b, np.float64))
+
+
+def default_max_views(H, W):
+    """The most views register_many renders at once by default: at most 65535, and at most 1 GiB of float32 pixels."""
+    return max(1, min(65535, (1 << 30) // (4 * int(H) * int(W))))
+
+
+def register_many(volume, geoms, fixed, moving=(0, 1, 2), theta0=None, P0=None, popsize=16, generations=80, sigma0=2.0, step_mm=1.0,
+                  masks=None, seed=0, centre=None, rot_unit=ROT_UNIT, similarity='global', patch_radius=7, patch_stride=4,
+                  patch_min_count=None, landmarks=None, landmark_weight=0.0, refine=0, refine_tol=1e-4, max_views=None, **unknown):
+    """register() for N projections of one volume at once: [Registration] * N.
+
+    geoms is a list of N drr.Geometry that share the output grid, K, I2P and the object masks (each has its own object
+    poses and may have its own E); fixed is float32 [N, H, W] on the GPU, masks uint8 [N, H, W] or None; theta0 [N, 6],
+    P0 [N, 4, 4] and landmarks (a list of N entries, (X3d, x2d) or None) are per problem or None; everything else is one
+    value for all.  Problem i is register(volume, geoms[i], fixed[i], theta0=theta0[i], P0=P0[i], mask=masks[i],
+    landmarks=landmarks[i], seed=seed, ...), and its theta, cost, theta_cma, refine_cost, final_cost, similarity_cost,
+    landmark_cost, pose, renders and gradient_evaluations have that call's bytes.
+
+    The device works on all running problems at once: a generation is one render of popsize views per problem and one
+    similarity launch against the bank of fixed images (SimilarityBank, PatchSimilarityBank); a round of the finish is one
+    render of one view per problem still running, one dfl_sim_bank_gradncc_bwd and one dfl_drr_pose_grad.  The float64
+    host work is done problem by problem with the functions register() uses.  max_views caps the views of one render
+    (default: default_max_views); problems are processed in chunks of max_views // popsize, which changes no result.
+    There is no coarse-to-fine here (no levels)."""
+    if unknown:
+        raise nat.DflError('register_many: no argument %s (levels: there is no coarse-to-fine here; register() has it)'
+                           % ', '.join(sorted(unknown)))
+    patch, landmark_weight = _cost_options(refine, refine_tol, similarity, patch_radius, patch_stride, patch_min_count, landmark_weight)
+    try:
+        geoms = list(geoms)
+    except TypeError:
+        raise nat.DflError('register_many: geoms is a list of drr.Geometry, one per problem') from None
+    N = len(geoms)
+    if N < 1:
+        raise nat.DflError('register_many: no problem (N = 0)')
+
+    def per_problem(what, value, shape):
+        if value is None:
+            return [None] * N
+        if shape is not None:
+            value = np.asarray(value, np.float64)
+            if value.shape != (N,) + shape:
+                raise nat.DflError('register_many: %s has shape %s for %d problems: %s expected' % (what, value.shape, N, (N,) + shape))
+        elif not isinstance(value, (list, tuple)) or len(value) != N:
+            raise nat.DflError('register_many: %s is a list of %d entries, one per problem' % (what, N))
+        return list(value)
+
+    theta0s, P0s = per_problem('theta0', theta0, (6,)), per_problem('P0', P0, (4, 4))
+    lands = [_landmarks_of(l, moving) for l in per_problem('landmarks', landmarks, None)]
+    for what, t in (('fixed', fixed), ('masks', masks)):
+        if t is not None and (not hasattr(t, 'shape') or len(t.shape) != 3 or int(t.shape[0]) != N):
+            raise nat.DflError('register_many: %s is [N, H, W] with N = %d problems, got %s' % (what, N, tuple(getattr(t, 'shape', ()))))
+    g0 = geoms[0]
+    for i, g in enumerate(geoms):
+        if not isinstance(g, drr.Geometry):
+            raise nat.DflError('register_many: geoms[%d] is no drr.Geometry' % i)
+        if not (_same(g.grid.Q, g0.grid.Q) and (g.grid.H, g.grid.W) == (g0.grid.H, g0.grid.W) and _same(g.K, g0.K) and _same(g.I2P, g0.I2P) and
+                [ob.mask for ob in g.objects] == [ob.mask for ob in g0.objects]):
+            raise nat.DflError('register_many: geoms[%d] differs from geoms[0] in the grid, K, I2P or the object masks, which all '
+                               'problems share' % i)
+    moving, lam = _moving_and_population(g0, moving, popsize)
+    H, W = g0.grid.H, g0.grid.W
+    cap = default_max_views(H, W) if max_views is None else max_views
+    if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or cap < lam or cap > 65535:
+        raise nat.DflError('register_many: max_views = %r (an integer from popsize = %d to 65535)' % (max_views, lam))
+    if not isinstance(volume, drr.Volume):
+        raise nat.DflError('register_many needs a drr.Volume (device tensors; no CPU path)')
+    for what, t in (('fixed', fixed), ('masks', masks)):
+        if t is not None and (not torch.is_tensor(t) or not t.is_cuda):
+            raise nat.DflError('register_many needs %s on the GPU (no CPU path)' % what)
+    fixed = _device_image(fixed, 'the fixed images', 3)
+    if tuple(fixed.shape[1:]) != (H, W):
+        raise nat.DflError('register: the fixed image is %s, the output grid %d x %d' % (tuple(fixed.shape[1:]), H, W))
+    probs = [_Problem(volume.shape, g, moving, P0s[i], centre, rot_unit, lands[i], landmark_weight) for i, g in enumerate(geoms)]
+    starts = [np.zeros(6) if t is None else t for t in theta0s]
+    per, out = max(1, int(cap) // lam), []
+    for lo in range(0, N, per):
+        hi = min(N, lo + per)
+        out.extend(_register_chunk(volume, g0.grid, probs[lo:hi], starts[lo:hi], fixed[lo:hi], None if masks is None else masks[lo:hi],
+                                   lam, int(generations), float(sigma0), step_mm, seed, patch, int(refine), float(refine_tol)))
+    return out
+
+
+def _register_chunk(volume, grid, probs, starts, fixed, masks, lam, generations, sigma0, step_mm, seed, patch, refine, refine_tol):
+    """register_many for problems whose lambda candidates fit into one render together."""
+    n, moving, obj_masks = len(probs), list(probs[0].moving), probs[0].masks
+    level = _Level(volume, grid, None, None, n * lam, step_mm, patch, bank=(fixed, masks))
+
+    def similarity_costs(idx, c2is):
+        """One render of the views c2is (a list of [views_i, n_obj, 4, 4], one per problem of idx) and one bank launch."""
+        fixed_of = np.repeat(np.asarray(idx, np.int32), [c.shape[0] for c in c2is])
+        return level.costs(np.concatenate(c2is), obj_masks, fixed_of)
+
+    def generation(idx, thetas):
+        c = similarity_costs(idx, [probs[i].c2is_of(th) for i, th in zip(idx, thetas)])
+        return [probs[i].with_penalty(c[k * lam:(k + 1) * lam], th) for k, (i, th) in enumerate(zip(idx, thetas))]
+
+    cma = lockstep([cma_steps(starts[i], sigma0, lam, generations, seed) for i in range(n)], generation)
+    means, fins = [r.mean for r in cma], [None] * n
+    if refine > 0:
+        def round_of_the_finish(idx, thetas):
+            ths = [t[None] for t in thetas]
+            recs, att, keep = level._render(np.concatenate([probs[i].c2is_of(th) for i, th in zip(idx, ths)]), obj_masks)
+            both, piv = level._cost_and_moments(recs, att, *level.sim.cost_and_adjoint(att, np.asarray(idx, np.int32)))
+            del keep
+            return [probs[i].cost_and_grad(*_theta_chain(both[k:k + 1], piv[k:k + 1], probs[i].xis_of(th), moving), th)
+                    for k, (i, th) in enumerate(zip(idx, ths))]
+
+        fins = lockstep([bfgs_steps(means[i], refine, refine_tol) for i in range(n)], round_of_the_finish)
+    ends = [means[i] if fins[i] is None else fins[i].x for i in range(n)]
+    last = similarity_costs(list(range(n)), [probs[i].c2is_of(ends[i][None]) for i in range(n)])
+    out = []
+    for i in range(n):
+        evals = 0 if fins[i] is None else fins[i].evaluations
+        out.append(probs[i].result(ends[i], float(last[i]), cma[i].trace.tolist(), cma[i].evaluations + evals + 1,
+                                   [(None, generations, grid.H, grid.W)], means[i], np.zeros(0) if fins[i] is None else fins[i].trace, evals))
+    return out

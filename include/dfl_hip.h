@@ -48,8 +48,8 @@ const char* dfl_last_error(void);
  * bn_bwd_finalize, bn_relu_bwd, affine_copy, pool, head_fwd, head_bwd, loss, ensemble, op, reduce_job, prep,
  * est_lands, upsample, augment_args, augment_item, overlay, resample_plan, resample_args, fullres, mesh_mc,
  * mesh_decode, mesh_topo, mesh_csr, mesh_smooth, mesh_xform, mesh_normals, preproc_projs, preproc_segs, restore_labels,
- * sim_prepare, sim_gradncc, expose, sim_patch_prepare, sim_patch_gradncc, sim_gradncc_bwd, drr_pose_grad, drr_object,
- * drr_args, optim_pack): lets a
+ * sim_prepare, sim_gradncc, expose, sim_patch_prepare, sim_patch_gradncc, sim_gradncc_bwd, drr_pose_grad,
+ * sim_bank_gradncc, sim_bank_gradncc_bwd, sim_patch_bank_gradncc, drr_object, drr_args, optim_pack): lets a
  * binding written in another language verify the size of its struct mirrors at load time.  Returns -1 past the end.
  * Sizes say nothing about field order or type: the Python binding derives its structs, constants and signatures from this
  * file (dfl_amd/_cabi.py), and tests/test_cabi_cpu.py holds every field offset against a C compiler's offsetof. */
@@ -1196,6 +1196,67 @@ typedef struct {
 int dfl_sim_patch_gradncc(const dfl_sim_patch_gradncc_args* a, dfl_stream_t stream);
 int64_t dfl_sim_patch_count(int32_t H, int32_t W, int32_t rho, int32_t stride);
 int64_t dfl_sim_patch_scratch_doubles(int32_t V, int32_t H, int32_t W, int32_t rho, int32_t stride);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * The three similarity entry points above against a BANK of F fixed images: view v is scored
+ * against image fixed_of[v].  fx, fy, counted are [F][H][W] and totals [F][DFL_SIM_TOTALS]; for patches ptotals is
+ * [F][P][DFL_SIM_TOTALS], pflags [F][P], pcount [F][2].  Image f's slice of every bank is what dfl_sim_prepare (and
+ * dfl_sim_patch_prepare) writes for it, called once per image on the slices.  fixed_of is a device array [V].
+ * The kernels are those of the single-image entry points, which differ only in where a view's planes and totals start:
+ * cost[v] and d_moving[v] have the bits the single-image entry point gives view v against image fixed_of[v], whatever V,
+ * F and the other entries of fixed_of are.  No atomics.  Scratch: dfl_sim_scratch_doubles,
+ * dfl_sim_gradncc_bwd_scratch_doubles, dfl_sim_patch_scratch_doubles.
+ * fixed_of cannot be checked on the host: a view whose fixed_of[v] is outside [0, F) reads nothing from the banks, gets
+ * cost[v] = NaN and, in the adjoint, d_moving[v] = 0; the other views are not affected.
+ * Refused with nothing launched: what the single-image entry point refuses, F < 1, F > 65535, a NULL fixed_of,
+ * F H W >= 2^31.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct {
+  const float* moving;            /* [V][H][W] */
+  const float* fx;                /* [F][H][W] */
+  const float* fy;                /* [F][H][W] */
+  const unsigned char* counted;   /* [F][H][W] */
+  const double* totals;           /* [F][DFL_SIM_TOTALS] */
+  const int32_t* fixed_of;        /* [V], device */
+  double* scratch;                /* [V][bands][6] */
+  double* cost;                   /* [V] */
+  const void* reserved;           /* not read */
+  int64_t scratch_doubles;        /* what scratch holds */
+  int32_t V, H, W, F;
+} dfl_sim_bank_gradncc_args;
+int dfl_sim_bank_gradncc(const dfl_sim_bank_gradncc_args* a, dfl_stream_t stream);
+
+typedef struct {
+  const float* moving;            /* [V][H][W] */
+  const float* fx;                /* [F][H][W] */
+  const float* fy;                /* [F][H][W] */
+  const unsigned char* counted;   /* [F][H][W] */
+  const double* totals;           /* [F][DFL_SIM_TOTALS] */
+  const int32_t* fixed_of;        /* [V], device */
+  double* scratch;
+  double* cost;                   /* [V] */
+  float* d_moving;                /* [V][H][W] */
+  const void* reserved;           /* not read */
+  int64_t scratch_doubles;        /* what scratch holds */
+  int32_t V, H, W, F;
+} dfl_sim_bank_gradncc_bwd_args;
+int dfl_sim_bank_gradncc_bwd(const dfl_sim_bank_gradncc_bwd_args* a, dfl_stream_t stream);
+
+typedef struct {
+  const float* moving;            /* [V][H][W] */
+  const float* fx;                /* [F][H][W] */
+  const float* fy;                /* [F][H][W] */
+  const unsigned char* counted;   /* [F][H][W] */
+  const double* ptotals;          /* [F][P][DFL_SIM_TOTALS] */
+  const unsigned char* pflags;    /* [F][P] */
+  const int32_t* pcount;          /* [F][2] */
+  const int32_t* fixed_of;        /* [V], device */
+  double* scratch;                /* [V][PR][2] */
+  double* cost;                   /* [V] */
+  int64_t scratch_doubles;        /* what scratch holds */
+  int32_t V, H, W, rho, stride, F;
+} dfl_sim_patch_bank_gradncc_args;
+int dfl_sim_patch_bank_gradncc(const dfl_sim_patch_bank_gradncc_args* a, dfl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Detector model: rendered line integrals -> detector intensities (csrc/expose.hip; DESIGN.md section 17 states the

@@ -13,6 +13,11 @@ phantom's poses and the candidates are drawn around a start 2 units away in ever
               adjoint of the similarity (dfl_sim_gradncc_bwd) and the pose gradient (dfl_drr_pose_grad) timed as calls with
               device events, the whole evaluation (with packing, uploads, the copy and the chain on the host) by the wall
               clock, next to one cost evaluation of one view; in render-equivalents = (render + adjoint + pose gradient) / render
+  many        16 problems with lambda = 32 (register_many) against the same 16 one after the other, in this
+              process and run, alternating windows: (i) a generation of register_many against a generation of each of 16
+              register() calls, (ii) one lockstep cost-and-gradient round of the finish against 16 single evaluations (wall
+              clock), (iii) one dfl_sim_bank_gradncc launch for 512 views against 16 dfl_sim_gradncc launches of 32 (device
+              events); (i) and (ii) carry a check: together is no slower than the loop beyond the spread between windows
   host        what is left of a whole generation of register(): sampling, the batched packing, the upload of the
               records, the copy of 32 doubles and the CMA-ES update
 
@@ -40,6 +45,7 @@ sys.path.insert(0, os.path.join(ROOT, 'tools'))
 import bench_drr as B  # noqa: E402
 
 FACTOR, LAMBDA, STEP_MM = 8, 32, 1.0
+MANY = 16                        # problems of the register_many comparison
 PATCH_RADIUS, PATCH_STRIDE = 7, 4
 THETA0 = (2.0, -2.0, 2.0, 2.0, -2.0, 2.0)
 
@@ -182,6 +188,96 @@ def main():
     print('one view: render %.4f ms, adjoint %.4f ms, pose gradient %.4f ms = %.2f render-equivalents; wall clock of an evaluation: cost '
           '%.3f ms, cost and gradient %.3f ms' % (grad['render']['ms'], grad['adjoint']['ms'], grad['pose_gradient']['ms'],
                                                    grad['render_equivalents'], grad['cost_wall_ms'], grad['cost_and_gradient_wall_ms']), flush=True)
+    # N problems at once (register_many) against the same N one after the other, in this process
+    N = MANY
+    offsets = 1.5 * np.random.default_rng(1).standard_normal((N, 6))
+    geoms, fixeds = [], []
+    for t in offsets:                                                                 # every problem: its own poses and fixed image
+        Dn = reg.pose_delta(t, ctr)
+        named = {k: Dn @ P for k, P in poses.items()}
+        obs = [drr.Obj(back @ named[k] @ np.linalg.inv(E), ob.mask) for k, ob in zip(drr.POSES, objects)]
+        geoms.append(drr.Geometry(K, E, named, I2P, G, obs, grid))
+        fixeds.append(drr.render(vol, obs, grid, want_labels=False)[0])
+    fixed_n = torch.stack(fixeds).contiguous()
+    theta_n = np.tile(np.asarray(THETA0), (N, 1))
+
+    def pair(many, loop, unit):
+        """`reps` windows of both, alternating; ms per `unit` of each, their ratio and the check against the spread."""
+        many(), loop()                                                                # warm-up
+        a, b = [], []
+        for _ in range(args.reps):
+            for fn, into in ((many, a), (loop, b)):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                n = fn()
+                torch.cuda.synchronize()
+                into.append(1e3 * (time.perf_counter() - t0) / n)
+        spread = max(max(a) - min(a), max(b) - min(b))
+        ma, mb = statistics.median(a), statistics.median(b)
+        return {'unit': unit, 'together_ms': round(ma, 4), 'together_min_max_ms': [round(min(a), 4), round(max(a), 4)],
+                'one_after_the_other_ms': round(mb, 4), 'one_after_the_other_min_max_ms': [round(min(b), 4), round(max(b), 4)],
+                'ratio_together_over_loop': round(ma / mb, 4), 'spread_ms': round(spread, 4),
+                'rule': 'together_ms <= one_after_the_other_ms + the larger spread (max - min) of the two', 'ok': bool(ma <= mb + spread)}
+
+    gens_many = max(int(args.window / (N * 1e-3 * res['generation']['ms'])) + 1, 3)
+
+    def many_generations():
+        reg.register_many(vol, geoms, fixed_n, theta0=theta_n, popsize=LAMBDA, generations=gens_many, step_mm=STEP_MM)
+        return gens_many + 1                                                          # + 1: the evaluation of the final means
+
+    def loop_generations():
+        for i in range(N):
+            reg.register(vol, geoms[i], fixed_n[i], theta0=theta_n[i], popsize=LAMBDA, generations=gens_many, step_mm=STEP_MM)
+        return gens_many + 1
+
+    many = {'problems': N, 'lambda': LAMBDA, 'generations_per_window': gens_many,
+            'generation': pair(many_generations, loop_generations, 'one generation of %d problems (%d views)' % (N, N * LAMBDA))}
+    # one round of the finish: a cost-and-gradient evaluation of every problem at its start
+    probs = [reg._Problem(vol.shape, g_, (0, 1, 2), None, None, reg.ROT_UNIT, None, 0.0) for g_ in geoms]
+    c2i_n = [p.c2is_of(th1) for p in probs]
+    xis_n = [p.xis_of(th1) for p in probs]
+    level_n = reg._Level(vol, grid, None, None, N, STEP_MM, None, bank=(fixed_n, None))
+    levels_1 = [reg._Level(vol, grid, fixed_n[i], None, 1, STEP_MM) for i in range(N)]
+    which = np.arange(N, dtype=np.int32)
+    rounds = max(int(args.window / (N * 1e-3 * grad['cost_and_gradient_wall_ms'])) + 1, 3)
+
+    def round_together():
+        for _ in range(rounds):
+            recs, att_n, alive = level_n._render(np.concatenate(c2i_n), masks)
+            both, piv = level_n._cost_and_moments(recs, att_n, *level_n.sim.cost_and_adjoint(att_n, which))
+            for k in range(N):
+                reg._theta_chain(both[k:k + 1], piv[k:k + 1], xis_n[k], [0, 1, 2])
+        return rounds
+
+    def round_loop():
+        for _ in range(rounds):
+            for k in range(N):
+                levels_1[k].costs_and_grads(c2i_n[k], masks, xis_n[k], [0, 1, 2])
+        return rounds
+
+    many['gradient_round'] = pair(round_together, round_loop, 'one cost-and-gradient evaluation of each of %d problems' % N)
+    # the similarity alone: one bank launch for N lambda views against N launches of lambda views
+    att_many = att.repeat(N, 1, 1).contiguous()
+    bank = reg.SimilarityBank(fixed_n, None, N * LAMBDA)
+    ba = bank.args(att_many, bank.fixed_of(np.repeat(which, LAMBDA), N * LAMBDA))
+    sims = [reg.Similarity(fixed_n[i], None, LAMBDA) for i in range(N)]
+    sas = [s_.args(att_many[i * LAMBDA:(i + 1) * LAMBDA]) for i, s_ in enumerate(sims)]
+    nat.call('dfl_sim_bank_gradncc', ba, stream)
+    for sa_ in sas:
+        nat.call('dfl_sim_gradncc', sa_, stream)
+    assert torch.equal(bank.out, torch.cat([s_.out for s_ in sims]))                  # the same bits, as the tests hold
+    one_launch = windows(lambda: nat.call('dfl_sim_bank_gradncc', ba, stream), args.window, args.reps)
+    n_launches = windows(lambda: [nat.call('dfl_sim_gradncc', sa_, stream) for sa_ in sas], args.window, args.reps)
+    many['similarity'] = {'bank_launch_%d_views' % (N * LAMBDA): one_launch, '%d_launches_of_%d_views' % (N, LAMBDA): n_launches,
+                          'ratio_bank_over_launches': round(one_launch['ms'] / n_launches['ms'], 4)}
+    res['many'] = many
+    print('%d problems, lambda %d: generation %.3f ms together, %.3f ms one after the other (ratio %.3f, %s); gradient round %.3f ms '
+          'together, %.3f ms one after the other (ratio %.3f, %s); similarity %.4f ms in one bank launch, %.4f ms in %d launches (ratio %.3f)'
+          % (N, LAMBDA, many['generation']['together_ms'], many['generation']['one_after_the_other_ms'],
+             many['generation']['ratio_together_over_loop'], 'ok' if many['generation']['ok'] else 'SLOWER',
+             many['gradient_round']['together_ms'], many['gradient_round']['one_after_the_other_ms'],
+             many['gradient_round']['ratio_together_over_loop'], 'ok' if many['gradient_round']['ok'] else 'SLOWER',
+             one_launch['ms'], n_launches['ms'], N, many['similarity']['ratio_bank_over_launches']), flush=True)
     res['host_side'] = {'ms': round(res['generation']['ms'] - res['render']['ms'] - res['similarity']['ms'], 4)}
     print('180 x 180, lambda 32: generation %.3f ms = render %.3f + similarity %.3f (torch ops %.3f) + host %.3f (of which packing %.3f)'
           % (res['generation']['ms'], res['render']['ms'], res['similarity']['ms'], res['similarity_torch_ops']['ms'], res['host_side']['ms'],
