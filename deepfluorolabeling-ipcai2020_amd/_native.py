@@ -39,7 +39,7 @@ _SIZEOF_ORDER = [ConvArgs, WgradArgs, PackJob, BnFinalizeArgs, ColstatsArgs, BnB
                  UpsampleArgs, AugmentArgs, AugmentItem, OverlayArgs, ResamplePlan, ResampleArgs, FullresArgs, MeshMcArgs, MeshDecodeArgs,
                  MeshTopoArgs, MeshCsrArgs, MeshSmoothArgs, MeshXformArgs, MeshNormalsArgs, PreprocProjsArgs, PreprocSegsArgs,
                  RestoreLabelsArgs, SimPrepareArgs, SimGradnccArgs, ExposeArgs, SimPatchPrepareArgs, SimPatchGradnccArgs,
-                 SimGradnccBwdArgs, DrrPoseGradArgs, SimBankGradnccArgs, SimBankGradnccBwdArgs, SimPatchBankGradnccArgs, DrrObject, DrrArgs,
+                 SimGradnccBwdArgs, SimPatchWeightsArgs, SimPatchEvalArgs, DrrPoseGradArgs, SimBankGradnccArgs, SimBankGradnccBwdArgs, SimPatchBankGradnccArgs, DrrObject, DrrArgs,
                  OptimPackArgs]
 
 

@@ -84,4 +84,27 @@ __device__ __forceinline__ double sim_ncc(double n, double sa, double saa, doubl
   return (sab - sa * sb / n) / sqrt(va * vb);
 }
 
+// ---- what the two adjoint kernels share (sim_adjoint_kernel, csrc/sim.hip; sim_patch_adjoint_kernel, csrc/sim_patch.hip) ------------
+constexpr int SIM_TILE = 16;         // an adjoint kernel's tile of output pixels; 16 x 16 = SIM_THREADS
+constexpr int SIM_TILE_IN = SIM_TILE + 4, SIM_TILE_G = SIM_TILE + 2;   // the tile of `moving` with a halo of 2; of g with a halo of 1
+
+// The tile of one view's `moving` at (r0, c0) with a halo of 2 -> LDS, 0 outside the image
+__device__ __forceinline__ void sim_stage_tile(float (&sm)[SIM_TILE_IN][SIM_TILE_IN + 1], const float* __restrict__ img, int H, int W, int r0,
+                                               int c0) {
+  for (int i = threadIdx.x; i < SIM_TILE_IN * SIM_TILE_IN; i += SIM_THREADS) {
+    const int lr = i / SIM_TILE_IN, lc = i % SIM_TILE_IN, r = r0 - 2 + lr, c = c0 - 2 + lc;
+    sm[lr][lc] = r >= 0 && r < H && c >= 0 && c < W ? img[(size_t)r * W + c] : 0.f;
+  }
+}
+
+// Sobel^T at output pixel (tr, tc) of the tile from g on the 18 x 18 pixels around it: pixel q is at offset (dr, dc) in the window
+// of p = q - (dr, dc), which sits at sg[tr + 1 - dr][tc + 1 - dc]; Sobel x has weight dc (2 - |dr|) there, Sobel y dr (2 - |dc|)
+__device__ __forceinline__ float sim_sobel_gather(const float (&sgx)[SIM_TILE_G][SIM_TILE_G + 1], const float (&sgy)[SIM_TILE_G][SIM_TILE_G + 1],
+                                                  int tr, int tc) {
+#pragma clang fp contract(off)
+  const float x = ((sgx[tr + 2][tc] + 2.f * sgx[tr + 1][tc]) + sgx[tr][tc]) - ((sgx[tr + 2][tc + 2] + 2.f * sgx[tr + 1][tc + 2]) + sgx[tr][tc + 2]);
+  const float y = ((sgy[tr][tc + 2] + 2.f * sgy[tr][tc + 1]) + sgy[tr][tc]) - ((sgy[tr + 2][tc + 2] + 2.f * sgy[tr + 2][tc + 1]) + sgy[tr + 2][tc]);
+  return x + y;
+}
+
 }  // namespace dfl

@@ -112,7 +112,6 @@ inline int sim_bands(int H) { return (int)ceil_div(H - 2, SIM_ROWS); }
 // With a the moving and b the fixed Sobel values of one direction, d(-ncc / 2) / d a_p = alpha (b_p - mean b) + beta (a_p - mean a)
 // at a counted pixel, alpha = -1 / (2 sqrt(va vb)), beta = cab / (2 va sqrt(va vb)); both 0 where the forward rule makes the ncc 0.
 constexpr int SIM_COEF = 8;          // per view: alpha, beta, mean a, mean b of x, then of y (float32)
-constexpr int SIM_TILE = 16;         // the adjoint kernel's tile of output pixels; 16 x 16 = SIM_THREADS
 
 // One thread per view: the view's records added in index order (as sim_finish_kernel adds them), the coefficients in float64
 __global__ __launch_bounds__(64) void sim_coef_kernel(const double* __restrict__ scratch, const double* __restrict__ totals,
@@ -161,7 +160,7 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_adjoint_kernel(const float* _
                                                                   float* __restrict__ d_moving, int H, int W, int F) {
   // every product is rounded on its own: where moving matches fixed the two terms of g cancel exactly, which an FMA would undo
 #pragma clang fp contract(off)
-  constexpr int IN = SIM_TILE + 4, G = SIM_TILE + 2;
+  constexpr int IN = SIM_TILE_IN, G = SIM_TILE_G;
   __shared__ float sm[IN][IN + 1];
   __shared__ float sgx[G][G + 1], sgy[G][G + 1];
   const int view = blockIdx.z;
@@ -177,10 +176,7 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_adjoint_kernel(const float* _
   fy += plane;
   counted += plane;
   const float* img = moving + (size_t)view * H * W;
-  for (int i = threadIdx.x; i < IN * IN; i += SIM_THREADS) {
-    const int lr = i / IN, lc = i % IN, r = r0 - 2 + lr, c = c0 - 2 + lc;
-    sm[lr][lc] = r >= 0 && r < H && c >= 0 && c < W ? img[(size_t)r * W + c] : 0.f;
-  }
+  sim_stage_tile(sm, img, H, W, r0, c0);
   const float* cf = coef + (size_t)view * SIM_COEF;
   const float ax = cf[0], bx = cf[1], max_ = cf[2], mbx = cf[3], ay = cf[4], by = cf[5], may = cf[6], mby = cf[7];
   __syncthreads();
@@ -204,13 +200,7 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_adjoint_kernel(const float* _
   }
   __syncthreads();
   const int tr = threadIdx.x / SIM_TILE, tc = threadIdx.x % SIM_TILE, r = r0 + tr, c = c0 + tc;
-  if (r < H && c < W) {
-    // pixel q is at offset (dr, dc) in the window of p = q - (dr, dc); p sits at sg[tr + 1 - dr][tc + 1 - dc].
-    // Sobel x has weight dc (2 - |dr|) there, Sobel y dr (2 - |dc|)
-    const float x = ((sgx[tr + 2][tc] + 2.f * sgx[tr + 1][tc]) + sgx[tr][tc]) - ((sgx[tr + 2][tc + 2] + 2.f * sgx[tr + 1][tc + 2]) + sgx[tr][tc + 2]);
-    const float y = ((sgy[tr][tc + 2] + 2.f * sgy[tr][tc + 1]) + sgy[tr][tc]) - ((sgy[tr + 2][tc + 2] + 2.f * sgy[tr + 2][tc + 1]) + sgy[tr + 2][tc]);
-    d_moving[((size_t)view * H + r) * W + c] = x + y;
-  }
+  if (r < H && c < W) d_moving[((size_t)view * H + r) * W + c] = sim_sobel_gather(sgx, sgy, tr, tc);
 }
 
 // records [V][bands][6], then the coefficients [V][8] float32

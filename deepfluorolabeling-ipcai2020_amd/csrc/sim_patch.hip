@@ -15,6 +15,10 @@
 //   block_sum's fixed order and writes ONE record of two doubles with plain stores.
 //   sim_patch_finish_kernel (one wave per view): adds the PR records in index order, divides by pcount, writes the cost.
 // No atomics: the bits of a view's cost depend on that view's pixels and on H, W, rho and the stride only.
+// dfl_sim_patch_eval is the same forward with two optional parts: pweights / pwsum weigh every patch
+// by the energy of its fixed gradient (sim_patch_weights_kernel, once per fixed image), and d_moving asks for the adjoint:
+// phase 2 then also leaves eight float32 per patch (c alpha, c beta, mean a, mean b of x, then of y; c the patch's share of
+// the cost) and sim_patch_adjoint_kernel gathers them per pixel.
 // dfl_sim_patch_bank_gradncc launches the same two kernels with fixed_of [V] and F: view v reads the
 // planes, patch totals, flags and counts of image fixed_of[v] of a bank (sim_image_of, csrc/sim.h); dfl_sim_patch_gradncc
 // passes fixed_of = nullptr and every view reads image 0.
@@ -89,12 +93,63 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_patch_count_kernel(const unsi
   }
 }
 
+// One workgroup, once per fixed image: w_d[p] = sum (f_d - mean f_d)^2 over the counted pixels of a patch that counts in d, else
+// 0.  Thread t adds the patches t, t + 256, ... in index order, then block_sum: the sums are no integers, the order is the contract
+__global__ __launch_bounds__(SIM_THREADS) void sim_patch_weights_kernel(const double* __restrict__ ptotals,
+                                                                        const unsigned char* __restrict__ pflags,
+                                                                        double* __restrict__ pweights, double* __restrict__ pwsum, int64_t P) {
+  __shared__ double lds[2 * 4];
+  double s[2] = {0.0, 0.0};
+  for (int64_t p = threadIdx.x; p < P; p += SIM_THREADS) {
+    const unsigned char f = pflags[p];
+    const double* t = ptotals + p * SIM_FIXED;
+    const double wx = (f & 1) ? sim_var(t[0], t[1], t[2]) : 0.0, wy = (f & 2) ? sim_var(t[0], t[3], t[4]) : 0.0;
+    pweights[p * 2] = wx;
+    pweights[p * 2 + 1] = wy;
+    s[0] += wx;
+    s[1] += wy;
+  }
+  block_sum<2>(s, lds);
+  if (threadIdx.x == 0) {
+    pwsum[0] = s[0];
+    pwsum[1] = s[1];
+  }
+}
+
+constexpr int SIM_PCOEF = 8;         // per view and patch: c alpha, c beta, mean a, mean b of x, then of y (float32)
+
+// The four coefficients of one direction of one patch that counts in it (the rule of sim_ncc and sim_coef_kernel, csrc/sim.hip),
+// formed in float64 and rounded once; share = the patch's part of the cost: w / pwsum, or 1 / pcount
+__device__ __forceinline__ void sim_patch_coef(float* __restrict__ out, double share, double n, double sa, double saa, double sb, double sbb,
+                                               double sab) {
+  double ca = 0.0, cb = 0.0, ma = 0.0, mb = 0.0;
+  const double va = sim_var(n, sa, saa), vb = sim_var(n, sb, sbb);
+  if (sim_live(va, saa) && sim_live(vb, sbb)) {
+    const double root = sqrt(va * vb);
+    ca = share * (-0.5 / root);
+    cb = share * (0.5 * (sab - sa * sb / n) / (va * root));
+    ma = sa / n;
+    mb = sb / n;
+  }
+  out[0] = (float)ca;
+  out[1] = (float)cb;
+  out[2] = (float)ma;
+  out[3] = (float)mb;
+}
+
+// pweights (with pwsum) and coef are optional: both nullptr is the cost of section 18 as dfl_sim_patch_gradncc always gave it.
+// One body, two instantiations: EXT = false is launched when both are nullptr and holds nothing of the two parts, so the existing
+// entry points keep their registers (62 VGPRs, 8 waves per SIMD) next to the 118 of the coefficients' float64 arithmetic
+template <bool EXT>
 __global__ __launch_bounds__(SIM_THREADS) void sim_patch_gradncc_kernel(const float* __restrict__ moving, const float* __restrict__ fx,
                                                                         const float* __restrict__ fy,
                                                                         const unsigned char* __restrict__ counted,
                                                                         const double* __restrict__ ptotals,
                                                                         const unsigned char* __restrict__ pflags,
                                                                         const int32_t* __restrict__ fixed_of,
+                                                                        const int32_t* __restrict__ pcount,
+                                                                        const double* __restrict__ pweights,
+                                                                        const double* __restrict__ pwsum, float* __restrict__ coef,
                                                                         double* __restrict__ scratch, int H, int W, int S, int stride,
                                                                         int PC, int F) {
   extern __shared__ double cols[];                                      // [SIM_MOVING][W - 2]
@@ -109,6 +164,13 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_patch_gradncc_kernel(const fl
   counted += plane;
   ptotals += patches * SIM_FIXED;
   pflags += patches;
+  const bool weighted = EXT && pweights != nullptr, with_coef = EXT && coef != nullptr;
+  if (weighted) {
+    pweights += patches * 2;
+    pwsum += 2 * (size_t)f;
+  }
+  pcount += 2 * (size_t)f;
+  if (with_coef) coef += (size_t)view * gridDim.x * PC * SIM_PCOEF;
   const float* img = moving + (size_t)view * H * W;
   for (int j = threadIdx.x; j < wi; j += SIM_THREADS) {
     double s[SIM_MOVING] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -124,7 +186,13 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_patch_gradncc_kernel(const fl
   for (int b = threadIdx.x; b < PC; b += SIM_THREADS) {
     const size_t p = (size_t)a * PC + b;
     const unsigned char flags = pflags[p];
-    if (flags == 0) continue;
+    if (flags == 0) {
+      if (with_coef) {
+#pragma unroll
+        for (int q = 0; q < SIM_PCOEF; ++q) coef[p * SIM_PCOEF + q] = 0.f;
+      }
+      continue;
+    }
     double s[SIM_MOVING] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     const int j0 = b * stride;
     for (int k = 0; k < S; ++k) {
@@ -132,8 +200,25 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_patch_gradncc_kernel(const fl
       for (int q = 0; q < SIM_MOVING; ++q) s[q] += cols[q * wi + j0 + k];
     }
     const double* t = ptotals + p * SIM_FIXED;
-    if (flags & 1) acc[0] += sim_ncc(t[0], s[0], s[1], t[1], t[2], s[2]);
-    if (flags & 2) acc[1] += sim_ncc(t[0], s[3], s[4], t[3], t[4], s[5]);
+    if (!weighted) {
+      if (flags & 1) acc[0] += sim_ncc(t[0], s[0], s[1], t[1], t[2], s[2]);
+      if (flags & 2) acc[1] += sim_ncc(t[0], s[3], s[4], t[3], t[4], s[5]);
+    } else {                                                            // a patch that does not count in d has w_d = 0
+      if (flags & 1) acc[0] += pweights[p * 2] * sim_ncc(t[0], s[0], s[1], t[1], t[2], s[2]);
+      if (flags & 2) acc[1] += pweights[p * 2 + 1] * sim_ncc(t[0], s[3], s[4], t[3], t[4], s[5]);
+    }
+    if (with_coef) {
+#pragma unroll
+      for (int d = 0; d < 2; ++d) {
+        float* out = coef + p * SIM_PCOEF + 4 * d;
+        if (flags & (1 << d)) {                                         // it counts: pcount[d] >= 1, and pwsum[d] >= w_d > 0
+          const double share = weighted ? pweights[p * 2 + d] / pwsum[d] : 1.0 / (double)pcount[d];
+          sim_patch_coef(out, share, t[0], s[3 * d], s[3 * d + 1], t[1 + 2 * d], t[2 + 2 * d], s[3 * d + 2]);
+        } else {
+          out[0] = out[1] = out[2] = out[3] = 0.f;
+        }
+      }
+    }
   }
   block_sum<2>(acc, lds);
   if (threadIdx.x == 0) {
@@ -143,8 +228,9 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_patch_gradncc_kernel(const fl
   }
 }
 
-// One wave per view: lanes 0 and 1 add the view's PR records of ncc_x / ncc_y in index order
+// One wave per view: lanes 0 and 1 add the view's PR records of ncc_x / ncc_y in index order; pwsum = nullptr: the uniform cost
 __global__ __launch_bounds__(64) void sim_patch_finish_kernel(const double* __restrict__ scratch, const int* __restrict__ pcount,
+                                                              const double* __restrict__ pwsum,
                                                               const int32_t* __restrict__ fixed_of, double* __restrict__ cost, int PR,
                                                               int F) {
   __shared__ double m[2];
@@ -157,11 +243,79 @@ __global__ __launch_bounds__(64) void sim_patch_finish_kernel(const double* __re
   pcount += 2 * f;
   if (threadIdx.x < 2) {
     const double acc = records_sum(scratch + (size_t)view * PR * 2 + threadIdx.x, PR, 2);
-    const int n = pcount[threadIdx.x];
-    m[threadIdx.x] = n > 0 ? acc / (double)n : 0.0;
+    if (pwsum == nullptr) {
+      const int n = pcount[threadIdx.x];
+      m[threadIdx.x] = n > 0 ? acc / (double)n : 0.0;
+    } else {                                                            // the weighted mean: the records hold sum w ncc
+      const double w = pwsum[2 * (size_t)f + threadIdx.x];
+      m[threadIdx.x] = w > 0.0 ? acc / w : 0.0;
+    }
   }
   __syncthreads();
   if (threadIdx.x == 0) cost[view] = 1.0 - 0.5 * (m[0] + m[1]);
+}
+
+// ---- the adjoint: d cost[v] / d moving[v][r][c] (dfl_sim_patch_eval with d_moving) ------------------------------------------------
+// sim_adjoint_kernel's shape (csrc/sim.hip): a workgroup owns a 16 x 16 tile of one view's d_moving, stages the tile of `moving`
+// with a halo of 2 in LDS and computes g = d cost / d (Sobel value) on the 18 x 18 pixels around the tile; here g at interior
+// pixel (i, j) is the sum over the patches that hold it -- a from max(0, ceil((i - S + 1) / s)) to min(PR - 1, i / s), b likewise,
+// a outer and b inner -- of c alpha (b_q - mean b) + c beta (a_q - mean a) with the patch's eight coefficients, read straight
+// from global memory (32 B per patch, L1/L2-resident: a tile of 18 x 18 pixels shares at most (17 / s + S / s + 2)^2 patches).
+// LDS is 4.4 KB whatever rho and s are.  No atomics: a view's bits depend on its own pixels, its fixed image and H, W, rho, s only.
+__global__ __launch_bounds__(SIM_THREADS) void sim_patch_adjoint_kernel(const float* __restrict__ moving, const float* __restrict__ fx,
+                                                                        const float* __restrict__ fy,
+                                                                        const unsigned char* __restrict__ counted,
+                                                                        const int32_t* __restrict__ fixed_of, const float* __restrict__ coef,
+                                                                        float* __restrict__ d_moving, int H, int W, int S, int stride,
+                                                                        int PR, int PC, int F) {
+  // every product is rounded on its own, as in sim_adjoint_kernel: where moving matches fixed the two terms of a patch cancel
+#pragma clang fp contract(off)
+  constexpr int G = SIM_TILE_G;
+  __shared__ float sm[SIM_TILE_IN][SIM_TILE_IN + 1];
+  __shared__ float sgx[G][G + 1], sgy[G][G + 1];
+  const int view = blockIdx.z;
+  const int r0 = blockIdx.y * SIM_TILE, c0 = blockIdx.x * SIM_TILE;
+  const int f = sim_image_of(fixed_of, view, F);
+  if (f < 0) {                                                          // the whole workgroup, before its first barrier
+    const int r = r0 + threadIdx.x / SIM_TILE, c = c0 + threadIdx.x % SIM_TILE;
+    if (r < H && c < W) d_moving[((size_t)view * H + r) * W + c] = 0.f;
+    return;
+  }
+  const size_t plane = (size_t)f * H * W;
+  fx += plane;
+  fy += plane;
+  counted += plane;
+  coef += (size_t)view * PR * PC * SIM_PCOEF;
+  sim_stage_tile(sm, moving + (size_t)view * H * W, H, W, r0, c0);
+  __syncthreads();
+  for (int t = threadIdx.x; t < G * G; t += SIM_THREADS) {
+    const int lr = t / G, lc = t % G, r = r0 - 1 + lr, c = c0 - 1 + lc;
+    float gx = 0.f, gy = 0.f;
+    if (r >= 1 && r <= H - 2 && c >= 1 && c <= W - 2) {
+      const size_t at = (size_t)r * W + c;
+      if (counted[at]) {
+        float mx, my;                                                   // pixel (r, c) sits at sm[lr + 1][lc + 1]
+        sim_sobel9(sm[lr][lc], sm[lr][lc + 1], sm[lr][lc + 2], sm[lr + 1][lc], sm[lr + 1][lc + 2], sm[lr + 2][lc], sm[lr + 2][lc + 1],
+                   sm[lr + 2][lc + 2], mx, my);
+        const float bx = fx[at], by = fy[at];
+        const int i = r - 1, j = c - 1;
+        const int a_lo = i < S ? 0 : (i - S + stride) / stride, a_hi = min(PR - 1, i / stride);     // ceil((i - S + 1) / s)
+        const int b_lo = j < S ? 0 : (j - S + stride) / stride, b_hi = min(PC - 1, j / stride);
+        for (int a = a_lo; a <= a_hi; ++a) {
+          const float* cf = coef + ((size_t)a * PC + b_lo) * SIM_PCOEF;
+          for (int b = b_lo; b <= b_hi; ++b, cf += SIM_PCOEF) {
+            gx += cf[0] * (bx - cf[3]) + cf[1] * (mx - cf[2]);
+            gy += cf[4] * (by - cf[7]) + cf[5] * (my - cf[6]);
+          }
+        }
+      }
+    }
+    sgx[lr][lc] = gx;
+    sgy[lr][lc] = gy;
+  }
+  __syncthreads();
+  const int tr = threadIdx.x / SIM_TILE, tc = threadIdx.x % SIM_TILE, r = r0 + tr, c = c0 + tc;
+  if (r < H && c < W) d_moving[((size_t)view * H + r) * W + c] = sim_sobel_gather(sgx, sgy, tr, tc);
 }
 
 // the checks on sizes that every entry point shares; `who` names it in the message
@@ -212,38 +366,75 @@ extern "C" int dfl_sim_patch_prepare(const dfl_sim_patch_prepare_args* a, dfl_st
   return dfl::check_launch("dfl_sim_patch_prepare");
 }
 
+extern "C" int dfl_sim_patch_weights(const dfl_sim_patch_weights_args* a, dfl_stream_t stream) {
+  DFL_REQUIRE(a != nullptr, "dfl_sim_patch_weights: null args");
+  DFL_REQUIRE(a->ptotals != nullptr && a->pflags != nullptr && a->pweights != nullptr && a->pwsum != nullptr,
+              "dfl_sim_patch_weights: ptotals, pflags, pweights and pwsum are required");
+  DFL_REQUIRE(a->P >= 1 && a->P < ((int64_t)1 << 31), "dfl_sim_patch_weights: %lld patches (1 .. 2^31 - 1: dfl_sim_patch_count)",
+              (long long)a->P);
+  dfl::sim_patch_weights_kernel<<<1, dfl::SIM_THREADS, 0, static_cast<hipStream_t>(stream)>>>(a->ptotals, a->pflags, a->pweights, a->pwsum,
+                                                                                                a->P);
+  return dfl::check_launch("dfl_sim_patch_weights");
+}
+
 namespace dfl {
 
-// what dfl_sim_patch_gradncc and its bank form are called with: fixed_of == nullptr is one fixed image (F = 1)
+// What dfl_sim_patch_gradncc, its bank form and dfl_sim_patch_eval are called with: fixed_of == nullptr is one fixed image
+// (F = 1), pweights == nullptr the uniform cost, d_moving == nullptr the forward alone
 struct sim_patch_call {
   const float *moving, *fx, *fy;
   const unsigned char* counted;
   const double* ptotals;
   const unsigned char* pflags;
   const int32_t *pcount, *fixed_of;
+  const double *pweights, *pwsum;
   double *scratch, *cost;
+  float* d_moving;
   int64_t scratch_doubles;
   int V, H, W, rho, stride, F;
 };
 
-static int sim_patch_launch(const char* who, const sim_patch_call& c, bool bank, dfl_stream_t stream) {
+// records [V][PR][2], then with the adjoint the coefficients [V][P][8] float32
+inline int64_t sim_patch_need(int64_t V, const patch_grid& g, bool bwd) {
+  return V * g.PR * 2 + (bwd ? V * g.PR * g.PC * (SIM_PCOEF / 2) : 0);
+}
+
+// `sizes` names the function that says how long the scratch has to be
+static int sim_patch_launch(const char* who, const char* sizes, const sim_patch_call& c, bool bank, dfl_stream_t stream) {
   DFL_REQUIRE(c.moving != nullptr && c.fx != nullptr && c.fy != nullptr && c.counted != nullptr && c.ptotals != nullptr &&
                   c.pflags != nullptr && c.pcount != nullptr && c.scratch != nullptr && c.cost != nullptr,
               "%s: moving, fx, fy, counted, ptotals, pflags, pcount, scratch and cost are required", who);
+  DFL_REQUIRE((c.pweights == nullptr) == (c.pwsum == nullptr), "%s: pweights and pwsum come together (both NULL: the uniform cost)", who);
   patch_grid g;
   int rc = patch_sizes_ok(who, c.H, c.W, c.rho, c.stride, &g);
   if (rc != DFL_OK) return rc;
   DFL_REQUIRE(c.V >= 1 && c.V <= 65535, "%s: 1..65535 views per call, got %d", who, c.V);
   if (bank && (rc = sim_bank_ok(who, c.fixed_of, c.F, c.H, c.W)) != DFL_OK) return rc;
-  const int64_t need = (int64_t)c.V * g.PR * 2;
-  DFL_REQUIRE(c.scratch_doubles >= need, "%s: a scratch of %lld doubles, %lld are needed (dfl_sim_patch_scratch_doubles)", who,
-              (long long)c.scratch_doubles, (long long)need);
+  const bool bwd = c.d_moving != nullptr;
+  const int64_t need = sim_patch_need(c.V, g, bwd);
+  DFL_REQUIRE(c.scratch_doubles >= need, "%s: a scratch of %lld doubles, %lld are needed (%s)", who, (long long)c.scratch_doubles,
+              (long long)need, sizes);
+  DFL_REQUIRE(!bwd || ceil_div(c.H, SIM_TILE) <= 65535, "%s: an image of %d rows is too tall for the adjoint", who, c.H);
   const int lds = SIM_MOVING * (c.W - 2) * (int)sizeof(double);
-  DFL_LDS_OPT_IN(sim_patch_gradncc_kernel, DFL_SIM_PATCH_MAX_W * SIM_MOVING * sizeof(double), who)
   hipStream_t s = static_cast<hipStream_t>(stream);
-  sim_patch_gradncc_kernel<<<dim3((unsigned)g.PR, (unsigned)c.V), SIM_THREADS, lds, s>>>(
-      c.moving, c.fx, c.fy, c.counted, c.ptotals, c.pflags, c.fixed_of, c.scratch, c.H, c.W, g.S, c.stride, g.PC, c.F);
-  sim_patch_finish_kernel<<<(unsigned)c.V, 64, 0, s>>>(c.scratch, c.pcount, c.fixed_of, c.cost, g.PR, c.F);
+  float* coef = bwd ? reinterpret_cast<float*>(c.scratch + (size_t)c.V * g.PR * 2) : nullptr;
+  const dim3 rows((unsigned)g.PR, (unsigned)c.V);
+  // the adjoint runs the forward's own two kernels first: its cost has the forward's bits
+  if (c.pweights != nullptr || bwd) {
+    DFL_LDS_OPT_IN(sim_patch_gradncc_kernel<true>, DFL_SIM_PATCH_MAX_W * SIM_MOVING * sizeof(double), who)
+    sim_patch_gradncc_kernel<true><<<rows, SIM_THREADS, lds, s>>>(c.moving, c.fx, c.fy, c.counted, c.ptotals, c.pflags, c.fixed_of, c.pcount,
+                                                                  c.pweights, c.pwsum, coef, c.scratch, c.H, c.W, g.S, c.stride, g.PC, c.F);
+  } else {
+    DFL_LDS_OPT_IN(sim_patch_gradncc_kernel<false>, DFL_SIM_PATCH_MAX_W * SIM_MOVING * sizeof(double), who)
+    sim_patch_gradncc_kernel<false><<<rows, SIM_THREADS, lds, s>>>(c.moving, c.fx, c.fy, c.counted, c.ptotals, c.pflags, c.fixed_of, c.pcount,
+                                                                   nullptr, nullptr, nullptr, c.scratch, c.H, c.W, g.S, c.stride, g.PC, c.F);
+  }
+  sim_patch_finish_kernel<<<(unsigned)c.V, 64, 0, s>>>(c.scratch, c.pcount, c.pwsum, c.fixed_of, c.cost, g.PR, c.F);
+  if (bwd) {
+    const dim3 grid((unsigned)ceil_div(c.W, SIM_TILE), (unsigned)ceil_div(c.H, SIM_TILE), (unsigned)c.V);
+    sim_patch_adjoint_kernel<<<grid, SIM_THREADS, 0, s>>>(c.moving, c.fx, c.fy, c.counted, c.fixed_of, coef, c.d_moving, c.H, c.W, g.S,
+                                                          c.stride, g.PR, g.PC, c.F);
+  }
   return check_launch(who);
 }
 
@@ -251,14 +442,36 @@ static int sim_patch_launch(const char* who, const sim_patch_call& c, bool bank,
 
 extern "C" int dfl_sim_patch_gradncc(const dfl_sim_patch_gradncc_args* a, dfl_stream_t stream) {
   DFL_REQUIRE(a != nullptr, "dfl_sim_patch_gradncc: null args");
-  const dfl::sim_patch_call c = {a->moving,  a->fx,   a->fy, a->counted, a->ptotals, a->pflags, a->pcount, nullptr,
-                                 a->scratch, a->cost, a->scratch_doubles, a->V, a->H, a->W, a->rho, a->stride, 1};
-  return dfl::sim_patch_launch("dfl_sim_patch_gradncc", c, false, stream);
+  const dfl::sim_patch_call c = {a->moving, a->fx,      a->fy,   a->counted, a->ptotals,         a->pflags, a->pcount, nullptr, nullptr,
+                                 nullptr,   a->scratch, a->cost, nullptr,    a->scratch_doubles, a->V,      a->H,      a->W,    a->rho,
+                                 a->stride, 1};
+  return dfl::sim_patch_launch("dfl_sim_patch_gradncc", "dfl_sim_patch_scratch_doubles", c, false, stream);
 }
 
 extern "C" int dfl_sim_patch_bank_gradncc(const dfl_sim_patch_bank_gradncc_args* a, dfl_stream_t stream) {
   DFL_REQUIRE(a != nullptr, "dfl_sim_patch_bank_gradncc: null args");
-  const dfl::sim_patch_call c = {a->moving,  a->fx,   a->fy, a->counted, a->ptotals, a->pflags, a->pcount, a->fixed_of,
-                                 a->scratch, a->cost, a->scratch_doubles, a->V, a->H, a->W, a->rho, a->stride, a->F};
-  return dfl::sim_patch_launch("dfl_sim_patch_bank_gradncc", c, true, stream);
+  const dfl::sim_patch_call c = {a->moving, a->fx,      a->fy,   a->counted, a->ptotals,         a->pflags, a->pcount, a->fixed_of, nullptr,
+                                 nullptr,   a->scratch, a->cost, nullptr,    a->scratch_doubles, a->V,      a->H,      a->W,        a->rho,
+                                 a->stride, a->F};
+  return dfl::sim_patch_launch("dfl_sim_patch_bank_gradncc", "dfl_sim_patch_scratch_doubles", c, true, stream);
 }
+
+extern "C" int dfl_sim_patch_eval_scratch_doubles(int32_t V, int32_t H, int32_t W, int32_t rho, int32_t stride, int32_t bwd) {
+  dfl::patch_grid g;
+  const int rc = dfl::patch_sizes_ok("dfl_sim_patch_eval_scratch_doubles", H, W, rho, stride, &g);
+  if (rc != DFL_OK) return rc;
+  DFL_REQUIRE(V >= 1 && V <= 65535, "dfl_sim_patch_eval_scratch_doubles: 1..65535 views per call, got %d", V);
+  const int64_t need = dfl::sim_patch_need(V, g, bwd != 0);
+  DFL_REQUIRE(need < ((int64_t)1 << 31), "dfl_sim_patch_eval_scratch_doubles: %lld doubles, more than 2^31 - 1", (long long)need);
+  return (int)need;
+}
+
+extern "C" int dfl_sim_patch_eval(const dfl_sim_patch_eval_args* a, dfl_stream_t stream) {
+  DFL_REQUIRE(a != nullptr, "dfl_sim_patch_eval: null args");
+  const bool bank = a->fixed_of != nullptr;                             // without fixed_of there is one image and F is not read
+  const dfl::sim_patch_call c = {a->moving,   a->fx,      a->fy,   a->counted,  a->ptotals,         a->pflags, a->pcount, a->fixed_of, a->pweights,
+                                 a->pwsum,    a->scratch, a->cost, a->d_moving, a->scratch_doubles, a->V,      a->H,      a->W,        a->rho,
+                                 a->stride,   bank ? a->F : 1};
+  return dfl::sim_patch_launch("dfl_sim_patch_eval", "dfl_sim_patch_eval_scratch_doubles", c, bank, stream);
+}
+

@@ -14,6 +14,8 @@ it exerts on every object (dfl_drr_pose_grad, sampling frozen), chained to theta
 and tests/grad_ref.py.  register_many registers N projections of one volume at once: the candidates of all problems go through
 one render and one launch against a bank of fixed images (SimilarityBank, dfl_sim_bank_gradncc), the optimisers advance in
 lockstep (cma_steps, bfgs_steps, lockstep), and every result has the bytes register() finds for it alone; section 20.
+patch_weight='variance' weighs every patch by the energy of its fixed gradient (dfl_sim_patch_weights) and has an adjoint
+(dfl_sim_patch_eval), so the patch cost can be refined too; section 21 and tests/patch_grad_ref.py.
 
     D(theta) = [[R, centre - R centre + theta[3:]], [0, 1]],  R = exp(rot_unit theta[:3])      (pose_delta)
     P(theta) = D(theta) P0                                   a cam-to-*-vol matrix as in gt-poses
@@ -487,14 +489,54 @@ def _patch_params(radius, stride, min_count):
     return int(radius), int(stride), (side * side + 1) // 2 if min_count is None else int(min_count)
 
 
+def _patch_weight(weight):
+    if weight not in ('uniform', 'variance'):
+        raise nat.DflError("register: a patch weight of %r ('uniform' or 'variance')" % (weight,))
+    return weight
+
+
+def _patch_weights(dev, ptotals, pflags, pweights, pwsum, P):
+    """dfl_sim_patch_weights on one image's patch totals and flags (for a bank: on that image's slices)."""
+    a = nat.SimPatchWeightsArgs(ptotals=ptotals.data_ptr(), pflags=pflags.data_ptr(), pweights=pweights.data_ptr(), pwsum=pwsum.data_ptr(), P=P)
+    drr.launch(dev, 'dfl_sim_patch_weights', a)
+
+
+def _patch_eval_args(sim, moving, fixed_of, scratch, out, d_moving):
+    """The dfl_sim_patch_eval block of a weighted PatchSimilarity (fixed_of None) or PatchSimilarityBank."""
+    return nat.SimPatchEvalArgs(moving=moving.data_ptr(), fx=sim.fx.data_ptr(), fy=sim.fy.data_ptr(), counted=sim.counted.data_ptr(),
+                                ptotals=sim.ptotals.data_ptr(), pflags=sim.pflags.data_ptr(), pcount=sim.pcount.data_ptr(),
+                                pweights=sim.pweights.data_ptr(), pwsum=sim.pwsum.data_ptr(), fixed_of=nat.ptr(fixed_of),
+                                scratch=scratch.data_ptr(), cost=out.data_ptr(), d_moving=nat.ptr(d_moving), scratch_doubles=scratch.numel(),
+                                V=int(moving.shape[0]), H=sim.H, W=sim.W, rho=sim.radius, stride=sim.stride, F=getattr(sim, 'F', 1))
+
+
+def _patch_cost_and_adjoint(sim, mv, fixed_of):
+    V, dev = int(mv.shape[0]), mv.device
+    if getattr(sim, 'bwd_scratch', None) is None:
+        lib = nat.lib()
+        need = int(lib.dfl_sim_patch_eval_scratch_doubles(sim.views, sim.H, sim.W, sim.radius, sim.stride, 1))
+        if need < 0:
+            raise nat.DflError('register: %s' % lib.dfl_last_error().decode())
+        sim.bwd_scratch = torch.empty(need, dtype=torch.float64, device=dev)
+    out = torch.empty(V, dtype=torch.float64, device=dev)
+    d_moving = torch.empty((V, sim.H, sim.W), dtype=torch.float32, device=dev)
+    drr.launch(dev, 'dfl_sim_patch_eval', _patch_eval_args(sim, mv, fixed_of, sim.bwd_scratch, out, d_moving))
+    return out, d_moving
+
+
 class PatchSimilarity(Similarity):
     """The patch-wise gradient-NCC cost with the interface of Similarity: patches of side
     2 radius + 1 every `stride` interior pixels; a patch with fewer than min_count counted pixels (default: half of it,
     rounded up), or whose fixed gradient does not vary, does not take part.  dfl_sim_prepare and dfl_sim_patch_prepare
-    run here, once; cost(moving) is one dfl_sim_patch_gradncc launch."""
+    run here, once; cost(moving) is one dfl_sim_patch_gradncc launch.
 
-    def __init__(self, fixed, mask=None, views=1, radius=7, stride=4, min_count=None):
+    weight='variance'  weighs every patch by the energy of its fixed gradient: dfl_sim_patch_weights
+    runs after the prepare, cost(moving) is one dfl_sim_patch_eval launch and cost_and_adjoint(moving) works.  The default
+    'uniform' is the cost of section 18 through the entry point it always used, and has no adjoint here."""
+
+    def __init__(self, fixed, mask=None, views=1, radius=7, stride=4, min_count=None, weight='uniform'):
         self.radius, self.stride, self.min_count = _patch_params(radius, stride, min_count)
+        self.weight = _patch_weight(weight)
         Similarity.__init__(self, fixed, mask, views)
         lib = nat.lib()
         dev, H, W = self.fixed.device, self.H, self.W
@@ -511,11 +553,18 @@ class PatchSimilarity(Similarity):
                                     ptotals=self.ptotals.data_ptr(), pflags=self.pflags.data_ptr(), pcount=self.pcount.data_ptr(),
                                     H=H, W=W, rho=self.radius, stride=self.stride, min_count=self.min_count)
         drr.launch(dev, 'dfl_sim_patch_prepare', a)
+        if self.weight == 'variance':
+            self.entry = 'dfl_sim_patch_eval'
+            self.pweights = torch.empty((P, 2), dtype=torch.float64, device=dev)
+            self.pwsum = torch.empty(2, dtype=torch.float64, device=dev)
+            _patch_weights(dev, self.ptotals, self.pflags, self.pweights, self.pwsum, P)
 
     entry = 'dfl_sim_patch_gradncc'
 
     def args(self, moving, out=None):
         out = self.out if out is None else out
+        if self.weight == 'variance':
+            return _patch_eval_args(self, moving, None, self.pscratch, out, None)
         return nat.SimPatchGradnccArgs(moving=moving.data_ptr(), fx=self.fx.data_ptr(), fy=self.fy.data_ptr(),
                                        counted=self.counted.data_ptr(), ptotals=self.ptotals.data_ptr(), pflags=self.pflags.data_ptr(),
                                        pcount=self.pcount.data_ptr(), scratch=self.pscratch.data_ptr(), cost=out.data_ptr(),
@@ -523,7 +572,12 @@ class PatchSimilarity(Similarity):
                                        rho=self.radius, stride=self.stride)
 
     def cost_and_adjoint(self, moving):
-        raise nat.DflError('register: the patch similarity has no adjoint kernel yet (DESIGN.md section 19 names it as next)')
+        """(cost [V] float64, d_moving [V, H, W] float32) on the device: one dfl_sim_patch_eval launch (DESIGN.md section 21);
+        the cost has the bits cost(moving) gives.  With weight='variance' only."""
+        if self.weight != 'variance':
+            raise nat.DflError("register: the uniform patch similarity has no adjoint here; weight='variance' has (DESIGN.md section 21)")
+        mv = self._moving(moving)
+        return _patch_cost_and_adjoint(self, mv, None)
 
 
 # ---- the similarity against a bank of fixed images ---------------------------------------------------------------------
@@ -632,10 +686,12 @@ class SimilarityBank(Similarity):
 
 class PatchSimilarityBank(SimilarityBank):
     """PatchSimilarity against F fixed images, with the interface of SimilarityBank: dfl_sim_patch_prepare runs once per
-    image on its slice of the patch banks; cost(moving, fixed_of) is one dfl_sim_patch_bank_gradncc launch."""
+    image on its slice of the patch banks; cost(moving, fixed_of) is one dfl_sim_patch_bank_gradncc launch.  weight='variance'
+    is PatchSimilarity's: dfl_sim_patch_weights per image, dfl_sim_patch_eval for the cost, and cost_and_adjoint works."""
 
-    def __init__(self, fixed, masks=None, views=1, radius=7, stride=4, min_count=None):
+    def __init__(self, fixed, masks=None, views=1, radius=7, stride=4, min_count=None, weight='uniform'):
         self.radius, self.stride, self.min_count = _patch_params(radius, stride, min_count)
+        self.weight = _patch_weight(weight)
         SimilarityBank.__init__(self, fixed, masks, views)
         lib = nat.lib()
         dev, F, H, W = self.fixed.device, self.F, self.H, self.W
@@ -654,11 +710,19 @@ class PatchSimilarityBank(SimilarityBank):
                                         pcount=self.pcount[f].data_ptr(), H=H, W=W, rho=self.radius, stride=self.stride,
                                         min_count=self.min_count)
             drr.launch(dev, 'dfl_sim_patch_prepare', a)
+        if self.weight == 'variance':
+            self.entry = 'dfl_sim_patch_eval'
+            self.pweights = torch.empty((F, P, 2), dtype=torch.float64, device=dev)
+            self.pwsum = torch.empty((F, 2), dtype=torch.float64, device=dev)
+            for f in range(F):
+                _patch_weights(dev, self.ptotals[f], self.pflags[f], self.pweights[f], self.pwsum[f], P)
 
     entry = 'dfl_sim_patch_bank_gradncc'
 
     def args(self, moving, fixed_of, out=None):
         out = self.out if out is None else out
+        if self.weight == 'variance':
+            return _patch_eval_args(self, moving, fixed_of, self.pscratch, out, None)
         return nat.SimPatchBankGradnccArgs(moving=moving.data_ptr(), fx=self.fx.data_ptr(), fy=self.fy.data_ptr(),
                                            counted=self.counted.data_ptr(), ptotals=self.ptotals.data_ptr(), pflags=self.pflags.data_ptr(),
                                            pcount=self.pcount.data_ptr(), fixed_of=fixed_of.data_ptr(), scratch=self.pscratch.data_ptr(),
@@ -666,7 +730,11 @@ class PatchSimilarityBank(SimilarityBank):
                                            W=self.W, rho=self.radius, stride=self.stride, F=self.F)
 
     def cost_and_adjoint(self, moving, fixed_of):
-        raise nat.DflError('register: the patch similarity has no adjoint kernel yet (DESIGN.md section 19 names it as next)')
+        """(cost [V] float64, d_moving [V, H, W] float32) on the device: one dfl_sim_patch_eval launch.  With weight='variance' only."""
+        if self.weight != 'variance':
+            raise nat.DflError("register: the uniform patch similarity has no adjoint here; weight='variance' has (DESIGN.md section 21)")
+        mv = self._moving(moving)
+        return _patch_cost_and_adjoint(self, mv, self.fixed_of(fixed_of, int(mv.shape[0])))
 
 
 # ---- the landmark term -------------------------------------------------------------------------------------------------
@@ -769,15 +837,20 @@ def _theta_chain(both, piv, xis, moving):
     return both[:, 0], ((Mom[:, None] * L).sum((-1, -2)) + (F[:, None] * lever).sum(-1)).sum(-1)
 
 
-def _cost_options(refine, refine_tol, similarity, patch_radius, patch_stride, patch_min_count, landmark_weight):
-    """The checks register() and register_many() make first: (the patch parameters or None, the landmark weight)."""
+def _cost_options(refine, refine_tol, similarity, patch_radius, patch_stride, patch_min_count, landmark_weight, patch_weight='uniform'):
+    """The checks register() and register_many() make first, before anything touches a device: (the patch parameters --
+    radius, stride, min_count, weight -- or None, the landmark weight)."""
     if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or refine < 0 or not float(refine_tol) >= 0.0:
         raise nat.DflError('register: refine = %r (an integer, at least 0) and refine_tol = %r (not negative)' % (refine, refine_tol))
-    if refine > 0 and similarity == 'patch':
-        raise nat.DflError("register: refine needs the adjoint of the similarity, which similarity='patch' does not have yet")
+    _patch_weight(patch_weight)
+    if refine > 0 and similarity == 'patch' and patch_weight == 'uniform':
+        raise nat.DflError("register: refine needs the adjoint of the similarity, which similarity='patch' does not have yet "
+                           "with patch_weight='uniform' (patch_weight='variance' has it)")
     if similarity not in ('global', 'patch'):
         raise nat.DflError("register: similarity = %r ('global' or 'patch')" % (similarity,))
-    patch = _patch_params(patch_radius, patch_stride, patch_min_count) if similarity == 'patch' else None
+    if similarity == 'global' and patch_weight != 'uniform':
+        raise nat.DflError("register: patch_weight = %r belongs to similarity='patch'; similarity='global' has no patches" % (patch_weight,))
+    patch = _patch_params(patch_radius, patch_stride, patch_min_count) + (patch_weight,) if similarity == 'patch' else None
     landmark_weight = float(landmark_weight)
     if not landmark_weight >= 0.0 or not np.isfinite(landmark_weight):
         raise nat.DflError('register: a landmark_weight of %r (finite, not negative)' % landmark_weight)
@@ -869,7 +942,7 @@ class _Problem:
 def register(volume, geom, fixed, moving=(0, 1, 2), theta0=None, P0=None, levels=None, popsize=16, generations=80, sigma0=2.0,
              step_mm=1.0, mask=None, seed=0, centre=None, rot_unit=ROT_UNIT, crop=0, rot180=False, sigma_shrink=0.5,
              similarity='global', patch_radius=7, patch_stride=4, patch_min_count=None, landmarks=None, landmark_weight=0.0,
-             refine=0, refine_tol=1e-4):
+             refine=0, refine_tol=1e-4, patch_weight='uniform'):
     """Find theta such that the DRR of `volume` under P = D(theta) P0 matches `fixed`.
 
     moving selects the objects of geom.objects that share the pose under optimisation; the others are rendered at their
@@ -892,9 +965,13 @@ def register(volume, geom, fixed, moving=(0, 1, 2), theta0=None, P0=None, levels
     gradient of the frozen-sampling renderer and the adjoint of the global similarity (the landmark
     term joins with central differences of its host function); refine_tol is the step length that ends it.  The result
     never costs more than the CMA-ES mean (Registration.theta_cma).  generations=0 with refine=K refines theta0 alone.
-    similarity='patch' has no adjoint yet and is refused together with refine.
+    similarity='patch' with the default patch_weight='uniform' is refused together with refine.
+
+    patch_weight='variance' (with similarity='patch') weighs every patch by the energy of its fixed
+    gradient, which quiets the background patches of a preprocessed projection, and has an adjoint: refine=K works with it.
     """
-    patch, landmark_weight = _cost_options(refine, refine_tol, similarity, patch_radius, patch_stride, patch_min_count, landmark_weight)
+    patch, landmark_weight = _cost_options(refine, refine_tol, similarity, patch_radius, patch_stride, patch_min_count, landmark_weight,
+                                           patch_weight)
     if landmarks is not None and levels is not None:
         raise nat.DflError('register: landmarks belong to one grid; they are not supported together with levels')
     lands = _landmarks_of(landmarks, moving)
@@ -957,7 +1034,8 @@ def default_max_views(H, W):
 
 def register_many(volume, geoms, fixed, moving=(0, 1, 2), theta0=None, P0=None, popsize=16, generations=80, sigma0=2.0, step_mm=1.0,
                   masks=None, seed=0, centre=None, rot_unit=ROT_UNIT, similarity='global', patch_radius=7, patch_stride=4,
-                  patch_min_count=None, landmarks=None, landmark_weight=0.0, refine=0, refine_tol=1e-4, max_views=None, **unknown):
+                  patch_min_count=None, landmarks=None, landmark_weight=0.0, refine=0, refine_tol=1e-4, max_views=None,
+                  patch_weight='uniform', **unknown):
     """register() for N projections of one volume at once: [Registration] * N.
 
     geoms is a list of N drr.Geometry that share the output grid, K, I2P and the object masks (each has its own object
@@ -969,14 +1047,16 @@ def register_many(volume, geoms, fixed, moving=(0, 1, 2), theta0=None, P0=None, 
 
     The device works on all running problems at once: a generation is one render of popsize views per problem and one
     similarity launch against the bank of fixed images (SimilarityBank, PatchSimilarityBank); a round of the finish is one
-    render of one view per problem still running, one dfl_sim_bank_gradncc_bwd and one dfl_drr_pose_grad.  The float64
+    render of one view per problem still running, one dfl_sim_bank_gradncc_bwd (with patch_weight='variance': one
+    dfl_sim_patch_eval) and one dfl_drr_pose_grad.  The float64
     host work is done problem by problem with the functions register() uses.  max_views caps the views of one render
     (default: default_max_views); problems are processed in chunks of max_views // popsize, which changes no result.
     There is no coarse-to-fine here (no levels)."""
     if unknown:
         raise nat.DflError('register_many: no argument %s (levels: there is no coarse-to-fine here; register() has it)'
                            % ', '.join(sorted(unknown)))
-    patch, landmark_weight = _cost_options(refine, refine_tol, similarity, patch_radius, patch_stride, patch_min_count, landmark_weight)
+    patch, landmark_weight = _cost_options(refine, refine_tol, similarity, patch_radius, patch_stride, patch_min_count, landmark_weight,
+                                           patch_weight)
     try:
         geoms = list(geoms)
     except TypeError:

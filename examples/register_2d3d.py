@@ -9,6 +9,7 @@ same --crop and --ds-factor.
     python examples/register_2d3d.py full_res.h5 17-1882 0 --offset 2,-1.5,2.5,4,-3,15 --seed 1 --out run1
     python examples/register_2d3d.py full_res.h5 17-1882 0 --lands-csv lands.csv --similarity patch --landmark-weight 0.01
     python examples/register_2d3d.py full_res.h5 17-1882 0 --offset 2,-1.5,2.5,4,-3,15 --generations 25 --refine 30
+    python examples/register_2d3d.py full_res.h5 17-1882 0 --gt-lands --similarity patch --patch-weight variance --refine 20
 
 The start pose comes from exactly one of
   --lands-csv FILE   2D landmarks as est_lands_csv.py writes them (pat,proj,land,row,col,time on this grid; land indexes
@@ -21,7 +22,9 @@ patches of radius --patch-radius (7) every --patch-stride (4) pixels, which is l
 --landmark-weight W (per square pixel, default 0) adds W times the mean squared distance between the projected 3D
 landmarks and the 2D landmarks that gave the start to the pelvis cost; it needs a landmark start, not --offset.
 --refine K (default 0) finishes every registration with at most K quasi-Newton iterations on the pose gradient of the
-renderer (dfl_drr_pose_grad, dfl_sim_gradncc_bwd; global similarity only) and prints the cost before and after them.
+renderer (dfl_drr_pose_grad, dfl_sim_gradncc_bwd; the global similarity, or the patch one with --patch-weight variance) and
+prints the cost before and after them.  --patch-weight variance (with --similarity patch; default uniform) weighs every
+patch by the energy of the projection's gradient in it, so that flat background patches hardly count (dfl_sim_patch_eval).
 With a landmark start all bones begin at the pelvis pose (the anatomy as it was scanned).  The pelvis is registered with
 every bone following it; --femurs then registers each femur on its own with the others held.
 PREFIX_reg.npz holds start_poses and poses ([3, 4, 4] cam-to-{pelvis, left-femur, right-femur}-vol), cost (the best cost
@@ -46,7 +49,7 @@ from full_res_drr import parse_options, to_u8  # noqa: E402
 
 USAGE = ('Usage: {} <HDF5 full-res data file> <specimen ID> <projection index> (--lands-csv FILE | --gt-lands | --offset '
          'rx,ry,rz,tx,ty,tz) [--femurs] [--out PREFIX] [--crop 50] [--ds-factor 8] [--popsize 16] [--generations 80] [--sigma 2.0] '
-         '[--step 1.0] [--refine 0] [--seed 0] [--similarity global|patch] [--patch-radius 7] [--patch-stride 4] [--landmark-weight 0]')
+         '[--step 1.0] [--patch-weight uniform|variance] [--refine 0] [--seed 0] [--similarity global|patch] [--patch-radius 7] [--patch-stride 4] [--landmark-weight 0]')
 
 
 def _six(text):
@@ -93,6 +96,20 @@ def parse_similarity(argv):
             (w is not None and not (w >= 0.0 and np.isfinite(w))):
         return None
     return rest, opts
+
+
+def parse_patch_weight(argv):
+    """(the command line without --patch-weight W, W), W = 'uniform' when it was not given; None when it has no or an unknown value."""
+    rest, weight = [], 'uniform'
+    it = iter(argv)
+    for a in it:
+        if a != '--patch-weight':
+            rest.append(a)
+            continue
+        weight = next(it, None)
+        if weight not in ('uniform', 'variance'):
+            return None
+    return rest, weight
 
 
 def parse_refine(argv):
@@ -153,11 +170,13 @@ def pose_errors(P, P_gt, centre):
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
-    fine = parse_refine(argv)
+    weighted = parse_patch_weight(argv)
+    fine = None if weighted is None else parse_refine(weighted[0])
     cost = None if fine is None else parse_similarity(fine[0])
     parsed = None if cost is None else parse(cost[0])
     if parsed is None or (cost[1]['--landmark-weight'] is not None and parsed[1]['--offset'] is not None) or \
-            (fine[1] > 0 and cost[1]['--similarity'] == 'patch'):
+            (fine[1] > 0 and cost[1]['--similarity'] == 'patch' and weighted[1] == 'uniform') or \
+            (weighted[1] != 'uniform' and cost[1]['--similarity'] != 'patch'):
         print(USAGE.format(os.path.basename(sys.argv[0])))
         return 1
     (path, spec, idx), o = parsed
@@ -186,7 +205,8 @@ def main(argv=None):
         centre = reg.volume_centre(vol.shape, geom.I2P)
         back, Ei = np.linalg.inv(geom.I2P), np.linalg.inv(geom.E)
         kw = dict(popsize=o['--popsize'], generations=o['--generations'], sigma0=o['--sigma'], step_mm=o['--step'], seed=o['--seed'],
-                  similarity=so['--similarity'], patch_radius=so['--patch-radius'], patch_stride=so['--patch-stride'], refine=fine[1])
+                  similarity=so['--similarity'], patch_radius=so['--patch-radius'], patch_stride=so['--patch-stride'], refine=fine[1],
+                  patch_weight=weighted[1])
 
         def refined(what, r):
             if len(r.refine_cost):

@@ -6,6 +6,7 @@ dfl_sim_bank_gradncc launch).
 
     python examples/register_specimen.py full_res.h5 17-1882 --lands-csv lands.csv
     python examples/register_specimen.py full_res.h5 17-1882 --gt-lands --projs 0,3,7 --refine 20 --out run1
+    python examples/register_specimen.py full_res.h5 17-1882 --gt-lands --similarity patch --patch-weight variance --refine 20
 
 Every selected projection (--projs, default: all of the specimen) gets its geometry, its preprocessed fixed image and its
 start pose from landmarks (register.pnp) exactly as register_2d3d.py gives them to one projection: --lands-csv FILE reads
@@ -30,10 +31,10 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dfl_amd  # noqa: E402,F401
 from dfl_amd import _native as nat, drr, fullres, preprocess, register as reg  # noqa: E402
-from register_2d3d import _WithPoses, parse_refine, parse_similarity, pose_errors, read_lands_csv  # noqa: E402
+from register_2d3d import _WithPoses, parse_patch_weight, parse_refine, parse_similarity, pose_errors, read_lands_csv  # noqa: E402
 
 USAGE = ('Usage: {} <HDF5 full-res data file> <specimen ID> (--lands-csv FILE | --gt-lands) [--projs 0,3,7] [--out PREFIX] [--crop 50] '
-         '[--ds-factor 8] [--popsize 16] [--generations 80] [--seed 0] [--similarity global|patch] [--patch-radius 7] [--patch-stride 4] '
+         '[--ds-factor 8] [--popsize 16] [--generations 80] [--patch-weight uniform|variance] [--seed 0] [--similarity global|patch] [--patch-radius 7] [--patch-stride 4] '
          '[--landmark-weight 0] [--refine 0] [--max-views N]')
 
 
@@ -50,9 +51,10 @@ DEFAULTS = {'--out': None, '--crop': 50, '--ds-factor': 8, '--popsize': 16, '--g
             '--projs': None, '--max-views': None, '--gt-lands': False}
 
 
-def parse(argv):
+def parse(argv, patch_weight='uniform'):
     """((file, specimen), options) with '--refine', the options of the cost and the rest in one dict, or None when the
-    command line is not understood, names no or two landmark sources, or asks for what register_many refuses."""
+    command line is not understood, names no or two landmark sources, or asks for what register_many refuses.
+    patch_weight is what register_2d3d.parse_patch_weight took out of the command line before."""
     fine = parse_refine(list(argv))
     cost = None if fine is None else parse_similarity(fine[0])
     if cost is None:
@@ -73,13 +75,15 @@ def parse(argv):
         else:
             pos.append(a)
     ok = len(pos) == 2 and (opts['--lands-csv'] is not None) + opts['--gt-lands'] == 1 and opts['--popsize'] >= 4 and \
-        opts['--generations'] >= 0 and not (opts['--refine'] > 0 and opts['--similarity'] == 'patch') and \
+        opts['--generations'] >= 0 and not (opts['--refine'] > 0 and opts['--similarity'] == 'patch' and patch_weight == 'uniform') and \
+        not (patch_weight != 'uniform' and opts['--similarity'] != 'patch') and \
         (opts['--max-views'] is None or opts['--popsize'] <= opts['--max-views'] <= 65535)
     return (tuple(pos), opts) if ok else None
 
 
 def main(argv=None):
-    parsed = parse(sys.argv[1:] if argv is None else argv)
+    weighted = parse_patch_weight(sys.argv[1:] if argv is None else argv)
+    parsed = None if weighted is None else parse(*weighted)
     if parsed is None:
         print(USAGE.format(os.path.basename(sys.argv[0])))
         return 1
@@ -137,7 +141,8 @@ def main(argv=None):
                                     P0=np.stack([jobs[i]['P0'] for i in group]), popsize=o['--popsize'], generations=o['--generations'],
                                     seed=o['--seed'], similarity=o['--similarity'], patch_radius=o['--patch-radius'],
                                     patch_stride=o['--patch-stride'], landmarks=[jobs[i]['lands'] for i in group],
-                                    landmark_weight=o['--landmark-weight'] or 0.0, refine=o['--refine'], max_views=o['--max-views'])
+                                    landmark_weight=o['--landmark-weight'] or 0.0, refine=o['--refine'], max_views=o['--max-views'],
+                                    patch_weight=weighted[1])
             for i, r in zip(group, res):
                 rows[i] = r
         prefix = o['--out'] or '{}_all'.format(spec)

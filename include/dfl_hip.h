@@ -48,8 +48,8 @@ const char* dfl_last_error(void);
  * bn_bwd_finalize, bn_relu_bwd, affine_copy, pool, head_fwd, head_bwd, loss, ensemble, op, reduce_job, prep,
  * est_lands, upsample, augment_args, augment_item, overlay, resample_plan, resample_args, fullres, mesh_mc,
  * mesh_decode, mesh_topo, mesh_csr, mesh_smooth, mesh_xform, mesh_normals, preproc_projs, preproc_segs, restore_labels,
- * sim_prepare, sim_gradncc, expose, sim_patch_prepare, sim_patch_gradncc, sim_gradncc_bwd, drr_pose_grad,
- * sim_bank_gradncc, sim_bank_gradncc_bwd, sim_patch_bank_gradncc, drr_object, drr_args, optim_pack): lets a
+ * sim_prepare, sim_gradncc, expose, sim_patch_prepare, sim_patch_gradncc, sim_gradncc_bwd, sim_patch_weights,
+ * sim_patch_eval, drr_pose_grad, sim_bank_gradncc, sim_bank_gradncc_bwd, sim_patch_bank_gradncc, drr_object, drr_args, optim_pack): lets a
  * binding written in another language verify the size of its struct mirrors at load time.  Returns -1 past the end.
  * Sizes say nothing about field order or type: the Python binding derives its structs, constants and signatures from this
  * file (dfl_amd/_cabi.py), and tests/test_cabi_cpu.py holds every field offset against a C compiler's offsetof. */
@@ -1257,6 +1257,70 @@ typedef struct {
   int32_t V, H, W, rho, stride, F;
 } dfl_sim_patch_bank_gradncc_args;
 int dfl_sim_patch_bank_gradncc(const dfl_sim_patch_bank_gradncc_args* a, dfl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Weighted patch gradient-NCC and the patch adjoint (csrc/sim_patch.hip; DESIGN.md section 21 states the semantics,
+ * tests/patch_grad_ref.py restates them in numpy float64).  Patches, flags and the per-patch ncc are those above.
+ *
+ * Weights: w_x[p] = sum (fx - mean fx)^2 over the counted pixels of a patch that counts in x, else 0; w_y likewise;
+ * pwsum[d] = sum_p w_d[p], positive exactly when some patch counts in d.  dfl_sim_patch_weights, once per fixed image after
+ * dfl_sim_patch_prepare (for a bank: once per image on its slices), writes pweights[P][2] and pwsum[2] in one workgroup:
+ * thread t adds the patches t, t + 256, ... in index order, then the threads in a fixed order.
+ *   weighted cost[v] = 1 - (X + Y) / 2,  X = sum_p w_x[p] ncc_x[p] / pwsum[0] (0 when pwsum[0] = 0), Y likewise;
+ * the uniform cost above is w = 1 on the patches that count, pwsum = pcount.
+ *
+ * dfl_sim_patch_eval is dfl_sim_patch_gradncc with three optional parts.  pweights with pwsum (both or neither): the
+ * weighted cost; both NULL: the uniform one.  fixed_of [V] (device) with F: a bank, as dfl_sim_patch_bank_gradncc (pweights
+ * is then [F][P][2] and pwsum [F][2]); NULL: one image, and F is not read.  d_moving [V][H][W]: the adjoint
+ * d cost[v] / d moving[v][r][c] for every pixel, the border included; NULL: the forward alone.  The forward kernels always
+ * run first, so cost has the same bits with and without d_moving; with pweights, fixed_of and d_moving all NULL it has the
+ * bits of dfl_sim_patch_gradncc, with fixed_of alone those of dfl_sim_patch_bank_gradncc.
+ *
+ * The adjoint: let c_d[p] = w_d[p] / pwsum[d] (weighted) or 1 / pcount[d] on the patches that count in d (uniform), else
+ * 0.  With a the moving and b the fixed Sobel values of direction d over the counted pixels of patch p, va and vb their
+ * sums of squared deviations, cab the sum of the products of the deviations:
+ *   alpha_p = -1 / (2 sqrt(va vb)),  beta_p = cab / (2 va sqrt(va vb)),  both 0 where the forward rule makes that ncc 0;
+ *   g_d(q) = sum over the patches p that hold the counted interior pixel q, in ascending (a, b) order, of
+ *            c_d[p] alpha_p (b_q - mean_p b) + c_d[p] beta_p (a_q - mean_p a);   0 at a pixel that is not counted or in no patch;
+ *   d_moving = Sobel^T (g_x, g_y), as dfl_sim_gradncc_bwd gathers it.
+ * Per view and patch eight float32 (c alpha, c beta, mean a, mean b of x, then of y) are formed in float64, rounded once
+ * and kept in scratch; a workgroup owns a 16 x 16 tile of d_moving and adds the patches of a pixel in float32, every product
+ * rounded on its own.  No atomics: a view's outputs depend on its own pixels, its fixed image and H, W, rho, stride only.
+ * A view whose fixed_of entry is outside [0, F) gets cost = NaN and d_moving = 0; the other views are not affected.
+ * scratch holds at least dfl_sim_patch_eval_scratch_doubles(V, H, W, rho, stride, bwd) doubles: 2 V PR, and 4 V P more
+ * with bwd != 0 (negative: bad sizes, or more than 2^31 - 1).
+ * Refused with nothing launched: what dfl_sim_patch_gradncc refuses (and, with fixed_of, what the bank form refuses),
+ * pweights without pwsum or pwsum without pweights, a short scratch, and with d_moving an image of more than 16 x 65535
+ * rows; for dfl_sim_patch_weights NULL pointers and P < 1 or P >= 2^31.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct {
+  const double* ptotals;          /* [P][DFL_SIM_TOTALS], of dfl_sim_patch_prepare */
+  const unsigned char* pflags;    /* [P] */
+  double* pweights;               /* [P][2] */
+  double* pwsum;                  /* [2] */
+  int64_t P;                      /* dfl_sim_patch_count(H, W, rho, stride) */
+} dfl_sim_patch_weights_args;
+int dfl_sim_patch_weights(const dfl_sim_patch_weights_args* a, dfl_stream_t stream);
+
+typedef struct {
+  const float* moving;            /* [V][H][W] */
+  const float* fx;                /* [H][W], or [F][H][W] with fixed_of */
+  const float* fy;
+  const unsigned char* counted;
+  const double* ptotals;          /* [P][DFL_SIM_TOTALS], or [F][P][DFL_SIM_TOTALS] */
+  const unsigned char* pflags;    /* [P], or [F][P] */
+  const int32_t* pcount;          /* [2], or [F][2] */
+  const double* pweights;         /* [P][2], or [F][P][2]; NULL: the uniform cost */
+  const double* pwsum;            /* [2], or [F][2]; NULL exactly when pweights is */
+  const int32_t* fixed_of;        /* [V], device; NULL: one fixed image */
+  double* scratch;                /* [V][PR][2], then [V][P][8] float32 with d_moving */
+  double* cost;                   /* [V] */
+  float* d_moving;                /* [V][H][W]; NULL: the forward alone */
+  int64_t scratch_doubles;        /* what scratch holds */
+  int32_t V, H, W, rho, stride, F;
+} dfl_sim_patch_eval_args;
+int dfl_sim_patch_eval(const dfl_sim_patch_eval_args* a, dfl_stream_t stream);
+int dfl_sim_patch_eval_scratch_doubles(int32_t V, int32_t H, int32_t W, int32_t rho, int32_t stride, int32_t bwd);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Detector model: rendered line integrals -> detector intensities (csrc/expose.hip; DESIGN.md section 17 states the

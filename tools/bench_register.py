@@ -13,6 +13,10 @@ phantom's poses and the candidates are drawn around a start 2 units away in ever
               adjoint of the similarity (dfl_sim_gradncc_bwd) and the pose gradient (dfl_drr_pose_grad) timed as calls with
               device events, the whole evaluation (with packing, uploads, the copy and the chain on the host) by the wall
               clock, next to one cost evaluation of one view; in render-equivalents = (render + adjoint + pose gradient) / render
+  weighted    the weighted patch cost and the patch adjoint (dfl_sim_patch_eval): the forward on the 32 views
+              and the adjoint of one view (device events), and in alternating windows of this process a one-view cost-and-gradient
+              evaluation next to the global one (check: within 5 % plus the spread) and a generation next to one with the uniform
+              patch cost (check: within 1 % plus the spread)
   many        16 problems with lambda = 32 (register_many) against the same 16 one after the other, in this
               process and run, alternating windows: (i) a generation of register_many against a generation of each of 16
               register() calls, (ii) one lockstep cost-and-gradient round of the finish against 16 single evaluations (wall
@@ -188,6 +192,68 @@ def main():
     print('one view: render %.4f ms, adjoint %.4f ms, pose gradient %.4f ms = %.2f render-equivalents; wall clock of an evaluation: cost '
           '%.3f ms, cost and gradient %.3f ms' % (grad['render']['ms'], grad['adjoint']['ms'], grad['pose_gradient']['ms'],
                                                    grad['render_equivalents'], grad['cost_wall_ms'], grad['cost_and_gradient_wall_ms']), flush=True)
+    # the weighted patch cost and the patch adjoint, next to what they stand beside: the forward next to
+    # dfl_sim_patch_gradncc, the adjoint next to dfl_sim_gradncc_bwd, a one-view evaluation next to the global one and a generation
+    # next to one with the uniform patch cost -- the last two in alternating windows of this process
+    wsim = reg.PatchSimilarity(fixed, None, LAMBDA, PATCH_RADIUS, PATCH_STRIDE, weight='variance')
+    wa = wsim.args(att)
+    nat.call('dfl_sim_patch_eval', wa, stream)
+    wcost = wsim.out.cpu().numpy()
+    assert np.isfinite(wcost).all() and (wcost > 0).all() and (wcost < 2).all(), wcost
+    wsim1 = reg.PatchSimilarity(fixed, None, 1, PATCH_RADIUS, PATCH_STRIDE, weight='variance')
+    wpatch = reg._patch_params(PATCH_RADIUS, PATCH_STRIDE, None) + ('variance',)
+    wlevel1 = reg._Level(vol, grid, fixed, None, 1, STEP_MM, wpatch)
+
+    def alternating(fa, fb):
+        """`reps` windows of fa and fb in turn (each returns ms per unit): (medians, min and max of each, the larger spread)."""
+        fa(), fb()
+        a, b = [], []
+        for _ in range(args.reps):
+            a.append(fa())
+            b.append(fb())
+        return a, b, max(max(a) - min(a), max(b) - min(b))
+
+    def evaluation(level):
+        n = max(int(args.window / (1e-3 * grad['cost_and_gradient_wall_ms'])) + 1, 10)
+        return lambda: wall(lambda: level.costs_and_grads(c2i1, masks, xis1, [0, 1, 2]), n)
+
+    ea, eb, espread = alternating(evaluation(level1), evaluation(wlevel1))
+    eg, ew = statistics.median(ea), statistics.median(eb)
+
+    def generations_of(**kw):
+        gens = max(res['generation']['generations_per_window'], 5)
+
+        def run():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            reg.register(vol, geom, fixed, theta0=THETA0, popsize=LAMBDA, generations=gens, step_mm=STEP_MM, similarity='patch',
+                         patch_radius=PATCH_RADIUS, patch_stride=PATCH_STRIDE, **kw)
+            return 1e3 * (time.perf_counter() - t0) / (gens + 1)
+        return run
+
+    ga, gb, gspread = alternating(generations_of(), generations_of(patch_weight='variance'))
+    gu, gw = statistics.median(ga), statistics.median(gb)
+    res['weighted_patch'] = {
+        'radius': PATCH_RADIUS, 'stride': PATCH_STRIDE, 'patches': wsim.patches,
+        'similarity': windows(lambda: nat.call('dfl_sim_patch_eval', wa, stream), args.window, args.reps),
+        'adjoint_one_view': windows(lambda: wsim1.cost_and_adjoint(att1), args.window, args.reps),
+        'global_adjoint_one_view_ms': grad['adjoint']['ms'],
+        'cost_and_gradient': {'global_wall_ms': round(eg, 4), 'global_min_max_ms': [round(min(ea), 4), round(max(ea), 4)],
+                              'weighted_patch_wall_ms': round(ew, 4), 'weighted_patch_min_max_ms': [round(min(eb), 4), round(max(eb), 4)],
+                              'spread_ms': round(espread, 4), 'limit_ms': round(eg * 1.05 + espread, 4),
+                              'rule': 'weighted_patch_wall_ms <= global_wall_ms * 1.05 + the larger spread (max - min) of the two',
+                              'ok': bool(ew <= eg * 1.05 + espread)},
+        'generation': {'uniform_patch_ms': round(gu, 4), 'uniform_patch_min_max_ms': [round(min(ga), 4), round(max(ga), 4)],
+                       'weighted_patch_ms': round(gw, 4), 'weighted_patch_min_max_ms': [round(min(gb), 4), round(max(gb), 4)],
+                       'spread_ms': round(gspread, 4), 'limit_ms': round(gu * 1.01 + gspread, 4),
+                       'rule': 'weighted_patch_ms <= uniform_patch_ms * 1.01 + the larger spread (max - min) of the two',
+                       'ok': bool(gw <= gu * 1.01 + gspread)}}
+    wp = res['weighted_patch']
+    print('weighted patch cost: similarity %.4f ms (uniform %.4f), adjoint of one view %.4f ms (global %.4f); one-view cost and gradient %.3f '
+          'ms (global %.3f, limit %.3f: %s); generation %.3f ms (uniform patch %.3f, limit %.3f: %s)'
+          % (wp['similarity']['ms'], res['similarity_patch']['ms'], wp['adjoint_one_view']['ms'], grad['adjoint']['ms'], ew, eg,
+             wp['cost_and_gradient']['limit_ms'], 'ok' if wp['cost_and_gradient']['ok'] else 'ABOVE', gw, gu, wp['generation']['limit_ms'],
+             'ok' if wp['generation']['ok'] else 'ABOVE'), flush=True)
     # N problems at once (register_many, DESIGN.md section 20) against the same N one after the other, in this process
     N = MANY
     offsets = 1.5 * np.random.default_rng(1).standard_normal((N, 6))
