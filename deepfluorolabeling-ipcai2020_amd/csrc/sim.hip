@@ -61,10 +61,7 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_gradncc_kernel(const float* _
   __shared__ double lds[SIM_MOVING * 4];
   const int band = blockIdx.x, view = blockIdx.y;
   const int f = sim_image_of(fixed_of, view, F);
-  const size_t plane = f < 0 ? 0 : (size_t)f * H * W;                   // f < 0: the loop below has no pixel
-  fx += plane;
-  fy += plane;
-  counted += plane;
+  sim_planes_of(fx, fy, counted, f < 0 ? 0 : f, H, W);                   // f < 0: the loop below has no pixel
   const int r0 = 1 + band * SIM_ROWS;                                   // first interior row of the band
   const int rows = min(SIM_ROWS, H - 1 - r0);                           // interior rows are 1 .. H - 2
   const int wi = W - 2;
@@ -109,9 +106,7 @@ __global__ __launch_bounds__(64) void sim_finish_kernel(const double* __restrict
 inline int sim_bands(int H) { return (int)ceil_div(H - 2, SIM_ROWS); }
 
 // ---- the adjoint: d cost[v] / d moving[v][r][c] (dfl_sim_gradncc_bwd) ----------------------------------------------------------
-// With a the moving and b the fixed Sobel values of one direction, d(-ncc / 2) / d a_p = alpha (b_p - mean b) + beta (a_p - mean a)
-// at a counted pixel, alpha = -1 / (2 sqrt(va vb)), beta = cab / (2 va sqrt(va vb)); both 0 where the forward rule makes the ncc 0.
-constexpr int SIM_COEF = 8;          // per view: alpha, beta, mean a, mean b of x, then of y (float32)
+constexpr int SIM_COEF = 8;          // per view: alpha, beta, mean a, mean b of x, then of y (float32; sim_coef4, csrc/sim.h)
 
 // One thread per view: the view's records added in index order (as sim_finish_kernel adds them), the coefficients in float64
 __global__ __launch_bounds__(64) void sim_coef_kernel(const double* __restrict__ scratch, const double* __restrict__ totals,
@@ -131,76 +126,28 @@ __global__ __launch_bounds__(64) void sim_coef_kernel(const double* __restrict__
   const double n = totals[0];
 #pragma unroll
   for (int dir = 0; dir < 2; ++dir) {
-    const double sa = m[3 * dir], saa = m[3 * dir + 1], sab = m[3 * dir + 2], sb = totals[1 + 2 * dir], sbb = totals[2 + 2 * dir];
-    double alpha = 0.0, beta = 0.0, ma = 0.0, mb = 0.0;
-    if (n >= 1.0) {
-      const double va = sim_var(n, sa, saa), vb = sim_var(n, sb, sbb);
-      if (sim_live(va, saa) && sim_live(vb, sbb)) {                     // the rule of sim_ncc
-        const double root = sqrt(va * vb);
-        alpha = -0.5 / root;
-        beta = 0.5 * (sab - sa * sb / n) / (va * root);
-        ma = sa / n;
-        mb = sb / n;
-      }
-    }
     float* out = coef + (size_t)view * SIM_COEF + 4 * dir;
-    out[0] = (float)alpha;
-    out[1] = (float)beta;
-    out[2] = (float)ma;
-    out[3] = (float)mb;
+    if (n >= 1.0)
+      sim_coef4(out, 1.0, n, m[3 * dir], m[3 * dir + 1], totals[1 + 2 * dir], totals[2 + 2 * dir], m[3 * dir + 2]);
+    else
+      out[0] = out[1] = out[2] = out[3] = 0.f;
   }
 }
 
-// A workgroup owns a 16 x 16 tile of one view's d_moving.  The tile of `moving` with a halo of 2 goes to LDS (0 outside the
-// image); from it the 18 x 18 pixels around the tile get g = d cost / d (Sobel value), 0 where the pixel is not counted; every
-// output pixel then gathers the nine pixels whose window holds it with the Sobel weight it has there.
+// sim_adjoint_tile (csrc/sim.h) with the g of one correlation over the whole image: the view's eight coefficients
 __global__ __launch_bounds__(SIM_THREADS) void sim_adjoint_kernel(const float* __restrict__ moving, const float* __restrict__ fx,
                                                                   const float* __restrict__ fy, const unsigned char* __restrict__ counted,
                                                                   const int32_t* __restrict__ fixed_of, const float* __restrict__ coef,
                                                                   float* __restrict__ d_moving, int H, int W, int F) {
   // every product is rounded on its own: where moving matches fixed the two terms of g cancel exactly, which an FMA would undo
 #pragma clang fp contract(off)
-  constexpr int IN = SIM_TILE_IN, G = SIM_TILE_G;
-  __shared__ float sm[IN][IN + 1];
-  __shared__ float sgx[G][G + 1], sgy[G][G + 1];
-  const int view = blockIdx.z;
-  const int r0 = blockIdx.y * SIM_TILE, c0 = blockIdx.x * SIM_TILE;
-  const int f = sim_image_of(fixed_of, view, F);
-  if (f < 0) {                                                          // the whole workgroup, before its first barrier
-    const int r = r0 + threadIdx.x / SIM_TILE, c = c0 + threadIdx.x % SIM_TILE;
-    if (r < H && c < W) d_moving[((size_t)view * H + r) * W + c] = 0.f;
-    return;
-  }
-  const size_t plane = (size_t)f * H * W;
-  fx += plane;
-  fy += plane;
-  counted += plane;
-  const float* img = moving + (size_t)view * H * W;
-  sim_stage_tile(sm, img, H, W, r0, c0);
-  const float* cf = coef + (size_t)view * SIM_COEF;
+  const float* cf = coef + (size_t)blockIdx.z * SIM_COEF;              // zeros for a view outside the bank (sim_coef_kernel)
   const float ax = cf[0], bx = cf[1], max_ = cf[2], mbx = cf[3], ay = cf[4], by = cf[5], may = cf[6], mby = cf[7];
-  __syncthreads();
-  for (int i = threadIdx.x; i < G * G; i += SIM_THREADS) {
-    const int lr = i / G, lc = i % G, r = r0 - 1 + lr, c = c0 - 1 + lc;
-    float gx = 0.f, gy = 0.f;
-    if (r >= 1 && r <= H - 2 && c >= 1 && c <= W - 2) {
-      const size_t at = (size_t)r * W + c;
-      if (counted[at]) {
-        // Sobel on the staged tile: pixel (r, c) sits at sm[lr + 1][lc + 1].  sim_sobel9 is defined outside this function's
-        // contract(off) and may fuse x + 2 y; that gives the same bits either way, since 2 y is exact
-        float mx, my;
-        sim_sobel9(sm[lr][lc], sm[lr][lc + 1], sm[lr][lc + 2], sm[lr + 1][lc], sm[lr + 1][lc + 2], sm[lr + 2][lc], sm[lr + 2][lc + 1],
-                   sm[lr + 2][lc + 2], mx, my);
-        gx = ax * (fx[at] - mbx) + bx * (mx - max_);
-        gy = ay * (fy[at] - mby) + by * (my - may);
-      }
-    }
-    sgx[lr][lc] = gx;
-    sgy[lr][lc] = gy;
-  }
-  __syncthreads();
-  const int tr = threadIdx.x / SIM_TILE, tc = threadIdx.x % SIM_TILE, r = r0 + tr, c = c0 + tc;
-  if (r < H && c < W) d_moving[((size_t)view * H + r) * W + c] = sim_sobel_gather(sgx, sgy, tr, tc);
+  sim_adjoint_tile(moving, fx, fy, counted, fixed_of, d_moving, H, W, F,
+                   [=](float fxp, float fyp, float mx, float my, int, int, float& gx, float& gy) {
+                     gx = ax * (fxp - mbx) + bx * (mx - max_);
+                     gy = ay * (fyp - mby) + by * (my - may);
+                   });
 }
 
 // records [V][bands][6], then the coefficients [V][8] float32

@@ -48,23 +48,14 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_patch_prepare_kernel(const fl
   extern __shared__ double cols[];                                      // [SIM_FIXED][W - 2]
   const int a = blockIdx.x, wi = W - 2;
   const int r0 = 1 + a * stride;                                        // first image row of the band
-  for (int j = threadIdx.x; j < wi; j += SIM_THREADS) {
-    double s[SIM_FIXED] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int k = 0; k < S; ++k) {
-      const size_t at = (size_t)(r0 + k) * W + (1 + j);
-      if (counted[at]) sim_fixed_sums(s, fx[at], fy[at]);
-    }
-#pragma unroll
-    for (int q = 0; q < SIM_FIXED; ++q) cols[q * wi + j] = s[q];
-  }
+  sim_column_sums<SIM_FIXED>(cols, wi, r0, S, [=](double (&s)[SIM_FIXED], int r, int c) {
+    const size_t at = (size_t)r * W + c;
+    if (counted[at]) sim_fixed_sums(s, fx[at], fy[at]);
+  });
   __syncthreads();
   for (int b = threadIdx.x; b < PC; b += SIM_THREADS) {
-    double s[SIM_FIXED] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    const int j0 = b * stride;
-    for (int k = 0; k < S; ++k) {
-#pragma unroll
-      for (int q = 0; q < SIM_FIXED; ++q) s[q] += cols[q * wi + j0 + k];
-    }
+    double s[SIM_FIXED];
+    sim_patch_sums<SIM_FIXED>(s, cols, wi, b * stride, S);
     const size_t p = (size_t)a * PC + b;
 #pragma unroll
     for (int q = 0; q < SIM_FIXED; ++q) ptotals[p * SIM_FIXED + q] = s[q];
@@ -116,26 +107,7 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_patch_weights_kernel(const do
   }
 }
 
-constexpr int SIM_PCOEF = 8;         // per view and patch: c alpha, c beta, mean a, mean b of x, then of y (float32)
-
-// The four coefficients of one direction of one patch that counts in it (the rule of sim_ncc and sim_coef_kernel, csrc/sim.hip),
-// formed in float64 and rounded once; share = the patch's part of the cost: w / pwsum, or 1 / pcount
-__device__ __forceinline__ void sim_patch_coef(float* __restrict__ out, double share, double n, double sa, double saa, double sb, double sbb,
-                                               double sab) {
-  double ca = 0.0, cb = 0.0, ma = 0.0, mb = 0.0;
-  const double va = sim_var(n, sa, saa), vb = sim_var(n, sb, sbb);
-  if (sim_live(va, saa) && sim_live(vb, sbb)) {
-    const double root = sqrt(va * vb);
-    ca = share * (-0.5 / root);
-    cb = share * (0.5 * (sab - sa * sb / n) / (va * root));
-    ma = sa / n;
-    mb = sb / n;
-  }
-  out[0] = (float)ca;
-  out[1] = (float)cb;
-  out[2] = (float)ma;
-  out[3] = (float)mb;
-}
+constexpr int SIM_PCOEF = 8;         // per view and patch: c alpha, c beta, mean a, mean b of x, then of y (float32; sim_coef4, csrc/sim.h)
 
 // pweights (with pwsum) and coef are optional: both nullptr is the cost of section 18 as dfl_sim_patch_gradncc always gave it.
 // One body, two instantiations: EXT = false is launched when both are nullptr and holds nothing of the two parts, so the existing
@@ -158,10 +130,8 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_patch_gradncc_kernel(const fl
   const int r0 = 1 + a * stride;
   const int f = sim_image_of(fixed_of, view, F);
   if (f < 0) return;                                                    // the whole workgroup: sim_patch_finish_kernel reads no record
-  const size_t plane = (size_t)f * H * W, patches = (size_t)f * gridDim.x * PC;
-  fx += plane;
-  fy += plane;
-  counted += plane;
+  const size_t patches = (size_t)f * gridDim.x * PC;
+  sim_planes_of(fx, fy, counted, f, H, W);
   ptotals += patches * SIM_FIXED;
   pflags += patches;
   const bool weighted = EXT && pweights != nullptr, with_coef = EXT && coef != nullptr;
@@ -172,15 +142,9 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_patch_gradncc_kernel(const fl
   pcount += 2 * (size_t)f;
   if (with_coef) coef += (size_t)view * gridDim.x * PC * SIM_PCOEF;
   const float* img = moving + (size_t)view * H * W;
-  for (int j = threadIdx.x; j < wi; j += SIM_THREADS) {
-    double s[SIM_MOVING] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int k = 0; k < S; ++k) {
-      const int r = r0 + k, c = 1 + j;
-      if (counted[(size_t)r * W + c]) sim_moving_sums(s, img, fx, fy, W, r, c);
-    }
-#pragma unroll
-    for (int q = 0; q < SIM_MOVING; ++q) cols[q * wi + j] = s[q];
-  }
+  sim_column_sums<SIM_MOVING>(cols, wi, r0, S, [=](double (&s)[SIM_MOVING], int r, int c) {
+    if (counted[(size_t)r * W + c]) sim_moving_sums(s, img, fx, fy, W, r, c);
+  });
   __syncthreads();
   double acc[2] = {0.0, 0.0};
   for (int b = threadIdx.x; b < PC; b += SIM_THREADS) {
@@ -193,12 +157,8 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_patch_gradncc_kernel(const fl
       }
       continue;
     }
-    double s[SIM_MOVING] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    const int j0 = b * stride;
-    for (int k = 0; k < S; ++k) {
-#pragma unroll
-      for (int q = 0; q < SIM_MOVING; ++q) s[q] += cols[q * wi + j0 + k];
-    }
+    double s[SIM_MOVING];
+    sim_patch_sums<SIM_MOVING>(s, cols, wi, b * stride, S);
     const double* t = ptotals + p * SIM_FIXED;
     if (!weighted) {
       if (flags & 1) acc[0] += sim_ncc(t[0], s[0], s[1], t[1], t[2], s[2]);
@@ -213,7 +173,7 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_patch_gradncc_kernel(const fl
         float* out = coef + p * SIM_PCOEF + 4 * d;
         if (flags & (1 << d)) {                                         // it counts: pcount[d] >= 1, and pwsum[d] >= w_d > 0
           const double share = weighted ? pweights[p * 2 + d] / pwsum[d] : 1.0 / (double)pcount[d];
-          sim_patch_coef(out, share, t[0], s[3 * d], s[3 * d + 1], t[1 + 2 * d], t[2 + 2 * d], s[3 * d + 2]);
+          sim_coef4(out, share, t[0], s[3 * d], s[3 * d + 1], t[1 + 2 * d], t[2 + 2 * d], s[3 * d + 2]);
         } else {
           out[0] = out[1] = out[2] = out[3] = 0.f;
         }
@@ -256,8 +216,8 @@ __global__ __launch_bounds__(64) void sim_patch_finish_kernel(const double* __re
 }
 
 // ---- the adjoint: d cost[v] / d moving[v][r][c] (dfl_sim_patch_eval with d_moving) ------------------------------------------------
-// sim_adjoint_kernel's shape (csrc/sim.hip): a workgroup owns a 16 x 16 tile of one view's d_moving, stages the tile of `moving`
-// with a halo of 2 in LDS and computes g = d cost / d (Sobel value) on the 18 x 18 pixels around the tile; here g at interior
+// sim_adjoint_tile (csrc/sim.h), as sim_adjoint_kernel (csrc/sim.hip): a workgroup owns a 16 x 16 tile of one view's d_moving, stages
+// the tile of `moving` with a halo of 2 in LDS and computes g = d cost / d (Sobel value) on the 18 x 18 pixels around the tile; here g at interior
 // pixel (i, j) is the sum over the patches that hold it -- a from max(0, ceil((i - S + 1) / s)) to min(PR - 1, i / s), b likewise,
 // a outer and b inner -- of c alpha (b_q - mean b) + c beta (a_q - mean a) with the patch's eight coefficients, read straight
 // from global memory (32 B per patch, L1/L2-resident: a tile of 18 x 18 pixels shares at most (17 / s + S / s + 2)^2 patches).
@@ -270,52 +230,20 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_patch_adjoint_kernel(const fl
                                                                         int PR, int PC, int F) {
   // every product is rounded on its own, as in sim_adjoint_kernel: where moving matches fixed the two terms of a patch cancel
 #pragma clang fp contract(off)
-  constexpr int G = SIM_TILE_G;
-  __shared__ float sm[SIM_TILE_IN][SIM_TILE_IN + 1];
-  __shared__ float sgx[G][G + 1], sgy[G][G + 1];
-  const int view = blockIdx.z;
-  const int r0 = blockIdx.y * SIM_TILE, c0 = blockIdx.x * SIM_TILE;
-  const int f = sim_image_of(fixed_of, view, F);
-  if (f < 0) {                                                          // the whole workgroup, before its first barrier
-    const int r = r0 + threadIdx.x / SIM_TILE, c = c0 + threadIdx.x % SIM_TILE;
-    if (r < H && c < W) d_moving[((size_t)view * H + r) * W + c] = 0.f;
-    return;
-  }
-  const size_t plane = (size_t)f * H * W;
-  fx += plane;
-  fy += plane;
-  counted += plane;
-  coef += (size_t)view * PR * PC * SIM_PCOEF;
-  sim_stage_tile(sm, moving + (size_t)view * H * W, H, W, r0, c0);
-  __syncthreads();
-  for (int t = threadIdx.x; t < G * G; t += SIM_THREADS) {
-    const int lr = t / G, lc = t % G, r = r0 - 1 + lr, c = c0 - 1 + lc;
-    float gx = 0.f, gy = 0.f;
-    if (r >= 1 && r <= H - 2 && c >= 1 && c <= W - 2) {
-      const size_t at = (size_t)r * W + c;
-      if (counted[at]) {
-        float mx, my;                                                   // pixel (r, c) sits at sm[lr + 1][lc + 1]
-        sim_sobel9(sm[lr][lc], sm[lr][lc + 1], sm[lr][lc + 2], sm[lr + 1][lc], sm[lr + 1][lc + 2], sm[lr + 2][lc], sm[lr + 2][lc + 1],
-                   sm[lr + 2][lc + 2], mx, my);
-        const float bx = fx[at], by = fy[at];
-        const int i = r - 1, j = c - 1;
-        const int a_lo = i < S ? 0 : (i - S + stride) / stride, a_hi = min(PR - 1, i / stride);     // ceil((i - S + 1) / s)
-        const int b_lo = j < S ? 0 : (j - S + stride) / stride, b_hi = min(PC - 1, j / stride);
-        for (int a = a_lo; a <= a_hi; ++a) {
-          const float* cf = coef + ((size_t)a * PC + b_lo) * SIM_PCOEF;
-          for (int b = b_lo; b <= b_hi; ++b, cf += SIM_PCOEF) {
-            gx += cf[0] * (bx - cf[3]) + cf[1] * (mx - cf[2]);
-            gy += cf[4] * (by - cf[7]) + cf[5] * (my - cf[6]);
-          }
-        }
-      }
-    }
-    sgx[lr][lc] = gx;
-    sgy[lr][lc] = gy;
-  }
-  __syncthreads();
-  const int tr = threadIdx.x / SIM_TILE, tc = threadIdx.x % SIM_TILE, r = r0 + tr, c = c0 + tc;
-  if (r < H && c < W) d_moving[((size_t)view * H + r) * W + c] = sim_sobel_gather(sgx, sgy, tr, tc);
+  coef += (size_t)blockIdx.z * PR * PC * SIM_PCOEF;
+  sim_adjoint_tile(moving, fx, fy, counted, fixed_of, d_moving, H, W, F,
+                   [=](float bx, float by, float mx, float my, int r, int c, float& gx, float& gy) {
+                     const int i = r - 1, j = c - 1;
+                     const int a_lo = i < S ? 0 : (i - S + stride) / stride, a_hi = min(PR - 1, i / stride);     // ceil((i - S + 1) / s)
+                     const int b_lo = j < S ? 0 : (j - S + stride) / stride, b_hi = min(PC - 1, j / stride);
+                     for (int a = a_lo; a <= a_hi; ++a) {
+                       const float* cf = coef + ((size_t)a * PC + b_lo) * SIM_PCOEF;
+                       for (int b = b_lo; b <= b_hi; ++b, cf += SIM_PCOEF) {
+                         gx += cf[0] * (bx - cf[3]) + cf[1] * (mx - cf[2]);
+                         gy += cf[4] * (by - cf[7]) + cf[5] * (my - cf[6]);
+                       }
+                     }
+                   });
 }
 
 // the checks on sizes that every entry point shares; `who` names it in the message

@@ -403,81 +403,6 @@ def _device_image(t, what, dims, dtypes=(torch.float32,)):
     return t.detach().contiguous()
 
 
-class Similarity:
-    """The gradient-NCC cost of `views` moving images against one fixed image [H, W] (float32, on the GPU) with an
-    optional uint8 [H, W] mask: dfl_sim_prepare runs here, once; cost(moving) is one dfl_sim_gradncc launch and
-    returns a float64 tensor [V] on the device."""
-
-    def __init__(self, fixed, mask=None, views=1):
-        self.fixed = _device_image(fixed, 'the fixed image', 2)
-        dev = self.fixed.device
-        H, W = (int(s) for s in self.fixed.shape)
-        self.H, self.W, self.views = H, W, int(views)
-        self.mask = None
-        if mask is not None:
-            self.mask = _device_image(mask, 'the mask', 2, (torch.uint8,))
-            if tuple(self.mask.shape) != (H, W) or self.mask.device != dev:
-                raise nat.DflError('register: the mask is %s on %s, the fixed image %s on %s'
-                                   % (tuple(self.mask.shape), self.mask.device, (H, W), dev))
-        lib = nat.lib()
-        need = int(lib.dfl_sim_scratch_doubles(self.views, H, W))
-        if need < 0:
-            raise nat.DflError('register: %s' % lib.dfl_last_error().decode())
-        self.fx = torch.empty((H, W), dtype=torch.float32, device=dev)
-        self.fy = torch.empty((H, W), dtype=torch.float32, device=dev)
-        self.counted = torch.empty((H, W), dtype=torch.uint8, device=dev)
-        self.totals = torch.empty(nat.SIM_TOTALS, dtype=torch.float64, device=dev)
-        self.scratch = torch.empty(max(need, 1), dtype=torch.float64, device=dev)
-        self.out = torch.empty(self.views, dtype=torch.float64, device=dev)
-        a = nat.SimPrepareArgs(fixed=self.fixed.data_ptr(), mask=nat.ptr(self.mask), fx=self.fx.data_ptr(), fy=self.fy.data_ptr(),
-                               counted=self.counted.data_ptr(), totals=self.totals.data_ptr(), H=H, W=W)
-        drr.launch(dev, 'dfl_sim_prepare', a)
-
-    entry = 'dfl_sim_gradncc'                                       # what launch() calls with args()
-
-    def args(self, moving, out=None):
-        out = self.out if out is None else out
-        return nat.SimGradnccArgs(moving=moving.data_ptr(), fx=self.fx.data_ptr(), fy=self.fy.data_ptr(), counted=self.counted.data_ptr(),
-                                  totals=self.totals.data_ptr(), scratch=self.scratch.data_ptr(), cost=out.data_ptr(),
-                                  scratch_doubles=self.scratch.numel(), V=int(moving.shape[0]), H=self.H, W=self.W)
-
-    def _moving(self, moving):
-        mv = _device_image(moving, 'the moving images', 3)
-        if tuple(mv.shape[1:]) != (self.H, self.W) or mv.device != self.fixed.device or not 1 <= mv.shape[0] <= self.views:
-            raise nat.DflError('register: moving images of shape %s on %s for a fixed image of %d x %d on %s and at most %d views'
-                               % (tuple(mv.shape), mv.device, self.H, self.W, self.fixed.device, self.views))
-        return mv
-
-    def launch(self, moving, out=None):
-        """One launch of `entry` on checked moving images; the costs go to `out` (default: the first rows of self.out)."""
-        drr.launch(moving.device, self.entry, self.args(moving, out))
-
-    def cost(self, moving):
-        mv = self._moving(moving)
-        out = torch.empty(mv.shape[0], dtype=torch.float64, device=mv.device)
-        self.launch(mv, out)
-        return out
-
-    def cost_and_adjoint(self, moving):
-        """(cost [V] float64, d_moving [V, H, W] float32 = d cost[v] / d moving[v]) on the device: one dfl_sim_gradncc_bwd
-        launch.  The cost has the bits cost(moving) gives."""
-        mv = self._moving(moving)
-        V, dev = int(mv.shape[0]), mv.device
-        if getattr(self, 'bwd_scratch', None) is None:
-            lib = nat.lib()
-            need = int(lib.dfl_sim_gradncc_bwd_scratch_doubles(self.views, self.H, self.W))
-            if need < 0:
-                raise nat.DflError('register: %s' % lib.dfl_last_error().decode())
-            self.bwd_scratch = torch.empty(need, dtype=torch.float64, device=dev)
-        out = torch.empty(V, dtype=torch.float64, device=dev)
-        d_moving = torch.empty((V, self.H, self.W), dtype=torch.float32, device=dev)
-        a = nat.SimGradnccBwdArgs(moving=mv.data_ptr(), fx=self.fx.data_ptr(), fy=self.fy.data_ptr(), counted=self.counted.data_ptr(),
-                                  totals=self.totals.data_ptr(), scratch=self.bwd_scratch.data_ptr(), cost=out.data_ptr(),
-                                  d_moving=d_moving.data_ptr(), scratch_doubles=self.bwd_scratch.numel(), V=V, H=self.H, W=self.W)
-        drr.launch(dev, 'dfl_sim_gradncc_bwd', a)
-        return out, d_moving
-
-
 def _patch_params(radius, stride, min_count):
     """(rho, stride, min_count) as integers; min_count=None is half a patch, rounded up."""
     ok = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in (radius, stride)) and \
@@ -495,33 +420,158 @@ def _patch_weight(weight):
     return weight
 
 
-def _patch_weights(dev, ptotals, pflags, pweights, pwsum, P):
-    """dfl_sim_patch_weights on one image's patch totals and flags (for a bank: on that image's slices)."""
-    a = nat.SimPatchWeightsArgs(ptotals=ptotals.data_ptr(), pflags=pflags.data_ptr(), pweights=pweights.data_ptr(), pwsum=pwsum.data_ptr(), P=P)
-    drr.launch(dev, 'dfl_sim_patch_weights', a)
+def fixed_of_array(fixed_of, V, F):
+    """A sequence or array that says which of F fixed images each of V views is scored against -> int32 [V], checked on
+    the host: integers, one per view, each in [0, F)."""
+    a = np.asarray(fixed_of)
+    if a.ndim != 1 or a.shape[0] != V or a.dtype.kind not in 'iu':
+        raise nat.DflError('register: fixed_of has shape %s and dtype %s: %d integers expected, one per view' % (a.shape, a.dtype, V))
+    if V and (int(a.min()) < 0 or int(a.max()) >= F):
+        raise nat.DflError('register: fixed_of holds %d .. %d, the bank has the images 0 .. %d' % (int(a.min()), int(a.max()), F - 1))
+    return np.ascontiguousarray(a, np.int32)
 
 
-def _patch_eval_args(sim, moving, fixed_of, scratch, out, d_moving):
-    """The dfl_sim_patch_eval block of a weighted PatchSimilarity (fixed_of None) or PatchSimilarityBank."""
-    return nat.SimPatchEvalArgs(moving=moving.data_ptr(), fx=sim.fx.data_ptr(), fy=sim.fy.data_ptr(), counted=sim.counted.data_ptr(),
-                                ptotals=sim.ptotals.data_ptr(), pflags=sim.pflags.data_ptr(), pcount=sim.pcount.data_ptr(),
-                                pweights=sim.pweights.data_ptr(), pwsum=sim.pwsum.data_ptr(), fixed_of=nat.ptr(fixed_of),
-                                scratch=scratch.data_ptr(), cost=out.data_ptr(), d_moving=nat.ptr(d_moving), scratch_doubles=scratch.numel(),
-                                V=int(moving.shape[0]), H=sim.H, W=sim.W, rho=sim.radius, stride=sim.stride, F=getattr(sim, 'F', 1))
+_BLOCKS = {}                                                        # entry point -> (its struct, the names of the struct's fields)
 
 
-def _patch_cost_and_adjoint(sim, mv, fixed_of):
-    V, dev = int(mv.shape[0]), mv.device
-    if getattr(sim, 'bwd_scratch', None) is None:
+def _block(entry, values):
+    """The argument block of a dfl_sim_* entry point (dfl_sim_patch_eval -> nat.SimPatchEvalArgs) filled from `values`, a dict of
+    every field any of these blocks has, addresses and integers: the struct takes the ones its _fields_ name, in their order."""
+    if entry not in _BLOCKS:
+        cls = getattr(nat, ''.join(word.capitalize() for word in entry.split('_')[1:]) + 'Args')
+        _BLOCKS[entry] = cls, tuple(name for name, *_ in cls._fields_)
+    cls, names = _BLOCKS[entry]
+    return cls(*map(values.__getitem__, names))
+
+
+def _scratch(need, dev, least=0):
+    """A float64 scratch of `need` doubles, which is what a dfl_*_scratch_doubles function just said: negative is its refusal."""
+    if need < 0:
+        raise nat.DflError('register: %s' % nat.lib().dfl_last_error().decode())
+    return torch.empty(max(int(need), least), dtype=torch.float64, device=dev)
+
+
+class Similarity:
+    """The gradient-NCC cost of `views` moving images against one fixed image [H, W] (float32, on the GPU) with an
+    optional uint8 [H, W] mask: dfl_sim_prepare runs here, once; cost(moving) is one dfl_sim_gradncc launch and
+    returns a float64 tensor [V] on the device.
+
+    This class holds the one body of the four similarities: the work is done on banks [F, ...]; a class says what it
+    calls (`entry`), whether it is a bank (else F = 1 and the attributes are the [0] views of the banks, and fixed_of is
+    None everywhere) and whether it has patches."""
+
+    entry, _bank, _patches = 'dfl_sim_gradncc', False, False        # entry: what launch() calls with args()
+
+    def __init__(self, fixed, mask=None, views=1):
+        self._setup(fixed, mask, views)
+
+    def _setup(self, fixed, mask, views, patch=None):
+        """patch = (radius, stride, min_count, weight) as the caller gave them, for the classes with patches."""
+        if self._patches:
+            self.radius, self.stride, self.min_count = _patch_params(*patch[:3])
+            self.weight = _patch_weight(patch[3])
+        dims = 3 if self._bank else 2
+        image, the_mask, verb = ('the fixed images', 'the masks', 'are') if self._bank else ('the fixed image', 'the mask', 'is')
+        fixed = _device_image(fixed, image, dims)
+        dev, shape = fixed.device, tuple(int(s) for s in fixed.shape)
+        H, W = shape[-2:]
+        F = shape[0] if self._bank else 1
+        self.H, self.W, self.views = H, W, int(views)
+        if mask is not None:
+            mask = _device_image(mask, the_mask, dims, (torch.uint8,))
+            if tuple(mask.shape) != shape or mask.device != dev:
+                raise nat.DflError('register: %s %s %s on %s, %s %s on %s' % (the_mask, verb, tuple(mask.shape), mask.device, image, shape, dev))
+        if self._bank:
+            if not 1 <= F <= 65535 or F * H * W >= 2 ** 31:
+                raise nat.DflError('register: a bank of %d images of %d x %d (1..65535 images, fewer than 2^31 pixels)' % (F, H, W))
+            self.F, self._fixed_of = F, {}
         lib = nat.lib()
-        need = int(lib.dfl_sim_patch_eval_scratch_doubles(sim.views, sim.H, sim.W, sim.radius, sim.stride, 1))
-        if need < 0:
-            raise nat.DflError('register: %s' % lib.dfl_last_error().decode())
-        sim.bwd_scratch = torch.empty(need, dtype=torch.float64, device=dev)
-    out = torch.empty(V, dtype=torch.float64, device=dev)
-    d_moving = torch.empty((V, sim.H, sim.W), dtype=torch.float32, device=dev)
-    drr.launch(dev, 'dfl_sim_patch_eval', _patch_eval_args(sim, mv, fixed_of, sim.bwd_scratch, out, d_moving))
-    return out, d_moving
+        self.scratch = _scratch(lib.dfl_sim_scratch_doubles(self.views, H, W), dev, 1)
+        self.out = torch.empty(self.views, dtype=torch.float64, device=dev)
+        self.bwd_scratch = None                                     # cost_and_adjoint sizes it when it first runs
+        self._sizes = dict(H=H, W=W, F=F, reserved=0)
+
+        def bank(dtype, *per_image):
+            return torch.empty((F,) + per_image, dtype=dtype, device=dev)
+
+        self._banks = dict(fixed=fixed.reshape(F, H, W), mask=None if mask is None else mask.reshape(F, H, W),
+                           fx=bank(torch.float32, H, W), fy=bank(torch.float32, H, W), counted=bank(torch.uint8, H, W),
+                           totals=bank(torch.float64, nat.SIM_TOTALS))
+        self._each_image(dev, 'dfl_sim_prepare')
+        if self._patches:
+            P = int(lib.dfl_sim_patch_count(H, W, self.radius, self.stride))
+            if P < 0:
+                raise nat.DflError('register: %s' % lib.dfl_last_error().decode())
+            self.pscratch = _scratch(lib.dfl_sim_patch_scratch_doubles(self.views, H, W, self.radius, self.stride), dev)
+            self.patches = P
+            self._sizes.update(rho=self.radius, stride=self.stride, min_count=self.min_count, P=P)
+            self._banks.update(ptotals=bank(torch.float64, P, nat.SIM_TOTALS), pflags=bank(torch.uint8, P), pcount=bank(torch.int32, 2))
+            self._each_image(dev, 'dfl_sim_patch_prepare')
+            if self.weight == 'variance':
+                self.entry = 'dfl_sim_patch_eval'
+                self._banks.update(pweights=bank(torch.float64, P, 2), pwsum=bank(torch.float64, 2))
+                self._each_image(dev, 'dfl_sim_patch_weights')
+        for name, t in self._banks.items():                         # fixed, mask, fx, fy, counted, totals, ptotals, pflags, ...
+            setattr(self, name, t if self._bank or t is None else t[0])
+        self._fields = dict({name: nat.ptr(t) for name, t in self._banks.items()}, **self._sizes)      # what every launch passes
+
+    def _each_image(self, dev, entry):
+        """One launch of a preparing entry point per image, on that image's slices of the banks."""
+        for f in range(self._sizes['F']):
+            drr.launch(dev, entry, _block(entry, dict({name: None if t is None else t[f].data_ptr() for name, t in self._banks.items()}, **self._sizes)))
+
+    def _args(self, entry, moving, fixed_of, scratch, out, d_moving=None):
+        return _block(entry, dict(self._fields, moving=moving.data_ptr(), fixed_of=nat.ptr(fixed_of), scratch=scratch.data_ptr(), cost=out.data_ptr(),
+                                  d_moving=nat.ptr(d_moving), scratch_doubles=scratch.numel(), V=int(moving.shape[0])))
+
+    def _which(self, fixed_of, V):
+        """fixed_of as the kernels read it: a bank's checked device tensor, None for one image."""
+        return self.fixed_of(fixed_of, V) if self._bank else None
+
+    def _forward(self, moving, fixed_of, out):
+        return self._args(self.entry, moving, fixed_of, self.pscratch if self._patches else self.scratch, self.out if out is None else out)
+
+    def _launch(self, moving, fixed_of=None, out=None):
+        drr.launch(moving.device, self.entry, self._forward(moving, self._which(fixed_of, int(moving.shape[0])), out))
+
+    def args(self, moving, out=None):
+        return self._forward(moving, None, out)
+
+    def _moving(self, moving):
+        mv = _device_image(moving, 'the moving images', 3)
+        if tuple(mv.shape[1:]) != (self.H, self.W) or mv.device != self.out.device or not 1 <= mv.shape[0] <= self.views:
+            raise nat.DflError('register: moving images of shape %s on %s for a fixed image of %d x %d on %s and at most %d views'
+                               % (tuple(mv.shape), mv.device, self.H, self.W, self.out.device, self.views))
+        return mv
+
+    def launch(self, moving, out=None):
+        """One launch of `entry` on checked moving images; the costs go to `out` (default: the first rows of self.out)."""
+        self._launch(moving, None, out)
+
+    def cost(self, moving, fixed_of=None):
+        mv = self._moving(moving)
+        out = torch.empty(mv.shape[0], dtype=torch.float64, device=mv.device)
+        self._launch(mv, fixed_of, out)
+        return out
+
+    def cost_and_adjoint(self, moving, fixed_of=None):
+        """(cost [V] float64, d_moving [V, H, W] float32 = d cost[v] / d moving[v]) on the device: one dfl_sim_gradncc_bwd or
+        dfl_sim_bank_gradncc_bwd launch, with patches one dfl_sim_patch_eval launch (section 21), which
+        weight='variance' alone has.  The cost has the bits cost(moving) gives."""
+        if self._patches and self.weight != 'variance':
+            raise nat.DflError("register: the uniform patch similarity has no adjoint here; weight='variance' has (DESIGN.md section 21)")
+        mv = self._moving(moving)
+        V, dev = int(mv.shape[0]), mv.device
+        fixed_of = self._which(fixed_of, V)
+        if self.bwd_scratch is None:
+            lib = nat.lib()
+            self.bwd_scratch = _scratch(lib.dfl_sim_patch_eval_scratch_doubles(self.views, self.H, self.W, self.radius, self.stride, 1)
+                                        if self._patches else lib.dfl_sim_gradncc_bwd_scratch_doubles(self.views, self.H, self.W), dev)
+        out = torch.empty(V, dtype=torch.float64, device=dev)
+        d_moving = torch.empty((V, self.H, self.W), dtype=torch.float32, device=dev)
+        entry = 'dfl_sim_patch_eval' if self._patches else self.entry + '_bwd'
+        drr.launch(dev, entry, self._args(entry, mv, fixed_of, self.bwd_scratch, out, d_moving))
+        return out, d_moving
 
 
 class PatchSimilarity(Similarity):
@@ -534,64 +584,13 @@ class PatchSimilarity(Similarity):
     runs after the prepare, cost(moving) is one dfl_sim_patch_eval launch and cost_and_adjoint(moving) works.  The default
     'uniform' is the cost of section 18 through the entry point it always used, and has no adjoint here."""
 
+    entry, _patches = 'dfl_sim_patch_gradncc', True
+
     def __init__(self, fixed, mask=None, views=1, radius=7, stride=4, min_count=None, weight='uniform'):
-        self.radius, self.stride, self.min_count = _patch_params(radius, stride, min_count)
-        self.weight = _patch_weight(weight)
-        Similarity.__init__(self, fixed, mask, views)
-        lib = nat.lib()
-        dev, H, W = self.fixed.device, self.H, self.W
-        P = int(lib.dfl_sim_patch_count(H, W, self.radius, self.stride))
-        need = int(lib.dfl_sim_patch_scratch_doubles(self.views, H, W, self.radius, self.stride)) if P >= 0 else -1
-        if P < 0 or need < 0:
-            raise nat.DflError('register: %s' % lib.dfl_last_error().decode())
-        self.patches = P
-        self.ptotals = torch.empty((P, nat.SIM_TOTALS), dtype=torch.float64, device=dev)
-        self.pflags = torch.empty(P, dtype=torch.uint8, device=dev)
-        self.pcount = torch.empty(2, dtype=torch.int32, device=dev)
-        self.pscratch = torch.empty(need, dtype=torch.float64, device=dev)
-        a = nat.SimPatchPrepareArgs(fx=self.fx.data_ptr(), fy=self.fy.data_ptr(), counted=self.counted.data_ptr(),
-                                    ptotals=self.ptotals.data_ptr(), pflags=self.pflags.data_ptr(), pcount=self.pcount.data_ptr(),
-                                    H=H, W=W, rho=self.radius, stride=self.stride, min_count=self.min_count)
-        drr.launch(dev, 'dfl_sim_patch_prepare', a)
-        if self.weight == 'variance':
-            self.entry = 'dfl_sim_patch_eval'
-            self.pweights = torch.empty((P, 2), dtype=torch.float64, device=dev)
-            self.pwsum = torch.empty(2, dtype=torch.float64, device=dev)
-            _patch_weights(dev, self.ptotals, self.pflags, self.pweights, self.pwsum, P)
-
-    entry = 'dfl_sim_patch_gradncc'
-
-    def args(self, moving, out=None):
-        out = self.out if out is None else out
-        if self.weight == 'variance':
-            return _patch_eval_args(self, moving, None, self.pscratch, out, None)
-        return nat.SimPatchGradnccArgs(moving=moving.data_ptr(), fx=self.fx.data_ptr(), fy=self.fy.data_ptr(),
-                                       counted=self.counted.data_ptr(), ptotals=self.ptotals.data_ptr(), pflags=self.pflags.data_ptr(),
-                                       pcount=self.pcount.data_ptr(), scratch=self.pscratch.data_ptr(), cost=out.data_ptr(),
-                                       scratch_doubles=self.pscratch.numel(), V=int(moving.shape[0]), H=self.H, W=self.W,
-                                       rho=self.radius, stride=self.stride)
-
-    def cost_and_adjoint(self, moving):
-        """(cost [V] float64, d_moving [V, H, W] float32) on the device: one dfl_sim_patch_eval launch (DESIGN.md section 21);
-        the cost has the bits cost(moving) gives.  With weight='variance' only."""
-        if self.weight != 'variance':
-            raise nat.DflError("register: the uniform patch similarity has no adjoint here; weight='variance' has (DESIGN.md section 21)")
-        mv = self._moving(moving)
-        return _patch_cost_and_adjoint(self, mv, None)
+        self._setup(fixed, mask, views, (radius, stride, min_count, weight))
 
 
 # ---- the similarity against a bank of fixed images ---------------------------------------------------------------------
-def fixed_of_array(fixed_of, V, F):
-    """A sequence or array that says which of F fixed images each of V views is scored against -> int32 [V], checked on
-    the host: integers, one per view, each in [0, F)."""
-    a = np.asarray(fixed_of)
-    if a.ndim != 1 or a.shape[0] != V or a.dtype.kind not in 'iu':
-        raise nat.DflError('register: fixed_of has shape %s and dtype %s: %d integers expected, one per view' % (a.shape, a.dtype, V))
-    if V and (int(a.min()) < 0 or int(a.max()) >= F):
-        raise nat.DflError('register: fixed_of holds %d .. %d, the bank has the images 0 .. %d' % (int(a.min()), int(a.max()), F - 1))
-    return np.ascontiguousarray(a, np.int32)
-
-
 class SimilarityBank(Similarity):
     """Similarity against F fixed images [F, H, W] (float32, on the GPU) with optional uint8 masks [F, H, W]: dfl_sim_prepare
     runs here, once per image, on that image's slice of the banks.  cost(moving, fixed_of) scores view v against image
@@ -599,89 +598,33 @@ class SimilarityBank(Similarity):
     gives it.  fixed_of is an int32 tensor [V] on the device (not checked: a view whose entry is outside [0, F) costs NaN
     and gets a zero adjoint) or a sequence, which is checked here (fixed_of_array)."""
 
-    def __init__(self, fixed, masks=None, views=1):
-        self.fixed = _device_image(fixed, 'the fixed images', 3)
-        dev = self.fixed.device
-        F, H, W = (int(s) for s in self.fixed.shape)
-        self.F, self.H, self.W, self.views = F, H, W, int(views)
-        self.mask = None
-        if masks is not None:
-            self.mask = _device_image(masks, 'the masks', 3, (torch.uint8,))
-            if tuple(self.mask.shape) != (F, H, W) or self.mask.device != dev:
-                raise nat.DflError('register: the masks are %s on %s, the fixed images %s on %s'
-                                   % (tuple(self.mask.shape), self.mask.device, (F, H, W), dev))
-        if not 1 <= F <= 65535 or F * H * W >= 2 ** 31:
-            raise nat.DflError('register: a bank of %d images of %d x %d (1..65535 images, fewer than 2^31 pixels)' % (F, H, W))
-        lib = nat.lib()
-        need = int(lib.dfl_sim_scratch_doubles(self.views, H, W))
-        if need < 0:
-            raise nat.DflError('register: %s' % lib.dfl_last_error().decode())
-        self.fx = torch.empty((F, H, W), dtype=torch.float32, device=dev)
-        self.fy = torch.empty((F, H, W), dtype=torch.float32, device=dev)
-        self.counted = torch.empty((F, H, W), dtype=torch.uint8, device=dev)
-        self.totals = torch.empty((F, nat.SIM_TOTALS), dtype=torch.float64, device=dev)
-        self.scratch = torch.empty(max(need, 1), dtype=torch.float64, device=dev)
-        self.out = torch.empty(self.views, dtype=torch.float64, device=dev)
-        self._fixed_of = {}
-        for f in range(F):
-            a = nat.SimPrepareArgs(fixed=self.fixed[f].data_ptr(), mask=None if self.mask is None else self.mask[f].data_ptr(),
-                                   fx=self.fx[f].data_ptr(), fy=self.fy[f].data_ptr(), counted=self.counted[f].data_ptr(),
-                                   totals=self.totals[f].data_ptr(), H=H, W=W)
-            drr.launch(dev, 'dfl_sim_prepare', a)
+    entry, _bank = 'dfl_sim_bank_gradncc', True
 
-    entry = 'dfl_sim_bank_gradncc'
+    def __init__(self, fixed, masks=None, views=1):
+        self._setup(fixed, masks, views)
 
     def fixed_of(self, fixed_of, V):
         """The int32 device tensor [V] the kernels read; sequences are checked on the host and uploaded once each."""
+        dev = self.out.device
         if torch.is_tensor(fixed_of):
-            if not fixed_of.is_cuda or fixed_of.dtype != torch.int32 or tuple(fixed_of.shape) != (V,) or fixed_of.device != self.fixed.device:
+            if not fixed_of.is_cuda or fixed_of.dtype != torch.int32 or tuple(fixed_of.shape) != (V,) or fixed_of.device != dev:
                 raise nat.DflError('register: fixed_of is a tensor of shape %s and dtype %s on %s: int32 [%d] on %s expected'
-                                   % (tuple(fixed_of.shape), fixed_of.dtype, fixed_of.device, V, self.fixed.device))
+                                   % (tuple(fixed_of.shape), fixed_of.dtype, fixed_of.device, V, dev))
             return fixed_of.detach().contiguous()
         a = fixed_of_array(fixed_of, V, self.F)
         key = a.tobytes()
         if key not in self._fixed_of:
             if len(self._fixed_of) >= 64:
                 self._fixed_of.clear()
-            self._fixed_of[key] = torch.from_numpy(a).to(self.fixed.device)
+            self._fixed_of[key] = torch.from_numpy(a).to(dev)
         return self._fixed_of[key]
 
     def args(self, moving, fixed_of, out=None):
-        out = self.out if out is None else out
-        return nat.SimBankGradnccArgs(moving=moving.data_ptr(), fx=self.fx.data_ptr(), fy=self.fy.data_ptr(), counted=self.counted.data_ptr(),
-                                      totals=self.totals.data_ptr(), fixed_of=fixed_of.data_ptr(), scratch=self.scratch.data_ptr(),
-                                      cost=out.data_ptr(), scratch_doubles=self.scratch.numel(), V=int(moving.shape[0]), H=self.H, W=self.W,
-                                      F=self.F)
+        return self._forward(moving, fixed_of, out)
 
     def launch(self, moving, fixed_of, out=None):
         """One launch of `entry` on checked moving images; the costs go to `out` (default: the first rows of self.out)."""
-        drr.launch(moving.device, self.entry, self.args(moving, self.fixed_of(fixed_of, int(moving.shape[0])), out))
-
-    def cost(self, moving, fixed_of):
-        mv = self._moving(moving)
-        out = torch.empty(mv.shape[0], dtype=torch.float64, device=mv.device)
-        self.launch(mv, fixed_of, out)
-        return out
-
-    def cost_and_adjoint(self, moving, fixed_of):
-        """(cost [V] float64, d_moving [V, H, W] float32) on the device: one dfl_sim_bank_gradncc_bwd launch."""
-        mv = self._moving(moving)
-        V, dev = int(mv.shape[0]), mv.device
-        of = self.fixed_of(fixed_of, V)
-        if getattr(self, 'bwd_scratch', None) is None:
-            lib = nat.lib()
-            need = int(lib.dfl_sim_gradncc_bwd_scratch_doubles(self.views, self.H, self.W))
-            if need < 0:
-                raise nat.DflError('register: %s' % lib.dfl_last_error().decode())
-            self.bwd_scratch = torch.empty(need, dtype=torch.float64, device=dev)
-        out = torch.empty(V, dtype=torch.float64, device=dev)
-        d_moving = torch.empty((V, self.H, self.W), dtype=torch.float32, device=dev)
-        a = nat.SimBankGradnccBwdArgs(moving=mv.data_ptr(), fx=self.fx.data_ptr(), fy=self.fy.data_ptr(), counted=self.counted.data_ptr(),
-                                      totals=self.totals.data_ptr(), fixed_of=of.data_ptr(), scratch=self.bwd_scratch.data_ptr(),
-                                      cost=out.data_ptr(), d_moving=d_moving.data_ptr(), scratch_doubles=self.bwd_scratch.numel(), V=V,
-                                      H=self.H, W=self.W, F=self.F)
-        drr.launch(dev, 'dfl_sim_bank_gradncc_bwd', a)
-        return out, d_moving
+        self._launch(moving, fixed_of, out)
 
 
 class PatchSimilarityBank(SimilarityBank):
@@ -689,52 +632,10 @@ class PatchSimilarityBank(SimilarityBank):
     image on its slice of the patch banks; cost(moving, fixed_of) is one dfl_sim_patch_bank_gradncc launch.  weight='variance'
     is PatchSimilarity's: dfl_sim_patch_weights per image, dfl_sim_patch_eval for the cost, and cost_and_adjoint works."""
 
+    entry, _patches = 'dfl_sim_patch_bank_gradncc', True
+
     def __init__(self, fixed, masks=None, views=1, radius=7, stride=4, min_count=None, weight='uniform'):
-        self.radius, self.stride, self.min_count = _patch_params(radius, stride, min_count)
-        self.weight = _patch_weight(weight)
-        SimilarityBank.__init__(self, fixed, masks, views)
-        lib = nat.lib()
-        dev, F, H, W = self.fixed.device, self.F, self.H, self.W
-        P = int(lib.dfl_sim_patch_count(H, W, self.radius, self.stride))
-        need = int(lib.dfl_sim_patch_scratch_doubles(self.views, H, W, self.radius, self.stride)) if P >= 0 else -1
-        if P < 0 or need < 0:
-            raise nat.DflError('register: %s' % lib.dfl_last_error().decode())
-        self.patches = P
-        self.ptotals = torch.empty((F, P, nat.SIM_TOTALS), dtype=torch.float64, device=dev)
-        self.pflags = torch.empty((F, P), dtype=torch.uint8, device=dev)
-        self.pcount = torch.empty((F, 2), dtype=torch.int32, device=dev)
-        self.pscratch = torch.empty(need, dtype=torch.float64, device=dev)
-        for f in range(F):
-            a = nat.SimPatchPrepareArgs(fx=self.fx[f].data_ptr(), fy=self.fy[f].data_ptr(), counted=self.counted[f].data_ptr(),
-                                        ptotals=self.ptotals[f].data_ptr(), pflags=self.pflags[f].data_ptr(),
-                                        pcount=self.pcount[f].data_ptr(), H=H, W=W, rho=self.radius, stride=self.stride,
-                                        min_count=self.min_count)
-            drr.launch(dev, 'dfl_sim_patch_prepare', a)
-        if self.weight == 'variance':
-            self.entry = 'dfl_sim_patch_eval'
-            self.pweights = torch.empty((F, P, 2), dtype=torch.float64, device=dev)
-            self.pwsum = torch.empty((F, 2), dtype=torch.float64, device=dev)
-            for f in range(F):
-                _patch_weights(dev, self.ptotals[f], self.pflags[f], self.pweights[f], self.pwsum[f], P)
-
-    entry = 'dfl_sim_patch_bank_gradncc'
-
-    def args(self, moving, fixed_of, out=None):
-        out = self.out if out is None else out
-        if self.weight == 'variance':
-            return _patch_eval_args(self, moving, fixed_of, self.pscratch, out, None)
-        return nat.SimPatchBankGradnccArgs(moving=moving.data_ptr(), fx=self.fx.data_ptr(), fy=self.fy.data_ptr(),
-                                           counted=self.counted.data_ptr(), ptotals=self.ptotals.data_ptr(), pflags=self.pflags.data_ptr(),
-                                           pcount=self.pcount.data_ptr(), fixed_of=fixed_of.data_ptr(), scratch=self.pscratch.data_ptr(),
-                                           cost=out.data_ptr(), scratch_doubles=self.pscratch.numel(), V=int(moving.shape[0]), H=self.H,
-                                           W=self.W, rho=self.radius, stride=self.stride, F=self.F)
-
-    def cost_and_adjoint(self, moving, fixed_of):
-        """(cost [V] float64, d_moving [V, H, W] float32) on the device: one dfl_sim_patch_eval launch.  With weight='variance' only."""
-        if self.weight != 'variance':
-            raise nat.DflError("register: the uniform patch similarity has no adjoint here; weight='variance' has (DESIGN.md section 21)")
-        mv = self._moving(moving)
-        return _patch_cost_and_adjoint(self, mv, self.fixed_of(fixed_of, int(mv.shape[0])))
+        self._setup(fixed, masks, views, (radius, stride, min_count, weight))
 
 
 # ---- the landmark term -------------------------------------------------------------------------------------------------
@@ -803,19 +704,20 @@ class _Level:
         drr.launch(att.device, 'dfl_drr_render', a)
         return recs, att, keep
 
-    def costs(self, c2is, masks, *fixed_of):
+    def costs(self, c2is, masks, fixed_of=None):
         """[views <= lambda, n_obj, 4, 4] (and, with a bank, fixed_of [views]) -> float64 [views] on the host: one render, one
         similarity launch, one copy."""
         recs, att, keep = self._render(c2is, masks)
-        self.sim.launch(att, *fixed_of)
+        self.sim._launch(att, fixed_of)
         return self.sim.out[:recs.shape[0]].cpu().numpy()           # the copy waits for both launches: `keep` lives until then
 
-    def costs_and_grads(self, c2is, masks, xis, moving):
+    def costs_and_grads(self, c2is, masks, xis, moving, fixed_of=None):
         """[views <= lambda, n_obj, 4, 4], xis [views, 6, 4, 4] (the motion of the moving objects in index coordinates per
-        unit of every parameter) -> (float64 [views], float64 [views, 6]) on the host: one render, one dfl_sim_gradncc_bwd,
-        one dfl_drr_pose_grad, one copy; the chain from forces and moments to the parameters is float64 numpy."""
+        unit of every parameter; with a bank, fixed_of [views]) -> (float64 [views], float64 [views, 6]) on the host: one render,
+        one adjoint of the similarity (cost_and_adjoint), one dfl_drr_pose_grad, one copy; the chain from forces and moments to
+        the parameters is float64 numpy."""
         recs, att, keep = self._render(c2is, masks)
-        both, piv = self._cost_and_moments(recs, att, *self.sim.cost_and_adjoint(att))
+        both, piv = self._cost_and_moments(recs, att, *self.sim.cost_and_adjoint(att, fixed_of))
         del keep
         return _theta_chain(both, piv, xis, moving)
 
@@ -868,6 +770,15 @@ def _landmarks_of(landmarks, moving):
     except (TypeError, ValueError):
         raise nat.DflError('register: landmarks = (X3d [L, 3], x2d [2, L]) expected') from None
     return _usable_landmarks(X3d, x2d, 'register: landmarks')
+
+
+def _on_the_gpu(who, volume, tensors):
+    """The refusals of host data by register() and register_many(): `tensors` maps what a tensor is called to the tensor."""
+    if not isinstance(volume, drr.Volume):
+        raise nat.DflError('%s needs a drr.Volume (device tensors; no CPU path)' % who)
+    for what, t in tensors.items():
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise nat.DflError('%s needs %s on the GPU (no CPU path)' % (who, what))
 
 
 def _moving_and_population(geom, moving, popsize):
@@ -939,6 +850,59 @@ class _Problem:
                             theta_cma=theta_cma, refine_cost=refine_cost, gradient_evaluations=gradient_evaluations)
 
 
+# ---- the driver: register() is these on one problem and one fixed image, register_many() on n problems and a bank --------------
+def _views(level, probs, idx, thetas):
+    """What _Level.costs and costs_and_grads get for the points thetas[k] [views_k, 6] of the problems idx[k] of `probs`: the
+    C2I matrices of all of them, the object masks, and which fixed image each view is scored against (None without a bank)."""
+    fixed_of = np.repeat(np.asarray(idx, np.int32), [len(th) for th in thetas]) if level.sim._bank else None
+    return np.concatenate([probs[i].c2is_of(th) for i, th in zip(idx, thetas)]), probs[0].masks, fixed_of
+
+
+def _search(level, probs, starts, sigma, lam, generations, seed):
+    """The CMA-ES of every problem from its start, in lockstep: [CmaResult].  A generation is one render of lam views per
+    problem, one similarity launch and one copy."""
+    def generation(idx, thetas):
+        c = level.costs(*_views(level, probs, idx, thetas))
+        return [probs[i].with_penalty(c[k * lam:(k + 1) * lam], th) for k, (i, th) in enumerate(zip(idx, thetas))]
+
+    return lockstep([cma_steps(start, sigma, lam, generations, seed) for start in starts], generation)
+
+
+def _finish(level, probs, means, refine, refine_tol):
+    """bfgs from every problem's mean, in lockstep: [BfgsResult], or [None] * n with refine = 0.  A round is one render of one
+    view per problem still running, one adjoint of the similarity, one dfl_drr_pose_grad and one copy."""
+    if refine <= 0:
+        return [None] * len(probs)
+
+    def round_of_the_finish(idx, thetas):
+        ths = [t[None] for t in thetas]
+        xis = np.concatenate([probs[i].xis_of(th) for i, th in zip(idx, ths)])
+        c2is, masks, fixed_of = _views(level, probs, idx, ths)
+        c, g = level.costs_and_grads(c2is, masks, xis, list(probs[0].moving), fixed_of)
+        return [probs[i].cost_and_grad(c[k:k + 1], g[k:k + 1], th) for k, (i, th) in enumerate(zip(idx, ths))]
+
+    return lockstep([bfgs_steps(mean, refine, refine_tol) for mean in means], round_of_the_finish)
+
+
+def _final_costs(level, probs, ends):
+    """The similarity cost of every problem at its end point: one render, one similarity launch, one copy."""
+    return level.costs(*_views(level, probs, list(range(len(probs))), [end[None] for end in ends]))
+
+
+def _close(level, probs, means, refine, refine_tol, traces, renders, done):
+    """The finish from the means of the search and the final costs, on `level`: every problem's Registration.  traces and
+    renders are each problem's best costs and rendered views of the search, `done` the levels it ran."""
+    fins = _finish(level, probs, means, refine, refine_tol)
+    ends = [mean if fin is None else fin.x for mean, fin in zip(means, fins)]
+    last = _final_costs(level, probs, ends)
+    out = []
+    for i, (prob, fin) in enumerate(zip(probs, fins)):
+        evals = 0 if fin is None else fin.evaluations
+        out.append(prob.result(ends[i], float(last[i]), traces[i], renders[i] + evals + 1, done, means[i],
+                               np.zeros(0) if fin is None else fin.trace, evals))
+    return out
+
+
 def register(volume, geom, fixed, moving=(0, 1, 2), theta0=None, P0=None, levels=None, popsize=16, generations=80, sigma0=2.0,
              step_mm=1.0, mask=None, seed=0, centre=None, rot_unit=ROT_UNIT, crop=0, rot180=False, sigma_shrink=0.5,
              similarity='global', patch_radius=7, patch_stride=4, patch_min_count=None, landmarks=None, landmark_weight=0.0,
@@ -975,14 +939,10 @@ def register(volume, geom, fixed, moving=(0, 1, 2), theta0=None, P0=None, levels
     if landmarks is not None and levels is not None:
         raise nat.DflError('register: landmarks belong to one grid; they are not supported together with levels')
     lands = _landmarks_of(landmarks, moving)
-    if not isinstance(volume, drr.Volume):
-        raise nat.DflError('register needs a drr.Volume (device tensors; no CPU path)')
-    if not torch.is_tensor(fixed) or not fixed.is_cuda:
-        raise nat.DflError('register needs the fixed image on the GPU (no CPU path)')
+    _on_the_gpu('register', volume, {'the fixed image': fixed})
     moving, lam = _moving_and_population(geom, moving, popsize)
     theta0 = np.zeros(6) if theta0 is None else np.asarray(theta0, np.float64).reshape(6)
     prob = _Problem(volume.shape, geom, moving, P0, centre, rot_unit, lands, landmark_weight)
-    masks = prob.masks
 
     if levels is None:
         plan = [(None, int(generations), geom.grid, _device_image(fixed, 'the fixed image', 2))]
@@ -1005,22 +965,12 @@ def register(volume, geom, fixed, moving=(0, 1, 2), theta0=None, P0=None, levels
     mean, sigma, trace, renders, done = theta0, float(sigma0), [], 0, []
     for k, (factor, gens, grid, img) in enumerate(plan):
         level = _Level(volume, grid, img, mask, lam, step_mm, patch)
-        res = cma_es(lambda th: prob.with_penalty(level.costs(prob.c2is_of(th), masks), th), mean, sigma, lam, gens, seed + k)
+        res = _search(level, [prob], [mean], sigma, lam, gens, seed + k)[0]
         mean, sigma = res.mean, sigma * float(sigma_shrink)
         trace.extend(res.trace.tolist())
         renders += res.evaluations
         done.append((factor, gens, grid.H, grid.W))
-    theta_cma, refine_cost, gradient_evaluations = mean, np.zeros(0), 0
-    if refine > 0:
-        def cost_and_grad(theta):
-            th = theta[None]
-            return prob.cost_and_grad(*level.costs_and_grads(prob.c2is_of(th), masks, prob.xis_of(th), list(moving)), th)
-
-        fin = bfgs(cost_and_grad, mean, int(refine), float(refine_tol))
-        mean, refine_cost, gradient_evaluations = fin.x, fin.trace, fin.evaluations
-        renders += fin.evaluations
-    similarity_cost = float(level.costs(prob.c2is_of(mean[None]), masks)[0])
-    return prob.result(mean, similarity_cost, trace, renders + 1, done, theta_cma, refine_cost, gradient_evaluations)
+    return _close(level, [prob], [mean], int(refine), float(refine_tol), [trace], [renders], done)[0]
 
 
 def _same(a, b):
@@ -1078,8 +1028,9 @@ def register_many(volume, geoms, fixed, moving=(0, 1, 2), theta0=None, P0=None, 
 
     theta0s, P0s = per_problem('theta0', theta0, (6,)), per_problem('P0', P0, (4, 4))
     lands = [_landmarks_of(l, moving) for l in per_problem('landmarks', landmarks, None)]
-    for what, t in (('fixed', fixed), ('masks', masks)):
-        if t is not None and (not hasattr(t, 'shape') or len(t.shape) != 3 or int(t.shape[0]) != N):
+    images = {what: t for what, t in (('fixed', fixed), ('masks', masks)) if t is not None}
+    for what, t in images.items():
+        if not hasattr(t, 'shape') or len(t.shape) != 3 or int(t.shape[0]) != N:
             raise nat.DflError('register_many: %s is [N, H, W] with N = %d problems, got %s' % (what, N, tuple(getattr(t, 'shape', ()))))
     g0 = geoms[0]
     for i, g in enumerate(geoms):
@@ -1094,11 +1045,7 @@ def register_many(volume, geoms, fixed, moving=(0, 1, 2), theta0=None, P0=None, 
     cap = default_max_views(H, W) if max_views is None else max_views
     if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or cap < lam or cap > 65535:
         raise nat.DflError('register_many: max_views = %r (an integer from popsize = %d to 65535)' % (max_views, lam))
-    if not isinstance(volume, drr.Volume):
-        raise nat.DflError('register_many needs a drr.Volume (device tensors; no CPU path)')
-    for what, t in (('fixed', fixed), ('masks', masks)):
-        if t is not None and (not torch.is_tensor(t) or not t.is_cuda):
-            raise nat.DflError('register_many needs %s on the GPU (no CPU path)' % what)
+    _on_the_gpu('register_many', volume, images)
     fixed = _device_image(fixed, 'the fixed images', 3)
     if tuple(fixed.shape[1:]) != (H, W):
         raise nat.DflError('register: the fixed image is %s, the output grid %d x %d' % (tuple(fixed.shape[1:]), H, W))
@@ -1114,35 +1061,7 @@ def register_many(volume, geoms, fixed, moving=(0, 1, 2), theta0=None, P0=None, 
 
 def _register_chunk(volume, grid, probs, starts, fixed, masks, lam, generations, sigma0, step_mm, seed, patch, refine, refine_tol):
     """register_many for problems whose lambda candidates fit into one render together."""
-    n, moving, obj_masks = len(probs), list(probs[0].moving), probs[0].masks
-    level = _Level(volume, grid, None, None, n * lam, step_mm, patch, bank=(fixed, masks))
-
-    def similarity_costs(idx, c2is):
-        """One render of the views c2is (a list of [views_i, n_obj, 4, 4], one per problem of idx) and one bank launch."""
-        fixed_of = np.repeat(np.asarray(idx, np.int32), [c.shape[0] for c in c2is])
-        return level.costs(np.concatenate(c2is), obj_masks, fixed_of)
-
-    def generation(idx, thetas):
-        c = similarity_costs(idx, [probs[i].c2is_of(th) for i, th in zip(idx, thetas)])
-        return [probs[i].with_penalty(c[k * lam:(k + 1) * lam], th) for k, (i, th) in enumerate(zip(idx, thetas))]
-
-    cma = lockstep([cma_steps(starts[i], sigma0, lam, generations, seed) for i in range(n)], generation)
-    means, fins = [r.mean for r in cma], [None] * n
-    if refine > 0:
-        def round_of_the_finish(idx, thetas):
-            ths = [t[None] for t in thetas]
-            recs, att, keep = level._render(np.concatenate([probs[i].c2is_of(th) for i, th in zip(idx, ths)]), obj_masks)
-            both, piv = level._cost_and_moments(recs, att, *level.sim.cost_and_adjoint(att, np.asarray(idx, np.int32)))
-            del keep
-            return [probs[i].cost_and_grad(*_theta_chain(both[k:k + 1], piv[k:k + 1], probs[i].xis_of(th), moving), th)
-                    for k, (i, th) in enumerate(zip(idx, ths))]
-
-        fins = lockstep([bfgs_steps(means[i], refine, refine_tol) for i in range(n)], round_of_the_finish)
-    ends = [means[i] if fins[i] is None else fins[i].x for i in range(n)]
-    last = similarity_costs(list(range(n)), [probs[i].c2is_of(ends[i][None]) for i in range(n)])
-    out = []
-    for i in range(n):
-        evals = 0 if fins[i] is None else fins[i].evaluations
-        out.append(probs[i].result(ends[i], float(last[i]), cma[i].trace.tolist(), cma[i].evaluations + evals + 1,
-                                   [(None, generations, grid.H, grid.W)], means[i], np.zeros(0) if fins[i] is None else fins[i].trace, evals))
-    return out
+    level = _Level(volume, grid, None, None, len(probs) * lam, step_mm, patch, bank=(fixed, masks))
+    cma = _search(level, probs, starts, sigma0, lam, generations, seed)
+    return _close(level, probs, [r.mean for r in cma], refine, refine_tol, [r.trace.tolist() for r in cma], [r.evaluations for r in cma],
+                  [(None, generations, grid.H, grid.W)])

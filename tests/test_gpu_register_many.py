@@ -287,6 +287,20 @@ def test_register_many_with_masks_and_start_poses():
         _same_bytes(got[i], one, ('masks', i))
 
 
+@pytest.mark.parametrize('kw', [dict(similarity='global'), dict(similarity='patch', patch_weight='variance')], ids=['global', 'wpatch'])
+def test_register_many_of_one_problem_has_the_bytes_of_register(kw):
+    """register() and register_many() share one driver; N = 1 holds the bank entry points (F = 1, fixed_of = [0, ...]) against
+    the single-image ones at the smallest problem count, search and finish."""
+    vol, geoms, fixed, theta0, _ = _problems()
+    kw = dict(kw, popsize=16, generations=6, refine=2)
+    got = reg.register_many(vol, geoms[2:], fixed[2:], theta0=theta0[2:], **kw)
+    one = reg.register(vol, geoms[2], fixed[2], theta0=theta0[2], **kw)
+    assert len(got) == 1 and one.gradient_evaluations >= 1
+    for name in FIELDS:
+        a, b = getattr(got[0], name), getattr(one, name)
+        assert np.array_equal(a, b) if isinstance(a, np.ndarray) else a == b, (name, a, b)
+
+
 # ---- 7. the example, end to end ----------------------------------------------------------------------------------------
 SPEC, CROP = '17-1882', 2
 
