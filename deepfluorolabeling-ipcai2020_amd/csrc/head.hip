@@ -519,8 +519,7 @@ static int launch_bwd(const dfl_head_bwd_args* a, dfl_stream_t stream) {
       hipLaunchKernelGGL(head_mfma_bwd_kernel<false>, dim3(grid), dim3(256), HEAD_WG_LDS, hs, *a);
     rc = check_launch("dfl_head_bwd");
   } else {
-    if constexpr (C::SMALL)
-      DFL_REQUIRE(a->stat_totals == nullptr, "dfl_head_bwd: live statistics (stat_totals) are taken by the matrix-core kernels only");
+    DFL_REQUIRE(a->stat_totals == nullptr, "dfl_head_bwd: live statistics (stat_totals) are taken by the matrix-core kernels only");
     if (!fused)
       head_with_shape<C>(a->NC, a->NM, a->L, a->w_l2, [&](auto shape) { rc = launch_bwd_pixel<decltype(shape), false>(a, grid, lds, hs); });
     else if constexpr (C::SMALL)      // a single landmark 1x1, or a w_seg that is not 16-byte aligned

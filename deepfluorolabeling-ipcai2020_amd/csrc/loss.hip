@@ -114,8 +114,15 @@ __global__ void __launch_bounds__(256) loss_finalize_kernel(const dfl_loss_args 
   const double* npart = part + (int64_t)BC * LOSS_NS * 3;       // [BL][LOSS_NS][5]
   double* dcoef = a.sums + (int64_t)BC * 3 + (int64_t)BL * 5;  // [BC][2]
   double* ncoef = dcoef + (int64_t)BC * 2;                      // [BL][3]
+  double* naux = a.sums + (int64_t)BC * 3;                      // [BL][5]: plane means mx, my and the size of a correction worth making
   const int ceff = a.C - (a.skip_bg ? 1 : 0);
   double dice_acc = 0.0, ncc_acc = 0.0;
+  // The gradient kernel reads every coefficient, whatever the weights are: a term with weight zero leaves explicit zeros
+  // (not 0 * E, which is NaN on a constant plane), so its gradient is exact zeros as the reference's is.
+  if (a.dice_wgt == 0.f)
+    for (int i = threadIdx.x; i < BC * 2; i += 256) dcoef[i] = 0.0;
+  if (a.heat_wgt == 0.f)
+    for (int i = threadIdx.x; i < BL * 3; i += 256) ncoef[i] = naux[(i / 3) * 5 + i % 3] = 0.0;
   if (a.dice_wgt != 0.f && a.C > 0) {
     const double g = (double)a.dice_wgt / ((double)a.B * (double)ceff);
     for (int i = threadIdx.x; i < BC; i += 256) {
@@ -156,11 +163,15 @@ __global__ void __launch_bounds__(256) loss_finalize_kernel(const dfl_loss_args 
       const double ncc = cxy / D;
       if (a.ncc_vals != nullptr) a.ncc_vals[i] = (float)ncc;
       ncc_acc += -(ncc + 1.0) * 0.5;
+      if (a.heat_wgt == 0.f) continue;            // (ncc_vals only: the zeros above stand)
       const double E = cxy * N * sdy / (D * D * (N - 1.0) * sdx);
       const double k1 = q / D, k2 = -q * E;
       ncoef[i * 3 + 0] = k1;
       ncoef[i * 3 + 1] = k2;
       ncoef[i * 3 + 2] = -k1 * my - k2 * mx;
+      naux[i * 5 + 0] = mx;
+      naux[i * 5 + 1] = my;
+      naux[i * 5 + 2] = 0x1p-21 * (fabs(k2) * sdx + fabs(k1) * sdy);
     }
   }
   red[0][threadIdx.x] = dice_acc;
@@ -185,10 +196,23 @@ __global__ void __launch_bounds__(256) loss_finalize_kernel(const dfl_loss_args 
 // row ranges, a wave per row, a lane per 4 pixels (float4 when the windows are 16-byte aligned) -- no index division per
 // element.  dseg = gs * (a1 * t + a2 * s), dheat = gs * (k1 * y + k2 * x + k0) with the per-plane coefficients of the
 // finalize kernel and gs = the incoming gradient of the loss.
+// The gradient of the NCC is k1 (y - my) + k2 (x - mx): with the coefficients rounded to fp32, k2 x + k0 keeps an error of
+// 2^-24 |k2 mx| on every pixel of the plane -- 3e-5 of the largest gradient for a heat map of mean 10 and deviation 0.01 (fp32
+// autograd of the reference: 4e-7, its mean subtraction takes a constant off).  e0 = -(c2 my + c1 mx + c0), taken in fp64 from
+// the rounded coefficients, is what the fp32 form returns at the plane means instead of zero; it is added back where it exceeds
+// 2^-21 of the gradient's scale |k2| sd(x) + |k1| sd(y), i.e. on planes whose mean is several deviations from zero.  Every
+// other plane (the heat maps a network produces, their Gaussian targets) keeps the two fmas and their bits.
+__device__ __forceinline__ float loss_grad_elem(float c2, float q, float c1, float p, float c0, float e0) {
+  float r = fmaf(c1, p, c0);
+  if (e0 != 0.f) r += e0;
+  return fmaf(c2, q, r);
+}
+
 __global__ void __launch_bounds__(256) loss_grad_kernel(const dfl_loss_args a) {
   const int BC = a.B * a.C, BL = a.B * a.L;
   const double* dcoef = a.sums + (int64_t)BC * 3 + (int64_t)BL * 5;
   const double* ncoef = dcoef + (int64_t)BC * 2;
+  const double* naux = a.sums + (int64_t)BC * 3;
   const float gs = a.grad_scale != nullptr ? *a.grad_scale : 1.f;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int rows = (a.h + LOSS_NS - 1) / LOSS_NS;
@@ -197,7 +221,7 @@ __global__ void __launch_bounds__(256) loss_grad_kernel(const dfl_loss_args a) {
   const float *p, *q;
   float* o;
   int64_t pH, qH, oH;
-  float c1, c2, c0;
+  float c1, c2, c0, e0 = 0.f;
   if (dice) {
     if (a.dseg == nullptr) return;
     const int pc = blockIdx.x, n = pc / a.C, c = pc % a.C;
@@ -222,6 +246,9 @@ __global__ void __launch_bounds__(256) loss_grad_kernel(const dfl_loss_args a) {
     c1 = gs * (float)ncoef[pc * 3 + 1];       // * x
     c2 = gs * (float)ncoef[pc * 3 + 0];       // * y
     c0 = gs * (float)ncoef[pc * 3 + 2];
+    const double* ax = naux + pc * 5;
+    const double e = -((double)c2 * ax[1] + (double)c1 * ax[0] + (double)c0);
+    if (fabs(e) > fabs((double)gs) * ax[2]) e0 = (float)e;
   }
   const bool vec = (a.w & 3) == 0 && (pH & 3) == 0 && (qH & 3) == 0 && (oH & 3) == 0 &&
                    ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(o)) & 15) == 0;
@@ -232,10 +259,10 @@ __global__ void __launch_bounds__(256) loss_grad_kernel(const dfl_loss_args a) {
       float* orow = o + y * oH + x;
       if (vec) {
         const float4 pv = *reinterpret_cast<const float4*>(pr), qv = *reinterpret_cast<const float4*>(qr);
-        *reinterpret_cast<float4*>(orow) = make_float4(fmaf(c2, qv.x, fmaf(c1, pv.x, c0)), fmaf(c2, qv.y, fmaf(c1, pv.y, c0)),
-                                                       fmaf(c2, qv.z, fmaf(c1, pv.z, c0)), fmaf(c2, qv.w, fmaf(c1, pv.w, c0)));
+        *reinterpret_cast<float4*>(orow) = make_float4(loss_grad_elem(c2, qv.x, c1, pv.x, c0, e0), loss_grad_elem(c2, qv.y, c1, pv.y, c0, e0),
+                                                       loss_grad_elem(c2, qv.z, c1, pv.z, c0, e0), loss_grad_elem(c2, qv.w, c1, pv.w, c0, e0));
       } else {
-        for (int e = 0; e < 4 && x + e < a.w; ++e) orow[e] = fmaf(c2, qr[e], fmaf(c1, pr[e], c0));
+        for (int k = 0; k < 4 && x + k < a.w; ++k) orow[k] = loss_grad_elem(c2, qr[k], c1, pr[k], c0, e0);
       }
     }
   }

@@ -670,10 +670,37 @@ def test_head_fused_weight_gradients_with_misaligned_w_seg(NC, L, two, softmax):
     _head_fused_case(NC, L, two, softmax, w_seg_offset=1)
 
 
-def _head_fused_case(NC, L, two, softmax, w_seg_offset=0):
+@pytest.mark.parametrize('NC,L,two,softmax,w_seg_offset', [(7, 14, True, 1, 0), (7, 0, True, 1, 0), (7, 14, True, 1, 1)])
+def test_head_fused_kernels_walk_a_second_tile(NC, L, two, softmax, w_seg_offset):
+    """2 x 257 x 257 = 132 098 pixels, the smallest size at which both caps of 512 workgroups (1033 tiles of 128 pixels in the
+    matrix-core kernels, 517 tiles of 256 in the thread-per-pixel one) make a workgroup walk a second tile, the last tile
+    ragged: the loop the training shape (16 x 192 x 192) runs.  Same bars as the one-tile cases."""
+    _head_fused_case(NC, L, two, softmax, w_seg_offset=w_seg_offset, N=2, H=257, W=257)
+
+
+@pytest.mark.parametrize('live', ['zero', 'preload'])
+@pytest.mark.parametrize('N,H,W', [(3, 37, 29), (2, 257, 257)])
+@pytest.mark.parametrize('NC,L', [(7, 14), (7, 0)])
+def test_head_backward_live_statistics(NC, L, N, H, W, live):
+    """dfl_head_bwd_args.stat_totals (the matrix-core kernels): the workgroups add (sum dx, sum dx * r) of the values they store
+    to [DFL_BN_R][2][32] doubles -- from zeros and on top of known values -- with the bars of test_convn_live_totals; dx has
+    pixel stride 40 here, and its padding columns stay untouched."""
+    _head_fused_case(NC, L, True, 1, N=N, H=H, W=W, lddx=40, live=live)
+
+
+def test_head_backward_live_statistics_are_refused_by_the_thread_per_pixel_kernel():
+    """A w_seg the matrix-core kernels refuse, with stat_totals set: an error, not silently dropped statistics."""
+    with pytest.raises(nat.DflError, match='stat_totals'):
+        _head_fused_case(7, 14, True, 1, w_seg_offset=1, lddx=40, live='zero')
+
+
+def _head_fused_case(NC, L, two, softmax, w_seg_offset=0, N=3, H=37, W=29, lddx=32, live=None):
+    """N x H x W pixels (default 3219: ragged last tile, images that straddle tiles).  lddx: pixel stride of dx, whose padding
+    columns must keep their NaN fill.  live = 'zero' / 'preload': the matrix-core kernel's live statistics (stat_totals, with a
+    bf16 partner tensor of pixel stride 40) added to totals that start as zeros / as known values."""
     lib = nat.lib()
     g = torch.Generator().manual_seed(NC + L + 1)
-    N, H, W, F_ = 3, 37, 29, 32                                     # 3219 pixels: ragged last tile, images that straddle tiles
+    F_ = 32
     x = rb(torch.randn(N, F_, H, W, generator=g)).double().requires_grad_(True)
     wseg = (torch.randn(NC, F_, 1, 1, generator=g, dtype=torch.float64) / 3).float().double().requires_grad_(True)
     NM = (NC + L if two else L) if L > 0 else 0
@@ -716,16 +743,34 @@ def _head_fused_case(NC, L, two, softmax, w_seg_offset=0):
     M = N * H * W
     nb = nat.check(lib.dfl_head_wgrad_blocks(M), 'blocks')
     part = torch.full((nb * 4096,), float('nan'), device=DEV)
-    dxd = torch.full((N, H, W, F_), float('nan'), device=DEV, dtype=BF)
+    dxd = torch.full((N, H, W, lddx), float('nan'), device=DEV, dtype=BF)
+    live_kw, so, tot, pre = {}, None, None, None
+    if live is not None:
+        so = F.pad(rb(torch.randn(M, F_, generator=g)), (0, 8), value=float('nan')).to(DEV).to(BF).contiguous()      # [M][40]
+        pre = torch.zeros(nat.BN_R, 2, F_, dtype=torch.float64)
+        if live == 'preload':
+            pre = torch.randint(-9, 10, pre.shape, generator=g).double() * 0.25
+        tot = pre.to(DEV)
+        live_kw = dict(stat_other=so.data_ptr(), ldso=F_ + 8, stat_totals=tot.data_ptr())
     dws = torch.full((NC, F_), float('nan'), device=DEV)
     dw1 = torch.full((NM, F_ + NC), float('nan'), device=DEV) if L > 0 else None
     dw2 = torch.full((L, NM), float('nan'), device=DEV) if (L > 0 and two) else None
     nat.call('dfl_head_bwd', nat.HeadBwdArgs(
         x=xd.data_ptr(), seg=segd.data_ptr(), dseg=dsegd.data_ptr(), dheat=nat.ptr(dheatd), w_seg=wsd.data_ptr(),
-        w_l1=nat.ptr(w1d), w_l2=nat.ptr(w2d), dx=dxd.data_ptr(), N=N, H=H, W=W, F=F_, ldx=F_ + 8, lddx=F_, NC=NC, NM=NM, L=L,
-        softmax=softmax, x_bf16=1, dw_seg=dws.data_ptr(), dw_l1=nat.ptr(dw1), dw_l2=nat.ptr(dw2), wg_partial=part.data_ptr()), stream())
+        w_l1=nat.ptr(w1d), w_l2=nat.ptr(w2d), dx=dxd.data_ptr(), N=N, H=H, W=W, F=F_, ldx=F_ + 8, lddx=lddx, NC=NC, NM=NM, L=L,
+        softmax=softmax, x_bf16=1, dw_seg=dws.data_ptr(), dw_l1=nat.ptr(dw1), dw_l2=nat.ptr(dw2), wg_partial=part.data_ptr(),
+        **live_kw), stream())
     torch.cuda.synchronize()
-    close_bf16(dxd.float().cpu(), nhwc(x.grad), 'dx')
+    dxc = dxd.float().cpu()
+    assert bool(torch.isnan(dxc[..., F_:]).all()), 'the padding columns of dx were written'
+    dxc = dxc[..., :F_]
+    close_bf16(dxc, nhwc(x.grad), 'dx')
+    if live is not None:
+        # the kernel ADDS (sum dx, sum dx * r) of the bf16 values it stored to the totals' rows: taken here from those values in fp64
+        dxs, r = dxc.double().reshape(M, F_), so.float().cpu().double()[:, :F_]
+        got = (tot.cpu() - pre).sum(0)
+        np.testing.assert_allclose(got[0].numpy(), dxs.sum(0).numpy(), rtol=2e-5, atol=2e-5 * float(dxs.abs().sum(0).max()))
+        np.testing.assert_allclose(got[1].numpy(), (dxs * r).sum(0).numpy(), rtol=2e-5, atol=2e-5 * float((dxs * r).abs().sum(0).max()))
     for got, ref, name in ((dws, wseg.grad, 'seg_conv'), (dw1, None if w1 is None else w1.grad, 'lands_1x1.0'),
                            (dw2, None if w2 is None else w2.grad, 'lands_1x1.1')):
         if got is None:

@@ -554,11 +554,19 @@ def test_affine_copy_window():
         assert float(yd.cpu()[..., :C_].abs().max()) == 0.0
 
 
-@pytest.mark.parametrize('NC,L,two,softmax,F_', [(7, 14, True, True, 32), (3, 14, False, True, 8), (5, 0, True, False, 8),
-                                                 (7, 14, True, True, 4),
-                                                 # beyond 8 classes / 16 landmarks / 24 mid channels: the large-capacity build of the kernels
-                                                 (12, 20, True, True, 32), (16, 32, True, True, 16), (10, 0, True, True, 8), (3, 30, False, False, 8)])
-def test_heads_forward_backward(NC, L, two, softmax, F_):
+HEAD_CASES = [(7, 14, True, True, 32), (3, 14, False, True, 8), (5, 0, True, False, 8),
+              (7, 14, True, True, 4),
+              # beyond 8 classes / 16 landmarks / 24 mid channels: the large-capacity build of the kernels
+              (12, 20, True, True, 32), (16, 32, True, True, 16), (10, 0, True, True, 8), (3, 30, False, False, 8)]
+
+
+@pytest.mark.parametrize('NC,L,two,softmax,F_,ldx,lddx',
+                         [pytest.param(*c, c[4], c[4], id='-'.join(str(v) for v in c)) for c in HEAD_CASES] +
+                         # pixel strides wider than the feature count (plan.py passes ldx = the activation's ld): x rows of F + 4,
+                         # dx rows of F + 8 whose padding columns must stay untouched
+                         [pytest.param(*c, c[4] + 4, c[4] + 8, id='-'.join(str(v) for v in c) + '-ldx%d-lddx%d' % (c[4] + 4, c[4] + 8))
+                          for c in HEAD_CASES])
+def test_heads_forward_backward(NC, L, two, softmax, F_, ldx, lddx):
     lib = nat.lib()
     g = torch.Generator().manual_seed(NC + L)
     N, H, W = 2, 11, 13
@@ -582,7 +590,7 @@ def test_heads_forward_backward(NC, L, two, softmax, F_):
     gouts = [torch.randn(o.shape, generator=g, dtype=torch.float64) for o in outs]
     torch.autograd.backward(outs, gouts)
     dv = lambda t: t.detach().float().contiguous().to(DEV)
-    xd = nhwc(x.detach().float()).to(DEV)
+    xd = F.pad(nhwc(x.detach().float()), (0, ldx - F_), value=float('nan')).to(DEV)
     wsd = dv(wseg)
     w1d = dv(w1) if L > 0 else None
     w2d = dv(w2) if (L > 0 and two) else None
@@ -590,7 +598,7 @@ def test_heads_forward_backward(NC, L, two, softmax, F_):
     heatd = torch.empty(N, L, H, W, device=DEV) if L > 0 else None
     nat.call('dfl_head_fwd', nat.HeadFwdArgs(
         x=xd.data_ptr(), w_seg=wsd.data_ptr(), w_l1=nat.ptr(w1d), w_l2=nat.ptr(w2d), seg=segd.data_ptr(), heat=nat.ptr(heatd),
-        N=N, H=H, W=W, F=F_, ldx=F_, NC=NC, NM=NM, L=L, softmax=int(softmax)), stream())
+        N=N, H=H, W=W, F=F_, ldx=ldx, NC=NC, NM=NM, L=L, softmax=int(softmax)), stream())
     torch.cuda.synchronize()
     aclose(segd.cpu().numpy(), seg.detach().numpy(), rtol=1e-5, atol=1e-6)
     if L > 0:
@@ -598,15 +606,17 @@ def test_heads_forward_backward(NC, L, two, softmax, F_):
     # backward
     sld = lib.dfl_head_scratch_ld_for(F_, NC, NM, L)
     scratch = torch.full((N * H * W, sld), float('nan'), device=DEV)
-    dxd = torch.empty(N, H, W, F_, device=DEV)
+    SENT = -777.0
+    dxd = torch.full((N, H, W, lddx), SENT, device=DEV)
     dsegd = dv(gouts[0])
     dheatd = dv(gouts[1]) if L > 0 else None
     nat.call('dfl_head_bwd', nat.HeadBwdArgs(
         x=xd.data_ptr(), seg=segd.data_ptr(), dseg=dsegd.data_ptr(), dheat=nat.ptr(dheatd), w_seg=wsd.data_ptr(),
-        w_l1=nat.ptr(w1d), w_l2=nat.ptr(w2d), dx=dxd.data_ptr(), scratch=scratch.data_ptr(), N=N, H=H, W=W, F=F_, ldx=F_,
-        lddx=F_, NC=NC, NM=NM, L=L, softmax=int(softmax), scratch_ld=sld), stream())
+        w_l1=nat.ptr(w1d), w_l2=nat.ptr(w2d), dx=dxd.data_ptr(), scratch=scratch.data_ptr(), N=N, H=H, W=W, F=F_, ldx=ldx,
+        lddx=lddx, NC=NC, NM=NM, L=L, softmax=int(softmax), scratch_ld=sld), stream())
     torch.cuda.synchronize()
-    aclose(nchw(dxd.cpu()).numpy(), x.grad.numpy(), rtol=1e-4, atol=1e-5)
+    assert bool((dxd[..., F_:] == SENT).all()), 'the padding columns of dx were written'
+    aclose(nchw(dxd[..., :F_].cpu()).numpy(), x.grad.numpy(), rtol=1e-4, atol=1e-5)
     sc = scratch.cpu().double()
     assert torch.isfinite(sc).all()
     off = [lib.dfl_head_scratch_off_for(F_, NC, NM, L, k) for k in range(5)]

@@ -284,6 +284,21 @@ def test_loss_stage_and_stride_arguments_are_validated():
     assert L.dfl_dice_ncc_loss(C.addressof(a), None) < 0 and b'strides' in L.dfl_last_error()
 
 
+def test_head_backward_refuses_live_statistics_outside_the_matrix_core_kernels():
+    """stat_totals is served by the matrix-core kernels alone; every other route of dfl_head_bwd -- the large-capacity head
+    (more than 8 classes) included -- refuses it instead of dropping the statistics."""
+    L = nat.lib()
+    for NC, F_ in ((12, 8), (7, 8)):
+        a = nat.HeadBwdArgs()
+        a.x = a.seg = a.dseg = a.w_seg = a.dx = a.scratch = a.stat_totals = a.stat_other = 4096
+        a.N, a.H, a.W, a.F, a.ldx, a.lddx = 1, 4, 4, F_, F_, F_
+        a.NC, a.NM, a.L, a.softmax = NC, 0, 0, 1
+        a.scratch_ld = L.dfl_head_scratch_ld_for(F_, NC, 0, 0)
+        assert L.dfl_head_bwd(C.addressof(a), None) < 0, NC
+        msg = L.dfl_last_error()
+        assert b'stat_totals' in msg and b'matrix-core' in msg, (NC, msg)
+
+
 def test_product_path_never_touches_the_oracle():
     """oracle/ is test infrastructure: only tests/, tools/ (fixture generation), __graft_entry__.smoke() and bench.py's cpu_baseline
     leg may import it -- never the package or the host scripts (a product path that routes through the CPU restatement would void
