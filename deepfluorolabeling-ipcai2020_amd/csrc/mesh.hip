@@ -209,12 +209,13 @@ __global__ __launch_bounds__(256) void mesh_smooth_kernel(dfl_mesh_smooth_args a
     const float4 p = prev[j];
     return make_float3(p.x, p.y, p.z);
   };
-  const bool fixed = a.fixed[i] != 0;
+  // a vertex without neighbours (no triangle uses it) is held like a fixed one: W is the identity there, not 0 / 0
+  const int32_t k0 = a.row_ptr[i], k1 = a.row_ptr[i + 1];
+  const bool fixed = a.fixed[i] != 0 || k1 == k0;
   float3 m;
   if (fixed) {
     m = at(i);
   } else {
-    const int32_t k0 = a.row_ptr[i], k1 = a.row_ptr[i + 1];
     float sx = 0.f, sy = 0.f, sz = 0.f;
     for (int32_t k = k0; k < k1; ++k) {
       const float3 p = at(a.col[k]);

@@ -191,7 +191,8 @@ def normalize(verts):
 def smooth(verts, tris, iterations=ITERATIONS, passband=PASSBAND):
     """Windowed-sinc smoothing of verts [V, 3] fp32 with the triangles tris [T, 3] int32:
     (smoothed positions in the normalised frame of normalize(), fp32 [V, 3]; the fp64 4x4 back to the input frame).
-    Vertices on an edge of exactly one triangle keep their normalised position bit for bit."""
+    Vertices on an edge of exactly one triangle, and vertices that no triangle uses, keep their normalised position bit
+    for bit."""
     verts, tris = _check_mesh(verts, tris, 'smooth')
     if not 1 <= int(iterations) <= nat.MESH_MAX_ITERS:
         raise nat.DflError('mesh.smooth: 1 to %d iterations' % nat.MESH_MAX_ITERS)

@@ -899,8 +899,9 @@ int dfl_mesh_csr(const dfl_mesh_csr_args* a, dfl_stream_t stream);
 
 /* Windowed-sinc smoothing: out = sum_{n <= iterations} coef[n] T_n with T_0 = x, T_1 = W x, T_{n+1} = 2 W T_n - T_{n-1};
  * (W y)_i = the mean of y over the neighbours col[row_ptr[i] .. row_ptr[i+1]-1] in that order, or y_i when fixed[i].
- * Fixed vertices are copied from x bit for bit.  One gather launch per n, fp32; t_a, t_b, acc are [V][4] scratch.
- * x, out [V][3]. */
+ * A vertex without neighbours (row_ptr[i] == row_ptr[i+1]: no triangle uses it) is treated as fixed.  Fixed vertices
+ * are copied from x bit for bit.  One gather launch per n, fp32; t_a, t_b, acc are [V][4] scratch (unused when
+ * iterations == 1).  x, out [V][3]. */
 typedef struct {
   const float* x;
   const int32_t* row_ptr;

@@ -70,6 +70,84 @@ def test_model_matches_the_fixtures(name):
         np.testing.assert_allclose(R.smooth(xn, T)[0], z['smooth_%d' % i], rtol=0, atol=1e-12)
 
 
+@pytest.mark.parametrize('name', SURFACES)
+def test_triangle_keys_and_block_counts_match_the_fixtures(name):
+    import mesh_ref as R
+    from dfl_amd import _native as nat
+    z = load_golden('viz3d_' + name)
+    labels = [int(v) for v in z['labels']]
+    cells = int(np.prod(np.array(z['volume'].shape) - 1))
+    counts, offsets, totals = R.block_counts(z['volume'], labels)
+    nb = -(-cells // nat.MESH_MC_CELLS)
+    assert counts.shape == offsets.shape == (nb, nat.MESH_MAX_LABELS) and totals.shape == (nat.MESH_MAX_LABELS + 1,)
+    first = 0
+    for i, lab in enumerate(labels):
+        K, ntri = R.triangle_keys(z['volume'], lab)
+        T = len(z['tris_%d' % i])
+        assert K.shape == (T, 3) and K.dtype == np.int64 and ntri.shape == (cells,) and int(ntri.sum()) == T
+        uniq, inv = np.unique(K.reshape(-1), return_inverse=True)
+        assert np.array_equal(uniq, z['keys_%d' % i]) and np.array_equal(inv.reshape(-1, 3), z['tris_%d' % i])
+        assert int(counts[:, i].sum()) == T and totals[i] == first
+        assert np.array_equal(offsets[:, i], first + np.cumsum(counts[:, i]) - counts[:, i])
+        assert np.array_equal(counts[:, i], [ntri[b * nat.MESH_MC_CELLS:(b + 1) * nat.MESH_MC_CELLS].sum() for b in range(nb)])
+        first += T
+    n = len(labels)
+    assert totals[n] == first and np.all(totals[n + 1:] == -1)
+    assert not counts[:, n:].any() and np.all(offsets[:, n:] == -1)          # written as 0; not written
+
+
+def two_triangles():
+    """A unit square cut along its diagonal 0-2, in the z = 0 plane, counter-clockwise seen from +z; vertex 4 unused."""
+    P = np.array([[0, 0, 0], [1, 0, 0], [1, 1, 0], [0, 1, 0], [5, 5, 5]], np.float32)
+    return P, np.array([[0, 1, 2], [0, 2, 3]], np.int32)
+
+
+def test_vertex_triangles_and_normals_by_hand():
+    import mesh_ref as R
+    P, T = two_triangles()
+    assert R.vt_keys(T).tolist() == [0, 7, 14, 3, 16, 23]
+    assert R.edge_keys(T, 5).tolist() == [1, 5, 7, 11, 10, 2, 2, 10, 13, 17, 15, 3]
+    ptr, tri = R.vertex_triangles(T, 5)
+    assert ptr.tolist() == [0, 2, 3, 5, 6, 6] and tri.tolist() == [0, 1, 0, 0, 1, 1]
+    n = R.normals(P, T, 5)
+    assert n.dtype == np.float64 and np.array_equal(n, [[0, 0, 1]] * 4 + [[0, 0, 0]])
+    # tilt triangle 1 about the diagonal: vertex 3 up by 1.  Areas: (0, 0, 1) and (1, -1, 1) (twice the area vectors)
+    P[3, 2] = 1
+    n = R.normals(P, T, 5)
+    s3, s6 = 1 / np.sqrt(3), 1 / np.sqrt(6)
+    np.testing.assert_allclose(n, [[s6, -s6, 2 * s6], [0, 0, 1], [s6, -s6, 2 * s6], [s3, -s3, s3], [0, 0, 0]], rtol=0, atol=1e-15)
+    # degenerate (a repeated vertex; collinear points) and exactly cancelling triangles give exact zeros
+    Q = np.array([[0, 0, 0], [1, 1, 1], [2, 2, 2], [3, 0, 1]], np.float32)
+    assert not R.normals(Q, np.array([[0, 1, 2], [3, 3, 0]], np.int32), 4).any()
+    assert not R.normals(Q, np.array([[0, 1, 3], [0, 3, 1]], np.int32), 4).any()
+
+
+def test_neighbours_of_two_triangles():
+    import mesh_ref as R
+    _, T = two_triangles()
+    ptr, col, fixed = R.neighbours(T, 5)
+    assert ptr.tolist() == [0, 3, 5, 8, 10, 10] and col.tolist() == [1, 2, 3, 0, 2, 0, 1, 3, 0, 2]
+    assert fixed.tolist() == [True, True, True, True, False]                  # every vertex is on a border edge
+
+
+def test_vertex_without_neighbours_keeps_its_position():
+    """A closed tetrahedron (no fixed vertex) plus one vertex that no triangle uses: the model leaves it in place bit for
+    bit, in fp64 and in fp32, for every number of terms, and moves the others as it moves them without it."""
+    import mesh_ref as R
+    rng = np.random.default_rng(5)
+    x = rng.uniform(-1, 1, (5, 3)).astype(np.float32)
+    T = np.array([[0, 1, 2], [0, 3, 1], [0, 2, 3], [1, 3, 2]], np.int32)
+    ptr, _, fixed = R.neighbours(T, 5)
+    assert not fixed.any() and ptr[4] == ptr[5]
+    for n in (1, 2, 3, 25):
+        for dtype in (np.float64, np.float32):
+            got, fx = R.smooth(x, T, iterations=n, dtype=dtype)
+            assert np.all(np.isfinite(got)) and not fx.any()
+            assert np.array_equal(got[4], x[4].astype(np.float64))
+            assert np.array_equal(got[:4], R.smooth(x[:4], T, iterations=n, dtype=dtype)[0])
+            assert np.abs(got[:4] - x[:4]).max() > 1e-2
+
+
 def test_single_voxel_is_an_octahedron():
     import mesh_ref as R
     z = load_golden('viz3d_voxel')
