@@ -38,7 +38,7 @@ _SIZEOF_ORDER = [ConvArgs, WgradArgs, PackJob, BnFinalizeArgs, ColstatsArgs, BnB
                  AffineCopyArgs, PoolArgs, HeadFwdArgs, HeadBwdArgs, LossArgs, EnsembleArgs, Op, ReduceJob, PrepArgs, EstLandsArgs,
                  UpsampleArgs, AugmentArgs, AugmentItem, OverlayArgs, ResamplePlan, ResampleArgs, FullresArgs, MeshMcArgs, MeshDecodeArgs,
                  MeshTopoArgs, MeshCsrArgs, MeshSmoothArgs, MeshXformArgs, MeshNormalsArgs, PreprocProjsArgs, PreprocSegsArgs,
-                 RestoreLabelsArgs, SimPrepareArgs, SimGradnccArgs, ExposeArgs, SimPatchPrepareArgs, SimPatchGradnccArgs,
+                 RestoreLabelsArgs, SimPrepareArgs, SimGradnccArgs, ExposeArgs, SimPatchPrepareArgs, SimPatchGradnccArgs, RasterMesh, RasterArgs,
                  SimGradnccBwdArgs, SimPatchWeightsArgs, SimPatchEvalArgs, DrrPoseGradArgs, SimBankGradnccArgs, SimBankGradnccBwdArgs, SimPatchBankGradnccArgs, DrrObject, DrrArgs,
                  OptimPackArgs]
 

@@ -48,7 +48,7 @@ const char* dfl_last_error(void);
  * bn_bwd_finalize, bn_relu_bwd, affine_copy, pool, head_fwd, head_bwd, loss, ensemble, op, reduce_job, prep,
  * est_lands, upsample, augment_args, augment_item, overlay, resample_plan, resample_args, fullres, mesh_mc,
  * mesh_decode, mesh_topo, mesh_csr, mesh_smooth, mesh_xform, mesh_normals, preproc_projs, preproc_segs, restore_labels,
- * sim_prepare, sim_gradncc, expose, sim_patch_prepare, sim_patch_gradncc, sim_gradncc_bwd, sim_patch_weights,
+ * sim_prepare, sim_gradncc, expose, sim_patch_prepare, sim_patch_gradncc, raster_mesh, raster_args, sim_gradncc_bwd, sim_patch_weights,
  * sim_patch_eval, drr_pose_grad, sim_bank_gradncc, sim_bank_gradncc_bwd, sim_patch_bank_gradncc, drr_object, drr_args, optim_pack): lets a
  * binding written in another language verify the size of its struct mirrors at load time.  Returns -1 past the end.
  * Sizes say nothing about field order or type: the Python binding derives its structs, constants and signatures from this
@@ -937,6 +937,84 @@ typedef struct {
   int64_t V;
 } dfl_mesh_normals_args;
 int dfl_mesh_normals(const dfl_mesh_normals_args* a, dfl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Rasteriser: the scene of full_res_3d_viz.py (the surfaces above, spheres, ray ribbons, the textured detector) drawn
+ * into an 8-bit RGB image through a visibility buffer, restated in DESIGN.md section 22.  Triangles only.
+ *
+ * A scene is n_mesh records.  The caller passes them twice: `meshes` on the host (read for the checks below and the
+ * launch sizes, never by a kernel) and `meshes_dev`, a device copy of the same bytes (read by the kernels).  pos, nrm,
+ * uv, tris and tex are device pointers in both.  Records that share buffers under another matrix are instances.
+ * Primitive id of triangle t of a record = first_prim + t (uint32); the ranges of the records ascend without overlap
+ * and end below 0xffffffff, the background.  A triangle with a vertex index outside [0, n_verts) counts as degenerate.
+ *
+ * Built with -ffp-contract=off: every product and sum below is rounded on its own, divisions and square roots are
+ * correctly rounded (tests/raster_ref.py restates them in numpy float32).
+ *
+ * Vertex stage, per corner (x, y, z), m = mvp:  clip_k = ((m[4k] x + m[4k+1] y) + m[4k+2] z) + m[4k+3];  w = clip_3;
+ *   px = (clip_0 / w + 1) (0.5 Ws),  py = (1 - clip_1 / w) (0.5 Hs),  Ws = ssaa W, Hs = ssaa H (y down, sample centres
+ *   at integer + 1/2);  X = rintf(256 px), Y = rintf(256 py);  zd = clip_2 / w.
+ * A triangle is dropped whole when a corner has a non-finite clip value or w < znear (counts[1]; there is no near-plane
+ * clipping), else when a corner has |X| or |Y| > 2^22 (counts[2]), else when its area is 0 (counts[3]); else it is
+ * drawn (counts[0]), also where it then covers no sample.
+ * Coverage: with s the sign of the area A = (X1-X0)(Y2-Y0) - (Y1-Y0)(X2-X0) (int64), edge k runs from corner k+1 to
+ *   corner k+2 (mod 3), d = s (b - a), E_k = d.x (Py - a.y) - d.y (Px - a.x) at P = (256 i + 128, 256 j + 128).  Sample
+ *   (i, j) is covered when every E_k > 0, or E_k = 0 on an edge with d.y < 0 or (d.y = 0 and d.x > 0) (top-left).
+ * Depth: l_k = (float)E_k / (float)|A|;  depth = (l_0 zd_0 + l_1 zd_1) + l_2 zd_2 (-0 counts as +0); the sample counts
+ *   only when 0 <= depth <= 1.  vis[j][i] = min over the triangles of (bits(depth) << 32) | prim, by the 64-bit unsigned
+ *   integer atomic minimum (order-independent: every run gives the same bytes; equal depths go to the lower id).
+ * Triangles whose clamped bounding box is at most DFL_RASTER_SMALL_BOX samples wide and high are walked by the thread
+ *   that set them up; the others go to a list of DFL_RASTER_MAX_LARGE entries and are covered by workgroups in
+ *   DFL_RASTER_TILE x DFL_RASTER_TILE tiles (when the list is full, by their thread).  Both ways give the same keys.
+ * Shade, per sample: b_k = l_k / w_k, then b_k / ((b_0 + b_1) + b_2).  q = (b_0 q_0 + b_1 q_1) + b_2 q_2 for the
+ *   normal components and u, v.  base = rgb, for a textured record rgb * ((float)tex[ty][tx] / 255) with
+ *   tx = clamp((int)floorf(u tw), 0, tw - 1), ty from v and th.  Unless unlit: r = nmat n (rows as clip_k above, three
+ *   terms), len = sqrtf((r_x r_x + r_y r_y) + r_z r_z), intensity = ambient + diffuse * (len > 0 ? |r_z| / len : 0),
+ *   colour = base * intensity.  byte = rintf(255 * min(max(colour, 0), 1)).  Background samples take `background`.
+ * Resolve: rgb[y][x][c] = (sum of the ssaa x ssaa sample bytes + ssaa^2 / 2) / ssaa^2 in integers.
+ *
+ * ids (optional) int32 [Hs][Ws]: the primitive id, -1 for background.  depth (optional) float [Hs][Ws]: +infinity for
+ * background.  counts (optional) int32 [4].  scratch: dfl_raster_scratch_bytes(W, H, ssaa, n_mesh) bytes, 8-aligned
+ * (negative: bad sizes or more than 2^31 - 1 bytes).  ssaa 1..DFL_RASTER_MAX_SSAA, Ws, Hs <= DFL_RASTER_MAX_DIM,
+ * 0 <= n_mesh <= DFL_RASTER_MAX_MESHES, fewer than 2^31 triangles in all.  An empty scene gives the background.
+ * Refused with nothing launched: NULL args, meshes (n_mesh > 0), scratch, rgb, pos or tris; bad sizes; a short
+ * scratch; znear <= 0; nrm NULL without DFL_RASTER_UNLIT; DFL_RASTER_TEXTURED without uv, tex, tw > 0 and th > 0.
+ * Launches: clear, triangles, large triangles (skipped when the scene is empty), shade, resolve.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define DFL_RASTER_UNLIT 1
+#define DFL_RASTER_TEXTURED 2
+#define DFL_RASTER_SMALL_BOX 16           /* samples: the widest / highest box a single thread walks */
+#define DFL_RASTER_TILE 64
+#define DFL_RASTER_MAX_LARGE 65536
+#define DFL_RASTER_MAX_SSAA 4
+#define DFL_RASTER_MAX_DIM 16384
+#define DFL_RASTER_MAX_MESHES 4096
+typedef struct {
+  const float* pos;               /* [n_verts][3] */
+  const float* nrm;               /* [n_verts][3] or NULL (unlit only) */
+  const float* uv;                /* [n_verts][2] or NULL */
+  const int32_t* tris;            /* [n_tris][3] */
+  const unsigned char* tex;       /* [th][tw] grey or NULL */
+  int32_t n_verts, n_tris, tw, th;
+  uint32_t first_prim, flags;
+  float mvp[16];                  /* row-major, object to clip */
+  float nmat[9];                  /* row-major, object normal to eye */
+  float rgb[3];
+} dfl_raster_mesh;
+typedef struct {
+  const dfl_raster_mesh* meshes;      /* host [n_mesh] */
+  const dfl_raster_mesh* meshes_dev;  /* device [n_mesh], the same bytes */
+  void* scratch;
+  unsigned char* rgb;                 /* [H][W][3] */
+  int32_t* ids;
+  float* depth;
+  int32_t* counts;
+  int32_t n_mesh, W, H, ssaa, scratch_bytes;
+  float znear, ambient, diffuse;
+  float background[3];
+} dfl_raster_args;
+int dfl_raster_scratch_bytes(int32_t W, int32_t H, int32_t ssaa, int32_t n_mesh);
+int dfl_raster_draw(const dfl_raster_args* a, dfl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Training files from the full-resolution dataset (the reference's README: crop 50 pixels from each border,
