@@ -37,7 +37,8 @@ _KIND_OF = {ConvArgs: OP_CONV, WgradArgs: OP_WGRAD, SumPartialsArgs: OP_SUM_PART
 _SIZEOF_ORDER = [ConvArgs, WgradArgs, PackJob, BnFinalizeArgs, ColstatsArgs, BnBwdFinalizeArgs, BnReluBwdArgs,
                  AffineCopyArgs, PoolArgs, HeadFwdArgs, HeadBwdArgs, LossArgs, EnsembleArgs, Op, ReduceJob, PrepArgs, EstLandsArgs,
                  UpsampleArgs, AugmentArgs, AugmentItem, OverlayArgs, ResamplePlan, ResampleArgs, FullresArgs, MeshMcArgs, MeshDecodeArgs,
-                 MeshTopoArgs, MeshCsrArgs, MeshSmoothArgs, MeshXformArgs, MeshNormalsArgs, PreprocProjsArgs, PreprocSegsArgs,
+                 MeshTopoArgs, MeshCsrArgs, MeshSmoothArgs, MeshXformArgs, MeshNormalsArgs, MeshQuadricsArgs,
+                 MeshCollapseKeysArgs, MeshCollapseSelectArgs, MeshCollapseApplyArgs, PreprocProjsArgs, PreprocSegsArgs,
                  RestoreLabelsArgs, SimPrepareArgs, SimGradnccArgs, ExposeArgs, SimPatchPrepareArgs, SimPatchGradnccArgs, RasterMesh, RasterArgs,
                  SimGradnccBwdArgs, SimPatchWeightsArgs, SimPatchEvalArgs, DrrPoseGradArgs, SimBankGradnccArgs, SimBankGradnccBwdArgs, SimPatchBankGradnccArgs, DrrObject, DrrArgs,
                  OptimPackArgs]

@@ -83,7 +83,10 @@ extern "C" int dfl_sizeof(int which) {
       (int)sizeof(dfl_resample_plan),   (int)sizeof(dfl_resample_args),        (int)sizeof(dfl_fullres_args),
       (int)sizeof(dfl_mesh_mc_args),    (int)sizeof(dfl_mesh_decode_args),     (int)sizeof(dfl_mesh_topo_args),
       (int)sizeof(dfl_mesh_csr_args),   (int)sizeof(dfl_mesh_smooth_args),     (int)sizeof(dfl_mesh_xform_args),
-      (int)sizeof(dfl_mesh_normals_args),  (int)sizeof(dfl_preproc_projs_args),   (int)sizeof(dfl_preproc_segs_args),
+      (int)sizeof(dfl_mesh_normals_args),
+      (int)sizeof(dfl_mesh_quadrics_args), (int)sizeof(dfl_mesh_collapse_keys_args), (int)sizeof(dfl_mesh_collapse_select_args),
+      (int)sizeof(dfl_mesh_collapse_apply_args),
+      (int)sizeof(dfl_preproc_projs_args),   (int)sizeof(dfl_preproc_segs_args),
       (int)sizeof(dfl_restore_labels_args), (int)sizeof(dfl_sim_prepare_args),  (int)sizeof(dfl_sim_gradncc_args),
       (int)sizeof(dfl_expose_args),     (int)sizeof(dfl_sim_patch_prepare_args), (int)sizeof(dfl_sim_patch_gradncc_args),
       (int)sizeof(dfl_raster_mesh),    (int)sizeof(dfl_raster_args),

@@ -3,8 +3,9 @@ reference's examples_dataset/full_res_3d_viz.py, restated in DESIGN.md section 1
 
 label_surfaces() runs discrete marching cubes for up to MAX_LABELS labels in one pass over a uint8 volume; smooth()
 applies the windowed-sinc filter; transform() applies an fp64 affine 4x4; vertex_normals() gives area-weighted
-normals.  The kernels are csrc/mesh.hip (include/dfl_hip.h "Bone surfaces"); sorting and deduplicating keys is done
-with torch.  There is no host path: CPU tensors are refused."""
+normals; decimate() reduces a surface by rounds of quadric-error edge collapses (the place of the
+reference's vtkQuadricDecimation).  The kernels are csrc/mesh.hip and csrc/decimate.hip (include/dfl_hip.h "Bone
+surfaces"); sorting and deduplicating keys is done with torch.  There is no host path: CPU tensors are refused."""
 import math
 import os
 
@@ -225,6 +226,96 @@ def transform(x, M):
         a.M[i] = float(v)
     nat.call('dfl_mesh_transform', a, _stream(x))
     return out
+
+
+REDUCTION, MAX_ROUNDS = 0.25, 64         # full_res_3d_viz.py create_mesh: vtkQuadricDecimation.SetTargetReduction(0.25)
+
+
+def collapse_budget(reduction, T):
+    """Edge collapses that take `reduction` of T triangles away, two per collapse: floor(reduction T) // 2."""
+    return int(math.floor(float(reduction) * T)) // 2
+
+
+def _round_topology(tris, V):
+    """The lists one decimation round gathers over (include/dfl_hip.h: dfl_mesh_collapse_keys): the neighbour CSR with the
+    use count and the undirected edge of every entry, the undirected edges in ascending order, the vertex-triangle CSR."""
+    T = tris.shape[0]
+    ek = torch.empty(6 * T, dtype=torch.int64, device=tris.device)
+    vk = torch.empty(3 * T, dtype=torch.int64, device=tris.device)
+    nat.call('dfl_mesh_topology', nat.MeshTopoArgs(tris=tris.data_ptr(), edge_keys=ek.data_ptr(), vt_keys=vk.data_ptr(), T=T, V=V),
+             _stream(tris))
+    uk, cnt = torch.unique(ek, sorted=True, return_counts=True)
+    row_ptr, col, _ = _csr(uk, cnt, V, 1, V)
+    vt_ptr, vt_tri, _ = _csr(torch.sort(vk).values, None, 3 * T, 3, V)
+    row = torch.div(uk, V, rounding_mode='floor')
+    to = uk - row * V
+    und = row < to
+    eid = torch.searchsorted(uk[und], torch.minimum(row, to) * V + torch.maximum(row, to)).to(torch.int32)
+    return dict(row_ptr=row_ptr, col=col, use=cnt.to(torch.int32), eid=eid, edge_u=row[und].to(torch.int32),
+                edge_v=to[und].to(torch.int32), vt_ptr=vt_ptr, vt_tri=vt_tri)
+
+
+def decimate(verts, tris, reduction=REDUCTION, max_rounds=MAX_ROUNDS):
+    """Quadric-error decimation by rounds of edge collapses that do not touch: (verts', tris',
+    {'collapses', 'rounds', 'budget'}).  budget = floor(reduction T) // 2 collapses, each taking one vertex and two
+    triangles away; rounds end when the budget is spent, a round finds no collapse, or after max_rounds.  Vertices on a
+    border or a non-manifold edge stay where they are; surviving vertices and triangles keep their order and winding."""
+    if not 0.0 < float(reduction) < 1.0:
+        raise nat.DflError('mesh.decimate: reduction %r outside (0, 1)' % (reduction,))
+    verts, tris = _check_mesh(verts, tris, 'decimate')
+    if tris.shape[0] == 0:
+        raise nat.DflError('mesh.decimate: no triangles')
+    lo, hi = (int(v) for v in torch.aminmax(tris))
+    if lo < 0 or hi >= verts.shape[0]:
+        raise nat.DflError('mesh.decimate: triangle indices %d .. %d outside [0, %d)' % (lo, hi, verts.shape[0]))
+    if bool(((tris[:, 0] == tris[:, 1]) | (tris[:, 1] == tris[:, 2]) | (tris[:, 2] == tris[:, 0])).any()):
+        raise nat.DflError('mesh.decimate: a triangle repeats a vertex')
+    dev, s = verts.device, _stream(verts)
+    budget = collapse_budget(reduction, tris.shape[0])
+    done = rounds = 0
+    while done < budget and rounds < int(max_rounds):
+        V, T = verts.shape[0], tris.shape[0]
+        tp = _round_topology(tris, V)
+        E = tp['edge_u'].numel()
+        p = {k: t.data_ptr() for k, t in tp.items()}
+        Q = torch.empty((V, 10), dtype=torch.float64, device=dev)
+        nat.call('dfl_mesh_quadrics', nat.MeshQuadricsArgs(pos=verts.data_ptr(), tris=tris.data_ptr(), vt_ptr=p['vt_ptr'],
+                                                           vt_tri=p['vt_tri'], Q=Q.data_ptr(), V=V, T=T), s)
+        key = torch.empty(E, dtype=torch.int64, device=dev)          # uint64 bits; torch sorts them as int64 below
+        cand = torch.empty((E, 3), dtype=torch.float32, device=dev)
+        nat.call('dfl_mesh_collapse_keys', nat.MeshCollapseKeysArgs(
+            pos=verts.data_ptr(), tris=tris.data_ptr(), row_ptr=p['row_ptr'], col=p['col'], use=p['use'], vt_ptr=p['vt_ptr'],
+            vt_tri=p['vt_tri'], Q=Q.data_ptr(), edge_u=p['edge_u'], edge_v=p['edge_v'], key=key.data_ptr(), cand=cand.data_ptr(),
+            V=V, T=T, E=E), s)
+        m1, m2 = (torch.empty(V, dtype=torch.int64, device=dev) for _ in range(2))
+        sel = torch.empty(E, dtype=torch.uint8, device=dev)
+        nat.call('dfl_mesh_collapse_select', nat.MeshCollapseSelectArgs(
+            row_ptr=p['row_ptr'], col=p['col'], eid=p['eid'], edge_u=p['edge_u'], edge_v=p['edge_v'], key=key.data_ptr(),
+            m1=m1.data_ptr(), m2=m2.data_ptr(), sel=sel.data_ptr(), V=V, E=E), s)
+        chosen = torch.nonzero(sel).view(-1)
+        if chosen.numel() > budget - done:
+            # the lowest keys win: a selected key has a finite non-negative cost, so its sign bit is clear and the
+            # signed order is the unsigned one
+            chosen = chosen[torch.sort(key[chosen]).indices[:budget - done]]
+        n = chosen.numel()
+        if n == 0:
+            break
+        take = torch.zeros(E, dtype=torch.uint8, device=dev)
+        take[chosen] = 1
+        remap = torch.empty(V, dtype=torch.int32, device=dev)
+        pos_out, tris_out = torch.empty_like(verts), torch.empty_like(tris)
+        degen = torch.empty(T, dtype=torch.uint8, device=dev)
+        nat.call('dfl_mesh_collapse_apply', nat.MeshCollapseApplyArgs(
+            pos=verts.data_ptr(), tris=tris.data_ptr(), row_ptr=p['row_ptr'], col=p['col'], eid=p['eid'], take=take.data_ptr(),
+            cand=cand.data_ptr(), remap=remap.data_ptr(), pos_out=pos_out.data_ptr(), tris_out=tris_out.data_ptr(),
+            degen=degen.data_ptr(), V=V, T=T, E=E), s)
+        keep = remap == torch.arange(V, dtype=torch.int32, device=dev)
+        new_id = (torch.cumsum(keep, 0) - 1).to(torch.int32)
+        verts = pos_out[keep].contiguous()
+        tris = new_id[tris_out[degen == 0].long()].contiguous()
+        done += n
+        rounds += 1
+    return verts, tris, {'collapses': done, 'rounds': rounds, 'budget': budget}
 
 
 def vertex_normals(pos, tris):

@@ -14,6 +14,9 @@ matrix: the bones in front of their own projection (the source sphere lies behin
 seen end-on, are left out).  --png-size WxH (default 1280x960; for the source view the detector's shape scaled to at
 most 1280 columns), --ssaa N samples per pixel side (1..4, default 2).
 
+--decimate R reduces every bone surface by the fraction R of its triangles after smoothing (dfl_amd.mesh.decimate,
+DESIGN.md section 23; the reference's vtkQuadricDecimation runs at 0.25).  Without it the surfaces are not decimated.
+
 Scene, in the camera projective frame, in mm: the left / right hemipelvis (labels 1 / 2, green / red) and the left /
 right femur (5 / 6, cyan / orange) placed by the ground-truth poses, the 3D landmarks (purple spheres, radius 5), the
 X-ray source (green, radius 10), the detector plane textured with the projection, and for each visible 2D landmark a
@@ -148,9 +151,10 @@ def unit_sphere(res=SPHERE_RES):
     return pos.astype(np.float32), np.array(tris, np.uint32)
 
 
-def surfaces_on_gpu(g, dev, log=print, on_device=None):
+def surfaces_on_gpu(g, dev, log=print, on_device=None, decimate=None):
     """[(positions, normals, triangles) or None] per entry of SURFACES: one marching-cubes pass for all labels, then
-    per label the smoother, the transform into the camera projective frame and the normals.  A list passed as on_device
+    per label the smoother, with decimate=R the quadric decimation by R in the smoother's normalised frame (where the
+    reference decimates), the transform into the camera projective frame and the normals.  A list passed as on_device
     receives the same entries as GPU tensors."""
     vol = torch.from_numpy(np.ascontiguousarray(g['volume'])).to(dev)
     meshes = mesh.label_surfaces(vol, [s[2] for s in SURFACES])
@@ -163,6 +167,8 @@ def surfaces_on_gpu(g, dev, log=print, on_device=None):
                 on_device.append(None)
             continue
         xs, undo = mesh.smooth(verts, tris)
+        if decimate is not None:
+            xs, tris, _ = mesh.decimate(xs, tris, decimate)
         pos = mesh.transform(xs, M @ undo)
         nrm = mesh.vertex_normals(pos, tris)
         out.append((pos.cpu().numpy(), nrm.cpu().numpy(), tris.cpu().numpy()))
@@ -279,15 +285,23 @@ def render_png(g, surfaces, dev, which, width, height, ssaa, return_ids=False):
 
 
 def options(argv):
-    """(positional arguments, {flag: value}) or a message: --out, --png, --png-size, --view and --ssaa take one value."""
+    """(positional arguments, {flag: value}) or a message: --out, --png, --png-size, --view, --ssaa and --decimate take
+    one value."""
     argv, opt = list(argv), {}
-    for flag in ('--out', '--png', '--png-size', '--view', '--ssaa'):
+    for flag in ('--out', '--png', '--png-size', '--view', '--ssaa', '--decimate'):
         if flag in argv:
             k = argv.index(flag)
             if k + 1 >= len(argv):
                 return '{} needs a {}'.format(flag, 'path' if flag in ('--out', '--png') else 'value')
             opt[flag] = argv[k + 1]
             del argv[k:k + 2]
+    if '--decimate' in opt:
+        try:
+            opt['--decimate'] = float(opt['--decimate'])
+        except ValueError:
+            opt['--decimate'] = float('nan')
+        if not 0.0 < opt['--decimate'] < 1.0:
+            return '--decimate is a reduction between 0 and 1 (the reference: {})'.format(mesh.REDUCTION)
     if any(f in opt for f in ('--png-size', '--view', '--ssaa')) and '--png' not in opt:
         return '--png-size, --view and --ssaa go with --png'
     if '--png' in opt:
@@ -327,7 +341,7 @@ def main(argv=None):
         src.close()
     dev = dfl_amd.get_device()
     on_device = [] if '--png' in opt else None
-    surfaces = surfaces_on_gpu(g, dev, on_device=on_device)
+    surfaces = surfaces_on_gpu(g, dev, on_device=on_device, decimate=opt.get('--decimate'))
     out = out or '{}_{:03d}.glb'.format(spec, idx)
     build_scene(g, surfaces).write(out)
     print('wrote {}'.format(out))

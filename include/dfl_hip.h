@@ -938,6 +938,84 @@ typedef struct {
 } dfl_mesh_normals_args;
 int dfl_mesh_normals(const dfl_mesh_normals_args* a, dfl_stream_t stream);
 
+/* Quadric-error decimation, one round (csrc/decimate.hip, built with -ffp-contract=off: all
+ * arithmetic is fp64 on the fp32 positions, every product and sum rounded on its own, tests/decimate_ref.py restates it).
+ * The caller (dfl_amd.mesh.decimate) rebuilds, every round, the neighbour CSR (row_ptr, col) and the vertex-triangle CSR
+ * (vt_ptr, vt_tri) with dfl_mesh_topology and dfl_mesh_csr, and beside them: use[k] = the number of triangles on the
+ * edge (row, col[k]); the undirected edges e = 0 .. E - 1 in ascending (u, v) order, u = edge_u[e] < v = edge_v[e]; and
+ * eid[k] = the undirected edge of entry k.  Counts below 2^31; V, T, E >= 1.  No atomics: one writer per element.
+ *
+ * dfl_mesh_quadrics: Q[v] = the sum over the triangles of v, in vt_tri order, of K_t = plane plane^T / l as the 10
+ * entries (aa ab ac ad bb bc bd cc cd dd), plane = (n, -n . p0), n = (p1 - p0) x (p2 - p0), l = sqrt(n . n); K_t = 0
+ * when l == 0. */
+typedef struct {
+  const float* pos;               /* [V][3] */
+  const int32_t* tris;            /* [T][3] */
+  const int32_t* vt_ptr;          /* [V + 1] */
+  const int32_t* vt_tri;          /* [3T] */
+  double* Q;                      /* [V][10] */
+  int64_t V, T;
+} dfl_mesh_quadrics_args;
+int dfl_mesh_quadrics(const dfl_mesh_quadrics_args* a, dfl_stream_t stream);
+
+/* One thread per undirected edge: key[e] = (bits(fp32(cost)) << 32) | e for a candidate, all ones otherwise, and
+ * cand[e] = the position the collapse would give u (zeros for a non-candidate).  Candidate: use 2, no edge of use != 2
+ * at u or v, exactly two common neighbours, both of degree >= 5, deg(u) + deg(v) - 4 >= 3, and no triangle at u or v
+ * (without both) whose normal turns: n0 . n1 > 0 and (n0 . n1)^2 >= 0.04 (n0 . n0)(n1 . n1).  Position: -A^-1 b of
+ * q = Q[u] + Q[v] by cofactors when det A > 1e-3 (trace A / 3)^3 and it lies within twice the edge length of the
+ * midpoint, else the cheapest of midpoint, p_u, p_v; rounded to fp32 before the cost and the flip test. */
+typedef struct {
+  const float* pos;
+  const int32_t* tris;
+  const int32_t* row_ptr;         /* [V + 1] */
+  const int32_t* col;             /* [2E] */
+  const int32_t* use;             /* [2E], aligned with col */
+  const int32_t* vt_ptr;
+  const int32_t* vt_tri;
+  const double* Q;
+  const int32_t* edge_u;          /* [E] */
+  const int32_t* edge_v;          /* [E] */
+  uint64_t* key;                  /* [E] */
+  float* cand;                    /* [E][3] */
+  int64_t V, T, E;
+} dfl_mesh_collapse_keys_args;
+int dfl_mesh_collapse_keys(const dfl_mesh_collapse_keys_args* a, dfl_stream_t stream);
+
+/* Three gather launches: m1[v] = min of key over the edges at v; m2[v] = min of m1 over v and its neighbours;
+ * sel[e] = 1 when e is a candidate and m2[u] == m2[v] == key[e], else 0. */
+typedef struct {
+  const int32_t* row_ptr;
+  const int32_t* col;
+  const int32_t* eid;             /* [2E], aligned with col */
+  const int32_t* edge_u;
+  const int32_t* edge_v;
+  const uint64_t* key;
+  uint64_t* m1;                   /* [V] */
+  uint64_t* m2;                   /* [V] */
+  unsigned char* sel;             /* [E] */
+  int64_t V, E;
+} dfl_mesh_collapse_select_args;
+int dfl_mesh_collapse_select(const dfl_mesh_collapse_select_args* a, dfl_stream_t stream);
+
+/* The collapses take[e] != 0 (vertex-disjoint): remap[v] = the lower end of the taken edge whose upper end v is, else
+ * v; pos_out = pos with the lower end of every taken edge at cand[e]; tris_out = remap of tris; degen[t] = 1 when two
+ * corners of tris_out[t] are equal. */
+typedef struct {
+  const float* pos;
+  const int32_t* tris;
+  const int32_t* row_ptr;
+  const int32_t* col;
+  const int32_t* eid;
+  const unsigned char* take;      /* [E] */
+  const float* cand;
+  int32_t* remap;                 /* [V] */
+  float* pos_out;                 /* [V][3] */
+  int32_t* tris_out;              /* [T][3] */
+  unsigned char* degen;           /* [T] */
+  int64_t V, T, E;
+} dfl_mesh_collapse_apply_args;
+int dfl_mesh_collapse_apply(const dfl_mesh_collapse_apply_args* a, dfl_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Rasteriser: the scene of full_res_3d_viz.py (the surfaces above, spheres, ray ribbons, the textured detector) drawn
  * into an 8-bit RGB image through a visibility buffer, restated in DESIGN.md section 22.  Triangles only.
