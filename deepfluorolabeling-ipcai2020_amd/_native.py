@@ -226,20 +226,21 @@ class Program:
     MIN_GRAPH_OPS = 2
 
     def graph_chunks(self, stream, start=0, count=None):
-        """Cut ops [start, start + count) into maximal runs that one hipGraph can stand for -- main-stream kernels whose
-        argument blocks do not change between replays -- and the ops in between (event record / wait, side-stream work,
-        volatile ops), which stay plain launches in program order.  Graphs are captured here, once per range."""
+        """Cut ops [start, start + count) into maximal runs that one hipGraph can stand for -- ops whose argument blocks do
+        not change between replays -- and the volatile ops in between, which stay plain launches in program order.  Side-stream
+        ops and event record / wait do not cut: the executor joins every range at its end (include/dfl_hip.h, "Side
+        streams"), so a run is one forked graph.  Graphs are captured here, once per range."""
         n = len(self.structs) - start if count is None else count
         key = (start, n)
         chunks = self._chunks.get(key)
         if chunks is None:
             chunks, i, end = [], start, start + n
             while i < end:
-                plain = self.kinds[i] in (OP_RECORD, OP_WAIT) or self.streams[i] != 0 or self.volatile[i]
+                plain = self.volatile[i]
                 j = i + 1
-                while j < end and (self.kinds[j] in (OP_RECORD, OP_WAIT) or self.streams[j] != 0 or self.volatile[j]) == plain:
+                while j < end and self.volatile[j] == plain:
                     j += 1
-                if not plain and j - i >= self.MIN_GRAPH_OPS:
+                if not plain and sum(1 for k in self.kinds[i:j] if k not in (OP_RECORD, OP_WAIT)) >= self.MIN_GRAPH_OPS:
                     chunks.append((i, j - i, self.capture(stream, i, j - i)))
                 else:
                     chunks.append((i, j - i, None))

@@ -101,16 +101,81 @@ extern "C" int dfl_sizeof(int which) {
 
 static int exec_one(const dfl_op* ops, int i, dfl_stream_t stream, bool serial);
 
+namespace dfl {
+// Fork / join events of exec_range, one pair per side stream (created with the stream's first use).
+static hipEvent_t g_fork_ev[DFL_MAX_SIDE_STREAMS] = {nullptr};
+static hipEvent_t g_join_ev[DFL_MAX_SIDE_STREAMS] = {nullptr};
+
+static bool range_events(int id) {
+  std::lock_guard<std::mutex> lk(g_sync_mu);
+  if (g_fork_ev[id] == nullptr && hipEventCreateWithFlags(&g_fork_ev[id], hipEventDisableTiming) != hipSuccess) return false;
+  if (g_join_ev[id] == nullptr && hipEventCreateWithFlags(&g_join_ev[id], hipEventDisableTiming) != hipSuccess) return false;
+  return true;
+}
+}  // namespace dfl
+
+// One range of a program with its side streams (include/dfl_hip.h, "Side streams"): the same walk for the op-by-op replay
+// (dfl_exec) and under stream capture (dfl_graph_capture), where the side streams join the capture through their first
+// wait and leave it through the join at the end -- so a range is a closed sub-graph either way.
+static int exec_range(const dfl_op* ops, int n_ops, hipStream_t main) {
+  bool used[DFL_MAX_SIDE_STREAMS] = {false};
+  std::vector<bool> recorded;                      // events recorded inside this range
+  int rc = DFL_OK;
+  for (int i = 0; i < n_ops && rc == DFL_OK; ++i) {
+    const int sid = ops[i].stream;
+    if (sid < 0 || sid > DFL_MAX_SIDE_STREAMS) {
+      dfl::set_error("dfl_exec: op %d names stream %d (0..%d)", i, sid, DFL_MAX_SIDE_STREAMS);
+      rc = DFL_ERR_INVALID_ARG;
+      break;
+    }
+    if (sid != 0 && !used[sid - 1]) {
+      // first op of this side stream in the range: behind everything the caller's stream holds so far
+      hipStream_t side = dfl::pick_stream(sid, main);
+      if (side == nullptr || !dfl::range_events(sid - 1) || hipEventRecord(dfl::g_fork_ev[sid - 1], main) != hipSuccess ||
+          hipStreamWaitEvent(side, dfl::g_fork_ev[sid - 1], 0) != hipSuccess) {
+        dfl::set_error("dfl_exec: cannot fork side stream %d (op %d)", sid, i);
+        rc = DFL_ERR_LAUNCH;
+        break;
+      }
+      used[sid - 1] = true;
+    }
+    if (ops[i].kind == DFL_OP_RECORD || ops[i].kind == DFL_OP_WAIT) {
+      const int ev = ops[i].args != nullptr ? static_cast<const dfl_sync_args*>(ops[i].args)->event : -1;
+      if (ev < 0 || ev >= 65536) {
+        dfl::set_error("dfl_exec: op %d names event %d (0..65535)", i, ev);
+        rc = DFL_ERR_INVALID_ARG;
+        break;
+      }
+      if (ops[i].kind == DFL_OP_RECORD) {
+        if ((int)recorded.size() <= ev) recorded.resize(ev + 1, false);
+        recorded[ev] = true;
+      } else if (ev >= (int)recorded.size() || !recorded[ev]) {
+        continue;   // recorded in an earlier range: that range was joined at its end, which orders more than this wait asks
+      }
+    }
+    rc = exec_one(ops, i, static_cast<dfl_stream_t>(main), false);
+  }
+  // the join: the caller's stream waits for every side stream used, also after a failed op (a capture must end whole)
+  for (int k = 0; k < DFL_MAX_SIDE_STREAMS; ++k) {
+    if (!used[k]) continue;
+    hipStream_t side = dfl::pick_stream(k + 1, main);
+    if (side == nullptr || hipEventRecord(dfl::g_join_ev[k], side) != hipSuccess ||
+        hipStreamWaitEvent(main, dfl::g_join_ev[k], 0) != hipSuccess) {
+      if (rc == DFL_OK) {
+        dfl::set_error("dfl_exec: cannot join side stream %d", k + 1);
+        rc = DFL_ERR_LAUNCH;
+      }
+    }
+  }
+  return rc;
+}
+
 extern "C" int dfl_exec(const dfl_op* ops, int32_t n_ops, dfl_stream_t stream) {
   if (ops == nullptr || n_ops < 0) {
     dfl::set_error("dfl_exec: bad arguments");
     return DFL_ERR_INVALID_ARG;
   }
-  for (int i = 0; i < n_ops; ++i) {
-    int rc = exec_one(ops, i, stream, false);
-    if (rc != DFL_OK) return rc;
-  }
-  return DFL_OK;
+  return exec_range(ops, n_ops, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int dfl_exec_timed(const dfl_op* ops, int32_t n_ops, dfl_stream_t stream, float* ms_out) {
@@ -166,8 +231,8 @@ extern "C" int dfl_graph_capture(const dfl_op* ops, int32_t n_ops, dfl_stream_t 
     dfl::set_error("dfl_graph_capture: hipStreamBeginCapture: %s", hipGetErrorString(err));
     return DFL_ERR_LAUNCH;
   }
-  int rc = DFL_OK;
-  for (int i = 0; i < n_ops && rc == DFL_OK; ++i) rc = exec_one(ops, i, static_cast<dfl_stream_t>(s), true);
+  // forks and joins are captured as they are: side-stream ops become parallel branches of the one graph, joined at its end
+  int rc = exec_range(ops, n_ops, s);
   hipGraph_t g = nullptr;
   err = hipStreamEndCapture(s, &g);   // always end the capture, also after a failed op
   (void)hipStreamDestroy(s);

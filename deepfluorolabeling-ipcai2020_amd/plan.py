@@ -51,6 +51,72 @@ class PlanError(RuntimeError):
     pass
 
 
+def _span(a):
+    """Bytes an op touches through Act a: (first, end, row pitch, row width), pitch 0 = one dense run."""
+    pitch, width = a.ld * a.esz, a.C * a.esz
+    return (a.ptr, a.ptr + (a.M - 1) * pitch + width, pitch if width < pitch else 0, width)
+
+
+def _flat(ptr, nbytes):
+    return (int(ptr), int(ptr) + int(nbytes), 0, int(nbytes))
+
+
+def _spans_meet(a, b):
+    if a[0] >= b[1] or b[0] >= a[1]:
+        return False
+    if a[2] and a[2] == b[2]:                      # two channel windows of rows with one pitch (the halves of a concat buffer)
+        off = (a[0] - b[0]) % a[2]
+        return off < b[3] or off + a[3] > a[2]
+    return True
+
+
+class _Fork:
+    """Dependency tracker of a forked program: ops of the main chain on stream 0, branch ops on one side stream.
+
+    A branch op starts behind the main chain as it stands where the op is emitted (RECORD on the main chain, WAIT on the
+    branch): it sees what the serial program showed it, so only the other direction needs bookkeeping.  Every branch op is
+    followed by a RECORD of its own; a later main-chain op that writes what a pending branch op reads or writes, or reads
+    what it writes, is given a WAIT for that op's event (and with it for every earlier branch op: one stream).  A main-chain
+    op whose accesses are not declared (reads is None) waits for the whole branch.  Spans are (first, end, pitch, width)."""
+    BRANCH = 1
+
+    def __init__(self, prog):
+        self.prog = prog
+        self.pending = []           # (event, reads, writes) of the branch ops the main chain is not ordered behind, oldest first
+        self.events = 0
+        self.at_main = None         # event recorded behind the main chain's latest op
+        self.seen = 0               # ops emitted through the tracker
+        self.waits = 0              # WAITs given to the main chain
+
+    def main(self, reads, writes):
+        """In front of a main-chain op."""
+        hit = -1
+        for k, (_, r, w) in enumerate(self.pending):
+            if reads is None or any(_spans_meet(x, y) for x in writes for y in r + w) or any(_spans_meet(x, y) for x in reads for y in w):
+                hit = k
+        if hit >= 0:
+            self.prog.wait(self.pending[hit][0], 0)
+            self.waits += 1
+            del self.pending[:hit + 1]
+        self.at_main = None
+        self.seen += 1
+
+    def fork(self):
+        """In front of a branch op."""
+        if self.at_main is None:
+            self.at_main = self.events
+            self.events += 1
+            self.prog.record(self.at_main, 0)
+            self.prog.wait(self.at_main, self.BRANCH)
+        self.seen += 1
+
+    def forked(self, reads, writes):
+        """Behind the branch op just added."""
+        self.prog.record(self.events, self.BRANCH)
+        self.pending.append((self.events, list(reads), list(writes)))
+        self.events += 1
+
+
 # Diagnosis (tests/test_gpu_bf16_stepwise.py): plans built while this is True give every activation gradient its own buffer
 # instead of the three shared scratch tensors, so that all of them can be read after a backward pass (UNetPlan.dbg names them).
 KEEP_GRADS = False
@@ -90,6 +156,10 @@ class UNetPlan:
     DPRE_OUT_BYTES = int(float(os.environ.get('DFL_DPRE_OUT_MB', '12')) * (1 << 20))   # data gradient also writes the operand it forms up to this size
     LIVE_BN = os.environ.get('DFL_LIVE_BN', '1') != '0'           # BatchNorm statistics completed by their consumers (live totals)
     LIVE_HEAD = os.environ.get('DFL_LIVE_HEAD', '1') != '0'       # ... and the head's backward kernel adds the sums of its dx itself (no colstats pass)
+    # Forked backward: weight gradients and the batched sums run on a branch (dfl_op.stream 1) beside the data-gradient chain,
+    # ordered by the _Fork tracker; 0 = the serial program, op for op what it was before the fork existed (tests flip FORK)
+    FORK = os.environ.get('DFL_FORK', '1') != '0'
+    FORK_RING = max(1, int(os.environ.get('DFL_FORK_RING', '2')))   # slots per backward scratch tensor of a forked program
     BN_R = nat.BN_R
 
     def __init__(self, cfg, params, buffers, N, H, W, training, need_grad, device, input_grad=False):
@@ -133,6 +203,9 @@ class UNetPlan:
         # inference plans ask for the latency form of the bf16 convolution (include/dfl_hip.h: a hint the library honours for the
         # small problems of a batch-1 forward -- the per-image loops of util.py -- and ignores for everything else)
         self._latency_form = int(not training and not need_grad and os.environ.get('DFL_PLAN_LATENCY_FORM', '1') != '0')
+        self._deps = _Fork(self.bwd) if (self.FORK and need_grad) else None      # the forward and the inference plans stay serial
+        self._rings = {}                # backward scratch key -> [slots, next turn] (forked programs)
+        self.host_jobs = {}             # device address of an uploaded job array -> the ctypes array (hazard checks read it)
         self._build()
 
     # ------------------------------------------------------------------------------------------ memory
@@ -163,7 +236,20 @@ class UNetPlan:
             raise PlanError('scratch %s not sized' % key)
         if self.keep_grads:
             return self._act(N, H, W, C)
+        if self._deps is not None:
+            # forked program: a branch op (weight gradient) still reads the tensor handed out here when the main chain asks for
+            # this key again -- it gets the next slot of a ring, so the WAIT the tracker gives its writer is for a branch op that is
+            # FORK_RING uses back and has long finished: ordered by slack, not by a stall
+            ring = self._rings.setdefault(key, [[t], 0])
+            if len(ring[0]) < self.FORK_RING and ring[1] >= len(ring[0]):
+                ring[0].append(self._new(t.numel(), t.dtype))
+            t = ring[0][ring[1] % len(ring[0])]
+            ring[1] = (ring[1] + 1) % self.FORK_RING
         return Act(t, t.data_ptr(), C, N, H, W, C, self.aesz)
+
+    def _is_scratch(self, t, key):
+        """t is (a ring slot of) the backward scratch tensor `key`."""
+        return t is self._scratch.get(key) or any(t is s for s in self._rings.get(key, [[]])[0])
 
     # ------------------------------------------------------------------------------------------ weights
     def _pack(self, w, kind, flip=0):
@@ -213,7 +299,27 @@ class UNetPlan:
         """Address of a device copy of the ctypes array arr, kept alive by the plan."""
         t = torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(self.dev)
         self._keep.append(t)
+        self.host_jobs[t.data_ptr()] = arr
         return t.data_ptr()
+
+    def _emit(self, prog, a, reads=None, writes=None, branch=False, **kw):
+        """Add op a to prog and return its index.  In a forked backward program the op goes through the dependency tracker
+        with the spans it reads and writes (_span / _flat): on the branch if asked, else on the main chain, behind a WAIT for
+        whatever pending branch op it conflicts with -- for all of them if it declares nothing."""
+        dep = self._deps if prog is self.bwd else None
+        if dep is None:
+            prog.add(a, **kw)
+        elif branch:
+            assert reads is not None and writes is not None, 'a branch op declares what it touches'
+            dep.fork()
+            prog.add(a, stream=dep.BRANCH, **kw)
+            idx = len(prog) - 1
+            dep.forked(reads or [], writes or [])
+            return idx
+        else:
+            dep.main(reads, writes)
+            prog.add(a, **kw)
+        return len(prog) - 1
 
     def _finish_pack(self):
         """The pack program: the eval-mode BatchNorm prep of an inference plan, then the weight re-layouts."""
@@ -336,7 +442,20 @@ class UNetPlan:
             if stat_other is not None:
                 a.stat_other, a.ldso = stat_other.ptr, stat_other.ld
             partials = (partials, 4 * gm if scatter else gm)    # scatter2x2: rows = (row block, 2x2 position), Ntot / 4 columns
-        prog.add(a)
+        if prog is self.bwd and self._deps is not None:
+            reads = [_span(t) for t in (x, add, stat_other, brb[0] if brb is not None else None) if t is not None]
+            if accumulate:
+                reads.append(_span(y))
+            writes = [_span(y)] + ([_span(x_out)] if (brb is not None and x_out is not None) else [])
+            if a.partial:
+                writes.append(_flat(a.partial, 4 * a.splits * x.N * (x.H * x.W if scatter else a.Hout * a.Wout) * Ntot))
+            if a.stat_partials:
+                writes.append(_flat(a.stat_partials, 4 * partials[0].numel()))
+            if a.stat_totals:
+                writes.append(_flat(a.stat_totals, 8 * self.BN_R * 2 * (Ntot // 4 if scatter else Ntot)))
+            self._emit(prog, a, reads, writes)
+        else:
+            prog.add(a)
         return partials
 
     def _wgrad(self, prog, g, d, dw, KH, KW, stride, pad, Hout, Wout, in_aff=None, d_split=0, brb=None,
@@ -375,7 +494,21 @@ class UNetPlan:
             big = 4 * n >= self.FLUSH_BYTES
             part = self._shared_scratch('wg_partial', s * n) if big else self._new(s * n)   # deferred sums keep their own slices
             a.partial = part.data_ptr()
-        prog.add(a)
+        if prog is self.bwd and self._deps is not None:
+            # on the branch: nothing on the main chain consumes a weight gradient (the sums that finish it follow it there)
+            reads = [_span(g), _flat(d.t.data_ptr(), d.t.numel() * d.t.element_size()) if d_split else _span(d)]
+            if brb is not None:
+                reads.append(_span(brb[0]))
+                if isinstance(brb[1], dict):
+                    reads.append(_flat(brb[1]['tot'], 8 * self.BN_R * 2 * d.C))
+                elif brb[1] is not None:
+                    reads.append(_flat(brb[1].data_ptr(), 4 * brb[1].numel()))
+            writes = [_flat(a.partial, 4 * s * n) if s > 1 else _flat(a.dw, 4 * n)]
+            if a.bias_partial:
+                writes.append(_flat(a.bias_partial, 4 * s * d.C))
+            self._emit(prog, a, reads, writes, branch=True)
+        else:
+            prog.add(a)
         if bias_job is not None:
             self._red_pending.append(bias_job)
             self._red_bytes += 4 * d.C
@@ -403,16 +536,19 @@ class UNetPlan:
         for a, (src, dst, n, stride, count, T) in zip(arr, jobs):
             a.src, a.dst, a.n, a.stride, a.count, a.first_block, a.T = src, dst, n, stride, count, blocks, T
             blocks += nat.check(self.lib.dfl_reduce_job_blocks(n, count), 'dfl_reduce_job_blocks')
-        self._red_flushes.append((len(prog.structs), [j[1] for j in jobs]))
         self.partial_sum_bytes += sum(4 * n * count for (_, _, n, _, count, _) in jobs)
-        prog.add(ReduceBatchArgs(jobs_dev=self._upload(arr), njobs=len(jobs), total_blocks=blocks))
+        # (on the branch of a forked program: behind the weight gradients whose slices it sums, and nothing on the main chain reads a sum)
+        idx = self._emit(prog, ReduceBatchArgs(jobs_dev=self._upload(arr), njobs=len(jobs), total_blocks=blocks),
+                         [_flat(src, 4 * ((count - 1) * stride + n)) for (src, _, n, stride, count, _) in jobs],
+                         [_flat(dst, 4 * n) for (_, dst, n, _, _, _) in jobs], branch=True)
+        self._red_flushes.append((idx, [j[1] for j in jobs]))
         self._red_pending, self._red_bytes = [], 0
 
     def _dz_for(self, g, N, H, W, Cc, fused):
         """Scratch for the data gradient a layer hands to the layer below.  With the BatchNorm + ReLU backward folded into the
         data-gradient kernel that kernel READS the incoming gradient g while it writes: never the same buffer -- 'dz' and 'dpre0'
         (idle in that mode) alternate."""
-        key = 'dpre0' if fused and g.t is self._scratch.get('dz') else 'dz'
+        key = 'dpre0' if fused and self._is_scratch(g.t, 'dz') else 'dz'
         return self._scratch_act(key, N, H, W, Cc)
 
     def _bn_totals(self, Cc, bwd=False):
@@ -437,8 +573,12 @@ class UNetPlan:
             a.totals, a.save_mean, a.save_invstd = j['tot'], j['mean'].data_ptr(), j['invstd'].data_ptr()
             a.dgamma, a.dbeta, a.sum_out, a.C = j['dgamma'].data_ptr(), j['dbeta'].data_ptr(), nat.ptr(j['sum_out']), j['C']
         dsts = [j[k].data_ptr() for j in jobs for k in ('dgamma', 'dbeta', 'sum_out') if j[k] is not None]
-        self._red_flushes.append((len(prog.structs), dsts))
-        prog.add(BnBwdLiveArgs(jobs_dev=self._upload(arr), njobs=len(jobs), max_C=max(j['C'] for j in jobs)))
+        reads = [_flat(j['tot'], 8 * self.BN_R * 2 * j['C']) for j in jobs]
+        reads += [_flat(j[k].data_ptr(), 4 * j['C']) for j in jobs for k in ('mean', 'invstd')]
+        idx = self._emit(prog, BnBwdLiveArgs(jobs_dev=self._upload(arr), njobs=len(jobs), max_C=max(j['C'] for j in jobs)),
+                         reads, [_flat(j[k].data_ptr(), 4 * j['C']) for j in jobs for k in ('dgamma', 'dbeta', 'sum_out') if j[k] is not None],
+                         branch=True)
+        self._red_flushes.append((idx, dsts))
         self._live_bwd_pending = []
 
     def _finish_live_bn(self):
@@ -468,8 +608,8 @@ class UNetPlan:
         """out[c] = sum over pixels of a[:, c]."""
         nb = self.lib.dfl_rowblock_count(a.M, a.C)
         part = self._new(nb * 2 * a.C)
-        prog.add(ColstatsArgs(a=a.ptr, b=None, partials=part.data_ptr(), M=a.M, C=a.C, lda=a.ld, ldb=0, nblocks=nb,
-                              bf16=a.bf16))
+        self._emit(prog, ColstatsArgs(a=a.ptr, b=None, partials=part.data_ptr(), M=a.M, C=a.C, lda=a.ld, ldb=0, nblocks=nb,
+                                        bf16=a.bf16), [_span(a)], [_flat(part.data_ptr(), 4 * part.numel())])
         self._defer_sum(prog, part.data_ptr(), out.data_ptr(), a.C, 2 * a.C, nb)
 
     # ------------------------------------------------------------------------------------------ circular padding
@@ -493,7 +633,7 @@ class UNetPlan:
         t = self._new(n, torch.bfloat16 if x.esz == 2 else torch.float32)
         xp = Act(t, t.data_ptr(), x.C, x.N, x.H + 2, x.W + 2, x.C, x.esz)
         for sy, sx, dy, dx, h, w in self._wrap_regions(x.H, x.W):
-            prog.add(AffineCopyArgs(x=x.ptr, y=xp.ptr, N=x.N, H=h, W=w, C=x.C, ldx=x.ld, xH=x.H, xW=x.W, xoy=sy, xox=sx,
+            self._emit(prog, AffineCopyArgs(x=x.ptr, y=xp.ptr, N=x.N, H=h, W=w, C=x.C, ldx=x.ld, xH=x.H, xW=x.W, xoy=sy, xox=sx,
                                     ldy=xp.ld, yH=xp.H, yW=xp.W, yoy=dy, yox=dx, bf16=x.bf16))
         return xp
 
@@ -502,7 +642,7 @@ class UNetPlan:
         regs = self._wrap_regions(dx.H, dx.W)
         regs.sort(key=lambda r: 0 if (r[4] == dx.H and r[5] == dx.W) else 1)     # the interior first: it may overwrite
         for i, (sy, sx, dy, dx_, h, w) in enumerate(regs):
-            prog.add(AffineCopyArgs(x=dxp.ptr, y=dx.ptr, N=dx.N, H=h, W=w, C=dx.C, ldx=dxp.ld, xH=dxp.H, xW=dxp.W, xoy=dy, xox=dx_,
+            self._emit(prog, AffineCopyArgs(x=dxp.ptr, y=dx.ptr, N=dx.N, H=h, W=w, C=dx.C, ldx=dxp.ld, xH=dxp.H, xW=dxp.W, xoy=dy, xox=dx_,
                                     ldy=dx.ld, yH=dx.H, yW=dx.W, yoy=sy, yox=sx, accumulate=(accumulate if i == 0 else 1), bf16=dx.bf16))
 
     def _framed_grad(self, like):
@@ -964,7 +1104,7 @@ class UNetPlan:
         else:
             scratch = self._new(M_ * sld)
             hb.scratch = scratch.data_ptr()
-        bwd.add(hb, volatile=True)                 # reads the caller-owned seg / dseg / dheat
+        self._emit(bwd, hb, volatile=True)                 # reads the caller-owned seg / dseg / dheat
         if not fused_head:
             off = [self.lib.dfl_head_scratch_off_for(Fx, NC, nm, nl, k) for k in range(5)]
             sact = lambda o, c: Act(scratch, scratch.data_ptr() + 4 * o, sld, N, H_, W_, c)
@@ -986,7 +1126,7 @@ class UNetPlan:
             # the u columns of the landmark call's dx belong to the centre window of the full-size feature gradient
             dout = dfeat_a
             src_u = dfeat.chan_slice(0, F)
-            bwd.add(AffineCopyArgs(x=src_u.ptr, y=dout.ptr, N=N, H=hl, W=wl, C=F, ldx=src_u.ld, xH=hl, xW=wl, ldy=dout.ld,
+            self._emit(bwd, AffineCopyArgs(x=src_u.ptr, y=dout.ptr, N=N, H=hl, W=wl, C=F, ldx=src_u.ld, xH=hl, xW=wl, ldy=dout.ld,
                                    yH=u.H, yW=u.W, yoy=(u.H - hl) // 2, yox=(u.W - wl) // 2, accumulate=1, bf16=dout.bf16))
         else:
             dout = dfeat.chan_slice(0, F)
@@ -1031,8 +1171,8 @@ class UNetPlan:
             if self.upsample:
                 # gradient of the small-grid 1x1 result = adjoint of the interpolation applied to dy; then an ordinary 1x1 layer
                 dylow = self._act(N, uin.H, uin.W, Ci)
-                bwd.add(UpsampleArgs(x=dylow.ptr, y=dy.ptr, N=N, H=uin.H, W=uin.W, C=Ci, ldx=dylow.ld, ldy=dy.ld, bf16=dy.bf16),
-                        nat.OP_UPSAMPLE_BWD)
+                self._emit(bwd, UpsampleArgs(x=dylow.ptr, y=dy.ptr, N=N, H=uin.H, W=uin.W, C=Ci, ldx=dylow.ld, ldy=dy.ld, bf16=dy.bf16),
+                           kind=nat.OP_UPSAMPLE_BWD)
                 self._wgrad(bwd, uin, dylow, G[rec['name'] + '.up.1.weight'], 1, 1, 1, 0, uin.H, uin.W)
                 sums = self._conv(bwd, dylow, self._pack_conv_dgrad(rec['w']), du, 1, 1, 1, 0, uin.C,
                                   stats=r_last is not None, stat_other=r_last,
@@ -1064,13 +1204,13 @@ class UNetPlan:
                     dout = self._act(N, out.H, out.W, Ci)
                     oy, ox, ch, cw = rec['crop']
                     src = self.dcat[i].chan_slice(Ci, Ci)
-                    bwd.add(MemsetArgs(ptr=dout.ptr, bytes=dout.esz * dout.M * Ci))
-                    bwd.add(AffineCopyArgs(x=src.ptr, y=dout.ptr, N=N, H=ch, W=cw, C=Ci, ldx=src.ld, xH=ch, xW=cw,
+                    self._emit(bwd, MemsetArgs(ptr=dout.ptr, bytes=dout.esz * dout.M * Ci))
+                    self._emit(bwd, AffineCopyArgs(x=src.ptr, y=dout.ptr, N=N, H=ch, W=cw, C=Ci, ldx=src.ld, xH=ch, xW=cw,
                                            ldy=dout.ld, yH=out.H, yW=out.W, yoy=oy, yox=ox, bf16=src.bf16))
                 nxt = rec['nxt']
                 if self.cfg['max_pool']:
-                    bwd.add_pool(PoolArgs(x=out.ptr, y=dnxt.ptr, dx=dout.ptr, N=N, H=out.H, W=out.W, C=Ci, ldx=out.ld,
-                                          ldy=dnxt.ld, lddx=dout.ld, bf16=out.bf16), backward=True)
+                    self._emit(bwd, PoolArgs(x=out.ptr, y=dnxt.ptr, dx=dout.ptr, N=N, H=out.H, W=out.W, C=Ci, ldx=out.ld,
+                                             ldy=dnxt.ld, lddx=dout.ld, bf16=out.bf16), kind=nat.OP_POOL_BWD)
                 else:
                     wname = 'downsample_convs.%d' % i
                     if dnxt_sums is not None:
@@ -1144,18 +1284,21 @@ class UNetPlan:
         if sums is None:
             nb = self.lib.dfl_rowblock_count(r.M, Cout)
             part = self._new(nb * 2 * Cout)
-            bwd.add(ColstatsArgs(a=g.ptr, b=r.ptr, partials=part.data_ptr(), M=r.M, C=Cout, lda=g.ld,
-                                 ldb=r.ld, nblocks=nb, bf16=r.bf16))
+            self._emit(bwd, ColstatsArgs(a=g.ptr, b=r.ptr, partials=part.data_ptr(), M=r.M, C=Cout, lda=g.ld,
+                                         ldb=r.ld, nblocks=nb, bf16=r.bf16),
+                       [_span(g), _span(r)], [_flat(part.data_ptr(), 4 * part.numel())])
             sums = (part, nb)
         part, prow = sums
         coef = self._new(3 * Cout)
         self.dbg['coef:' + cv.relu] = coef
-        bwd.add(BnBwdFinalizeArgs(partials=part.data_ptr(), gamma=gamma.data_ptr(),
+        self._emit(bwd, BnBwdFinalizeArgs(partials=part.data_ptr(), gamma=gamma.data_ptr(),
                                   save_mean=mean.data_ptr(), save_invstd=invstd.data_ptr(),
                                   dgamma=G[bname + '.weight'].data_ptr(),
                                   dbeta=G[bname + '.bias'].data_ptr(), coef=coef.data_ptr(),
                                   count=r.M if self.training else 0,      # 0: fixed (running) statistics
-                                  nblocks=prow, C=Cout))
+                                  nblocks=prow, C=Cout),
+                   [_flat(part.data_ptr(), 4 * part.numel())],
+                   [_flat(coef.data_ptr(), 12 * Cout), _flat(G[bname + '.weight'].data_ptr(), 4 * Cout), _flat(G[bname + '.bias'].data_ptr(), 4 * Cout)])
         if res_bias is not None:
             # residual bias gradient = column sums of dout, already in the same partials
             self._defer_sum(bwd, part.data_ptr(), res_bias.data_ptr(), Cout, 2 * Cout, prow)
@@ -1171,7 +1314,7 @@ class UNetPlan:
         # two dpre buffers alternate: a layer's dpre is never the buffer its incoming gradient lives in (the case when
         # _dz_for handed out 'dpre0' as the data gradient of a fused layer above)
         self._dpre_turn ^= 1
-        if g.t is self._scratch.get('dpre%d' % self._dpre_turn):
+        if self._is_scratch(g.t, 'dpre%d' % self._dpre_turn):
             self._dpre_turn ^= 1
         # BatchNorm + ReLU backward folded into its two consumers (bf16 patch kernels; round 3): the weight-gradient
         # and data-gradient kernels form [r > 0] * (A dy + B r + C) from (dy, r) while they stage their patches --
@@ -1194,9 +1337,13 @@ class UNetPlan:
             # dpre feeds exactly two GEMMs (weight gradient: dense operand; data gradient: gathered operand);
             # with split-bf16 products it is written split once here instead of being split by every tile of both
             dsplit = int(self.math in (1, 3) and Cout % 16 == 0 and inp.C % 4 == 0 and inp.C * 9 > 12)
-            bwd.add(BnReluBwdArgs(dy=g.ptr, r=r.ptr, coef=nat.ptr(coef), dpre=dpre.ptr,
+            self._emit(bwd, BnReluBwdArgs(dy=g.ptr, r=r.ptr, coef=nat.ptr(coef), dpre=dpre.ptr,
                                   partials=bpart.data_ptr(), M=r.M, C=Cout, lddy=g.ld, ldr=r.ld, ldo=dpre.ld,
-                                  nblocks=nb, split_out=dsplit, bf16=r.bf16))
+                                  nblocks=nb, split_out=dsplit, bf16=r.bf16),
+                       [_span(g), _span(r)] + ([_flat(coef.data_ptr(), 12 * Cout)] if coef is not None else []),
+                       # (a split operand is laid out over the whole slot)
+                       [_flat(dpre.t.data_ptr(), dpre.t.numel() * dpre.t.element_size()) if dsplit else _span(dpre),
+                        _flat(bpart.data_ptr(), 4 * bpart.numel())])
             self._defer_sum(bwd, bpart.data_ptr(), G[cv.wname + '.bias'].data_ptr(), Cout, Cout, nb)
         # Small tensors (deep levels: many (cm, cg) tiles, each of which would form the operand again): the data-gradient
         # kernel, which forms it anyway, writes it once (x_out) and the weight gradient -- emitted BEHIND it -- reads it
@@ -1256,6 +1403,10 @@ class UNetPlan:
     def _finish_backward(self):
         """The last batched sums, and the zero fill of the backward totals arena in front of the program."""
         self._flush_sums(self.bwd)
+        if self._deps is not None:
+            # every op of a forked program has passed the tracker (the zero fill below leads the program: in front of every fork)
+            if self._deps.seen != sum(1 for k in self.bwd.kinds if k not in (nat.OP_RECORD, nat.OP_WAIT)):
+                raise PlanError('internal: a backward op was recorded past the dependency tracker')
         if self._tot_bwd[0] is not None:
             self.bwd.insert(0, MemsetArgs(ptr=self._tot_bwd[0].data_ptr(), bytes=8 * self._tot_bwd[1]))
             # every op index recorded while the program was emitted moved up by one (ADVICE r04: the flushes' indices

@@ -347,12 +347,13 @@ class UNet(nn.Module):
         return self.use_graphs and (self.train_graphs or not plan.training)
 
     def run_program(self, plan, prog, stream, start=0, count=None):
-        """Replay (part of) a recorded program.  With graphs on, every run of main-stream kernels with fixed argument blocks
+        """Replay (part of) a recorded program.  With graphs on, every run of ops with fixed argument blocks
         is ONE hipGraph launch (captured on first use): the inference forward up to the heads (BASELINE configs[4]; the
         per-image loops of util.test_dataset / seg_dataset_ensemble replay ~100 small launches per net) and -- round 3 --
         the training forward and backward (~250 launches per step: on a slow host the GPU waited for them).
-        The head ops read / write caller-owned tensors whose addresses change per call, event waits order the side-stream
-        weight packing: both stay plain launches in program order (Program.graph_chunks)."""
+        The head ops read / write caller-owned tensors whose addresses change per call: they stay plain launches in
+        program order (Program.graph_chunks).  Side-stream ops and their events do not cut a graph: the branch of the
+        forked backward is captured as a parallel branch, and every range is joined at its end (include/dfl_hip.h)."""
         if self.graphs_on(plan):
             chunks = prog.graph_chunks(stream, start, count)
             if prog is plan.fwd and plan.graph is None:

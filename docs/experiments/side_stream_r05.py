@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Round 5 re-measurement of the side-stream weight gradients (plan.SIDE_STREAM, off since round 1: measured with the fp32 kernels):
 a layer's weight gradient next to the NEXT layer's data gradient -- the drain of one kernel over the fill of the other -- with the
-bf16 patch kernels.  Training graphs serialise branches, so they are off here.  python docs/experiments/side_stream_r05.py <0|1> [max pixels]"""
+bf16 patch kernels.  Training graphs serialised branches when this was measured, so they are off here (the executor
+has captured forks and joins since the forked backward, docs/experiments/forked_backward/).  python docs/experiments/side_stream_r05.py <0|1> [max pixels]"""
 import os
 import sys
 import time

@@ -1555,8 +1555,24 @@ typedef struct { const dfl_bn_live_job* jobs_dev; int32_t njobs, max_C; } dfl_bn
 typedef struct { const dfl_bn_bwd_live_job* jobs_dev; int32_t njobs, max_C; } dfl_bn_bwd_live_args;
 typedef struct { const dfl_conv_args* a; const dfl_conv_args* b; } dfl_conv_pair_args;   /* dfl_conv2d_pair */
 
-/* DFL_OP_RECORD: record library event `event` on the op's stream; DFL_OP_WAIT: make the op's stream wait for it.
- * Events are library-owned, identified by small integers the program chooses (0..65535). */
+/* Side streams.  An op with stream = 1..DFL_MAX_SIDE_STREAMS runs on a library-owned side stream, beside the ops of the
+ * caller's stream (stream 0).  DFL_OP_RECORD records library event `event` on the op's stream, DFL_OP_WAIT makes the op's
+ * stream wait for it; events are library-owned, identified by small integers the program chooses (0..65535).
+ * What the executor guarantees for every range [ops, ops + n_ops) it is given -- dfl_exec and dfl_graph_capture alike, so a
+ * program means the same replayed op by op, as one hipGraph, or cut into ranges:
+ *   - the first op of a side stream in the range starts behind everything the caller's stream held when that op was reached
+ *     (earlier ops of the range included);
+ *   - at the end of the range, also after a failed op, the caller's stream waits for every side stream the range used: behind
+ *     the call (the graph launch) everything the range enqueued is ordered in front of later work of the caller's stream;
+ *   - ops of one stream run in program order;
+ *   - a DFL_OP_WAIT for an event that no op of THIS range recorded is skipped: the range that recorded it was joined at
+ *     its end, which orders more than the wait asks for.
+ * What a side-stream op may assume: exactly that.  Everything else is the program's job -- a side-stream op that reads what
+ * the caller's stream writes LATER in the range, or writes what it reads or writes later, needs a RECORD behind it and a
+ * WAIT in front of the later op; memory that both sides touch without such a pair is a race.
+ * Under dfl_graph_capture the side streams join the capture (fork) and leave it (join) inside the one graph; no event or
+ * stream call survives as a node.  The side streams and events are process-wide: one thread replays or captures at a time.
+ * dfl_exec_timed ignores streams and events: program order on one stream is a valid schedule of any program. */
 typedef struct { int32_t event; int32_t reserved; } dfl_sync_args;
 #define DFL_MAX_SIDE_STREAMS 2
 
@@ -1574,8 +1590,8 @@ int dfl_exec(const dfl_op* ops, int32_t n_ops, dfl_stream_t stream);
 int dfl_exec_timed(const dfl_op* ops, int32_t n_ops, dfl_stream_t stream, float* ms_out);
 
 /* hipGraph form of a program (BASELINE configs[4]: "test_ensemble.py 5-model ensemble, hipGraph-captured"; the reference
- * enqueues every torch op of UNet.forward one by one, util.py:318-373).  dfl_graph_capture records the ops -- in program
- * order on one stream, side-stream annotations ignored, which is a valid schedule of any program -- into a hipGraph by
+ * enqueues every torch op of UNet.forward one by one, util.py:318-373).  dfl_graph_capture records the ops -- side-stream
+ * ops as parallel branches, forked and joined as "Side streams" above says -- into a hipGraph by
  * stream capture on a private stream (nothing executes; `stream` is accepted for symmetry and unused: callers usually
  * sit on the null stream, which cannot capture) and instantiates it; dfl_graph_launch replays it on any stream.  The argument structs are
  * consumed at capture time: pointers and sizes are frozen into the graph, memory CONTENTS are read at replay.  The
