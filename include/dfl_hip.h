@@ -722,6 +722,48 @@ int dfl_hard_dice(const unsigned char* est, const unsigned char* gt, int64_t pix
                   int64_t* counts, double* dice, dfl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Clean-up of predicted label maps: connected components per value, selection, and a dilated bone mask.
+ * (The reference has no counterpart: its tools take 'nn-segs' as the arg-max left it; the usual remedy is a round trip
+ * through scipy.ndimage on the host.)  Label maps are segs [B][H][W] of unsigned char, as test_ensemble.py writes them.
+ * The FLAT INDEX of a pixel is row * W + col within its image (int32): H * W < 2^31 is required and checked before
+ * anything else, offsets across the batch are 64-bit.  Plain library calls, not dfl_exec ops.
+ *
+ * dfl_label_components: root[p] = the smallest flat index among the pixels connected to p through pixels of the same byte
+ * value (connectivity 4 or 8; every value is a label, 0 included; nothing connects across images) -- canonical, so the
+ * result depends on no tile size, schedule or arrival order.  area[p] = pixels of the component at its root pixel, 0
+ * elsewhere.  info[p] at a root: bit 31 = the component touches the image border; bits 0..30 = the union of
+ * 1 << min(v, 30) over the values v of the 4-neighbours of the component's pixels that lie outside the component; 0
+ * elsewhere.  Three launches whatever the data (csrc/labels.hip): union-find per DFL_LABEL_TILE_H x DFL_LABEL_TILE_W tile
+ * in LDS, unions across tile borders in global memory, then flattening with area and info; integer atomics only.
+ *
+ * dfl_label_select: one pass over (segs, root, area, info) of dfl_label_components, one of two jobs.
+ *   remove (fill_below == 0): for the labels l = 1..num_classes-1 a component is kept when area >= min_area and, with
+ *     keep == 1, when it is the largest component of its label in its image (ties: the smallest root); pixels of the other
+ *     components become 0; value 0 and values >= num_classes are copied through.  (keep == 0 keeps every component.)
+ *   fill (fill_below > 0): a component of value 0 that does not touch the border, has area <= fill_below and whose
+ *     neighbour set (info) is exactly one label l with 1 <= l < min(num_classes, 30) becomes l (bit 30 of info stands for
+ *     "30 or more" and is never filled from); everything else is copied through.
+ * counts (or NULL) [B][num_classes][2] = (pixels removed of label l, pixels filled with label l) per image.  scratch:
+ * dfl_label_select_scratch_bytes(B, num_classes) bytes, 8-byte aligned: per (image, label) the 64-bit slot where the
+ * components of a label meet (atomic max of (area << 32) | ~root, as the arg-max of dfl_est_lands meets in rowcol).
+ *
+ * dfl_label_dilate: mask[p] = 1 when some pixel q of the same image with (drow)^2 + (dcol)^2 <= radius^2 has a value v < 32
+ * with bit v of label_set set, else 0 (pixels outside the image do not count; radius 0..DFL_LABEL_MAX_RADIUS).
+ * ------------------------------------------------------------------------------------------------------------ */
+#define DFL_LABEL_TILE_H 32
+#define DFL_LABEL_TILE_W 64
+#define DFL_LABEL_MAX_CLASSES 31
+#define DFL_LABEL_MAX_RADIUS 32
+int dfl_label_components(const unsigned char* segs, int32_t B, int32_t H, int32_t W, int32_t connectivity, int32_t* root,
+                         int32_t* area, uint32_t* info, dfl_stream_t stream);
+int dfl_label_select_scratch_bytes(int32_t B, int32_t num_classes);
+int dfl_label_select(const unsigned char* segs, const int32_t* root, const int32_t* area, const uint32_t* info, int32_t B,
+                     int32_t H, int32_t W, int32_t num_classes, int32_t keep, int32_t min_area, int32_t fill_below,
+                     unsigned char* out, int32_t* counts, void* scratch, dfl_stream_t stream);
+int dfl_label_dilate(const unsigned char* segs, int32_t B, int32_t H, int32_t W, uint32_t label_set, int32_t radius,
+                     unsigned char* mask, dfl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Result overlays (overlay_est_ann.py, overlay_est_heat.py, examples_dataset/make_preproc_overlays.py of the reference):
  * uint8 RGB for a batch of B fp32 images, two launches.  Phase 1: per-image min / max of the image (and of the heat map).
  * Phase 2, per pixel, every fp32 operation rounded on its own (built with -ffp-contract=off):
