@@ -487,42 +487,42 @@ __global__ void __launch_bounds__(WM* WN * 64 * WS, wg_occ(TM* TN* TPB, FAST)) w
   }
 }
 
-// i walks the slices' order ([T][R]); the sum lands at [R][T]
+// i walks the slices' order ([T][R]); the sum lands at [R][T].  Accumulated in fp64 and rounded once, as dfl_reduce_batch does.
 __global__ void sum_partials_kernel(const float* __restrict__ src, float* __restrict__ dst, int64_t n, int splits,
                                     int T) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const int64_t R = n / T;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    float s = 0.f;
-    for (int k = 0; k < splits; ++k) s += src[(int64_t)k * n + i];
-    dst[T > 1 ? (i % R) * T + i / R : i] = s;
+    double s = 0.0;
+    for (int k = 0; k < splits; ++k) s += (double)src[(int64_t)k * n + i];
+    dst[T > 1 ? (i % R) * T + i / R : i] = (float)s;
   }
 }
 
 // Many slices of a small tensor (narrow layers cut the pixel range into ~1000 slices): 16 outputs x 16 slice lanes per
-// workgroup, 8 independent loads in flight per thread, LDS tree over the lanes.  Same summation order every run.
+// workgroup, 8 independent loads in flight per thread, LDS tree over the lanes.  Same summation order every run, fp64.
 __global__ void __launch_bounds__(256) sum_partials_wide_kernel(const float* __restrict__ src, float* __restrict__ dst,
                                                                 int64_t n, int splits, int T) {
-  __shared__ float red[16][17];
+  __shared__ double red[16][17];
   const int o = threadIdx.x & 15, sl = threadIdx.x >> 4;
   const int64_t i = (int64_t)blockIdx.x * 16 + o;
-  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   if (i < n) {
     int k = sl;
     for (; k + 7 * 16 < splits; k += 8 * 16) {
 #pragma unroll
-      for (int u = 0; u < 8; ++u) acc[u] += src[(int64_t)(k + u * 16) * n + i];
+      for (int u = 0; u < 8; ++u) acc[u] += (double)src[(int64_t)(k + u * 16) * n + i];
     }
-    for (; k < splits; k += 16) acc[0] += src[(int64_t)k * n + i];
+    for (; k < splits; k += 16) acc[0] += (double)src[(int64_t)k * n + i];
   }
   red[sl][o] = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
   __syncthreads();
   if (sl == 0 && i < n) {
-    float s = 0.f;
+    double s = 0.0;
 #pragma unroll
     for (int j = 0; j < 16; ++j) s += red[j][o];
     const int64_t R = n / T;
-    dst[T > 1 ? (i % R) * T + i / R : i] = s;
+    dst[T > 1 ? (i % R) * T + i / R : i] = (float)s;
   }
 }
 

@@ -243,7 +243,8 @@ int dfl_conv2d_wgrad(const dfl_wgrad_args* a, dfl_stream_t stream);
 /* Suggested number of splits for a problem (>= 1); the caller sizes `partial` from it. */
 int dfl_wgrad_suggest_splits(const dfl_wgrad_args* a);
 
-/* dst[r*T + t] = sum_{s < splits} src[s*n + t*(n/T) + r],  r < n/T, t < T  (T = 1: plain sum of slices). */
+/* dst[r*T + t] = sum_{s < splits} src[s*n + t*(n/T) + r],  r < n/T, t < T  (T = 1: plain sum of slices); fp64 accumulation
+ * in a fixed order, rounded to fp32 once. */
 int dfl_sum_partials(const float* src, float* dst, int64_t n, int32_t splits, int32_t T, dfl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
