@@ -750,6 +750,38 @@ int dfl_hard_dice(const unsigned char* est, const unsigned char* gt, int64_t pix
  *
  * dfl_label_dilate: mask[p] = 1 when some pixel q of the same image with (drow)^2 + (dcol)^2 <= radius^2 has a value v < 32
  * with bit v of label_set set, else 0 (pixels outside the image do not count; radius 0..DFL_LABEL_MAX_RADIUS).
+ *
+ * Boundary distances (csrc/labels_dist.hip; restated in numpy by tests/surface_ref.py).
+ * A LABEL SET is a 32-bit word as in dfl_label_dilate: value v < 32 is in the set when bit v is set, values >= 32 never.
+ * The SITES of a set in an image: with boundary == 0 all pixels whose value is in the set; with boundary == 1 the in-set
+ * pixels that have a 4-neighbour not in the set or lie on the image border (a neighbour outside the image is "not in the
+ * set"): mask & ~binary_erosion(mask, 4-neighbourhood, border_value=0), the usual convention.
+ *
+ * dfl_label_edt: dist2[b][s][p] = the minimum of drow^2 + dcol^2 over the sites q of label_sets[s] in image b: the exact
+ * squared Euclidean distance transform, int32.  DFL_LABEL_EDT_NONE everywhere in an image that has no site of that set;
+ * nothing reaches across images.  (H-1)^2 + (W-1)^2 < 2^31 - 1 is required and checked before anything else.  label_sets
+ * is HOST memory, [S], S = 1..DFL_LABEL_MAX_CLASSES.  rowdist is scratch of B * S * (H * W + 1) int32: per row the squared
+ * horizontal distance to the nearest site of that row, then one "has a site" word per (image, set).  Three launches
+ * whatever the data: the has-a-site words cleared, pass 1 along the rows (a wave per row, ballots; integer atomics
+ * for the has-a-site words), pass 2 down the columns (min over r' of (r - r')^2 + rowdist[r'][c], a scan outwards from r
+ * that ends once k^2 >= the best so far).
+ *
+ * Surface distances of label l = 1..num_classes-1 in image b: E = the boundary sites of {l} in est, G = those in gt;
+ * direction 0 is the multiset { sqrt(dist2_gt[b][l-1][p]) : p in E }, direction 1 { sqrt(dist2_est[b][l-1][p]) : p in G },
+ * where dist2_gt = dfl_label_edt(gt, sets {1}..{num_classes-1}, boundary 1) and dist2_est the same of est.
+ *
+ * dfl_label_surface_stats: n, max2 (int32) and sum (double), each [B][num_classes-1][2]: per direction the number of boundary
+ * pixels, the largest squared distance and the sum of sqrt(squared distance) added in a fixed order (csrc/fixed_sum.h: one
+ * record per workgroup, records in index order, no float atomics: two runs give the same bits).  Where either n of a
+ * (b, l) is 0, max2 and sum of that (b, l) are 0.  The boundary test is recomputed from est / gt; no boundary map is stored.
+ *
+ * dfl_label_surface_select: kth2[b][l-1][j] = the squared distance of 0-based rank ranks[b][l-1][j] (device memory) in the
+ * ascending union of both directions of (b, l); -1 for a rank < 0 or >= the size of the union.  Radix select on the int32
+ * keys, four passes of 8 bits, each one scan of the maps: 256-bin histograms per (b, l, j) in LDS, added with integer
+ * atomics, one prefix step between passes.  Integers only: the result cannot depend on arrival order.
+ *
+ * scratch of both: dfl_label_surface_scratch_bytes(B, H, W, num_classes) bytes, 8-byte aligned (the larger of the per-workgroup
+ * records of the sums and the histograms with the state of the select).
  * ------------------------------------------------------------------------------------------------------------ */
 #define DFL_LABEL_TILE_H 32
 #define DFL_LABEL_TILE_W 64
@@ -763,6 +795,16 @@ int dfl_label_select(const unsigned char* segs, const int32_t* root, const int32
                      unsigned char* out, int32_t* counts, void* scratch, dfl_stream_t stream);
 int dfl_label_dilate(const unsigned char* segs, int32_t B, int32_t H, int32_t W, uint32_t label_set, int32_t radius,
                      unsigned char* mask, dfl_stream_t stream);
+#define DFL_LABEL_EDT_NONE 2147483647
+int dfl_label_edt(const unsigned char* segs, int32_t B, int32_t H, int32_t W, const uint32_t* label_sets, int32_t S,
+                  int32_t boundary, int32_t* rowdist, int32_t* dist2, dfl_stream_t stream);
+int dfl_label_surface_scratch_bytes(int32_t B, int32_t H, int32_t W, int32_t num_classes);
+int dfl_label_surface_stats(const unsigned char* est, const unsigned char* gt, int32_t B, int32_t H, int32_t W,
+                            int32_t num_classes, const int32_t* dist2_gt, const int32_t* dist2_est, int32_t* n, int32_t* max2,
+                            double* sum, void* scratch, dfl_stream_t stream);
+int dfl_label_surface_select(const unsigned char* est, const unsigned char* gt, int32_t B, int32_t H, int32_t W,
+                             int32_t num_classes, const int32_t* dist2_gt, const int32_t* dist2_est, const int32_t* ranks,
+                             int32_t* kth2, void* scratch, dfl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Result overlays (overlay_est_ann.py, overlay_est_heat.py, examples_dataset/make_preproc_overlays.py of the reference):
