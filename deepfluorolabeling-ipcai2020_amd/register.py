@@ -16,6 +16,9 @@ one render and one launch against a bank of fixed images (SimilarityBank, dfl_si
 lockstep (cma_steps, bfgs_steps, lockstep), and every result has the bytes register() finds for it alone; section 20.
 patch_weight='variance' weighs every patch by the energy of its fixed gradient (dfl_sim_patch_weights) and has an adjoint
 (dfl_sim_patch_eval), so the patch cost can be refined too; section 21 and tests/patch_grad_ref.py.
+similarity='outline' matches the bone outlines of a predicted label map instead of intensities: the exact render writes the
+label map of every candidate, dfl_label_edt their boundary distance maps, and dfl_sim_outline (csrc/sim_outline.hip,
+OutlineSimilarity) the truncated chamfer cost against the segmentation's; section 26 and tests/outline_ref.py.
 
     D(theta) = [[R, centre - R centre + theta[3:]], [0, 1]],  R = exp(rot_unit theta[:3])      (pose_delta)
     P(theta) = D(theta) P0                                   a cam-to-*-vol matrix as in gt-poses
@@ -29,9 +32,10 @@ import torch
 
 from . import _native as nat
 from . import drr, preprocess
+from . import labels as _labels
 
 __all__ = ['se3_exp', 'se3_log', 'pose_delta', 'pose_deltas', 'pose_delta_jacobians', 'pnp', 'cma_es', 'cma_steps', 'CmaResult', 'bfgs', 'bfgs_steps', 'BfgsResult', 'lockstep',
-           'Similarity', 'PatchSimilarity', 'SimilarityBank', 'PatchSimilarityBank', 'fixed_of_array', 'landmark_penalty', 'register',
+           'Similarity', 'PatchSimilarity', 'SimilarityBank', 'PatchSimilarityBank', 'OutlineSimilarity', 'fixed_of_array', 'landmark_penalty', 'register',
            'register_many', 'default_max_views', 'Registration', 'with_pelvis_pose', 'volume_centre']
 
 ROT_UNIT = 0.02
@@ -638,6 +642,75 @@ class PatchSimilarityBank(SimilarityBank):
         self._setup(fixed, masks, views, (radius, stride, min_count, weight))
 
 
+# ---- the outline cost --------------------------------------------------------------------------------------------------
+class OutlineSimilarity:
+    """The outline cost of `views` moving label maps against a fixed label map: the truncated chamfer
+    distance between the boundaries of every label set, 0 .. 1.  segs is uint8 [H, W], or a bank [F, H, W], on the GPU (a
+    cleaned 'nn-segs' row); label_sets is what labels.edt takes (an integer or a flat sequence is ONE set, a sequence of
+    sequences several); cap is the truncation in pixels.  The exact boundary distance maps of segs (dfl_label_edt) are made
+    here, once.
+
+    cost(label_maps [V, H, W] uint8, fixed_of=None) returns a float64 tensor [V] on the device: dfl_label_edt on the views
+    (three launches, into buffers made here) and dfl_sim_outline (two); nothing is read back to the host.  With a bank,
+    fixed_of says which map each view is scored against, as SimilarityBank takes it.  counts [views, S, 2] (int32: nM, nF)
+    and sums [views, S, 2] (float64: a, b) hold the terms of the last call in their first V rows."""
+
+    entry = 'dfl_sim_outline'
+    fixed_of = SimilarityBank.fixed_of
+
+    def __init__(self, segs, label_sets, views=1, cap=32.0):
+        self._bank = torch.is_tensor(segs) and segs.dim() == 3
+        what = 'the segmentations' if self._bank else 'the segmentation'
+        segs = _device_image(segs, what, 3 if self._bank else 2, (torch.uint8,))
+        self.words, _ = _labels._label_sets(label_sets, 'edt (register.OutlineSimilarity)')
+        self.cap, self.views = float(cap), int(views)
+        if not self.cap > 0.0 or not np.isfinite(self.cap):
+            raise nat.DflError('register: an outline cap of %r pixels (finite, positive)' % (cap,))
+        dev, (H, W) = segs.device, (int(s) for s in segs.shape[-2:])
+        self.segs, self.H, self.W, self.S = segs, H, W, len(self.words)
+        self.F, self._fixed_of = (int(segs.shape[0]) if self._bank else 1), {}
+        if segs.numel() == 0 or self.views < 1:
+            raise nat.DflError('register: %s of shape %s for %d views: an empty problem' % (what, tuple(segs.shape), self.views))
+        self.scratch = _scratch(nat.lib().dfl_sim_outline_scratch_doubles(self.views, self.S, H, W), dev, 1)
+        self.d2_fixed = _labels._edt(segs.reshape(self.F, H, W), self.words, True)
+        self.rowdist = torch.empty(self.views * self.S * (H * W + 1), dtype=torch.int32, device=dev)
+        self.d2_moving = torch.empty((self.views, self.S, H, W), dtype=torch.int32, device=dev)
+        self.counts = torch.zeros((self.views, self.S, 2), dtype=torch.int32, device=dev)
+        self.sums = torch.zeros((self.views, self.S, 2), dtype=torch.float64, device=dev)
+        self.out = torch.empty(self.views, dtype=torch.float64, device=dev)
+
+    def args(self, V, fixed_of=None, out=None):
+        """The argument block of dfl_sim_outline for the first V views of d2_moving."""
+        return nat.SimOutlineArgs(d2_moving=self.d2_moving.data_ptr(), d2_fixed=self.d2_fixed.data_ptr(), fixed_of=nat.ptr(fixed_of),
+                                  counts=self.counts.data_ptr(), sums=self.sums.data_ptr(), cost=(self.out if out is None else out).data_ptr(),
+                                  scratch=self.scratch.data_ptr(), scratch_doubles=self.scratch.numel(), cap=self.cap, V=V, F=self.F,
+                                  S=self.S, H=self.H, W=self.W, reserved=0)
+
+    def _moving(self, label_maps):
+        mv = _device_image(label_maps, 'the moving label maps', 3, (torch.uint8,))
+        if tuple(mv.shape[1:]) != (self.H, self.W) or mv.device != self.out.device or not 1 <= mv.shape[0] <= self.views:
+            raise nat.DflError('register: moving label maps of shape %s on %s for a segmentation of %d x %d on %s and at most %d views'
+                               % (tuple(mv.shape), mv.device, self.H, self.W, self.out.device, self.views))
+        return mv
+
+    def _launch(self, label_maps, fixed_of=None, out=None):
+        """The distance maps of checked label maps, then one dfl_sim_outline; the costs go to `out` (default: the first rows
+        of self.out)."""
+        V = int(label_maps.shape[0])
+        if self._bank and fixed_of is not None:                     # None: every view against map 0
+            fixed_of = self.fixed_of(fixed_of, V)
+        elif fixed_of is not None:
+            raise nat.DflError('register: fixed_of belongs to a bank of segmentations [F, H, W]; this one is a single map')
+        _labels._edt(label_maps, self.words, True, self.rowdist, self.d2_moving[:V])
+        drr.launch(label_maps.device, self.entry, self.args(V, fixed_of, out))
+
+    def cost(self, label_maps, fixed_of=None):
+        mv = self._moving(label_maps)
+        out = torch.empty(mv.shape[0], dtype=torch.float64, device=mv.device)
+        self._launch(mv, fixed_of, out)
+        return out
+
+
 # ---- the landmark term -------------------------------------------------------------------------------------------------
 def _usable_landmarks(X3d, x2d, who):
     X = np.asarray(X3d, np.float64)
@@ -729,6 +802,49 @@ class _Level:
         return torch.cat([cost[:, None], grad.reshape(recs.shape[0], -1)], 1).cpu().numpy(), piv    # the copy waits for every launch
 
 
+class _OutlineLevel(_Level):
+    """_Level for similarity='outline': the views are the label maps of one exact render with tight boxes, the similarity
+    an OutlineSimilarity against the segmentation; costs() is _Level's."""
+
+    def __init__(self, volume, grid, segmentation, sets, cap, lam, step_mm):
+        self.volume, self.grid, self.lam, self.step_mm = volume, grid, lam, float(step_mm)
+        self.sim = OutlineSimilarity(segmentation, sets, lam, cap)
+
+    def _render(self, c2is, masks):
+        """(records, label_map [views, H, W] uint8, tensors to keep alive until the render ran)"""
+        recs = drr.pack(self.volume, c2is, masks, self.grid, 'exact', True)
+        a, (_, _, lab), keep = drr.args_for_records(self.volume, recs, self.grid, 'exact', self.step_mm, want_labels=True)
+        drr.launch(lab.device, 'dfl_drr_render', a)
+        return recs, lab, keep
+
+
+def _outline_options(geom, segmentation, levels, mask, outline_cap):
+    """The checks of register(similarity='outline'), made before anything touches a device."""
+    if levels is not None or mask is not None:
+        raise nat.DflError("register: similarity='outline' works on one grid and on label maps: levels and mask are not supported with it")
+    H, W = geom.grid.H, geom.grid.W
+    if not torch.is_tensor(segmentation) or segmentation.dim() != 2 or segmentation.dtype != torch.uint8 or tuple(segmentation.shape) != (H, W):
+        got = 'None' if segmentation is None else '%s of %s' % (tuple(getattr(segmentation, 'shape', ())), getattr(segmentation, 'dtype', type(segmentation)))
+        raise nat.DflError("register: similarity='outline' needs segmentation = a uint8 label map [%d, %d] on the output grid, got %s" % (H, W, got))
+    cap = float(outline_cap)
+    if not cap > 0.0 or not np.isfinite(cap):
+        raise nat.DflError('register: an outline_cap of %r pixels (finite, positive)' % (outline_cap,))
+    return cap
+
+
+def _outline_sets(geom, moving, outline_sets):
+    """outline_sets as given, or one set per label >= 1 found in the masks of the moving objects."""
+    if outline_sets is not None:
+        return outline_sets
+    found = 0
+    for m in moving:
+        found |= int(geom.objects[m].mask)
+    sets = [[l] for l in range(1, 32) if (found >> l) & 1]
+    if not sets:
+        raise nat.DflError('register: the masks of the moving objects %r hold no label >= 1 to take outlines of' % (tuple(moving),))
+    return sets
+
+
 def _theta_chain(both, piv, xis, moving):
     """_Level._cost_and_moments' rows and pivots, xis [V, 6, 4, 4] -> (cost [V], d cost / d theta [V, 6]), float64 numpy."""
     V = both.shape[0]
@@ -748,10 +864,13 @@ def _cost_options(refine, refine_tol, similarity, patch_radius, patch_stride, pa
     if refine > 0 and similarity == 'patch' and patch_weight == 'uniform':
         raise nat.DflError("register: refine needs the adjoint of the similarity, which similarity='patch' does not have yet "
                            "with patch_weight='uniform' (patch_weight='variance' has it)")
-    if similarity not in ('global', 'patch'):
-        raise nat.DflError("register: similarity = %r ('global' or 'patch')" % (similarity,))
-    if similarity == 'global' and patch_weight != 'uniform':
-        raise nat.DflError("register: patch_weight = %r belongs to similarity='patch'; similarity='global' has no patches" % (patch_weight,))
+    if similarity not in ('global', 'patch', 'outline'):
+        raise nat.DflError("register: similarity = %r ('global', 'patch' or 'outline')" % (similarity,))
+    if similarity != 'patch' and patch_weight != 'uniform':
+        raise nat.DflError("register: patch_weight = %r belongs to similarity='patch'; similarity=%r has no patches" % (patch_weight, similarity))
+    if similarity == 'outline' and refine > 0:
+        raise nat.DflError("register: refine needs the gradient of the cost, which similarity='outline' does not have: the outline cost "
+                           "is piecewise constant (DESIGN.md section 26); refine a later stage with similarity='global'")
     patch = _patch_params(patch_radius, patch_stride, patch_min_count) + (patch_weight,) if similarity == 'patch' else None
     landmark_weight = float(landmark_weight)
     if not landmark_weight >= 0.0 or not np.isfinite(landmark_weight):
@@ -906,7 +1025,7 @@ def _close(level, probs, means, refine, refine_tol, traces, renders, done):
 def register(volume, geom, fixed, moving=(0, 1, 2), theta0=None, P0=None, levels=None, popsize=16, generations=80, sigma0=2.0,
              step_mm=1.0, mask=None, seed=0, centre=None, rot_unit=ROT_UNIT, crop=0, rot180=False, sigma_shrink=0.5,
              similarity='global', patch_radius=7, patch_stride=4, patch_min_count=None, landmarks=None, landmark_weight=0.0,
-             refine=0, refine_tol=1e-4, patch_weight='uniform'):
+             refine=0, refine_tol=1e-4, patch_weight='uniform', segmentation=None, outline_sets=None, outline_cap=32.0):
     """Find theta such that the DRR of `volume` under P = D(theta) P0 matches `fixed`.
 
     moving selects the objects of geom.objects that share the pose under optimisation; the others are rendered at their
@@ -933,18 +1052,35 @@ def register(volume, geom, fixed, moving=(0, 1, 2), theta0=None, P0=None, levels
 
     patch_weight='variance' (with similarity='patch') weighs every patch by the energy of its fixed
     gradient, which quiets the background patches of a preprocessed projection, and has an adjoint: refine=K works with it.
+
+    similarity='outline'  matches bone outlines instead of intensities: `segmentation` is a uint8
+    label map [H, W] on geom.grid on the GPU (a row of 'nn-segs', best cleaned: labels.clean), `fixed` may be None and is
+    not read.  Every generation is one exact render that writes the winner-takes-all label_map of every candidate, the
+    boundary distance maps of those (dfl_label_edt), one dfl_sim_outline and one copy of lambda doubles (OutlineSimilarity).
+    The cost is the truncated chamfer distance between the boundaries of every set of outline_sets (what labels.edt takes;
+    default: one set per label >= 1 in the masks of the moving objects), truncated at outline_cap pixels, 0 .. 1.  It sees
+    a pose from half an image away and needs no landmarks, but it is piecewise constant: no refine, no levels, no mask,
+    and no motion below a pixel -- a start and a coarse stage for the intensity costs, not a replacement.  The landmark
+    term adds to it as to the others.
     """
     patch, landmark_weight = _cost_options(refine, refine_tol, similarity, patch_radius, patch_stride, patch_min_count, landmark_weight,
                                            patch_weight)
+    outline = similarity == 'outline'
+    if outline:
+        outline_cap = _outline_options(geom, segmentation, levels, mask, outline_cap)
+    elif segmentation is not None or outline_sets is not None:
+        raise nat.DflError("register: segmentation and outline_sets belong to similarity='outline', not to similarity=%r" % (similarity,))
     if landmarks is not None and levels is not None:
         raise nat.DflError('register: landmarks belong to one grid; they are not supported together with levels')
     lands = _landmarks_of(landmarks, moving)
-    _on_the_gpu('register', volume, {'the fixed image': fixed})
+    _on_the_gpu('register', volume, {'the segmentation': segmentation} if outline else {'the fixed image': fixed})
     moving, lam = _moving_and_population(geom, moving, popsize)
     theta0 = np.zeros(6) if theta0 is None else np.asarray(theta0, np.float64).reshape(6)
     prob = _Problem(volume.shape, geom, moving, P0, centre, rot_unit, lands, landmark_weight)
 
-    if levels is None:
+    if outline:
+        plan = [(None, int(generations), geom.grid, None)]
+    elif levels is None:
         plan = [(None, int(generations), geom.grid, _device_image(fixed, 'the fixed image', 2))]
     else:
         if mask is not None:
@@ -964,7 +1100,8 @@ def register(volume, geom, fixed, moving=(0, 1, 2), theta0=None, P0=None, levels
             raise nat.DflError('register: an empty list of levels')
     mean, sigma, trace, renders, done = theta0, float(sigma0), [], 0, []
     for k, (factor, gens, grid, img) in enumerate(plan):
-        level = _Level(volume, grid, img, mask, lam, step_mm, patch)
+        level = _OutlineLevel(volume, grid, segmentation, _outline_sets(geom, moving, outline_sets), outline_cap, lam, step_mm) if outline \
+            else _Level(volume, grid, img, mask, lam, step_mm, patch)
         res = _search(level, [prob], [mean], sigma, lam, gens, seed + k)[0]
         mean, sigma = res.mean, sigma * float(sigma_shrink)
         trace.extend(res.trace.tolist())
@@ -1005,6 +1142,9 @@ def register_many(volume, geoms, fixed, moving=(0, 1, 2), theta0=None, P0=None, 
     if unknown:
         raise nat.DflError('register_many: no argument %s (levels: there is no coarse-to-fine here; register() has it)'
                            % ', '.join(sorted(unknown)))
+    if similarity == 'outline':
+        raise nat.DflError("register_many: similarity='outline' is not supported here: register() has it, one projection at a time "
+                           "(dfl_sim_outline takes fixed_of, but the driver for a bank of segmentations is not written)")
     patch, landmark_weight = _cost_options(refine, refine_tol, similarity, patch_radius, patch_stride, patch_min_count, landmark_weight,
                                            patch_weight)
     try:

@@ -1565,6 +1565,55 @@ int dfl_sim_patch_eval(const dfl_sim_patch_eval_args* a, dfl_stream_t stream);
 int dfl_sim_patch_eval_scratch_doubles(int32_t V, int32_t H, int32_t W, int32_t rho, int32_t stride, int32_t bwd);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Outline cost (csrc/sim_outline.hip; DESIGN.md section 26 states the semantics, tests/outline_ref.py restates them in
+ * numpy float64): the truncated chamfer distance between the boundaries of S label sets in V moving label maps and in
+ * the fixed label maps they are scored against -- the similarity of register(similarity='outline').
+ *
+ * A label set is a 32-bit word, as for dfl_label_edt.  For set k, a view's label map m and its fixed map f:
+ *   M_k, F_k = the boundary sites of the set in m and in f, as dfl_label_edt(boundary = 1) defines them: an in-set pixel
+ *              with a 4-neighbour outside the set, or on the image border;
+ *   d2m, d2f = the exact squared boundary distance maps of m and of f for set k.  A pixel p is a boundary site of its map
+ *              exactly when that map's own distance at p is 0, so the entry point takes the distance maps alone.
+ * With cap > 0 in pixels and t(d2) = min(sqrt((double) d2), cap):
+ *   a_k = sum over p in M_k of t(d2f[k][p]),  b_k = sum over p in F_k of t(d2m[k][p]),  nM_k = |M_k|,  nF_k = |F_k|;
+ *   both counts positive:      c_k = (a_k / nM_k + b_k / nF_k) / (2 cap);
+ *   exactly one count positive: c_k = 1, and both sums are reported as 0;
+ *   both counts zero:           the set is not scored (sums 0);
+ *   cost[v] = the mean of c_k over the scored sets in ascending k, or 1.0 when none is scored.
+ * So the cost lies in 0 .. 1 and is 0 exactly when every scored set has the same boundary in both maps.
+ * DFL_LABEL_EDT_NONE in either map means "no boundary of that set" (such a map has no zero either).
+ *
+ * Two launches.  The first: one workgroup per (view, chunk of DFL_SIM_OUTLINE_CHUNK pixels); it loops over the S sets,
+ * reads both distance planes coalesced and writes ONE record of 4 S doubles (nM, nF, a, b per set) in scratch: the counts
+ * are exact integers in float64, the sums go through csrc/fixed_sum.h.  The second: one workgroup per view; one thread per
+ * number of a record adds that number over the view's records in index order, then one thread finishes counts, sums and
+ * cost in ascending k.  No atomics: a view's numbers have the same bits alone, in any batch
+ * and in any order of views.  scratch holds at least dfl_sim_outline_scratch_doubles(V, S, H, W) =
+ * 4 V S ceil(H W / DFL_SIM_OUTLINE_CHUNK) doubles (an int: negative on bad sizes, and when the count exceeds 2^31 - 1).
+ * fixed_of (device, [V]) says which of the F fixed maps a view is scored against; NULL: every view against map 0.  It
+ * cannot be checked on the host: a view whose entry is outside [0, F) reads nothing out of bounds and gets cost = NaN,
+ * counts and sums 0; the other views are not affected.
+ * Refused with nothing launched: NULL pointers (only fixed_of may be NULL), V < 1, V > 65535, F < 1, S outside
+ * 1..DFL_LABEL_MAX_CLASSES, H < 1, W < 1, (H-1)^2 + (W-1)^2 >= 2^31 - 1 (the size condition of dfl_label_edt), a cap
+ * that is not finite and positive, a short scratch.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define DFL_SIM_OUTLINE_CHUNK 1024
+typedef struct {
+  const int32_t* d2_moving;       /* [V][S][H][W]  dfl_label_edt(the views' label maps, sets, boundary 1) */
+  const int32_t* d2_fixed;        /* [F][S][H][W]  the same of the fixed maps, made once */
+  const int32_t* fixed_of;        /* device [V], 0..F-1, or NULL: every view against fixed map 0 */
+  int32_t* counts;                /* [V][S][2]  nM, nF */
+  double* sums;                   /* [V][S][2]  a, b */
+  double* cost;                   /* [V] */
+  double* scratch;
+  int64_t scratch_doubles;        /* what scratch holds */
+  double cap;                     /* pixels */
+  int32_t V, F, S, H, W, reserved;
+} dfl_sim_outline_args;
+int dfl_sim_outline(const dfl_sim_outline_args* a, dfl_stream_t stream);
+int dfl_sim_outline_scratch_doubles(int32_t V, int32_t S, int32_t H, int32_t W);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Detector model: rendered line integrals -> detector intensities (csrc/expose.hip; DESIGN.md section 17 states the
  * semantics, tests/expose_ref.py restates them in numpy).  Per view v and pixel i = r C + c, all in fp32:
  *   T = expf(-att);  B = the separable blur of T with taps[0 .. 2 rho] (rows first, then columns, indices clamped to
