@@ -21,6 +21,10 @@ Every draw takes 12 normals from numpy.random.default_rng([seed, specimen index]
 whatever the specimen has, so the stream of one specimen does not depend on another.  The noise keys of view n do not
 come from that stream (noise_keys): its image noise does not depend on how many draws were rejected.
 
+Tools (tools > 0; dfl_amd.tools): view n of specimen k draws up to `tools` capsules around the
+landmarks from its own stream numpy.random.default_rng([seed, k, 1, n]) and adds their line integrals between the render
+and the detector model.  The pose stream and the noise keys do not move; tools = 0 takes no draw and makes no launch.
+
 Tensors on the CPU and a machine without a GPU are refused: there is no CPU path.
 """
 import numpy as np
@@ -28,9 +32,10 @@ import torch
 
 from . import _native as nat
 from . import drr, fullres, h5lite, preprocess, register
+from . import tools as tools_mod
 
 __all__ = ['gaussian_taps', 'noise_keys', 'expose', 'expose_args', 'draw_motion', 'apply_motion', 'lands_in_window', 'fov_flags',
-           'sample_pose', 'sample_poses', 'synthesize', 'MAX_DRAWS', 'DEFAULTS']
+           'sample_pose', 'sample_poses', 'tool_rng', 'synthesize', 'MAX_DRAWS', 'DEFAULTS']
 
 MAX_DRAWS = 20
 FEMUR_HEADS = ('FH-l', 'FH-r')
@@ -189,6 +194,11 @@ def sample_poses(seed, specimen_index, specimen, seeds, views, K, E, lands3d, ro
     return out
 
 
+def tool_rng(seed, specimen_index, view):
+    """The stream the tools of one synthetic view are drawn from: apart from the pose stream [seed, specimen index]."""
+    return np.random.default_rng([int(seed), int(specimen_index), 1, int(view)])
+
+
 # ---- the pipeline ------------------------------------------------------------------------------------------------------
 def _copy(src, out, path, to=None):
     """Copy group or dataset `path` of an open h5lite file into the writer (at `to`), as it is stored."""
@@ -211,15 +221,25 @@ def synthesize(src, dst, views, seed=0, layout='preprocessed', specimens=None, c
                rot_sigma_deg=DEFAULTS['rot_sigma_deg'], trans_sigma_mm=DEFAULTS['trans_sigma_mm'],
                femur_sigma_deg=DEFAULTS['femur_sigma_deg'], min_lands=DEFAULTS['min_lands'], photons=DEFAULTS['photons'],
                gain=DEFAULTS['gain'], electronic_sigma=DEFAULTS['electronic_sigma'], blur_sigma_px=DEFAULTS['blur_sigma_px'],
-               noise=True, bones_only=False, volumes=True, chunk=8, compression=None, device=None, report=None):
+               noise=True, bones_only=False, volumes=True, chunk=8, compression=None, device=None, report=None, tools=0,
+               tool_options=None, tool_mask=False):
     """A file of `views` synthetic projections per specimen from the full-resolution file `src` (its CT, 3D annotation,
     3D landmarks, projection parameters and acquired poses).  layout 'full-res' writes the reference's full-resolution
     layout (volumes=False leaves out 'vol' and 'vol-seg'); 'preprocessed' the training file that
     preprocess.convert_file(crop, factor) makes of it, without the detour.  crop also bounds the acceptance window;
-    factor is used by 'preprocessed' only.  Returns [(specimen id, index, views, rejected draws)]; report(line) gets one
-    line per specimen."""
+    factor is used by 'preprocessed' only.  tools > 0 adds up to that many capsules per view (tools.sample_tools with the
+    keyword arguments tool_options); 'full-res' then also writes 'projections/NNN/tools/capsules' (float64 [n, 8]: a, b, r,
+    mu; views that drew a capsule) and, with tool_mask, 'projections/NNN/tools/mask/pixels' (uint8, 1 where a ray crosses a
+    tool; every view); 'preprocessed' keeps its datasets: the tools are in the pixels and nowhere else.
+    Returns [(specimen id, index, views, rejected draws)]; report(line) gets one line per specimen."""
     if layout not in ('full-res', 'preprocessed'):
         raise nat.DflError("synth.synthesize: layout must be 'full-res' or 'preprocessed', got %r" % (layout,))
+    tools, tool_options = int(tools), dict(tool_options or {})
+    if not 0 <= tools <= nat.TOOLS_MAX:
+        raise nat.DflError('synth.synthesize: tools must be 0..%d per view, got %d' % (nat.TOOLS_MAX, tools))
+    unknown = sorted(set(tool_options) - set(tools_mod.TOOL_DEFAULTS))
+    if unknown:
+        raise nat.DflError('synth.synthesize: unknown tool option %s (known: %s)' % (', '.join(unknown), ', '.join(sorted(tools_mod.TOOL_DEFAULTS))))
     if not torch.cuda.is_available():
         raise nat.DflError('synth.synthesize: no GPU visible (the renderer and the detector model are HIP kernels; no CPU path)')
     if int(views) < 1 or int(chunk) < 1:
@@ -272,6 +292,11 @@ def synthesize(src, dst, views, seed=0, layout='preprocessed', specimens=None, c
                     part = plan[n0:n0 + chunk]
                     objs = [drr.default_objects(E, poses, I2P, bones_only) for poses, _, _ in part]
                     att, _, lab = drr.render(volume, objs, grid, interp='exact', want_plen=False, want_labels=True, tight_boxes=True)
+                    caps, tlen = [[] for _ in part], None
+                    if tools > 0:
+                        caps = [tools_mod.sample_tools(tool_rng(seed, k, n0 + j), tools_mod.lands_in_camera(E, poses[drr.POSES[0]], lands3d[s]),
+                                                       tools, **tool_options) for j, (poses, _, _) in enumerate(part)]
+                        tlen = tools_mod.add_tools(att, grid, caps, want_len=tool_mask and not pre)
                     keys = [noise_keys(seed, k, n0 + j) for j in range(len(part))]
                     img = expose(att, photons, gain, electronic_sigma, blur_sigma_px, keys_q=[q for q, _ in keys] if noise else None,
                                  keys_e=[e for _, e in keys] if noise else None, u16=True)
@@ -283,6 +308,7 @@ def synthesize(src, dst, views, seed=0, layout='preprocessed', specimens=None, c
                         lands2d[n0:n0 + len(part)] = np.stack(uv)
                         continue
                     img, lab = img.cpu().numpy(), lab.cpu().numpy()
+                    mask = None if tlen is None else (tlen > 0).to(torch.uint8).cpu().numpy()
                     for j, (poses, sd, _) in enumerate(part):
                         pfx, spfx = fullres.projection_prefix(s, n0 + j), seeds[sd]['pfx']
                         out.create_dataset(pfx + 'image/pixels', data=img[j], dtype=np.uint16, **kw_img)
@@ -298,6 +324,10 @@ def synthesize(src, dst, views, seed=0, layout='preprocessed', specimens=None, c
                         for side, flag in zip(('left', 'right'), fov_flags(K, E, poses, lands3d[s], R, Cn, seeds[sd]['fov'])):
                             out[pfx + 'gt-poses/%s-femur-good-fov' % side] = np.int64(flag)
                         out[pfx + 'rot-180-for-up'] = np.int64(seeds[sd]['rot'])
+                        if caps[j]:
+                            out[pfx + 'tools/capsules'] = np.stack([cap.row() for cap in caps[j]])
+                        if mask is not None:
+                            out.create_dataset(pfx + 'tools/mask/pixels', data=mask[j], dtype=np.uint8, **kw_img)
                 if pre:
                     out[grp + '/lands'] = preprocess.map_lands(lands2d, [seeds[sd]['rot'] for _, sd, _ in plan], R, Cn, crop,
                                                                factor).astype(np.float32)

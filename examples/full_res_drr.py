@@ -6,6 +6,7 @@ preprocess_full_res.py writes for the same --crop and --ds-factor.
 
     python examples/full_res_drr.py full_res.h5 17-1882 0                      # writes 17-1882_000_drr.png, _labels.png, .npz
     python examples/full_res_drr.py full_res.h5 17-1882 0 --out view --ds-factor 4 --interp trilinear --step 0.25 --compare
+    python examples/full_res_drr.py synth.h5 17-1882 3 --tools-from synth.h5   # one tooled view of synthesize_dataset.py --tools
 
 PREFIX_drr.png is the line integral, 8-bit, min / max scaled (a constant image comes out as 0); PREFIX_labels.png the
 label map tinted over it in the overlay palette; PREFIX.npz holds att, labels and lands ([2, L] (column, row) in
@@ -13,6 +14,9 @@ preprocess.LAND_ORDER; inf where the file has no such 3D landmark).  --bones-onl
 label map always comes from the exact radiological path; --interp chooses how att is integrated.
 --compare renders the file's own projection, gt-seg and gt-landmarks on the same grid and prints the NCC of the DRR
 with the projection, the hard Dice per label and the largest landmark distance in output pixels.
+--tools-from FILE reads 'projections/NNN/tools/capsules' of the same specimen and projection from FILE (a full-res file
+of synthesize_dataset.py --tools N) and adds those capsules to att (dfl_amd.tools.add_tools); the
+label map is the anatomy's, whatever lies in front of it.  A projection without that dataset has no tools.
 Files: the reference's HDF5 (dfl_amd.h5lite) or .npz with the same names as keys.
 """
 import os
@@ -24,10 +28,10 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dfl_amd  # noqa: E402,F401
-from dfl_amd import _native as nat, drr, fullres, ncc, overlay, png, preprocess, util  # noqa: E402
+from dfl_amd import _native as nat, drr, fullres, ncc, overlay, png, preprocess, tools, util  # noqa: E402
 
 USAGE = ('Usage: {} <HDF5 full-res data file> <specimen ID> <projection index> [--out PREFIX] [--crop 50] [--ds-factor 8] '
-         '[--interp exact|trilinear] [--step 0.5] [--bones-only] [--compare]')
+         '[--interp exact|trilinear] [--step 0.5] [--bones-only] [--compare] [--tools-from FILE]')
 VALUED = {'--out': str, '--crop': int, '--ds-factor': int, '--interp': str, '--step': float}
 FLAGS = ('--bones-only', '--compare')
 
@@ -63,6 +67,17 @@ def parse(argv):
     return parsed if parsed and parsed[1]['--interp'] in ('exact', 'trilinear') else None
 
 
+def parse_tools(argv):
+    """(argv without '--tools-from FILE', FILE or None), or None when the option has no value."""
+    argv = list(argv)
+    if '--tools-from' not in argv:
+        return argv, None
+    k = argv.index('--tools-from')
+    if k + 1 >= len(argv) or argv[k + 1].startswith('--') or '--tools-from' in argv[k + 2:]:
+        return None
+    return argv[:k] + argv[k + 2:], argv[k + 1]
+
+
 def to_u8(img):
     """Min / max scaling to 8 bits; a constant image comes out as 0."""
     lo, hi = img.min(), img.max()
@@ -75,6 +90,18 @@ def projected_landmarks(src, spec, geom):
     """[2, L] in preprocess.LAND_ORDER; inf where the name is absent."""
     have = fullres.volume_landmarks(src, spec)
     return np.stack([drr.project_points(geom, have[n])[:, 0] if n in have else np.full(2, np.inf) for n in preprocess.LAND_ORDER], 1)
+
+
+def read_capsules(path, spec, idx):
+    """[tools.Capsule] of 'projections/NNN/tools/capsules' of a file synthesize_dataset.py --tools wrote; none: []."""
+    src = fullres.Source(path)
+    try:
+        pfx = fullres.projection_prefix(spec, idx)
+        if 'tools' not in src.children(pfx) or 'capsules' not in src.children(pfx + 'tools'):
+            return []
+        return [tools.Capsule.from_row(row) for row in np.asarray(src.get(pfx + 'tools/capsules')).reshape(-1, 8)]
+    finally:
+        src.close()
 
 
 def compare(src, spec, idx, crop, factor, geom, att, labels, lands, n_classes, dev, log=print):
@@ -106,7 +133,8 @@ def compare(src, spec, idx, crop, factor, geom, att, labels, lands, n_classes, d
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
-    parsed = parse(argv)
+    split = parse_tools(argv)
+    parsed = parse(split[0]) if split is not None else None
     if parsed is None:
         print(USAGE.format(os.path.basename(sys.argv[0])))
         return 1
@@ -122,6 +150,12 @@ def main(argv=None):
         att, _, labels = drr.render(vol, geom.objects, geom.grid)
         if o['--interp'] == 'trilinear':
             att, _, _ = drr.render(vol, geom.objects, geom.grid, interp='trilinear', step_mm=o['--step'])
+        if split[1] is not None:
+            caps = read_capsules(split[1], spec, idx)
+            att = att[None].contiguous()
+            tools.add_tools(att, geom.grid, [caps])
+            att = att[0]
+            print('{} capsules from {}'.format(len(caps), split[1]))
         lands = projected_landmarks(src, spec, geom)
         n_classes = max(vol.n_labels, 2)
         prefix = o['--out'] or '{}_{:03d}'.format(spec, idx)

@@ -48,7 +48,7 @@ const char* dfl_last_error(void);
  * bn_bwd_finalize, bn_relu_bwd, affine_copy, pool, head_fwd, head_bwd, loss, ensemble, op, reduce_job, prep,
  * est_lands, upsample, augment_args, augment_item, overlay, resample_plan, resample_args, fullres, mesh_mc,
  * mesh_decode, mesh_topo, mesh_csr, mesh_smooth, mesh_xform, mesh_normals, preproc_projs, preproc_segs, restore_labels,
- * sim_prepare, sim_gradncc, expose, sim_patch_prepare, sim_patch_gradncc, raster_mesh, raster_args, sim_gradncc_bwd, sim_patch_weights,
+ * sim_prepare, sim_gradncc, expose, tools_capsule, tools_args, sim_patch_prepare, sim_patch_gradncc, raster_mesh, raster_args, sim_gradncc_bwd, sim_patch_weights,
  * sim_patch_eval, drr_pose_grad, sim_bank_gradncc, sim_bank_gradncc_bwd, sim_patch_bank_gradncc, drr_object, drr_args, optim_pack): lets a
  * binding written in another language verify the size of its struct mirrors at load time.  Returns -1 past the end.
  * Sizes say nothing about field order or type: the Python binding derives its structs, constants and signatures from this
@@ -1641,6 +1641,66 @@ typedef struct {
   float photons, gain, electronic_sigma;
 } dfl_expose_args;
 int dfl_drr_expose(const dfl_expose_args* a, dfl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Tools: straight metal instruments and beads in a rendered view, as analytic capsules (csrc/drr_tools.hip; DESIGN.md
+ * section 27; tests/tools_ref.py restates this text in numpy float64).  dfl_drr_tools runs between dfl_drr_render and
+ * dfl_drr_expose: it adds line integrals to att in place.
+ *
+ * Frame.  A capsule is (a[3], b[3], r, mu): every point within r of the segment [a, b].  a and b are in mm in the camera
+ * projective frame (the frame the C2I matrices of dfl_drr_render map from; the source is its origin), r > 0 in mm, mu >= 0
+ * per mm.  a == b is a sphere (a bead).
+ * Ray.  The ray of output pixel (c, r) is x(t) = t d, t >= 0, d = Q [c, r, 1], Q = qscale (row-major 3 x 3, the qscale of
+ * dfl_drr_render).
+ * Chord.  len_j = |d| * measure{ t >= 0 : dist(x(t), segment[a_j, b_j]) <= r_j }.  A capsule is convex, so the set is one
+ * interval: from the smallest entry to the largest exit over the pieces the ray hits, clipped to t >= 0.  The pieces are the
+ * sphere about a, the sphere about b and -- when a != b -- the cylinder about the axis, clipped to the slab between the
+ * planes through a and b normal to the axis.  With u = d / |d| and e = (b - a) / |b - a|, u_perp = u - (u . e) e: a ray
+ * with |u_perp|^2 <= 1e-10 (within 1e-5 rad of the axis; TOOLS_PARALLEL in csrc/drr_tools.hip) is parallel to the axis
+ * and takes the two spheres alone.
+ * Output.  s = 0; for j = 0 .. n_tools - 1 ascending: s += mu_j * len_j, in float32; then att[v][r][c] += s (one rounding:
+ * float32(old + s)).  tool_len[v][r][c] = sum_j len_j, formed in the same order; NULL: not wanted.
+ * Simplifications.  Metal adds to the tissue it displaces (the CT's attenuation along the chord is not removed).
+ * Overlapping capsules count twice.  Attenuation is monoenergetic: no beam hardening and no streaks.  The label map is not
+ * touched: a label is the projected anatomy whatever lies in front of it.
+ *
+ * Arithmetic (float32, every product and sum rounded on its own: the file is built with -ffp-contract=off; dots are summed
+ * x, y, z from the left).  Per pixel: d, |d| = sqrtf(d . d), u = d / |d| per component (|d| = 0 or not finite: s = 0).
+ * Per capsule and sphere centre p: tc = u . p; q = p - tc u as a VECTOR, then q2 = q . q -- never |p|^2 - tc^2, which at
+ * 800 mm loses the radius of a wire -- h2 = r r - q2; hit when h2 >= 0: [tc - h, tc + h], h = sqrtf(h2).
+ * Cylinder: w = b - a, L = sqrtf(w . w), e = w / L, ue = u . e, u_perp = u - ue e, A = u_perp . u_perp, ae = a . e,
+ * a_perp = a - ae e, tcyl = (u_perp . a_perp) / A, q = a_perp - tcyl u_perp (the offset in the plane normal to the axis, a
+ * vector again), h2 = r r - q . q; hit when h2 >= 0: [tcyl - h, tcyl + h], h = sqrtf(h2 / A), cut to the slab
+ * [min, max] of ae / ue and (ae + L) / ue (ue = 0: kept whole when 0 <= -ae <= L, else dropped), dropped when empty.
+ * len = max(exit - max(entry, 0), 0): u is a unit vector, so t is in mm.
+ *
+ * tools is a device array [views][n_tools] of dfl_tools_capsule (48 bytes).  rect = c0, r0, c1, r1 (inclusive) is a pixel
+ * rectangle computed conservatively on the host: a pixel outside it skips the capsule (its chord must be 0 there), and a
+ * wave whose 8 x 8 pixels are all outside skips it without diverging.  n_tools is 0 .. DFL_TOOLS_MAX and is the stride of
+ * every view; a view with fewer capsules pads with r = 0 records.  Values inside the device array cannot be checked on
+ * the host: a record with a field that is not finite or with r <= 0 contributes nothing.
+ * One launch, one thread per pixel and view (a wave covers 8 x 8 pixels, as dfl_drr_render mapping 0); no atomics, no LDS,
+ * one 4-byte load and store per pixel and output, 64-bit offsets.  n_tools == 0 returns 0 and launches nothing.
+ * Refused with nothing launched and the outputs untouched: NULL att, NULL tools with n_tools > 0, views outside
+ * 1..65535, H < 1, W < 1, H W >= 2^31, n_tools outside 0..DFL_TOOLS_MAX, a qscale entry that is not finite.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define DFL_TOOLS_MAX 64
+typedef struct {
+  float a[3];                     /* mm, camera projective frame */
+  float b[3];
+  float r;                        /* mm; <= 0: a padding record */
+  float mu;                       /* per mm */
+  int32_t rect[4];                /* c0, r0, c1, r1, inclusive */
+} dfl_tools_capsule;
+typedef struct {
+  float* att;                     /* [views][H][W], modified in place */
+  float* tool_len;                /* [views][H][W] or NULL */
+  const dfl_tools_capsule* tools; /* device, [views][n_tools]; NULL allowed when n_tools == 0 */
+  float qscale[9];                /* Q, row-major */
+  int32_t views, H, W, n_tools;
+  int32_t reserved;               /* not read */
+} dfl_tools_args;
+int dfl_drr_tools(const dfl_tools_args* a, dfl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Product arithmetic of the convolution / weight-gradient GEMMs (fast paths; odd channel counts always use fp32):

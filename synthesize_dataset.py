@@ -8,9 +8,12 @@ training file.  'gt-seg', 'gt-landmarks' and 'gt-poses' are exact by constructio
            [--specimens a,b] [--crop 50] [--ds-factor 8] [--rot-sigma-deg 10] [--trans-sigma-mm 20,20,50]
            [--femur-sigma-deg 5] [--min-lands 4] [--photons 20000] [--gain 2] [--electronic-sigma 3] [--blur-sigma-px 1]
            [--no-noise] [--bones-only] [--no-volumes] [--chunk 8] [--gzip]
+           [--tools 0] [--tool-mu 0.5] [--tool-anchor-sigma-mm 30] [--tool-length-mm 60,220] [--tool-radius-mm 0.5,1.6]
+           [--bead-prob 0.25] [--tool-mask]
 
 --views is per specimen.  Specimens are numbered as preprocess_full_res.py numbers them.  One line per specimen is
-printed.  The renderer and the detector model are HIP kernels: a machine without a GPU is refused.
+printed.  --tools N puts up to N straight metal tools (wires as capsules, beads as spheres) into every
+view; --tool-mask (full-res layout) also writes where they are.  The renderer and the detector model are HIP kernels: a machine without a GPU is refused.
 """
 import argparse
 import os
@@ -24,6 +27,34 @@ def _triple(s):
     if len(v) != 3:
         raise argparse.ArgumentTypeError('three comma-separated numbers expected, got %r' % s)
     return tuple(v)
+
+
+def _pair(s):
+    v = [float(t) for t in s.split(',')]
+    if len(v) != 2 or not 0 < v[0] <= v[1]:
+        raise argparse.ArgumentTypeError('two comma-separated numbers lo,hi with 0 < lo <= hi expected, got %r' % s)
+    return tuple(v)
+
+
+def _count(s):
+    v = int(s)
+    if not 0 <= v <= 64:
+        raise argparse.ArgumentTypeError('0..64 expected, got %r' % s)
+    return v
+
+
+def _prob(s):
+    v = float(s)
+    if not 0 <= v <= 1:
+        raise argparse.ArgumentTypeError('a probability 0..1 expected, got %r' % s)
+    return v
+
+
+def _not_negative(s):
+    v = float(s)
+    if not 0 <= v < float('inf'):
+        raise argparse.ArgumentTypeError('a finite number that is not negative expected, got %r' % s)
+    return v
 
 
 def build_parser():
@@ -51,6 +82,13 @@ def build_parser():
     p.add_argument('--no-volumes', action='store_true', help="full-res layout: leave out 'vol' and 'vol-seg'")
     p.add_argument('--chunk', type=int, default=8, help='views rendered per launch')
     p.add_argument('--gzip', action='store_true', help='compress the pixel datasets (gzip)')
+    p.add_argument('--tools', type=_count, default=0, help='at most this many tools per view (0: none, and the file of a run without the flag)')
+    p.add_argument('--tool-mu', type=_not_negative, default=0.5, help='attenuation of every tool per mm (a parameter, not an alloy)')
+    p.add_argument('--tool-anchor-sigma-mm', type=_not_negative, default=30.0, help='sigma of a tool\'s anchor about a landmark, per axis')
+    p.add_argument('--tool-length-mm', type=_pair, default=(60.0, 220.0), help='length of a wire lo,hi')
+    p.add_argument('--tool-radius-mm', type=_pair, default=(0.5, 1.6), help='radius of a wire lo,hi')
+    p.add_argument('--bead-prob', type=_prob, default=0.25, help='probability that a tool is a bead of 0.75 mm radius')
+    p.add_argument('--tool-mask', action='store_true', help="full-res layout: write 'tools/mask' (1 where a ray crosses a tool)")
     return p
 
 
@@ -66,7 +104,9 @@ def main(argv=None):
                        femur_sigma_deg=args.femur_sigma_deg, min_lands=args.min_lands, photons=args.photons, gain=args.gain,
                        electronic_sigma=args.electronic_sigma, blur_sigma_px=args.blur_sigma_px, noise=not args.no_noise,
                        bones_only=args.bones_only, volumes=not args.no_volumes, chunk=args.chunk,
-                       compression='gzip' if args.gzip else None, report=print)
+                       compression='gzip' if args.gzip else None, report=print, tools=args.tools,
+                       tool_options=dict(tool_mu=args.tool_mu, anchor_sigma_mm=args.tool_anchor_sigma_mm, length_mm=args.tool_length_mm,
+                                         wire_radius_mm=args.tool_radius_mm, bead_prob=args.bead_prob), tool_mask=args.tool_mask)
     return 0
 
 
