@@ -536,8 +536,16 @@ __global__ void __launch_bounds__(256) maxpool_bwd_kernel(const dfl_pool_args a,
 // GEMM operand layout of dfl_conv2d: w[kq][n][r] = W(k = 4*kq + r, n), zero for k >= K ("quad-packed": one float4 is four
 // consecutive k of one output column).  The source is always a contiguous [A][B][C] parameter (C = KH*KW) and the
 // (k, n) <-> (a, b, c) mapping is one of three kinds (include/dfl_hip.h).  Fast path: LDS-tiled -- a 32(A) x 32(B) x C
-// tile is read as 32 runs of 32*C contiguous floats and written as 512-byte runs; element-wise fallback otherwise.
+// tile is read as 32 runs of 32*C contiguous floats and one emitter per format (pack_emit_cells, pack_emit_quads) writes it
+// as 512-byte runs; element-wise fallback (pack_src) otherwise.
 constexpr int PK_T = 32, PK_CMAX = 9;
+using PackTile = float[PK_T][PK_T * PK_CMAX + 1];
+
+// K x N of the matrix a job of this kind builds
+struct PackDims { int K, N; };
+__device__ __forceinline__ PackDims pack_dims(int kind, int A, int B, int C) {
+  return {(kind == 1) ? C * B : (kind == 2 ? C * A : A), (kind == 1) ? A : (kind == 2 ? B : C * B)};
+}
 
 __device__ __forceinline__ float pack_src(const dfl_pack_job& j, int k, int n) {
   int a, b, c;
@@ -553,7 +561,7 @@ __device__ __forceinline__ float pack_src(const dfl_pack_job& j, int k, int n) {
 }
 
 // element r of quad slot q: a float, or (split format) hi bf16 at half-word r and lo bf16 at half-word 4 + r of the slot
-// (the bf16 chunk layout, split = 2, has its own path in pack_kernel)
+// (the bf16 chunk layout, split = 2, is written cell by cell: pack_emit_cells and pack_kernel's element-wise cells)
 __device__ __forceinline__ void pack_put(float* dst, int64_t q, int r, float v, int split) {
   if (!split) {
     dst[q * 4 + r] = v;
@@ -566,56 +574,89 @@ __device__ __forceinline__ void pack_put(float* dst, int64_t q, int r, float v, 
   }
 }
 
+// ---- a tile in LDS becomes a layout: the only two places that know the index maps of the tiled path.  (a0, b0) is the tile's
+// corner in the parameter, na x nb its extent: 32 x 32 in pack_tile, where the edge guards fold away after inlining (x, 16 * blk,
+// ar and bb are below 32 by construction); the last tiles of pack_kernel are smaller.
+// bf16 chunk layout [K/16][N][16]: a thread builds whole cells (16 consecutive k of one column = 32 bytes) and consecutive threads
+// take consecutive columns: coalesced on both sides.  The k-run channel count is a multiple of 16 here, so a block of 16 k inside
+// the extent is whole.
+__device__ __forceinline__ void pack_emit_cells(const PackTile& tile, unsigned short* dst16, int kind, int flip, int A, int B, int Cc,
+                                                int a0, int b0, int na, int nb) {
+  const int N = pack_dims(kind, A, B, Cc).N;
+  const int nx = (kind == 1) ? na : nb, nk = (kind == 1) ? nb : na;   // extent along the columns and along the k run
+  for (int e = threadIdx.x; e < 64 * Cc; e += 256) {           // cells of this tile: 32 columns x 2 blocks of 16 k x C taps
+    const int x = e & 31, blk = (e >> 5) & 1, cp = e >> 6;
+    if (x >= nx || 16 * blk >= nk) continue;
+    float f[16];
+    int64_t cell;
+    if (kind == 1) {                // k = c*B + b (16 consecutive b), n = a
+#pragma unroll
+      for (int r = 0; r < 16; ++r) f[r] = tile[x][(16 * blk + r) * Cc + cp];
+      cell = (int64_t)((cp * B + b0) / 16 + blk) * N + a0 + x;
+    } else if (kind == 2) {         // k = c'*A + a (16 consecutive a), n = b
+      const int c = flip ? (Cc - 1 - cp) : cp;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) f[r] = tile[16 * blk + r][x * Cc + c];
+      cell = (int64_t)((cp * A + a0) / 16 + blk) * N + b0 + x;
+    } else {                        // k = a (16 consecutive a), n = c*B + b
+#pragma unroll
+      for (int r = 0; r < 16; ++r) f[r] = tile[16 * blk + r][x * Cc + cp];
+      cell = (int64_t)(a0 / 16 + blk) * N + cp * B + b0 + x;
+    }
+    u32x4* d = reinterpret_cast<u32x4*>(dst16 + cell * 16);
+    d[0] = pack8(f);
+    d[1] = pack8(f + 8);
+  }
+}
+
+// the quad layouts (4 floats, or 4 hi | 4 lo bf16: pack_put): the k-run channel count is a multiple of 4 here
+__device__ __forceinline__ void pack_emit_quads(const PackTile& tile, float* dst, int kind, int flip, int split, int A, int B, int Cc,
+                                                int a0, int b0, int na, int nb) {
+  const int N = pack_dims(kind, A, B, Cc).N;
+  for (int e = threadIdx.x; e < PK_T * PK_T * Cc; e += 256) {
+    const int r = e & 3, x = (e >> 2) & 31, rest = e >> 7;     // rest in [0, 8*C): tap, and quad of the tile's 8 along the k run
+    if (kind == 1) {                // k = c*B + b, n = a: quads run along b, columns along a
+      const int c = rest >> 3, bq = rest & 7, bb = 4 * bq + r, ar = x;
+      if (ar < na && bb < nb) pack_put(dst, (int64_t)((c * B + b0) / 4 + bq) * N + a0 + ar, r, tile[ar][bb * Cc + c], split);
+    } else if (kind == 2) {         // k = c'*A + a, n = b: quads along a, columns along b
+      const int cp = rest >> 3, aq = rest & 7, ar = 4 * aq + r, bb = x;
+      const int c = flip ? (Cc - 1 - cp) : cp;
+      if (ar < na && bb < nb) pack_put(dst, (int64_t)((cp * A + a0) / 4 + aq) * N + b0 + bb, r, tile[ar][bb * Cc + c], split);
+    } else {                        // k = a, n = c*B + b
+      const int c = rest >> 3, aq = rest & 7, ar = 4 * aq + r, bb = x;
+      if (ar < na && bb < nb) pack_put(dst, (int64_t)(a0 / 4 + aq) * N + c * B + b0 + bb, r, tile[ar][bb * Cc + c], split);
+    }
+  }
+}
+
+__device__ __forceinline__ void pack_emit(const PackTile& tile, float* dst, int kind, int flip, int split, int A, int B, int Cc, int a0,
+                                          int b0, int na, int nb) {
+  if (split == 2) pack_emit_cells(tile, reinterpret_cast<unsigned short*>(dst), kind, flip, A, B, Cc, a0, b0, na, nb);
+  else pack_emit_quads(tile, dst, kind, flip, split, A, B, Cc, a0, b0, na, nb);
+}
+
+// dfl_pack_weights: a (tiles, jobs) grid; a job that tiles walks its 32 x 32 x C tiles (the last ones smaller), any other one
+// goes element by element
 __global__ void __launch_bounds__(256) pack_kernel(const dfl_pack_job* __restrict__ jobs) {
-  __shared__ float tile[PK_T][PK_T * PK_CMAX + 1];
+  __shared__ PackTile tile;
   const dfl_pack_job j = jobs[blockIdx.y];
   const int A = j.A, B = j.B, Cc = j.C;
-  const int K = (j.kind == 1) ? Cc * B : (j.kind == 2 ? Cc * A : A);
-  const int N = (j.kind == 1) ? A : (j.kind == 2 ? B : Cc * B);
-  if (j.split == 2 && Cc <= PK_CMAX && ((j.kind == 1) ? (B % 16 == 0) : (A % 16 == 0))) {
-    // bf16 chunk layout [K/16][N][16], LDS-tiled: a 32(A) x 32(B) x C tile is read as 32 runs of 32*C contiguous floats;
-    // a thread then builds whole cells (16 consecutive k of one column = 32 bytes) and consecutive threads take consecutive
-    // columns: coalesced on both sides (the element-wise form below gathers 4-byte words 4*B*C bytes apart)
+  const PackDims dims = pack_dims(j.kind, A, B, Cc);
+  const int K = dims.K, N = dims.N;
+  // tileable: the taps fit the LDS tile and the k-run channel count (B for kind 1, A for kinds 2 and 3) fills whole cells / quads
+  if (Cc <= PK_CMAX && (((j.kind == 1) ? B : A) & (j.split == 2 ? 15 : 3)) == 0) {
     const int tb = (B + PK_T - 1) / PK_T, ta = (A + PK_T - 1) / PK_T;
     const int run = PK_T * Cc;
-    unsigned short* dst16 = reinterpret_cast<unsigned short*>(j.dst);
     for (int tidx = blockIdx.x; tidx < ta * tb; tidx += gridDim.x) {
       const int a0 = (tidx / tb) * PK_T, b0 = (tidx % tb) * PK_T;
       const int nb = min(PK_T, B - b0), na = min(PK_T, A - a0);
-      __syncthreads();
-      for (int e = threadIdx.x; e < PK_T * run; e += 256) {
+      __syncthreads();                                         // the previous tile has been emitted
+      for (int e = threadIdx.x; e < PK_T * run; e += 256) {    // 32 rows of 32*C contiguous source floats
         const int ar = e / run, q = e - ar * run;
         if (ar < na && q < nb * Cc) tile[ar][q] = j.src[((int64_t)(a0 + ar) * B + b0) * Cc + q];
       }
       __syncthreads();
-      for (int e = threadIdx.x; e < 64 * Cc; e += 256) {       // cells of this tile: 32 columns x 2 blocks of 16 k x C taps
-        const int x = e & 31, blk = (e >> 5) & 1, cp = e >> 6;
-        float f[16];
-        int64_t cell;
-        bool ok;
-        if (j.kind == 1) {          // k = c*B + b (16 consecutive b), n = a
-          ok = x < na && 16 * blk < nb;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) f[r] = tile[x][(16 * blk + r) * Cc + cp];
-          cell = (int64_t)((cp * B + b0) / 16 + blk) * N + a0 + x;
-        } else if (j.kind == 2) {   // k = c'*A + a (16 consecutive a), n = b
-          const int c = j.flip ? (Cc - 1 - cp) : cp;
-          ok = x < nb && 16 * blk < na;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) f[r] = tile[16 * blk + r][x * Cc + c];
-          cell = (int64_t)((cp * A + a0) / 16 + blk) * N + b0 + x;
-        } else {                    // k = a (16 consecutive a), n = c*B + b
-          ok = x < nb && 16 * blk < na;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) f[r] = tile[16 * blk + r][x * Cc + cp];
-          cell = (int64_t)(a0 / 16 + blk) * N + cp * B + b0 + x;
-        }
-        if (ok) {
-          u32x4* d = reinterpret_cast<u32x4*>(dst16 + cell * 16);
-          d[0] = pack8(f);
-          d[1] = pack8(f + 8);
-        }
-      }
+      pack_emit(tile, j.dst, j.kind, j.flip, j.split, A, B, Cc, a0, b0, na, nb);
     }
     return;
   }
@@ -639,39 +680,6 @@ __global__ void __launch_bounds__(256) pack_kernel(const dfl_pack_job* __restric
     }
     return;
   }
-  const bool tiled = Cc <= PK_CMAX && ((j.kind == 1) ? (B % 4 == 0) : (A % 4 == 0));
-  if (tiled) {
-    const int tb = (B + PK_T - 1) / PK_T, ta = (A + PK_T - 1) / PK_T;
-    const int run = PK_T * Cc;
-    for (int tidx = blockIdx.x; tidx < ta * tb; tidx += gridDim.x) {
-      const int a0 = (tidx / tb) * PK_T, b0 = (tidx % tb) * PK_T;
-      const int nb = min(PK_T, B - b0), na = min(PK_T, A - a0);
-      __syncthreads();
-      for (int e = threadIdx.x; e < PK_T * run; e += 256) {   // 32 rows of 32*C contiguous source floats
-        const int ar = e / run, q = e - ar * run;
-        if (ar < na && q < nb * Cc) tile[ar][q] = j.src[((int64_t)(a0 + ar) * B + b0) * Cc + q];
-      }
-      __syncthreads();
-      for (int e = threadIdx.x; e < PK_T * run; e += 256) {
-        const int r = e & 3, x = (e >> 2) & 31, rest = e >> 7;   // rest in [0, 8*C)
-        if (j.kind == 1) {          // k = c*B + b, n = a: quads run along b, columns along a
-          const int c = rest >> 3, bq = rest & 7, bb = 4 * bq + r, ar = x;
-          if (ar < na && bb < nb)
-            pack_put(j.dst, (int64_t)((c * B + b0) / 4 + bq) * N + a0 + ar, r, tile[ar][bb * Cc + c], j.split);
-        } else if (j.kind == 2) {   // k = c'*A + a, n = b: quads along a, columns along b
-          const int cp = rest >> 3, aq = rest & 7, ar = 4 * aq + r, bb = x;
-          const int c = j.flip ? (Cc - 1 - cp) : cp;
-          if (ar < na && bb < nb)
-            pack_put(j.dst, (int64_t)((cp * A + a0) / 4 + aq) * N + b0 + bb, r, tile[ar][bb * Cc + c], j.split);
-        } else {                    // k = a, n = c*B + b
-          const int c = rest >> 3, aq = rest & 7, ar = 4 * aq + r, bb = x;
-          if (ar < na && bb < nb)
-            pack_put(j.dst, (int64_t)(a0 / 4 + aq) * N + c * B + b0 + bb, r, tile[ar][bb * Cc + c], j.split);
-        }
-      }
-    }
-    return;
-  }
   const int Kq = (K + 3) / 4;
   const int64_t total = (int64_t)Kq * N * 4;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -682,64 +690,6 @@ __global__ void __launch_bounds__(256) pack_kernel(const dfl_pack_job* __restric
     const int k = 4 * kq + r;
     pack_put(j.dst, i >> 2, r, (k < K) ? pack_src(j, k, n) : 0.f, j.split);
   }
-}
-
-// ---- tiled dual-layout pack (dfl_pack_weights_tiled; round 4) ------------------------------------------------------------
-// One workgroup per 32(A) x 32(B) x C tile of ALL jobs of the launch (flat list: no idle blocks for the small layers, which a
-// (1024, jobs) grid spends 9 of 10 blocks on), the tile read with 16-byte loads, and BOTH bf16 chunk layouts of the parameter --
-// the forward operand and the data-gradient operand -- written from the same LDS tile: the fp32 master is read once.
-__device__ __forceinline__ void pack_emit_cells(const float (*tile)[PK_T * PK_CMAX + 1], unsigned short* dst16, int kind, int flip,
-                                                int A, int B, int Cc, int a0, int b0) {
-  const int N = (kind == 1) ? A : (kind == 2 ? B : Cc * B);
-  for (int e = threadIdx.x; e < 64 * Cc; e += 256) {           // cells of this tile: 32 columns x 2 blocks of 16 k x C taps
-    const int x = e & 31, blk = (e >> 5) & 1, cp = e >> 6;
-    float f[16];
-    int64_t cell;
-    if (kind == 1) {                // k = c*B + b (16 consecutive b), n = a
-#pragma unroll
-      for (int r = 0; r < 16; ++r) f[r] = tile[x][(16 * blk + r) * Cc + cp];
-      cell = (int64_t)((cp * B + b0) / 16 + blk) * N + a0 + x;
-    } else if (kind == 2) {         // k = c'*A + a (16 consecutive a), n = b
-      const int c = flip ? (Cc - 1 - cp) : cp;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) f[r] = tile[16 * blk + r][x * Cc + c];
-      cell = (int64_t)((cp * A + a0) / 16 + blk) * N + b0 + x;
-    } else {                        // k = a (16 consecutive a), n = c*B + b
-#pragma unroll
-      for (int r = 0; r < 16; ++r) f[r] = tile[16 * blk + r][x * Cc + cp];
-      cell = (int64_t)(a0 / 16 + blk) * N + cp * B + b0 + x;
-    }
-    u32x4* d = reinterpret_cast<u32x4*>(dst16 + cell * 16);
-    d[0] = pack8(f);
-    d[1] = pack8(f + 8);
-  }
-}
-
-// ... and the quad layouts of the fp32-tensor arithmetics (4 floats, or 4 hi | 4 lo bf16: pack_put) from the same tile -- the
-// element order of pack_kernel's tiled branch for a full 32 x 32 tile (round 5: the parity modes take the one-pass update too)
-__device__ __forceinline__ void pack_emit_quads(const float (*tile)[PK_T * PK_CMAX + 1], float* dst, int kind, int flip, int split,
-                                                int A, int B, int Cc, int a0, int b0) {
-  const int N = (kind == 1) ? A : (kind == 2 ? B : Cc * B);
-  const int run = PK_T * Cc;
-  for (int e = threadIdx.x; e < PK_T * run; e += 256) {
-    const int r = e & 3, x = (e >> 2) & 31, rest = e >> 7;   // rest in [0, 8*C)
-    if (kind == 1) {            // k = c*B + b, n = a: quads run along b, columns along a
-      const int c = rest >> 3, bq = rest & 7, bb = 4 * bq + r, ar = x;
-      pack_put(dst, (int64_t)((c * B + b0) / 4 + bq) * N + a0 + ar, r, tile[ar][bb * Cc + c], split);
-    } else if (kind == 2) {     // k = c'*A + a, n = b: quads along a, columns along b
-      const int cp = rest >> 3, aq = rest & 7, ar = 4 * aq + r, bb = x;
-      const int c = flip ? (Cc - 1 - cp) : cp;
-      pack_put(dst, (int64_t)((cp * A + a0) / 4 + aq) * N + b0 + bb, r, tile[ar][bb * Cc + c], split);
-    } else {                    // k = a, n = c*B + b
-      const int c = rest >> 3, aq = rest & 7, ar = 4 * aq + r, bb = x;
-      pack_put(dst, (int64_t)(a0 / 4 + aq) * N + c * B + b0 + bb, r, tile[ar][bb * Cc + c], split);
-    }
-  }
-}
-__device__ __forceinline__ void pack_emit(const float (*tile)[PK_T * PK_CMAX + 1], float* dst, int kind, int flip, int split, int A, int B,
-                                          int Cc, int a0, int b0) {
-  if (split == 2) pack_emit_cells(tile, reinterpret_cast<unsigned short*>(dst), kind, flip, A, B, Cc, a0, b0);
-  else pack_emit_quads(tile, dst, kind, flip, split, A, B, Cc, a0, b0);
 }
 
 // ------------------------------------------------------------------------------------------------ optimizer update rules
@@ -819,7 +769,9 @@ __global__ void __launch_bounds__(256) optim_kernel(float* __restrict__ p, const
   }
 }
 
-// One workgroup of the tiled re-layout: finds its job, updates its 32 x 32 x C tile of the fp32 master with 16-byte accesses to
+// One workgroup of the tiled re-layout (a flat list of the full 32 x 32 x C tiles of ALL jobs of the launch: no idle workgroups for
+// the small layers, and both layouts of a parameter -- forward and data-gradient operand -- from one read of the master): finds
+// its job, updates its 32 x 32 x C tile of the fp32 master with 16-byte accesses to
 // the master, the gradient and the rule's state arenas (all at the master's offsets plus a delta, in elements), and emits the
 // tile's layouts from LDS -- the weights are read once per step, and the update costs no launch of its own.  A DFL_PACK_PLAIN job
 // (something without a tiled layout) updates DFL_SGD_PLAIN_TILE elements as optim_kernel does, and emits nothing.
@@ -827,7 +779,7 @@ template <class Rule>
 __device__ __forceinline__ void pack_tile(const dfl_pack_job* __restrict__ jobs, int njobs, int64_t grad_delta, int64_t s1_delta,
                                           int64_t s2_delta, Rule r) {
   constexpr bool updates = !std::is_same<Rule, PackOnly>::value;
-  __shared__ float tile[PK_T][PK_T * PK_CMAX + 1];
+  __shared__ PackTile tile;
   // which job: the last one whose first_tile <= blockIdx.x (binary search; the few records stay in the scalar cache)
   int lo = 0, hi = njobs - 1;
   while (lo < hi) {
@@ -876,8 +828,8 @@ __device__ __forceinline__ void pack_tile(const dfl_pack_job* __restrict__ jobs,
     t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
   }
   __syncthreads();
-  pack_emit(tile, j.dst, j.kind, j.flip, j.split, A, B, Cc, a0, b0);
-  if (j.dst2 != nullptr) pack_emit(tile, j.dst2, j.kind2, j.flip2, j.split2, A, B, Cc, a0, b0);
+  pack_emit(tile, j.dst, j.kind, j.flip, j.split, A, B, Cc, a0, b0, PK_T, PK_T);
+  if (j.dst2 != nullptr) pack_emit(tile, j.dst2, j.kind2, j.flip2, j.split2, A, B, Cc, a0, b0, PK_T, PK_T);
 }
 
 // dfl_pack_weights_tiled

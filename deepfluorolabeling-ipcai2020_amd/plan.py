@@ -149,7 +149,6 @@ class _Block:
 
 class UNetPlan:
     # Switches: the DFL_* environment knobs are read once, at import; tests flip LIVE_BN, LIVE_HEAD and DPRE_OUT_BYTES.
-    PACK_TILED = os.environ.get('DFL_PACK_TILED', '1') != '0'     # weight layouts that tile into 32 x 32 x C blocks: dfl_pack_weights_tiled
     FUSE_BRB = os.environ.get('DFL_FUSE_BRB', '1') != '0'         # BatchNorm + ReLU backward inside the weight-/data-gradient staging (bf16 storage)
     FUSE_DOWN_STATS = os.environ.get('DFL_FUSE_DOWN_STATS', '1') != '0'   # ... and BN-backward sums from the strided-conv data gradient's scatter
     FLUSH_BYTES = int(float(os.environ.get('DFL_FLUSH_MB', '16')) * (1 << 20))   # queued sums flushed from here (4 / 16 / 64 MB: 0.414 / 0.373 / 0.367 ms per step)
@@ -187,7 +186,7 @@ class UNetPlan:
         self._red_bytes = 0
         self._red_flushes = []          # (index of the batch op in bwd, [dst pointers])
         self.partial_sum_bytes = 0      # bytes of fp32 partial sums the batched reductions of one backward pass read
-        self._tiled_host = self._tiled_index = None     # the tiled pack launch, for optim.py (see _finish_pack_tiled)
+        self._tiled_host = self._tiled_index = None     # the tiled pack launch, for optim.py (see _finish_pack)
         self.math = self.lib.dfl_get_math_mode()   # product arithmetic the plan is recorded for (split operand formats)
         # math mode 4, "bf16 storage": internal activations, their gradients and the GEMM copies of the weights are bf16
         # tensors (BASELINE configs[1] as named); statistics, losses, master weights and weight gradients stay fp32
@@ -322,28 +321,12 @@ class UNetPlan:
         return len(prog) - 1
 
     def _finish_pack(self):
-        """The pack program: the eval-mode BatchNorm prep of an inference plan, then the weight re-layouts."""
+        """The pack program: the eval-mode BatchNorm prep of an inference plan, then the weight re-layouts.  The layouts of
+        parameters that tile into 32 x 32 x C blocks go through dfl_pack_weights_tiled -- a flat list of tiles over all jobs, BOTH
+        layouts of a parameter (forward operand and data-gradient operand) from one read of the fp32 master --, everything else
+        (the first layer, heads, odd sizes) through dfl_pack_weights."""
         self.pack = Program()
         self.pack.extend(self._prep)
-        if not self._pack_jobs:
-            return
-        if self.PACK_TILED:
-            self._finish_pack_tiled()
-        else:
-            self._add_pack_launch(self._pack_jobs)
-
-    def _add_pack_launch(self, jobs):
-        """One dfl_pack_weights launch over a flat PackJob array."""
-        arr = (PackJob * len(jobs))()
-        for a, job in zip(arr, jobs):
-            self._set_pack_job(a, job)
-        mx = max(A * B * Cc for (_, _, A, B, Cc, _, _, _) in jobs)
-        self.pack.add(PackArgs(jobs_dev=self._upload(arr), max_elems=mx, njobs=len(jobs)))
-
-    def _finish_pack_tiled(self):
-        """One-stream pack (round 4; round 5: every arithmetic, not only bf16 storage): the layouts of parameters that tile into 32 x 32 x C blocks go through
-        dfl_pack_weights_tiled -- a flat list of tiles over all jobs, BOTH layouts of a parameter (forward operand and data-gradient
-        operand) from one read of the fp32 master --, everything else (the first layer, heads, odd sizes) through dfl_pack_weights."""
         tiled, rest, by_src = [], [], {}
         for job in self._pack_jobs:
             src, dst, A, B, Cc, kind, flip, split = job
@@ -370,8 +353,12 @@ class UNetPlan:
             srcs = [g[0][0].data_ptr() for g in tiled]
             if len(set(srcs)) == len(srcs):                   # (a parameter with a third layout: its second record would read
                 self._tiled_host = (bytes(arr), len(tiled), tiles, {g[0][0].data_ptr(): g[0][0].numel() for g in tiled})   # what the first one writes)
-        if rest:
-            self._add_pack_launch(rest)
+        if rest:                                         # one dfl_pack_weights launch over a flat PackJob array
+            arr = (PackJob * len(rest))()
+            for a, job in zip(arr, rest):
+                self._set_pack_job(a, job)
+            mx = max(A * B * Cc for (_, _, A, B, Cc, _, _, _) in rest)
+            self.pack.add(PackArgs(jobs_dev=self._upload(arr), max_elems=mx, njobs=len(rest)))
 
     # ------------------------------------------------------------------------------------------ op helpers
     def _conv(self, prog, x, w, y, KH, KW, stride, pad, Ntot, bias=None, in_aff=None, relu=0, add=None,

@@ -22,6 +22,7 @@ from conftest import PAPER_CFGS
 from oracle import ref_cpu as R
 import noise_floor as NF
 import problems as PR
+from pack_ref import dims as pack_dims
 from gpu_common import oracle64, label_mask, hip_net, hip_step
 
 pytestmark = pytest.mark.gpu
@@ -52,40 +53,19 @@ def nhwc(t):
 
 
 def pack16(w, kind, flip=0):
-    """dfl_pack_weights with split = 2: parameter [A][B][KH][KW] -> bf16 chunk layout [K/16][N][16]."""
+    """dfl_pack_weights with split = 2: parameter [A][B][KH][KW] -> bf16 chunk layout [K/16][N][16] (the layout itself:
+    tests/test_gpu_pack.py)."""
     lib = nat.lib()
     src = w.to(DEV).contiguous()
     A, B, KH, KW = w.shape
     Cc = KH * KW
-    K = {1: Cc * B, 2: Cc * A, 3: A}[kind]
-    N = {1: A, 2: B, 3: Cc * B}[kind]
+    K, N = pack_dims(kind, A, B, Cc)
     dst = torch.full(((K + 15) // 16 * N * 16,), float('nan'), device=DEV, dtype=BF)
     job = nat.PackJob(src=src.data_ptr(), dst=dst.data_ptr(), A=A, B=B, C=Cc, kind=kind, flip=flip, split=2)
     jobs = torch.from_numpy(np.frombuffer(bytes(job), dtype=np.uint8).copy()).to(DEV)
     nat.check(lib.dfl_pack_weights(jobs.data_ptr(), 1, A * B * Cc, stream()))
     torch.cuda.synchronize()
     return dst
-
-
-def test_pack_bf16_chunk_layout():
-    g = torch.Generator().manual_seed(1)
-    for (A, B, KK, kind, flip) in ((32, 16, 3, 1, 0), (32, 16, 3, 2, 1), (64, 32, 1, 1, 0), (48, 16, 2, 3, 0), (16, 32, 2, 1, 0)):
-        w = torch.randn(A, B, KK, KK, generator=g)
-        Cc = KK * KK
-        wn = w.reshape(A, B, Cc).numpy()
-        if kind == 1:
-            W = wn.transpose(2, 1, 0).reshape(Cc * B, A)
-        elif kind == 2:
-            W = wn[:, :, ::-1].transpose(2, 0, 1).reshape(Cc * A, B) if flip else wn.transpose(2, 0, 1).reshape(Cc * A, B)
-        else:
-            W = wn.transpose(0, 2, 1).reshape(A, Cc * B)
-        K, N = W.shape
-        Kc = (K + 15) // 16
-        ref = np.zeros((Kc * 16, N), dtype=np.float32)
-        ref[:K] = W
-        ref = torch.from_numpy(ref.reshape(Kc, 16, N).transpose(0, 2, 1).reshape(-1).copy()).to(BF)
-        got = pack16(w, kind, flip).cpu()
-        assert torch.equal(got, ref), (A, B, KK, kind, flip)
 
 
 def conv_bf16(x, wp, Ntot, KH, KW, stride, pad, Hout, Wout, bias=None, in_aff=None, relu=0, add=None, add_aff=None,

@@ -25,6 +25,7 @@ import torch
 
 from dfl_amd import _native as nat
 import finalize_ref as FR
+import pack_ref as PK
 from test_gpu_streaming import Buf, DEV, GUARD, U, assert_bits, assert_close, gen, stream
 
 pytestmark = pytest.mark.gpu
@@ -765,7 +766,8 @@ def test_update_with_tiled_relayout(rule, which):
         if not j.get('plain'):
             j['dst'] = layout_buf(j, j['split'])
             j['dst2'] = layout_buf(j, j['split2']) if 'kind2' in j else None
-    # what is expected: the flat kernel over each job's elements, then dfl_pack_weights_tiled on the updated master
+    # what is expected: the flat kernel over each job's elements, then dfl_pack_weights_tiled on the updated master (and, below,
+    # tests/pack_ref.py's bytes of that master: the two launches share their emitters)
     for j in jobs:
         a, n = j['at'], j['n']
         dev = [values[o + a:o + a + n].to(DEV) if on else None for o, on in ((0, True), (gd, True), (d1, has1), (d2, has2))]
@@ -804,10 +806,14 @@ def test_update_with_tiled_relayout(rule, which):
             if exp is not None:
                 assert_bits(bits[o + a:o + a + n], exp, 'fused %s job %d: %s against the flat kernel' % (rule, k, name))
         if not j.get('plain'):
-            for b, ref in ((j['dst'], j['ref_dst']), (j['dst2'], j['ref_dst2'])):
+            updated = j['expect'][0].view(torch.float32).numpy().reshape(j['A'], j['B'], j['C'])
+            for b, ref, form in ((j['dst'], j['ref_dst'], (j['kind'], j.get('flip', 0), j['split'])),
+                                 (j['dst2'], j['ref_dst2'], (j.get('kind2'), j.get('flip2'), j.get('split2')))):
                 if b is not None:
                     got = next(layouts)[1]
                     assert_bits(got, ref.cpu()[b.off:b.off + got.numel()], 'fused %s job %d: a layout against dfl_pack_weights_tiled' % (rule, k))
+                    assert_bits(got.contiguous().view(torch.uint8), torch.from_numpy(PK.encode(updated, *form)),
+                                'fused %s job %d: a layout against pack_ref of the updated master' % (rule, k))
 
 
 # ---------------------------------------------------------------------------------------------------- refusals

@@ -11,6 +11,7 @@ import torch.nn.functional as F
 import dfl_amd
 from dfl_amd import _native as nat
 from oracle import ref_cpu as R
+from pack_ref import dims as pack_dims
 
 pytestmark = pytest.mark.gpu
 
@@ -45,13 +46,13 @@ def nchw(t):
 
 
 def pack(w, kind, flip=0, split=0):
-    """Run one dfl_pack_weights job on the device: parameter [A][B][KH][KW] -> quad-packed GEMM operand."""
+    """Run one dfl_pack_weights job on the device: parameter [A][B][KH][KW] -> quad-packed GEMM operand (the layouts themselves:
+    tests/test_gpu_pack.py)."""
     lib = nat.lib()
     src = w.to(DEV).contiguous()
     A, B, KH, KW = w.shape
     Cc = KH * KW
-    K = {1: Cc * B, 2: Cc * A, 3: A}[kind]
-    N = {1: A, 2: B, 3: Cc * B}[kind]
+    K, N = pack_dims(kind, A, B, Cc)
     dst = torch.full(((K + 3) // 4 * N * 4,), float('nan'), device=DEV)
     job = nat.PackJob(src=src.data_ptr(), dst=dst.data_ptr(), A=A, B=B, C=Cc, kind=kind, flip=flip, split=split)
     jobs = torch.from_numpy(np.frombuffer(bytes(job), dtype=np.uint8).copy()).to(DEV)
@@ -134,58 +135,6 @@ def conv_call(x, wp, Ntot, KH, KW, stride, pad, Hout, Wout, bias=None, in_aff=No
     torch.cuda.synchronize()
     y = yd.cpu()[..., :Cout]
     return (y, part.cpu().double().sum(0)) if stats else y
-
-
-@pytest.mark.parametrize('shape', [(64, 32, 3), (48, 20, 3), (7, 5, 3), (32, 1, 3), (128, 64, 1), (16, 16, 2), (6, 10, 2)])
-def test_pack_weights_layout(shape):
-    """All three index maps of dfl_pack_weights (tiled and element-wise paths) against a numpy construction."""
-    A, B, KK = shape
-    g = torch.Generator().manual_seed(A + B)
-    w = torch.randn(A, B, KK, KK, generator=g)
-    Cc = KK * KK
-    wn = w.reshape(A, B, Cc).numpy()
-    for kind, flip in ((1, 0), (2, 1), (2, 0), (3, 0)):
-        if kind == 1:
-            W = wn.transpose(2, 1, 0).reshape(Cc * B, A)                       # k = c*B + b, n = a
-        elif kind == 2:
-            src = wn[:, :, ::-1] if flip else wn
-            W = src.transpose(2, 0, 1).reshape(Cc * A, B)                      # k = c'*A + a, n = b
-        else:
-            W = wn.transpose(0, 2, 1).reshape(A, Cc * B)                       # k = a, n = c*B + b
-        K, N = W.shape
-        Kq = (K + 3) // 4
-        ref = np.zeros((Kq * 4, N), dtype=np.float32)
-        ref[:K] = W
-        ref = ref.reshape(Kq, 4, N).transpose(0, 2, 1).reshape(-1)
-        got = pack(w, kind, flip).cpu().numpy()
-        assert np.array_equal(got, ref), (shape, kind, flip)
-
-
-@pytest.mark.parametrize('shape', [(64, 32, 3), (32, 64, 1), (128, 96, 2), (64, 64, 3)])
-@pytest.mark.parametrize('split', [0, 1])
-def test_pack_weights_tiled_quad_layouts(shape, split):
-    """dfl_pack_weights_tiled writes the fp32 quad layouts (and the split hi | lo bf16 quads) too (round 5: the update inside the
-    weight re-layout for the parity arithmetics): both layouts of a job, bit for bit what dfl_pack_weights writes."""
-    lib = nat.lib()
-    A, B, KK = shape
-    w = torch.randn(A, B, KK, KK, generator=torch.Generator().manual_seed(A * B + KK))
-    src = w.to(DEV).contiguous()
-    Cc = KK * KK
-    for (k1, f1), (k2, f2) in (((1, 0), (2, 1)), ((3, 0), (1, 0)), ((2, 0), (3, 0))):
-        def size(kind):
-            K = {1: Cc * B, 2: Cc * A, 3: A}[kind]
-            N = {1: A, 2: B, 3: Cc * B}[kind]
-            return (K + 3) // 4 * N * 4
-        d1 = torch.full((size(k1),), float('nan'), device=DEV)
-        d2 = torch.full((size(k2),), float('nan'), device=DEV)
-        job = nat.PackJob(src=src.data_ptr(), dst=d1.data_ptr(), A=A, B=B, C=Cc, kind=k1, flip=f1, split=split, dst2=d2.data_ptr(),
-                          kind2=k2, flip2=f2, first_tile=0, split2=split)
-        jobs = torch.from_numpy(np.frombuffer(bytes(job), dtype=np.uint8).copy()).to(DEV)
-        nat.check(lib.dfl_pack_weights_tiled(jobs.data_ptr(), 1, (A // 32) * (B // 32), stream()), 'dfl_pack_weights_tiled')
-        torch.cuda.synchronize()
-        r1, r2 = pack(w, k1, f1, split), pack(w, k2, f2, split)
-        assert torch.equal(d1.view(torch.int32), r1.view(torch.int32)), (shape, split, k1, f1)
-        assert torch.equal(d2.view(torch.int32), r2.view(torch.int32)), (shape, split, k2, f2)
 
 
 CONV_CASES = [
