@@ -20,6 +20,8 @@ from . import drr
 from .drr import hu_to_mu
 from . import register
 from . import labels
+from . import boundary
+from .boundary import DiceBoundaryLoss2D, DiceHeatMapBoundaryLoss2D
 from . import tools
 from . import synth
 from .synth import synthesize
@@ -27,4 +29,4 @@ from .synth import synthesize
 __all__ = ['UNet', 'DiceLoss2D', 'DiceAndHeatMapLoss2D', 'ncc_2d', 'center_crop', 'get_device', 'WarmRestartLR', 'SGD',
            'Adam', 'RMSprop', 'DataParallel', 'parallel', 'DeviceAugment', 'preprocess', 'out_size', 'map_lands', 'unmap_lands',
            'preprocess_projs', 'preprocess_segs', 'restore_labels', 'convert_file', 'drr', 'hu_to_mu', 'register', 'labels', 'tools', 'synth',
-           'synthesize']
+           'synthesize', 'boundary', 'DiceBoundaryLoss2D', 'DiceHeatMapBoundaryLoss2D']

@@ -1703,6 +1703,74 @@ typedef struct {
 int dfl_drr_tools(const dfl_tools_args* a, dfl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Boundary loss (csrc/boundary.hip; tests/boundary_ref.py restates this text in numpy): the signed
+ * distance maps of a batch of one-hot targets and the term of Kervadec et al. (MIDL 2019) on them, fused with the value
+ * and the gradient of dfl_dice_ncc_loss.
+ *
+ * Labels.  tseg is the one-hot target [B, C, h, w] fp32 seen through element strides (sN, sC, sH; unit stride along w), as
+ * dfl_dice_ncc_loss takes it.  g[b][p] = argmax_c tseg[b][c][p], the first maximum winning (torch.max's rule).
+ * Regions.  S_c = the pixels of image b with g == c;  D2(p, A) = the exact squared Euclidean distance from p to the
+ * nearest pixel of A: dfl_label_edt with boundary = 0.
+ * Signed distance map, per (b, c), in pixels of the target grid:
+ *   phi[b][c][p] = 0                                      for every p when S_c is empty or the whole image;
+ *   phi[b][c][p] = +sqrt(D2(p, S_c))                      for p outside S_c (>= 1);
+ *   phi[b][c][p] = -(sqrt(D2(p, complement of S_c)) - 1)  for p in S_c (<= 0; the pixels just inside the edge get 0).
+ * This is one_hot2dist of the paper's code: edt(neg) * neg - (edt(pos) - 1) * pos.  Zeros are +0.0.  The root is taken
+ * in double and rounded once: (float) sqrt((double) d2) outside, (float) (1.0 - sqrt((double) d2)) inside, so a perfect
+ * square gives its exact root.
+ *
+ * dfl_boundary_maps: phi dense [B][C][h][w] fp32, 16-byte aligned for the 16-byte loads of dfl_boundary_loss.  Three
+ * stages on the caller's stream, nothing read back: (1) arg-max -> uint8 labels in scratch; (2) dfl_label_edt over pairs
+ * of label sets -- {c} and "every label < C but c" -- in chunks of images x classes of at most 15 pairs (30 of the 31 sets
+ * a call takes) whose int32 planes stay below 256 MiB (a single pair may exceed that); (3) per chunk, combine: a pixel
+ * reads its label and the plane that applies to it; DFL_LABEL_EDT_NONE there says "class absent" (outside) or "class
+ * fills the image" (inside), which is the zero rule without a reduction of its own.  Nothing reaches across images: an
+ * image has the same bits alone and inside any batch.  scratch: dfl_boundary_maps_scratch_bytes(B, C, h, w) bytes (an
+ * int: negative on a refusal, and when the count exceeds 2^31 - 1), 16-byte aligned.
+ * Refused before any pointer is followed: B, h or w < 1, C outside 2..DFL_LABEL_MAX_CLASSES, (h-1)^2 + (w-1)^2 >=
+ * 2^31 - 1 (the size condition of dfl_label_edt), a scratch beyond 2^31 - 1 bytes, NULL pointers, a misaligned scratch.
+ *
+ * Term.  L_B = (1/N) sum over b, c >= skip_bg, p of seg[b][c][p] * phi[b][c][p],  N = B (C - skip_bg) h w;
+ *        d(beta L_B) / d seg[b][c][p] = beta phi[b][c][p] / N for c >= skip_bg, 0 for a skipped background channel.
+ * dfl_boundary_loss, stage 1: the sum in float64 in a fixed order (csrc/fixed_sum.h: wave shuffle, four waves through
+ * LDS, one record per workgroup in sums, the records in index order; no float atomics; the pixel-to-thread assignment is
+ * fixed by the shape, so two runs give the same bits).  Then one thread: *loss = (float)(beta L_B), or with
+ * accumulate_loss *loss = (float)((double) *loss + beta L_B) -- onto the value dfl_dice_ncc_loss stage 1 left there, one
+ * rounding.  sums holds dfl_boundary_loss_scratch_doubles(B, C, h) doubles (an int, at most 1024; 0 on sizes < 1).
+ * Stage 2: dseg[b][c][p] = k phi[b][c][p] with k = *grad_scale * (float)(beta / N) (grad_scale: a DEVICE scalar, NULL =
+ * 1), through element strides (all 0 = dense [B][C][h][w]).  With accumulate_grad the product is added onto what is
+ * there -- what dfl_dice_ncc_loss stage 2 wrote, launched before on the same stream -- and a skipped background channel
+ * is left alone; without, that channel is written as zeros.
+ * Both stages stream rows: 256 threads, a wave per row of an (image, class), at most 1024 workgroups; 16-byte accesses
+ * of phi, and of seg / dseg on the rows whose address allows it (a centre-crop window starts at any column), 4-byte
+ * ones otherwise and for the head and tail of a row; 64-bit offsets.
+ * Refused before any pointer is followed: a NULL block, sizes as above (h w < 2^31 follows), stage other than 1 or 2,
+ * a beta that is not finite, NULL phi, NULL seg / loss / sums in stage 1, NULL dseg in stage 2, gradient strides of
+ * which some but not all are 0.
+ * ------------------------------------------------------------------------------------------------------------ */
+int dfl_boundary_maps_scratch_bytes(int32_t B, int32_t C, int32_t h, int32_t w);
+int dfl_boundary_maps(const float* tseg, int64_t sN, int64_t sC, int64_t sH, int32_t B, int32_t C, int32_t h, int32_t w,
+                      float* phi, void* scratch, dfl_stream_t stream);
+typedef struct {
+  const float* seg;               /* [B, C, h, w] through seg_s*; stage 1 */
+  const float* phi;               /* dense [B][C][h][w], dfl_boundary_maps */
+  float* loss;                    /* 1 float; stage 1 */
+  double* sums;                   /* dfl_boundary_loss_scratch_doubles(B, C, h) doubles; stage 1 */
+  const float* grad_scale;        /* device scalar or NULL (= 1); stage 2 */
+  float* dseg;                    /* [B, C, h, w] through dseg_s* (all 0: dense); stage 2 */
+  int64_t seg_sN, seg_sC, seg_sH;
+  int64_t dseg_sN, dseg_sC, dseg_sH;
+  int32_t B, C, h, w;
+  int32_t skip_bg;
+  int32_t stage;                  /* 1: value, 2: gradient */
+  int32_t accumulate_loss, accumulate_grad;
+  float beta;
+  int32_t reserved;               /* not read */
+} dfl_boundary_loss_args;
+int dfl_boundary_loss_scratch_doubles(int32_t B, int32_t C, int32_t h);
+int dfl_boundary_loss(const dfl_boundary_loss_args* a, dfl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Product arithmetic of the convolution / weight-gradient GEMMs (fast paths; odd channel counts always use fp32):
  *   0 "fp32"    v_mfma_f32_32x32x2_f32: fp32 products, fp32 accumulation.
  *   1 "bf16x3"  every fp32 operand value is split into hi + lo bf16 parts when it is staged in LDS and the product is

@@ -20,7 +20,9 @@ batch is --batch-size x world size.
         --nesterov --wgt-decay 1e-4
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 train.py data.h5 ...
 
-Extensions (not in the reference): --math, --seed, --dist-backend.  Refused loudly: --no-gpu (there is no CPU path).
+Extensions (not in the reference): --math, --seed, --dist-backend, and --boundary-coeff / --boundary-ramp (the boundary-
+distance term of dfl_amd.boundary in the training loss; validation stays on Dice and heat maps).  Refused loudly: --no-gpu
+(there is no CPU path).
 --data-aug runs the reference's augmentation recipe on the device (dfl_amd.DeviceAugment), its
 draws seeded from --seed (or a fresh system seed, broadcast to every rank).  The data file is the
 reference's HDF5 layout (read by the dependency-free dfl_amd.h5lite) or an .npz with the same dataset names.
@@ -104,7 +106,15 @@ def build_parser():
     return p
 
 
-EXTENSION_FLAGS = {'math': None, 'seed': None, 'dist_backend': None, 'sync_loss': False, 'grad_compress': None}
+EXTENSION_FLAGS = {'math': None, 'seed': None, 'dist_backend': None, 'sync_loss': False, 'grad_compress': None,
+                   'boundary_coeff': None, 'boundary_ramp': 0}
+
+
+def _ramp_epochs(text):
+    value = int(text)
+    if value < 0:
+        raise argparse.ArgumentTypeError('--boundary-ramp takes a number of epochs >= 0, not {}'.format(text))
+    return value
 
 
 def build_full_parser():
@@ -119,7 +129,19 @@ def build_full_parser():
                    help='data parallel: all-reduce the gradient buckets as bf16 (half the xGMI bytes; default: fp32)')
     p.add_argument('--sync-loss', action='store_true', help='read every minibatch loss right after its optimizer step, as the '
                                                              'reference does (default: one step late, the GPU never waits for the host)')
+    p.add_argument('--boundary-coeff', type=float, default=None, nargs='?', const=0.01,
+                   help='add this weight times the boundary-distance term (Kervadec et al. 2019) to the training loss; 0.01 '
+                        'when given without a value.  Not stored in checkpoints: give it again when resuming')
+    p.add_argument('--boundary-ramp', type=_ramp_epochs, default=0,
+                   help='with --boundary-coeff B: train epoch e with B * min(1, (e + 1) / E) for this E > 0 (default 0: B from '
+                        'the first epoch); e counts from the checkpoint when resuming')
     return p
+
+
+def boundary_weight(coeff, ramp, epoch):
+    """The weight of the boundary term in (0-based) epoch `epoch`: it comes in over the first `ramp` epochs, while Dice has
+    already found the bones."""
+    return coeff * min(1.0, (epoch + 1) / ramp) if ramp > 0 else coeff
 
 
 # ----------------------------------------------------------------------------------------------------- settings
@@ -302,7 +324,17 @@ class Trainer:
             self.net.load_state_dict(resume['model-state-dict'])
         self.net.to(self.dev)
         self.dp = dfl_amd.DataParallel(self.net, compress=self.args.grad_compress) if self.world > 1 else None   # broadcasts rank 0's weights
-        if c['num-lands'] > 0:
+        coeff = self.args.boundary_coeff
+        if coeff is not None:                            # a property of the command line, like --math: not in checkpoints
+            ramp = self.args.boundary_ramp
+            if c['num-lands'] > 0:
+                self.say('loss: Dice + heat-map NCC (weight {}) + boundary distance (weight {}, ramp {})'.format(
+                    c['heat-coeff'], coeff, ramp))
+                self.criterion = dfl_amd.DiceHeatMapBoundaryLoss2D(skip_bg=False, heatmap_wgt=c['heat-coeff'], boundary_wgt=coeff)
+            else:
+                self.say('loss: Dice + boundary distance (weight {}, ramp {})'.format(coeff, ramp))
+                self.criterion = dfl_amd.DiceBoundaryLoss2D(skip_bg=False, boundary_wgt=coeff)
+        elif c['num-lands'] > 0:
             self.say('loss: Dice + heat-map NCC (weight {})'.format(c['heat-coeff']))
             self.criterion = dfl_amd.DiceAndHeatMapLoss2D(skip_bg=False, heatmap_wgt=c['heat-coeff'])
         else:
@@ -362,6 +394,8 @@ class Trainer:
         cosine = self.sched is not None and c['lrs-meth'] == 'cos'
         report_every = int(0.05 * n_images)              # running average printed every 5 % of an epoch's images
         net.train()
+        if self.args.boundary_coeff is not None:
+            self.criterion.boundary_wgt = boundary_weight(self.args.boundary_coeff, self.args.boundary_ramp, self.epoch)
         seen = steps = 0
         self._acc = [0.0, 0, 0.0, 0, report_every]       # total, steps, window sum, window count, window length
         late = util.LateScalars(depth=0 if self.args.sync_loss else 1)   # loss values are read one step late (util.LateScalars)
