@@ -315,7 +315,7 @@ __global__ void __launch_bounds__(256) aug_write_kernel(const dfl_augment_args a
     const float kexp = 1.f / (s2 * -2.f), knorm = 1.f / (2.f * 3.14159265358979323846f * s2);
     for (int l = 0; l < a.L; ++l) {
       const float lx = lin[l], ly = lin[a.L + l];
-      float mx = INFINITY, my = INFINITY;
+      float mx = lx, my = ly;                                   // dataset.py:242: an inf coordinate leaves the pair as it is
       if (!isinf(lx) && !isinf(ly)) {
         const double X = M[0] * (double)lx + M[1] * (double)ly + M[2], Y = M[3] * (double)lx + M[4] * (double)ly + M[5];
         bool drop = false;
@@ -323,10 +323,8 @@ __global__ void __launch_bounds__(256) aug_write_kernel(const dfl_augment_args a
           drop = X < 0.0 || X > (double)(a.H - 1) || Y < 0.0 || Y < (double)(a.C - 1);
         else if (a.land_rule == DFL_AUG_LANDS_IN_VIEW)
           drop = X < 0.0 || X > (double)(a.W - 1) || Y < 0.0 || Y > (double)(a.H - 1);
-        if (!drop) {
-          mx = (float)X;
-          my = (float)Y;
-        }
+        mx = drop ? INFINITY : (float)X;
+        my = drop ? INFINITY : (float)Y;
       }
       if (t0 == 0) {
         lout[l] = mx;

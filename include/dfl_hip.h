@@ -676,7 +676,9 @@ typedef struct {
   float noise_sigma, gamma;
   int32_t row;                  /* batch row this item overwrites */
   int32_t flags;                /* DFL_AUG_* */
-  int32_t n_box;                /* 0..5 */
+  int32_t n_box;                /* 0..5 (more: the first 5); a box that does not fit the image or has a side <= 0
+                                   ends the list: the boxes before it apply, it and those after it do not.  An item
+                                   whose row is outside [0, B) is skipped: it writes no output, levels or noise */
   int32_t reserved;
 } dfl_augment_item;
 typedef struct {
