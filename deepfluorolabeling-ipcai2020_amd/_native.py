@@ -39,7 +39,8 @@ _SIZEOF_ORDER = [ConvArgs, WgradArgs, PackJob, BnFinalizeArgs, ColstatsArgs, BnB
                  UpsampleArgs, AugmentArgs, AugmentItem, OverlayArgs, ResamplePlan, ResampleArgs, FullresArgs, MeshMcArgs, MeshDecodeArgs,
                  MeshTopoArgs, MeshCsrArgs, MeshSmoothArgs, MeshXformArgs, MeshNormalsArgs, MeshQuadricsArgs,
                  MeshCollapseKeysArgs, MeshCollapseSelectArgs, MeshCollapseApplyArgs, PreprocProjsArgs, PreprocSegsArgs,
-                 RestoreLabelsArgs, SimPrepareArgs, SimGradnccArgs, ExposeArgs, ToolsCapsule, ToolsArgs, SimPatchPrepareArgs, SimPatchGradnccArgs, RasterMesh, RasterArgs,
+                 RestoreLabelsArgs, SimPrepareArgs, SimGradnccArgs, ExposeArgs, ToolsCapsule, ToolsArgs, SimMiPrepareArgs, SimMiArgs, SimMiBwdArgs,
+                 SimPatchPrepareArgs, SimPatchGradnccArgs, RasterMesh, RasterArgs,
                  SimGradnccBwdArgs, SimPatchWeightsArgs, SimPatchEvalArgs, DrrPoseGradArgs, SimBankGradnccArgs, SimBankGradnccBwdArgs, SimPatchBankGradnccArgs, DrrObject, DrrArgs,
                  OptimPackArgs]
 

@@ -89,6 +89,7 @@ extern "C" int dfl_sizeof(int which) {
       (int)sizeof(dfl_preproc_projs_args),   (int)sizeof(dfl_preproc_segs_args),
       (int)sizeof(dfl_restore_labels_args), (int)sizeof(dfl_sim_prepare_args),  (int)sizeof(dfl_sim_gradncc_args),
       (int)sizeof(dfl_expose_args),     (int)sizeof(dfl_tools_capsule),         (int)sizeof(dfl_tools_args),
+      (int)sizeof(dfl_sim_mi_prepare_args), (int)sizeof(dfl_sim_mi_args), (int)sizeof(dfl_sim_mi_bwd_args),
       (int)sizeof(dfl_sim_patch_prepare_args), (int)sizeof(dfl_sim_patch_gradncc_args),
       (int)sizeof(dfl_raster_mesh),    (int)sizeof(dfl_raster_args),
       (int)sizeof(dfl_sim_gradncc_bwd_args), (int)sizeof(dfl_sim_patch_weights_args), (int)sizeof(dfl_sim_patch_eval_args),

@@ -4,7 +4,7 @@ set -euo pipefail
 here="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 out="$here/../lib"
 mkdir -p "$out"
-srcs=(api.hip conv_gemm.hip conv_plan.hip conv_rows.hip convp_bf16.hip convq_bf16.hip convn_bf16.hip convs.hip wgradp_bf16.hip wgrad_gemm.hip direct_small.hip bn_elem.hip head.hip loss.hip prep.hip augment.hip upsample.hip overlay.hip overlay_fullres.hip mesh.hip decimate.hip preproc.hip drr.hip drr_grad.hip sim.hip sim_patch.hip sim_outline.hip expose.hip drr_tools.hip raster.hip labels.hip labels_dist.hip boundary.hip)
+srcs=(api.hip conv_gemm.hip conv_plan.hip conv_rows.hip convp_bf16.hip convq_bf16.hip convn_bf16.hip convs.hip wgradp_bf16.hip wgrad_gemm.hip direct_small.hip bn_elem.hip head.hip loss.hip prep.hip augment.hip upsample.hip overlay.hip overlay_fullres.hip mesh.hip decimate.hip preproc.hip drr.hip drr_grad.hip sim.hip sim_patch.hip sim_outline.hip sim_mi.hip expose.hip drr_tools.hip raster.hip labels.hip labels_dist.hip boundary.hip)
 objs=()
 pids=()
 # one hipcc per source, at most $MAX_JOBS (default 16) at a time
@@ -28,8 +28,9 @@ for s in "${srcs[@]}"; do
     # the augmentation rounds every product and sum separately, as its numpy restatement (tests/aug_ref.py) does, and the
     # overlays as torch's CPU ops do (an FMA moves results across the 8-bit truncation boundaries)
     # (so does the detector model, as tests/expose_ref.py does, the rasteriser, as tests/raster_ref.py does, and the
-    # decimation, as tests/decimate_ref.py does, and the tool chords, as tests/tools_ref.py does)
-    case "$s" in augment.hip|overlay.hip|overlay_fullres.hip|expose.hip|drr_tools.hip|raster.hip|decimate.hip) extra="-ffp-contract=off";; esac
+    # decimation, as tests/decimate_ref.py does, and the tool chords, as tests/tools_ref.py does, and the bins and Parzen
+    # weights of the mutual-information cost, as tests/mi_ref.py does)
+    case "$s" in augment.hip|overlay.hip|overlay_fullres.hip|expose.hip|drr_tools.hip|raster.hip|decimate.hip|sim_mi.hip) extra="-ffp-contract=off";; esac
     if [ "${#pids[@]}" -ge "$jobs_max" ]; then
       wait "${pids[0]}"
       pids=("${pids[@]:1}")

@@ -19,6 +19,9 @@ patch_weight='variance' weighs every patch by the energy of its fixed gradient (
 similarity='outline' matches the bone outlines of a predicted label map instead of intensities: the exact render writes the
 label map of every candidate, dfl_label_edt their boundary distance maps, and dfl_sim_outline (csrc/sim_outline.hip,
 OutlineSimilarity) the truncated chamfer cost against the segmentation's; section 26 and tests/outline_ref.py.
+similarity='mi' is the negative mutual information of the intensities (MISimilarity: dfl_sim_mi, csrc/sim_mi.hip), from a joint
+histogram of integers: it needs neither a known intensity mapping of the fixed image nor edges, and has an adjoint
+(dfl_sim_mi_bwd), so refine works with it; section 29 and tests/mi_ref.py.
 
     D(theta) = [[R, centre - R centre + theta[3:]], [0, 1]],  R = exp(rot_unit theta[:3])      (pose_delta)
     P(theta) = D(theta) P0                                   a cam-to-*-vol matrix as in gt-poses
@@ -35,7 +38,7 @@ from . import drr, preprocess
 from . import labels as _labels
 
 __all__ = ['se3_exp', 'se3_log', 'pose_delta', 'pose_deltas', 'pose_delta_jacobians', 'pnp', 'cma_es', 'cma_steps', 'CmaResult', 'bfgs', 'bfgs_steps', 'BfgsResult', 'lockstep',
-           'Similarity', 'PatchSimilarity', 'SimilarityBank', 'PatchSimilarityBank', 'OutlineSimilarity', 'fixed_of_array', 'landmark_penalty', 'register',
+           'Similarity', 'PatchSimilarity', 'SimilarityBank', 'PatchSimilarityBank', 'OutlineSimilarity', 'MISimilarity', 'fixed_of_array', 'landmark_penalty', 'register',
            'register_many', 'default_max_views', 'Registration', 'with_pelvis_pose', 'volume_centre']
 
 ROT_UNIT = 0.02
@@ -711,6 +714,134 @@ class OutlineSimilarity:
         return out
 
 
+# ---- mutual information -----------------------------------------------------------------------------------------------
+def _mi_bins(bins):
+    """bins as (Bf, Bm): an integer for both, or a pair; each 2 .. SIM_MI_MAX_BINS."""
+    pair = (bins, bins) if isinstance(bins, (int, np.integer)) else tuple(bins) if isinstance(bins, (tuple, list)) else ()
+    if len(pair) != 2 or any(isinstance(b, bool) or not isinstance(b, (int, np.integer)) or not 2 <= b <= nat.SIM_MI_MAX_BINS for b in pair):
+        raise nat.DflError('register: mi_bins = %r (an integer or a pair (Bf, Bm) of integers, each 2..%d)' % (bins, nat.SIM_MI_MAX_BINS))
+    return int(pair[0]), int(pair[1])
+
+
+def _mi_range(lo, hi):
+    """(lo, hi) as float32 scalars, checked on the host: finite, hi > lo, also after rounding."""
+    try:
+        lo32, hi32 = np.float32(lo), np.float32(hi)
+    except (TypeError, ValueError):
+        lo32 = hi32 = np.float32('nan')
+    if not (np.isfinite(lo32) and np.isfinite(hi32) and hi32 > lo32):
+        raise nat.DflError('register: an mi_range of (%r, %r): two finite numbers with hi > lo' % (lo, hi))
+    return lo32, hi32
+
+
+class MISimilarity:
+    """The mutual-information cost of `views` moving images against a fixed image [H, W] (float32, on the
+    GPU), or a bank [F, H, W], with an optional uint8 mask of the same shape: cost = -MI of the joint histogram of the moving
+    intensity (Bm bins over the moving range, a first-order Parzen window in units of 1/4096 pixel) and the fixed intensity
+    (Bf bins between the smallest and largest counted value).  bins is an integer or (Bf, Bm).  A pixel counts when its fixed
+    value is finite and its mask byte non-zero; the fixed image needs no known intensity mapping.  dfl_sim_mi_prepare runs here,
+    once per image.
+
+    The moving range is set with set_range (or moving_range=(lo, hi), or an [F, 2] array); until then every cost is NaN.
+    cost(moving [V, H, W], fixed_of=None) is one dfl_sim_mi launch and returns float64 [V] on the device; with a bank fixed_of says
+    which image a view is scored against, as SimilarityBank takes it (None: image 0).  cost_and_adjoint adds d cost / d moving
+    (dfl_sim_mi_bwd).  hist [views, Bm, Bf] (int64) holds the histograms of the last call in its first V rows."""
+
+    entry, _patches = 'dfl_sim_mi', False
+    fixed_of = SimilarityBank.fixed_of
+
+    def __init__(self, fixed, mask=None, views=1, bins=32, moving_range=None):
+        self.Bf, self.Bm = _mi_bins(bins)
+        self._bank = torch.is_tensor(fixed) and fixed.dim() == 3
+        dims = 3 if self._bank else 2
+        image, the_mask = ('the fixed images', 'the masks') if self._bank else ('the fixed image', 'the mask')
+        fixed = _device_image(fixed, image, dims)
+        dev, shape = fixed.device, tuple(int(s) for s in fixed.shape)
+        H, W = shape[-2:]
+        F = shape[0] if self._bank else 1
+        self.H, self.W, self.F, self.views, self._fixed_of = H, W, F, int(views), {}
+        if mask is not None:
+            mask = _device_image(mask, the_mask, dims, (torch.uint8,))
+            if tuple(mask.shape) != shape or mask.device != dev:
+                raise nat.DflError('register: %s of shape %s on %s, %s of shape %s on %s' % (the_mask, tuple(mask.shape), mask.device, image, shape, dev))
+        if H < 1 or W < 1 or not 1 <= F <= 65535 or F * H * W >= 2 ** 31 or not 1 <= self.views <= 65535:
+            raise nat.DflError('register: %d fixed images of %d x %d for %d views (1..65535 images and views, fewer than 2^31 pixels, none empty)'
+                               % (F, H, W, self.views))
+        self._banks = dict(fixed=fixed.reshape(F, H, W), mask=None if mask is None else mask.reshape(F, H, W),
+                           fbin=torch.empty((F, H, W), dtype=torch.uint8, device=dev),
+                           info=torch.empty((F, nat.SIM_MI_INFO), dtype=torch.float64, device=dev),
+                           mrange=torch.full((F, 2), float('nan'), dtype=torch.float32, device=dev))
+        sizes = dict(H=H, W=W, F=F, Bf=self.Bf, Bm=self.Bm, reserved=0)
+        for f in range(F):
+            drr.launch(dev, 'dfl_sim_mi_prepare', _block('dfl_sim_mi_prepare', dict({name: None if t is None else t[f].data_ptr()
+                                                                                      for name, t in self._banks.items()}, **sizes)))
+        for name, t in self._banks.items():                         # fixed, mask, fbin, info, mrange
+            setattr(self, name, t if self._bank or t is None else t[0])
+        self._fields = dict({name: nat.ptr(t) for name, t in self._banks.items()}, **sizes)
+        self.hist = torch.zeros((self.views, self.Bm, self.Bf), dtype=torch.int64, device=dev)
+        self.out = torch.empty(self.views, dtype=torch.float64, device=dev)
+        self.ell = None                                             # cost_and_adjoint makes it when it first runs
+        if moving_range is not None:
+            pair = isinstance(moving_range, (tuple, list)) and len(moving_range) == 2 and np.ndim(moving_range[0]) == 0
+            self.set_range(*(moving_range if pair else (moving_range,)))
+
+    def set_range(self, lo, hi=None):
+        """The moving range: two numbers (checked here; the same for every image), or one [F, 2] tensor or array of (lo, hi) rows.
+        A float32 tensor on the device is copied as it is: values cannot be checked without a copy to the host, and an image
+        whose row is not finite or has hi <= lo makes its views void (cost NaN, zero adjoint)."""
+        rng = self._banks['mrange']
+        if hi is not None:
+            lo32, hi32 = _mi_range(lo, hi)
+            rng.copy_(torch.tensor([[float(lo32), float(hi32)]] * self.F, dtype=torch.float32))
+            return
+        if torch.is_tensor(lo) and lo.is_cuda:
+            if lo.dtype != torch.float32 or tuple(lo.shape) != (self.F, 2) or lo.device != rng.device:
+                raise nat.DflError('register: a moving range of shape %s and dtype %s on %s: float32 [%d, 2] on %s expected'
+                                   % (tuple(lo.shape), lo.dtype, lo.device, self.F, rng.device))
+            rng.copy_(lo.detach())
+            return
+        rows = np.asarray(lo.cpu() if torch.is_tensor(lo) else lo, np.float64)
+        if rows.shape != (self.F, 2):
+            raise nat.DflError('register: a moving range of shape %s: two numbers or [%d, 2] expected' % (rows.shape, self.F))
+        rng.copy_(torch.tensor([[float(v) for v in _mi_range(*row)] for row in rows], dtype=torch.float32))
+
+    _moving = Similarity._moving
+
+    def _args(self, entry, moving, fixed_of, out, ell=None, d_moving=None):
+        return _block(entry, dict(self._fields, moving=moving.data_ptr(), fixed_of=nat.ptr(fixed_of), hist=self.hist.data_ptr(), cost=out.data_ptr(),
+                                  ell=nat.ptr(ell), d_moving=nat.ptr(d_moving), V=int(moving.shape[0])))
+
+    def _which(self, fixed_of, V):
+        if fixed_of is None:                                        # every view against image 0
+            return None
+        if not self._bank:
+            raise nat.DflError('register: fixed_of belongs to a bank of fixed images [F, H, W]; this one is a single image')
+        return self.fixed_of(fixed_of, V)
+
+    def _launch(self, moving, fixed_of=None, out=None):
+        """One dfl_sim_mi on checked moving images; the costs go to `out` (default: the first rows of self.out)."""
+        drr.launch(moving.device, self.entry, self._args(self.entry, moving, self._which(fixed_of, int(moving.shape[0])), self.out if out is None else out))
+
+    def cost(self, moving, fixed_of=None):
+        mv = self._moving(moving)
+        out = torch.empty(mv.shape[0], dtype=torch.float64, device=mv.device)
+        self._launch(mv, fixed_of, out)
+        return out
+
+    def cost_and_adjoint(self, moving, fixed_of=None):
+        """(cost [V] float64, d_moving [V, H, W] float32 = d cost[v] / d moving[v] at the range as it is set) on the device: one
+        dfl_sim_mi_bwd launch.  The cost has the bits cost(moving) gives; clamped, NaN and uncounted pixels get exactly 0."""
+        mv = self._moving(moving)
+        V, dev = int(mv.shape[0]), mv.device
+        fixed_of = self._which(fixed_of, V)
+        if self.ell is None:
+            self.ell = torch.empty((self.views, self.Bm, self.Bf), dtype=torch.float64, device=dev)
+        out = torch.empty(V, dtype=torch.float64, device=dev)
+        d_moving = torch.empty((V, self.H, self.W), dtype=torch.float32, device=dev)
+        drr.launch(dev, 'dfl_sim_mi_bwd', self._args('dfl_sim_mi_bwd', mv, fixed_of, out, self.ell, d_moving))
+        return out, d_moving
+
+
 # ---- the landmark term -------------------------------------------------------------------------------------------------
 def _usable_landmarks(X3d, x2d, who):
     X = np.asarray(X3d, np.float64)
@@ -818,6 +949,54 @@ class _OutlineLevel(_Level):
         return recs, lab, keep
 
 
+class _MILevel(_Level):
+    """_Level for similarity='mi': an MISimilarity against the fixed image, or against a bank; the views are _Level's trilinear
+    renders.  start_range sets the moving range before the search."""
+
+    def __init__(self, volume, grid, fixed, mask, lam, step_mm, bins, bank=None):
+        self.volume, self.grid, self.lam, self.step_mm = volume, grid, lam, float(step_mm)
+        if bank is None and tuple(fixed.shape) != (grid.H, grid.W):
+            raise nat.DflError('register: the fixed image is %s, the output grid %d x %d' % (tuple(fixed.shape), grid.H, grid.W))
+        self.sim = MISimilarity(fixed, mask, lam, bins) if bank is None else MISimilarity(bank[0], bank[1], lam, bins)
+
+    def start_range(self, probs, starts, mi_range):
+        """The moving range of every problem: mi_range as given (0 views rendered), else (0, 1.25 x the largest value of the
+        problem's view at its start): one render of one view per problem.  Returns the views rendered per problem."""
+        if mi_range is not None:
+            self.sim.set_range(*mi_range)
+            return 0
+        c2is, masks, _ = _views(self, probs, list(range(len(probs))), [np.asarray(s, np.float64)[None] for s in starts])
+        recs, att, keep = self._render(c2is, masks)
+        top = att.reshape(att.shape[0], -1).amax(1)
+        seen = top.cpu().numpy()                                    # the copy waits for the render: `keep` lives until then
+        del keep
+        for i, t in enumerate(seen):
+            if not t > 0:
+                raise nat.DflError("register: nothing is in view at the start of problem %d (the largest value of its rendered view is %r): "
+                                   "similarity='mi' takes its moving range from that view; move the start or give mi_range" % (i, float(t)))
+        self.sim.set_range(torch.stack([torch.zeros_like(top), top * 1.25], 1))
+        return 1
+
+
+def _mi_options(similarity, mi_bins, mi_range, segmentation, outline_sets):
+    """The checks of similarity='mi', made before anything touches a device: ((Bf, Bm), the range or None), or (None, None) for
+    another similarity."""
+    if similarity != 'mi':
+        if mi_range is not None:
+            raise nat.DflError("register: mi_range belongs to similarity='mi', not to similarity=%r" % (similarity,))
+        return None, None
+    if segmentation is not None or outline_sets is not None:
+        raise nat.DflError("register: segmentation and outline_sets belong to similarity='outline', not to similarity='mi'")
+    bins = _mi_bins(mi_bins)
+    if mi_range is not None:
+        try:
+            lo, hi = mi_range
+        except (TypeError, ValueError):
+            raise nat.DflError('register: mi_range = (lo, hi) expected, got %r' % (mi_range,)) from None
+        mi_range = _mi_range(lo, hi)
+    return bins, mi_range
+
+
 def _outline_options(geom, segmentation, levels, mask, outline_cap):
     """The checks of register(similarity='outline'), made before anything touches a device."""
     if levels is not None or mask is not None:
@@ -864,8 +1043,8 @@ def _cost_options(refine, refine_tol, similarity, patch_radius, patch_stride, pa
     if refine > 0 and similarity == 'patch' and patch_weight == 'uniform':
         raise nat.DflError("register: refine needs the adjoint of the similarity, which similarity='patch' does not have yet "
                            "with patch_weight='uniform' (patch_weight='variance' has it)")
-    if similarity not in ('global', 'patch', 'outline'):
-        raise nat.DflError("register: similarity = %r ('global', 'patch' or 'outline')" % (similarity,))
+    if similarity not in ('global', 'patch', 'outline', 'mi'):
+        raise nat.DflError("register: similarity = %r ('global', 'patch', 'outline' or 'mi')" % (similarity,))
     if similarity != 'patch' and patch_weight != 'uniform':
         raise nat.DflError("register: patch_weight = %r belongs to similarity='patch'; similarity=%r has no patches" % (patch_weight, similarity))
     if similarity == 'outline' and refine > 0:
@@ -1025,7 +1204,8 @@ def _close(level, probs, means, refine, refine_tol, traces, renders, done):
 def register(volume, geom, fixed, moving=(0, 1, 2), theta0=None, P0=None, levels=None, popsize=16, generations=80, sigma0=2.0,
              step_mm=1.0, mask=None, seed=0, centre=None, rot_unit=ROT_UNIT, crop=0, rot180=False, sigma_shrink=0.5,
              similarity='global', patch_radius=7, patch_stride=4, patch_min_count=None, landmarks=None, landmark_weight=0.0,
-             refine=0, refine_tol=1e-4, patch_weight='uniform', segmentation=None, outline_sets=None, outline_cap=32.0):
+             refine=0, refine_tol=1e-4, patch_weight='uniform', segmentation=None, outline_sets=None, outline_cap=32.0, mi_bins=32,
+             mi_range=None):
     """Find theta such that the DRR of `volume` under P = D(theta) P0 matches `fixed`.
 
     moving selects the objects of geom.objects that share the pose under optimisation; the others are rendered at their
@@ -1062,9 +1242,18 @@ def register(volume, geom, fixed, moving=(0, 1, 2), theta0=None, P0=None, levels
     a pose from half an image away and needs no landmarks, but it is piecewise constant: no refine, no levels, no mask,
     and no motion below a pixel -- a start and a coarse stage for the intensity costs, not a replacement.  The landmark
     term adds to it as to the others.
+
+    similarity='mi'  is the negative mutual information between the intensities of the DRR and of
+    `fixed` (MISimilarity): it needs no known intensity mapping of the fixed image -- any monotone or even non-monotone
+    look-up table gives the same cost up to binning -- and no edges.  mi_bins is the number of bins, an integer or (Bf, Bm),
+    2..64.  mi_range=(lo, hi) is the range of the moving intensities the Bm bins span; None takes (0, 1.25 x the largest
+    value of the view rendered at the start), per level: one more render, counted in Registration.renders, and a start with
+    nothing in view is refused.  mask, levels, landmarks and refine=K work with it; patch_weight, segmentation and outline_sets
+    do not belong to it.
     """
     patch, landmark_weight = _cost_options(refine, refine_tol, similarity, patch_radius, patch_stride, patch_min_count, landmark_weight,
                                            patch_weight)
+    mi_bins, mi_range = _mi_options(similarity, mi_bins, mi_range, segmentation, outline_sets)
     outline = similarity == 'outline'
     if outline:
         outline_cap = _outline_options(geom, segmentation, levels, mask, outline_cap)
@@ -1101,7 +1290,10 @@ def register(volume, geom, fixed, moving=(0, 1, 2), theta0=None, P0=None, levels
     mean, sigma, trace, renders, done = theta0, float(sigma0), [], 0, []
     for k, (factor, gens, grid, img) in enumerate(plan):
         level = _OutlineLevel(volume, grid, segmentation, _outline_sets(geom, moving, outline_sets), outline_cap, lam, step_mm) if outline \
+            else _MILevel(volume, grid, img, mask, lam, step_mm, mi_bins) if mi_bins is not None \
             else _Level(volume, grid, img, mask, lam, step_mm, patch)
+        if mi_bins is not None:
+            renders += level.start_range([prob], [mean], mi_range)
         res = _search(level, [prob], [mean], sigma, lam, gens, seed + k)[0]
         mean, sigma = res.mean, sigma * float(sigma_shrink)
         trace.extend(res.trace.tolist())
@@ -1122,7 +1314,7 @@ def default_max_views(H, W):
 def register_many(volume, geoms, fixed, moving=(0, 1, 2), theta0=None, P0=None, popsize=16, generations=80, sigma0=2.0, step_mm=1.0,
                   masks=None, seed=0, centre=None, rot_unit=ROT_UNIT, similarity='global', patch_radius=7, patch_stride=4,
                   patch_min_count=None, landmarks=None, landmark_weight=0.0, refine=0, refine_tol=1e-4, max_views=None,
-                  patch_weight='uniform', **unknown):
+                  patch_weight='uniform', mi_bins=32, mi_range=None, **unknown):
     """register() for N projections of one volume at once: [Registration] * N.
 
     geoms is a list of N drr.Geometry that share the output grid, K, I2P and the object masks (each has its own object
@@ -1138,7 +1330,8 @@ def register_many(volume, geoms, fixed, moving=(0, 1, 2), theta0=None, P0=None, 
     dfl_sim_patch_eval) and one dfl_drr_pose_grad.  The float64
     host work is done problem by problem with the functions register() uses.  max_views caps the views of one render
     (default: default_max_views); problems are processed in chunks of max_views // popsize, which changes no result.
-    There is no coarse-to-fine here (no levels)."""
+    There is no coarse-to-fine here (no levels).  similarity='mi' works as in register(): with mi_range=None the start views of a
+    chunk of problems are one render and their ranges one [F, 2] tensor on the device."""
     if unknown:
         raise nat.DflError('register_many: no argument %s (levels: there is no coarse-to-fine here; register() has it)'
                            % ', '.join(sorted(unknown)))
@@ -1147,6 +1340,7 @@ def register_many(volume, geoms, fixed, moving=(0, 1, 2), theta0=None, P0=None, 
                            "(dfl_sim_outline takes fixed_of, but the driver for a bank of segmentations is not written)")
     patch, landmark_weight = _cost_options(refine, refine_tol, similarity, patch_radius, patch_stride, patch_min_count, landmark_weight,
                                            patch_weight)
+    mi = _mi_options(similarity, mi_bins, mi_range, None, None)
     try:
         geoms = list(geoms)
     except TypeError:
@@ -1195,13 +1389,19 @@ def register_many(volume, geoms, fixed, moving=(0, 1, 2), theta0=None, P0=None, 
     for lo in range(0, N, per):
         hi = min(N, lo + per)
         out.extend(_register_chunk(volume, g0.grid, probs[lo:hi], starts[lo:hi], fixed[lo:hi], None if masks is None else masks[lo:hi],
-                                   lam, int(generations), float(sigma0), step_mm, seed, patch, int(refine), float(refine_tol)))
+                                   lam, int(generations), float(sigma0), step_mm, seed, patch, int(refine), float(refine_tol), mi))
     return out
 
 
-def _register_chunk(volume, grid, probs, starts, fixed, masks, lam, generations, sigma0, step_mm, seed, patch, refine, refine_tol):
+def _register_chunk(volume, grid, probs, starts, fixed, masks, lam, generations, sigma0, step_mm, seed, patch, refine, refine_tol,
+                    mi=(None, None)):
     """register_many for problems whose lambda candidates fit into one render together."""
-    level = _Level(volume, grid, None, None, len(probs) * lam, step_mm, patch, bank=(fixed, masks))
+    first = 0
+    if mi[0] is not None:
+        level = _MILevel(volume, grid, None, None, len(probs) * lam, step_mm, mi[0], bank=(fixed, masks))
+        first = level.start_range(probs, starts, mi[1])
+    else:
+        level = _Level(volume, grid, None, None, len(probs) * lam, step_mm, patch, bank=(fixed, masks))
     cma = _search(level, probs, starts, sigma0, lam, generations, seed)
-    return _close(level, probs, [r.mean for r in cma], refine, refine_tol, [r.trace.tolist() for r in cma], [r.evaluations for r in cma],
+    return _close(level, probs, [r.mean for r in cma], refine, refine_tol, [r.trace.tolist() for r in cma], [first + r.evaluations for r in cma],
                   [(None, generations, grid.H, grid.W)])

@@ -10,6 +10,7 @@ same --crop and --ds-factor.
     python examples/register_2d3d.py full_res.h5 17-1882 0 --lands-csv lands.csv --similarity patch --landmark-weight 0.01
     python examples/register_2d3d.py full_res.h5 17-1882 0 --offset 2,-1.5,2.5,4,-3,15 --generations 25 --refine 30
     python examples/register_2d3d.py full_res.h5 17-1882 0 --gt-lands --similarity patch --patch-weight variance --refine 20
+    python examples/register_2d3d.py full_res.h5 17-1882 0 --gt-lands --mi-bins 16 --refine 10
 
 The start pose comes from exactly one of
   --lands-csv FILE   2D landmarks as est_lands_csv.py writes them (pat,proj,land,row,col,time on this grid; land indexes
@@ -25,6 +26,9 @@ landmarks and the 2D landmarks that gave the start to the pelvis cost; it needs 
 renderer (dfl_drr_pose_grad, dfl_sim_gradncc_bwd; the global similarity, or the patch one with --patch-weight variance) and
 prints the cost before and after them.  --patch-weight variance (with --similarity patch; default uniform) weighs every
 patch by the energy of the projection's gradient in it, so that flat background patches hardly count (dfl_sim_patch_eval).
+--mi-bins N (2..64) replaces the gradient-NCC by the negative mutual information of the intensities over N x N bins
+(dfl_sim_mi, register(similarity='mi'): no known intensity mapping of the projection is needed, and strong edges the CT
+does not hold count as a few pixels); --refine works with it (dfl_sim_mi_bwd); not with --similarity patch or --patch-weight variance.
 With a landmark start all bones begin at the pelvis pose (the anatomy as it was scanned).  The pelvis is registered with
 every bone following it; --femurs then registers each femur on its own with the others held.
 PREFIX_reg.npz holds start_poses and poses ([3, 4, 4] cam-to-{pelvis, left-femur, right-femur}-vol), cost (the best cost
@@ -49,7 +53,7 @@ from full_res_drr import parse_options, to_u8  # noqa: E402
 
 USAGE = ('Usage: {} <HDF5 full-res data file> <specimen ID> <projection index> (--lands-csv FILE | --gt-lands | --offset '
          'rx,ry,rz,tx,ty,tz) [--femurs] [--out PREFIX] [--crop 50] [--ds-factor 8] [--popsize 16] [--generations 80] [--sigma 2.0] '
-         '[--step 1.0] [--patch-weight uniform|variance] [--refine 0] [--seed 0] [--similarity global|patch] [--patch-radius 7] [--patch-stride 4] [--landmark-weight 0]')
+         '[--step 1.0] [--mi-bins N] [--patch-weight uniform|variance] [--refine 0] [--seed 0] [--similarity global|patch] [--patch-radius 7] [--patch-stride 4] [--landmark-weight 0]')
 
 
 def _six(text):
@@ -112,6 +116,32 @@ def parse_patch_weight(argv):
     return rest, weight
 
 
+def parse_mi_bins(argv):
+    """(the command line without --mi-bins N, N), N = None when it was not given; None when it has no value or one outside 2..64."""
+    rest, bins = [], None
+    it = iter(argv)
+    for a in it:
+        if a != '--mi-bins':
+            rest.append(a)
+            continue
+        try:
+            bins = int(next(it))
+        except (StopIteration, ValueError):
+            return None
+        if not 2 <= bins <= 64:
+            return None
+    return rest, bins
+
+
+def cost_keywords(similarity, patch_weight, mi_bins):
+    """The keywords of register() and register_many() that select the cost, or None for --mi-bins together with patches."""
+    if mi_bins is None:
+        return dict(similarity=similarity, patch_weight=patch_weight)
+    if similarity == 'patch' or patch_weight != 'uniform':
+        return None
+    return dict(similarity='mi', mi_bins=mi_bins)
+
+
 def parse_refine(argv):
     """(the command line without --refine K, K), K = 0 when it was not given; None when it has no or a bad value."""
     rest, refine = [], 0
@@ -170,13 +200,15 @@ def pose_errors(P, P_gt, centre):
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
-    weighted = parse_patch_weight(argv)
+    binned = parse_mi_bins(argv)
+    weighted = None if binned is None else parse_patch_weight(binned[0])
     fine = None if weighted is None else parse_refine(weighted[0])
     cost = None if fine is None else parse_similarity(fine[0])
     parsed = None if cost is None else parse(cost[0])
     if parsed is None or (cost[1]['--landmark-weight'] is not None and parsed[1]['--offset'] is not None) or \
             (fine[1] > 0 and cost[1]['--similarity'] == 'patch' and weighted[1] == 'uniform') or \
-            (weighted[1] != 'uniform' and cost[1]['--similarity'] != 'patch'):
+            (weighted[1] != 'uniform' and cost[1]['--similarity'] != 'patch') or \
+            cost_keywords(cost[1]['--similarity'], weighted[1], binned[1]) is None:
         print(USAGE.format(os.path.basename(sys.argv[0])))
         return 1
     (path, spec, idx), o = parsed
@@ -205,8 +237,8 @@ def main(argv=None):
         centre = reg.volume_centre(vol.shape, geom.I2P)
         back, Ei = np.linalg.inv(geom.I2P), np.linalg.inv(geom.E)
         kw = dict(popsize=o['--popsize'], generations=o['--generations'], sigma0=o['--sigma'], step_mm=o['--step'], seed=o['--seed'],
-                  similarity=so['--similarity'], patch_radius=so['--patch-radius'], patch_stride=so['--patch-stride'], refine=fine[1],
-                  patch_weight=weighted[1])
+                  patch_radius=so['--patch-radius'], patch_stride=so['--patch-stride'], refine=fine[1],
+                  **cost_keywords(so['--similarity'], weighted[1], binned[1]))
 
         def refined(what, r):
             if len(r.refine_cost):

@@ -7,6 +7,7 @@ dfl_sim_bank_gradncc launch).
     python examples/register_specimen.py full_res.h5 17-1882 --lands-csv lands.csv
     python examples/register_specimen.py full_res.h5 17-1882 --gt-lands --projs 0,3,7 --refine 20 --out run1
     python examples/register_specimen.py full_res.h5 17-1882 --gt-lands --similarity patch --patch-weight variance --refine 20
+    python examples/register_specimen.py full_res.h5 17-1882 --gt-lands --mi-bins 16
 
 Every selected projection (--projs, default: all of the specimen) gets its geometry, its preprocessed fixed image and its
 start pose from landmarks (register.pnp) exactly as register_2d3d.py gives them to one projection: --lands-csv FILE reads
@@ -14,6 +15,7 @@ the 2D landmarks est_lands_csv.py writes, --gt-lands takes the projection's gt-l
 pose and follow it.  Projections whose detector image is turned (rot-180-for-up) have another pixel grid than the others,
 so the two kinds go into one register_many call each.  The result of a projection has the bytes register_2d3d.py finds
 for it alone with the same options.
+--mi-bins N selects the mutual-information cost, as in register_2d3d.py (not with --similarity patch or --patch-weight variance).
 A projection without enough usable landmarks for pnp is left out of the batch and written with empty fields; the exit
 status is 1 only when no projection could be registered or the command line is not understood.
 PREFIX_reg.csv: proj, start_rot_deg, start_trans_mm, rot_deg, trans_mm (register_2d3d.pose_errors against gt-poses; empty
@@ -31,10 +33,10 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dfl_amd  # noqa: E402,F401
 from dfl_amd import _native as nat, drr, fullres, preprocess, register as reg  # noqa: E402
-from register_2d3d import _WithPoses, parse_patch_weight, parse_refine, parse_similarity, pose_errors, read_lands_csv  # noqa: E402
+from register_2d3d import _WithPoses, cost_keywords, parse_mi_bins, parse_patch_weight, parse_refine, parse_similarity, pose_errors, read_lands_csv  # noqa: E402
 
 USAGE = ('Usage: {} <HDF5 full-res data file> <specimen ID> (--lands-csv FILE | --gt-lands) [--projs 0,3,7] [--out PREFIX] [--crop 50] '
-         '[--ds-factor 8] [--popsize 16] [--generations 80] [--patch-weight uniform|variance] [--seed 0] [--similarity global|patch] [--patch-radius 7] [--patch-stride 4] '
+         '[--ds-factor 8] [--popsize 16] [--generations 80] [--mi-bins N] [--patch-weight uniform|variance] [--seed 0] [--similarity global|patch] [--patch-radius 7] [--patch-stride 4] '
          '[--landmark-weight 0] [--refine 0] [--max-views N]')
 
 
@@ -82,9 +84,10 @@ def parse(argv, patch_weight='uniform'):
 
 
 def main(argv=None):
-    weighted = parse_patch_weight(sys.argv[1:] if argv is None else argv)
+    binned = parse_mi_bins(sys.argv[1:] if argv is None else argv)
+    weighted = None if binned is None else parse_patch_weight(binned[0])
     parsed = None if weighted is None else parse(*weighted)
-    if parsed is None:
+    if parsed is None or cost_keywords(parsed[1]['--similarity'], weighted[1], binned[1]) is None:
         print(USAGE.format(os.path.basename(sys.argv[0])))
         return 1
     (path, spec), o = parsed
@@ -139,10 +142,10 @@ def main(argv=None):
                 continue
             res = reg.register_many(vol, [jobs[i]['geom'] for i in group], torch.stack([jobs[i]['fixed'] for i in group]), moving=(0, 1, 2),
                                     P0=np.stack([jobs[i]['P0'] for i in group]), popsize=o['--popsize'], generations=o['--generations'],
-                                    seed=o['--seed'], similarity=o['--similarity'], patch_radius=o['--patch-radius'],
+                                    seed=o['--seed'], patch_radius=o['--patch-radius'],
                                     patch_stride=o['--patch-stride'], landmarks=[jobs[i]['lands'] for i in group],
                                     landmark_weight=o['--landmark-weight'] or 0.0, refine=o['--refine'], max_views=o['--max-views'],
-                                    patch_weight=weighted[1])
+                                    **cost_keywords(o['--similarity'], weighted[1], binned[1]))
             for i, r in zip(group, res):
                 rows[i] = r
         prefix = o['--out'] or '{}_all'.format(spec)

@@ -1616,6 +1616,90 @@ int dfl_sim_outline(const dfl_sim_outline_args* a, dfl_stream_t stream);
 int dfl_sim_outline_scratch_doubles(int32_t V, int32_t S, int32_t H, int32_t W);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Mutual information (csrc/sim_mi.hip; tests/mi_ref.py restates this section in numpy): the
+ * negative mutual information between the intensities of V rendered views and of the fixed images they are scored
+ * against, from a joint histogram of integers -- the similarity of register(similarity='mi').  It needs neither a known
+ * intensity mapping of the fixed image nor edges.  Every float32 step below is rounded on its own (csrc/build.sh compiles
+ * the file with -ffp-contract=off); divisions are correctly rounded.
+ *
+ * dfl_sim_mi_prepare, once per fixed image (a bank: once per image on its slices of fbin [F][H][W] and info [F][4]).
+ *   A pixel is counted when its fixed value is finite and mask is NULL or its mask byte is non-zero: all pixels are
+ *   candidates, the border included.  lo_f, hi_f = the smallest and largest counted value, n = how many are counted;
+ *   s_f = (float) Bf / (hi_f - lo_f);  fbin = clip((int) floorf((f - lo_f) s_f), 0, Bf - 1) for a counted pixel (0 when
+ *   hi_f == lo_f, and where the product is NaN), DFL_SIM_MI_SKIP for one that is not counted.
+ *   info[DFL_SIM_MI_INFO] = n, lo_f, hi_f, 0 (0, 0, 0, 0 when nothing is counted).  Two launches.
+ *
+ * dfl_sim_mi, once per batch.  View v is scored against image f = fixed_of[v] (device, [V]), or image 0 when fixed_of is
+ * NULL.  mrange [F][2] (device, float32) holds the moving range (lo, hi) of every image, s = (float)(Bm - 1) / (hi - lo).
+ * For a counted pixel with moving value m:
+ *   x = (fminf(fmaxf(m, lo), hi) - lo) s      values outside the range clamp, NaN counts as lo
+ *   a = x >= Bm - 1 ? Bm - 2 : (int) floorf(x)
+ *   q = (int) floorf((x - (float) a) 4096.0f + 0.5f)
+ *   hist[v][a][fbin] += DFL_SIM_MI_UNIT - q,  hist[v][a + 1][fbin] += q
+ * a first-order Parzen window on the moving intensity in units of 1 / DFL_SIM_MI_UNIT pixel.  hist [V][Bm][Bf] is an
+ * output and is overwritten; a view's entries sum to exactly DFL_SIM_MI_UNIT n.  With N = DFL_SIM_MI_UNIT n,
+ * h_a = sum_b hist[a][b] and h_b = sum_a hist[a][b] (integers):
+ *   MI = sum over hist[a][b] > 0 of (h / N) log((h N) / (h_a h_b))  in float64,  cost[v] = -MI,  0 when n == 0.
+ * A view is void when lo, hi, hi - lo or s is not finite, when hi > lo does not hold, or when its fixed_of entry is
+ * outside [0, F): cost NaN, hist 0, and in the adjoint ell 0 and d_moving 0; the other views are not affected (device
+ * values cannot be refused on the host).
+ *
+ * dfl_sim_mi_bwd writes cost and hist with the bits of dfl_sim_mi (the same kernels), the table
+ *   ell[v][a][b] = log(max(hist[a][b], 1)) - log(max(h_a, 1))  (float64, [V][Bm][Bf]), and
+ *   d_moving[v][r][c] = (float)(-((double) s / n) (ell[a + 1][fbin] - ell[a][fbin]))  at a counted pixel with lo < m < hi,
+ * exactly 0 at every other pixel (not counted, at or beyond the range, NaN).  This is the derivative of the unquantised
+ * cost at a fixed range: the "+ 1" terms and log N cancel because the weights of a pixel sum to a constant, and h_b does
+ * not move.  At the ends of the range the clamp makes the cost one-sided, hence the exact zeros there.
+ *
+ * Kernels: mi_clear zeroes hist; mi_hist_kernel: a workgroup takes DFL_SIM_MI_RUN consecutive pixels of one view, every
+ * wave adds into its own uint32 histogram in LDS (integer LDS adds), and the workgroup adds its non-zero bins to hist
+ * with 64-bit integer global atomic adds.  Integer sums: no decomposition, batch or arrival order changes a bit; there
+ * are no float atomics.  mi_finish_kernel: one workgroup per view, marginals as integers, the float64 sum in an order
+ * that depends on Bf and Bm only.  mi_adjoint_kernel stages the view's table in LDS.
+ * Refused with nothing launched and the outputs untouched: NULL pointers (mask and fixed_of may be NULL), H < 1, W < 1,
+ * H W >= 2^31, F < 1, F > 65535, F H W >= 2^31, V < 1, V > 65535, Bf or Bm outside 2..DFL_SIM_MI_MAX_BINS.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define DFL_SIM_MI_UNIT 4096
+#define DFL_SIM_MI_MAX_BINS 64
+#define DFL_SIM_MI_SKIP 255
+#define DFL_SIM_MI_INFO 4
+#define DFL_SIM_MI_RUN 8192
+typedef struct {
+  const float* fixed;             /* [H][W] */
+  const unsigned char* mask;      /* [H][W], or NULL */
+  unsigned char* fbin;            /* [H][W] */
+  double* info;                   /* [DFL_SIM_MI_INFO] */
+  int32_t H, W, Bf, reserved;
+} dfl_sim_mi_prepare_args;
+int dfl_sim_mi_prepare(const dfl_sim_mi_prepare_args* a, dfl_stream_t stream);
+
+typedef struct {
+  const float* moving;            /* [V][H][W] */
+  const unsigned char* fbin;      /* [F][H][W], of dfl_sim_mi_prepare with the same Bf */
+  const double* info;             /* [F][DFL_SIM_MI_INFO] */
+  const float* mrange;            /* [F][2], device: lo, hi of the moving intensities */
+  const int32_t* fixed_of;        /* [V], device, or NULL: every view against image 0 */
+  uint64_t* hist;                 /* [V][Bm][Bf] */
+  double* cost;                   /* [V] */
+  int32_t V, H, W, F, Bf, Bm;
+} dfl_sim_mi_args;
+int dfl_sim_mi(const dfl_sim_mi_args* a, dfl_stream_t stream);
+
+typedef struct {
+  const float* moving;            /* [V][H][W] */
+  const unsigned char* fbin;      /* [F][H][W] */
+  const double* info;             /* [F][DFL_SIM_MI_INFO] */
+  const float* mrange;            /* [F][2], device */
+  const int32_t* fixed_of;        /* [V], device, or NULL */
+  uint64_t* hist;                 /* [V][Bm][Bf] */
+  double* cost;                   /* [V] */
+  double* ell;                    /* [V][Bm][Bf] */
+  float* d_moving;                /* [V][H][W] */
+  int32_t V, H, W, F, Bf, Bm;
+} dfl_sim_mi_bwd_args;
+int dfl_sim_mi_bwd(const dfl_sim_mi_bwd_args* a, dfl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Detector model: rendered line integrals -> detector intensities (csrc/expose.hip; DESIGN.md section 17 states the
  * semantics, tests/expose_ref.py restates them in numpy).  Per view v and pixel i = r C + c, all in fp32:
  *   T = expf(-att);  B = the separable blur of T with taps[0 .. 2 rho] (rows first, then columns, indices clamped to
