@@ -22,6 +22,8 @@ from . import register
 from . import labels
 from . import boundary
 from .boundary import DiceBoundaryLoss2D, DiceHeatMapBoundaryLoss2D
+from . import ce
+from .ce import DiceCELoss2D, DiceHeatMapCELoss2D, balanced_class_weights, cross_entropy_term
 from . import tools
 from . import synth
 from .synth import synthesize
@@ -29,4 +31,5 @@ from .synth import synthesize
 __all__ = ['UNet', 'DiceLoss2D', 'DiceAndHeatMapLoss2D', 'ncc_2d', 'center_crop', 'get_device', 'WarmRestartLR', 'SGD',
            'Adam', 'RMSprop', 'DataParallel', 'parallel', 'DeviceAugment', 'preprocess', 'out_size', 'map_lands', 'unmap_lands',
            'preprocess_projs', 'preprocess_segs', 'restore_labels', 'convert_file', 'drr', 'hu_to_mu', 'register', 'labels', 'tools', 'synth',
-           'synthesize', 'boundary', 'DiceBoundaryLoss2D', 'DiceHeatMapBoundaryLoss2D']
+           'synthesize', 'boundary', 'DiceBoundaryLoss2D', 'DiceHeatMapBoundaryLoss2D', 'ce',
+           'DiceCELoss2D', 'DiceHeatMapCELoss2D', 'balanced_class_weights', 'cross_entropy_term']

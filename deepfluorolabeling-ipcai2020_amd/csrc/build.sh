@@ -4,7 +4,7 @@ set -euo pipefail
 here="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 out="$here/../lib"
 mkdir -p "$out"
-srcs=(api.hip conv_gemm.hip conv_plan.hip conv_rows.hip convp_bf16.hip convq_bf16.hip convn_bf16.hip convs.hip wgradp_bf16.hip wgrad_gemm.hip direct_small.hip bn_elem.hip head.hip loss.hip prep.hip augment.hip upsample.hip overlay.hip overlay_fullres.hip mesh.hip decimate.hip preproc.hip drr.hip drr_grad.hip sim.hip sim_patch.hip sim_outline.hip sim_mi.hip expose.hip drr_tools.hip raster.hip labels.hip labels_dist.hip boundary.hip)
+srcs=(api.hip conv_gemm.hip conv_plan.hip conv_rows.hip convp_bf16.hip convq_bf16.hip convn_bf16.hip convs.hip wgradp_bf16.hip wgrad_gemm.hip direct_small.hip bn_elem.hip head.hip loss.hip prep.hip augment.hip upsample.hip overlay.hip overlay_fullres.hip mesh.hip decimate.hip preproc.hip drr.hip drr_grad.hip sim.hip sim_patch.hip sim_outline.hip sim_mi.hip expose.hip drr_tools.hip raster.hip labels.hip labels_dist.hip boundary.hip ce_loss.hip)
 objs=()
 pids=()
 # one hipcc per source, at most $MAX_JOBS (default 16) at a time

@@ -1857,6 +1857,64 @@ int dfl_boundary_loss_scratch_doubles(int32_t B, int32_t C, int32_t h);
 int dfl_boundary_loss(const dfl_boundary_loss_args* a, dfl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Cross-entropy and focal term (csrc/ce_loss.hip; tests/ce_ref.py restates this text in numpy): the
+ * per-pixel likelihood term on the soft-max PROBABILITIES the head writes, fused with the value and the gradient of
+ * dfl_dice_ncc_loss (and of dfl_boundary_loss).  There is no logits form: dfl_head_fwd fuses the soft-max and Dice needs
+ * the probabilities.
+ *
+ * seg [B, C, h, w] fp32 probabilities and tseg, the target of the same shape (one-hot in training; any finite values >= 0),
+ * each through element strides (sN, sC, sH; unit stride along w).  class_wgt[c] >= 0 (entries >= C are not read), gamma the
+ * focusing exponent.  EPS = 2^-100 (0x1p-100f), s' = min(max(s, EPS), 1):
+ *   f(s, t, w) = -w t (1 - s')^gamma log s'                          with 0^0 = 1
+ *   L_CE       = (1 / N) sum over b, c, p of f(seg, tseg, class_wgt[c]),   N = B h w  (pixels, not elements)
+ *   d(lambda L_CE) / d seg[b][c][p] = -(lambda / N) w_c t [ (1 - s')^gamma / s' - gamma (1 - s')^(gamma-1) log s' ]
+ * Every channel counts, background included (the skip_bg of Dice is not read here; class_wgt[0] = 0 leaves it out).
+ * gamma = 0 is plain cross-entropy and runs without powf; otherwise 1 <= gamma <= 8 (between 0 and 1 the derivative is
+ * unbounded at s = 1: refused).
+ * Below EPS the gradient is STILL the formula above at s' -- not the zero that the clamped value's true derivative would
+ * give: a confidently wrong pixel keeps its gradient.  1 / EPS times lambda / N is finite in fp32, and dfl_head_bwd
+ * multiplies by s, so the products it forms are O(1).
+ * An element with w_c t == 0 contributes exactly +0 and evaluates no logarithm; stage 2 writes it as 0.0f, and with
+ * accumulate_grad leaves it as it is (the augmentation's "outside the frame: all masks 0" pixels add nothing).
+ * Element terms are fp32 with the accurate logf / powf (no fast intrinsics).
+ *
+ * dfl_ce_loss, stage 1: the sum in float64 in a fixed order (csrc/fixed_sum.h: wave shuffle, four waves through LDS, one
+ * record per workgroup in sums, the records in index order; no float atomics; the pixel-to-thread assignment is fixed by
+ * the shape, so two runs give the same bits).  Then one thread: *loss = (float)(lambda L_CE), or with accumulate_loss
+ * *loss = (float)((double) *loss + lambda L_CE) -- onto what dfl_dice_ncc_loss and optionally dfl_boundary_loss stage 1 left
+ * there, one rounding.  sums holds dfl_ce_loss_scratch_doubles(B, C, h) doubles (an int, at most 1024; 0 on sizes < 1).
+ * Stage 2: dseg[b][c][p] = the derivative above with lambda / N replaced by k = *grad_scale * (float)(lambda / N)
+ * (grad_scale: a DEVICE scalar, NULL = 1), through element strides (all 0 = dense [B][C][h][w]); with accumulate_grad it
+ * is added onto what is there -- what dfl_dice_ncc_loss / dfl_boundary_loss stage 2 wrote, launched before on the same
+ * stream.
+ * Both stages stream rows: 256 threads, a wave per row of an (image, class), at most 1024 workgroups, rows grid-strided;
+ * 16-byte accesses of seg / tseg / dseg on the rows whose address allows it (a centre-crop window starts at any column),
+ * 4-byte ones otherwise and for the head and tail of a row; 64-bit offsets.
+ * Refused before any pointer is followed: a NULL block; B, h or w < 1; C outside 2..DFL_LABEL_MAX_CLASSES; a stage other
+ * than 1 or 2; a lambda or gamma that is not finite; a gamma outside {0} and [1, 8]; a class weight (of the first C) that is
+ * negative or not finite; NULL seg / tseg / loss / sums in stage 1, NULL seg / tseg / dseg in stage 2; gradient strides
+ * of which some but not all are 0.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct {
+  const float* seg;               /* [B, C, h, w] through seg_s* */
+  const float* tseg;              /* [B, C, h, w] through tseg_s* */
+  float* loss;                    /* 1 float; stage 1 */
+  double* sums;                   /* dfl_ce_loss_scratch_doubles(B, C, h) doubles; stage 1 */
+  const float* grad_scale;        /* device scalar or NULL (= 1); stage 2 */
+  float* dseg;                    /* [B, C, h, w] through dseg_s* (all 0: dense); stage 2 */
+  int64_t seg_sN, seg_sC, seg_sH;
+  int64_t tseg_sN, tseg_sC, tseg_sH;
+  int64_t dseg_sN, dseg_sC, dseg_sH;
+  int32_t B, C, h, w;
+  int32_t stage;                  /* 1: value, 2: gradient */
+  int32_t accumulate_loss, accumulate_grad;
+  float lambda, gamma;
+  float class_wgt[32];            /* entries >= C are not read */
+} dfl_ce_loss_args;
+int dfl_ce_loss_scratch_doubles(int32_t B, int32_t C, int32_t h);
+int dfl_ce_loss(const dfl_ce_loss_args* a, dfl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Product arithmetic of the convolution / weight-gradient GEMMs (fast paths; odd channel counts always use fp32):
  *   0 "fp32"    v_mfma_f32_32x32x2_f32: fp32 products, fp32 accumulation.
  *   1 "bf16x3"  every fp32 operand value is split into hi + lo bf16 parts when it is staged in LDS and the product is

@@ -20,9 +20,9 @@ batch is --batch-size x world size.
         --nesterov --wgt-decay 1e-4
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 train.py data.h5 ...
 
-Extensions (not in the reference): --math, --seed, --dist-backend, and --boundary-coeff / --boundary-ramp (the boundary-
-distance term of dfl_amd.boundary in the training loss; validation stays on Dice and heat maps).  Refused loudly: --no-gpu
-(there is no CPU path).
+Extensions (not in the reference): --math, --seed, --dist-backend, --boundary-coeff / --boundary-ramp (the boundary-
+distance term of dfl_amd.boundary in the training loss) and --ce-coeff / --focal-gamma / --class-weights (the cross-entropy
+or focal term of dfl_amd.ce); validation stays on Dice and heat maps.  Refused loudly: --no-gpu (there is no CPU path).
 --data-aug runs the reference's augmentation recipe on the device (dfl_amd.DeviceAugment), its
 draws seeded from --seed (or a fresh system seed, broadcast to every rank).  The data file is the
 reference's HDF5 layout (read by the dependency-free dfl_amd.h5lite) or an .npz with the same dataset names.
@@ -107,7 +107,7 @@ def build_parser():
 
 
 EXTENSION_FLAGS = {'math': None, 'seed': None, 'dist_backend': None, 'sync_loss': False, 'grad_compress': None,
-                   'boundary_coeff': None, 'boundary_ramp': 0}
+                   'boundary_coeff': None, 'boundary_ramp': 0, 'ce_coeff': None, 'focal_gamma': 0.0, 'class_weights': None}
 
 
 def _ramp_epochs(text):
@@ -115,6 +115,26 @@ def _ramp_epochs(text):
     if value < 0:
         raise argparse.ArgumentTypeError('--boundary-ramp takes a number of epochs >= 0, not {}'.format(text))
     return value
+
+
+def _focal_gamma(text):
+    value = float(text)
+    if not (value == 0.0 or 1.0 <= value <= 8.0):        # (a NaN fails both)
+        raise argparse.ArgumentTypeError('--focal-gamma takes 0 (cross-entropy) or a number in 1..8, not {}'.format(text))
+    return value
+
+
+def _class_weights(text):
+    """'balanced', or comma-separated weights >= 0 -> a tuple of floats."""
+    if text.strip() == 'balanced':
+        return 'balanced'
+    try:
+        values = tuple(float(t) for t in text.split(','))
+    except ValueError:
+        raise argparse.ArgumentTypeError("--class-weights takes 'balanced' or comma-separated numbers, not {}".format(text))
+    if not all(0.0 <= v < float('inf') for v in values):
+        raise argparse.ArgumentTypeError('--class-weights takes finite weights >= 0, not {}'.format(text))
+    return values
 
 
 def build_full_parser():
@@ -135,7 +155,32 @@ def build_full_parser():
     p.add_argument('--boundary-ramp', type=_ramp_epochs, default=0,
                    help='with --boundary-coeff B: train epoch e with B * min(1, (e + 1) / E) for this E > 0 (default 0: B from '
                         'the first epoch); e counts from the checkpoint when resuming')
+    p.add_argument('--ce-coeff', type=float, default=None, nargs='?', const=1.0,
+                   help='add this weight times the cross-entropy term (the focal term with --focal-gamma) of the soft-max '
+                        'probabilities to the training loss; 1.0 when given without a value.  Not stored in checkpoints: give '
+                        'it again when resuming')
+    p.add_argument('--focal-gamma', type=_focal_gamma, default=0.0,
+                   help='with --ce-coeff: the focusing exponent of the focal loss, 0 (plain cross-entropy) or 1..8.  Not stored '
+                        'in checkpoints: give it again when resuming')
+    p.add_argument('--class-weights', type=_class_weights, default=None,
+                   help="with --ce-coeff: --num-classes comma-separated weights >= 0 of the term's classes, or 'balanced' "
+                        '(total / (classes * pixels of the class), counted over the training set).  Not stored in checkpoints: '
+                        'give it again when resuming')
     return p
+
+
+def parse_args(argv=None):
+    """The full parser's result, with the combinations of extension flags that make no sense refused by the parser's own
+    error, before any data is read."""
+    p = build_full_parser()
+    a = p.parse_args(argv)
+    if a.ce_coeff is None and (a.focal_gamma != 0.0 or a.class_weights is not None):
+        p.error('--focal-gamma and --class-weights belong to the cross-entropy term: give --ce-coeff')
+    if a.ce_coeff is not None and not abs(a.ce_coeff) < float('inf'):
+        p.error('--ce-coeff takes a finite number')
+    if isinstance(a.class_weights, tuple) and a.num_classes is not None and len(a.class_weights) != a.num_classes:
+        p.error('--class-weights: {} weights for --num-classes {}'.format(len(a.class_weights), a.num_classes))
+    return a
 
 
 def boundary_weight(coeff, ramp, epoch):
@@ -325,7 +370,9 @@ class Trainer:
         self.net.to(self.dev)
         self.dp = dfl_amd.DataParallel(self.net, compress=self.args.grad_compress) if self.world > 1 else None   # broadcasts rank 0's weights
         coeff = self.args.boundary_coeff
-        if coeff is not None:                            # a property of the command line, like --math: not in checkpoints
+        if self.args.ce_coeff is not None:               # (both: properties of the command line, like --math: not in checkpoints)
+            self._build_ce_criterion()
+        elif coeff is not None:
             ramp = self.args.boundary_ramp
             if c['num-lands'] > 0:
                 self.say('loss: Dice + heat-map NCC (weight {}) + boundary distance (weight {}, ramp {})'.format(
@@ -340,6 +387,46 @@ class Trainer:
         else:
             self.say('loss: Dice')
             self.criterion = dfl_amd.DiceLoss2D(skip_bg=False)
+
+    def _build_ce_criterion(self):
+        """--ce-coeff: Dice [+ heat-map NCC] [+ boundary distance] + cross-entropy, one node (dfl_amd.ce)."""
+        a, c = self.args, self.cfg
+        weights, how = a.class_weights, 'none' if a.class_weights is None else 'given'
+        if weights == 'balanced':
+            weights, how = self._balanced_class_weights(), 'balanced'
+            self.say('class weights (balanced): {}'.format(', '.join('{:.6g}'.format(v) for v in weights)))
+        elif weights is not None and len(weights) != c['num-classes']:
+            raise ValueError('--class-weights: {} weights for {} classes'.format(len(weights), c['num-classes']))
+        line = 'loss: Dice'
+        if c['num-lands'] > 0:
+            line += ' + heat-map NCC (weight {})'.format(c['heat-coeff'])
+        if a.boundary_coeff is not None:
+            line += ' + boundary distance (weight {}, ramp {})'.format(a.boundary_coeff, a.boundary_ramp)
+        self.say(line + ' + cross-entropy (weight {}, gamma {}, class weights {})'.format(a.ce_coeff, a.focal_gamma, how))
+        kw = dict(skip_bg=False, ce_wgt=a.ce_coeff, gamma=a.focal_gamma, class_weights=weights,
+                  boundary_wgt=a.boundary_coeff if a.boundary_coeff is not None else 0.0)
+        if c['num-lands'] > 0:
+            self.criterion = dfl_amd.DiceHeatMapCELoss2D(heatmap_wgt=c['heat-coeff'], **kw)
+        else:
+            self.criterion = dfl_amd.DiceCELoss2D(**kw)
+
+    def _balanced_class_weights(self):
+        """The label pixels of the whole training set, before augmentation, counted on the device (dfl_hard_dice of the
+        labels against themselves returns the counts exactly); every rank holds the whole set, and rank 0's numbers go to
+        all of them."""
+        C_ = self.cfg['num-classes']
+        segs = self.train_ds.segs
+        counts = torch.zeros(C_, dtype=torch.int64, device=segs.device)
+        for i in range(0, segs.shape[0], 256):
+            part = segs[i:i + 256]
+            counts += util.hard_dice(part, part, C_, return_counts=True)[1][:, :, 1].sum(dim=0)
+        counts = counts.tolist()
+        if self.world > 1:
+            import torch.distributed as dist
+            box = [counts]
+            dist.broadcast_object_list(box, src=0)
+            counts = box[0]
+        return dfl_amd.balanced_class_weights(counts)
 
     def _build_optimizer(self, resume):
         a, c = self.args, self.cfg
@@ -555,7 +642,7 @@ class Trainer:
 
 
 def main(argv=None):
-    Trainer(build_full_parser().parse_args(argv)).run()
+    Trainer(parse_args(argv)).run()
 
 
 if __name__ == '__main__':
